@@ -20,6 +20,9 @@ per recording-band (276,120 windows -> the (1416, 220) feature matrix of v2:404-
 
 `python bench.py --gpus N` with WORLD_SIZE unset starts the N ranks itself (child processes, before this process
 touches a GPU); under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times `--steps` passes, saves the last pass' result rows (`--dump-outputs DIR`) and
+prints the headline; `--full` adds what takes runs of its own: `stage_ms`, the rooflines, the secondary legs
+(`--no-extras` skips them) and `cpu_baseline` (`--no-cpu` skips it).
 `roofline` is for the dominant kernel (audio Rips), its launch duration measured live (kernel-stamped wall clock
 over every launch of the timed region + HIP events on the launch stream in the eager warm-up); `roofline_lds`
 restates the resource that actually binds it from the committed rocprofv3 PMC summary.  `cpu_baseline` times the
@@ -61,8 +64,12 @@ def parse_args():
     ap.add_argument("--features-windows", type=int, default=39, help="v2 min-equalised windows per recording-band")
     ap.add_argument("--features-steps", type=int, default=3, help="passes of the features leg (0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="budget of the cpu_baseline leg (both legs)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the features / PCIe legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: stage_ms (one eager pass), the rooflines (kernel "
+                         "probe), the secondary legs and cpu_baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the features / PCIe / front-end / "
+                                                             "recordings legs")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying HIP graphs")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("TDA_LANES", "3")),
                     help="batches in flight (pipeline.Lanes), each on ONE stream.  One batch per pass: three lanes are "
@@ -77,10 +84,13 @@ def parse_args():
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 and the all-gather goes through gloo "
                          "(exercises the N>1 code path on a one-GPU box; numbers are meaningless)")
-    ap.add_argument("--dump-rows", default=None, help="rank 0 saves the gathered (n_rec, 5 x 48) result rows of the last "
-                                                      "pass to this .npy file (tests compare N ranks with one)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed pass returns, the gathered (n_rec, 5 x 48) float64 result "
+                         "rows, as DIR/rows.npy (tests compare N ranks with one; two builds compare output for output)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)     # internal: the cpu_baseline child process
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
 
 
@@ -194,39 +204,42 @@ def main():
     total_pairs = int(counts.sum()) * nb          # window pairs of one pass of the whole job
     lanes = runner.lanes
 
-    # dominant kernel: rips_cloud_kernel (first pass of stage rips_audio).  The one-shot probe of the C ABI is armed
-    # before every eager launch and before the capture of a band's graph, so that it is baked into the replays: the
-    # kernel accumulates its own duration (first workgroup start .. last workgroup end, 100 MHz wall clock) in a
-    # per-lane device buffer; in the eager warm-up pass HIP events bracket the same launch on its stream.
-    DOM = "rips_audio"
-    spans = torch.zeros((lanes.depth, 4), dtype=torch.int64, device=device)
-    cur_events = [None]
+    # ---- warm-up: (--full: one eager pass with per-stage events, stage_ms and event_ms), then W passes (the first
+    # captures) ----
+    if args.full:
+        # dominant kernel: rips_cloud_kernel (first pass of stage rips_audio).  The one-shot probe of the C ABI is armed
+        # before every eager launch and before the capture of a band's graph, so that it is baked into the replays: the
+        # kernel accumulates its own duration (first workgroup start .. last workgroup end, 100 MHz wall clock) in a
+        # per-lane device buffer; in the eager warm-up pass HIP events bracket the same launch on its stream.  A plain
+        # run does not arm it: the headline does not need it.
+        DOM = "rips_audio"
+        spans = torch.zeros((lanes.depth, 4), dtype=torch.int64, device=device)
+        cur_events = [None]
 
-    def arm(i):
-        ev = cur_events[0]
-        ctx.arm_probe(DOM, ev[0] if ev else None, ev[1] if ev else None, spans[i].data_ptr())
-    lanes.before_step = arm
+        def arm(i):
+            ev = cur_events[0]
+            ctx.arm_probe(DOM, ev[0] if ev else None, ev[1] if ev else None, spans[i].data_ptr())
+        lanes.before_step = arm
 
-    # ---- warm-up: one eager pass with per-stage events (stage_ms, event_ms), then W passes (the first captures) ----
-    ev_log, probes = [], []
-    for b, (eb, ab, _) in enumerate(runner.batches):
-        timers = {s: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                  for s in pipeline.STAGES}
-        cur_events[0] = (ctx.new_event(), ctx.new_event())
-        probes.append(cur_events[0])
-        lanes.submit(eb, ab, ctx=ctx, timers=timers, sync_inputs=False, lane=b)
-        lanes.drain()
-        ev_log.append(timers)
-    cur_events[0] = None
-    torch.cuda.synchronize()
-    def _ms(t, s):
-        try:
-            return t[s][0].elapsed_time(t[s][1])
-        except Exception:                        # stage not on this path (fused / two-kernel EEG chain)
-            return 0.0
-    stage_ms = {s: sum(_ms(t, s) for t in ev_log) for s in pipeline.STAGES}    # per pass, every stage alone on the GPU
-    stage_ms = {s: v for s, v in stage_ms.items() if v > 0.0}
-    event_ms = [ctx.elapsed_ms(a, b) for a, b in probes]
+        ev_log, probes = [], []
+        for b, (eb, ab, _) in enumerate(runner.batches):
+            timers = {s: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                      for s in pipeline.STAGES}
+            cur_events[0] = (ctx.new_event(), ctx.new_event())
+            probes.append(cur_events[0])
+            lanes.submit(eb, ab, ctx=ctx, timers=timers, sync_inputs=False, lane=b)
+            lanes.drain()
+            ev_log.append(timers)
+        cur_events[0] = None
+        torch.cuda.synchronize()
+        def _ms(t, s):
+            try:
+                return t[s][0].elapsed_time(t[s][1])
+            except Exception:                        # stage not on this path (fused / two-kernel EEG chain)
+                return 0.0
+        stage_ms = {s: sum(_ms(t, s) for t in ev_log) for s in pipeline.STAGES}    # per pass, every stage alone on the GPU
+        stage_ms = {s: v for s, v in stage_ms.items() if v > 0.0}
+        event_ms = [ctx.elapsed_ms(a, b) for a, b in probes]
     try:
         runner.prime()                          # every lane captures its graph (set-up, not a warm-up step)
         for _ in range(max(1, args.warmup)):
@@ -251,7 +264,8 @@ def main():
     if bad:
         print(f"bench: {bad} windows reported a non-zero status (overflow beyond the ladder / not converged)", file=sys.stderr)
         return 3
-    sp_before = spans.cpu().numpy().copy()            # accumulators at the start of the timed region
+    if args.full:
+        sp_before = spans.cpu().numpy().copy()        # accumulators at the start of the timed region
     retry_before = retry_ctr.cpu().numpy().copy()
 
     # ---- timed region ----
@@ -274,16 +288,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)          # every rank's own time; the job's time is the slowest rank's
         dt_rank = [float(x) for x in t.tolist()]
         dt = max(dt_rank)
-    if args.dump_rows and rank == 0:
-        np.save(args.dump_rows, rows.cpu().numpy())
-    sp = spans.cpu().numpy()
-    retry_after = retry_ctr.cpu().numpy()
     assert rows.shape == ((n_rec if world > 1 else len(mine)), nb * pipeline.RESULT_COLS)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), rows.cpu().numpy())
+    retry_after = retry_ctr.cpu().numpy()
     finite_frac = float(torch.isfinite(rows).double().mean().item())
 
-    # ---- secondary legs (outside the headline's timed region) ----
+    # ---- secondary legs (--full, outside the headline's timed region) ----
     extras = {}
-    if not args.no_extras and uniform:
+    if args.full and not args.no_extras and uniform:
         if args.features_steps > 0:
             extras["features_pass"] = features_leg(args, ctx, device, mine, shards, n_rec, rank, world, nb)
         if rank == 0:
@@ -293,23 +307,6 @@ def main():
 
     if rank == 0:
         value = total_pairs * args.steps / dt
-        launches = int(sp[:, 3].sum() - sp_before[:, 3].sum())
-        exp = args.steps * n_batches
-        assert launches == exp, f"probe saw {launches} launches of the dominant kernel, expected {exp}"
-        kernel_ms = float(sp[:, 2].sum() - sp_before[:, 2].sum()) / launches / 100e6 * 1e3   # timed region only
-        kernel_ms_all = float(sp[:, 2].sum()) / int(sp[:, 3].sum()) / 100e6 * 1e3            # every launch of the process
-        achieved = ALG_BYTES[DOM] * n_win_batch / (kernel_ms * 1e-3) / 1e9
-
-        def prof(name):
-            path = os.path.join(ROOT, "profiles", name)
-            try:
-                return json.load(open(path))
-            except Exception:
-                return None
-        tr = prof("traffic.json") or {}
-        traffic = tr.get(DOM)
-        if traffic is not None and tr.get("_windows_per_launch"):        # counted at another launch size: scale it
-            traffic = int(round(traffic * n_win_batch / tr["_windows_per_launch"]))
         line = {
             "metric": "windows/sec end-to-end (dist->Rips H0/H1->Wasserstein), 47-ch EEG",
             "value": value, "unit": "windows/s", "n_gpus": world, "steps": args.steps, "warmup": max(1, args.warmup),
@@ -337,61 +334,81 @@ def main():
                        "batches_rerun_with_full_ladder": lanes.repairs,
                        "result_rows_finite_frac": round(finite_frac, 6),
                        "data_generation_s": round(t_gen, 2)},
-            "stage_ms": {s: round(v, 4) for s, v in stage_ms.items()},     # one eager pass, every stage alone on the GPU
             "host_loop_ms_per_step": round(t_enq / args.steps * 1e3, 4),
-            "roofline": {"bound": "hbm", "kernel": "rips_cloud_kernel<512, 1, unsigned int, false, true> (stage rips_audio: first pass, "
-                                                   "narrow layout, three workgroups per CU)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel_ms": round(kernel_ms, 4),
-                         "event_ms": round(float(np.mean(event_ms)), 4), "event_ms_per_batch": [round(x, 4) for x in event_ms],
-                         "kernel_ms_all_launches": round(kernel_ms_all, 4),
-                         "launches_probed": int(sp[:, 3].sum()),
-                         "alg_bytes_per_launch": ALG_BYTES[DOM] * n_win_batch,
-                         "note": "irregular integer work in LDS/registers: the resource that binds it is LDS latency / "
-                                 "issue (see roofline_lds), so the HBM fraction is small by construction.  kernel_ms: "
-                                 "average over every launch of the timed region of (first workgroup start .. last "
-                                 "workgroup end), stamped by the kernel itself (100 MHz wall clock) -- the interval "
-                                 "rocprofv3 --kernel-trace reports; `achieved` uses it.  event_ms: HIP events around the "
-                                 "same launch on its stream, alone on the GPU (eager warm-up pass)"},
-            "roofline_lds": prof("r03_lds_roofline.json") or prof("r02_lds_roofline.json"),
         }
-        vp = (line["roofline_lds"] or {}).get("valu_per_window")
-        if vp and args.workload == "corpus":
-            # the step as a whole against the vector-issue roof: a SIMD-32 issues a wave64 instruction over 2 cycles
-            # once two or more waves share it (MI355X_MICROARCH.md, row v_fma_f32: "2 cyc (SIMD-32); one wave alone: 4")
-            peak = world * 256 * 4 * VALU_CLOCK_HZ / 2.0
-            ach = vp["total"] * value
-            line["roofline_valu"] = {"bound": "valu_issue", "achieved": ach / 1e9, "peak": peak / 1e9,
-                                     "unit": "G wave-instructions/s", "frac": ach / peak,
-                                     "valu_wave_instructions_per_window": vp["total"],
-                                     "note": "instructions per window pair from the committed SQ_INSTS_VALU counters "
-                                             "(profiles/r03_sq_counters.json, every kernel of the step), rate from this "
-                                             "run; peak = CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (SIMD-32, two or "
-                                             "more waves per SIMD: the guide's figure).  frac_of_measured_issue_rate: against "
-                                             "4 cycles per instruction at the 2.13 GHz the chip holds under load -- what "
-                                             "tools/probes/valu_rate.hip measures for the integer / 64-bit / f64 instructions "
-                                             "these kernels consist of (profiles/r03_valu_rate.txt; only v_add_u32, v_and_b32 "
-                                             "and f32 fma issue in 2)",
-                                     "frac_of_measured_issue_rate": ach / (world * 256 * 4 * 2.13e9 / 4.0)}
-        fp = extras.get("features_pass")
-        if fp:                                   # secondary: the one HBM-streaming kernel of the step
-            nw, ms = fp.pop("eeg_kernel_windows"), fp.pop("eeg_kernel_ms")
-            ach = ALG_BYTES["eeg_fused"] * nw / (ms * 1e-3) / 1e9
-            tre = tr.get("eeg_window")
-            line["roofline_hbm_kernel"] = {
-                "kernel": "eeg_window_kernel<3, false, 1, false> (fused EEG window: samples -> corr -> dist -> Rips)",
-                "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                "event_ms": round(ms, 4), "windows_per_launch": nw, "alg_bytes_per_launch": ALG_BYTES["eeg_fused"] * nw,
-                "traffic": int(round(tre * nw / tr["_windows_per_launch"])) if tre and tr.get("_windows_per_launch") else None,
-                "note": "secondary: the kernel that streams the corpus (95.1 KB per window, SURVEY.md section 8d); HIP "
-                        "events around one launch of the EEG-only features leg, nothing else on the GPU.  Its time is "
-                        "the Rips sweep behind the fetch, not the fetch.  traffic: the window is fetched twice (means, then "
-                        "products); the second fetch misses L2 and is counted by FETCH_SIZE, but the windows in flight (96 MB) "
-                        "sit in the 256 MiB Infinity Cache, which the counter does not tell from HBM; TDA_EEG_RESIDENT=1 "
-                        "keeps the window in registers instead (one fetch, 11 % slower on this leg)"}
-        line.update(extras)
-        if not args.no_cpu:
-            line["cpu_baseline"] = cpu_baseline(eeg, aud, wpr if uniform else 15, args.cpu_seconds)
+        if args.full:
+            sp = spans.cpu().numpy()
+            launches = int(sp[:, 3].sum() - sp_before[:, 3].sum())
+            exp = args.steps * n_batches
+            assert launches == exp, f"probe saw {launches} launches of the dominant kernel, expected {exp}"
+            kernel_ms = float(sp[:, 2].sum() - sp_before[:, 2].sum()) / launches / 100e6 * 1e3   # timed region only
+            kernel_ms_all = float(sp[:, 2].sum()) / int(sp[:, 3].sum()) / 100e6 * 1e3            # every launch of the process
+            achieved = ALG_BYTES[DOM] * n_win_batch / (kernel_ms * 1e-3) / 1e9
+
+            def prof(name):
+                path = os.path.join(ROOT, "profiles", name)
+                try:
+                    return json.load(open(path))
+                except Exception:
+                    return None
+            tr = prof("traffic.json") or {}
+            traffic = tr.get(DOM)
+            if traffic is not None and tr.get("_windows_per_launch"):        # counted at another launch size: scale it
+                traffic = int(round(traffic * n_win_batch / tr["_windows_per_launch"]))
+            line["stage_ms"] = {s: round(v, 4) for s, v in stage_ms.items()}     # one eager pass, every stage alone on the GPU
+            line["roofline"] = {
+                "bound": "hbm", "kernel": "rips_cloud_kernel<512, 1, unsigned int, false, true> (stage rips_audio: first pass, "
+                                          "narrow layout, three workgroups per CU)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel_ms": round(kernel_ms, 4),
+                "event_ms": round(float(np.mean(event_ms)), 4), "event_ms_per_batch": [round(x, 4) for x in event_ms],
+                "kernel_ms_all_launches": round(kernel_ms_all, 4),
+                "launches_probed": int(sp[:, 3].sum()),
+                "alg_bytes_per_launch": ALG_BYTES[DOM] * n_win_batch,
+                "note": "irregular integer work in LDS/registers: the resource that binds it is LDS latency / "
+                        "issue (see roofline_lds), so the HBM fraction is small by construction.  kernel_ms: "
+                        "average over every launch of the timed region of (first workgroup start .. last "
+                        "workgroup end), stamped by the kernel itself (100 MHz wall clock) -- the interval "
+                        "rocprofv3 --kernel-trace reports; `achieved` uses it.  event_ms: HIP events around the "
+                        "same launch on its stream, alone on the GPU (eager warm-up pass)"}
+            line["roofline_lds"] = prof("r03_lds_roofline.json") or prof("r02_lds_roofline.json")
+            vp = (line["roofline_lds"] or {}).get("valu_per_window")
+            if vp and args.workload == "corpus":
+                # the step as a whole against the vector-issue roof: a SIMD-32 issues a wave64 instruction over 2 cycles
+                # once two or more waves share it (v_fma_f32: 2 cycles; one wave alone: 4)
+                peak = world * 256 * 4 * VALU_CLOCK_HZ / 2.0
+                ach = vp["total"] * value
+                line["roofline_valu"] = {"bound": "valu_issue", "achieved": ach / 1e9, "peak": peak / 1e9,
+                                         "unit": "G wave-instructions/s", "frac": ach / peak,
+                                         "valu_wave_instructions_per_window": vp["total"],
+                                         "note": "instructions per window pair from the committed SQ_INSTS_VALU counters "
+                                                 "(profiles/r03_sq_counters.json, every kernel of the step), rate from this "
+                                                 "run; peak = CUs x 4 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction (SIMD-32, two or "
+                                                 "more waves per SIMD: the nominal figure).  frac_of_measured_issue_rate: against "
+                                                 "4 cycles per instruction at the 2.13 GHz the chip holds under load -- what "
+                                                 "tools/probes/valu_rate.hip measures for the integer / 64-bit / f64 instructions "
+                                                 "these kernels consist of (profiles/r03_valu_rate.txt; only v_add_u32, v_and_b32 "
+                                                 "and f32 fma issue in 2)",
+                                         "frac_of_measured_issue_rate": ach / (world * 256 * 4 * 2.13e9 / 4.0)}
+            fp = extras.get("features_pass")
+            if fp:                                   # secondary: the one HBM-streaming kernel of the step
+                nw, ms = fp.pop("eeg_kernel_windows"), fp.pop("eeg_kernel_ms")
+                ach = ALG_BYTES["eeg_fused"] * nw / (ms * 1e-3) / 1e9
+                tre = tr.get("eeg_window")
+                line["roofline_hbm_kernel"] = {
+                    "kernel": "eeg_window_kernel<3, false, 1, false> (fused EEG window: samples -> corr -> dist -> Rips)",
+                    "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                    "event_ms": round(ms, 4), "windows_per_launch": nw, "alg_bytes_per_launch": ALG_BYTES["eeg_fused"] * nw,
+                    "traffic": int(round(tre * nw / tr["_windows_per_launch"])) if tre and tr.get("_windows_per_launch") else None,
+                    "note": "secondary: the kernel that streams the corpus (95.1 KB per window, SURVEY.md section 8d); HIP "
+                            "events around one launch of the EEG-only features leg, nothing else on the GPU.  Its time is "
+                            "the Rips sweep behind the fetch, not the fetch.  traffic: the window is fetched twice (means, then "
+                            "products); the second fetch misses L2 and is counted by FETCH_SIZE, but the windows in flight (96 MB) "
+                            "sit in the 256 MiB Infinity Cache, which the counter does not tell from HBM; TDA_EEG_RESIDENT=1 "
+                            "keeps the window in registers instead (one fetch, 11 % slower on this leg)"}
+            line.update(extras)
+            if not args.no_cpu:
+                line["cpu_baseline"] = cpu_baseline(eeg, aud, wpr if uniform else 15, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

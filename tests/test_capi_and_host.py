@@ -79,12 +79,12 @@ def test_pure_index_mirrors_match_reference(golden):
 
 def test_feature_names_match_reference_file():
     from tda_eeg_audio_amd import drivers
-    ref = os.path.join("/root/reference", "features", "feature_names.txt")
+    # the reference's features/feature_names.txt, stored as data
+    ref = os.path.join(ROOT, "tests", "golden", "reference_feature_names.txt")
     names = drivers.feature_names()
     assert len(names) == 220 and names[0] == "delta_h0_n_features_mean" and names[3] == "delta_h1_n_features_std"
     assert names[-1] == "gamma_h1_persistence_entropy_std"
-    if os.path.exists(ref):          # only in the build container; the GPU box has no reference
-        assert names == open(ref).read().split()
+    assert names == open(ref).read().split()
 
 
 def test_pack_diagrams_and_sharding():
