@@ -157,7 +157,8 @@ tda_status tda_eeg_window_batch_dev(tda_ctx* ctx, const double* win, int n_win, 
                                     double* dist, double* corr, double* h0, int h0_cap, int* h0_cnt,
                                     double* h1, int h1_cap, int* h1_cnt, int* status, void* stream);
 
-/* The same kernel on windows read IN PLACE from band-passed recordings of equal length, sig: (n_rec, n_ch,
+/* The same kernel on windows read IN PLACE from band-passed recordings of equal length (recordings of different
+ * lengths: tda_eeg_window_ragged_dev below), sig: (n_rec, n_ch,
  * n_samples) float64 -- create_sliding_windows (notebooks/1_preprocesamiento.ipynb:314-381: window k of a recording =
  * samples [k*step, k*step + win_len), n_win_per_rec = (n_samples - win_len) / step + 1) + process_file_graphs
  * (nb2:198-207) + compute_eeg_persistence (utils.py:135-141) without ever materialising the (n_win, n_ch, win_len)
@@ -169,6 +170,17 @@ tda_status tda_eeg_window_sliding_dev(tda_ctx* ctx, const double* sig, int n_rec
                                       double* dist, double* corr, double* h0, int h0_cap, int* h0_cnt,
                                       double* h1, int h1_cap, int* h1_cnt, int* status, int* n_win_per_rec,
                                       void* stream);
+
+/* The same kernel on windows of RAGGED recordings, read in place from a window table: recordings of different lengths
+ * L_r are packed back to back (recording r is an (n_ch, L_r) row-major block at element n_ch * off[r], off the
+ * exclusive prefix sum of L); output window w starts at element win_start[w] of sig and its rows are win_ld[w] = L_r
+ * apart.  win_start / win_ld: device int64 (n_win), built once on the host -- create_sliding_windows
+ * (notebooks/1_preprocesamiento.ipynb:314-381) of each recording at its own length + the window selection (cmp:77-80) +
+ * nb2:198-207 + utils.py:135-141.  Diagrams identical to tda_eeg_window_batch_dev on the same windows stacked. */
+tda_status tda_eeg_window_ragged_dev(tda_ctx* ctx, const double* sig, const long long* win_start,
+                                     const long long* win_ld, int n_win, int n_ch, int win_len, double thresh,
+                                     double* dist, double* corr, double* h0, int h0_cap, int* h0_cnt, double* h1,
+                                     int h1_cap, int* h1_cnt, int* status, void* stream);
 
 /* ---- Takens embedding + Rips (audio branch) ---------------------------------
  * replaces takens_embedding (scripts/utils.py:107-116) followed by
@@ -234,6 +246,31 @@ tda_status tda_sosfiltfilt_bank_dev(tda_ctx* ctx, const double* x, int n_sig, in
 tda_status tda_filtfilt_bank_dev(tda_ctx* ctx, const double* x, int n_sig, int n_samples, const double* b,
                                  const double* a, const double* zi, int n_filters, int ntaps, int edge, double* y,
                                  double* work, void* stream);
+
+/* RAGGED filter banks: signals of different lengths, packed back to back, each filtered over its own length with its
+ * own odd extension and trim -- scipy.signal.sosfiltfilt / filtfilt on every signal alone, bit-identical.
+ * tda_sosfiltfilt_bank_ragged_dev replaces apply_bandpass_filter (nb1:236-263) for the EEG of n_rec recordings of
+ * lengths len[r]: recording r is an (n_ch, len[r]) block of x at element n_ch * off[r] (off: exclusive prefix sum of
+ * len, n_rec + 1 entries); y (n_filters, n_ch * off[n_rec]) in the same layout per filter; work (n_filters, n_ch *
+ * (off[n_rec] + 2*edge*n_rec)), recording r at n_ch * (off[r] + 2*edge*r).
+ * tda_filtfilt_bank_ragged_dev replaces bandpass_filter (utils.py:66-74, cmp:63-64) for n_sig envelopes of lengths
+ * len[s] (one channel each): signal s at element off[s]; y (n_filters, off[n_sig]); work (n_filters, off[n_sig] +
+ * 2*edge*n_sig), signal s at off[s] + 2*edge*s; ntaps <= 9.
+ * len, off: device int64 tables; len_host: the same lengths on the host -- a length <= edge is TDA_ERR_INVALID (scipy
+ * raises too).  sos / zi / b / a: host, as in the equal-length banks. */
+tda_status tda_sosfiltfilt_bank_ragged_dev(tda_ctx* ctx, const double* x, int n_rec, int n_ch, const long long* len,
+                                           const long long* off, const long long* len_host, const double* sos,
+                                           const double* zi, int n_filters, int n_sections, int edge, double* y,
+                                           double* work, void* stream);
+tda_status tda_filtfilt_bank_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len,
+                                        const long long* off, const long long* len_host, const double* b,
+                                        const double* a, const double* zi, int n_filters, int ntaps, int edge,
+                                        double* y, double* work, void* stream);
+/* Selected windows of packed signals into a stack: out[w, t] = src[start[w] + t], t < win_len (start: device int64,
+ * n_win) -- create_windows + the np.linspace selection (cmp:65,77-80) of the band-passed envelopes of ragged
+ * recordings, for the tau / Takens kernels. */
+tda_status tda_gather_windows_dev(tda_ctx* ctx, const double* src, const long long* start, int n_win, int win_len,
+                                  double* out, void* stream);
 
 /* Audio front end.  tda_upfirdn replaces scipy.signal.resample_poly(audio, 250, 44100) (scripts/utils.py:77-79):
  * h (len_h, host-designed exactly as scipy does, incl. its zero padding and the factor `up`),

@@ -58,6 +58,11 @@ SYMBOLS = {
     "tda_filtfilt": (_I, [c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, _I, _I, c_vp]),
     "tda_sosfiltfilt_bank_dev": (_I, [c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
     "tda_filtfilt_bank_dev": (_I, [c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_sosfiltfilt_bank_ragged_dev": (_I, [c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_filtfilt_bank_ragged_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_gather_windows_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp]),
+    "tda_eeg_window_ragged_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, _D, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp,
+                                       c_vp, c_vp]),
     "tda_upfirdn_dev": (_I, [c_vp, c_vp, C.c_longlong, c_vp, _I, _I, _I, C.c_longlong, C.c_longlong, c_vp, c_vp]),
     "tda_upfirdn": (_I, [c_vp, c_vp, C.c_longlong, c_vp, _I, _I, _I, C.c_longlong, C.c_longlong, c_vp]),
     "tda_hilbert_envelope_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp]),

@@ -166,6 +166,19 @@ tda_status tda_eeg_window_sliding_dev(tda_ctx* ctx, const double* sig, int n_rec
                               h0_cnt, h1, h1_cap, h1_cnt, status, n_win_per_rec, (hipStream_t)stream);
 }
 
+tda_status tda_eeg_window_ragged_dev(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                     int n_win, int n_ch, int win_len, double thresh, double* dist, double* corr, double* h0,
+                                     int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, sig); CHECK_PTR(ctx, win_start); CHECK_PTR(ctx, win_ld); CHECK_PTR(ctx, h0);
+                 CHECK_PTR(ctx, h0_cnt); CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status); }
+    if (corr && !dist) TDA_FAIL(ctx, TDA_ERR_INVALID, "corr needs dist");
+    if (h1_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "h1_cap must be >= 1");
+    return launch_eeg_ragged(ctx, sig, win_start, win_ld, n_win, n_ch, win_len, thresh, dist, corr, h0, h0_cap, h0_cnt, h1,
+                             h1_cap, h1_cnt, status, (hipStream_t)stream);
+}
+
 tda_status tda_takens_rips_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
                                      int subsample, double thresh, double* h0, int h0_cap, int* h0_cnt, double* h1,
                                      int h1_cap, int* h1_cnt, int* n_points, int* status, void* stream)
@@ -227,6 +240,39 @@ tda_status tda_filtfilt_bank_dev(tda_ctx* ctx, const double* x, int n_sig, int n
     if (n_sig) { CHECK_PTR(ctx, x); CHECK_PTR(ctx, y); CHECK_PTR(ctx, work); }
     CHECK_PTR(ctx, b); CHECK_PTR(ctx, a); CHECK_PTR(ctx, zi);
     return launch_filtfilt(ctx, x, n_sig, n_samples, b, a, zi, ntaps, edge, y, work, (hipStream_t)stream, n_filters);
+}
+
+tda_status tda_sosfiltfilt_bank_ragged_dev(tda_ctx* ctx, const double* x, int n_rec, int n_ch, const long long* len,
+                                           const long long* off, const long long* len_host, const double* sos,
+                                           const double* zi, int n_filters, int n_sections, int edge, double* y,
+                                           double* work, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_rec); CHECK_NONNEG(ctx, n_ch);
+    if (n_rec && n_ch) { CHECK_PTR(ctx, x); CHECK_PTR(ctx, len); CHECK_PTR(ctx, off); CHECK_PTR(ctx, len_host);
+                         CHECK_PTR(ctx, y); CHECK_PTR(ctx, work); }
+    CHECK_PTR(ctx, sos); CHECK_PTR(ctx, zi);
+    return launch_sosfiltfilt_ragged(ctx, x, n_rec, n_ch, len, off, len_host, sos, zi, n_filters, n_sections, edge, y, work,
+                                     (hipStream_t)stream);
+}
+
+tda_status tda_filtfilt_bank_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len, const long long* off,
+                                        const long long* len_host, const double* b, const double* a, const double* zi,
+                                        int n_filters, int ntaps, int edge, double* y, double* work, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_sig);
+    if (n_sig) { CHECK_PTR(ctx, x); CHECK_PTR(ctx, len); CHECK_PTR(ctx, off); CHECK_PTR(ctx, len_host);
+                 CHECK_PTR(ctx, y); CHECK_PTR(ctx, work); }
+    CHECK_PTR(ctx, b); CHECK_PTR(ctx, a); CHECK_PTR(ctx, zi);
+    return launch_filtfilt_ragged(ctx, x, n_sig, len, off, len_host, b, a, zi, n_filters, ntaps, edge, y, work,
+                                  (hipStream_t)stream);
+}
+
+tda_status tda_gather_windows_dev(tda_ctx* ctx, const double* src, const long long* start, int n_win, int win_len,
+                                  double* out, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, src); CHECK_PTR(ctx, start); CHECK_PTR(ctx, out); }
+    return launch_gather_windows(ctx, src, start, n_win, win_len, out, (hipStream_t)stream);
 }
 
 tda_status tda_upfirdn_dev(tda_ctx* ctx, const double* x, long long n_in, const double* h, int len_h, int up, int down,

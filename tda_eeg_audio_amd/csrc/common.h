@@ -195,6 +195,13 @@ tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, con
                            double*, hipStream_t, int n_filt = 1);
 tda_status launch_upfirdn(tda_ctx*, const double*, long long, const double*, int, int, int, long long, long long, double*,
                           hipStream_t);
+tda_status launch_sosfiltfilt_ragged(tda_ctx*, const double*, int, int, const long long*, const long long*, const long long*,
+                                     const double*, const double*, int, int, int, double*, double*, hipStream_t);
+tda_status launch_filtfilt_ragged(tda_ctx*, const double*, int, const long long*, const long long*, const long long*,
+                                  const double*, const double*, const double*, int, int, int, double*, double*, hipStream_t);
+tda_status launch_gather_windows(tda_ctx*, const double*, const long long*, int, int, double*, hipStream_t);
+tda_status launch_eeg_ragged(tda_ctx*, const double*, const long long*, const long long*, int, int, int, double, double*,
+                             double*, double*, int, int*, double*, int, int*, int*, hipStream_t);
 tda_status launch_hilbert_env(tda_ctx*, const double*, int, const double*, double*, hipStream_t);
 tda_status launch_tau(tda_ctx*, const double*, int, int, int, int*, hipStream_t);
 tda_status launch_tau_segments(tda_ctx*, const double*, const int*, int, int, int, int*, int*, hipStream_t);

@@ -273,6 +273,104 @@ sos_pipe_kernel(const double* __restrict__ x, int n_sig, int L, int edge, SosBan
     }
 }
 
+// RAGGED recordings (packed back to back: recording r is an (n_ch, len[r]) block at element n_ch * off[r], off the
+// exclusive prefix sum of len, off[n_rec] the total): the waves of one workgroup row take the channels of ONE recording
+// (ceil(n_ch / SPW) waves each; 47 channels: 3 waves of 16, 47 of 48 lanes busy), so the loop bound len[r] + 2*edge is
+// uniform within a wave.  y (n_filt, n_ch * off[n_rec]); work (n_filt, n_ch * (off[n_rec] + 2*edge*n_rec)), recording r
+// at n_ch * (off[r] + 2*edge*r).  Below the address computation the body is sos_pipe_kernel's, line for line (a copy,
+// not a shared function: sharing it changed the register allocation of the equal-length instantiations), so every
+// channel sees exactly the operations of sos_pipe_kernel: bit-identical to scipy.signal.sosfiltfilt on that channel.
+template <int LPS>
+__global__ void __launch_bounds__(64, 4)
+sos_pipe_ragged_kernel(const double* __restrict__ x, int n_rec, int n_ch, const long long* __restrict__ len,
+                       const long long* __restrict__ off, int edge, SosBank bank, double* __restrict__ y,
+                       double* __restrict__ work)
+{
+    constexpr int SPW = 64 / LPS;                      // signals per wave
+    __shared__ double tin[SPW * FTP];
+    double* tout = tin;
+    __shared__ double coef[F_MAX_SEC][8];              // b0 b1 b2 a0 a1 a2 zi0 zi1 per section (identity beyond n_sec)
+    const int wpr = (n_ch + SPW - 1) / SPW;            // waves per recording
+    const int rec = blockIdx.x / wpr;
+    if (rec >= n_rec) return;
+    const long long o = off[rec], total = off[n_rec];
+    if (len[rec] <= edge) return;                      // (rejected on the host; never read outside the recording)
+    const int L = (int)len[rec], n_sig = n_ch;
+    const SosParams& p = bank.f[blockIdx.y];
+    const int lane = threadIdx.x, sl = lane / LPS, s = lane % LPS;
+    const int s0 = (blockIdx.x - rec * wpr) * SPW, sig = s0 + sl;
+    const int N = L + 2 * edge;
+    x += n_ch * o;
+    y += (size_t)blockIdx.y * n_ch * total + n_ch * o;
+    work += (size_t)blockIdx.y * n_ch * (total + 2LL * edge * n_rec) + n_ch * (o + 2LL * edge * rec);
+    const bool live = sig < n_sig;
+    if (lane < F_MAX_SEC * 8) {
+        const int q = lane >> 3, k = lane & 7;
+        double v = (k == 0) ? 1.0 : 0.0;
+        if (q < p.n_sec) v = k < 6 ? p.c[q][k] : p.zi[q][k - 6];
+        coef[q][k] = v;
+    }
+    __syncthreads();
+    const double b0 = coef[s][0], b1 = coef[s][1], b2 = coef[s][2], a1 = coef[s][4], a2 = coef[s][5];
+    const double zi0 = coef[s][6], zi1 = coef[s][7];
+    for (int pass = 0; pass < 2; ++pass) {
+        // pass 0: forward over the odd extension -> work (n_sig, N); pass 1: backward over work -> y (trimmed)
+        double x0 = 0.0;
+        if (live) x0 = pass == 0 ? odd_ext_at(x + (size_t)sig * L, L, edge, 0) : work[(size_t)sig * N + N - 1];
+        double z0 = zi0 * x0, z1 = zi1 * x0;            // sosfilt_zi * first input sample, every section
+        double outp = 0.0;                              // this lane's output of the previous step
+        // input chunk: positions c0 .. c0+63 of the pass (lane = position: coalesced rows).  The rows of the NEXT chunk are
+        // fetched into registers before the steps of the current one: the load latency hides behind the recursion
+        double v[SPW];
+        auto fetch = [&](int c0) {
+            const int j = c0 + lane;
+#pragma unroll
+            for (int r = 0; r < SPW; ++r) {
+                v[r] = 0.0;
+                if (s0 + r < n_sig && j < N)
+                    v[r] = pass == 0 ? odd_ext_at(x + (size_t)(s0 + r) * L, L, edge, j) : work[(size_t)(s0 + r) * N + (N - 1 - j)];
+            }
+        };
+        fetch(0);
+        for (int c0 = 0; c0 < N + LPS - 1; c0 += FT) {
+#pragma unroll
+            for (int r = 0; r < SPW; ++r) tin[r * FTP + lane] = v[r];
+            __syncthreads();
+            if (c0 + FT < N + LPS - 1) fetch(c0 + FT);
+            double x_in = tin[sl * FTP];                // the first section's input, fetched one step ahead (the row is FT + 1 long)
+            for (int t = 0; t < FT; ++t) {
+                const int i = c0 + t - s;               // position this lane works on in this step
+                const double from_prev = dpp_row_shr1_f64(outp);
+                const double x_cur = s == 0 ? x_in : from_prev;
+                x_in = tin[sl * FTP + t + 1];
+                if (i >= 0 && i < N) {
+                    // scipy/signal/_sosfilt.pyx: x_new = b0*x + z0; z0 = (b1*x - a1*x_new + z1); z1 = (b2*x - a2*x_new)
+                    const double x_new = b0 * x_cur + z0;
+                    z0 = (b1 * x_cur - a1 * x_new) + z1;
+                    z1 = b2 * x_cur - a2 * x_new;
+                    outp = x_new;
+                }
+                if (s == LPS - 1) tout[sl * FTP + t] = outp;        // position c0 + t - (LPS - 1) of the output
+            }
+            __syncthreads();
+            for (int r = 0; r < SPW; ++r) {
+                const int j = c0 + lane - (LPS - 1);                // output position of the pass
+                if (s0 + r < n_sig && j >= 0 && j < N) {
+                    const double v = tout[r * FTP + lane];
+                    if (pass == 0) work[(size_t)(s0 + r) * N + j] = v;
+                    else {
+                        const int i = N - 1 - j;                    // index in the padded signal
+                        if (i >= edge && i < edge + L) y[(size_t)(s0 + r) * L + i - edge] = v;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        __threadfence_block();
+        __syncthreads();                                // work complete (this workgroup's rows) before the backward pass
+    }
+}
+
 tda_status launch_sosfiltfilt(tda_ctx* ctx, const double* x, int n_sig, int L, const double* sos, const double* zi,
                               int n_sec, int edge, double* y, double* work, hipStream_t st, int n_filt)
 {
@@ -409,6 +507,111 @@ ba_pipe_kernel(const double* __restrict__ x, int n_sig, int L, int edge, BaBank 
     }
 }
 
+// RAGGED signals (packed back to back: signal s has len[s] samples at element off[s], off the exclusive prefix sum of len,
+// off[n_sig] the total): the scheme of ba_pipe_kernel with a length per signal.  The eight signals of a wave may differ
+// in length: the wave loops to the longest, and the group of a signal past its own end computes but keeps nothing
+// (its eight lanes share the mask, so the DPP moves inside the group never see a stale neighbour).  The backward pass
+// runs in reversed coordinates j = N - 1 - i, so that every signal starts from its own end.  Each signal sees exactly
+// the operations of ba_pipe_kernel: bit-identical to scipy.signal.filtfilt on that signal alone.
+// y (n_filt, off[n_sig]); work (n_filt, off[n_sig] + 2*edge*n_sig), signal s at off[s] + 2*edge*s.
+__global__ void __launch_bounds__(64)
+ba_pipe_ragged_kernel(const double* __restrict__ x, int n_sig, const long long* __restrict__ len,
+                      const long long* __restrict__ off, int edge, BaBank bank, double* __restrict__ y,
+                      double* __restrict__ work)
+{
+    constexpr int ND = 8, SPW = 64 / ND;
+    __shared__ double tile[SPW * FTP];
+    const BaParams& p = bank.f[blockIdx.y];
+    const int lane = threadIdx.x, g = lane / ND, k = lane % ND;
+    const int s0 = blockIdx.x * SPW;
+    const long long total = off[n_sig];
+    y += (size_t)blockIdx.y * total;
+    work += (size_t)blockIdx.y * (total + 2LL * edge * n_sig);
+    // per row of the wave: length (0 = no signal, or one too short to pad: rejected on the host, never read here)
+    int Lr[SPW], Nr[SPW];
+    long long xo[SPW], wo[SPW];
+    int n_max = 0;
+#pragma unroll
+    for (int r = 0; r < SPW; ++r) {
+        const int s = s0 + r;
+        Lr[r] = 0; xo[r] = 0; wo[r] = 0;
+        if (s < n_sig) {
+            const long long l = len[s];
+            if (l > edge) { Lr[r] = (int)l; xo[r] = off[s]; wo[r] = off[s] + 2LL * edge * s; }
+        }
+        Nr[r] = Lr[r] ? Lr[r] + 2 * edge : 0;
+        n_max = Nr[r] > n_max ? Nr[r] : n_max;
+    }
+    int Ng = 0;                                         // this lane's signal
+#pragma unroll
+    for (int r = 0; r < SPW; ++r) Ng = r == g ? Nr[r] : Ng;
+    const double b0 = p.b[0], bk = p.b[k + 1], ak = p.a[k + 1], zik = p.zi[k];
+    const bool last = k == ND - 1;
+    double* row = tile + g * FTP;
+    double z = 0.0;
+    auto step = [&](int t, bool act) {
+        const double xn = row[t];
+        const double yn = dpp_bcast8_f64(z) + b0 * xn;
+        const double t1 = xn * bk;
+        const double zn = dpp_row_shl1_f64(z);
+        const double u = last ? t1 : zn + t1;
+        const double znew = u - yn * ak;
+        if (act) {
+            z = znew;
+            if (k == 0) row[t] = yn;
+        }
+    };
+    double v[SPW];
+    auto fetch_fwd = [&](int c0) {
+#pragma unroll
+        for (int r = 0; r < SPW; ++r)
+            v[r] = (c0 + lane < Nr[r]) ? odd_ext_at(x + xo[r], Lr[r], edge, c0 + lane) : 0.0;
+    };
+    auto fetch_bwd = [&](int c0) {                      // reversed: position j = c0 + lane is padded index N - 1 - j
+#pragma unroll
+        for (int r = 0; r < SPW; ++r)
+            v[r] = (c0 + lane < Nr[r]) ? work[wo[r] + (Nr[r] - 1 - (c0 + lane))] : 0.0;
+    };
+    // ---- forward over the odd extension, output to work ----
+    fetch_fwd(0);
+    for (int c0 = 0; c0 < n_max; c0 += FT) {
+        const int cn = (n_max - c0) < FT ? (n_max - c0) : FT;
+        const int cg = Ng - c0;                         // this signal's samples in the chunk (may be <= 0)
+#pragma unroll
+        for (int r = 0; r < SPW; ++r) tile[r * FTP + lane] = v[r];
+        __syncthreads();
+        if (c0 + FT < n_max) fetch_fwd(c0 + FT);
+        if (c0 == 0) z = zik * row[0];                  // lfilter_zi * x[0]
+        for (int t = 0; t < cn; ++t) step(t, t < cg);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < SPW; ++r)
+            if (c0 + lane < Nr[r]) work[wo[r] + c0 + lane] = tile[r * FTP + lane];
+        __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();                                    // this workgroup's rows of `work` are complete
+    // ---- backward over work (reversed coordinates), trimmed result to y ----
+    fetch_bwd(0);
+    for (int c0 = 0; c0 < n_max; c0 += FT) {
+        const int cn = (n_max - c0) < FT ? (n_max - c0) : FT;
+        const int cg = Ng - c0;
+#pragma unroll
+        for (int r = 0; r < SPW; ++r) tile[r * FTP + lane] = v[r];
+        __syncthreads();
+        if (c0 + FT < n_max) fetch_bwd(c0 + FT);
+        if (c0 == 0) z = zik * row[0];                  // zi * y[-1]
+        for (int t = 0; t < cn; ++t) step(t, t < cg);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < SPW; ++r) {
+            const int i = Nr[r] - 1 - (c0 + lane);      // index in the padded signal
+            if (c0 + lane < Nr[r] && i >= edge && i < edge + Lr[r]) y[xo[r] + i - edge] = tile[r * FTP + lane];
+        }
+        __syncthreads();
+    }
+}
+
 tda_status launch_filtfilt(tda_ctx* ctx, const double* x, int n_sig, int L, const double* b, const double* a,
                            const double* zi, int ntaps, int edge, double* y, double* work, hipStream_t st, int n_filt)
 {
@@ -435,6 +638,92 @@ tda_status launch_filtfilt(tda_ctx* ctx, const double* x, int n_sig, int L, cons
     else
         hipLaunchKernelGGL((zero_phase_kernel<BaFilter, BaBank>), dim3((n_sig + FT - 1) / FT, n_filt), dim3(FT), 0, st, x, n_sig,
                            L, edge, bank, y, work);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
+// ---- ragged banks (packed signals; see sos_pipe_ragged_kernel / ba_pipe_ragged_kernel) ----
+// len / off: device tables (int64); len_h: the same lengths on the host, checked here (scipy raises for a signal that is
+// not longer than the pad length, so does this)
+static tda_status check_ragged_lengths(tda_ctx* ctx, const long long* len_h, int n, int edge)
+{
+    if (edge < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "edge must be >= 0");
+    for (int i = 0; i < n; ++i)
+        if (len_h[i] <= edge || len_h[i] > 0x7fffffffLL - 2LL * edge)
+            TDA_FAIL(ctx, TDA_ERR_INVALID, "signal length must exceed the pad length");
+    return TDA_OK;
+}
+
+tda_status launch_sosfiltfilt_ragged(tda_ctx* ctx, const double* x, int n_rec, int n_ch, const long long* len,
+                                     const long long* off, const long long* len_h, const double* sos, const double* zi,
+                                     int n_filt, int n_sec, int edge, double* y, double* work, hipStream_t st)
+{
+    if (n_rec == 0 || n_ch == 0 || n_filt == 0) return TDA_OK;
+    if (n_sec < 1 || n_sec > F_MAX_SEC) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "n_sections must be in [1,8]");
+    if (n_filt < 1 || n_filt > F_MAX_BANK) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "a filter bank holds 1..5 filters");
+    { const tda_status rc = check_ragged_lengths(ctx, len_h, n_rec, edge); if (rc != TDA_OK) return rc; }
+    SosBank bank = {};
+    for (int f = 0; f < n_filt; ++f) {
+        SosParams& p = bank.f[f];
+        p.n_sec = n_sec;
+        for (int s = 0; s < n_sec; ++s) {
+            for (int k = 0; k < 6; ++k) p.c[s][k] = sos[(f * n_sec + s) * 6 + k];
+            p.zi[s][0] = zi[(f * n_sec + s) * 2]; p.zi[s][1] = zi[(f * n_sec + s) * 2 + 1];
+        }
+    }
+    // waves of one recording each: ceil(n_ch / signals per wave) per recording
+    if (n_sec <= 2)
+        hipLaunchKernelGGL(sos_pipe_ragged_kernel<2>, dim3(n_rec * ((n_ch + 31) / 32), n_filt), dim3(64), 0, st, x, n_rec, n_ch,
+                           len, off, edge, bank, y, work);
+    else if (n_sec <= 4)
+        hipLaunchKernelGGL(sos_pipe_ragged_kernel<4>, dim3(n_rec * ((n_ch + 15) / 16), n_filt), dim3(64), 0, st, x, n_rec, n_ch,
+                           len, off, edge, bank, y, work);
+    else
+        hipLaunchKernelGGL(sos_pipe_ragged_kernel<8>, dim3(n_rec * ((n_ch + 7) / 8), n_filt), dim3(64), 0, st, x, n_rec, n_ch,
+                           len, off, edge, bank, y, work);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
+tda_status launch_filtfilt_ragged(tda_ctx* ctx, const double* x, int n_sig, const long long* len, const long long* off,
+                                  const long long* len_h, const double* b, const double* a, const double* zi, int n_filt,
+                                  int ntaps, int edge, double* y, double* work, hipStream_t st)
+{
+    if (n_sig == 0 || n_filt == 0) return TDA_OK;
+    if (ntaps < 2 || ntaps > 9) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "the ragged bank takes len(b)=len(a) in [2,9]");
+    if (n_filt < 1 || n_filt > F_MAX_BANK) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "a filter bank holds 1..5 filters");
+    { const tda_status rc = check_ragged_lengths(ctx, len_h, n_sig, edge); if (rc != TDA_OK) return rc; }
+    BaBank bank = {};
+    for (int f = 0; f < n_filt; ++f) {
+        BaParams& p = bank.f[f];
+        p.ntaps = ntaps;
+        const double a0 = a[f * ntaps];
+        for (int k = 0; k < F_MAX_TAPS; ++k) { p.b[k] = k < ntaps ? b[f * ntaps + k] / a0 : 0.0; p.a[k] = k < ntaps ? a[f * ntaps + k] / a0 : 0.0; }
+        for (int k = 0; k < F_MAX_TAPS; ++k) p.zi[k] = k < ntaps - 1 ? zi[f * (ntaps - 1) + k] : 0.0;
+    }
+    hipLaunchKernelGGL(ba_pipe_ragged_kernel, dim3((n_sig + 7) / 8, n_filt), dim3(64), 0, st, x, n_sig, len, off, edge, bank, y, work);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
+// selected windows of packed signals into a stack: out[i, t] = src[start[i] + t], t < win_len -- the envelope windows
+// the tau / Takens kernels read (create_windows + np.linspace, cmp:65,77-80) for ragged recordings
+__global__ void __launch_bounds__(256)
+gather_windows_kernel(const double* __restrict__ src, const long long* __restrict__ start, int n_win, int win_len,
+                      double* __restrict__ out)
+{
+    const int w = blockIdx.x;
+    if (w >= n_win) return;
+    const double* s = src + start[w];
+    for (int t = threadIdx.x; t < win_len; t += 256) out[(size_t)w * win_len + t] = s[t];
+}
+
+tda_status launch_gather_windows(tda_ctx* ctx, const double* src, const long long* start, int n_win, int win_len, double* out,
+                                 hipStream_t st)
+{
+    if (n_win == 0) return TDA_OK;
+    if (win_len < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_len must be >= 1");
+    hipLaunchKernelGGL(gather_windows_kernel, dim3(n_win), dim3(256), 0, st, src, start, n_win, win_len, out);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }

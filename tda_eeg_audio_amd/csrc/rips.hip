@@ -2375,16 +2375,24 @@ struct WindowSource {
         const int r = g / wins_per_group, k = g - r * wins_per_group;
         return base + (size_t)r * (size_t)group_stride + (size_t)k * (size_t)win_stride;
     }
+    __device__ __forceinline__ int ld_of(int) const { return ld; }
+};
+// ragged form: windows of recordings of different lengths (packed back to back, recording r an (n_ch, L_r) block): a
+// table per output window w -- element offset of its first sample, start[w], and its row stride ld[w] = L_r
+struct RaggedWindowSource {
+    const double* base; const long long* start; const long long* ld;
+    __device__ __forceinline__ const double* at(int w) const { return base + start[w]; }
+    __device__ __forceinline__ int ld_of(int w) const { return (int)ld[w]; }
 };
 
-template <int NB, bool RES, int W, typename WT>
-__device__ __forceinline__ void eeg_one_window(unsigned char* smem, const WindowSource& src, int w, int n_ch,
+template <int NB, bool RES, int W, typename WT, class SRC>
+__device__ __forceinline__ void eeg_one_window(unsigned char* smem, const SRC& src, int w, int n_ch,
                                                int n_t, float thresh, const RipsLayout& L, const RipsOut& out,
                                                double* __restrict__ dist, double* __restrict__ corr)
 {
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6;
     PROF_BEGIN();
-    cd_window_products<NB, RES>(smem, src.at(w), n_ch, n_t, src.ld);
+    cd_window_products<NB, RES>(smem, src.at(w), n_ch, n_t, src.ld_of(w));
     const double* accs = reinterpret_cast<const double*>(smem) + CdLayout<NB>::TILE;
     const double* sdev = accs + CdLayout<NB>::ACCS + CdLayout<NB>::CP;
     const double fact = 1.0 / (double)(n_t - 1);
@@ -2460,6 +2468,29 @@ eeg_window_kernel(WindowSource windows, int n_win, int n_ch, int n_t, float thre
         RETRY_SCAN_END()
     }
 }
+// the same kernel on a window table (RaggedWindowSource); a kernel of its own so that the instantiations above keep
+// their names and their code
+template <int NB, bool RES, int W, bool RETRY, typename WT>
+__global__ void __launch_bounds__(256, (W > 2 || RETRY) ? TDA_EEG_WIDE_WAVES : (RES ? 3 : TDA_EEG_WAVES))
+eeg_window_ragged_kernel(RaggedWindowSource windows, int n_win, int n_ch, int n_t, float thresh, RipsLayout L, RipsOut out,
+                         double* __restrict__ dist, double* __restrict__ corr, unsigned long long* __restrict__ retry_ctr)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if constexpr (!RETRY) {
+        if ((int)blockIdx.x < n_win)
+            eeg_one_window<NB, RES, W, WT>(smem, windows, (int)blockIdx.x, n_ch, n_t, thresh, L, out, dist, corr);
+    } else {
+        RETRY_SCAN_BEGIN(256, out, n_win)
+            if (retry_ctr && threadIdx.x == 0) atomicAdd(retry_ctr, 1ull);
+            eeg_one_window<NB, RES, W, WT>(smem, windows, win, n_ch, n_t, thresh, L, out, dist, corr);
+        RETRY_SCAN_END()
+    }
+}
+// the kernel of a window source
+template <int NB, bool RES, int W, bool RETRY, typename WT>
+static auto eeg_kernel_of(const WindowSource*) { return eeg_window_kernel<NB, RES, W, RETRY, WT>; }
+template <int NB, bool RES, int W, bool RETRY, typename WT>
+static auto eeg_kernel_of(const RaggedWindowSource*) { return eeg_window_ragged_kernel<NB, RES, W, RETRY, WT>; }
 
 // ---------------------------------------------------------------------------------
 // host side
@@ -2655,14 +2686,14 @@ tda_status launch_rips_dm(tda_ctx* ctx, const double* dm, int n_win, int n, doub
     return order_h1(ctx, h1, h1_cap, h1_cnt, n_win, st);
 }
 
-template <int NB, bool RES, int W, bool RETRY, typename WT = u64>
-static tda_status launch_eeg_t(tda_ctx* ctx, const WindowSource& win, int n_win, int n_ch, int n_t, float thresh, RipsOut out,
+template <int NB, bool RES, int W, bool RETRY, typename WT = u64, class SRC>
+static tda_status launch_eeg_t(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float thresh, RipsOut out,
                                double* dist, double* corr, hipStream_t st)
 {
     RipsLayout L = make_layout(n_ch, W * (int)sizeof(WT), n_ch * (n_ch - 1) / 2 * 4, 256);
     if ((size_t)L.total < CdLayout<NB>::BYTES) L.total = (int)((CdLayout<NB>::BYTES + 15) & ~(size_t)15);
     if (L.total > LDS_MAX) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "window too large for LDS");
-    auto kern = eeg_window_kernel<NB, RES, W, RETRY, WT>;
+    auto kern = eeg_kernel_of<NB, RES, W, RETRY, WT>(&win);
     if (L.total > 48 * 1024)
         TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
@@ -2678,8 +2709,8 @@ static tda_status launch_eeg_t(tda_ctx* ctx, const WindowSource& win, int n_win,
     return TDA_OK;
 }
 
-template <bool RES>
-static tda_status launch_eeg_ladder(tda_ctx* ctx, const WindowSource& win, int n_win, int n_ch, int n_t, float th, RipsOut out,
+template <bool RES, class SRC>
+static tda_status launch_eeg_ladder(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float th, RipsOut out,
                                     double* dist, double* corr, hipStream_t st)
 {
     if (ctx->retry_policy == TDA_RETRY_LAST_RUNG) return TDA_OK;     // (512 bits cover every complex on 48 points: no such rung here)
@@ -2705,7 +2736,8 @@ static tda_status launch_eeg_ladder(tda_ctx* ctx, const WindowSource& win, int n
     return rc;
 }
 
-static tda_status launch_eeg_source(tda_ctx* ctx, const WindowSource& src, int n_win, int n_ch, int n_t, double thresh,
+template <class SRC>
+static tda_status launch_eeg_source(tda_ctx* ctx, const SRC& src, int n_win, int n_ch, int n_t, double thresh,
                                     double* dist, double* corr, double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap,
                                     int* h1_cnt, int* status, hipStream_t st)
 {
@@ -2749,6 +2781,16 @@ tda_status launch_eeg_sliding(tda_ctx* ctx, const double* sig, int n_rec, int n_
     const int n_out = sel ? n_sel : n_rec * per_rec;
     const WindowSource src{sig, (long long)step, (long long)n_ch * n_samples, n_samples, per_rec, sel};
     return launch_eeg_source(ctx, src, n_out, n_ch, win_len, thresh, dist, corr, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status, st);
+}
+
+// windows of ragged recordings from a window table (RaggedWindowSource): start / ld device int64 (n_win)
+tda_status launch_eeg_ragged(tda_ctx* ctx, const double* sig, const long long* start, const long long* ld, int n_win, int n_ch,
+                             int win_len, double thresh, double* dist, double* corr, double* h0, int h0_cap, int* h0_cnt,
+                             double* h1, int h1_cap, int* h1_cnt, int* status, hipStream_t st)
+{
+    if (win_len < 2) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_len must be >= 2");
+    const RaggedWindowSource src{sig, start, ld};
+    return launch_eeg_source(ctx, src, n_win, n_ch, win_len, thresh, dist, corr, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status, st);
 }
 
 template <int W, typename WT, bool NARROW = false>

@@ -248,6 +248,14 @@ class DeviceDiagrams:
         self.n_points = torch.empty(n_win, dtype=torch.int32, **kw)
         self.h0_cap, self.h1_cap, self.n_win = h0_cap, h1_cap, n_win
 
+    def head(self, n_win):
+        """The same buffers for the first n_win windows only (a view: nothing is copied)."""
+        v = object.__new__(DeviceDiagrams)
+        v.h0, v.h1, v.c0, v.c1 = self.h0[:n_win], self.h1[:n_win], self.c0[:n_win], self.c1[:n_win]
+        v.status, v.n_points = self.status[:n_win], self.n_points[:n_win]
+        v.h0_cap, v.h1_cap, v.n_win = self.h0_cap, self.h1_cap, n_win
+        return v
+
     def to_lists(self):
         h0, c0 = self.h0.cpu().numpy(), self.c0.cpu().numpy()
         h1, c1 = self.h1.cpu().numpy(), self.c1.cpu().numpy()
@@ -309,6 +317,39 @@ def eeg_window_sliding_dev(sig_t, win_len=250, step=62, sel_t=None, out=None, th
                                                  _tp(out.h0), out.h0_cap, _tp(out.c0), _tp(out.h1), out.h1_cap, _tp(out.c1),
                                                  _tp(out.status), None, _stream()))
     return out, per_rec
+
+
+def eeg_window_ragged_dev(sig_t, start_t, ld_t, win_len=250, out=None, thresh=MAX_EDGE_LENGTH, h1_cap=DEFAULT_H1_CAP,
+                          dist_t=None, corr_t=None, n_ch=47, ctx=None):
+    """Fused corr -> dist -> Rips on windows of RAGGED recordings read in place from a window table: window w starts at
+    element start_t[w] of sig_t (packed band-passed recordings) and its n_ch rows are ld_t[w] (= L_r) apart; both int64
+    device tensors (nb1:314-381 per recording + nb2:198-207 + utils.py:135-141).  Diagrams identical to eeg_window_dev on
+    the same windows stacked."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert sig_t.is_cuda and sig_t.dtype == torch.float64 and sig_t.is_contiguous()
+    assert start_t.dtype == torch.int64 and ld_t.dtype == torch.int64 and start_t.numel() == ld_t.numel()
+    n_win = int(start_t.numel())
+    out = out or DeviceDiagrams(n_win, n_ch, h1_cap, sig_t.device)
+    assert out.n_win == n_win
+    ctx.check(ctx.lib.tda_eeg_window_ragged_dev(ctx.h, _tp(sig_t), _tp(start_t), _tp(ld_t), n_win, n_ch, int(win_len),
+                                                float(thresh), _tp(dist_t), _tp(corr_t), _tp(out.h0), out.h0_cap, _tp(out.c0),
+                                                _tp(out.h1), out.h1_cap, _tp(out.c1), _tp(out.status), _stream()))
+    return out
+
+
+def gather_windows_dev(src_t, start_t, win_len=250, out_t=None, ctx=None):
+    """out_t[w] = src_t[start_t[w] : start_t[w] + win_len] (flat float64 source, int64 device table): the selected
+    windows of packed signals as a stack (create_windows + np.linspace, cmp:65,77-80, for ragged recordings)."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert src_t.is_cuda and src_t.dtype == torch.float64 and src_t.is_contiguous() and start_t.dtype == torch.int64
+    n_win = int(start_t.numel())
+    if out_t is None:
+        out_t = torch.empty((n_win, win_len), dtype=torch.float64, device=src_t.device)
+    assert out_t.is_contiguous() and out_t.numel() >= n_win * win_len
+    ctx.check(ctx.lib.tda_gather_windows_dev(ctx.h, _tp(src_t), _tp(start_t), n_win, int(win_len), _tp(out_t), _stream()))
+    return out_t
 
 
 def takens_rips_dev(win_t, tau_t, out=None, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, h1_cap=DEFAULT_H1_CAP,

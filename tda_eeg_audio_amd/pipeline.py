@@ -57,12 +57,38 @@ class Workspace:
         self.fused = os.environ.get("TDA_FUSED_EEG", "1") != "0" and 33 <= n_ch <= 48
         self.dist = None if self.fused else torch.empty((n_win, n_ch, n_ch), **f64)
 
+    def view(self, seg_off):
+        """A Workspace over the first seg_off[-1] windows and len(seg_off) - 1 groups of THIS one's buffers, with segment
+        tables of its own (uploaded once, here): one buffer set sized by the largest shard of
+        recordings.RaggedRecordingPass serves every shard through one view per shard.  Views share every buffer, so only
+        one of them may be in flight at a time."""
+        import copy
+        import torch
+        seg_off = np.asarray(seg_off, np.int32)
+        n_win, n_seg = int(seg_off[-1]), len(seg_off) - 1
+        assert seg_off[0] == 0 and (np.diff(seg_off) >= 0).all() and n_win <= self.n_win and n_seg <= self.n_seg
+        v = copy.copy(self)
+        v.n_win, v.n_seg = n_win, n_seg
+        v.seg_off = torch.from_numpy(seg_off).to(self.device)
+        v.rec_id = torch.from_numpy(np.repeat(np.arange(n_seg), np.diff(seg_off)).astype(np.int64)).to(self.device)
+        v.first_idx = torch.from_numpy(seg_off[:-1].astype(np.int64)).to(self.device)
+        v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
+        v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
+        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1"):
+            setattr(v, name, getattr(self, name)[:n_win])
+        for name in ("tau_seg", "seg_flags", "flags_host", "result"):
+            setattr(v, name, getattr(self, name)[:n_seg])
+        v.dist = None if self.dist is None else self.dist[:n_win]
+        return v
 
-def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="auto", eeg_sliding=None):
+
+def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="auto", eeg_sliding=None, eeg_table=None):
     """One pass of the hot path over the batch.  eeg_win (n_win,47,250) f64, audio_win (n_win,250)
     f64, both resident in HBM.  Returns ws.result (n_seg, 48).
     eeg_sliding = (sig_t (n_rec, 47, L), win_len, step, sel_t): the EEG windows are read IN PLACE from band-passed
     recordings instead (window sel_t[i] = r * n_win_per_rec + k; eeg_win is ignored) -- recordings.RecordingPass.
+    eeg_table = (sig_t, start_t, ld_t, win_len): the EEG windows are read in place from packed band-passed recordings of
+    different lengths through a window table (engine.eeg_window_ragged_dev) -- recordings.RaggedRecordingPass.
     `timers`: optional dict of
     (start,end) torch.cuda.Event pairs per stage, recorded on the launch stream.
     retry="auto": every Rips call launches its widening passes (exact by itself).  retry="first": first passes
@@ -77,14 +103,14 @@ def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="
         ctx.set_retry_policy(ctx.RETRY_FIRST_PASS if retry == "first" else ctx.RETRY_ONE_STEP)
     ctx.set_h1_order(ctx.ORDER_DEFERRED)         # one finishing pass for the three diagram sets of the batch
     try:
-        return _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding)
+        return _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding, eeg_table)
     finally:
         ctx.set_h1_order(ctx.ORDER_IN_CALL)
         if retry != "auto":
             ctx.set_retry_policy(ctx.RETRY_AUTO)
 
 
-def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=None):
+def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=None, eeg_table=None):
     import torch
 
     def stage(name, fn):
@@ -104,7 +130,11 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     if ws.overlap:
         side.wait_stream(main)
     with torch.cuda.stream(side):
-        if eeg_sliding is not None:
+        if eeg_table is not None:
+            sig_t, start_t, ld_t, win_len = eeg_table
+            stage("eeg_window", lambda: engine.eeg_window_ragged_dev(sig_t, start_t, ld_t, win_len, out=ws.eeg,
+                                                                     n_ch=ws.eeg.h0_cap, ctx=ctx))
+        elif eeg_sliding is not None:
             sig_t, win_len, step, sel_t = eeg_sliding
             stage("eeg_window", lambda: engine.eeg_window_sliding_dev(sig_t, win_len, step, sel_t=sel_t, out=ws.eeg, ctx=ctx))
         elif ws.fused and eeg_win.shape[2] <= 256:

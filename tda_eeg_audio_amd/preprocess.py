@@ -111,7 +111,8 @@ def create_sliding_windows(data, window_size, overlap, fs):
 
 def bandpass_dev(x_t, lowcut, highcut, fs, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
     """apply_bandpass_filter (nb1:236-263) on device tensors: x_t (n_sig, n_samples) float64 -- every channel of every
-    recording of equal length in ONE launch; returns y_t (same shape).  work_t: optional (n_sig, n_samples + 2*edge)."""
+    recording of equal length in ONE launch (bandpass_bank_ragged_dev: different lengths); returns y_t (same shape).
+    work_t: optional (n_sig, n_samples + 2*edge)."""
     import torch
     ctx = ctx or get_ctx()
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous() and x_t.dim() == 2
@@ -133,7 +134,8 @@ def recordings_to_features(raw_t, fs, sel_t=None, n_sel_per_rec=None, freq_bands
                            overlap=OVERLAP_PERCENT, order=FILTER_ORDER, ctx=None):
     """The EEG half of the corpus from RAW recordings, on the GPU end to end (preprocess_file nb1:388-494 +
     process_file_graphs nb2:158-218 + the hot loop and aggregation of process_file_features v2:404-436):
-    raw_t (n_rec, n_ch, n_samples) float64 in HBM, recordings of equal length -> per band: zero-phase band-pass of
+    raw_t (n_rec, n_ch, n_samples) float64 in HBM, recordings of equal length (recordings_to_features_ragged takes
+    recordings of different lengths) -> per band: zero-phase band-pass of
     all n_rec * n_ch channels in one launch -> fused window kernel on the sliding windows read in place (the
     (n_win, n_ch, 250) stacks and the distance matrices never exist) -> H1 row order + extract_features -> mean / std
     over each recording's windows.  sel_t: optional int32 window list (r * n_win_per_rec + k, n_sel_per_rec per
@@ -223,7 +225,8 @@ def bandpass_bank_dev(x_t, bands, fs, order=FILTER_ORDER, y_t=None, work_t=None,
 
 
 def filtfilt_bank_dev(x_t, bas, y_t=None, work_t=None, ctx=None):
-    """scipy.signal.filtfilt for a bank of (b, a) pairs of equal length in one launch: x_t (n_sig, n_samples) -> y_t
+    """scipy.signal.filtfilt for a bank of (b, a) pairs on signals of equal length in one launch (filtfilt_bank_ragged_dev:
+    different lengths): x_t (n_sig, n_samples) -> y_t
     (n_filters, n_sig, n_samples) -- bandpass_filter (utils.py:66-74) of the audio envelope for all bands (cmp:63-64)."""
     import torch
     ctx = ctx or get_ctx()
@@ -245,6 +248,158 @@ def filtfilt_bank_dev(x_t, bas, y_t=None, work_t=None, ctx=None):
                                             edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return y_t
+
+
+# --------------------------------------------------------------------------------------------
+# ragged ("packed") recordings: one recording after the other, each at its own length
+# --------------------------------------------------------------------------------------------
+def pack_recordings(arrays):
+    """list of (n_ch, L_r) (or (L_r,)) float64 arrays -> (pinned flat float64 tensor, lengths int64): recording r is an
+    (n_ch, L_r) row-major block at element n_ch * off[r], off the exclusive prefix sum of the lengths -- the layout of
+    every ragged entry point (bandpass_bank_ragged_dev, recordings.RaggedRecordingPass)."""
+    import torch
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in arrays]
+    assert len({a.shape[:-1] for a in arrs}) <= 1, "all recordings need the same channel count"
+    lengths = np.array([a.shape[-1] for a in arrs], dtype=np.int64)
+    flat = torch.empty(int(sum(a.size for a in arrs)), dtype=torch.float64).pin_memory()
+    fv = flat.numpy()
+    o = 0
+    for a in arrs:
+        fv[o:o + a.size] = a.ravel()
+        o += a.size
+    return flat, lengths
+
+
+class RaggedTables:
+    """Lengths and offsets of packed signals: host int64 copies (`len_h`, `off_h`: exclusive prefix sum, n + 1 entries) and
+    the device tables the ragged kernels read (`len_t`, `off_t`), uploaded once."""
+
+    def __init__(self, lengths, device):
+        import torch
+        self.len_h = np.ascontiguousarray(lengths, dtype=np.int64)
+        self.off_h = np.concatenate([[0], np.cumsum(self.len_h)]).astype(np.int64)
+        self.n, self.total = len(self.len_h), int(self.off_h[-1])
+        self.len_t = torch.from_numpy(self.len_h).to(device)
+        self.off_t = torch.from_numpy(self.off_h).to(device)
+
+
+def _tables(lengths, device):
+    return lengths if isinstance(lengths, RaggedTables) else RaggedTables(lengths, device)
+
+
+def bandpass_bank_ragged_dev(x_t, lengths, bands, fs, n_ch=47, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
+    """apply_bandpass_filter (nb1:236-263) for ALL bands in one launch on RAGGED recordings: x_t flat float64 (packed,
+    recording r an (n_ch, L_r) block at n_ch * off[r]; see pack_recordings), lengths: L_r (numpy) or RaggedTables.
+    Returns y_t (n_bands, n_ch * sum(L)) in the same layout per band, every channel bit-identical to
+    scipy.signal.sosfiltfilt on that channel alone.  work_t: optional, n_bands * n_ch * (sum(L) + 2*edge*n_rec) elements."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
+    tb = _tables(lengths, x_t.device)
+    assert x_t.numel() >= n_ch * tb.total
+    plans = [_sos_plan(design_bandpass_filter(lo, hi, fs, order)) for lo, hi in bands]
+    nf, n_sec, edge = len(plans), plans[0][0].shape[0], plans[0][2]
+    assert all(p[0].shape[0] == n_sec and p[2] == edge for p in plans), "the filters of a bank share their structure"
+    if tb.n and int(tb.len_h.min()) <= edge:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
+    sos = np.ascontiguousarray(np.stack([p[0] for p in plans])); zi = np.ascontiguousarray(np.stack([p[1] for p in plans]))
+    if y_t is None:
+        y_t = torch.empty((nf, n_ch * tb.total), dtype=torch.float64, device=x_t.device)
+    n_work = nf * n_ch * (tb.total + 2 * edge * tb.n)
+    if work_t is None or work_t.numel() < n_work:
+        work_t = torch.empty(n_work, dtype=torch.float64, device=x_t.device)
+    ctx.check(ctx.lib.tda_sosfiltfilt_bank_ragged_dev(ctx.h, C.c_void_p(x_t.data_ptr()), tb.n, n_ch, C.c_void_p(tb.len_t.data_ptr()),
+                                                      C.c_void_p(tb.off_t.data_ptr()), ptr(tb.len_h), ptr(sos), ptr(zi), nf, n_sec,
+                                                      edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y_t
+
+
+def filtfilt_bank_ragged_dev(x_t, lengths, bas, y_t=None, work_t=None, ctx=None):
+    """scipy.signal.filtfilt for a bank of (b, a) pairs (ntaps <= 9) in one launch on RAGGED signals: x_t flat float64,
+    signal s = L_s samples at off[s] (packed; lengths numpy or RaggedTables) -> y_t (n_filters, sum(L)) in the same
+    layout -- bandpass_filter (utils.py:66-74, cmp:63-64) of the envelopes of recordings of different lengths, each
+    bit-identical to scipy.signal.filtfilt on that signal alone.  work_t: optional, n_filters * (sum(L) + 2*edge*n)."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
+    tb = _tables(lengths, x_t.device)
+    assert x_t.numel() >= tb.total
+    ntaps = max(max(len(b), len(a)) for b, a in bas)
+    B = np.zeros((len(bas), ntaps)); A = np.zeros((len(bas), ntaps)); Z = np.zeros((len(bas), ntaps - 1))
+    for f, (b, a) in enumerate(bas):
+        B[f, :len(b)] = b; A[f, :len(a)] = a
+        Z[f] = signal.lfilter_zi(B[f], A[f])
+    edge = 3 * ntaps
+    if tb.n and int(tb.len_h.min()) <= edge:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
+    if y_t is None:
+        y_t = torch.empty((len(bas), tb.total), dtype=torch.float64, device=x_t.device)
+    n_work = len(bas) * (tb.total + 2 * edge * tb.n)
+    if work_t is None or work_t.numel() < n_work:
+        work_t = torch.empty(n_work, dtype=torch.float64, device=x_t.device)
+    ctx.check(ctx.lib.tda_filtfilt_bank_ragged_dev(ctx.h, C.c_void_p(x_t.data_ptr()), tb.n, C.c_void_p(tb.len_t.data_ptr()),
+                                                   C.c_void_p(tb.off_t.data_ptr()), ptr(tb.len_h), ptr(B), ptr(A), ptr(Z), len(bas),
+                                                   ntaps, edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y_t
+
+
+def n_windows(n_samples, window_size=WINDOW_SIZE_SEC, overlap=OVERLAP_PERCENT, fs=250):
+    """Sliding windows of a recording of n_samples (scalar or array): nb1:341, 0 below one window."""
+    win = int(window_size * fs)
+    step = int(win * (1 - overlap))
+    n = np.asarray(n_samples, dtype=np.int64)
+    return np.where(n >= win, (n - win) // step + 1, 0)
+
+
+def recordings_to_features_ragged(raw_packed_t, lengths, fs, sel=None, n_ch=47, freq_bands=FREQ_BANDS,
+                                  window_size=WINDOW_SIZE_SEC, overlap=OVERLAP_PERCENT, order=FILTER_ORDER, ctx=None):
+    """recordings_to_features for RAGGED recordings: raw_packed_t flat float64 in HBM (recording r an (n_ch, L_r) block
+    at n_ch * off[r]; pack_recordings), lengths L_r.  Per recording, the sliding windows at its own length (nb1:341), or
+    sel[r] (optional list of per-recording window-index arrays, sizes may differ -- the drivers' selection).  All bands
+    band-passed in ONE launch, then per band the fused window kernel on a window table (no stacks, no matrices), H1
+    order + extract_features, mean / std per recording.  Returns (n_rec, 44 * n_bands) float64 tensor -- NaN rows for
+    recordings without a window -- and the status words of the windows (recording-major, in table order), OR-ed over
+    the bands.  Each row equals recordings_to_features on that recording alone, bit for bit."""
+    import torch
+    from . import engine
+    ctx = ctx or get_ctx()
+    dev = raw_packed_t.device
+    tb = _tables(lengths, dev)
+    win = int(window_size * fs)
+    step = int(win * (1 - overlap))
+    per_rec = n_windows(tb.len_h, window_size, overlap, fs)
+    picks = [np.arange(int(n)) for n in per_rec] if sel is None else [np.asarray(s, dtype=np.int64).ravel() for s in sel]
+    assert len(picks) == tb.n and all(((p >= 0) & (p < n)).all() for p, n in zip(picks, per_rec)), "window index out of range"
+    k = np.array([len(p) for p in picks], dtype=np.int64)
+    live = np.flatnonzero(k > 0)
+    n_out = int(k.sum())
+    nb = len(freq_bands)
+    X = torch.full((tb.n, nb, 44), float("nan"), dtype=torch.float64, device=dev)
+    status = torch.zeros(n_out, dtype=torch.int32, device=dev)
+    if n_out == 0:
+        return X.view(tb.n, nb * 44), status
+    y = bandpass_bank_ragged_dev(raw_packed_t, tb, list(freq_bands.values()), fs, n_ch=n_ch, order=order, ctx=ctx)
+    band_len = n_ch * tb.total
+    start0 = np.concatenate([n_ch * tb.off_h[r] + picks[r] * step for r in live]).astype(np.int64)
+    ld = torch.from_numpy(np.repeat(tb.len_h[live], k[live]).astype(np.int64)).to(dev)
+    seg = torch.from_numpy(np.concatenate([[0], np.cumsum(k[live])]).astype(np.int32)).to(dev)
+    live_t = torch.from_numpy(live).to(dev)
+    dgm = engine.DeviceDiagrams(n_out, n_ch, engine.DEFAULT_H1_CAP, dev)
+    fe0 = torch.empty((n_out, 11), dtype=torch.float64, device=dev)
+    fe1 = torch.empty_like(fe0)
+    ctx.set_h1_order(ctx.ORDER_DEFERRED)
+    try:
+        for bi in range(nb):
+            start = torch.from_numpy(start0 + bi * band_len).to(dev)
+            engine.eeg_window_ragged_dev(y, start, ld, win, out=dgm, ctx=ctx)
+            engine.diagram_finish_dev([(dgm.h0, dgm.c0, False, fe0), (dgm.h1, dgm.c1, True, fe1)], ctx=ctx)
+            X[:, bi].index_copy_(0, live_t, engine.aggregate_dev(fe0, fe1, seg, ctx=ctx))
+            status |= dgm.status                 # (the next band overwrites the words)
+    finally:
+        ctx.set_h1_order(ctx.ORDER_IN_CALL)
+    return X.view(tb.n, nb * 44), status
 
 
 def eeg_to_distances(eeg, fs, freq_bands=FREQ_BANDS, window_size=WINDOW_SIZE_SEC, overlap=OVERLAP_PERCENT,

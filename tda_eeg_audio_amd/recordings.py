@@ -4,7 +4,8 @@ MEMORY: raw EEG (n_rec, 47, L) float64 and the 250 Hz audio envelope (n_rec, L) 
 resampled audio, utils.py:56-63 -- preprocess.compute_envelope) in pinned host buffers go in, the (n_rec, 5, 48) result
 rows [W_H0, W_H1, tau, n_windows, 44 aggregated EEG features] come back to the host.
 
-Per shard of recordings (recordings of equal length):
+Per shard of recordings (RecordingPass: recordings of equal length; RaggedRecordingPass below takes recordings of
+different lengths, packed back to back -- preprocess.pack_recordings):
     H2D of the shard (1.73 MB of EEG per recording instead of the 33 MB of its five window stacks)
     zero-phase band-pass of all 47 x n_rec EEG channels, all five bands in ONE launch   (nb1:236-263)
     zero-phase band-pass of the n_rec envelopes, all five bands in one launch, beside it  (utils.py:66-74, cmp:64)
@@ -20,7 +21,7 @@ The rows equal pipeline.run_step on the stacked windows of the same band-passed 
 """
 import numpy as np
 
-from . import pipeline, preprocess
+from . import engine, pipeline, preprocess
 from ._lib import get_ctx
 
 MAX_WINDOWS = 15            # cmp:39
@@ -151,6 +152,224 @@ class RecordingPass:
                 fl.copy_(st["ws"].seg_flags, non_blocking=True)
                 st["main"].synchronize()
         # (groups of the idle rows of a short last shard repeat real recordings: their flags say nothing new)
+        if bool(fl.any()):
+            from ._lib import TdaError
+            raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")
+
+
+# ------------------------------------------------------------------------------------------------------------
+# recordings of DIFFERENT lengths (the study's corpus: 46 distinct lengths, 2,663 .. 5,741 samples)
+# ------------------------------------------------------------------------------------------------------------
+DEFAULT_SHARD_SAMPLES = 1_100_000      # EEG samples per shard (~236 recordings of the corpus; 52 MB of raw EEG)
+
+
+class RaggedPlan:
+    """The host plan of RaggedRecordingPass, numpy only (tests/test_ragged_plan.py checks it without a GPU).
+    Per recording r (cmp:70-80 at its own length): n_win[r] = min(per_rec(L_r), per_rec(Le_r)) (nb1:341 for the EEG and
+    for the envelope), picks[r] = the selected windows, k[r] = len(picks[r]).  shards: contiguous ranges [r0, r1) of
+    recordings closed at a budget of EEG samples (a shard exceeds it only when it holds a single recording).  Per shard:
+      eeg_off / env_off  exclusive prefix sums of L / Le within the shard (the packed layout of its upload)
+      live               local indices of the recordings with k > 0 (the others get a NaN row, n_windows = 0)
+      seg_off            groups of k windows, band-major: group (b, j) = band b of live recording j
+      eeg_start, eeg_ld  window table of the band-passed EEG (n_bands, n_ch * sum L): element offset of the first sample,
+                         row stride L_r
+      env_start          window table of the band-passed envelopes (n_bands, sum Le)."""
+
+    def __init__(self, eeg_lengths, env_lengths=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_ch=47, n_bands=5, fs=250,
+                 window_sec=1.0, overlap=0.75, max_windows=MAX_WINDOWS):
+        self.L = np.asarray(eeg_lengths, dtype=np.int64).ravel()
+        self.Le = self.L.copy() if env_lengths is None else np.asarray(env_lengths, dtype=np.int64).ravel()
+        assert self.L.shape == self.Le.shape
+        self.n_rec, self.n_ch, self.nb = len(self.L), int(n_ch), int(n_bands)
+        self.win = int(window_sec * fs)
+        self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
+        self.n_win = np.minimum(preprocess.n_windows(self.L, window_sec, overlap, fs),
+                                preprocess.n_windows(self.Le, window_sec, overlap, fs))          # cmp:71
+        self.picks = [select_windows(int(n), max_windows) for n in self.n_win]                  # cmp:77-80
+        self.k = np.array([len(p) for p in self.picks], dtype=np.int64)
+        self.empty = np.flatnonzero(self.k == 0)                                                 # the reference's None
+        self.shards = []
+        r0, acc = 0, 0
+        for r in range(self.n_rec):
+            if r > r0 and acc + self.L[r] > shard_samples:
+                self.shards.append((r0, r))
+                r0, acc = r, 0
+            acc += int(self.L[r])
+        if self.n_rec:
+            self.shards.append((r0, self.n_rec))
+        self.tables = [self._shard_tables(a, b) for a, b in self.shards]
+
+    def _shard_tables(self, r0, r1):
+        L, Le, k = self.L[r0:r1], self.Le[r0:r1], self.k[r0:r1]
+        eeg_off = np.concatenate([[0], np.cumsum(L)]).astype(np.int64)
+        env_off = np.concatenate([[0], np.cumsum(Le)]).astype(np.int64)
+        live = np.flatnonzero(k > 0)
+        kl = k[live]
+        seg_off = np.concatenate([[0], np.cumsum(np.tile(kl, self.nb))]).astype(np.int32)
+        # one band's window offsets, recording-major over the live recordings, then the bands behind each other
+        pick_off = np.concatenate([self.picks[r0 + j] * self.step for j in live]).astype(np.int64) if len(live) else \
+            np.zeros(0, np.int64)
+        e1 = self.n_ch * np.repeat(eeg_off[live], kl) + pick_off
+        a1 = np.repeat(env_off[live], kl) + pick_off
+        band = np.arange(self.nb, dtype=np.int64)[:, None]
+        return dict(eeg_off=eeg_off, env_off=env_off, live=live, seg_off=seg_off,
+                    eeg_start=(band * self.n_ch * eeg_off[-1] + e1[None, :]).ravel(),
+                    eeg_ld=np.tile(np.repeat(L[live], kl), self.nb).astype(np.int64),
+                    env_start=(band * env_off[-1] + a1[None, :]).ravel())
+
+
+class RaggedRecordingPass:
+    """RecordingPass for recordings of DIFFERENT lengths: raw EEG packed back to back (recording r an (n_ch, L_r) block at
+    n_ch * off[r]) and the 250 Hz envelopes packed the same way with their own lengths (Le_r, default L_r), both in pinned
+    host memory (preprocess.pack_recordings).  `run` returns the (n_rec, n_bands, 48) rows of process_recording
+    (cmp:45-124) at every recording's own length, in the caller's order; a recording without a window (the reference
+    returns None) gets a NaN row with n_windows = 0 and is listed in `empty`.
+    Planned once at construction (RaggedPlan): shards are contiguous ranges of recordings (one H2D copy per tensor and
+    shard), the buffer sets are sized by the largest shard, and every shard's window tables and segment table are
+    uploaded once.  Per shard: the ragged SOS bank of all EEG channels and the ragged (b, a) bank of the envelopes (one
+    launch each), the selected envelope windows gathered into the stack the tau / Takens kernels read, ONE run_step over
+    the (band, recording) groups with the EEG windows read in place through the window table, rows scattered to the
+    recordings.  Upload / compute / download overlap and verify-then-publish as in RecordingPass."""
+
+    def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
+                 n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75):
+        import torch
+        from scipy import signal
+        self.ctx = ctx or get_ctx()
+        self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n_ch, self.fs = n_ch, fs
+        self.bands = list(dict(bands).values())
+        nb = len(self.bands)
+        self.plan = P = RaggedPlan(eeg_lengths, env_lengths, shard_samples, n_ch, nb, fs, window_sec, overlap, max_windows)
+        self.win, self.step, self.n_rec, self.empty = P.win, P.step, P.n_rec, P.empty
+        nyq = fs / 2                                                   # utils.py:66-74
+        self.bas = [signal.butter(4, [max(lo / nyq, 0.001), min(hi / nyq, 0.999)], btype="band") for lo, hi in self.bands]
+        self.edge = preprocess._sos_plan(preprocess.design_bandpass_filter(*self.bands[0], fs, preprocess.FILTER_ORDER))[2]
+        self.edge_a = 3 * max(max(len(b), len(a)) for b, a in self.bas)
+        short = np.flatnonzero((P.L <= self.edge) | (P.Le <= self.edge_a))
+        if len(short):
+            raise ValueError(f"recording(s) {short[:8].tolist()} not longer than the filters' pad length "
+                             f"({self.edge} EEG / {self.edge_a} envelope samples)")
+        self.eeg_off = np.concatenate([[0], np.cumsum(P.L)]).astype(np.int64)
+        self.env_off = np.concatenate([[0], np.cumsum(P.Le)]).astype(np.int64)
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        # per shard, uploaded once: length tables of the two banks, window tables, segment tables (a Workspace view)
+        self.shards = []
+        for (r0, r1), t in zip(P.shards, P.tables):
+            self.shards.append(dict(
+                r0=r0, r1=r1, n=r1 - r0, T=int(t["eeg_off"][-1]), Te=int(t["env_off"][-1]), seg_off=t["seg_off"],
+                eeg_tb=preprocess.RaggedTables(P.L[r0:r1], self.dev), env_tb=preprocess.RaggedTables(P.Le[r0:r1], self.dev),
+                eeg_start=torch.from_numpy(t["eeg_start"]).to(**i64), eeg_ld=torch.from_numpy(t["eeg_ld"]).to(**i64),
+                env_start=torch.from_numpy(t["env_start"]).to(**i64), live=torch.from_numpy(t["live"]).to(**i64),
+                n_live=len(t["live"]), n_win=int(t["seg_off"][-1])))
+        S = max(d["n"] for d in self.shards) if self.shards else 1
+        T = max((d["T"] for d in self.shards), default=1)
+        Te = max((d["Te"] for d in self.shards), default=1)
+        n_win = max((d["n_win"] for d in self.shards), default=0)
+        n_seg = max((nb * d["n_live"] for d in self.shards), default=0)
+        self.n_sets = int(n_sets)
+        self.set = []
+        for _ in range(self.n_sets):
+            # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
+            ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
+                                    n_ch=n_ch)
+            self.set.append(dict(
+                raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
+                y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
+                work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
+                aw=torch.empty((max(n_win, 1), self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
+                ws=ws, views=[ws.view(d["seg_off"]) for d in self.shards],
+                main=torch.cuda.Stream(device=self.dev), side=torch.cuda.Stream(device=self.dev),
+                up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event()))
+        self.copy = torch.cuda.Stream(device=self.dev)
+        self.back = torch.cuda.Stream(device=self.dev)
+        self.repairs = 0
+
+    def _rips_step(self, st, i, retry):
+        d = self.shards[i]
+        return pipeline.run_step(None, st["aw"][:d["n_win"]], st["views"][i], ctx=self.ctx, max_lag=self.win // 2, retry=retry,
+                                 eeg_table=(st["y"], d["eeg_start"], d["eeg_ld"], self.win))
+
+    def _rows(self, st, i, res):
+        """(n_bands * n_live, 48) band-major -> the shard's rows; recordings without a window: NaN, n_windows = 0."""
+        d = self.shards[i]
+        rows = st["rows"][:d["n"]]
+        if d["n_live"] < d["n"]:
+            rows.fill_(float("nan"))
+            rows[:, :, 3] = 0.0
+        if d["n_live"]:
+            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], pipeline.RESULT_COLS).transpose(0, 1))
+
+    def _shard_step(self, st, i):
+        import torch
+        ctx, d, nb = self.ctx, self.shards[i], len(self.bands)
+        if d["n_win"] == 0:                                            # no recording of the shard has a window
+            self._rows(st, i, None)
+            return
+        st["side"].wait_stream(st["main"])
+        with torch.cuda.stream(st["side"]):
+            preprocess.filtfilt_bank_ragged_dev(st["env"], d["env_tb"], self.bas, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
+            engine.gather_windows_dev(st["ya"], d["env_start"], self.win, out_t=st["aw"], ctx=ctx)
+        preprocess.bandpass_bank_ragged_dev(st["raw"], d["eeg_tb"], self.bands, self.fs, n_ch=self.n_ch, y_t=st["y"],
+                                            work_t=st["work"], ctx=ctx)
+        st["main"].wait_stream(st["side"])
+        self._rows(st, i, self._rips_step(st, i, "one"))
+
+    def run(self, raw_packed_h, env_packed_h, rows_h=None):
+        """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
+        (n_rec, n_bands, 48), pinned, complete when the call returns."""
+        import torch
+        assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and env_packed_h.numel() == self.env_off[-1]
+        nb = len(self.bands)
+        if rows_h is None:
+            rows_h = torch.empty((self.n_rec, nb, pipeline.RESULT_COLS), dtype=torch.float64).pin_memory()
+        raw_f, env_f = raw_packed_h.view(-1), env_packed_h.view(-1)
+        pend = []
+        for i, d in enumerate(self.shards):
+            st = self.set[i % self.n_sets]
+            r0, r1 = d["r0"], d["r1"]
+            with torch.cuda.stream(self.copy):
+                if i >= self.n_sets:                # the shard before in this buffer set has read it and its rows are out
+                    self.copy.wait_event(st["done"])
+                    self.copy.wait_event(st["down"])
+                e0, e1 = self.n_ch * int(self.eeg_off[r0]), self.n_ch * int(self.eeg_off[r1])
+                st["raw"][:e1 - e0].copy_(raw_f[e0:e1], non_blocking=True)
+                a0, a1 = int(self.env_off[r0]), int(self.env_off[r1])
+                st["env"][:a1 - a0].copy_(env_f[a0:a1], non_blocking=True)
+                st["up"].record(self.copy)
+            with torch.cuda.stream(st["main"]):
+                st["main"].wait_event(st["up"])
+                self._shard_step(st, i)
+                st["done"].record(st["main"])
+            with torch.cuda.stream(self.back):
+                self.back.wait_event(st["done"])
+                rows_h[r0:r1].copy_(st["rows"][:d["n"]], non_blocking=True)
+                st["down"].record(self.back)
+            pend.append(i)
+            if len(pend) >= self.n_sets:
+                self._verify(pend.pop(0), rows_h)
+        while pend:
+            self._verify(pend.pop(0), rows_h)
+        self.back.synchronize()
+        return rows_h
+
+    def _verify(self, i, rows_h):
+        """As RecordingPass._verify: a shard that left a class-overflow flag is run again with the full ladder, and its rows
+        replace the ones already copied; any flag still left withholds the rows."""
+        import torch
+        st, d = self.set[i % self.n_sets], self.shards[i]
+        st["down"].synchronize()
+        if d["n_win"] == 0:
+            return
+        fl = st["views"][i].flags_host
+        if bool((fl & 2).any()):
+            self.repairs += 1
+            with torch.cuda.stream(st["main"]):
+                self._rows(st, i, self._rips_step(st, i, "auto"))
+                rows_h[d["r0"]:d["r1"]].copy_(st["rows"][:d["n"]])
+                fl.copy_(st["views"][i].seg_flags, non_blocking=True)
+                st["main"].synchronize()
         if bool(fl.any()):
             from ._lib import TdaError
             raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")

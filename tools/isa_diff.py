@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""
+tools/isa_diff.py -- are the gfx950 kernels of csrc/ instruction for instruction what they were at a git revision?
+    python3 tools/isa_diff.py [--rev HEAD] [--files filters rips] [--match 'sos_pipe_kernel|ba_pipe_kernel|eeg_window_kernel']
+Compiles each csrc/<file>.hip device-only (the Makefile's flags) from the working tree and from `git show REV:...`,
+disassembles both code objects and compares every kernel whose mangled name matches, line by line.  Addresses are
+dropped, and so is the literal of the s_add_u32 / s_addc_u32 pair after an s_getpc_b64 (PC-relative offsets to constant
+data, which move whenever a kernel is added anywhere in the file).  No GPU needed.
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tda_eeg_audio_amd", "csrc")
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden"]
+
+
+def disasm(src_dir, name, tmp, tag):
+    co, elf = os.path.join(tmp, f"{tag}_{name}.co"), os.path.join(tmp, f"{tag}_{name}.elf")
+    subprocess.check_call([f"{ROCM}/bin/hipcc", "--offload-arch=gfx950", *FLAGS, "--cuda-device-only", "-c",
+                           os.path.join(src_dir, f"{name}.hip"), "-o", co], stderr=subprocess.DEVNULL)
+    subprocess.check_call([f"{ROCM}/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", f"--input={co}",
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={elf}"])
+    text = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", elf]).decode()
+    funcs, cur, after_pc = {}, None, 0
+    for line in text.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.*)>:", line)
+        if m:
+            cur = funcs.setdefault(m.group(1), []); after_pc = 0; continue
+        ins = line.split("//")[0].strip()
+        if cur is None or not ins or ins == "...":
+            continue
+        if after_pc and re.match(r"s_addc?_u32 ", ins):
+            ins = re.sub(r"0x[0-9a-f]+$", "<pcrel>", ins); after_pc -= 1
+        else:
+            after_pc = 2 if ins.startswith("s_getpc_b64") else 0
+        cur.append(ins)
+    return funcs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("--files", nargs="+", default=["filters", "rips"])
+    ap.add_argument("--match", default=r"sos_pipe_kernel|ba_pipe_kernel|eeg_window_kernel")
+    a = ap.parse_args()
+    pat, bad = re.compile(a.match), 0
+    with tempfile.TemporaryDirectory() as tmp:
+        old_dir = os.path.join(tmp, "old")
+        os.makedirs(old_dir)
+        for f in os.listdir(CSRC):                       # the revision's sources (headers included)
+            if f.endswith((".hip", ".h")):
+                rel = os.path.relpath(os.path.join(CSRC, f), ROOT)
+                r = subprocess.run(["git", "show", f"{a.rev}:{rel}"], cwd=ROOT, capture_output=True)
+                if r.returncode == 0:
+                    open(os.path.join(old_dir, f), "wb").write(r.stdout)
+        inc = os.path.join(tmp, "include")              # (csrc includes ../../include/tdaeeg.h)
+        os.makedirs(inc)
+        open(os.path.join(inc, "tdaeeg.h"), "wb").write(subprocess.check_output(["git", "show", f"{a.rev}:include/tdaeeg.h"], cwd=ROOT))
+        old_csrc = os.path.join(tmp, "x", "y")
+        os.makedirs(os.path.dirname(old_csrc))
+        os.rename(old_dir, old_csrc)
+        for name in a.files:
+            old, new = disasm(old_csrc, name, tmp, "old"), disasm(CSRC, name, tmp, "new")
+            for k in sorted(old):
+                if not pat.search(k):
+                    continue
+                same = new.get(k) == old[k]
+                bad += not same
+                print(f"{'same' if same else 'DIFFERENT' if k in new else 'MISSING'}  {len(old[k]):6d} instructions  {k}")
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
