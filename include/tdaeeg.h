@@ -285,6 +285,25 @@ tda_status tda_upfirdn(tda_ctx* ctx, const double* x, long long n_in, const doub
 tda_status tda_hilbert_envelope_dev(tda_ctx* ctx, const double* x, int n, const double* g, double* env,
                                     void* stream);
 tda_status tda_hilbert_envelope(tda_ctx* ctx, const double* x, int n, const double* g, double* env);
+/* Audio front end for RAGGED signals: every signal of a shard in one launch, signals packed back to back (signal s has
+ * len[s] samples at element off[s], off the exclusive prefix sum of len; len, off: device int64; len_host: the same
+ * lengths on the host, checked here).  float64, agreement with scipy to rounding, not bit-identical.
+ * tda_resample_poly_ragged_dev replaces scipy.signal.resample_poly(audio, up, down) of resample_audio
+ * (scripts/utils.py:77-79) for every signal: hp (up, n_phase_taps) device, the polyphase table hp[p][q] = h[p + up*q] of
+ * the host-designed filter (as for tda_upfirdn; zero past the end of h -- one table serves every length, see
+ * preprocess.AudioPlan); signal s gives ceil(len[s]*up/down) outputs at y + out_off[s] (out_off: device int64).
+ * up <= 8.  Geometry that makes no sense (up, down, n_phase_taps < 1, n_pre_remove < 0, a length < 1) is
+ * TDA_ERR_INVALID.
+ * tda_hilbert_envelope_ragged_dev replaces np.abs(scipy.signal.hilbert(s)) (utils.py:58-59) for every signal: g
+ * device, the table g_N = imag(ifft(h_hilbert)) of signal s's length at g + g_off[s] (g_off: device int64; signals of
+ * one length may share a table); env in the layout of x.  Lengths in [1, 8192]. */
+tda_status tda_resample_poly_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len,
+                                        const long long* off, const long long* len_host, const long long* out_off,
+                                        const double* hp, int n_phase_taps, int up, int down, int n_pre_remove,
+                                        double* y, void* stream);
+tda_status tda_hilbert_envelope_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len,
+                                           const long long* off, const long long* len_host, const double* g,
+                                           const long long* g_off, double* env, void* stream);
 
 /* ---- delay from the first zero crossing of the autocorrelation ---------------
  * replaces compute_tau (scripts/utils.py:92-104). max_lag < 0 = None (len/4).         */

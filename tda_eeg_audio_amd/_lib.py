@@ -67,6 +67,8 @@ SYMBOLS = {
     "tda_upfirdn": (_I, [c_vp, c_vp, C.c_longlong, c_vp, _I, _I, _I, C.c_longlong, C.c_longlong, c_vp]),
     "tda_hilbert_envelope_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_hilbert_envelope": (_I, [c_vp, c_vp, _I, c_vp, c_vp]),
+    "tda_resample_poly_ragged_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp]),
+    "tda_hilbert_envelope_ragged_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_tau_batch_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, c_vp]),
     "tda_tau_segments_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
     "tda_recording_rows_dev": (_I, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),

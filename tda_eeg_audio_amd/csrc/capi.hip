@@ -288,6 +288,27 @@ tda_status tda_hilbert_envelope_dev(tda_ctx* ctx, const double* x, int n, const 
     return launch_hilbert_env(ctx, x, n, g, env, (hipStream_t)stream);
 }
 
+tda_status tda_resample_poly_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len, const long long* off,
+                                        const long long* len_host, const long long* out_off, const double* hp,
+                                        int n_phase_taps, int up, int down, int n_pre_remove, double* y, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_sig);
+    if (n_sig) { CHECK_PTR(ctx, x); CHECK_PTR(ctx, len); CHECK_PTR(ctx, off); CHECK_PTR(ctx, len_host);
+                 CHECK_PTR(ctx, out_off); CHECK_PTR(ctx, hp); CHECK_PTR(ctx, y); }
+    return launch_resample_poly_ragged(ctx, x, n_sig, len, off, len_host, out_off, hp, n_phase_taps, up, down, n_pre_remove,
+                                       y, (hipStream_t)stream);
+}
+
+tda_status tda_hilbert_envelope_ragged_dev(tda_ctx* ctx, const double* x, int n_sig, const long long* len,
+                                           const long long* off, const long long* len_host, const double* g,
+                                           const long long* g_off, double* env, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_sig);
+    if (n_sig) { CHECK_PTR(ctx, x); CHECK_PTR(ctx, len); CHECK_PTR(ctx, off); CHECK_PTR(ctx, len_host);
+                 CHECK_PTR(ctx, g); CHECK_PTR(ctx, g_off); CHECK_PTR(ctx, env); }
+    return launch_hilbert_env_ragged(ctx, x, n_sig, len, off, len_host, g, g_off, env, (hipStream_t)stream);
+}
+
 tda_status tda_tau_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int* tau, void* stream)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);

@@ -203,6 +203,10 @@ tda_status launch_gather_windows(tda_ctx*, const double*, const long long*, int,
 tda_status launch_eeg_ragged(tda_ctx*, const double*, const long long*, const long long*, int, int, int, double, double*,
                              double*, double*, int, int*, double*, int, int*, int*, hipStream_t);
 tda_status launch_hilbert_env(tda_ctx*, const double*, int, const double*, double*, hipStream_t);
+tda_status launch_resample_poly_ragged(tda_ctx*, const double*, int, const long long*, const long long*, const long long*,
+                                       const long long*, const double*, int, int, int, int, double*, hipStream_t);
+tda_status launch_hilbert_env_ragged(tda_ctx*, const double*, int, const long long*, const long long*, const long long*,
+                                     const double*, const long long*, double*, hipStream_t);
 tda_status launch_tau(tda_ctx*, const double*, int, int, int, int*, hipStream_t);
 tda_status launch_tau_segments(tda_ctx*, const double*, const int*, int, int, int, int*, int*, hipStream_t);
 tda_status launch_recording_rows(tda_ctx*, const double*, const double*, const int*, const double*, const double*, const int*,

@@ -804,3 +804,177 @@ tda_status launch_hilbert_env(tda_ctx* ctx, const double* x, int n, const double
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Audio front end for RAGGED signals (packed back to back, len / off int64 as in ba_pipe_ragged_kernel): every signal
+// of a shard in ONE launch.  Sums are reordered against upfirdn_kernel / hilbert_env_kernel (fma, lanes across taps,
+// register blocking); the bar is scipy to rounding, as for the per-signal kernels.
+// ---------------------------------------------------------------------------------------------------
+
+// resample_poly_ragged_kernel replaces scipy.signal.resample_poly(x, up, down) (utils.py:77-79) for every signal:
+//   y[j] = sum_q hp[p][q] * x[base - q],  t = (j + n_pre_remove)*down, p = t mod up, base = t div up,
+// hp[p][q] = h[p + up*q] the polyphase table (nq taps per phase, zero past the end of h), x = 0 outside [0, n_in).
+// Outputs j and j + up share the phase and lie exactly `down` input samples apart, so a workgroup takes a tile of
+// up * RS_R consecutive outputs: wave d the outputs j0 + d + up*r (r < RS_R), its lanes across the taps (one read of
+// hp[p][q] feeds RS_R products), the x span of the tile staged once in LDS, a DPP tree over the lanes at the end.
+// grid (tiles of the longest signal, n_sig): tiles past a signal's end return at once.
+#define RS_R 4
+__global__ void __launch_bounds__(512)
+resample_poly_ragged_kernel(const double* __restrict__ x, const long long* __restrict__ len,
+                            const long long* __restrict__ off, const long long* __restrict__ out_off,
+                            const double* __restrict__ hp, int nq, int up, int down, int n_pre_remove,
+                            double* __restrict__ y)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double* xs = reinterpret_cast<double*>(smem);
+    const int s = blockIdx.y;
+    const long long n_in = len[s];
+    const long long n_out = (n_in * up + down - 1) / down;
+    const long long j0 = (long long)blockIdx.x * up * RS_R;
+    if (j0 >= n_out) return;                                // uniform over the workgroup
+    const long long xlo = ((j0 + n_pre_remove) * down) / up - (nq - 1);
+    const long long xhi = ((j0 + up * RS_R - 1 + n_pre_remove) * down) / up;   // the whole tile, even past n_out
+    const int span = (int)(xhi - xlo + 1);
+    const double* __restrict__ xr = x + off[s];
+    for (int k = threadIdx.x; k < span; k += blockDim.x) {
+        const long long i = xlo + k;
+        xs[k] = (i >= 0 && i < n_in) ? xr[i] : 0.0;
+    }
+    __syncthreads();
+    const int d = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long t = (j0 + d + n_pre_remove) * down;
+    const int p = (int)(t % up);
+    const int b = (int)(t / up - xlo);                      // LDS index of x[base] of output j0 + d
+    const double* __restrict__ h = hp + (size_t)p * nq;
+    double acc[RS_R];
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) acc[r] = 0.0;
+#pragma unroll 4
+    for (int q = lane; q < nq; q += 64) {
+        const double hq = h[q];
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) acc[r] = fma(hq, xs[b + r * down - q], acc[r]);
+    }
+    double* __restrict__ yr = y + out_off[s];
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) {
+        double v = acc[r];
+        TDA_DPP_REDUCE_F64(v, TDA_ADD_);
+        const long long j = j0 + d + (long long)up * r;
+        if (lane == 63 && j < n_out) yr[j] = v;
+    }
+}
+
+// hilbert_env_ragged_kernel replaces np.abs(scipy.signal.hilbert(s)) (utils.py:58-59) for every signal:
+//   env[n] = sqrt(x[n]^2 + (sum_k g[k] x[(n-k) mod N])^2),  g = imag(ifft(h_hilbert)) of length N (host table at g_off[s]).
+// One workgroup per signal.  Lane l takes the HB_R consecutive outputs n = HB_R*l + r and slides a window of HB_R
+// registers along the circularly extended signal: per k one new sample enters, g[k] (the same for every lane) feeds HB_R
+// products.  The extended signal xe[j] = x[j mod N] lies in LDS deinterleaved, sample at position P = j + pad in row
+// P mod HB_R, column P div HB_R (pad rounds N up to a multiple of HB_R), so the sample every lane loads at a step is one
+// contiguous row segment.  g streams through LDS in chunks of HB_KC (zero past N, so the k loop runs in steps of HB_R).
+// Block: 64 * ceil(ceil(N_max / HB_R) / 64) threads; LDS: HB_R * n_cols + HB_KC doubles, n_cols = threads + ceil(N_max / HB_R).
+#define HB_R 8
+#define HB_KC 1024
+__global__ void __launch_bounds__(1024)
+hilbert_env_ragged_kernel(const double* __restrict__ x, const long long* __restrict__ len, const long long* __restrict__ off,
+                          const double* __restrict__ g_tab, const long long* __restrict__ g_off, int n_cols,
+                          double* __restrict__ env)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    double* xs = reinterpret_cast<double*>(smem);          // HB_R rows of n_cols
+    double* gs = xs + HB_R * n_cols;                        // HB_KC
+    const int s = blockIdx.x;
+    const int N = (int)len[s];
+    const int kpad = (N + HB_R - 1) / HB_R * HB_R, pad = kpad - N;
+    const double* __restrict__ xr = x + off[s];
+    const double* __restrict__ g = g_tab + g_off[s];
+    for (int P = threadIdx.x; P < HB_R * n_cols; P += blockDim.x) {
+        const int j = P - pad;
+        xs[(P % HB_R) * n_cols + P / HB_R] = (j >= 0 && j < 2 * N) ? xr[j < N ? j : j - N] : 0.0;
+    }
+    const int l = threadIdx.x;
+    const bool active = HB_R * (l & ~63) < N;               // wave-uniform: the wave holds an output of this signal
+    double w[HB_R], acc[HB_R];
+    int col = l + kpad / HB_R;                              // column of position HB_R*l + kpad - k0
+    for (int kc = 0; kc < kpad; kc += HB_KC) {
+        __syncthreads();                                    // xs complete / the previous chunk of g consumed
+        for (int i = threadIdx.x; i < HB_KC; i += blockDim.x) gs[i] = kc + i < N ? g[kc + i] : 0.0;
+        __syncthreads();
+        if (!active) continue;
+        if (kc == 0) {
+#pragma unroll
+            for (int r = 0; r < HB_R; ++r) { w[r] = xs[r * n_cols + col]; acc[r] = 0.0; }
+        }
+        const int kend = kpad - kc < HB_KC ? kpad - kc : HB_KC;
+        for (int k0 = 0; k0 < kend; k0 += HB_R) {
+#pragma unroll
+            for (int u = 0; u < HB_R; ++u) {
+                const double gk = gs[k0 + u];
+                // register slot (r - u) mod HB_R holds the sample of output HB_R*l + r at this k
+#pragma unroll
+                for (int r = 0; r < HB_R; ++r) acc[r] = fma(gk, w[(r - u + HB_R) % HB_R], acc[r]);
+                w[HB_R - 1 - u] = xs[(HB_R - 1 - u) * n_cols + col - 1];   // the next sample (the oldest one leaves)
+            }
+            --col;
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int r = 0; r < HB_R; ++r) {
+        const int n = HB_R * l + r;
+        if (n < N) { const double re = xr[n]; env[off[s] + n] = sqrt(re * re + acc[r] * acc[r]); }
+    }
+}
+
+tda_status launch_resample_poly_ragged(tda_ctx* ctx, const double* x, int n_sig, const long long* len, const long long* off,
+                                       const long long* len_h, const long long* out_off, const double* hp, int nq, int up,
+                                       int down, int n_pre_remove, double* y, hipStream_t st)
+{
+    if (n_sig == 0) return TDA_OK;
+    if (up < 1 || down < 1 || nq < 1 || n_pre_remove < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "bad resampling geometry");
+    if (up > 8) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "the ragged resampler takes up <= 8 (one wave per phase)");
+    if (n_sig > 65535) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "the ragged resampler takes at most 65535 signals per launch");
+    long long n_out_max = 0;
+    for (int i = 0; i < n_sig; ++i) {
+        if (len_h[i] < 1 || len_h[i] > 0x7fffffffLL / up) TDA_FAIL(ctx, TDA_ERR_INVALID, "signal length must be in [1, 2^31/up)");
+        const long long n = (len_h[i] * up + down - 1) / down;
+        n_out_max = n > n_out_max ? n : n_out_max;
+    }
+    const long long span = nq + ((long long)(up * RS_R - 1) * down + up - 1) / up + 1;
+    const size_t lds = (size_t)span * sizeof(double);
+    if (lds > 160 * 1024) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "filter and tile do not fit the LDS of a CU");
+    if (lds > 64 * 1024)
+        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(resample_poly_ragged_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long long tiles = (n_out_max + up * RS_R - 1) / (up * RS_R);
+    if (tiles > 0x7fffffffLL) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "too many output tiles");
+    if (tiles == 0) return TDA_OK;
+    hipLaunchKernelGGL(resample_poly_ragged_kernel, dim3((unsigned)tiles, n_sig), dim3(64 * up), lds, st, x, len, off, out_off,
+                       hp, nq, up, down, n_pre_remove, y);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
+tda_status launch_hilbert_env_ragged(tda_ctx* ctx, const double* x, int n_sig, const long long* len, const long long* off,
+                                     const long long* len_h, const double* g, const long long* g_off, double* env,
+                                     hipStream_t st)
+{
+    if (n_sig == 0) return TDA_OK;
+    long long n_max = 0;
+    for (int i = 0; i < n_sig; ++i) {
+        if (len_h[i] < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "signal length must be >= 1");
+        n_max = len_h[i] > n_max ? len_h[i] : n_max;
+    }
+    if (n_max > 64 * 16 * HB_R) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "the ragged Hilbert envelope takes signals of <= 8192 samples");
+    const int cols = (int)((n_max + HB_R - 1) / HB_R);
+    const int threads = (cols + 63) / 64 * 64;
+    const int n_cols = threads + cols;
+    const size_t lds = (size_t)(HB_R * n_cols + HB_KC) * sizeof(double);
+    if (lds > 160 * 1024) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "signal does not fit the LDS of a CU");
+    if (lds > 64 * 1024)
+        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(hilbert_env_ragged_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(hilbert_env_ragged_kernel, dim3(n_sig), dim3(threads), lds, st, x, len, off, g, g_off, n_cols, env);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}

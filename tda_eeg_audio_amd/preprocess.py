@@ -471,17 +471,22 @@ def resample_audio(audio, fs_audio=FS_AUDIO, fs_target=FS_EEG, ctx=None):
     return y
 
 
-def hilbert_envelope(s, ctx=None):
-    """np.abs(scipy.signal.hilbert(s)) (utils.py:58-59)."""
-    ctx = ctx or get_ctx()
-    x = f64(np.asarray(s).ravel())
-    n = len(x)
+def _hilbert_g(n):
+    """g = imag(ifft(h)) of scipy.signal.hilbert at length n: the analytic signal's imaginary part is x (*) g."""
     hh = np.zeros(n)
     if n % 2 == 0:
         hh[0] = hh[n // 2] = 1; hh[1:n // 2] = 2
     else:
         hh[0] = 1; hh[1:(n + 1) // 2] = 2
-    g = np.ascontiguousarray(np.fft.ifft(hh).imag)
+    return np.ascontiguousarray(np.fft.ifft(hh).imag)
+
+
+def hilbert_envelope(s, ctx=None):
+    """np.abs(scipy.signal.hilbert(s)) (utils.py:58-59)."""
+    ctx = ctx or get_ctx()
+    x = f64(np.asarray(s).ravel())
+    n = len(x)
+    g = _hilbert_g(n)
     env = np.empty(n)
     ctx.check(ctx.lib.tda_hilbert_envelope(ctx.h, ptr(x), n, ptr(g), ptr(env)))
     return env
@@ -505,3 +510,146 @@ def audio_to_band_windows(audio, fs_audio=FS_AUDIO, freq_bands=FREQ_BANDS, ctx=N
     win = int(1.0 * FS_EEG)
     step = int(win * (1 - 0.75))
     return {name: create_windows(bandpass_filter(env, FS_EEG, lo, hi), win, step) for name, (lo, hi) in freq_bands.items()}
+
+
+# --------------------------------------------------------------------------------------------
+# audio front end for RAGGED recordings: every recording of a shard in one launch per stage
+# --------------------------------------------------------------------------------------------
+HILBERT_RAGGED_MAX = 8192       # longest signal of tda_hilbert_envelope_ragged_dev (it and its g table live in LDS)
+LOWPASS_ORDER = 4               # utils.py:60-62
+
+
+def envelope_lowpass(fs=FS_EEG):
+    """(b, a) of compute_envelope's low-pass (utils.py:60-62)."""
+    nyq = fs / 2
+    return signal.butter(LOWPASS_ORDER, min(50, nyq * 0.9) / nyq, btype="low")
+
+
+class HilbertTables:
+    """The g tables of hilbert_envelope for packed signals of lengths `lengths` (numpy only): one table per DISTINCT
+    length, packed back to back in `g`; `g_off[s]` is signal s's table."""
+
+    def __init__(self, lengths):
+        self.len_h = np.ascontiguousarray(lengths, dtype=np.int64)
+        self.lengths, inv = np.unique(self.len_h, return_inverse=True)
+        start = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.g = np.concatenate([_hilbert_g(int(n)) for n in self.lengths]) if len(self.lengths) else np.zeros(0)
+        self.g_off = np.ascontiguousarray(start[:-1][inv.ravel()], dtype=np.int64)
+
+
+class AudioPlan:
+    """The host plan of the ragged audio front end (envelopes_ragged_dev), numpy only: from the lengths La of packed
+    44.1 kHz recordings,
+      n_out, out_off   envelope lengths ceil(La * up / down) (resample_poly's) and their exclusive prefix sum
+      h, hp, nq        resample_poly's filter (_resample_plan) and its polyphase table hp[p, q] = h[p + up*q], nq taps per
+                       phase.  _resample_plan pads h with n_post_pad zeros that depend on the input length; zero taps
+                       only add exact +-0 products to a finite input, so the table padded for the longest input
+                       (n_in_max, default max(La)) serves every length.
+      n_pre_remove, up, down
+      hilbert          HilbertTables of the envelope lengths.
+    upload(device) adds the device tables (uploaded once): in_tb / out_tb (RaggedTables of La / n_out), hp_t, g_t, g_off_t."""
+
+    def __init__(self, audio_lengths, fs_audio=FS_AUDIO, fs=FS_EEG, n_in_max=None):
+        self.La = np.ascontiguousarray(audio_lengths, dtype=np.int64).ravel()
+        if len(self.La) and int(self.La.min()) < 1:
+            raise ValueError("every recording needs at least one audio sample")
+        if int(fs_audio) == int(fs):
+            raise ValueError("the ragged front end resamples: fs_audio must differ from fs")
+        n_max = max(int(self.La.max()) if len(self.La) else 1, int(n_in_max or 1))
+        self.h, self.up, self.down, self.n_pre_remove, _ = _resample_plan(n_max, int(fs), int(fs_audio))
+        self.nq = -(-len(self.h) // self.up)
+        hp = np.zeros(self.nq * self.up)
+        hp[:len(self.h)] = self.h
+        self.hp = np.ascontiguousarray(hp.reshape(self.nq, self.up).T)
+        n_out = self.La * self.up
+        self.n_out = n_out // self.down + (n_out % self.down > 0)
+        self.out_off = np.concatenate([[0], np.cumsum(self.n_out)]).astype(np.int64)
+        self.hilbert = HilbertTables(self.n_out)
+        self.device = None
+
+    def upload(self, device):
+        import torch
+        self.device = device
+        self.in_tb = RaggedTables(self.La, device)
+        self.out_tb = RaggedTables(self.n_out, device)
+        self.hp_t = torch.from_numpy(self.hp).to(device)
+        self.g_t = torch.from_numpy(self.hilbert.g).to(device)
+        self.g_off_t = torch.from_numpy(self.hilbert.g_off).to(device)
+        return self
+
+
+def _audio_plan(audio_lengths, device, fs_audio=FS_AUDIO, fs=FS_EEG):
+    if isinstance(audio_lengths, AudioPlan):
+        return audio_lengths if audio_lengths.device is not None else audio_lengths.upload(device)
+    return AudioPlan(audio_lengths, fs_audio, fs).upload(device)
+
+
+def resample_bank_ragged_dev(x_t, plan, y_t=None, ctx=None):
+    """resample_audio (utils.py:77-79, scipy.signal.resample_poly) of RAGGED signals in one launch: x_t flat float64,
+    signal s = plan.La[s] samples at plan.in_tb.off_h[s] (packed); plan: AudioPlan or the audio lengths.  Returns y_t
+    (sum n_out,) float64, signal s's output at plan.out_off[s]."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
+    P = _audio_plan(plan, x_t.device)
+    assert x_t.numel() >= P.in_tb.total
+    if y_t is None:
+        y_t = torch.empty(P.out_tb.total, dtype=torch.float64, device=x_t.device)
+    assert y_t.is_contiguous() and y_t.numel() >= P.out_tb.total
+    ctx.check(ctx.lib.tda_resample_poly_ragged_dev(ctx.h, C.c_void_p(x_t.data_ptr()), P.in_tb.n, C.c_void_p(P.in_tb.len_t.data_ptr()),
+                                                   C.c_void_p(P.in_tb.off_t.data_ptr()), ptr(P.in_tb.len_h),
+                                                   C.c_void_p(P.out_tb.off_t.data_ptr()), C.c_void_p(P.hp_t.data_ptr()), P.nq,
+                                                   P.up, P.down, P.n_pre_remove, C.c_void_p(y_t.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y_t
+
+
+def hilbert_envelope_ragged_dev(x_t, lengths, env_t=None, g_tables=None, ctx=None):
+    """hilbert_envelope (np.abs(scipy.signal.hilbert(s)), utils.py:58-59) of RAGGED signals in one launch: x_t flat float64,
+    signal s = L_s samples at off[s] (lengths numpy or RaggedTables; L_s <= HILBERT_RAGGED_MAX).  g_tables: optional
+    (g_t, g_off_t) device tables of HilbertTables(lengths) (built here otherwise).  Returns env_t in the layout of x_t."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
+    tb = _tables(lengths, x_t.device)
+    assert x_t.numel() >= tb.total
+    if g_tables is None:
+        ht = HilbertTables(tb.len_h)
+        g_tables = (torch.from_numpy(ht.g).to(x_t.device), torch.from_numpy(ht.g_off).to(x_t.device))
+    g_t, g_off_t = g_tables
+    if env_t is None:
+        env_t = torch.empty(tb.total, dtype=torch.float64, device=x_t.device)
+    assert env_t.is_contiguous() and env_t.numel() >= tb.total
+    ctx.check(ctx.lib.tda_hilbert_envelope_ragged_dev(ctx.h, C.c_void_p(x_t.data_ptr()), tb.n, C.c_void_p(tb.len_t.data_ptr()),
+                                                      C.c_void_p(tb.off_t.data_ptr()), ptr(tb.len_h), C.c_void_p(g_t.data_ptr()),
+                                                      C.c_void_p(g_off_t.data_ptr()), C.c_void_p(env_t.data_ptr()),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return env_t
+
+
+def envelopes_ragged_dev(audio_packed_t, audio_lengths, fs_audio=FS_AUDIO, fs=FS_EEG, out_t=None, work_t=None, ctx=None):
+    """compute_envelope(resample_audio(a), fs) (utils.py:56-63, 77-79; cmp:53-55) for every recording of a RAGGED set,
+    in HBM end to end: audio_packed_t flat float64 (recording s = La_s samples at the exclusive prefix sum of La;
+    pack_recordings of 1-D arrays), audio_lengths numpy or AudioPlan.  Three launches: the polyphase resampler, the
+    Hilbert envelope, the low-pass through filtfilt_bank_ragged_dev with one filter.  Returns (env_t flat float64, the
+    envelope lengths n_out, numpy int64), envelope s at the exclusive prefix sum of n_out.  Raises ValueError as scipy
+    does when an envelope is not longer than the low-pass pad length (15).  work_t: optional, 3 * sum(n_out) +
+    2 * 15 * n_rec elements."""
+    import torch
+    ctx = ctx or get_ctx()
+    P = _audio_plan(audio_lengths, audio_packed_t.device, fs_audio, fs)
+    b, a = envelope_lowpass(fs)
+    edge = 3 * max(len(a), len(b))
+    if P.out_tb.n and int(P.n_out.min()) <= edge:
+        raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
+    T, n = P.out_tb.total, P.out_tb.n
+    n_work = 3 * T + 2 * edge * n
+    if work_t is None or work_t.numel() < n_work:
+        work_t = torch.empty(n_work, dtype=torch.float64, device=audio_packed_t.device)
+    if out_t is None:
+        out_t = torch.empty(T, dtype=torch.float64, device=audio_packed_t.device)
+    rs, hil, fwork = work_t[:T], work_t[T:2 * T], work_t[2 * T:n_work]
+    resample_bank_ragged_dev(audio_packed_t, P, y_t=rs, ctx=ctx)
+    hilbert_envelope_ragged_dev(rs, P.out_tb, env_t=hil, g_tables=(P.g_t, P.g_off_t), ctx=ctx)
+    filtfilt_bank_ragged_dev(hil, P.out_tb, [(b, a)], y_t=out_t, work_t=fwork, ctx=ctx)
+    return out_t, P.n_out

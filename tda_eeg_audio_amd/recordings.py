@@ -161,13 +161,17 @@ class RecordingPass:
 # recordings of DIFFERENT lengths (the study's corpus: 46 distinct lengths, 2,663 .. 5,741 samples)
 # ------------------------------------------------------------------------------------------------------------
 DEFAULT_SHARD_SAMPLES = 1_100_000      # EEG samples per shard (~236 recordings of the corpus; 52 MB of raw EEG)
+DEFAULT_SHARD_BYTES = 1 << 30          # bytes uploaded per shard of RaggedAudioRecordingPass (EEG + 44.1 kHz audio: ~120
+                                       # recordings of the corpus, 11 shards)
 
 
 class RaggedPlan:
     """The host plan of RaggedRecordingPass, numpy only (tests/test_ragged_plan.py checks it without a GPU).
     Per recording r (cmp:70-80 at its own length): n_win[r] = min(per_rec(L_r), per_rec(Le_r)) (nb1:341 for the EEG and
     for the envelope), picks[r] = the selected windows, k[r] = len(picks[r]).  shards: contiguous ranges [r0, r1) of
-    recordings closed at a budget of EEG samples (a shard exceeds it only when it holds a single recording).  Per shard:
+    recordings closed at a budget of EEG samples (a shard exceeds it only when it holds a single recording) -- or, with
+    shard_bytes, at a budget of bytes uploaded: 8 * (n_ch * L_r + La_r) per recording, La the audio lengths
+    (RaggedAudioRecordingPass; default Le).  Per shard:
       eeg_off / env_off  exclusive prefix sums of L / Le within the shard (the packed layout of its upload)
       live               local indices of the recordings with k > 0 (the others get a NaN row, n_windows = 0)
       seg_off            groups of k windows, band-major: group (b, j) = band b of live recording j
@@ -176,7 +180,7 @@ class RaggedPlan:
       env_start          window table of the band-passed envelopes (n_bands, sum Le)."""
 
     def __init__(self, eeg_lengths, env_lengths=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_ch=47, n_bands=5, fs=250,
-                 window_sec=1.0, overlap=0.75, max_windows=MAX_WINDOWS):
+                 window_sec=1.0, overlap=0.75, max_windows=MAX_WINDOWS, shard_bytes=None, audio_lengths=None):
         self.L = np.asarray(eeg_lengths, dtype=np.int64).ravel()
         self.Le = self.L.copy() if env_lengths is None else np.asarray(env_lengths, dtype=np.int64).ravel()
         assert self.L.shape == self.Le.shape
@@ -188,13 +192,20 @@ class RaggedPlan:
         self.picks = [select_windows(int(n), max_windows) for n in self.n_win]                  # cmp:77-80
         self.k = np.array([len(p) for p in self.picks], dtype=np.int64)
         self.empty = np.flatnonzero(self.k == 0)                                                 # the reference's None
+        if shard_bytes is None:
+            cost, budget = self.L, shard_samples
+        else:
+            La = self.Le if audio_lengths is None else np.asarray(audio_lengths, dtype=np.int64).ravel()
+            assert La.shape == self.L.shape
+            cost, budget = 8 * (self.n_ch * self.L + La), shard_bytes
+        self.cost = cost
         self.shards = []
         r0, acc = 0, 0
         for r in range(self.n_rec):
-            if r > r0 and acc + self.L[r] > shard_samples:
+            if r > r0 and acc + cost[r] > budget:
                 self.shards.append((r0, r))
                 r0, acc = r, 0
-            acc += int(self.L[r])
+            acc += int(cost[r])
         if self.n_rec:
             self.shards.append((r0, self.n_rec))
         self.tables = [self._shard_tables(a, b) for a, b in self.shards]
@@ -232,7 +243,8 @@ class RaggedRecordingPass:
     recordings.  Upload / compute / download overlap and verify-then-publish as in RecordingPass."""
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
-                 n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75):
+                 n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
+                 plan=None):
         import torch
         from scipy import signal
         self.ctx = ctx or get_ctx()
@@ -240,7 +252,10 @@ class RaggedRecordingPass:
         self.n_ch, self.fs = n_ch, fs
         self.bands = list(dict(bands).values())
         nb = len(self.bands)
-        self.plan = P = RaggedPlan(eeg_lengths, env_lengths, shard_samples, n_ch, nb, fs, window_sec, overlap, max_windows)
+        # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
+        if plan is None:
+            plan = RaggedPlan(eeg_lengths, env_lengths, shard_samples, n_ch, nb, fs, window_sec, overlap, max_windows)
+        self.plan = P = plan
         self.win, self.step, self.n_rec, self.empty = P.win, P.step, P.n_rec, P.empty
         nyq = fs / 2                                                   # utils.py:66-74
         self.bas = [signal.butter(4, [max(lo / nyq, 0.001), min(hi / nyq, 0.999)], btype="band") for lo, hi in self.bands]
@@ -252,6 +267,7 @@ class RaggedRecordingPass:
                              f"({self.edge} EEG / {self.edge_a} envelope samples)")
         self.eeg_off = np.concatenate([[0], np.cumsum(P.L)]).astype(np.int64)
         self.env_off = np.concatenate([[0], np.cumsum(P.Le)]).astype(np.int64)
+        self.second = ("env", self.env_off)         # the per-recording host input uploaded beside the EEG: buffer, offsets
         i64 = dict(dtype=torch.int64, device=self.dev)
         f64 = dict(dtype=torch.float64, device=self.dev)
         # per shard, uploaded once: length tables of the two banks, window tables, segment tables (a Workspace view)
@@ -301,6 +317,9 @@ class RaggedRecordingPass:
         if d["n_live"]:
             rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], pipeline.RESULT_COLS).transpose(0, 1))
 
+    def _front_end(self, st, i):
+        """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""
+
     def _shard_step(self, st, i):
         import torch
         ctx, d, nb = self.ctx, self.shards[i], len(self.bands)
@@ -309,6 +328,7 @@ class RaggedRecordingPass:
             return
         st["side"].wait_stream(st["main"])
         with torch.cuda.stream(st["side"]):
+            self._front_end(st, i)
             preprocess.filtfilt_bank_ragged_dev(st["env"], d["env_tb"], self.bas, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
             engine.gather_windows_dev(st["ya"], d["env_start"], self.win, out_t=st["aw"], ctx=ctx)
         preprocess.bandpass_bank_ragged_dev(st["raw"], d["eeg_tb"], self.bands, self.fs, n_ch=self.n_ch, y_t=st["y"],
@@ -320,7 +340,8 @@ class RaggedRecordingPass:
         """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
         (n_rec, n_bands, 48), pinned, complete when the call returns."""
         import torch
-        assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and env_packed_h.numel() == self.env_off[-1]
+        key, sec_off = self.second
+        assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and env_packed_h.numel() == sec_off[-1]
         nb = len(self.bands)
         if rows_h is None:
             rows_h = torch.empty((self.n_rec, nb, pipeline.RESULT_COLS), dtype=torch.float64).pin_memory()
@@ -335,8 +356,8 @@ class RaggedRecordingPass:
                     self.copy.wait_event(st["down"])
                 e0, e1 = self.n_ch * int(self.eeg_off[r0]), self.n_ch * int(self.eeg_off[r1])
                 st["raw"][:e1 - e0].copy_(raw_f[e0:e1], non_blocking=True)
-                a0, a1 = int(self.env_off[r0]), int(self.env_off[r1])
-                st["env"][:a1 - a0].copy_(env_f[a0:a1], non_blocking=True)
+                a0, a1 = int(sec_off[r0]), int(sec_off[r1])
+                st[key][:a1 - a0].copy_(env_f[a0:a1], non_blocking=True)
                 st["up"].record(self.copy)
             with torch.cuda.stream(st["main"]):
                 st["main"].wait_event(st["up"])
@@ -373,3 +394,53 @@ class RaggedRecordingPass:
         if bool(fl.any()):
             from ._lib import TdaError
             raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")
+
+
+class RaggedAudioRecordingPass(RaggedRecordingPass):
+    """RaggedRecordingPass from the reference's own inputs: raw EEG packed as for RaggedRecordingPass and the raw 44.1 kHz
+    mono float64 audio of each recording (what load_audio returns) packed back to back, both in pinned host memory
+    (preprocess.pack_recordings takes 1-D arrays).  Per shard the AUDIO is uploaded instead of the envelopes, and the
+    front end of process_recording (cmp:53-55: resample_audio, then compute_envelope) runs on the side stream ahead of
+    the envelopes' band-pass bank: the ragged polyphase resampler, the ragged Hilbert envelope and the low-pass, one
+    launch each (preprocess.envelopes_ragged_dev).  Envelope lengths are the resampled lengths ceil(La * 250 / 44100).
+    Audio is ~3.75x the bytes of the EEG, so shards are planned by bytes uploaded (RaggedPlan shard_bytes).  Everything
+    else -- buffer sets sized by the largest shard, upload / compute / download overlap, verify-then-publish, NaN rows
+    for recordings without a window -- is RaggedRecordingPass's; the rows equal RaggedRecordingPass.run fed the
+    envelopes of envelopes_ragged_dev bit for bit."""
+
+    def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
+                 fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
+                 overlap=0.75):
+        import torch
+        A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
+        long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
+        if len(long_):
+            raise ValueError(f"recording(s) {long_[:8].tolist()} longer than {preprocess.HILBERT_RAGGED_MAX} envelope samples")
+        plan = RaggedPlan(eeg_lengths, A.n_out, n_ch=n_ch, n_bands=len(dict(bands)), fs=fs, window_sec=window_sec,
+                          overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
+        super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
+                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan)
+        self.audio_plan = A
+        self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
+        self.second = ("audio", self.audio_off)
+        # the filter and Hilbert tables once; per shard its own length / offset tables (AudioPlan of the shard's lengths,
+        # its filter designed for the longest audio of the whole set: the same taps in every shard)
+        self.lowpass = preprocess.envelope_lowpass(fs)
+        for d in self.shards:
+            d["audio"] = preprocess.AudioPlan(A.La[d["r0"]:d["r1"]], fs_audio, fs, n_in_max=int(A.La.max())).upload(self.dev)
+        Ta = max((int(self.audio_off[d["r1"]] - self.audio_off[d["r0"]]) for d in self.shards), default=1)
+        S = max((d["n"] for d in self.shards), default=1)
+        Te = max((d["Te"] for d in self.shards), default=1)
+        edge_lp = 3 * max(len(b) for b in self.lowpass)
+        for st in self.set:
+            st["audio"] = torch.empty(Ta, dtype=torch.float64, device=self.dev)
+            st["front"] = torch.empty(3 * Te + 2 * edge_lp * S, dtype=torch.float64, device=self.dev)
+
+    def _front_end(self, st, i):
+        d = self.shards[i]
+        preprocess.envelopes_ragged_dev(st["audio"], d["audio"], out_t=st["env"], work_t=st["front"], ctx=self.ctx)
+
+    def run(self, raw_packed_h, audio_packed_h, rows_h=None):
+        """raw_packed_h: flat pinned float64, n_ch * sum(L); audio_packed_h: flat pinned float64, sum(La).  Returns rows_h
+        (n_rec, n_bands, 48), pinned, complete when the call returns."""
+        return super().run(raw_packed_h, audio_packed_h, rows_h)
