@@ -50,6 +50,8 @@ typedef enum {
                                      exactly as scripts/utils.py:125-126                      */
 #define TDA_WIN_NOT_CONVERGED 8   /* assignment solver hit its iteration bound (-> NaN)        */
 #define TDA_WIN_TOO_LARGE     16  /* more than TDA_MAX_POINTS points (tau < 1?): no diagram    */
+#define TDA_WIN_NO_PAIR       32  /* tda_wasserstein_cross_dev: this diagram has no partner at
+                                     its position (mvm:89); the distance is NaN and is no member of the group's mean */
 
 #define TDA_N_FEATURES 11         /* scripts/utils.py:166-177 key order */
 #define TDA_MAX_POINTS 128        /* vertices per Rips complex (reference needs <= 124)        */
@@ -408,6 +410,39 @@ tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* c
                                  const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
                                  const int* idx_a, const int* idx_b, int n_pairs,
                                  double* out, int* status);
+
+/* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
+ * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
+ * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:
+ * n = min(len(eeg), len(audio)); matched: the recording's own audio, mvm:136-137; mismatched: the audio of the first
+ * file of the other condition, mvm:113-118,139-141).
+ * A side: dgm_a (n_a, cap_a, 2), cnt_a (n_a), seg_off_a (n_seg_a + 1) int32, grp_a (n_a) int32 = the group of every
+ * diagram.  B side: dgm_b (n_b, cap_b, 2), cnt_b, seg_off_b (n_seg_b + 1), status_b (n_b) = the status words of the
+ * Rips call that made the B diagrams.  partner_seg: (n_seg_a) int32, the B group of each A group or -1.
+ * A diagram w at position i of group g, p = partner_seg[g], has a pair iff p >= 0, i < seg_off_b[p+1] - seg_off_b[p]
+ * and status_b[seg_off_b[p] + i] does not carry TDA_WIN_DEGENERATE (mvm:60: a cloud with < 3 points gives no diagram).
+ * With a pair, out[w] / status[w] are what tda_wasserstein_batch_dev gives for it (the same solver); without one,
+ * out[w] = NaN and status[w] = TDA_WIN_NO_PAIR, and the workgroup leaves before the solver.  Table entries that point
+ * outside the tables count as "no pair".  out: (n_a) float64, status: (n_a) int32.  Device pointers only,
+ * enqueue-only, no allocation.                                                             */
+tda_status tda_wasserstein_cross_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                     const int* grp_a, const int* seg_off_a, int n_seg_a,
+                                     const double* dgm_b, const int* cnt_b, int cap_b, int n_b,
+                                     const int* seg_off_b, int n_seg_b, const int* status_b,
+                                     const int* partner_seg, double* out, int* status, void* stream);
+
+/* ---- one row of the control experiment per (recording, band) group ---------------------
+ * out: (n_seg, 4) float64 = [ nanmean of the matched distances (mvm:137), nanmean of the mismatched ones (mvm:141),
+ * number of matched pairs, number of mismatched pairs ] from the out / status arrays of two
+ * tda_wasserstein_cross_dev calls over the same A side.  The pairs of a group are its first n entries (mvm:89); the
+ * mean is np.nanmean over exactly those n values (mvm:95), numpy's pairwise tree; a pair whose solver status is set
+ * counts as NaN; no pair (mvm:90) or only NaN: NaN.
+ * status_a / seg_flags (nullable): the status words of the Rips call that made the A diagrams, and an (n_seg) int32
+ * output that receives, per group, the OR of status_a and of the two solver status arrays without TDA_WIN_NO_PAIR and
+ * TDA_WIN_DEGENERATE -- as tda_recording_rows_dev: any bit means a row the reference would not give.        */
+tda_status tda_cross_rows_dev(tda_ctx* ctx, const double* w_matched, const int* status_matched,
+                              const double* w_mismatched, const int* status_mismatched, const int* seg_off_a,
+                              int n_seg, double* out, const int* status_a, int* seg_flags, void* stream);
 
 /* ---- timing helper ------------------------------------------------------------
  * HIP-event timing on the stream the kernels are launched on (bench.py roofline). */

@@ -23,6 +23,7 @@ TDA_WIN_CLASS_OVERFLOW = 2
 TDA_WIN_DEGENERATE = 4
 TDA_WIN_NOT_CONVERGED = 8
 TDA_WIN_TOO_LARGE = 16
+TDA_WIN_NO_PAIR = 32          # tda_wasserstein_cross_dev: no partner at this position (mvm:89)
 N_FEATURES = 11
 MAX_POINTS = 128
 
@@ -86,6 +87,9 @@ SYMBOLS = {
     "tda_spearman_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
     "tda_spearman_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
     "tda_wasserstein_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_wasserstein_cross_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp]),
+    "tda_cross_rows_dev": (_I, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),

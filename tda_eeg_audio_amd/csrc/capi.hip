@@ -378,6 +378,33 @@ tda_status tda_wasserstein_batch_dev(tda_ctx* ctx, const double* dgm_a, const in
                               (hipStream_t)stream);
 }
 
+tda_status tda_wasserstein_cross_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                     const int* grp_a, const int* seg_off_a, int n_seg_a, const double* dgm_b,
+                                     const int* cnt_b, int cap_b, int n_b, const int* seg_off_b, int n_seg_b,
+                                     const int* status_b, const int* partner_seg, double* out, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_seg_a); CHECK_NONNEG(ctx, n_b); CHECK_NONNEG(ctx, n_seg_b);
+    if (n_a == 0) return TDA_OK;
+    if (n_seg_a < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagrams without a group");
+    CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, grp_a); CHECK_PTR(ctx, seg_off_a); CHECK_PTR(ctx, partner_seg);
+    CHECK_PTR(ctx, out); CHECK_PTR(ctx, status);
+    if (n_b && n_seg_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, seg_off_b); CHECK_PTR(ctx, status_b); }
+    else { n_b = 0; n_seg_b = 0; }                                     // nothing to pair with: every diagram gets "no pair"
+    return launch_wasserstein_cross(ctx, dgm_a, cnt_a, cap_a, n_a, grp_a, seg_off_a, n_seg_a, dgm_b, cnt_b, cap_b, n_b,
+                                    seg_off_b, n_seg_b, status_b, partner_seg, out, status, (hipStream_t)stream);
+}
+
+tda_status tda_cross_rows_dev(tda_ctx* ctx, const double* w_matched, const int* status_matched, const double* w_mismatched,
+                              const int* status_mismatched, const int* seg_off_a, int n_seg, double* out,
+                              const int* status_a, int* seg_flags, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg);
+    if (n_seg) { CHECK_PTR(ctx, w_matched); CHECK_PTR(ctx, status_matched); CHECK_PTR(ctx, w_mismatched);
+                 CHECK_PTR(ctx, status_mismatched); CHECK_PTR(ctx, seg_off_a); CHECK_PTR(ctx, out); }
+    return launch_cross_rows(ctx, w_matched, status_matched, w_mismatched, status_mismatched, seg_off_a, n_seg, out,
+                             status_a, seg_flags, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.

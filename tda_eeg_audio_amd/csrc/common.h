@@ -218,3 +218,7 @@ tda_status launch_nanmean(tda_ctx*, const double*, const int*, int, double*, hip
 tda_status launch_spearman(tda_ctx*, const double*, const double*, int, const int*, int, const int*, int, double*, hipStream_t);
 tda_status launch_wasserstein(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
                               const int*, int, double*, int*, hipStream_t);
+tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, int, const int*, const int*, int, const double*,
+                                    const int*, int, int, const int*, int, const int*, const int*, double*, int*, hipStream_t);
+tda_status launch_cross_rows(tda_ctx*, const double*, const int*, const double*, const int*, const int*, int, double*,
+                             const int*, int*, hipStream_t);

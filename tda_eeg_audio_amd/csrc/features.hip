@@ -413,6 +413,54 @@ tda_status launch_recording_rows(tda_ctx* ctx, const double* w0, const double* w
     return TDA_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// The rows of the control experiment (mvm:86-95, 134-145): per EEG group
+//   [ nanmean of the matched W_H1, nanmean of the mismatched W_H1, matched pairs, mismatched pairs ]
+// from the two outputs of the cross Wasserstein launches.  The pairs of a group are its first n entries (mvm:89:
+// n = min(len(eeg), len(audio))); the mean runs over exactly those, with nanmean_kernel's tree -- the entries
+// without a pair never enter it (as zeros they would move the values to other accumulators of numpy's unrolled
+// sum).  A pair whose solver status is set counts as NaN.  One lane per (group, side).
+// ---------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+cross_rows_kernel(const double* __restrict__ w_m, const int* __restrict__ st_m, const double* __restrict__ w_x,
+                  const int* __restrict__ st_x, const int* __restrict__ seg_off, int n_seg, double* __restrict__ out,
+                  const int* __restrict__ status_a, int* __restrict__ seg_flags)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    const int seg = t >> 1, side = t & 1;
+    if (seg >= n_seg) return;
+    const int s0 = seg_off[seg], s1 = seg_off[seg + 1];
+    const double* x = side ? w_x : w_m;
+    const int* st = side ? st_x : st_m;
+    int n = 0, cnt = 0, fl = 0;
+    for (int i = s0; i < s1; ++i) n += (st[i] & TDA_WIN_NO_PAIR) ? 0 : 1;
+    for (int i = s0; i < s0 + n; ++i) {
+        cnt += (st[i] == 0 && x[i] == x[i]) ? 1 : 0;
+        fl |= st[i];
+    }
+    auto val = [=](int j) { const double v = x[s0 + j]; return (st[s0 + j] == 0 && v == v) ? v : 0.0; };
+    const double sum = np_pairwise_fn(val, 0, n);
+    double* row = out + (size_t)seg * 4;
+    row[side] = cnt > 0 ? sum / (double)cnt : __longlong_as_double(0x7ff8000000000000ll);
+    row[2 + side] = (double)n;
+    if (seg_flags) {
+        // both sides of a group sit in neighbouring lanes of one wave
+        if (status_a && side == 0) for (int i = s0; i < s1; ++i) fl |= status_a[i];
+        fl |= __shfl_xor(fl, 1, 64);
+        if (side == 0) seg_flags[seg] = fl & ~(TDA_WIN_NO_PAIR | TDA_WIN_DEGENERATE);
+    }
+}
+
+tda_status launch_cross_rows(tda_ctx* ctx, const double* w_m, const int* st_m, const double* w_x, const int* st_x,
+                             const int* seg_off, int n_seg, double* out, const int* status_a, int* seg_flags, hipStream_t st)
+{
+    if (n_seg == 0) return TDA_OK;
+    hipLaunchKernelGGL(cross_rows_kernel, dim3((2 * n_seg + 63) / 64), dim3(64), 0, st, w_m, st_m, w_x, st_x, seg_off, n_seg,
+                       out, status_a, seg_flags);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
 tda_status launch_nanmean(tda_ctx* ctx, const double* x, const int* seg_off, int n_seg, double* out, hipStream_t st)
 {
     if (n_seg == 0) return TDA_OK;

@@ -14,6 +14,8 @@
 // pair per wavefront: columns live on lanes (CW per lane), one Dijkstra step = CW LDS reads
 // per lane + one wave min-reduction.  At most R(R+1)/2 steps for R rows.
 // The returned value re-sums the ORIGINAL costs (C_ij, s_i, t_j) of the optimal matching.
+// Which pair a wavefront solves is a template parameter of the kernel: explicit index arrays (tda_wasserstein_batch)
+// or group tables read on the device (tda_wasserstein_cross_dev: scripts/matched_vs_mismatched.py:86-95).
 #include "common.h"
 #include <type_traits>
 
@@ -70,11 +72,47 @@ __device__ __forceinline__ double ws_cost(double ab, double ad, double bb, doubl
     return sqrt_rn(d2);                         // (sqrt() bit for bit, six instructions less: common.h)
 }
 
-template <int CW>
+// Where workgroup pr finds its pair: the kernel's compile-time switch (one solver, two prologues).
+// ws_index_pairs: explicit index arrays (NULL = identity), every workgroup has a pair.  Two pointers, laid out as
+// the two kernel arguments they replace.
+struct ws_index_pairs {
+    const int* idx_a; const int* idx_b;
+    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
+    {
+        ia = idx_a ? idx_a[pr] : pr;
+        ib = idx_b ? idx_b[pr] : pr;
+        return true;
+    }
+};
+// ws_table_pairs: grouped diagrams paired by position (mvm:89-93).  A diagram pr, at position i of its group g =
+// grp_a[pr], is paired with B diagram seg_off_b[p] + i of the group p = partner_seg[g] -- if g has a partner, the
+// partner's group is that long, and that B diagram is a diagram at all (mvm:60 leaves out clouds with < 3 points).
+// Every table is indexed from blockIdx.x alone: the reads are wave-uniform (scalar loads).  Indices that leave the
+// tables mean "no pair", never a read out of bounds.
+struct ws_table_pairs {
+    const int* grp_a; const int* seg_off_a; const int* seg_off_b; const int* partner_seg; const int* status_b;
+    int n_seg_a, n_seg_b, n_b;
+    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
+    {
+        ia = pr;
+        const int g = grp_a[pr];
+        if (g < 0 || g >= n_seg_a) return false;
+        const int p = partner_seg[g];
+        if (p < 0 || p >= n_seg_b) return false;
+        const int i = pr - seg_off_a[g];
+        const int b0 = seg_off_b[p];
+        if (i < 0 || i >= seg_off_b[p + 1] - b0) return false;
+        ib = b0 + i;
+        if (ib < 0 || ib >= n_b) return false;
+        return !(status_b[ib] & TDA_WIN_DEGENERATE);
+    }
+};
+
+template <int CW, class SRC>
 __global__ void __launch_bounds__(64)
 wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                    const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
-                   const int* __restrict__ idx_a, const int* __restrict__ idx_b, int n_pairs,
+                   const SRC src, int n_pairs,
                    int max_rows, int max_cols,
                    double* __restrict__ out, int* __restrict__ status, int mode)
 {
@@ -99,8 +137,11 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
     int* owner = reinterpret_cast<int*>(ct + max_cols);                 // max_cols ints (padded to 8 B)
     double* G = ct + max_cols + ((max_cols + 1) >> 1);                  // max_cols doubles
 
-    const int ia = idx_a ? idx_a[pr] : pr;
-    const int ib = idx_b ? idx_b[pr] : pr;
+    int ia, ib;
+    if (!src.resolve(pr, ia, ib)) {                                     // no pair: leave before the solver
+        if (lane == 0) { out[pr] = __longlong_as_double(0x7ff8000000000000ll); status[pr] = TDA_WIN_NO_PAIR; }
+        return;
+    }
     const double* A = dgm_a + (size_t)ia * cap_a * 2;
     const double* B = dgm_b + (size_t)ib * cap_b * 2;
     int ka = cnt_a[ia]; ka = ka < cap_a ? ka : cap_a; ka = ka < 0 ? 0 : ka;
@@ -419,9 +460,11 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
 }
 
 // ---------------------------------------------------------------------------------
-tda_status launch_wasserstein(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, const double* dgm_b,
-                              const int* cnt_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
-                              double* out, int* status, hipStream_t st)
+// the two-launch scheme, whatever the source of the pairs
+template <class SRC>
+static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, const double* dgm_b,
+                                         const int* cnt_b, int cap_b, const SRC& src, int n_pairs, double* out, int* status,
+                                         hipStream_t st)
 {
     if (n_pairs == 0) return TDA_OK;
     if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
@@ -439,17 +482,17 @@ tda_status launch_wasserstein(tda_ctx* ctx, const double* dgm_a, const int* cnt_
     if (mode) {
         const int sr = max_rows < 64 ? max_rows : 64;
         const size_t lds_s = (size_t)(4 * sr + 4 * 64 + 32) * 8;
-        hipLaunchKernelGGL(wasserstein_kernel<1>, dim3(n_pairs), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b,
-                           idx_a, idx_b, n_pairs, sr, 64, out, status, 1);
+        hipLaunchKernelGGL((wasserstein_kernel<1, SRC>), dim3(n_pairs), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
+                           cap_b, src, n_pairs, sr, 64, out, status, 1);
     }
 #define WS_LAUNCH(CWV)                                                                                         \
     do {                                                                                                       \
-        auto kern = wasserstein_kernel<CWV>;                                                                   \
+        auto kern = wasserstein_kernel<CWV, SRC>;                                                              \
         if (lds > 48 * 1024)                                                                                   \
             TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                              \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
         hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b,   \
-                           idx_a, idx_b, n_pairs, max_rows, max_cols, out, status, mode);                      \
+                           src, n_pairs, max_rows, max_cols, out, status, mode);                               \
     } while (0)
     if (max_cols <= 128) WS_LAUNCH(2);
     else if (max_cols <= 256) WS_LAUNCH(4);
@@ -457,4 +500,22 @@ tda_status launch_wasserstein(tda_ctx* ctx, const double* dgm_a, const int* cnt_
 #undef WS_LAUNCH
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
+}
+
+tda_status launch_wasserstein(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, const double* dgm_b,
+                              const int* cnt_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
+                              double* out, int* status, hipStream_t st)
+{
+    return launch_wasserstein_src(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, ws_index_pairs{idx_a, idx_b}, n_pairs, out,
+                                  status, st);
+}
+
+// one workgroup per A diagram; the pairs come from the group tables (ws_table_pairs)
+tda_status launch_wasserstein_cross(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                    const int* grp_a, const int* seg_off_a, int n_seg_a, const double* dgm_b,
+                                    const int* cnt_b, int cap_b, int n_b, const int* seg_off_b, int n_seg_b,
+                                    const int* status_b, const int* partner_seg, double* out, int* status, hipStream_t st)
+{
+    const ws_table_pairs src{grp_a, seg_off_a, seg_off_b, partner_seg, status_b, n_seg_a, n_seg_b, n_b};
+    return launch_wasserstein_src(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, n_a, out, status, st);
 }

@@ -461,3 +461,57 @@ def process_recording(audio, eeg_dists_by_band, fs_audio=44100):
     (preprocess.audio_to_band_windows, all filters on the GPU) -> process_recording_arrays."""
     from . import preprocess
     return process_recording_arrays(preprocess.audio_to_band_windows(audio, fs_audio), eeg_dists_by_band)
+
+
+def fdr_bh(pvals, alpha=0.05):
+    """Benjamini-Hochberg as statsmodels' multipletests(method="fdr_bh") (mvm:213): p * m / rank on the sorted values, running
+    minimum from the largest down, clipped at 1.  Returns (reject, p_corrected) in the order given."""
+    p = np.asarray(pvals, dtype=np.float64)
+    m = len(p)
+    order = np.argsort(p, kind="stable")
+    adj = p[order] * m / np.arange(1, m + 1)
+    adj = np.minimum(np.minimum.accumulate(adj[::-1])[::-1], 1.0)
+    out = np.empty(m)
+    out[order] = adj
+    return out <= alpha, out
+
+
+def control_summary(rows, subjects, conditions=None, bands=BANDS):
+    """mvm:180-221, host only: the per-band statistics of the control experiment from the rows of
+    recordings.ControlPass ((n_rec, n_bands, >= 2): w_matched, w_mismatched first), one subject label per recording.
+    Per band: rows with a NaN are dropped (mvm:182), the subjects' means taken (mvm:183-186), then n, the two means, the
+    direction, Wilcoxon's p of the differences (1.0 when all are zero, mvm:197-200), Cohen's d (mvm:202), how many
+    subjects have matched < mismatched; below 5 subjects {"n", "status": "insufficient"} (mvm:189-191).  Benjamini-
+    Hochberg over the bands' p-values, a missing one counting as 1.0 (mvm:212-217).  The keys are those of the
+    reference's results/matched_vs_mismatched.json.  conditions: accepted for symmetry with mvm's rows; the summary
+    pools both (mvm's per-condition figures, mvm:226-247, are printed only and are this function on a subset of rows)."""
+    from scipy.stats import wilcoxon
+    rows = np.asarray(rows, dtype=np.float64)
+    subjects = np.asarray([str(s) for s in subjects])
+    bands = list(bands)
+    assert rows.ndim == 3 and rows.shape[0] == len(subjects) and rows.shape[1] == len(bands) and rows.shape[2] >= 2
+    assert conditions is None or len(conditions) == len(subjects)
+    results = {}
+    for b, band in enumerate(bands):
+        wm, wx = rows[:, b, 0], rows[:, b, 1]
+        ok = ~np.isnan(wm) & ~np.isnan(wx)
+        subj = sorted(set(subjects[ok]))                                       # groupby sorts its keys
+        sm = np.array([[wm[ok & (subjects == s)].mean(), wx[ok & (subjects == s)].mean()] for s in subj]).reshape(-1, 2)
+        n = len(sm)
+        if n < 5:
+            results[band] = {"n": n, "status": "insufficient"}
+            continue
+        diff = sm[:, 0] - sm[:, 1]
+        mean_m, mean_x = sm[:, 0].mean(), sm[:, 1].mean()
+        p = wilcoxon(diff)[1] if np.any(diff != 0) else 1.0
+        n_lower = int(np.sum(diff < 0))
+        results[band] = {"n": n, "w_matched": float(mean_m), "w_mismatched": float(mean_x),
+                         "direction": "matched < mismatched" if mean_m < mean_x else "matched > mismatched",
+                         "p": float(p), "cohens_d": float(np.mean(diff) / (np.std(diff, ddof=1) + 1e-10)),
+                         "n_matched_lower": n_lower, "pct_matched_lower": float(n_lower / n * 100)}
+    reject, pfdr = fdr_bh([results[b].get("p", 1.0) for b in bands])
+    for i, band in enumerate(bands):
+        if "p" in results[band]:
+            results[band]["p_fdr"] = float(pfdr[i])
+            results[band]["sig_fdr"] = bool(reject[i])
+    return results

@@ -8,6 +8,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
+                 wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
+                 from group tables (recordings.ControlPass).
 """
 import ctypes as C
 
@@ -465,3 +467,53 @@ def wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=
                                                 _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
                                                 _tp(out_t), _tp(status_t), _stream()))
     return out_t, status_t
+
+
+def group_table(seg_off_t, n):
+    """(n,) int32: the group of each of the n members of a segment table, made on the device without a host
+    synchronisation: what wasserstein_cross_dev takes as grp_a.  Plans that know their tables upload it instead."""
+    import torch
+    pos = torch.arange(n, dtype=seg_off_t.dtype, device=seg_off_t.device)
+    return torch.searchsorted(seg_off_t[1:].contiguous(), pos, right=True).to(torch.int32)
+
+
+def wasserstein_cross_dev(rows_a, cnt_a, seg_off_a, rows_b, cnt_b, seg_off_b, status_b, partner_seg, grp_a=None, out_t=None,
+                          status_t=None, ctx=None):
+    """mvm:86-95 for every (recording, band) group at once: A diagram w at position i of group g is paired with B
+    diagram seg_off_b[p] + i of group p = partner_seg[g]; out[w] = NaN and status[w] = TDA_WIN_NO_PAIR where there is
+    none (p < 0, the B group is shorter, or the B diagram is degenerate).  All tables int32 device tensors; grp_a:
+    (n_a,) group of every A diagram (group_table(seg_off_a, n_a) when not given)."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_a, n_b = rows_a.shape[0], rows_b.shape[0]
+    n_seg_a, n_seg_b = seg_off_a.numel() - 1, seg_off_b.numel() - 1
+    for t in (seg_off_a, seg_off_b, status_b, partner_seg):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert partner_seg.numel() == n_seg_a and status_b.numel() >= n_b and cnt_a.numel() >= n_a and cnt_b.numel() >= n_b
+    if grp_a is None:
+        grp_a = group_table(seg_off_a, n_a)
+    assert grp_a.dtype == torch.int32 and grp_a.numel() >= n_a and grp_a.is_contiguous()
+    if out_t is None:
+        out_t = torch.empty(n_a, dtype=torch.float64, device=rows_a.device)
+    if status_t is None:
+        status_t = torch.empty(n_a, dtype=torch.int32, device=rows_a.device)
+    assert out_t.numel() >= n_a and status_t.numel() >= n_a
+    ctx.check(ctx.lib.tda_wasserstein_cross_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], n_a, _tp(grp_a), _tp(seg_off_a),
+                                                n_seg_a, _tp(rows_b), _tp(cnt_b), rows_b.shape[1], n_b, _tp(seg_off_b), n_seg_b,
+                                                _tp(status_b), _tp(partner_seg), _tp(out_t), _tp(status_t), _stream()))
+    return out_t, status_t
+
+
+def cross_rows_dev(w_m, st_m, w_x, st_x, seg_off_a, out_t=None, status_a=None, seg_flags=None, ctx=None):
+    """(n_seg, 4) rows [nanmean matched, nanmean mismatched, matched pairs, mismatched pairs] from the outputs of two
+    wasserstein_cross_dev calls over the same A side (mvm:89-95).  seg_flags (optional, (n_seg,) int32): per group, OR of
+    status_a (the A side's Rips status) and the solver status words, without TDA_WIN_NO_PAIR / TDA_WIN_DEGENERATE."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_seg = seg_off_a.numel() - 1
+    if out_t is None:
+        out_t = torch.empty((n_seg, 4), dtype=torch.float64, device=w_m.device)
+    assert out_t.is_contiguous() and out_t.numel() >= 4 * n_seg and seg_off_a.dtype == torch.int32
+    ctx.check(ctx.lib.tda_cross_rows_dev(ctx.h, _tp(w_m), _tp(st_m), _tp(w_x), _tp(st_x), _tp(seg_off_a), n_seg, _tp(out_t),
+                                         _tp(status_a), _tp(seg_flags), _stream()))
+    return out_t

@@ -187,11 +187,7 @@ class RaggedPlan:
         self.n_rec, self.n_ch, self.nb = len(self.L), int(n_ch), int(n_bands)
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
-        self.n_win = np.minimum(preprocess.n_windows(self.L, window_sec, overlap, fs),
-                                preprocess.n_windows(self.Le, window_sec, overlap, fs))          # cmp:71
-        self.picks = [select_windows(int(n), max_windows) for n in self.n_win]                  # cmp:77-80
-        self.k = np.array([len(p) for p in self.picks], dtype=np.int64)
-        self.empty = np.flatnonzero(self.k == 0)                                                 # the reference's None
+        self._select(window_sec, overlap, fs, max_windows)
         if shard_bytes is None:
             cost, budget = self.L, shard_samples
         else:
@@ -209,6 +205,14 @@ class RaggedPlan:
         if self.n_rec:
             self.shards.append((r0, self.n_rec))
         self.tables = [self._shard_tables(a, b) for a, b in self.shards]
+
+    def _select(self, window_sec, overlap, fs, max_windows):
+        """The windows of every recording: n_win, picks, k, empty (a plan with another rule: ControlPlan)."""
+        self.n_win = np.minimum(preprocess.n_windows(self.L, window_sec, overlap, fs),
+                                preprocess.n_windows(self.Le, window_sec, overlap, fs))          # cmp:71
+        self.picks = [select_windows(int(n), max_windows) for n in self.n_win]                  # cmp:77-80
+        self.k = np.array([len(p) for p in self.picks], dtype=np.int64)
+        self.empty = np.flatnonzero(self.k == 0)                                                 # the reference's None
 
     def _shard_tables(self, r0, r1):
         L, Le, k = self.L[r0:r1], self.Le[r0:r1], self.k[r0:r1]
@@ -241,6 +245,8 @@ class RaggedRecordingPass:
     launch each), the selected envelope windows gathered into the stack the tau / Takens kernels read, ONE run_step over
     the (band, recording) groups with the EEG windows read in place through the window table, rows scattered to the
     recordings.  Upload / compute / download overlap and verify-then-publish as in RecordingPass."""
+
+    ROW_COLS = pipeline.RESULT_COLS     # width of a row (a subclass with other rows: ControlPass)
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
@@ -294,7 +300,7 @@ class RaggedRecordingPass:
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
-                aw=torch.empty((max(n_win, 1), self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
+                aw=torch.empty((max(n_win, 1), self.win), **f64), rows=torch.empty((S, nb, self.ROW_COLS), **f64),
                 ws=ws, views=[ws.view(d["seg_off"]) for d in self.shards],
                 main=torch.cuda.Stream(device=self.dev), side=torch.cuda.Stream(device=self.dev),
                 up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event()))
@@ -344,7 +350,7 @@ class RaggedRecordingPass:
         assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and env_packed_h.numel() == sec_off[-1]
         nb = len(self.bands)
         if rows_h is None:
-            rows_h = torch.empty((self.n_rec, nb, pipeline.RESULT_COLS), dtype=torch.float64).pin_memory()
+            rows_h = torch.empty((self.n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
         raw_f, env_f = raw_packed_h.view(-1), env_packed_h.view(-1)
         pend = []
         for i, d in enumerate(self.shards):
@@ -444,3 +450,261 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
         """raw_packed_h: flat pinned float64, n_ch * sum(L); audio_packed_h: flat pinned float64, sum(La).  Returns rows_h
         (n_rec, n_bands, 48), pinned, complete when the call returns."""
         return super().run(raw_packed_h, audio_packed_h, rows_h)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the control experiment (scripts/matched_vs_mismatched.py): every recording's EEG against its own audio and against the
+# audio of a recording of the other condition of the same infant
+# ------------------------------------------------------------------------------------------------------------
+def mismatch_partners(names, conditions):
+    """mvm:98-118, host only.  names: file names or stems of the recordings; conditions: the condition of each (two
+    distinct values, mvm's "slow" / "fast").  Subject = the part of the stem before the first "_" (mvm:102).  Returns
+    int64 (n_rec,): the index of the recording whose audio is the mismatched one -- the first file, in sorted order, of
+    the same subject in the other condition (mvm:100,113-114) -- or -1 where the subject has no recording there (mvm:106
+    leaves such subjects out).  The same name may occur in both conditions: a recording is (condition, name)."""
+    names = [str(n) for n in names]
+    conditions = [str(c) for c in conditions]
+    assert len(names) == len(conditions)
+    files = [n if n.lower().endswith(".mat") else n + ".mat" for n in names]           # mvm sorts the *.mat paths
+    conds = sorted(set(conditions))
+    if len(conds) > 2:
+        raise ValueError(f"two conditions expected, got {conds}")
+    first = {}                                                                           # (condition, subject) -> index
+    for r in sorted(range(len(files)), key=lambda r: files[r]):
+        first.setdefault((conditions[r], files[r][:-4].split("_")[0]), r)
+    other = {conds[0]: conds[-1], conds[-1]: conds[0]} if len(conds) == 2 else {}
+    return np.array([first.get((other.get(c), f[:-4].split("_")[0]), -1) for f, c in zip(files, conditions)], dtype=np.int64)
+
+
+class ControlPlan(RaggedPlan):
+    """The host plan of ControlPass, numpy only (tests/test_control_plan.py checks it without a GPU).  What differs from
+    RaggedPlan is mvm's: per recording r the EEG windows are selected from the EEG's own window count (mvm:74-78; k_e,
+    picks_e) and the audio windows from the envelope's own (mvm:44-49; k_a, picks_a) -- cmp:71 takes both from the
+    minimum -- and partner[r] (mismatch_partners, or any table: a shuffle for a permutation null) names the recording
+    whose audio is the mismatched one, -1 for none.  Shards as RaggedPlan makes them.  Per shard, beside RaggedPlan's
+    eeg_off / env_off / live / eeg_start / eeg_ld (by k_e and picks_e):
+      seg_off_e (= seg_off)  EEG groups of k_e windows, band-major over the live recordings (k_e > 0); grp_e: the group
+                             of every EEG window
+      live_a, seg_off_a      audio groups of k_a windows, band-major over the recordings with k_a > 0
+      env_start              window table of the band-passed envelopes by picks_a
+      partner_own            per EEG group the audio group of the same (recording, band), -1 when k_a = 0
+      partner_bank           per EEG group the bank group of (partner, band), -1 without a partner (or one with k_a = 0)
+    The bank, once per pass: U the sorted distinct partners, bank the ones of them with k_a > 0 (bank_pos[r]: position
+    in `bank` or -1), bank_off the offsets of their packed envelopes, seg_off_bank (band-major over `bank`) and
+    bank_start, the window table of their band-passed envelopes."""
+
+    def __init__(self, eeg_lengths, env_lengths=None, partner=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_ch=47, n_bands=5,
+                 fs=250, window_sec=1.0, overlap=0.75, max_windows=MAX_WINDOWS):
+        n_rec = len(np.asarray(eeg_lengths).ravel())
+        self.partner = np.full(n_rec, -1, np.int64) if partner is None else np.asarray(partner, dtype=np.int64).ravel()
+        assert self.partner.shape == (n_rec,) and ((self.partner >= -1) & (self.partner < n_rec)).all()
+        super().__init__(eeg_lengths, env_lengths, shard_samples, n_ch, n_bands, fs, window_sec, overlap, max_windows)
+
+    def _select(self, window_sec, overlap, fs, max_windows):
+        self.n_win_e = preprocess.n_windows(self.L, window_sec, overlap, fs)                     # mvm:72
+        self.n_win_a = preprocess.n_windows(self.Le, window_sec, overlap, fs)                    # mvm:44
+        self.picks_e = [select_windows(int(n), max_windows) for n in self.n_win_e]              # mvm:74-77
+        self.picks_a = [select_windows(int(n), max_windows) for n in self.n_win_a]              # mvm:46-49
+        self.k_e = np.array([len(p) for p in self.picks_e], dtype=np.int64)
+        self.k_a = np.array([len(p) for p in self.picks_a], dtype=np.int64)
+        # RaggedPlan's names are the EEG's: a recording without an EEG window has no row (mvm:73)
+        self.n_win, self.picks, self.k = self.n_win_e, self.picks_e, self.k_e
+        self.empty = np.flatnonzero(self.k_e == 0)
+        self.U = np.unique(self.partner[self.partner >= 0])
+        self.bank = self.U[self.k_a[self.U] > 0]
+        self.bank_pos = np.full(self.n_rec, -1, np.int64)
+        self.bank_pos[self.bank] = np.arange(len(self.bank))
+        kb = self.k_a[self.bank]
+        self.bank_off = np.concatenate([[0], np.cumsum(self.Le[self.bank])]).astype(np.int64)
+        self.seg_off_bank = np.concatenate([[0], np.cumsum(np.tile(kb, self.nb))]).astype(np.int32)
+        pick_off = np.concatenate([self.picks_a[u] * self.step for u in self.bank]).astype(np.int64) if len(self.bank) else \
+            np.zeros(0, np.int64)
+        b1 = np.repeat(self.bank_off[:-1], kb) + pick_off
+        self.bank_start = (np.arange(self.nb, dtype=np.int64)[:, None] * self.bank_off[-1] + b1[None, :]).ravel()
+
+    def _shard_tables(self, r0, r1):
+        t = super()._shard_tables(r0, r1)                                # the EEG side: k = k_e, picks = picks_e
+        n, nb = r1 - r0, self.nb
+        live, ka = t["live"], self.k_a[r0:r1]
+        live_a = np.flatnonzero(ka > 0)
+        kla = ka[live_a]
+        pick_off = np.concatenate([self.picks_a[r0 + j] * self.step for j in live_a]).astype(np.int64) if len(live_a) else \
+            np.zeros(0, np.int64)
+        a1 = np.repeat(t["env_off"][live_a], kla) + pick_off
+        band = np.arange(nb, dtype=np.int64)[:, None]
+        pos_a = np.full(n, -1, np.int64)
+        pos_a[live_a] = np.arange(len(live_a))
+        own = pos_a[live]
+        pr = self.partner[r0 + live]
+        pb = np.where(pr >= 0, self.bank_pos[np.maximum(pr, 0)], -1)
+        seg_off_e = t["seg_off"]
+        t.update(seg_off_e=seg_off_e, grp_e=np.repeat(np.arange(len(seg_off_e) - 1), np.diff(seg_off_e)).astype(np.int32),
+                 live_a=live_a, seg_off_a=np.concatenate([[0], np.cumsum(np.tile(kla, nb))]).astype(np.int32),
+                 env_start=(band * t["env_off"][-1] + a1[None, :]).ravel(),
+                 partner_own=np.where(own >= 0, band * len(live_a) + own[None, :], -1).astype(np.int32).ravel(),
+                 partner_bank=np.where(pb >= 0, band * len(self.bank) + pb[None, :], -1).astype(np.int32).ravel())
+        return t
+
+
+CONTROL_COLS = 4            # [w_matched, w_mismatched, n_matched, n_mismatched]
+
+
+class ControlPass(RaggedRecordingPass):
+    """The control experiment (scripts/matched_vs_mismatched.py:120-172) as a batched pass FROM HOST MEMORY: the inputs of
+    RaggedRecordingPass (raw EEG packed back to back, 250 Hz envelopes packed with their own lengths, both pinned) and a
+    partner table (mismatch_partners) go in, the (n_rec, n_bands, 4) rows [w_matched, w_mismatched, n_matched,
+    n_mismatched] come back: per (recording, band) the mean H1 Wasserstein distance between the EEG diagrams and the
+    diagrams of the recording's own audio, and of its partner's audio, paired by position (mvm:86-95), with the number of
+    pairs of each.  A recording without an EEG window (mvm:73) gets a NaN row with zero counts; a (recording, band)
+    without a pair NaN (mvm:90).
+    Phase 1, once per run: the envelopes of the distinct partners with a window (the bank: 90 recordings for the study's
+    table, sized by the table for any other) are staged, uploaded in one copy, band-passed, windowed and taken through
+    tau / Takens / Rips under the full ladder into a DeviceDiagrams that lives for the whole pass.
+    Phase 2, per shard: RaggedRecordingPass's pipeline (its run, _shard_step, _verify and buffer sets) with another Rips
+    step: the EEG windows by the EEG's own count, the audio windows by the envelope's own count, two
+    engine.wasserstein_cross_dev launches that resolve their pairs on the device from the plan's tables (own audio,
+    then the bank) and engine.cross_rows_dev.  No index array is built per shard and nothing synchronises with the host
+    between the Rips stages and the rows.
+    The 250 Hz envelopes are the upload (the _front_end hook is RaggedRecordingPass's)."""
+
+    ROW_COLS = CONTROL_COLS
+
+    def __init__(self, eeg_lengths, env_lengths=None, partner=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2,
+                 ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75):
+        import torch
+        from ._lib import MAX_POINTS
+        plan = ControlPlan(eeg_lengths, env_lengths, partner, shard_samples, n_ch, len(dict(bands)), fs, window_sec, overlap,
+                           max_windows)
+        super().__init__(eeg_lengths, env_lengths, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
+                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan)
+        P, dev, nb = plan, self.dev, len(self.bands)
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)      # noqa: E731
+        for d, t in zip(self.shards, P.tables):
+            d.update(seg_off_a=up(t["seg_off_a"], torch.int32), grp_e=up(t["grp_e"], torch.int32),
+                     partner_own=up(t["partner_own"], torch.int32), partner_bank=up(t["partner_bank"], torch.int32),
+                     n_win_a=int(t["seg_off_a"][-1]))
+        n_e = max((d["n_win"] for d in self.shards), default=0)
+        n_a = max((d["n_win_a"] for d in self.shards), default=0)
+        n_seg = max((nb * d["n_live"] for d in self.shards), default=0)
+        for st in self.set:
+            # the audio side of a shard has its own window count: its own stack, tau tables and -- where the Workspace's
+            # audio diagrams (sized by the EEG's count) do not hold it -- diagrams
+            st["aw"] = torch.empty((max(n_a, 1), self.win), **f64)
+            st["caud"] = st["ws"].aud if n_a <= st["ws"].aud.n_win else engine.DeviceDiagrams(n_a, MAX_POINTS, st["ws"].aud.h1_cap, dev)
+            st["tau_seg"], st["tau_win"] = torch.empty(max(n_a, 1), **i32), torch.empty(max(n_a, 1), **i32)
+            st["wm"], st["wx"] = torch.empty(max(n_e, 1), **f64), torch.empty(max(n_e, 1), **f64)
+            st["sm"], st["sx"] = torch.empty(max(n_e, 1), **i32), torch.empty(max(n_e, 1), **i32)
+            st["res"] = torch.empty((max(n_seg, 1), CONTROL_COLS), **f64)
+        self.bits = torch.tensor([1, 2, 8, 16], **i32)                  # every TDA_WIN_* bit but DEGENERATE (a result)
+        # the bank
+        Tb, n_b = int(P.bank_off[-1]), int(P.seg_off_bank[-1])
+        self.n_bank_win = n_b
+        self.bank = engine.DeviceDiagrams(n_b, MAX_POINTS, engine.DEFAULT_H1_CAP, dev)
+        self.bank_seg_off = up(P.seg_off_bank, torch.int32)
+        self.bank_start = up(P.bank_start, torch.int64)
+        self.bank_tb = preprocess.RaggedTables(P.Le[P.bank], dev)
+        self.bank_stage = torch.empty(max(Tb, 1), dtype=torch.float64).pin_memory()
+        self.bank_buf = dict(env=torch.empty(max(Tb, 1), **f64), ya=torch.empty(nb * max(Tb, 1), **f64),
+                             work=torch.empty(nb * (Tb + 2 * self.edge_a * max(len(P.bank), 1)), **f64),
+                             aw=torch.empty((max(n_b, 1), self.win), **f64), tau_seg=torch.empty(max(n_b, 1), **i32),
+                             tau_win=torch.empty(max(n_b, 1), **i32))
+        self.bank_stream = self.set[0]["main"]                           # (no stream of its own: the Rips retry lists are per stream)
+        self.bank_ready = torch.cuda.Event()
+        self.bank_flags = torch.zeros(1, **i32)
+        self.bank_flags_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+
+    def _or_bits(self, status_t):
+        """OR of the status words of a Rips call without TDA_WIN_DEGENERATE, on the device (0-d int32)."""
+        import torch
+        if status_t.numel() == 0:
+            return torch.zeros((), dtype=torch.int32, device=self.dev)
+        return (status_t.unsqueeze(1) & self.bits).amax(0).sum().to(torch.int32)
+
+    def _audio_diagrams(self, aw, seg_off_t, tau_seg, tau_win, out):
+        """mvm:56-61 for the groups of a window stack: tau from the first window of every group, Takens + Rips, the H1
+        rows into ripser's order (the finishing step of pipeline.run_step: a diagram is row for row the per-call API's)."""
+        engine.tau_segments_dev(aw, seg_off_t, self.win // 2, tau_seg, tau_win, ctx=self.ctx)
+        engine.takens_rips_dev(aw, tau_win, out, ctx=self.ctx)
+        engine.diagram_finish_dev([(out.h1, out.c1, True, None)], ctx=self.ctx)
+
+    def _phase1(self, env_f):
+        """The bank: one staging copy of the partners' envelopes, their band-pass bank, windows and diagrams."""
+        import torch
+        P, B, ctx = self.plan, self.bank_buf, self.ctx
+        if self.n_bank_win == 0:
+            self.bank_ready.record(self.bank_stream)
+            return
+        sv, ev = self.bank_stage.numpy(), env_f.numpy()
+        for j, u in enumerate(P.bank):
+            sv[P.bank_off[j]:P.bank_off[j + 1]] = ev[self.env_off[u]:self.env_off[u + 1]]
+        Tb = int(P.bank_off[-1])
+        with torch.cuda.stream(self.bank_stream):
+            for st in self.set[1:]:                                      # a run before this one may still read the bank
+                self.bank_stream.wait_stream(st["main"])
+            B["env"][:Tb].copy_(self.bank_stage[:Tb], non_blocking=True)
+            preprocess.filtfilt_bank_ragged_dev(B["env"][:Tb], self.bank_tb, self.bas, y_t=B["ya"], work_t=B["work"], ctx=ctx)
+            engine.gather_windows_dev(B["ya"], self.bank_start, self.win, out_t=B["aw"], ctx=ctx)
+            ctx.set_h1_order(ctx.ORDER_DEFERRED)
+            try:                                                         # (the retry policy is the default: the full ladder)
+                self._audio_diagrams(B["aw"][:self.n_bank_win], self.bank_seg_off, B["tau_seg"], B["tau_win"], self.bank)
+            finally:
+                ctx.set_h1_order(ctx.ORDER_IN_CALL)
+            self.bank_flags.copy_(self._or_bits(self.bank.status).view(1))
+            self.bank_flags_host.copy_(self.bank_flags, non_blocking=True)
+            self.bank_ready.record(self.bank_stream)
+
+    def _rips_step(self, st, i, retry):
+        """Both Rips stages of a shard, the two cross Wasserstein launches and the rows: (n_bands * n_live, 4)."""
+        import torch
+        ctx, d, v = self.ctx, self.shards[i], st["views"][i]
+        n_e, n_a = d["n_win"], d["n_win_a"]
+        aud = st["caud"].head(n_a)
+        if retry != "auto":
+            ctx.set_retry_policy(ctx.RETRY_ONE_STEP)
+        ctx.set_h1_order(ctx.ORDER_DEFERRED)
+        try:
+            engine.eeg_window_ragged_dev(st["y"], d["eeg_start"], d["eeg_ld"], self.win, out=v.eeg, n_ch=v.eeg.h0_cap, ctx=ctx)
+            if n_a:
+                self._audio_diagrams(st["aw"][:n_a], d["seg_off_a"], st["tau_seg"], st["tau_win"], aud)
+        finally:
+            ctx.set_h1_order(ctx.ORDER_IN_CALL)
+            if retry != "auto":
+                ctx.set_retry_policy(ctx.RETRY_AUTO)
+        engine.diagram_finish_dev([(v.eeg.h1, v.eeg.c1, True, None)], ctx=ctx)
+        torch.cuda.current_stream().wait_event(self.bank_ready)
+        wm, sm, wx, sx = st["wm"][:n_e], st["sm"][:n_e], st["wx"][:n_e], st["sx"][:n_e]
+        engine.wasserstein_cross_dev(v.eeg.h1, v.eeg.c1, v.seg_off, aud.h1, aud.c1, d["seg_off_a"], aud.status,
+                                     d["partner_own"], grp_a=d["grp_e"], out_t=wm, status_t=sm, ctx=ctx)
+        engine.wasserstein_cross_dev(v.eeg.h1, v.eeg.c1, v.seg_off, self.bank.h1, self.bank.c1, self.bank_seg_off,
+                                     self.bank.status, d["partner_bank"], grp_a=d["grp_e"], out_t=wx, status_t=sx, ctx=ctx)
+        res = engine.cross_rows_dev(wm, sm, wx, sx, v.seg_off, out_t=st["res"][:v.n_seg], status_a=v.eeg.status,
+                                    seg_flags=v.seg_flags, ctx=ctx)
+        if n_a:                                                          # the audio side's flags ask for the ladder too
+            v.seg_flags.bitwise_or_(self._or_bits(aud.status))
+        if retry != "auto":
+            v.flags_host.copy_(v.seg_flags, non_blocking=True)
+        return res
+
+    def _rows(self, st, i, res):
+        """(n_bands * n_live, 4) band-major -> the shard's rows; recordings without an EEG window: NaN, no pairs."""
+        d = self.shards[i]
+        rows = st["rows"][:d["n"]]
+        if d["n_live"] < d["n"]:
+            rows.fill_(float("nan"))
+            rows[:, :, 2:] = 0.0
+        if d["n_live"]:
+            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], CONTROL_COLS).transpose(0, 1))
+
+    def run(self, raw_packed_h, env_packed_h, rows_h=None):
+        """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
+        (n_rec, n_bands, 4) [w_matched, w_mismatched, n_matched, n_mismatched], pinned, complete when the call returns."""
+        assert env_packed_h.numel() == self.env_off[-1]
+        self._phase1(env_packed_h.view(-1))
+        rows_h = super().run(raw_packed_h, env_packed_h, rows_h)
+        self.bank_ready.synchronize()
+        if int(self.bank_flags_host[0]):
+            from ._lib import TdaError
+            raise TdaError(f"window status bits {int(self.bank_flags_host[0]):#x} left in the partners' diagrams: rows withheld")
+        return rows_h

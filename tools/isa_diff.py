@@ -6,6 +6,9 @@ Compiles each csrc/<file>.hip device-only (the Makefile's flags) from the workin
 disassembles both code objects and compares every kernel whose mangled name matches, line by line.  Addresses are
 dropped, and so is the literal of the s_add_u32 / s_addc_u32 pair after an s_getpc_b64 (PC-relative offsets to constant
 data, which move whenever a kernel is added anywhere in the file).  No GPU needed.
+An instantiation whose template arguments grew since REV is paired with its counterpart through RENAMED (mangled
+prefix at REV -> mangled prefix now):
+    python3 tools/isa_diff.py --files wasserstein --match wasserstein_kernel
 """
 import argparse
 import os
@@ -18,6 +21,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tda_eeg_audio_amd", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fvisibility=hidden"]
+
+
+# wasserstein_kernel<CW> became wasserstein_kernel<CW, SRC>; the pairs from index arrays are SRC = ws_index_pairs
+RENAMED = [(re.compile(r"^_Z18wasserstein_kernelILi(\d+)EEv"), r"_Z18wasserstein_kernelILi\g<1>E14ws_index_pairsEv")]
+
+
+def counterpart(old_name, new):
+    """The kernel of the working tree that old_name is compared with: the same mangled name, or -- for a renamed
+    instantiation -- the one whose name starts with the new prefix (the argument list that follows may be compressed
+    differently)."""
+    if old_name in new:
+        return old_name
+    for pat, rep in RENAMED:
+        m = pat.match(old_name)
+        if m:
+            hits = [k for k in new if k.startswith(m.expand(rep))]
+            if len(hits) == 1:
+                return hits[0]
+    return None
 
 
 def disasm(src_dir, name, tmp, tag):
@@ -70,9 +92,15 @@ def main():
             for k in sorted(old):
                 if not pat.search(k):
                     continue
-                same = new.get(k) == old[k]
+                k2 = counterpart(k, new)
+                same = k2 is not None and new[k2] == old[k]
                 bad += not same
-                print(f"{'same' if same else 'DIFFERENT' if k in new else 'MISSING'}  {len(old[k]):6d} instructions  {k}")
+                print(f"{'same' if same else 'DIFFERENT' if k2 else 'MISSING'}  {len(old[k]):6d} instructions  {k}"
+                      + (f"  ->  {k2}" if k2 and k2 != k else ""))
+                if k2 and not same:
+                    import difflib
+                    d = [l for l in difflib.unified_diff(old[k], new[k2], lineterm="", n=0) if l[:1] in "+-" and l[:3] not in ("+++", "---")]
+                    print(f"           {len(new[k2]):6d} instructions now, {len(d)} diff lines")
     sys.exit(1 if bad else 0)
 
 
