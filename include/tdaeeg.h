@@ -395,6 +395,26 @@ tda_status tda_spearman_batch_dev(tda_ctx* ctx, const double* x, const double* y
 tda_status tda_spearman_batch(tda_ctx* ctx, const double* x, const double* y, int n_total, int ld,
                               const int* cols, int n_cols, const int* seg_off, int n_seg, double* r);
 
+/* ---- temporal correlation of the H1 feature time series of a step ---------------------
+ * replaces the window filter and the spearmanr(a_ts, e_ts) loop of process_recording
+ * (scripts/tda_eeg_audio_comparison.py:90-91,104-114) on the per-window feature matrices of a step, r AND p:
+ * fa, fe: (n_total, ld) float64, the audio H1 and EEG H1 features of every window; cols: (n_cols) column indices
+ * (each < ld); seg_off: (n_seg+1) int32; status_b (nullable): (n_total) status words of the audio Rips call.
+ * The survivors of a group are its windows with (status_b & (TDA_WIN_DEGENERATE | TDA_WIN_TOO_LARGE)) == 0, in
+ * their order (cmp:90-91, the rule of tda_recording_rows_dev); m is their number.  Per group and column:
+ *   m == 0                              r = p = NaN   (the reference drops the band, cmp:101-102)
+ *   m < 5 or np.std of a series <= 1e-10  r = 0, p = 1  (cmp:110-114)
+ *   otherwise  r = Pearson correlation of the average ranks, the bits of tda_spearman_batch on the survivors;
+ *              p = I_{1-r^2}((m-2)/2, 1/2), the two-sided Student-t p-value scipy.stats.spearmanr reports (0 at r = +-1)
+ * out: (n_seg, 2 * n_cols) float64, [r, p] per column.  Any m.  The _dev call only enqueues one fixed-size launch
+ * (no allocation, no host synchronisation): it may be captured into a graph.  The host twin also checks the tables. */
+tda_status tda_temporal_corr_dev(tda_ctx* ctx, const double* fa, const double* fe, int ld, const int* cols,
+                                 int n_cols, const int* seg_off, int n_seg, const int* status_b, double* out,
+                                 void* stream);
+tda_status tda_temporal_corr_batch(tda_ctx* ctx, const double* fa, const double* fe, int n_total, int ld,
+                                   const int* cols, int n_cols, const int* seg_off, int n_seg, const int* status_b,
+                                   double* out);
+
 /* ---- Wasserstein distance between diagrams ------------------------------------
  * replaces safe_wasserstein (scripts/utils.py:180-191) -> persim.wasserstein
  * (order 1, Euclidean ground metric, diagonal cost (d-b)/sqrt 2).

@@ -86,6 +86,8 @@ SYMBOLS = {
     "tda_segment_nanmean": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp]),
     "tda_spearman_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
     "tda_spearman_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
+    "tda_temporal_corr_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_temporal_corr_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
     "tda_wasserstein_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_wasserstein_cross_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp,
                                        c_vp, c_vp, c_vp]),

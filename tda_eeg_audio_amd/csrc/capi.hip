@@ -367,6 +367,16 @@ tda_status tda_spearman_batch_dev(tda_ctx* ctx, const double* x, const double* y
     return launch_spearman(ctx, x, y, ld, cols, n_cols, seg_off, n_seg, r, (hipStream_t)stream);
 }
 
+tda_status tda_temporal_corr_dev(tda_ctx* ctx, const double* fa, const double* fe, int ld, const int* cols, int n_cols,
+                                 const int* seg_off, int n_seg, const int* status_b, double* out, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg); CHECK_NONNEG(ctx, n_cols);
+    if (n_seg == 0 || n_cols == 0) return TDA_OK;
+    CHECK_PTR(ctx, fa); CHECK_PTR(ctx, fe); CHECK_PTR(ctx, cols); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, out);
+    if (ld < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "ld must be >= 1");
+    return launch_temporal_corr(ctx, fa, fe, ld, cols, n_cols, seg_off, n_seg, status_b, out, (hipStream_t)stream);
+}
+
 tda_status tda_wasserstein_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
                                      const double* dgm_b, const int* cnt_b, int cap_b, const int* idx_a,
                                      const int* idx_b, int n_pairs, double* out, int* status, void* stream)
@@ -726,6 +736,32 @@ tda_status tda_spearman_batch(tda_ctx* ctx, const double* x, const double* y, in
     s.add((void**)&d_r, nullptr, r, (size_t)n_seg * n_cols * 8);
     RET_IF(s.upload());
     RET_IF(tda_spearman_batch_dev(ctx, d_x, d_y, ld, d_c, n_cols, d_o, n_seg, d_r, nullptr));
+    return s.download();
+}
+
+tda_status tda_temporal_corr_batch(tda_ctx* ctx, const double* fa, const double* fe, int n_total, int ld, const int* cols,
+                                   int n_cols, const int* seg_off, int n_seg, const int* status_b, double* out)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg);
+    if (n_seg == 0) return TDA_OK;
+    CHECK_PTR(ctx, fa); CHECK_PTR(ctx, fe); CHECK_PTR(ctx, cols); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, out);
+    if (n_total < 1 || ld < 1 || n_cols < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
+    for (int c = 0; c < n_cols; ++c)
+        if (cols[c] < 0 || cols[c] >= ld) TDA_FAIL(ctx, TDA_ERR_INVALID, "column index out of range");
+    if (seg_off[0] != 0 || seg_off[n_seg] != n_total) TDA_FAIL(ctx, TDA_ERR_INVALID, "seg_off must run from 0 to n_total");
+    for (int g = 0; g < n_seg; ++g)
+        if (seg_off[g + 1] < seg_off[g]) TDA_FAIL(ctx, TDA_ERR_INVALID, "seg_off must not decrease");
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_a, *d_e, *d_out; int *d_c, *d_o, *d_st = nullptr;
+    s.add((void**)&d_a, fa, nullptr, (size_t)n_total * ld * 8);
+    s.add((void**)&d_e, fe, nullptr, (size_t)n_total * ld * 8);
+    s.add((void**)&d_c, cols, nullptr, (size_t)n_cols * 4);
+    s.add((void**)&d_o, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
+    if (status_b) s.add((void**)&d_st, status_b, nullptr, (size_t)n_total * 4);
+    s.add((void**)&d_out, nullptr, out, (size_t)n_seg * 2 * n_cols * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_temporal_corr_dev(ctx, d_a, d_e, ld, d_c, n_cols, d_o, n_seg, d_st, d_out, nullptr));
     return s.download();
 }
 

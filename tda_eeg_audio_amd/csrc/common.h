@@ -216,6 +216,8 @@ tda_status launch_diagram_finish(tda_ctx*, const tda_diagram_set*, int, int, hip
 tda_status launch_aggregate(tda_ctx*, const double*, const double*, const int*, int, double*, hipStream_t);
 tda_status launch_nanmean(tda_ctx*, const double*, const int*, int, double*, hipStream_t);
 tda_status launch_spearman(tda_ctx*, const double*, const double*, int, const int*, int, const int*, int, double*, hipStream_t);
+tda_status launch_temporal_corr(tda_ctx*, const double*, const double*, int, const int*, int, const int*, int, const int*,
+                                double*, hipStream_t);
 tda_status launch_wasserstein(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
                               const int*, int, double*, int*, hipStream_t);
 tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, int, const int*, const int*, int, const double*,

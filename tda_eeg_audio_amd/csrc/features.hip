@@ -4,6 +4,7 @@
 //   features_kernel   replaces extract_features             (scripts/utils.py:144-177)
 //                     == extract_persistence_features       (tda_eeg_classification_v2.py:179-250)
 //   aggregate_kernel  replaces the mean/std over windows    (tda_eeg_classification_v2.py:429-436)
+//   temporal_corr_kernel  replaces the window filter and the spearmanr loop, r and p   (tda_eeg_audio_comparison.py:90-91,104-114)
 //
 // All float64.  Sums follow numpy's pairwise-summation tree (8 interleaved partial sums for
 // n <= 128, halving above) so that mean/std agree with np.mean/np.std to the last bit on the
@@ -524,6 +525,217 @@ tda_status launch_spearman(tda_ctx* ctx, const double* x, const double* y, int l
     if (n_seg == 0 || n_cols == 0) return TDA_OK;
     if (n_cols > 64) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "at most 64 columns");
     hipLaunchKernelGGL(spearman_kernel, dim3(n_seg), dim3(64), 0, st, x, y, ld, cols, n_cols, seg_off, n_seg, r_out);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// Temporal correlation of the H1 feature time series of a step (cmp:90-91,104-114): per (recording, band) group and
+// feature column, Spearman r AND its two-sided p-value of the audio series against the EEG series over the windows that
+// reached the distances.  Unlike spearman_kernel it takes the per-window matrices of a step as they are: the windows
+// cmp:90-91 skips are left out here, by the rule and the constants of recording_rows_kernel.
+//   m = survivors;  m == 0: NaN, NaN (the reference drops the band, cmp:101-102);  m < 5 or np.std of a series
+//   <= 1e-10: 0, 1 (cmp:110-114);  otherwise r as spearman_kernel on the compacted series, bit for bit, and
+//   p = I_{1-r^2}((m-2)/2, 1/2).
+// One wavefront per group.  Up to TC_CAP survivors (numpy's pairwise leaf; the reference has <= 15, every window of the
+// corpus <= 89) are compacted into LDS with a ballot and a prefix popcount, all columns of a trip at once; a longer
+// group is read in place from global memory, the skipped windows stepped over.  Either way the series sit behind one
+// accessor: slot k (valid or not), and for the guard's sums the j-th survivor.
+//   * guard: every lane evaluates the same four sums per column with numpy's pairwise tree (same-address reads)
+//   * ranks: lane i owns slot i (chunks of 64) and walks all slots j -- same-address reads again, a broadcast.  The
+//     centred average ranks are multiples of 1/2, their products multiples of 1/4 and their sums (<= m^3 / 4) stay
+//     below 2^53 quarters for m < 2^17: the three sums are EXACT in float64 in any order, so the per-lane partial sums and the butterfly give
+//     the bits spearman_kernel's sequential loop gives
+//   * p: lane c evaluates column c's p-value (the serial part: a product of <= m/2 factors and a continued fraction)
+// No allocation, no host round trip, fixed launch shape: it can be captured into a graph.
+// ---------------------------------------------------------------------------------
+#define TC_CAP 128
+#define TC_COLS 8
+
+struct TcLds {                     // compacted survivors in LDS: every slot valid, survivor j = slot j
+    const double* xs; const double* ys; int m;
+    __device__ __forceinline__ int slots() const { return m; }
+    __device__ __forceinline__ bool valid(int) const { return true; }
+    __device__ __forceinline__ double x(int k) const { return xs[k]; }
+    __device__ __forceinline__ double y(int k) const { return ys[k]; }
+    __device__ __forceinline__ int survivor(int j) { return j; }
+};
+struct TcGlobal {                  // the group in place: slot k = window k, survivor j found by a cursor
+    const double* xa; const double* ya; int ld; const int* st; int n;
+    int cur = -1, seen = -1;       // slot `cur` is survivor number `seen`
+    __device__ __forceinline__ int slots() const { return n; }
+    __device__ __forceinline__ bool valid(int k) const { return !(st && (st[k] & (TDA_WIN_DEGENERATE | TDA_WIN_TOO_LARGE))); }
+    __device__ __forceinline__ double x(int k) const { return xa[(size_t)k * ld]; }
+    __device__ __forceinline__ double y(int k) const { return ya[(size_t)k * ld]; }
+    // numpy's pairwise tree asks for its terms in rising order, so the cursor only ever steps forward within a sum
+    __device__ __forceinline__ int survivor(int j)
+    {
+        if (j < seen) { cur = -1; seen = -1; }
+        while (seen < j) { ++cur; seen += valid(cur) ? 1 : 0; }
+        return cur;
+    }
+};
+
+// np.sum of f(0) .. f(m-1), the same sum in every lane of the wave: no call, no private array
+template <class F>
+__device__ __forceinline__ double tc_sum(const F& f, int m)
+{
+    return m <= 128 ? np_pairwise_leaf(f, 0, m) : np_pairwise_split_uniform(f, 0, m);
+}
+
+// r of one column; 0 under the guard of cmp:110 (m >= 5 is the caller's)
+template <class A>
+__device__ __forceinline__ double tc_column(A acc, int m, int lane)
+{
+    auto fx = [&](int j) { return acc.x(acc.survivor(j)); };
+    auto fy = [&](int j) { return acc.y(acc.survivor(j)); };
+    const double mx = tc_sum(fx, m) / m, my = tc_sum(fy, m) / m;
+    auto vx = [&](int j) { const double z = acc.x(acc.survivor(j)) - mx; return z * z; };
+    auto vy = [&](int j) { const double z = acc.y(acc.survivor(j)) - my; return z * z; };
+    const double sx = sqrt(tc_sum(vx, m) / m), sy = sqrt(tc_sum(vy, m) / m);
+    if (!(sx > 1e-10 && sy > 1e-10)) return 0.0;
+    // average ranks (scipy.stats.rankdata, method="average"), centred: sum of ranks = m(m+1)/2
+    const double mr = 0.5 * (double)(m + 1);
+    const int K = acc.slots();
+    double sxx = 0.0, syy = 0.0, sxy = 0.0;
+    for (int i0 = 0; i0 < K; i0 += 64) {
+        const int i = i0 + lane;
+        if (i < K && acc.valid(i)) {
+            const double xi = acc.x(i), yi = acc.y(i);
+            int lx = 0, ex = 0, ly = 0, ey = 0;
+            for (int j = 0; j < K; ++j) {
+                if (!acc.valid(j)) continue;
+                const double xj = acc.x(j), yj = acc.y(j);
+                lx += xj < xi; ex += xj == xi; ly += yj < yi; ey += yj == yi;
+            }
+            const double rx = (double)lx + 0.5 * (double)(ex + 1) - mr;
+            const double ry = (double)ly + 0.5 * (double)(ey + 1) - mr;
+            sxx += rx * rx; syy += ry * ry; sxy += rx * ry;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sxx += __shfl_xor(sxx, off, 64); syy += __shfl_xor(syy, off, 64); sxy += __shfl_xor(sxy, off, 64);
+    }
+    double r = (sxy / sqrt(sxx)) / sqrt(syy);
+    if (r > 1.0) r = 1.0;
+    if (r < -1.0) r = -1.0;
+    return r;
+}
+
+// Continued fraction of the incomplete beta function, modified Lentz evaluation (Numerical Recipes 6.4): converges in
+// O(sqrt(max(a, b))) trips for x < (a + 1) / (a + b + 2).
+__device__ __forceinline__ double tc_betacf(double a, double b, double x)
+{
+    const double tiny = 1e-300, eps = 3e-16;            // (one ulp of 1 and a little: del may settle an ulp off 1)
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double h = d;
+    for (int i = 1; i <= 20000; ++i) {
+        const double i2 = 2.0 * i;
+        double aa = i * (b - i) * x / ((qam + i2) * (a + i2));
+        d = 1.0 + aa * d; if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        h *= d * c;
+        aa = -(a + i) * (qab + i) * x / ((a + i2) * (qap + i2));
+        d = 1.0 + aa * d; if (fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        h *= del;
+        if (fabs(del - 1.0) <= eps) break;
+    }
+    return h;
+}
+// Two-sided p-value of a correlation r of m pairs under Student's t with m - 2 degrees of freedom (what
+// scipy.stats.spearmanr reports): I_x(a, 1/2) with x = 1 - r^2, a = (m - 2) / 2.  a is an integer or a half-integer, so
+// 1 / B(a, 1/2) is a finite product from 1 / B(1/2, 1/2) = 1 / pi or 1 / B(1, 1/2) = 1 / 2; (1 - x)^(1/2) = |r|.
+// Exactly 0 at r = +-1 and exactly 1 at r = 0.
+__device__ __forceinline__ double tc_pvalue(double r, int m)
+{
+    const double x = (1.0 + r) * (1.0 - r), y = r * r;
+    if (!(x > 0.0)) return 0.0;
+    if (!(y > 0.0)) return 1.0;
+    const int k = m - 2;
+    const double a = 0.5 * (double)k;
+    double ib = (k & 1) ? 0.31830988618379067154 : 0.5;
+    for (double t = (k & 1) ? 0.5 : 1.0; t < a; t += 1.0) ib *= (t + 0.5) / t;
+    const double bt = ib * fabs(r) * exp(a * log(x));
+    double p;
+    if (x < (a + 1.0) / (a + 2.5)) p = bt * tc_betacf(a, 0.5, x) / a;
+    else p = 1.0 - bt * tc_betacf(0.5, a, y) / 0.5;
+    return p < 0.0 ? 0.0 : (p > 1.0 ? 1.0 : p);
+}
+
+__global__ void __launch_bounds__(64)
+temporal_corr_kernel(const double* __restrict__ fa, const double* __restrict__ fe, int ld, const int* __restrict__ cols,
+                     int n_cols, const int* __restrict__ seg_off, int n_seg, const int* __restrict__ status_b,
+                     double* __restrict__ out)
+{
+    __shared__ double sx[TC_COLS][TC_CAP], sy[TC_COLS][TC_CAP];
+    const int seg = blockIdx.x;
+    if (seg >= n_seg) return;
+    const int lane = lane_id();
+    const int s0 = uni(seg_off[seg]), n = uni(seg_off[seg + 1]) - s0;
+    const int* st = status_b ? status_b + s0 : nullptr;
+    const int skip = TDA_WIN_DEGENERATE | TDA_WIN_TOO_LARGE;
+    int m = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        m += __popcll(__ballot(i < n && !(st && (st[i] & skip))));
+    }
+    double* row = out + (size_t)seg * 2 * n_cols;
+    if (m < 5) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int c = lane; c < 2 * n_cols; c += 64) row[c] = m == 0 ? nan : (double)(c & 1);
+        return;
+    }
+    for (int c0 = 0; c0 < n_cols; c0 += TC_COLS) {
+        const int nc = n_cols - c0 < TC_COLS ? n_cols - c0 : TC_COLS;
+        double r_mine = 0.0;                                           // lane c: r of column c0 + c
+        if (m <= TC_CAP) {
+            int base = 0;
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                const bool alive = i < n && !(st && (st[i] & skip));
+                const u64 bal = __ballot(alive);
+                const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+                if (alive) {
+                    const double* pa = fa + (size_t)(s0 + i) * ld;
+                    const double* pe = fe + (size_t)(s0 + i) * ld;
+                    for (int c = 0; c < nc; ++c) { const int col = cols[c0 + c]; sx[c][pos] = pa[col]; sy[c][pos] = pe[col]; }
+                }
+                base += __popcll(bal);
+            }
+            wave_sync();
+            for (int c = 0; c < nc; ++c) {
+                const double r = tc_column(TcLds{sx[c], sy[c], m}, m, lane);
+                r_mine = lane == c ? r : r_mine;
+            }
+            wave_sync();                                               // (the next trip overwrites the series)
+        } else {
+            for (int c = 0; c < nc; ++c) {
+                const int col = cols[c0 + c];
+                const double r = tc_column(TcGlobal{fa + (size_t)s0 * ld + col, fe + (size_t)s0 * ld + col, ld, st, n}, m, lane);
+                r_mine = lane == c ? r : r_mine;
+            }
+        }
+        if (lane < nc) {
+            row[2 * (c0 + lane)] = r_mine;
+            row[2 * (c0 + lane) + 1] = tc_pvalue(r_mine, m);
+        }
+    }
+}
+
+tda_status launch_temporal_corr(tda_ctx* ctx, const double* fa, const double* fe, int ld, const int* cols, int n_cols,
+                                const int* seg_off, int n_seg, const int* status_b, double* out, hipStream_t st)
+{
+    if (n_seg == 0 || n_cols == 0) return TDA_OK;
+    hipLaunchKernelGGL(temporal_corr_kernel, dim3(n_seg), dim3(64), 0, st, fa, fe, ld, cols, n_cols, seg_off, n_seg,
+                       status_b, out);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }

@@ -16,6 +16,10 @@ reference's on-disk formats.
                             results/eeg_audio_tda_detailed.csv
   validate_distance_matrix  scripts/tda_eeg_classification_v2.py:110-140 (first window of every band, v2:380-382)
   save_dataset              v2:670-688 incl. features/metadata.csv / metadata.json
+  comparison_rows / comparison_summary / run_comparison
+                            cmp:145-157 and cmp:161-220 from the rows and correlations of a batched pass
+                            (recordings.*RecordingPass(correlations=True)): the detailed table and the per-band statistics
+                            of results/eeg_audio_tda_comparison.json
 """
 import hashlib
 from pathlib import Path
@@ -439,7 +443,8 @@ def detailed_rows(all_results):
 def run_analysis(data_dir, graphs_dir, out_csv=None, conditions=("slow", "fast")):
     """cmp:126-157, the per-recording half: every data/<condition>/*.mat in sorted order through
     process_recording_file, then the detailed table (written as results/eeg_audio_tda_detailed.csv when out_csv is
-    given).  The statistics and plots behind it (cmp:159-349) are outside this engine."""
+    given).  The statistics behind it (cmp:161-220) are comparison_summary on that table; the batched route from raw
+    recordings to both is run_comparison.  The plots (cmp:238-304) are outside this engine."""
     import pandas as pd
     all_results = []
     for condition in conditions:
@@ -515,3 +520,115 @@ def control_summary(rows, subjects, conditions=None, bands=BANDS):
             results[band]["p_fdr"] = float(pfdr[i])
             results[band]["sig_fdr"] = bool(reject[i])
     return results
+
+
+# --------------------------------------------------------------------------------------
+# scripts/tda_eeg_audio_comparison.py from a batched pass: the detailed table and the per-band statistics
+# --------------------------------------------------------------------------------------
+COMPARISON_CONDITIONS = ("slow", "fast")        # cmp:131,171-172
+_SUMMARY_MEANS = ("wasserstein_h0", "wasserstein_h1", "corr_mean_persistence_r", "corr_persistence_entropy_r")   # cmp:165-169
+
+
+def comparison_rows(rows, corr, filenames, conditions, bands=BANDS):
+    """cmp:145-157 from the outputs of a pass built with correlations=True: rows (n_rec, n_bands, >= 4) [W_H0, W_H1, tau,
+    n_windows, ...], corr (n_rec, n_bands, 10) [r, p] of the five series.  One dict of DETAILED_COLUMNS per (recording,
+    band), recordings in the order given, bands in `bands` order; subject = the file name up to its first "_" (cmp:51).
+    Left out, as the reference leaves them out: a recording without a window (n_windows == 0, cmp:71-72) and a band none of
+    whose windows reached the distances (NaN correlation cells, cmp:101-102)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    corr = np.asarray(corr, dtype=np.float64)
+    bands = list(bands)
+    n_rec = len(filenames)
+    assert len(conditions) == n_rec and rows.shape[:2] == (n_rec, len(bands)) and rows.shape[2] >= 4
+    assert corr.shape == (n_rec, len(bands), len(DETAILED_COLUMNS) - 8)
+    out = []
+    for r in range(n_rec):
+        fn = str(filenames[r])
+        for b, band in enumerate(bands):
+            if rows[r, b, 3] == 0 or np.isnan(corr[r, b]).any():
+                continue
+            row = {"filename": fn, "condition": str(conditions[r]), "subject": fn.split("_")[0], "band": band,
+                   "wasserstein_h0": float(rows[r, b, 0]), "wasserstein_h1": float(rows[r, b, 1]),
+                   "n_windows": int(rows[r, b, 3]), "tau": int(rows[r, b, 2])}
+            row.update((c, float(v)) for c, v in zip(DETAILED_COLUMNS[8:], corr[r, b]))
+            out.append(row)
+    return out
+
+
+def comparison_summary(table, bands=BANDS, n_permutations=1000, alpha=0.05):
+    """cmp:161-220, host only: the `band_results` of results/eeg_audio_tda_comparison.json from the detailed table (the
+    dicts of comparison_rows / detailed_rows, or a DataFrame with those columns).  Per band: the means per (subject,
+    condition) of the two distances and two correlations (cmp:165-169), the subjects present in both conditions, sorted
+    (cmp:173-175); below 5 of them only {"n_subjects", "band"}; otherwise Wilcoxon's p of the slow - fast differences of
+    W_H0, W_H1 and corr_mean_persistence_r (1.0 when all are zero, cmp:184-186), the sign-flip permutation p of W_H1
+    (default_rng(42) anew per band, n_permutations draws of choice([-1, 1], n), (exceed + 1) / (n_permutations + 1),
+    cmp:189-193), Cohen's d with the sample standard deviation (cmp:196), the direction, how many subjects have slow <
+    fast and the condition means.  Then Benjamini-Hochberg over the bands' wass_h1_p, a missing one counting as 1.0, written
+    into every band (cmp:216-220)."""
+    from scipy.stats import wilcoxon
+    if hasattr(table, "to_dict"):
+        table = table.to_dict("records")
+    bands = list(bands)
+    slow_c, fast_c = COMPARISON_CONDITIONS
+    stats = {}
+    for band in bands:
+        cells = {}                                                       # (subject, condition) -> rows of the four columns
+        for row in table:
+            if row["band"] == band:
+                cells.setdefault((str(row["subject"]), str(row["condition"])), []).append([row[c] for c in _SUMMARY_MEANS])
+        means = {k: np.mean(np.asarray(v, dtype=np.float64), axis=0) for k, v in cells.items()}
+        common = sorted({s for s, c in means if c == slow_c} & {s for s, c in means if c == fast_c})
+        n = len(common)
+        bs = {"n_subjects": n, "band": band}
+        if n >= 5:
+            slow = np.array([means[s, slow_c] for s in common])
+            fast = np.array([means[s, fast_c] for s in common])
+            d0, d1, dc = (slow[:, k] - fast[:, k] for k in (0, 1, 2))
+            p0, p1, pc = (float(wilcoxon(d)[1]) if np.any(d != 0) else 1.0 for d in (d0, d1, dc))
+            rng = np.random.default_rng(42)
+            obs = abs(np.mean(d1))
+            exceed = sum(1 for _ in range(n_permutations) if abs(np.mean(d1 * rng.choice([-1, 1], n))) >= obs)
+            bs.update({
+                "wass_h0_slow": float(slow[:, 0].mean()), "wass_h0_fast": float(fast[:, 0].mean()), "wass_h0_p": p0,
+                "wass_h1_slow": float(slow[:, 1].mean()), "wass_h1_fast": float(fast[:, 1].mean()), "wass_h1_p": p1,
+                "wass_h1_perm_p": float((exceed + 1) / (n_permutations + 1)),
+                "wass_h1_cohens_d": float(np.mean(d1) / (np.std(d1, ddof=1) + 1e-10)),
+                "wass_h1_direction": "slow < fast" if np.mean(d1) < 0 else "slow > fast",
+                "corr_slow": float(slow[:, 2].mean()), "corr_fast": float(fast[:, 2].mean()), "corr_p": pc,
+                "n_slow_lower": int(np.sum(d1 < 0)),
+            })
+        stats[band] = bs
+    reject, pfdr = fdr_bh([stats[b].get("wass_h1_p", 1.0) for b in bands], alpha)
+    for i, band in enumerate(bands):
+        stats[band]["wass_h1_p_fdr"] = float(pfdr[i])
+        stats[band]["wass_h1_sig_fdr"] = bool(reject[i])
+    return stats
+
+
+def run_comparison(pass_, raw_h, second_h, filenames, conditions, out_csv=None, out_json=None):
+    """cmp:126-220 from raw recordings in one batched pass: pass_ is a recordings.RecordingPass, RaggedRecordingPass or
+    RaggedAudioRecordingPass built with correlations=True, raw_h / second_h the two pinned inputs of its `run`.  Returns
+    (rows, corr, table, summary): the pass' rows and correlations as numpy arrays, comparison_rows and
+    comparison_summary of them.  out_csv: the table as results/eeg_audio_tda_detailed.csv; out_json: the counts and
+    `band_results` of results/eeg_audio_tda_comparison.json."""
+    if not getattr(pass_, "correlations", False):
+        raise ValueError("run_comparison needs a pass built with correlations=True")
+    bands = BANDS if len(pass_.bands) == len(BANDS) else [f"band{b}" for b in range(len(pass_.bands))]
+    rows = pass_.run(raw_h, second_h).numpy().copy()
+    corr = pass_.corr_h.numpy().copy()
+    table = comparison_rows(rows, corr, filenames, conditions, bands)
+    summary = comparison_summary(table, bands)
+    if out_csv:
+        import pandas as pd
+        Path(out_csv).parent.mkdir(parents=True, exist_ok=True)
+        pd.DataFrame(table, columns=DETAILED_COLUMNS).to_csv(out_csv, index=False)
+    if out_json:
+        import json
+        Path(out_json).parent.mkdir(parents=True, exist_ok=True)
+        kept = {(t["filename"], t["condition"]) for t in table}
+        doc = {"n_recordings": len(kept), "n_subjects": len({t["subject"] for t in table}),
+               "n_slow": sum(1 for _, c in kept if c == COMPARISON_CONDITIONS[0]),
+               "n_fast": sum(1 for _, c in kept if c == COMPARISON_CONDITIONS[1]), "band_results": summary}
+        with open(out_json, "w") as f:
+            json.dump(doc, f, indent=2)
+    return rows, corr, table, summary

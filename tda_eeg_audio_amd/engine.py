@@ -5,7 +5,7 @@ Every function here is a thin marshalling layer over one C-ABI entry point of
 include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU path.
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
-                 tau_batch, features_batch, aggregate_batch, wasserstein_batch
+                 tau_batch, features_batch, aggregate_batch, wasserstein_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -205,6 +205,33 @@ def _degenerate(fa, fb, off, cols):
         a, b = off[s], off[s + 1]
         for k, c in enumerate(cols):
             out[s, k] = (b - a) < 5 or np.std(fa[a:b, c]) <= 1e-10 or np.std(fb[a:b, c]) <= 1e-10
+    return out
+
+
+def _check_cols(cols, ld):
+    cc = i32(cols).ravel()
+    if len(cc) == 0 or cc.min() < 0 or cc.max() >= ld:
+        raise ValueError(f"feature columns {cc.tolist()} outside [0, {ld})")
+    return cc
+
+
+def temporal_corr_batch(feat_a, feat_b, seg_off, status_b=None, cols=SPEARMAN_COLS, ctx=None):
+    """cmp:90-91,104-114 on the per-window H1 feature matrices of a step, (n_win, 11) each: per group (n_seg, 2 *
+    len(cols)) = [r, p] per column over the windows whose audio status has neither TDA_WIN_DEGENERATE nor
+    TDA_WIN_TOO_LARGE; NaN where none is left, (0, 1) under the reference's guard.  r and p both come from the device."""
+    ctx = ctx or get_ctx()
+    fa = f64(feat_a); fb = f64(feat_b); off = i32(seg_off)
+    assert fa.ndim == 2 and fa.shape == fb.shape
+    cc = _check_cols(cols, fa.shape[1])
+    st = None if status_b is None else i32(status_b)
+    assert st is None or st.shape == (fa.shape[0],)
+    n_seg = len(off) - 1
+    out = np.empty((n_seg, 2 * len(cc)))
+    if fa.shape[0] == 0:                           # groups without a window: nothing to stage
+        out.fill(np.nan)
+        return out
+    ctx.check(ctx.lib.tda_temporal_corr_batch(ctx.h, ptr(fa), ptr(fb), fa.shape[0], fa.shape[1], ptr(cc), len(cc), ptr(off),
+                                              n_seg, ptr(st), ptr(out)))
     return out
 
 
@@ -408,6 +435,41 @@ def recording_rows_dev(w0_t, w1_t, tau_seg_t, fe0_t, fe1_t, seg_off_t, out_t=Non
     ctx.check(ctx.lib.tda_recording_rows_dev(ctx.h, _tp(w0_t), _tp(w1_t), _tp(tau_seg_t), _tp(fe0_t), _tp(fe1_t),
                                              _tp(seg_off_t), n_seg, _tp(out_t), _tp(status_a), _tp(status_b),
                                              _tp(seg_flags), _stream()))
+    return out_t
+
+
+_COLS_DEV = {}
+
+
+def _cols_dev(cols, ld, device):
+    """The column list on the device, uploaded once per (list, device): temporal_corr_dev must not copy inside a capture."""
+    import torch
+    key = (tuple(int(c) for c in cols), int(ld), str(device))
+    t = _COLS_DEV.get(key)
+    if t is None:
+        t = _COLS_DEV[key] = torch.from_numpy(_check_cols(cols, ld)).to(device)
+    return t
+
+
+def temporal_corr_dev(fa_t, fe_t, seg_off_t, status_b=None, cols=SPEARMAN_COLS, out_t=None, ctx=None):
+    """temporal_corr_batch on device tensors: fa_t, fe_t (n_win, ld) float64 (pipeline.Workspace's fa1 / fe1), seg_off_t
+    int32, status_b the audio Rips status words or None -> out_t (n_seg, 2 * len(cols)) float64, [r, p] per column (for
+    the default columns the order of drivers.DETAILED_COLUMNS[8:]).  One launch on torch's current stream; cols may
+    also be an int32 device tensor."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert fa_t.is_cuda and fa_t.dtype == torch.float64 and fa_t.is_contiguous() and fa_t.dim() == 2
+    assert fe_t.dtype == torch.float64 and fe_t.is_contiguous() and fe_t.shape == fa_t.shape
+    assert seg_off_t.dtype == torch.int32 and seg_off_t.is_contiguous()
+    assert status_b is None or (status_b.dtype == torch.int32 and status_b.is_contiguous() and status_b.numel() >= fa_t.shape[0])
+    cols_t = cols if isinstance(cols, torch.Tensor) else _cols_dev(cols, fa_t.shape[1], fa_t.device)
+    assert cols_t.dtype == torch.int32 and cols_t.is_cuda
+    n_seg, n_cols = seg_off_t.numel() - 1, int(cols_t.numel())
+    if out_t is None:
+        out_t = torch.empty((n_seg, 2 * n_cols), dtype=torch.float64, device=fa_t.device)
+    assert out_t.is_contiguous() and out_t.numel() >= n_seg * 2 * n_cols
+    ctx.check(ctx.lib.tda_temporal_corr_dev(ctx.h, _tp(fa_t), _tp(fe_t), fa_t.shape[1], _tp(cols_t), n_cols, _tp(seg_off_t),
+                                            n_seg, _tp(status_b), _tp(out_t), _stream()))
     return out_t
 
 

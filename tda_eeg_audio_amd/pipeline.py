@@ -16,12 +16,16 @@ import numpy as np
 from . import engine
 
 RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG features per recording-band
+CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
 
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
-    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP):
+    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False):
+        """correlations=True: run_step also fills `corr` (n_seg, 10): Spearman [r, p] of the five feature series of
+        engine.SPEARMAN_COLS, audio H1 against EEG H1, per group (cmp:104-114; engine.temporal_corr_dev).  `result` is
+        the same either way."""
         import torch
         self.n_win, self.device = n_win, device
         seg_off = np.asarray(seg_off, np.int32)
@@ -44,6 +48,8 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
+        self.corr = torch.empty((self.n_seg, CORR_COLS), **f64) if correlations else None
+        self.corr_cols = torch.tensor(engine.SPEARMAN_COLS, dtype=torch.int32, device=device) if correlations else None
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -79,6 +85,7 @@ class Workspace:
         for name in ("tau_seg", "seg_flags", "flags_host", "result"):
             setattr(v, name, getattr(self, name)[:n_seg])
         v.dist = None if self.dist is None else self.dist[:n_win]
+        v.corr = None if self.corr is None else self.corr[:n_seg]
         return v
 
 
@@ -154,6 +161,10 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     stage("finish", lambda: engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0),
                                                         (ws.eeg.h1, ws.eeg.c1, True, ws.fe1),
                                                         (ws.aud.h1, ws.aud.c1, True, ws.fa1)], ctx=ctx))
+    if ws.corr is not None:
+        # temporal correlation of the H1 feature series over the windows that reach the distances (cmp:90-91,104-114)
+        stage("temporal_corr", lambda: engine.temporal_corr_dev(ws.fa1, ws.fe1, ws.seg_off, ws.aud.status, cols=ws.corr_cols,
+                                                                out_t=ws.corr, ctx=ctx))
     stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
                                                            out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
     stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
@@ -443,3 +454,4 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
+# (a Workspace(correlations=True) has one more, "temporal_corr", after "finish")

@@ -18,6 +18,10 @@ and the upload of shard k + 1 overlaps the compute of shard k (two sets of buffe
 (class-overflow flags of its groups) after the next one has been queued.
 The rows equal pipeline.run_step on the stacked windows of the same band-passed signals bit for bit
 (tests/test_gpu_frontend.py::test_recording_pass_equals_stacked_windows).
+With correlations=True the passes also return the third result of the script per (recording, band): Spearman r and p of
+the five H1 feature series, audio against EEG (cmp:104-114), computed on the device from the step's own feature matrices
+(engine.temporal_corr_dev) and downloaded beside the rows as corr_h (n_rec, 5, 10); drivers.comparison_rows /
+comparison_summary turn rows and corr_h into the script's table and statistics.
 """
 import numpy as np
 
@@ -34,7 +38,10 @@ def select_windows(n_win, max_windows=MAX_WINDOWS):
 
 class RecordingPass:
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
-                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None):
+                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False):
+        """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
+        feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
+        drivers.DETAILED_COLUMNS[8:].  The rows are the same either way."""
         import os
         import torch
         from scipy import signal
@@ -47,6 +54,7 @@ class RecordingPass:
         assert self.per_rec > 0, "recordings shorter than one window"
         self.pick = select_windows(self.per_rec, max_windows)
         self.k = len(self.pick)
+        self.correlations, self.corr_h = bool(correlations), None
         S, L, k, nb = self.S, self.L, self.k, len(self.bands)
         nyq = fs / 2                                                   # utils.py:66-74
         self.bas = [signal.butter(4, [max(lo / nyq, 0.001), min(hi / nyq, 0.999)], btype="band") for lo, hi in self.bands]
@@ -62,7 +70,8 @@ class RecordingPass:
         self.set = [dict(raw=torch.empty((S, n_ch, L), **f64), env=torch.empty((S, L), **f64),
                          y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
                          aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
-                         ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch),
+                         ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations),
+                         corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                          work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * 3 * 9), **f64),
                          # a stream pair per buffer set: the filters of shard k + 1 (chains of dependent operations on few
                          # waves) run beside the Rips kernels of shard k (which fill the vector units)
@@ -91,8 +100,14 @@ class RecordingPass:
                 st["ya"].view(nb * S, self.L).unfold(1, self.win, self.step).index_select(1, self.pick_t))
         preprocess.bandpass_bank_dev(st["raw"].view(S * self.n_ch, self.L), self.bands, self.fs, y_t=st["y"], work_t=st["work"], ctx=ctx)
         st["main"].wait_stream(st["side"])
-        res = self._rips_step(st, "one")                               # (nb * S, 48), band-major groups
-        st["rows"].copy_(res.view(nb, S, pipeline.RESULT_COLS).transpose(0, 1))
+        self._rows(st, self._rips_step(st, "one"))
+
+    def _rows(self, st, res):
+        """(nb * S, 48) band-major groups -> the shard's rows (and, with correlations, the same for the workspace's corr)."""
+        nb = len(self.bands)
+        st["rows"].copy_(res.view(nb, self.S, pipeline.RESULT_COLS).transpose(0, 1))
+        if self.correlations:
+            st["corr"].copy_(st["ws"].corr.view(nb, self.S, pipeline.CORR_COLS).transpose(0, 1))
 
     def run(self, raw_h, env_h, rows_h=None):
         """raw_h (n_rec, n_ch, L), env_h (n_rec, L): pinned float64 host tensors.  Returns rows_h (n_rec, n_bands, 48),
@@ -103,6 +118,8 @@ class RecordingPass:
         nb = len(self.bands)
         if rows_h is None:
             rows_h = torch.empty((n_rec, nb, pipeline.RESULT_COLS), dtype=torch.float64).pin_memory()
+        if self.correlations and (self.corr_h is None or self.corr_h.shape[0] != n_rec):
+            self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
         S = self.S
         shards = [(s0, min(S, n_rec - s0)) for s0 in range(0, n_rec, S)]
         pend = []
@@ -125,6 +142,8 @@ class RecordingPass:
             with torch.cuda.stream(self.back):
                 self.back.wait_event(st["done"])
                 rows_h[s0:s0 + n].copy_(st["rows"][:n], non_blocking=True)
+                if self.correlations:
+                    self.corr_h[s0:s0 + n].copy_(st["corr"][:n], non_blocking=True)
                 st["down"].record(self.back)
             pend.append(i)
             if len(pend) >= self.n_sets:            # (the GPU has the later shards to work on while the host looks at this one;
@@ -144,11 +163,11 @@ class RecordingPass:
         fl = st["ws"].flags_host
         if bool((fl & 2).any()):
             self.repairs += 1
-            nb = len(self.bands)
             with torch.cuda.stream(st["main"]):
-                res = self._rips_step(st, "auto")
-                st["rows"].copy_(res.view(nb, self.S, pipeline.RESULT_COLS).transpose(0, 1))
+                self._rows(st, self._rips_step(st, "auto"))
                 rows_h[s0:s0 + n].copy_(st["rows"][:n])
+                if self.correlations:
+                    self.corr_h[s0:s0 + n].copy_(st["corr"][:n])
                 fl.copy_(st["ws"].seg_flags, non_blocking=True)
                 st["main"].synchronize()
         # (groups of the idle rows of a short last shard repeat real recordings: their flags say nothing new)
@@ -250,12 +269,15 @@ class RaggedRecordingPass:
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None):
+                 plan=None, correlations=False):
+        """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
+        recording without a window."""
         import torch
         from scipy import signal
         self.ctx = ctx or get_ctx()
         self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.n_ch, self.fs = n_ch, fs
+        self.correlations, self.corr_h = bool(correlations), None
         self.bands = list(dict(bands).values())
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -295,8 +317,9 @@ class RaggedRecordingPass:
         for _ in range(self.n_sets):
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
-                                    n_ch=n_ch)
+                                    n_ch=n_ch, correlations=self.correlations)
             self.set.append(dict(
+                corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
@@ -322,6 +345,12 @@ class RaggedRecordingPass:
             rows[:, :, 3] = 0.0
         if d["n_live"]:
             rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], pipeline.RESULT_COLS).transpose(0, 1))
+        if self.correlations:
+            corr = st["corr"][:d["n"]]
+            if d["n_live"] < d["n"]:
+                corr.fill_(float("nan"))
+            if d["n_live"]:
+                corr.index_copy_(0, d["live"], st["views"][i].corr.view(len(self.bands), d["n_live"], pipeline.CORR_COLS).transpose(0, 1))
 
     def _front_end(self, st, i):
         """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""
@@ -351,6 +380,8 @@ class RaggedRecordingPass:
         nb = len(self.bands)
         if rows_h is None:
             rows_h = torch.empty((self.n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
+        if self.correlations and self.corr_h is None:
+            self.corr_h = torch.empty((self.n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
         raw_f, env_f = raw_packed_h.view(-1), env_packed_h.view(-1)
         pend = []
         for i, d in enumerate(self.shards):
@@ -372,6 +403,8 @@ class RaggedRecordingPass:
             with torch.cuda.stream(self.back):
                 self.back.wait_event(st["done"])
                 rows_h[r0:r1].copy_(st["rows"][:d["n"]], non_blocking=True)
+                if self.correlations:
+                    self.corr_h[r0:r1].copy_(st["corr"][:d["n"]], non_blocking=True)
                 st["down"].record(self.back)
             pend.append(i)
             if len(pend) >= self.n_sets:
@@ -395,6 +428,8 @@ class RaggedRecordingPass:
             with torch.cuda.stream(st["main"]):
                 self._rows(st, i, self._rips_step(st, i, "auto"))
                 rows_h[d["r0"]:d["r1"]].copy_(st["rows"][:d["n"]])
+                if self.correlations:
+                    self.corr_h[d["r0"]:d["r1"]].copy_(st["corr"][:d["n"]])
                 fl.copy_(st["views"][i].seg_flags, non_blocking=True)
                 st["main"].synchronize()
         if bool(fl.any()):
@@ -416,7 +451,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75):
+                 overlap=0.75, correlations=False):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -425,7 +460,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
         plan = RaggedPlan(eeg_lengths, A.n_out, n_ch=n_ch, n_bands=len(dict(bands)), fs=fs, window_sec=window_sec,
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
-                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan)
+                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)
@@ -570,9 +605,14 @@ class ControlPass(RaggedRecordingPass):
     ROW_COLS = CONTROL_COLS
 
     def __init__(self, eeg_lengths, env_lengths=None, partner=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2,
-                 ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75):
+                 ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
+                 correlations=False):
         import torch
         from ._lib import MAX_POINTS
+        if correlations:
+            # its EEG and audio windows are selected apart (mvm:44-49,74-78) and paired by position with two audios:
+            # there is no series of (audio, EEG) window pairs in cmp's sense
+            raise ValueError("ControlPass has no temporal correlations (correlations=True): use RaggedRecordingPass")
         plan = ControlPlan(eeg_lengths, env_lengths, partner, shard_samples, n_ch, len(dict(bands)), fs, window_sec, overlap,
                            max_windows)
         super().__init__(eeg_lengths, env_lengths, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,

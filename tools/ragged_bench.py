@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """
 tools/ragged_bench.py -- the raw-recordings leg on the study's REAL length column, one JSON line:
-    python3 tools/ragged_bench.py [--runs 2] [--shard-samples N]
+    python3 tools/ragged_bench.py [--runs 2] [--shard-samples N] [--correlations]
 1,416 recordings at the lengths of tests/golden/corpus_n_samples.npy (sum 6,007,447 samples x 47 channels, envelope
 length = EEG length), synthetic samples as in bench.recordings_leg, through recordings.RaggedRecordingPass; beside it,
 in the same process, the equal-length recordings.RecordingPass at 1,416 x 4,243 samples (the corpus mean) in shards of 236.
 Reported: window pairs/s, ms per run, h2d GB/s, shards, and the same for the equal-length leg.
+--correlations: the ragged leg once more in the same process with RaggedRecordingPass(correlations=True) (Spearman r and p
+of the five H1 feature series per recording-band, cmp:104-114, beside the rows): its ms per run next to the plain one,
+whether the rows are bit-identical to the plain pass', and how many correlation cells are finite.
 """
 import argparse
 import json
@@ -44,6 +47,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--shard-samples", type=int, default=None)
+    ap.add_argument("--correlations", action="store_true")
     a = ap.parse_args()
     import torch
     from tda_eeg_audio_amd import _lib, recordings
@@ -60,6 +64,20 @@ def main():
     out = {"value": n_pairs / dt, "unit": "window pairs/s", "ms_per_run": dt * 1e3, "h2d_GBps": nbytes / dt / 1e9,
            "shards": len(rp.plan.shards), "recordings": len(L), "samples": int(L.sum()), "window_pairs": n_pairs,
            "rows_finite": bool(torch.isfinite(rows).all().item()), "repairs": rp.repairs}
+    if a.correlations:
+        rows_plain = rows.clone()
+        cp = recordings.RaggedRecordingPass(L, None, dev, ctx=ctx, correlations=True, **kw)
+        # on the plain pass' streams: which hardware queue a stream lands on depends on how many were made before it, and
+        # that alone moves this leg by 2.6 ms (the second of two identical passes built in one process: 59.6 against 57.0)
+        cp.copy, cp.back = rp.copy, rp.back
+        for sc, sp in zip(cp.set, rp.set):
+            sc["main"], sc["side"] = sp["main"], sp["side"]
+        dtc, rows_c = timed(lambda r: cp.run(raw_h, env_h, r), a.runs)
+        out["correlations"] = {"value": n_pairs / dtc, "ms_per_run": dtc * 1e3, "ms_over_plain": (dtc - dt) * 1e3,
+                               "rows_identical": bool(np.array_equal(rows_c.numpy(), rows_plain.numpy(), equal_nan=True)),
+                               "cells_finite": int(torch.isfinite(cp.corr_h).sum().item()), "cells": cp.corr_h.numel(),
+                               "d2h_bytes": cp.corr_h.numel() * 8, "repairs": cp.repairs}
+        del cp, rows_plain, rows_c
     del rp, raw_h, env_h
     # the equal-length leg at the corpus mean, same process
     n_eq, S = int(round(L.mean())), 236
@@ -73,6 +91,8 @@ def main():
                            "shards": -(-len(L) // S), "window_pairs": pe}
     out["ratio_pairs_per_s"] = out["value"] / out["equal_length"]["value"]
     print(json.dumps(out))
+    if a.correlations and not out["correlations"]["rows_identical"]:
+        sys.exit("rows of the pass with correlations differ from the plain pass' rows")
 
 
 if __name__ == "__main__":
