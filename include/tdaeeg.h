@@ -329,7 +329,8 @@ tda_status tda_features_batch(tda_ctx* ctx, const double* dgm, const int* cnt, i
                               int cap, double* feat);
 
 /* ---- finishing pass over the diagrams of a batch ---------------------------------
- * Up to four diagram sets in ONE launch (one wavefront per diagram): for sets with order != 0 the H1 rows are put
+ * Up to four diagram sets in ONE call (a launch for the diagrams of up to 64 rows and, where a set has room for more, one
+ * for the larger ones: tda_set_launch_scheme): for sets with order != 0 the H1 rows are put
  * into ripser's order in place, and where feat != NULL the 11 scalars of extract_features are written -- what
  * tda_features_batch_dev does for one set.  The driver of a whole step runs the Rips entry points under
  * TDA_ORDER_DEFERRED and finishes the EEG H0 / EEG H1 / audio H1 diagrams of the batch with one call
@@ -348,6 +349,20 @@ tda_status tda_diagram_finish_dev(tda_ctx* ctx, const tda_diagram_set* sets, int
 #define TDA_ORDER_IN_CALL  0
 #define TDA_ORDER_DEFERRED 1
 tda_status tda_set_h1_order(tda_ctx* ctx, int policy);
+/* How tda_diagram_finish_dev (and the finishing pass inside the Rips entry points) and the Wasserstein entry points
+ * split their work over launches when the diagram buffers have room for more rows than the diagrams usually have.  The
+ * results do not depend on it, bit for bit; it exists so that one process can run the schemes against each other.
+ * LISTS (default): diagrams of up to 64 rows are finished by the packed kernel (eight lanes per diagram), pairs of up
+ *   to 64 x 64 points solved by the small launch; what they leave goes onto a per-stream list, and the launch sized by
+ *   the capacities runs over that list on a small fixed grid.
+ * GRID: the small launch has one wavefront per diagram, and the launch sized by the capacities starts a wavefront for
+ *   every diagram / pair of the batch (those that are not its own leave after one load).
+ * ONE: the launch sized by the capacities alone (what the environment variables TDA_FINISH_ONE_LAUNCH /
+ *   TDA_WS_ONE_LAUNCH select for their kernel, whatever is set here). */
+#define TDA_SCHEME_LISTS 0
+#define TDA_SCHEME_GRID  1
+#define TDA_SCHEME_ONE   2
+tda_status tda_set_launch_scheme(tda_ctx* ctx, int scheme);
 
 /* ---- per-recording aggregation -------------------------------------------------
  * replaces the mean/std over windows of process_file_features

@@ -76,6 +76,7 @@ SYMBOLS = {
     "tda_set_retry_policy": (_I, [c_vp, _I]),
     "tda_set_retry_counter": (_I, [c_vp, c_vp]),
     "tda_set_h1_order": (_I, [c_vp, _I]),
+    "tda_set_launch_scheme": (_I, [c_vp, _I]),
     "tda_diagram_finish_dev": (_I, [c_vp, c_vp, _I, _I, c_vp]),
     "tda_tau_batch": (_I, [c_vp, c_vp, _I, _I, _I, c_vp]),
     "tda_features_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp]),
@@ -174,6 +175,12 @@ class Context:
 
     def set_h1_order(self, policy):
         self.check(self.lib.tda_set_h1_order(self.h, int(policy)))
+
+    SCHEME_LISTS, SCHEME_GRID, SCHEME_ONE = 0, 1, 2
+
+    def set_launch_scheme(self, scheme):
+        """How the finishing pass and the Wasserstein launches split their work (include/tdaeeg.h); results do not change."""
+        self.check(self.lib.tda_set_launch_scheme(self.h, int(scheme)))
 
     def set_retry_counter(self, dev_ptr):
         """dev_ptr: device address of a zeroed u64[4] (or None): windows redone by the widening passes."""

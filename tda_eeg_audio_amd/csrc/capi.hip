@@ -74,6 +74,15 @@ tda_status tda_set_h1_order(tda_ctx* ctx, int policy)
     return TDA_OK;
 }
 
+tda_status tda_set_launch_scheme(tda_ctx* ctx, int scheme)
+{
+    if (!ctx) return TDA_ERR_INVALID;
+    if (scheme != TDA_SCHEME_LISTS && scheme != TDA_SCHEME_GRID && scheme != TDA_SCHEME_ONE)
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "unknown launch scheme");
+    ctx->launch_scheme = scheme;
+    return TDA_OK;
+}
+
 tda_status tda_diagram_finish_dev(tda_ctx* ctx, const tda_diagram_set* sets, int n_sets, int n_dgm, void* stream)
 {
     if (!ctx) return TDA_ERR_INVALID;

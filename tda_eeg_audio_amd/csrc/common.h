@@ -18,13 +18,19 @@ struct tda_ctx {
     unsigned long long* retry_ctr = nullptr;   // tda_set_retry_counter: device u64[4]
     unsigned long long* total_scratch = nullptr;   // class vectors of the last rung of the Rips ladders (rips.hip: TOT_SLOTS x 8.3 MB)
     int h1_order = 0;       // TDA_ORDER_*
+    int launch_scheme = 0;  // TDA_SCHEME_*
     // Lists of the windows a widening pass has to redo (rips.hip: retry_collect): one buffer per STREAM -- the Rips calls
     // of a stream, eager or replayed from a HIP graph captured on it, run one after the other, so a stream's list is never
     // in use twice, while calls on different streams never share one.  TDA_RETRY_SLOTS buffers, allocated with the context
     // and assigned to streams in the order they are first seen (more streams than buffers: the last one is shared and
     // retry_shared counts it).  [0] = entries, [1] = workgroups done, the window indices from [4] on.  A call with more
     // windows than retry_cap replaces all buffers (the old ones stay alive for graphs that hold their addresses).
+    // fin_list / ws_list: the same per stream for the diagrams the packed finishing kernel leaves to the wide one
+    // (features.hip) and for the pairs the small Wasserstein launch defers (wasserstein.hip).  The three lists of a slot
+    // are one allocation (retry_buf[i] is its base) and have the same layout and capacity.
     int* retry_buf[32] = {};
+    int* fin_list[32] = {};
+    int* ws_list[32] = {};
     hipStream_t retry_stream[32] = {};
     int retry_streams = 0;
     int retry_shared = 0;
@@ -177,6 +183,9 @@ __device__ __forceinline__ float sortable_f32(u32 s)
 size_t rips_total_scratch_bytes();
 #define TDA_RETRY_SLOTS 32
 tda_status retry_lists_reserve(tda_ctx*, int n_win);      // (rips.hip) all slots to at least n_win entries
+// (rips.hip) slot of the stream, lists of at least n entries: -1 when they would have to grow while st is being captured
+// (never a hipMalloc inside a capture) -- the caller then takes its launch over the whole batch
+tda_status stream_lists_take(tda_ctx*, int n, hipStream_t st, int* slot);
 tda_status launch_corr_dist(tda_ctx*, const double*, int, int, int, double*, double*, hipStream_t);
 tda_status launch_corr_dist_sliding(tda_ctx*, const double*, int, int, int, int, double*, double*, int*, hipStream_t);
 tda_status launch_corr_to_dist(tda_ctx*, const double*, int, int, int, double*, hipStream_t);

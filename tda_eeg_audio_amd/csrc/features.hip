@@ -190,26 +190,20 @@ __device__ __forceinline__ void wave_sync()
 // A launch takes the diagrams with k_lo < rows <= lds_cap: the first one has slices of 64 rows (8 KB per workgroup:
 // eight workgroups = every wave slot of a CU), a second one, sized by the capacities of the buffers (H1: 256 rows,
 // 32 KB per workgroup, five per CU), the larger diagrams -- its other waves leave after one load.
-__global__ void __launch_bounds__(64 * FIN_WAVES, 8)
-diagram_finish_kernel(DiagramSets S, int n_dgm, int lds_cap, int k_lo)
+// diagram g of a set, by the wave that calls it; b: the wave's LDS slice.  (The set's fields come as values: a reference
+// to the kernel's DiagramSets argument would make a private copy of it, indexed in scratch memory.)
+__device__ __forceinline__ void finish_wave(double* rows_set, const int* cnt_set, int cap, int order, double* feat, int g,
+                                            int lds_cap, int k_lo, double* b)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wv = uni((int)(threadIdx.x >> 6));
-    double* b = reinterpret_cast<double*>(smem) + (size_t)wv * 4 * lds_cap;    // births | deaths | pers | tmp, lds_cap each
-    double* d = b + lds_cap;
+    double* d = b + lds_cap;                           // births | deaths | pers | tmp, lds_cap each
     double* p = d + lds_cap;
     double* tmp = p + lds_cap;
-    const long long gi = (long long)blockIdx.x * (blockDim.x >> 6) + wv;
-    const int set = (int)(gi / n_dgm), g = (int)(gi - (long long)set * n_dgm);
-    if (set >= S.n_sets) return;
-    const int cap = S.cap[set];
     const int lane = lane_id();
-    int k = S.cnt[set][g];
+    int k = cnt_set[g];
     k = k < cap ? k : cap;
     if (k > lds_cap || k <= k_lo) return;              // (wave-uniform: another launch's diagram)
-    double* rows = S.rows[set] + (size_t)g * cap * 2;
-    double* feat = S.feat[set];
-    const bool reorder = S.order[set] && k >= 2;
+    double* rows = rows_set + (size_t)g * cap * 2;
+    const bool reorder = order && k >= 2;
     if (!reorder && !feat) return;
     // rows -> LDS (p, tmp serve as staging while the rows are put in order)
     double* rb = reorder ? p : b;
@@ -253,6 +247,7 @@ diagram_finish_kernel(DiagramSets S, int n_dgm, int lds_cap, int k_lo)
     if (m > 0) {
         out[0] = (double)m;
         const double* arr[3] = {b, d, p};
+#pragma unroll
         for (int q = 0; q < 3; ++q) {
             const double mean = np_pairwise_sum_uniform(arr[q], m) / (double)m;
             out[2 + 2 * q] = mean;
@@ -294,6 +289,220 @@ diagram_finish_kernel(DiagramSets S, int n_dgm, int lds_cap, int k_lo)
         for (int i = 0; i < TDA_N_FEATURES; ++i) v = (lane == i) ? out[i] : v;
         feat[(size_t)g * TDA_N_FEATURES + lane] = v;
     }
+}
+
+__global__ void __launch_bounds__(64 * FIN_WAVES, 8)
+diagram_finish_kernel(DiagramSets S, int n_dgm, int lds_cap, int k_lo)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wv = uni((int)(threadIdx.x >> 6));
+    double* b = reinterpret_cast<double*>(smem) + (size_t)wv * 4 * lds_cap;
+    const long long gi = (long long)blockIdx.x * (blockDim.x >> 6) + wv;
+    const int set = (int)(gi / n_dgm), g = (int)(gi - (long long)set * n_dgm);
+    if (set >= S.n_sets) return;
+    finish_wave(S.rows[set], S.cnt[set], S.cap[set], S.order[set], S.feat[set], g, lds_cap, k_lo, b);
+}
+
+// The same for the diagrams on a list (those the packed kernel below leaves: more than FINP_ROWS rows), on a grid that
+// does not depend on the batch: wave w of the grid takes entries w, w + waves, ...  [0] = entries, [1] = waves done (the
+// last one through clears both, so the next packed launch appends from zero without a memset node in between:
+// RETRY_SCAN_END of rips.hip), global diagram indices set * n_dgm + g from [4] on.
+__global__ void __launch_bounds__(64 * FIN_WAVES)        // (its LDS allows five waves per SIMD: no need to squeeze into 64 VGPRs)
+diagram_finish_list_kernel(DiagramSets S, int n_dgm, int lds_cap, int k_lo, int* list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wv = uni((int)(threadIdx.x >> 6)), nw = (int)(blockDim.x >> 6);
+    double* b = reinterpret_cast<double*>(smem) + (size_t)wv * 4 * lds_cap;
+    const int n_all = S.n_sets * n_dgm;                // (the host checked that it fits an int)
+    int nl = uni(list[0]);
+    nl = nl < n_all ? nl : n_all;
+    for (int j = (int)blockIdx.x * nw + wv; j < nl; j += (int)gridDim.x * nw) {
+        const int gi = uni(list[4 + j]);
+        if (gi >= 0 && gi < n_all) {
+            const int set = gi / n_dgm;
+            finish_wave(S.rows[set], S.cnt[set], S.cap[set], S.order[set], S.feat[set], gi - set * n_dgm, lds_cap, k_lo, b);
+        }
+        wave_sync();
+    }
+    if (lane_id() == 0 && atomicAdd(&list[1], 1) == (int)gridDim.x * nw - 1) { list[0] = 0; list[1] = 0; }
+}
+
+// ---------------------------------------------------------------------------------
+// The packed finishing kernel: diagrams of at most FINP_ROWS = 64 rows (every diagram of the usual path: 12 to 47 rows),
+// EIGHT lanes per diagram, so a wave finishes eight consecutive diagrams of one set (order, feat and cap are
+// wave-uniform; the groups of a wave loop to the largest row count among them).  diagram_finish_kernel gives every sum
+// of a diagram to all 64 lanes of its wave -- the same serial chain of m loads and m additions 64 times over, eight sums
+// per diagram.  numpy's leaf IS eight independent accumulators, so here lane j of a group carries r_j (the same
+// additions in the same order), the three combining steps ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) run on the DPP network
+// inside the group (IEEE addition is commutative: which lane of a pair adds is free) and the n % 8 tail is added in order
+// to the combined value: bit for bit np_pairwise_leaf.  Control flow diverges between groups only (a group's eight
+// lanes take every branch together), and every DPP source lies in the reader's own group.
+// LDS: births | deaths of a diagram, 1 KB; pers = d - b, (x - mean)^2 and pn * log(pn + 1e-10) come from the functor of
+// the sum (the entropy terms are compacted over the births, which nobody reads any more by then).  Slices are
+// FINP_STRIDE = 136 doubles apart: the 16 banks of skew put the eight-row reads of the four groups of a half-wave on
+// 4 x 16 different banks (at 128 doubles all groups would meet on the same 16: a four-way conflict on every read).
+// 8.5 KB per wave = 18 waves = 144 diagrams in flight per CU (diagram_finish_kernel: 32); the b | d | pers | tmp layout
+// of diagram_finish_kernel would be 17 KB per wave and 9 waves per CU.  Chosen by this arithmetic, not by a measurement
+// of both layouts.
+// Rows are put in order by counting as before: lane j ranks rows j, j + 8, ... against all k rows of the slice, keeps
+// the ranks as bytes of one 64-bit word, writes the rows to their places in HBM at once and moves births, then deaths
+// inside the slice (eight values in registers between the reads and the writes).
+// The maximum is the one value that is not computed in diagram_finish_kernel's order: it is order-free except for the
+// sign of a zero maximum of a diagram that holds both +0 and -0 persistences (a death of -0: no Rips kernel emits one).
+// A diagram with more than FINP_ROWS rows is appended to `list` (wave-aggregated, as retry_collect_kernel) for
+// diagram_finish_list_kernel; list == NULL: no set has room for one.
+// ---------------------------------------------------------------------------------
+#define FINP_ROWS 64
+#define FINP_STRIDE (2 * FINP_ROWS + 8)
+#define FINP_WAVES 2
+
+template <class F>
+__device__ __forceinline__ double np_pairwise_group8(const F& f, int n, int sub)      // n <= 128, uniform in the group
+{
+    const int n8 = n & ~7;                             // n < 8: the serial loop alone (the "tail" from 0)
+    double r = 0.0;
+    if (n8) {
+        r = f(sub);
+        for (int i = 8; i < n8; i += 8) r += f(i + sub);
+    }
+    r += dpp_f64<0xB1, 0xF>(r);                        // quad_perm [1,0,3,2]: r0+r1, r2+r3, r4+r5, r6+r7
+    r += dpp_f64<0x4E, 0xF>(r);                        // quad_perm [2,3,0,1]: (r0+r1)+(r2+r3), (r4+r5)+(r6+r7)
+    r += dpp_f64<0x141, 0xF>(r);                       // row_half_mirror: lane j <-> 7 - j, the other quad's sum
+    double res = n8 ? r : 0.0;
+    for (int i = n8; i < n; ++i) res += f(i);
+    return res;
+}
+// np.mean and np.std of f(0) .. f(m-1)
+template <class F>
+__device__ __forceinline__ void group8_mean_std(const F& f, int m, int sub, double& mean, double& sd)
+{
+    mean = np_pairwise_group8(f, m, sub) / (double)m;
+    sd = 0.0;
+    if (m > 1) {
+        const double mu = mean;
+        auto sq = [=](int i) { const double z = f(i) - mu; return z * z; };
+        sd = sqrt(np_pairwise_group8(sq, m, sub) / (double)m);
+    }
+}
+
+__global__ void __launch_bounds__(64 * FINP_WAVES)
+diagram_finish_packed_kernel(DiagramSets S, int n_dgm, int* list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wv = uni((int)(threadIdx.x >> 6));
+    const int lane = lane_id(), grp = lane >> 3, sub = lane & 7;
+    const int wps = (n_dgm + 7) >> 3;                  // waves per set: the last one of a set may have idle groups
+    const long long wi = (long long)blockIdx.x * FINP_WAVES + wv;
+    const int set = (int)(wi / wps);
+    if (set >= S.n_sets) return;
+    const int g = ((int)(wi - (long long)set * wps) << 3) + grp;
+    const int cap = S.cap[set];
+    const bool in = g < n_dgm;
+    int k = 0;
+    if (in) { k = S.cnt[set][g]; k = k < cap ? k : cap; }
+    const bool big = in && k > FINP_ROWS;
+    if (list) {
+        const u64 bal = __ballot(big && sub == 0);
+        if (bal) {
+            const int lead = __builtin_ctzll(bal);
+            int base = 0;
+            if (lane == lead) base = atomicAdd(&list[0], __builtin_popcountll(bal));
+            base = __builtin_amdgcn_readlane(base, lead);
+            if (big && sub == 0) list[4 + base + __builtin_popcountll(bal & ((1ull << lane) - 1ull))] = set * n_dgm + g;
+        }
+    }
+    double* feat = S.feat[set];
+    const bool reorder = S.order[set] && k >= 2;
+    if (!in || big || (!reorder && !feat)) return;     // (uniform in the group, as every branch below)
+    double* b = reinterpret_cast<double*>(smem) + (size_t)(wv * 8 + grp) * FINP_STRIDE;
+    double* d = b + FINP_ROWS;
+    double* rows = S.rows[set] + (size_t)g * cap * 2;
+    for (int i = sub; i < k; i += 8) { b[i] = rows[2 * i]; d[i] = rows[2 * i + 1]; }
+    wave_sync();
+    if (reorder) {
+        u64 rank = 0;                                  // byte t: the place of row sub + 8 t
+        for (int t = 0, i = sub; i < k; ++t, i += 8) {
+            const double bi = b[i], di = d[i];
+            int pos = 0;
+            for (int j = 0; j < k; ++j) {
+                const double bj = b[j], dj = d[j];
+                pos += ((bj > bi) || (bj == bi && (dj > di || (dj == di && j < i)))) ? 1 : 0;
+            }
+            rank |= (u64)pos << (8 * t);
+            if (pos != i) { rows[2 * pos] = bi; rows[2 * pos + 1] = di; }
+        }
+        if (!feat) return;
+        for (int q = 0; q < 2; ++q) {
+            double* a = q ? d : b;
+            double v[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) v[t] = sub + 8 * t < k ? a[sub + 8 * t] : 0.0;
+            wave_sync();
+#pragma unroll
+            for (int t = 0; t < 8; ++t)
+                if (sub + 8 * t < k) a[(int)(rank >> (8 * t)) & 63] = v[t];
+            wave_sync();
+        }
+    }
+    if (!feat) return;
+    // compact finite rows in place, preserving order (utils.py:146-147), eight rows per trip: row i moves to pos <= i, and
+    // every lane has read its row before any lane of the same trip writes.  A group's byte of the ballot is its own.
+    int m = 0;
+    for (int i0 = 0; i0 < k; i0 += 8) {
+        const int i = i0 + sub;
+        double bi = 0.0, di = 0.0;
+        bool fin = false;
+        if (i < k) { bi = b[i]; di = d[i]; fin = isfinite(bi) && isfinite(di); }
+        const u32 bal = (u32)(__ballot(fin) >> (8 * grp)) & 0xffu;
+        const int pos = m + __popc(bal & ((1u << sub) - 1u));
+        wave_sync();
+        if (fin) { b[pos] = bi; d[pos] = di; }
+        m += __popc(bal);
+    }
+    wave_sync();
+    // lane sub carries features sub and sub + 8 of its diagram (every lane of the group computes the same values)
+    double o0 = 0.0, o1 = 0.0;
+    auto put = [&](int idx, double v) { o0 = sub == idx ? v : o0; o1 = sub + 8 == idx ? v : o1; };
+    put(1, (double)((k > 0 ? k : 0) - m));
+    if (m > 0) {
+        put(0, (double)m);
+        auto fb = [=](int i) { return b[i]; };
+        auto fd = [=](int i) { return d[i]; };
+        auto fp = [=](int i) { return d[i] - b[i]; };
+        double mean, sd;
+        group8_mean_std(fb, m, sub, mean, sd); put(2, mean); put(3, sd);
+        group8_mean_std(fd, m, sub, mean, sd); put(4, mean); put(5, sd);
+        group8_mean_std(fp, m, sub, mean, sd); put(6, mean); put(7, sd);
+        double mx = -INFINITY;
+        for (int i = sub; i < m; i += 8) { const double pi = d[i] - b[i]; mx = pi > mx ? pi : mx; }
+        { double o;
+          o = dpp_f64<0xB1, 0xF>(mx); mx = o > mx ? o : mx;
+          o = dpp_f64<0x4E, 0xF>(mx); mx = o > mx ? o : mx;
+          o = dpp_f64<0x141, 0xF>(mx); mx = o > mx ? o : mx; }
+        put(8, mx);
+        const double tot = np_pairwise_group8(fp, m, sub);
+        put(9, tot);
+        if (m > 1 && tot > 0.0) {
+            // pn = pers/sum; keep pn > 0 in order (utils.py:161-163): the terms go where the births were (term `at` <= row i,
+            // and the rows of a later trip lie above every term written so far)
+            int c = 0;
+            for (int i0 = 0; i0 < m; i0 += 8) {
+                const int i = i0 + sub;
+                double pn = 0.0;
+                if (i < m) pn = (d[i] - b[i]) / tot;
+                const bool pos = i < m && pn > 0.0;
+                const u32 bal = (u32)(__ballot(pos) >> (8 * grp)) & 0xffu;
+                const int at = c + __popc(bal & ((1u << sub) - 1u));
+                wave_sync();
+                if (pos) b[at] = pn * log(pn + 1e-10);
+                c += __popc(bal);
+            }
+            wave_sync();
+            put(10, -np_pairwise_group8(fb, c, sub) / log((double)m + 1e-10));
+        }
+    }
+    feat[(size_t)g * TDA_N_FEATURES + sub] = o0;
+    if (sub + 8 < TDA_N_FEATURES) feat[(size_t)g * TDA_N_FEATURES + 8 + sub] = o1;
 }
 
 // ---------------------------------------------------------------------------------
@@ -780,21 +989,47 @@ tda_status launch_diagram_finish(tda_ctx* ctx, const tda_diagram_set* sets, int 
     }
     S.n_sets = n_sets;
     const long long n_all = (long long)n_sets * n_dgm;
-    // small diagrams first (see the kernel), then whatever is larger with slices of the full capacity
+    // small diagrams first, then whatever is larger with slices of the full capacity.  TDA_SCHEME_LISTS: the packed kernel,
+    // and the wide launch over the list of the diagrams it left; TDA_SCHEME_GRID: the one-wave-per-diagram kernel with
+    // slices of 64 rows, and the wide launch over the whole batch; TDA_SCHEME_ONE (or TDA_FINISH_ONE_LAUNCH): that alone
     static const bool one_launch = getenv("TDA_FINISH_ONE_LAUNCH") != nullptr;
-    int k_lo = INT_MIN;
-    if (cap > 64 && !one_launch) {
-        const int nw = FIN_WAVES;
-        hipLaunchKernelGGL(diagram_finish_kernel, dim3((unsigned)((n_all + nw - 1) / nw)), dim3(64 * nw), (size_t)64 * 4 * 8 * nw, st, S,
-                           n_dgm, 64, k_lo);
-        k_lo = 64;
-    }
+    int scheme = one_launch ? TDA_SCHEME_ONE : ctx->launch_scheme;
     int nw = FIN_WAVES;                                  // diagrams per workgroup: fewer when the slices are large
     while (nw > 1 && (size_t)cap * 4 * 8 * nw > 32 * 1024) nw >>= 1;
     const size_t lds = (size_t)cap * 4 * 8 * nw;
-    if (lds > 48 * 1024)
+    if (lds > 48 * 1024 && (cap > FINP_ROWS || scheme != TDA_SCHEME_LISTS)) {
         TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(diagram_finish_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(diagram_finish_list_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    if (scheme == TDA_SCHEME_LISTS) {
+        int* list = nullptr;
+        if (cap > FINP_ROWS) {
+            int slot = -1;
+            if (n_all <= INT_MAX) { const tda_status rc = stream_lists_take(ctx, (int)n_all, st, &slot); if (rc != TDA_OK) return rc; }
+            if (slot < 0) scheme = TDA_SCHEME_GRID;      // no list of that size (see stream_lists_take)
+            else list = ctx->fin_list[slot];
+        }
+        if (scheme == TDA_SCHEME_LISTS) {
+            const long long waves = (long long)n_sets * ((n_dgm + 7) / 8);
+            hipLaunchKernelGGL(diagram_finish_packed_kernel, dim3((unsigned)((waves + FINP_WAVES - 1) / FINP_WAVES)),
+                               dim3(64 * FINP_WAVES), (size_t)FINP_WAVES * 8 * FINP_STRIDE * 8, st, S, n_dgm, list);
+            if (list) {
+                const long long wgs = (n_all + nw - 1) / nw;
+                hipLaunchKernelGGL(diagram_finish_list_kernel, dim3((unsigned)(wgs < 256 ? wgs : 256)), dim3(64 * nw), lds, st, S,
+                                   n_dgm, cap, FINP_ROWS, list);
+            }
+            TDA_HIP(ctx, hipGetLastError());
+            return TDA_OK;
+        }
+    }
+    int k_lo = INT_MIN;
+    if (cap > 64 && scheme == TDA_SCHEME_GRID) {
+        hipLaunchKernelGGL(diagram_finish_kernel, dim3((unsigned)((n_all + FIN_WAVES - 1) / FIN_WAVES)), dim3(64 * FIN_WAVES),
+                           (size_t)64 * 4 * 8 * FIN_WAVES, st, S, n_dgm, 64, k_lo);
+        k_lo = 64;
+    }
     hipLaunchKernelGGL(diagram_finish_kernel, dim3((unsigned)((n_all + nw - 1) / nw)), dim3(64 * nw), lds, st, S, n_dgm, cap, k_lo);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;

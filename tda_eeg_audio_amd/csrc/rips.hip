@@ -2502,28 +2502,47 @@ tda_status retry_lists_reserve(tda_ctx* ctx, int n_win)
 {
     if (n_win <= ctx->retry_cap) return TDA_OK;
     const int cap = (n_win + 1023) & ~1023;
+    const size_t one = (size_t)cap + 4;                                       // [retry | finish | wasserstein], `one` ints each
     for (int i = 0; i < TDA_RETRY_SLOTS; ++i) {
         int* q = nullptr;
-        TDA_HIP(ctx, hipMalloc((void**)&q, ((size_t)cap + 4) * sizeof(int)));
-        TDA_HIP(ctx, hipMemset(q, 0, 4 * sizeof(int)));                        // (every pass leaves its list empty: see RETRY_SCAN_END)
+        TDA_HIP(ctx, hipMalloc((void**)&q, 3 * one * sizeof(int)));
+        for (int l = 0; l < 3; ++l)
+            TDA_HIP(ctx, hipMemset(q + l * one, 0, 4 * sizeof(int)));         // (every pass leaves its list empty: see RETRY_SCAN_END)
         if (ctx->retry_buf[i]) ctx->retired.push_back(ctx->retry_buf[i]);     // (a captured graph may still name it)
-        ctx->retry_buf[i] = q;
+        ctx->retry_buf[i] = q; ctx->fin_list[i] = q + one; ctx->ws_list[i] = q + 2 * one;
     }
     ctx->retry_cap = cap;
     return TDA_OK;
 }
-// the list of the stream the call is enqueued on (see tda_ctx::retry_buf)
-static tda_status retry_list_take(tda_ctx* ctx, int n_win, RipsOut& out, hipStream_t st)
+// the slot of the stream the call is enqueued on (see tda_ctx::retry_buf)
+static int stream_slot(tda_ctx* ctx, hipStream_t st)
 {
-    const tda_status rc = retry_lists_reserve(ctx, n_win);
-    if (rc != TDA_OK) return rc;
     int i = 0;
     while (i < ctx->retry_streams && ctx->retry_stream[i] != st) ++i;
     if (i == ctx->retry_streams) {
         if (i < TDA_RETRY_SLOTS) ctx->retry_stream[ctx->retry_streams++] = st;
         else { i = TDA_RETRY_SLOTS - 1; ++ctx->retry_shared; }
     }
-    out.retry_list = ctx->retry_buf[i];
+    return i;
+}
+static tda_status retry_list_take(tda_ctx* ctx, int n_win, RipsOut& out, hipStream_t st)
+{
+    const tda_status rc = retry_lists_reserve(ctx, n_win);
+    if (rc != TDA_OK) return rc;
+    out.retry_list = ctx->retry_buf[stream_slot(ctx, st)];
+    return TDA_OK;
+}
+tda_status stream_lists_take(tda_ctx* ctx, int n, hipStream_t st, int* slot)
+{
+    *slot = -1;
+    if (n > ctx->retry_cap) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return TDA_OK; }
+        if (cs != hipStreamCaptureStatusNone) return TDA_OK;
+        const tda_status rc = retry_lists_reserve(ctx, n);
+        if (rc != TDA_OK) return rc;
+    }
+    *slot = stream_slot(ctx, st);
     return TDA_OK;
 }
 // before every widening pass: which windows are flagged now

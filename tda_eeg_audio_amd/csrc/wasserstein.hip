@@ -108,21 +108,14 @@ struct ws_table_pairs {
     }
 };
 
+// pair pr, by the one wave of the workgroup
 template <int CW, class SRC>
-__global__ void __launch_bounds__(64)
-wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
-                   const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
-                   const SRC src, int n_pairs,
-                   int max_rows, int max_cols,
-                   double* __restrict__ out, int* __restrict__ status, int mode)
+__device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                                         const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                                         const SRC& src, int pr, int max_rows, int max_cols,
+                                         double* __restrict__ out, int* __restrict__ status, int mode, int* list,
+                                         unsigned char* smem)
 {
-    // mode 1: the SMALL first launch (LDS for 64 x 64 points whatever the capacities of the diagram buffers: four times
-    // the workgroups per CU of a launch sized by a capacity of 256) leaves pairs that do not fit marked WS_DEFERRED;
-    // mode 2: the launch sized by the capacities takes exactly those; mode 0: one launch for everything
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int pr = blockIdx.x;
-    if (pr >= n_pairs) return;
-    if (mode == 2 && status[pr] != WS_DEFERRED) return;
     const int lane = lane_id();
     unsigned long long wt0 = WCLK();
     (void)wt0;
@@ -163,7 +156,10 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
     const int cw_used = (Cn + 63) >> 6;                // column slots per lane actually in use
     if (R > max_rows || Cn > max_cols || Cn > 64 * CW) {
         if (lane == 0) {
-            if (mode == 1) status[pr] = WS_DEFERRED;
+            if (mode == 1) {
+                status[pr] = WS_DEFERRED;
+                if (list) list[4 + atomicAdd(&list[0], 1)] = pr;        // (one wave and one pair per workgroup: nothing to aggregate)
+            }
             else { out[pr] = __longlong_as_double(0x7ff8000000000000ll); status[pr] = TDA_WIN_NOT_CONVERGED; }
         }
         return;
@@ -459,6 +455,49 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
     WPROF(2, WCLK() - wt0);
 }
 
+template <int CW, class SRC>
+__global__ void __launch_bounds__(64)
+wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                   const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                   const SRC src, int n_pairs,
+                   int max_rows, int max_cols,
+                   double* __restrict__ out, int* __restrict__ status, int mode, int* list)
+{
+    // mode 1: the SMALL first launch (LDS for 64 x 64 points whatever the capacities of the diagram buffers: four times
+    // the workgroups per CU of a launch sized by a capacity of 256) leaves pairs that do not fit marked WS_DEFERRED and,
+    // given a list, appends them to it; mode 2: the launch sized by the capacities takes exactly the marked ones
+    // (TDA_SCHEME_GRID; under TDA_SCHEME_LISTS wasserstein_list_kernel takes the listed ones); mode 0: one launch for
+    // everything
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int pr = blockIdx.x;
+    if (pr >= n_pairs) return;
+    if (mode == 2 && status[pr] != WS_DEFERRED) return;
+    ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, mode, list, smem);
+}
+
+// The pairs on the list of the small launch, on a grid that does not depend on the batch: workgroup b takes entries b,
+// b + gridDim.x, ...  [0] = entries, [1] = workgroups done (the last one through clears both: no memset node between a
+// step and the next), the pairs from [4] on.  A pair that does not fit here either is TDA_WIN_NOT_CONVERGED, as in mode 2.
+template <int CW, class SRC>
+__global__ void __launch_bounds__(64)
+wasserstein_list_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                        const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                        const SRC src, int n_pairs,
+                        int max_rows, int max_cols,
+                        double* __restrict__ out, int* __restrict__ status, int* list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int nl = uni(list[0]);
+    nl = nl < n_pairs ? nl : n_pairs;
+    for (int j = blockIdx.x; j < nl; j += gridDim.x) {
+        const int pr = uni(list[4 + j]);
+        if (pr >= 0 && pr < n_pairs)
+            ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, 0, nullptr, smem);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && atomicAdd(&list[1], 1) == (int)gridDim.x - 1) { list[0] = 0; list[1] = 0; }
+}
+
 // ---------------------------------------------------------------------------------
 // the two-launch scheme, whatever the source of the pairs
 template <class SRC>
@@ -477,22 +516,37 @@ static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, cons
     const size_t lds = (size_t)(4 * max_rows + 4 * max_cols + ((max_cols + 1) >> 1)) * 8;
     // diagram buffers with room for more than 128 rows (H1: 256) are mostly far from full (35 x 41 rows on the bench's
     // windows): a first launch with LDS for 64 x 64 points, the launch sized by the capacities for the pairs it defers
-    static const bool small_first = getenv("TDA_WS_ONE_LAUNCH") == nullptr;
-    const int mode = (small_first && max_cols > 128) ? 2 : 0;
+    // (TDA_SCHEME_LISTS: the second launch runs over the list of the deferred pairs, TDA_SCHEME_GRID: over the whole batch)
+    static const bool one_launch = getenv("TDA_WS_ONE_LAUNCH") != nullptr;
+    const int scheme = one_launch ? TDA_SCHEME_ONE : ctx->launch_scheme;
+    const int mode = (scheme != TDA_SCHEME_ONE && max_cols > 128) ? 2 : 0;
+    int* list = nullptr;
+    if (mode && scheme == TDA_SCHEME_LISTS) {
+        int slot = -1;
+        const tda_status rc = stream_lists_take(ctx, n_pairs, st, &slot);
+        if (rc != TDA_OK) return rc;
+        if (slot >= 0) list = ctx->ws_list[slot];        // (else: no list of that size, the launch over the batch)
+    }
     if (mode) {
         const int sr = max_rows < 64 ? max_rows : 64;
         const size_t lds_s = (size_t)(4 * sr + 4 * 64 + 32) * 8;
         hipLaunchKernelGGL((wasserstein_kernel<1, SRC>), dim3(n_pairs), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
-                           cap_b, src, n_pairs, sr, 64, out, status, 1);
+                           cap_b, src, n_pairs, sr, 64, out, status, 1, list);
     }
 #define WS_LAUNCH(CWV)                                                                                         \
     do {                                                                                                       \
         auto kern = wasserstein_kernel<CWV, SRC>;                                                              \
+        auto lkern = wasserstein_list_kernel<CWV, SRC>;                                                        \
         if (lds > 48 * 1024)                                                                                   \
-            TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                              \
+            TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern)                       \
+                                                  : reinterpret_cast<const void*>(kern),                       \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b,   \
-                           src, n_pairs, max_rows, max_cols, out, status, mode);                               \
+        if (list)                                                                                              \
+            hipLaunchKernelGGL(lkern, dim3(n_pairs < 256 ? n_pairs : 256), dim3(64), lds, st, dgm_a, cnt_a,    \
+                               cap_a, dgm_b, cnt_b, cap_b, src, n_pairs, max_rows, max_cols, out, status, list); \
+        else                                                                                                   \
+            hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,      \
+                               cap_b, src, n_pairs, max_rows, max_cols, out, status, mode, (int*)nullptr);     \
     } while (0)
     if (max_cols <= 128) WS_LAUNCH(2);
     else if (max_cols <= 256) WS_LAUNCH(4);
