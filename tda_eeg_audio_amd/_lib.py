@@ -5,6 +5,7 @@ The HIP library is the product; there is NO CPU fallback.  If the shared object 
 missing or no MI355X is visible, every entry point raises.  Build it with
 ``python -c "import __graft_entry__ as g; g.build()"`` or ``make -C tda_eeg_audio_amd/csrc``.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -175,6 +176,21 @@ class Context:
 
     def set_h1_order(self, policy):
         self.check(self.lib.tda_set_h1_order(self.h, int(policy)))
+
+    @contextlib.contextmanager
+    def deferred(self, retry="auto"):
+        """The policies of a batched step for the Rips calls inside the block: ORDER_DEFERRED (the caller runs ONE finishing
+        pass afterwards) and, for retry="first" / "one", RETRY_FIRST_PASS / RETRY_ONE_STEP (pipeline.run_step).  ORDER_IN_CALL
+        and RETRY_AUTO are back when the block is left, also by an exception."""
+        if retry != "auto":
+            self.set_retry_policy(self.RETRY_FIRST_PASS if retry == "first" else self.RETRY_ONE_STEP)
+        self.set_h1_order(self.ORDER_DEFERRED)
+        try:
+            yield self
+        finally:
+            self.set_h1_order(self.ORDER_IN_CALL)
+            if retry != "auto":
+                self.set_retry_policy(self.RETRY_AUTO)
 
     SCHEME_LISTS, SCHEME_GRID, SCHEME_ONE = 0, 1, 2
 

@@ -106,15 +106,8 @@ def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="
     import torch
     from . import _lib
     ctx = ctx or _lib.get_ctx()
-    if retry != "auto":
-        ctx.set_retry_policy(ctx.RETRY_FIRST_PASS if retry == "first" else ctx.RETRY_ONE_STEP)
-    ctx.set_h1_order(ctx.ORDER_DEFERRED)         # one finishing pass for the three diagram sets of the batch
-    try:
+    with ctx.deferred(retry):                    # one finishing pass for the three diagram sets of the batch
         return _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding, eeg_table)
-    finally:
-        ctx.set_h1_order(ctx.ORDER_IN_CALL)
-        if retry != "auto":
-            ctx.set_retry_policy(ctx.RETRY_AUTO)
 
 
 def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=None, eeg_table=None):
@@ -435,8 +428,7 @@ def run_features_step(eeg_win, ws, ctx=None):
     import torch
     from . import _lib
     ctx = ctx or _lib.get_ctx()
-    ctx.set_h1_order(ctx.ORDER_DEFERRED)
-    try:
+    with ctx.deferred():
         if ws.fused and eeg_win.shape[2] <= 256:
             engine.eeg_window_dev(eeg_win, ws.eeg, ctx=ctx)
         else:
@@ -444,8 +436,6 @@ def run_features_step(eeg_win, ws, ctx=None):
                 ws.dist = torch.empty((ws.n_win, eeg_win.shape[1], eeg_win.shape[1]), dtype=torch.float64, device=ws.device)
             engine.corr_dist_dev(eeg_win, ws.dist, None, ctx=ctx)
             engine.rips_dm_dev(ws.dist, ws.eeg, ctx=ctx)
-    finally:
-        ctx.set_h1_order(ctx.ORDER_IN_CALL)
     engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0), (ws.eeg.h1, ws.eeg.c1, True, ws.fe1)], ctx=ctx)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)

@@ -43,6 +43,37 @@ def _sos_plan(sos):
     return sos, np.ascontiguousarray(signal.sosfilt_zi(sos)), int(ntaps * 3)
 
 
+class SosBank:
+    """SOS filters applied in ONE launch, packed for the C entries once: `sos` (n, n_sec, 6) and `zi` (n, n_sec, 2) stacked
+    per filter (_sos_plan), and what a launch takes once for all its filters: `n_sec` and `edge`, sosfiltfilt's pad length."""
+
+    def __init__(self, designs):
+        plans = [_sos_plan(sos) for sos in designs]
+        self.n, self.n_sec, self.edge = len(plans), plans[0][0].shape[0], plans[0][2]
+        assert all(p[0].shape[0] == self.n_sec and p[2] == self.edge for p in plans), "the filters of a bank share their structure"
+        self.sos = np.ascontiguousarray(np.stack([p[0] for p in plans]))
+        self.zi = np.ascontiguousarray(np.stack([p[1] for p in plans]))
+
+    @classmethod
+    def bandpass(cls, bands, fs, order=FILTER_ORDER):
+        """design_bandpass_filter (nb1:209-233) of every (lowcut, highcut) of `bands`."""
+        return cls([design_bandpass_filter(lo, hi, fs, order) for lo, hi in bands])
+
+
+class BaBank:
+    """(b, a) filters applied by filtfilt in ONE launch, packed for the C entries once: `B`, `A` (n, ntaps) zero-padded to
+    the longest filter, `Z` (n, ntaps - 1) scipy.signal.lfilter_zi of the padded pairs, `edge` = 3 * ntaps (filtfilt's)."""
+
+    def __init__(self, bas):
+        bas = [(np.atleast_1d(b), np.atleast_1d(a)) for b, a in bas]
+        self.n, self.ntaps = len(bas), max(max(len(b), len(a)) for b, a in bas)
+        self.edge = 3 * self.ntaps
+        self.B, self.A, self.Z = (np.zeros((self.n, m)) for m in (self.ntaps, self.ntaps, self.ntaps - 1))
+        for f, (b, a) in enumerate(bas):
+            self.B[f, :len(b)] = b; self.A[f, :len(a)] = a
+            self.Z[f] = signal.lfilter_zi(self.B[f], self.A[f])
+
+
 def sosfiltfilt(sos, x, ctx=None):
     """scipy.signal.sosfiltfilt(sos, x, axis=-1) for a (n_sig, n_samples) float64 array."""
     ctx = ctx or get_ctx()
@@ -61,19 +92,15 @@ def sosfiltfilt(sos, x, ctx=None):
 def filtfilt(b, a, x, ctx=None):
     """scipy.signal.filtfilt(b, a, x, axis=-1) (default odd padding) for (n_sig, n_samples) float64."""
     ctx = ctx or get_ctx()
-    b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.float64)
-    a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64)
-    ntaps = max(len(a), len(b))
-    b = np.concatenate([b, np.zeros(ntaps - len(b))]); a = np.concatenate([a, np.zeros(ntaps - len(a))])
-    zi = np.ascontiguousarray(signal.lfilter_zi(b, a))
-    edge = 3 * ntaps
+    fb = BaBank([(b, a)])
+    ntaps, edge = fb.ntaps, fb.edge
     x = f64(x)
     one = x.ndim == 1
     x2 = x.reshape(1, -1) if one else x
     if x2.shape[1] <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     y = np.empty_like(x2)
-    ctx.check(ctx.lib.tda_filtfilt(ctx.h, ptr(x2), x2.shape[0], x2.shape[1], ptr(b), ptr(a), ptr(zi), ntaps, edge, ptr(y)))
+    ctx.check(ctx.lib.tda_filtfilt(ctx.h, ptr(x2), x2.shape[0], x2.shape[1], ptr(fb.B), ptr(fb.A), ptr(fb.Z), ntaps, edge, ptr(y)))
     return y[0] if one else y
 
 
@@ -82,14 +109,22 @@ def apply_bandpass_filter(data, lowcut, highcut, fs, order=4):
     return sosfiltfilt(design_bandpass_filter(lowcut, highcut, fs, order), np.asarray(data, dtype=np.float64))
 
 
+def _envelope_edges(low, high, fs):
+    nyq = fs / 2
+    return max(low / nyq, 0.001), min(high / nyq, 0.999)
+
+
+def envelope_bandpass(bands, fs):
+    """The (b, a) designs of bandpass_filter (utils.py:66-74, with its clamps) for every (low, high) of `bands`."""
+    return [signal.butter(4, list(_envelope_edges(lo, hi, fs)), btype="band") for lo, hi in bands]
+
+
 def bandpass_filter(s, fs, low, high):
     """scripts/utils.py:66-74."""
-    nyq = fs / 2
-    lo = max(low / nyq, 0.001)
-    hi = min(high / nyq, 0.999)
+    lo, hi = _envelope_edges(low, high, fs)
     if lo >= hi:
         return s
-    b, a = signal.butter(4, [lo, hi], btype="band")
+    (b, a), = envelope_bandpass([(low, high)], fs)
     return filtfilt(b, a, s)
 
 
@@ -160,8 +195,7 @@ def recordings_to_features(raw_t, fs, sel_t=None, n_sel_per_rec=None, freq_bands
     seg = torch.arange(0, n_out + 1, k, dtype=torch.int32, device=dev)
     X = torch.empty((n_rec, len(freq_bands), 44), dtype=torch.float64, device=dev)
     status = torch.zeros(n_out, dtype=torch.int32, device=dev)
-    ctx.set_h1_order(ctx.ORDER_DEFERRED)
-    try:
+    with ctx.deferred():
         for bi, (name, (lo, hi)) in enumerate(freq_bands.items()):
             sos, zi, edge = _sos_plan(design_bandpass_filter(lo, hi, fs, order))
             if work is None:
@@ -171,8 +205,6 @@ def recordings_to_features(raw_t, fs, sel_t=None, n_sel_per_rec=None, freq_bands
             engine.diagram_finish_dev([(dgm.h0, dgm.c0, False, fe0), (dgm.h1, dgm.c1, True, fe1)], ctx=ctx)
             X[:, bi].copy_(engine.aggregate_dev(fe0, fe1, seg, ctx=ctx))
             status |= dgm.status                 # (the next band overwrites the words)
-    finally:
-        ctx.set_h1_order(ctx.ORDER_IN_CALL)
     return X.view(n_rec, len(freq_bands) * 44), status
 
 
@@ -182,12 +214,8 @@ def filtfilt_dev(x_t, b, a, y_t=None, work_t=None, ctx=None):
     import torch
     ctx = ctx or get_ctx()
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous() and x_t.dim() == 2
-    b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.float64)
-    a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64)
-    ntaps = max(len(a), len(b))
-    b = np.concatenate([b, np.zeros(ntaps - len(b))]); a = np.concatenate([a, np.zeros(ntaps - len(a))])
-    zi = np.ascontiguousarray(signal.lfilter_zi(b, a))
-    edge = 3 * ntaps
+    fb = BaBank([(b, a)])
+    ntaps, edge = fb.ntaps, fb.edge
     n_sig, n_s = x_t.shape
     if n_s <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
@@ -195,25 +223,24 @@ def filtfilt_dev(x_t, b, a, y_t=None, work_t=None, ctx=None):
         y_t = torch.empty_like(x_t)
     if work_t is None or work_t.numel() < n_sig * (n_s + 2 * edge):
         work_t = torch.empty((n_sig, n_s + 2 * edge), dtype=torch.float64, device=x_t.device)
-    ctx.check(ctx.lib.tda_filtfilt_dev(ctx.h, C.c_void_p(x_t.data_ptr()), n_sig, n_s, ptr(b), ptr(a), ptr(zi), ntaps, edge,
+    ctx.check(ctx.lib.tda_filtfilt_dev(ctx.h, C.c_void_p(x_t.data_ptr()), n_sig, n_s, ptr(fb.B), ptr(fb.A), ptr(fb.Z), ntaps, edge,
                                        C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return y_t
 
 
-def bandpass_bank_dev(x_t, bands, fs, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
+def bandpass_bank_dev(x_t, bands, fs=None, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
     """apply_bandpass_filter (nb1:236-263) for ALL bands in one launch: x_t (n_sig, n_samples) -> y_t (n_bands, n_sig,
-    n_samples), bit-identical to one bandpass_dev call per band.  bands: iterable of (lowcut, highcut)."""
+    n_samples), bit-identical to one bandpass_dev call per band.  bands: iterable of (lowcut, highcut) (designed here for
+    `fs` and `order`) or the SosBank prepared once."""
     import torch
     ctx = ctx or get_ctx()
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous() and x_t.dim() == 2
     n_sig, n_s = x_t.shape
-    plans = [_sos_plan(design_bandpass_filter(lo, hi, fs, order)) for lo, hi in bands]
-    nf, n_sec, edge = len(plans), plans[0][0].shape[0], plans[0][2]
-    assert all(p[0].shape[0] == n_sec and p[2] == edge for p in plans), "the filters of a bank share their structure"
+    bank = bands if isinstance(bands, SosBank) else SosBank.bandpass(bands, fs, order)
+    sos, zi, nf, n_sec, edge = bank.sos, bank.zi, bank.n, bank.n_sec, bank.edge
     if n_s <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
-    sos = np.ascontiguousarray(np.stack([p[0] for p in plans])); zi = np.ascontiguousarray(np.stack([p[1] for p in plans]))
     if y_t is None:
         y_t = torch.empty((nf, n_sig, n_s), dtype=torch.float64, device=x_t.device)
     if work_t is None or work_t.numel() < nf * n_sig * (n_s + 2 * edge):
@@ -227,24 +254,21 @@ def bandpass_bank_dev(x_t, bands, fs, order=FILTER_ORDER, y_t=None, work_t=None,
 def filtfilt_bank_dev(x_t, bas, y_t=None, work_t=None, ctx=None):
     """scipy.signal.filtfilt for a bank of (b, a) pairs on signals of equal length in one launch (filtfilt_bank_ragged_dev:
     different lengths): x_t (n_sig, n_samples) -> y_t
-    (n_filters, n_sig, n_samples) -- bandpass_filter (utils.py:66-74) of the audio envelope for all bands (cmp:63-64)."""
+    (n_filters, n_sig, n_samples) -- bandpass_filter (utils.py:66-74) of the audio envelope for all bands (cmp:63-64).
+    bas: list of (b, a), or the BaBank prepared once."""
     import torch
     ctx = ctx or get_ctx()
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous() and x_t.dim() == 2
     n_sig, n_s = x_t.shape
-    ntaps = max(max(len(b), len(a)) for b, a in bas)
-    B = np.zeros((len(bas), ntaps)); A = np.zeros((len(bas), ntaps)); Z = np.zeros((len(bas), ntaps - 1))
-    for f, (b, a) in enumerate(bas):
-        B[f, :len(b)] = b; A[f, :len(a)] = a
-        Z[f] = signal.lfilter_zi(B[f], A[f])
-    edge = 3 * ntaps
+    bank = bas if isinstance(bas, BaBank) else BaBank(bas)
+    nf, ntaps, edge = bank.n, bank.ntaps, bank.edge
     if n_s <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     if y_t is None:
-        y_t = torch.empty((len(bas), n_sig, n_s), dtype=torch.float64, device=x_t.device)
-    if work_t is None or work_t.numel() < len(bas) * n_sig * (n_s + 2 * edge):
-        work_t = torch.empty((len(bas), n_sig, n_s + 2 * edge), dtype=torch.float64, device=x_t.device)
-    ctx.check(ctx.lib.tda_filtfilt_bank_dev(ctx.h, C.c_void_p(x_t.data_ptr()), n_sig, n_s, ptr(B), ptr(A), ptr(Z), len(bas), ntaps,
+        y_t = torch.empty((nf, n_sig, n_s), dtype=torch.float64, device=x_t.device)
+    if work_t is None or work_t.numel() < nf * n_sig * (n_s + 2 * edge):
+        work_t = torch.empty((nf, n_sig, n_s + 2 * edge), dtype=torch.float64, device=x_t.device)
+    ctx.check(ctx.lib.tda_filtfilt_bank_dev(ctx.h, C.c_void_p(x_t.data_ptr()), n_sig, n_s, ptr(bank.B), ptr(bank.A), ptr(bank.Z), nf, ntaps,
                                             edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return y_t
@@ -287,9 +311,10 @@ def _tables(lengths, device):
     return lengths if isinstance(lengths, RaggedTables) else RaggedTables(lengths, device)
 
 
-def bandpass_bank_ragged_dev(x_t, lengths, bands, fs, n_ch=47, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
+def bandpass_bank_ragged_dev(x_t, lengths, bands, fs=None, n_ch=47, order=FILTER_ORDER, y_t=None, work_t=None, ctx=None):
     """apply_bandpass_filter (nb1:236-263) for ALL bands in one launch on RAGGED recordings: x_t flat float64 (packed,
-    recording r an (n_ch, L_r) block at n_ch * off[r]; see pack_recordings), lengths: L_r (numpy) or RaggedTables.
+    recording r an (n_ch, L_r) block at n_ch * off[r]; see pack_recordings), lengths: L_r (numpy) or RaggedTables,
+    bands: (lowcut, highcut) pairs or a SosBank, as for bandpass_bank_dev.
     Returns y_t (n_bands, n_ch * sum(L)) in the same layout per band, every channel bit-identical to
     scipy.signal.sosfiltfilt on that channel alone.  work_t: optional, n_bands * n_ch * (sum(L) + 2*edge*n_rec) elements."""
     import torch
@@ -297,12 +322,10 @@ def bandpass_bank_ragged_dev(x_t, lengths, bands, fs, n_ch=47, order=FILTER_ORDE
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
     tb = _tables(lengths, x_t.device)
     assert x_t.numel() >= n_ch * tb.total
-    plans = [_sos_plan(design_bandpass_filter(lo, hi, fs, order)) for lo, hi in bands]
-    nf, n_sec, edge = len(plans), plans[0][0].shape[0], plans[0][2]
-    assert all(p[0].shape[0] == n_sec and p[2] == edge for p in plans), "the filters of a bank share their structure"
+    bank = bands if isinstance(bands, SosBank) else SosBank.bandpass(bands, fs, order)
+    sos, zi, nf, n_sec, edge = bank.sos, bank.zi, bank.n, bank.n_sec, bank.edge
     if tb.n and int(tb.len_h.min()) <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
-    sos = np.ascontiguousarray(np.stack([p[0] for p in plans])); zi = np.ascontiguousarray(np.stack([p[1] for p in plans]))
     if y_t is None:
         y_t = torch.empty((nf, n_ch * tb.total), dtype=torch.float64, device=x_t.device)
     n_work = nf * n_ch * (tb.total + 2 * edge * tb.n)
@@ -319,28 +342,25 @@ def filtfilt_bank_ragged_dev(x_t, lengths, bas, y_t=None, work_t=None, ctx=None)
     """scipy.signal.filtfilt for a bank of (b, a) pairs (ntaps <= 9) in one launch on RAGGED signals: x_t flat float64,
     signal s = L_s samples at off[s] (packed; lengths numpy or RaggedTables) -> y_t (n_filters, sum(L)) in the same
     layout -- bandpass_filter (utils.py:66-74, cmp:63-64) of the envelopes of recordings of different lengths, each
-    bit-identical to scipy.signal.filtfilt on that signal alone.  work_t: optional, n_filters * (sum(L) + 2*edge*n)."""
+    bit-identical to scipy.signal.filtfilt on that signal alone.  bas: list of (b, a) or a BaBank.  work_t: optional,
+    n_filters * (sum(L) + 2*edge*n)."""
     import torch
     ctx = ctx or get_ctx()
     assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous()
     tb = _tables(lengths, x_t.device)
     assert x_t.numel() >= tb.total
-    ntaps = max(max(len(b), len(a)) for b, a in bas)
-    B = np.zeros((len(bas), ntaps)); A = np.zeros((len(bas), ntaps)); Z = np.zeros((len(bas), ntaps - 1))
-    for f, (b, a) in enumerate(bas):
-        B[f, :len(b)] = b; A[f, :len(a)] = a
-        Z[f] = signal.lfilter_zi(B[f], A[f])
-    edge = 3 * ntaps
+    bank = bas if isinstance(bas, BaBank) else BaBank(bas)
+    nf, ntaps, edge = bank.n, bank.ntaps, bank.edge
     if tb.n and int(tb.len_h.min()) <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     if y_t is None:
-        y_t = torch.empty((len(bas), tb.total), dtype=torch.float64, device=x_t.device)
-    n_work = len(bas) * (tb.total + 2 * edge * tb.n)
+        y_t = torch.empty((nf, tb.total), dtype=torch.float64, device=x_t.device)
+    n_work = nf * (tb.total + 2 * edge * tb.n)
     if work_t is None or work_t.numel() < n_work:
         work_t = torch.empty(n_work, dtype=torch.float64, device=x_t.device)
     ctx.check(ctx.lib.tda_filtfilt_bank_ragged_dev(ctx.h, C.c_void_p(x_t.data_ptr()), tb.n, C.c_void_p(tb.len_t.data_ptr()),
-                                                   C.c_void_p(tb.off_t.data_ptr()), ptr(tb.len_h), ptr(B), ptr(A), ptr(Z), len(bas),
-                                                   ntaps, edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
+                                                   C.c_void_p(tb.off_t.data_ptr()), ptr(tb.len_h), ptr(bank.B), ptr(bank.A), ptr(bank.Z),
+                                                   nf, ntaps, edge, C.c_void_p(y_t.data_ptr()), C.c_void_p(work_t.data_ptr()),
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return y_t
 
@@ -389,16 +409,13 @@ def recordings_to_features_ragged(raw_packed_t, lengths, fs, sel=None, n_ch=47, 
     dgm = engine.DeviceDiagrams(n_out, n_ch, engine.DEFAULT_H1_CAP, dev)
     fe0 = torch.empty((n_out, 11), dtype=torch.float64, device=dev)
     fe1 = torch.empty_like(fe0)
-    ctx.set_h1_order(ctx.ORDER_DEFERRED)
-    try:
+    with ctx.deferred():
         for bi in range(nb):
             start = torch.from_numpy(start0 + bi * band_len).to(dev)
             engine.eeg_window_ragged_dev(y, start, ld, win, out=dgm, ctx=ctx)
             engine.diagram_finish_dev([(dgm.h0, dgm.c0, False, fe0), (dgm.h1, dgm.c1, True, fe1)], ctx=ctx)
             X[:, bi].index_copy_(0, live_t, engine.aggregate_dev(fe0, fe1, seg, ctx=ctx))
             status |= dgm.status                 # (the next band overwrites the words)
-    finally:
-        ctx.set_h1_order(ctx.ORDER_IN_CALL)
     return X.view(tb.n, nb * 44), status
 
 
@@ -494,11 +511,7 @@ def hilbert_envelope(s, ctx=None):
 
 def compute_envelope(s, fs, ctx=None):
     """scripts/utils.py:56-63 -- Hilbert envelope, then 4th-order low-pass (zero-phase)."""
-    env = hilbert_envelope(s, ctx=ctx)
-    nyq = fs / 2
-    cutoff = min(50, nyq * 0.9)
-    b, a = signal.butter(4, cutoff / nyq, btype="low")
-    return filtfilt(b, a, env, ctx=ctx)
+    return filtfilt(*envelope_lowpass(fs), hilbert_envelope(s, ctx=ctx), ctx=ctx)
 
 
 def audio_to_band_windows(audio, fs_audio=FS_AUDIO, freq_bands=FREQ_BANDS, ctx=None):
@@ -547,6 +560,7 @@ class AudioPlan:
                        (n_in_max, default max(La)) serves every length.
       n_pre_remove, up, down
       hilbert          HilbertTables of the envelope lengths.
+      lowpass          compute_envelope's low-pass at fs (envelope_lowpass) as a one-filter BaBank.
     upload(device) adds the device tables (uploaded once): in_tb / out_tb (RaggedTables of La / n_out), hp_t, g_t, g_off_t."""
 
     def __init__(self, audio_lengths, fs_audio=FS_AUDIO, fs=FS_EEG, n_in_max=None):
@@ -565,6 +579,7 @@ class AudioPlan:
         self.n_out = n_out // self.down + (n_out % self.down > 0)
         self.out_off = np.concatenate([[0], np.cumsum(self.n_out)]).astype(np.int64)
         self.hilbert = HilbertTables(self.n_out)
+        self.lowpass = BaBank([envelope_lowpass(fs)])
         self.device = None
 
     def upload(self, device):
@@ -631,15 +646,14 @@ def envelopes_ragged_dev(audio_packed_t, audio_lengths, fs_audio=FS_AUDIO, fs=FS
     """compute_envelope(resample_audio(a), fs) (utils.py:56-63, 77-79; cmp:53-55) for every recording of a RAGGED set,
     in HBM end to end: audio_packed_t flat float64 (recording s = La_s samples at the exclusive prefix sum of La;
     pack_recordings of 1-D arrays), audio_lengths numpy or AudioPlan.  Three launches: the polyphase resampler, the
-    Hilbert envelope, the low-pass through filtfilt_bank_ragged_dev with one filter.  Returns (env_t flat float64, the
-    envelope lengths n_out, numpy int64), envelope s at the exclusive prefix sum of n_out.  Raises ValueError as scipy
-    does when an envelope is not longer than the low-pass pad length (15).  work_t: optional, 3 * sum(n_out) +
+    Hilbert envelope, the low-pass (the plan's `lowpass` bank) through filtfilt_bank_ragged_dev.  Returns (env_t flat
+    float64, the envelope lengths n_out, numpy int64), envelope s at the exclusive prefix sum of n_out.  Raises ValueError
+    as scipy does when an envelope is not longer than the low-pass pad length (15).  work_t: optional, 3 * sum(n_out) +
     2 * 15 * n_rec elements."""
     import torch
     ctx = ctx or get_ctx()
     P = _audio_plan(audio_lengths, audio_packed_t.device, fs_audio, fs)
-    b, a = envelope_lowpass(fs)
-    edge = 3 * max(len(a), len(b))
+    edge = P.lowpass.edge
     if P.out_tb.n and int(P.n_out.min()) <= edge:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {edge}.")
     T, n = P.out_tb.total, P.out_tb.n
@@ -651,5 +665,5 @@ def envelopes_ragged_dev(audio_packed_t, audio_lengths, fs_audio=FS_AUDIO, fs=FS
     rs, hil, fwork = work_t[:T], work_t[T:2 * T], work_t[2 * T:n_work]
     resample_bank_ragged_dev(audio_packed_t, P, y_t=rs, ctx=ctx)
     hilbert_envelope_ragged_dev(rs, P.out_tb, env_t=hil, g_tables=(P.g_t, P.g_off_t), ctx=ctx)
-    filtfilt_bank_ragged_dev(hil, P.out_tb, [(b, a)], y_t=out_t, work_t=fwork, ctx=ctx)
+    filtfilt_bank_ragged_dev(hil, P.out_tb, P.lowpass, y_t=out_t, work_t=fwork, ctx=ctx)
     return out_t, P.n_out

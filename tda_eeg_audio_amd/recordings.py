@@ -4,18 +4,25 @@ MEMORY: raw EEG (n_rec, 47, L) float64 and the 250 Hz audio envelope (n_rec, L) 
 resampled audio, utils.py:56-63 -- preprocess.compute_envelope) in pinned host buffers go in, the (n_rec, 5, 48) result
 rows [W_H0, W_H1, tau, n_windows, 44 aggregated EEG features] come back to the host.
 
-Per shard of recordings (RecordingPass: recordings of equal length; RaggedRecordingPass below takes recordings of
-different lengths, packed back to back -- preprocess.pack_recordings):
-    H2D of the shard (1.73 MB of EEG per recording instead of the 33 MB of its five window stacks)
-    zero-phase band-pass of all 47 x n_rec EEG channels, all five bands in ONE launch   (nb1:236-263)
-    zero-phase band-pass of the n_rec envelopes, all five bands in one launch, beside it  (utils.py:66-74, cmp:64)
-    the selected 1 s windows of the band-passed envelopes                                (create_windows + np.linspace, cmp:65,77-80)
-    ONE run_step over the (band, recording) groups of the shard: the EEG windows are read IN PLACE from the band-passed
-    recordings (fused window kernel on sliding windows: neither the (n_win, 47, 250) stacks nor the distance matrices
-    exist), tau from the first selected window of every group, Takens + Rips, finish, Wasserstein H0 / H1, rows
-    D2H of the (n_shard, 5, 48) rows
-and the upload of shard k + 1 overlaps the compute of shard k (two sets of buffers, a copy stream); a shard is verified
-(class-overflow flags of its groups) after the next one has been queued.
+ONE shard driver (_ShardedPass.run / _verify) serves every pass of this module.  Per shard of recordings:
+    H2D of the shard on the copy stream (1.73 MB of EEG per recording, not the 33 MB of its five window stacks)
+    the shard's step on the main stream of its buffer set, the envelopes' filters on the set's side stream
+    D2H of the shard's rows on a stream of its own
+and the upload of shard k + 1 overlaps the compute of shard k (n_sets buffer sets); a shard is verified (class-overflow
+flags of its groups) after the later ones have been queued, run again with the full ladder if a flag is set, and its
+rows are withheld if any status bit is left.  The passes differ in how a shard is cut out of the host input and in its step:
+    RecordingPass             recordings of equal length; the step the benchmark's `recordings` leg times:
+        zero-phase band-pass of all 47 x n_rec EEG channels, all five bands in ONE launch   (nb1:236-263)
+        zero-phase band-pass of the n_rec envelopes, all five bands in one launch, beside it  (utils.py:66-74, cmp:64)
+        the selected 1 s windows of the band-passed envelopes                 (create_windows + np.linspace, cmp:65,77-80)
+        ONE run_step over the (band, recording) groups of the shard: the EEG windows are read IN PLACE from the
+        band-passed recordings (fused window kernel on sliding windows: neither the (n_win, 47, 250) stacks nor the
+        distance matrices exist), tau from the first selected window of every group, Takens + Rips, finish,
+        Wasserstein H0 / H1, rows
+    RaggedRecordingPass       recordings of different lengths, packed back to back (preprocess.pack_recordings)
+    RaggedAudioRecordingPass  the same from the raw 44.1 kHz audio instead of the envelopes
+    ControlPass               the matched-vs-mismatched control (scripts/matched_vs_mismatched.py)
+The filter banks are designed and packed once per pass (preprocess.SosBank / BaBank) and handed to every shard's step.
 The rows equal pipeline.run_step on the stacked windows of the same band-passed signals bit for bit
 (tests/test_gpu_frontend.py::test_recording_pass_equals_stacked_windows).
 With correlations=True the passes also return the third result of the script per (recording, band): Spearman r and p of
@@ -26,7 +33,7 @@ comparison_summary turn rows and corr_h into the script's table and statistics.
 import numpy as np
 
 from . import engine, pipeline, preprocess
-from ._lib import get_ctx
+from ._lib import TdaError, get_ctx
 
 MAX_WINDOWS = 15            # cmp:39
 
@@ -36,7 +43,118 @@ def select_windows(n_win, max_windows=MAX_WINDOWS):
     return np.linspace(0, n_win - 1, max_windows, dtype=int) if n_win > max_windows else np.arange(n_win)
 
 
-class RecordingPass:
+class _ShardedPass:
+    """The shard driver of every pass: state, `run` and `_verify`.  A subclass supplies
+      _begin(raw_h, second_h)       checks the host inputs; returns the shards of this run, a list of ranges (r0, r1) of
+                                    recordings (kept as self.ranges)
+      _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
+      _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
+      _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
+      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"])
+      _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
+                                    without a window (nothing to verify)."""
+
+    ROW_COLS = pipeline.RESULT_COLS     # width of a row
+
+    def __init__(self, device, ctx, fs, bands, correlations):
+        self.ctx = ctx or get_ctx()
+        self.dev, self.fs = device, fs
+        self.bands = list(dict(bands).values())
+        self.correlations, self.corr_h = bool(correlations), None
+        # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
+        self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
+        self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
+
+    def _make_sets(self, n_sets, buffers):
+        """buffers() -> the tensors and the Workspace ("ws") of one buffer set.  Buffer sets = shards in flight (upload,
+        filters, step, download of consecutive shards overlap).  A stream pair per set: the filters of shard k + 1 (chains
+        of dependent operations on few waves) run beside the Rips kernels of shard k (which fill the vector units).  Which
+        hardware queue a stream lands on depends on how many were made before it, and a pass' speed on that: the order
+        stays per set the Workspace's own, main, side; then copy, then back."""
+        import torch
+        self.n_sets = int(n_sets)
+        self.set = []
+        for _ in range(self.n_sets):
+            st = buffers()
+            st.update(main=torch.cuda.Stream(device=self.dev), side=torch.cuda.Stream(device=self.dev),
+                      up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event())
+            self.set.append(st)
+        self.copy = torch.cuda.Stream(device=self.dev)                 # uploads
+        self.back = torch.cuda.Stream(device=self.dev)                 # rows back (its own stream: the download of shard k waits
+                                                                       # for the compute of k, the upload of k + 1 must not)
+        self.repairs = 0
+
+    def run(self, raw_h, second_h, rows_h=None):
+        """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
+        call returns (and self.corr_h with correlations=True)."""
+        import torch
+        self.ranges = self._begin(raw_h, second_h)
+        n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
+        if rows_h is None:
+            rows_h = torch.empty((n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
+        if self.correlations and (self.corr_h is None or self.corr_h.shape[0] != n_rec):
+            self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
+        pend = []
+        try:
+            for i, (r0, r1) in enumerate(self.ranges):
+                st = self.set[i % self.n_sets]
+                with torch.cuda.stream(self.copy):
+                    if i >= self.n_sets:            # the shard before in this buffer set has read it and its rows are out
+                        self.copy.wait_event(st["done"])
+                        self.copy.wait_event(st["down"])
+                    self._upload(st, i, raw_h, second_h)
+                    st["up"].record(self.copy)
+                with torch.cuda.stream(st["main"]):
+                    st["main"].wait_event(st["up"])
+                    self._shard_step(st, i)
+                    st["done"].record(st["main"])
+                with torch.cuda.stream(self.back):
+                    self.back.wait_event(st["done"])
+                    rows_h[r0:r1].copy_(st["rows"][:r1 - r0], non_blocking=True)
+                    if self.correlations:
+                        self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0], non_blocking=True)
+                    st["down"].record(self.back)
+                pend.append(i)
+                if len(pend) >= self.n_sets:        # (the GPU has the later shards to work on while the host looks at this
+                    self._verify(pend.pop(0), rows_h)           # one; its buffer set is the next to be reused)
+            while pend:
+                self._verify(pend.pop(0), rows_h)
+        except BaseException:
+            torch.cuda.synchronize(self.dev)        # shards still in flight read the buffer sets the next run fills
+            raise
+        self.back.synchronize()
+        return rows_h
+
+    def _verify(self, i, rows_h):
+        """Verify, then publish: a shard whose step left a class-overflow flag (run_step copies the flags of its groups
+        to pinned memory) is run again with the full ladder -- rare -- and its rows replace the ones already copied; any
+        status bit still left withholds the rows."""
+        import torch
+        st = self.set[i % self.n_sets]
+        r0, r1 = self.ranges[i]
+        st["down"].synchronize()
+        ws = self._flags_ws(st, i)
+        if ws is None:
+            return
+        fl = ws.flags_host
+        if bool((fl & 2).any()):
+            self.repairs += 1
+            with torch.cuda.stream(st["main"]):
+                self._rows(st, i, self._rips_step(st, i, "auto"))
+                rows_h[r0:r1].copy_(st["rows"][:r1 - r0])
+                if self.correlations:
+                    self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0])
+                fl.copy_(ws.seg_flags, non_blocking=True)
+                st["main"].synchronize()
+        if bool(fl.any()):
+            raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")
+
+
+class RecordingPass(_ShardedPass):
+    """Recordings of EQUAL length: `run` takes raw_h (n_rec, n_ch, L) and env_h (n_rec, L), pinned float64, in shards of
+    `shard` recordings; the idle rows of a short last shard repeat its first recording (their groups repeat real ones:
+    their flags say nothing new)."""
+
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
                  max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
@@ -44,136 +162,72 @@ class RecordingPass:
         drivers.DETAILED_COLUMNS[8:].  The rows are the same either way."""
         import os
         import torch
-        from scipy import signal
-        self.ctx = ctx or get_ctx()
-        self.dev, self.S, self.L, self.n_ch, self.fs = device, int(shard), int(n_samples), n_ch, fs
-        self.bands = list(dict(bands).values())
+        super().__init__(device, ctx, fs, bands, correlations)
+        self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
         self.per_rec = (self.L - self.win) // self.step + 1 if self.L >= self.win else 0
         assert self.per_rec > 0, "recordings shorter than one window"
         self.pick = select_windows(self.per_rec, max_windows)
         self.k = len(self.pick)
-        self.correlations, self.corr_h = bool(correlations), None
         S, L, k, nb = self.S, self.L, self.k, len(self.bands)
-        nyq = fs / 2                                                   # utils.py:66-74
-        self.bas = [signal.butter(4, [max(lo / nyq, 0.001), min(hi / nyq, 0.999)], btype="band") for lo, hi in self.bands]
-        edge = preprocess._sos_plan(preprocess.design_bandpass_filter(*self.bands[0], fs, preprocess.FILTER_ORDER))[2]
+        edge, edge_a = self.eeg_bank.edge, self.env_bank.edge
         f64 = dict(dtype=torch.float64, device=device)
         # the (band, recording) groups of a shard are the "recordings" of ONE batch: window (b * S + r) * per_rec + pick
         sel = ((np.arange(nb * S)[:, None]) * self.per_rec + self.pick[None, :]).astype(np.int32).ravel()
         self.sel_t = torch.from_numpy(sel).to(device)
         self.pick_t = torch.from_numpy(self.pick.astype(np.int64)).to(device)
         seg_off = np.arange(0, nb * S * k + 1, k, dtype=np.int32)
-        # buffer sets = shards in flight (upload, filters, step, download of consecutive shards overlap)
-        self.n_sets = int(n_sets or os.environ.get("TDA_REC_SETS", "2"))
-        self.set = [dict(raw=torch.empty((S, n_ch, L), **f64), env=torch.empty((S, L), **f64),
-                         y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
-                         aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
-                         ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations),
-                         corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
-                         work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * 3 * 9), **f64),
-                         # a stream pair per buffer set: the filters of shard k + 1 (chains of dependent operations on few
-                         # waves) run beside the Rips kernels of shard k (which fill the vector units)
-                         main=torch.cuda.Stream(device=device), side=torch.cuda.Stream(device=device),
-                         up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event()) for _ in range(self.n_sets)]
-        self.copy = torch.cuda.Stream(device=device)                   # uploads
-        self.back = torch.cuda.Stream(device=device)                   # rows back (its own stream: the download of shard k waits
-                                                                       # for the compute of k, the upload of k + 1 must not)
-        self.repairs = 0
+        self._make_sets(n_sets or os.environ.get("TDA_REC_SETS", "2"), lambda: dict(
+            raw=torch.empty((S, n_ch, L), **f64), env=torch.empty((S, L), **f64),
+            y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
+            aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
+            ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations),
+            corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
+            work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
-    def _rips_step(self, st, retry):
+    def _begin(self, raw_h, env_h):
+        n_rec = raw_h.shape[0]
+        assert raw_h.shape[1:] == (self.n_ch, self.L) and env_h.shape == (n_rec, self.L)
+        return [(s0, min(s0 + self.S, n_rec)) for s0 in range(0, n_rec, self.S)]
+
+    def _upload(self, st, i, raw_h, env_h):
+        s0, s1 = self.ranges[i]
+        n = s1 - s0
+        st["raw"][:n].copy_(raw_h[s0:s1], non_blocking=True)
+        st["env"][:n].copy_(env_h[s0:s1], non_blocking=True)
+        if n < self.S:                              # a short last shard: the idle rows repeat its first recording
+            st["raw"][n:].copy_(st["raw"][:1].expand(self.S - n, -1, -1))
+            st["env"][n:].copy_(st["env"][:1].expand(self.S - n, -1))
+
+    def _flags_ws(self, st, i):
+        return st["ws"]
+
+    def _rips_step(self, st, i, retry):
         nb = len(self.bands)
         return pipeline.run_step(None, st["aw"], st["ws"], ctx=self.ctx, max_lag=self.win // 2, retry=retry,
                                  eeg_sliding=(st["y"].view(nb * self.S, self.n_ch, self.L), self.win, self.step, self.sel_t))
 
-    def _shard_step(self, st):
-        """Everything between the upload and the rows of one shard, on its main stream (the envelopes' filters on its side stream)."""
+    def _shard_step(self, st, i):
         import torch
         ctx, S, k, nb = self.ctx, self.S, self.k, len(self.bands)
         st["side"].wait_stream(st["main"])
         with torch.cuda.stream(st["side"]):
-            preprocess.filtfilt_bank_dev(st["env"], self.bas, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
+            preprocess.filtfilt_bank_dev(st["env"], self.env_bank, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
             # create_windows + the selection: a strided view of the band-passed envelopes, gathered into the stack the
             # tau / Takens kernels read (2 KB per window: plumbing)
             st["aw"].view(nb * S, k, self.win).copy_(
                 st["ya"].view(nb * S, self.L).unfold(1, self.win, self.step).index_select(1, self.pick_t))
-        preprocess.bandpass_bank_dev(st["raw"].view(S * self.n_ch, self.L), self.bands, self.fs, y_t=st["y"], work_t=st["work"], ctx=ctx)
+        preprocess.bandpass_bank_dev(st["raw"].view(S * self.n_ch, self.L), self.eeg_bank, y_t=st["y"], work_t=st["work"], ctx=ctx)
         st["main"].wait_stream(st["side"])
-        self._rows(st, self._rips_step(st, "one"))
+        self._rows(st, i, self._rips_step(st, i, "one"))
 
-    def _rows(self, st, res):
+    def _rows(self, st, i, res):
         """(nb * S, 48) band-major groups -> the shard's rows (and, with correlations, the same for the workspace's corr)."""
         nb = len(self.bands)
         st["rows"].copy_(res.view(nb, self.S, pipeline.RESULT_COLS).transpose(0, 1))
         if self.correlations:
             st["corr"].copy_(st["ws"].corr.view(nb, self.S, pipeline.CORR_COLS).transpose(0, 1))
-
-    def run(self, raw_h, env_h, rows_h=None):
-        """raw_h (n_rec, n_ch, L), env_h (n_rec, L): pinned float64 host tensors.  Returns rows_h (n_rec, n_bands, 48),
-        pinned, complete when the call returns."""
-        import torch
-        n_rec = raw_h.shape[0]
-        assert raw_h.shape[1:] == (self.n_ch, self.L) and env_h.shape == (n_rec, self.L)
-        nb = len(self.bands)
-        if rows_h is None:
-            rows_h = torch.empty((n_rec, nb, pipeline.RESULT_COLS), dtype=torch.float64).pin_memory()
-        if self.correlations and (self.corr_h is None or self.corr_h.shape[0] != n_rec):
-            self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
-        S = self.S
-        shards = [(s0, min(S, n_rec - s0)) for s0 in range(0, n_rec, S)]
-        pend = []
-        for i, (s0, n) in enumerate(shards):
-            st = self.set[i % self.n_sets]
-            with torch.cuda.stream(self.copy):
-                if i >= self.n_sets:                # the shard before in this buffer set has read it and its rows are out
-                    self.copy.wait_event(st["done"])
-                    self.copy.wait_event(st["down"])
-                st["raw"][:n].copy_(raw_h[s0:s0 + n], non_blocking=True)
-                st["env"][:n].copy_(env_h[s0:s0 + n], non_blocking=True)
-                if n < S:                           # a short last shard: the idle rows repeat its first recording
-                    st["raw"][n:].copy_(st["raw"][:1].expand(S - n, -1, -1))
-                    st["env"][n:].copy_(st["env"][:1].expand(S - n, -1))
-                st["up"].record(self.copy)
-            with torch.cuda.stream(st["main"]):
-                st["main"].wait_event(st["up"])
-                self._shard_step(st)
-                st["done"].record(st["main"])
-            with torch.cuda.stream(self.back):
-                self.back.wait_event(st["done"])
-                rows_h[s0:s0 + n].copy_(st["rows"][:n], non_blocking=True)
-                if self.correlations:
-                    self.corr_h[s0:s0 + n].copy_(st["corr"][:n], non_blocking=True)
-                st["down"].record(self.back)
-            pend.append(i)
-            if len(pend) >= self.n_sets:            # (the GPU has the later shards to work on while the host looks at this one;
-                self._verify(pend.pop(0), rows_h, shards)      # its buffer set is the next to be reused)
-        while pend:
-            self._verify(pend.pop(0), rows_h, shards)
-        self.back.synchronize()
-        return rows_h
-
-    def _verify(self, i, rows_h, shards):
-        """Verify, then publish: a shard whose step left a class-overflow flag (run_step copies the flags of its groups
-        to pinned memory) is run again with the full ladder -- rare -- and its rows replace the ones already copied."""
-        import torch
-        st = self.set[i % self.n_sets]
-        s0, n = shards[i]
-        st["down"].synchronize()
-        fl = st["ws"].flags_host
-        if bool((fl & 2).any()):
-            self.repairs += 1
-            with torch.cuda.stream(st["main"]):
-                self._rows(st, self._rips_step(st, "auto"))
-                rows_h[s0:s0 + n].copy_(st["rows"][:n])
-                if self.correlations:
-                    self.corr_h[s0:s0 + n].copy_(st["corr"][:n])
-                fl.copy_(st["ws"].seg_flags, non_blocking=True)
-                st["main"].synchronize()
-        # (groups of the idle rows of a short last shard repeat real recordings: their flags say nothing new)
-        if bool(fl.any()):
-            from ._lib import TdaError
-            raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -252,7 +306,7 @@ class RaggedPlan:
                     env_start=(band * env_off[-1] + a1[None, :]).ravel())
 
 
-class RaggedRecordingPass:
+class RaggedRecordingPass(_ShardedPass):
     """RecordingPass for recordings of DIFFERENT lengths: raw EEG packed back to back (recording r an (n_ch, L_r) block at
     n_ch * off[r]) and the 250 Hz envelopes packed the same way with their own lengths (Le_r, default L_r), both in pinned
     host memory (preprocess.pack_recordings).  `run` returns the (n_rec, n_bands, 48) rows of process_recording
@@ -263,9 +317,9 @@ class RaggedRecordingPass:
     uploaded once.  Per shard: the ragged SOS bank of all EEG channels and the ragged (b, a) bank of the envelopes (one
     launch each), the selected envelope windows gathered into the stack the tau / Takens kernels read, ONE run_step over
     the (band, recording) groups with the EEG windows read in place through the window table, rows scattered to the
-    recordings.  Upload / compute / download overlap and verify-then-publish as in RecordingPass."""
+    recordings.  Upload / compute / download overlap and verify-then-publish are the shared driver's (_ShardedPass)."""
 
-    ROW_COLS = pipeline.RESULT_COLS     # width of a row (a subclass with other rows: ControlPass)
+    ROW_ZERO = 3                        # the columns of the NaN row of a recording without a window that are 0: n_windows
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
@@ -273,22 +327,16 @@ class RaggedRecordingPass:
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
         recording without a window."""
         import torch
-        from scipy import signal
-        self.ctx = ctx or get_ctx()
-        self.dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n_ch, self.fs = n_ch, fs
-        self.correlations, self.corr_h = bool(correlations), None
-        self.bands = list(dict(bands).values())
+        super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
+                         correlations)
+        self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
         if plan is None:
             plan = RaggedPlan(eeg_lengths, env_lengths, shard_samples, n_ch, nb, fs, window_sec, overlap, max_windows)
         self.plan = P = plan
         self.win, self.step, self.n_rec, self.empty = P.win, P.step, P.n_rec, P.empty
-        nyq = fs / 2                                                   # utils.py:66-74
-        self.bas = [signal.butter(4, [max(lo / nyq, 0.001), min(hi / nyq, 0.999)], btype="band") for lo, hi in self.bands]
-        self.edge = preprocess._sos_plan(preprocess.design_bandpass_filter(*self.bands[0], fs, preprocess.FILTER_ORDER))[2]
-        self.edge_a = 3 * max(max(len(b), len(a)) for b, a in self.bas)
+        self.edge, self.edge_a = self.eeg_bank.edge, self.env_bank.edge
         short = np.flatnonzero((P.L <= self.edge) | (P.Le <= self.edge_a))
         if len(short):
             raise ValueError(f"recording(s) {short[:8].tolist()} not longer than the filters' pad length "
@@ -312,24 +360,34 @@ class RaggedRecordingPass:
         Te = max((d["Te"] for d in self.shards), default=1)
         n_win = max((d["n_win"] for d in self.shards), default=0)
         n_seg = max((nb * d["n_live"] for d in self.shards), default=0)
-        self.n_sets = int(n_sets)
-        self.set = []
-        for _ in range(self.n_sets):
+
+        def buffers():
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
                                     n_ch=n_ch, correlations=self.correlations)
-            self.set.append(dict(
+            return dict(
                 corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
                 aw=torch.empty((max(n_win, 1), self.win), **f64), rows=torch.empty((S, nb, self.ROW_COLS), **f64),
-                ws=ws, views=[ws.view(d["seg_off"]) for d in self.shards],
-                main=torch.cuda.Stream(device=self.dev), side=torch.cuda.Stream(device=self.dev),
-                up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event()))
-        self.copy = torch.cuda.Stream(device=self.dev)
-        self.back = torch.cuda.Stream(device=self.dev)
-        self.repairs = 0
+                ws=ws, views=[ws.view(d["seg_off"]) for d in self.shards])
+        self._make_sets(n_sets, buffers)
+
+    def _begin(self, raw_packed_h, second_packed_h):
+        assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and second_packed_h.numel() == self.second[1][-1]
+        return self.plan.shards
+
+    def _upload(self, st, i, raw_packed_h, second_packed_h):
+        key, sec_off = self.second
+        r0, r1 = self.ranges[i]
+        e0, e1 = self.n_ch * int(self.eeg_off[r0]), self.n_ch * int(self.eeg_off[r1])
+        st["raw"][:e1 - e0].copy_(raw_packed_h.view(-1)[e0:e1], non_blocking=True)
+        a0, a1 = int(sec_off[r0]), int(sec_off[r1])
+        st[key][:a1 - a0].copy_(second_packed_h.view(-1)[a0:a1], non_blocking=True)
+
+    def _flags_ws(self, st, i):
+        return st["views"][i] if self.shards[i]["n_win"] else None
 
     def _rips_step(self, st, i, retry):
         d = self.shards[i]
@@ -337,14 +395,15 @@ class RaggedRecordingPass:
                                  eeg_table=(st["y"], d["eeg_start"], d["eeg_ld"], self.win))
 
     def _rows(self, st, i, res):
-        """(n_bands * n_live, 48) band-major -> the shard's rows; recordings without a window: NaN, n_windows = 0."""
+        """(n_bands * n_live, ROW_COLS) band-major -> the shard's rows; recordings without a window: NaN, with 0 in the
+        columns ROW_ZERO."""
         d = self.shards[i]
         rows = st["rows"][:d["n"]]
         if d["n_live"] < d["n"]:
             rows.fill_(float("nan"))
-            rows[:, :, 3] = 0.0
+            rows[:, :, self.ROW_ZERO] = 0.0
         if d["n_live"]:
-            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], pipeline.RESULT_COLS).transpose(0, 1))
+            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], self.ROW_COLS).transpose(0, 1))
         if self.correlations:
             corr = st["corr"][:d["n"]]
             if d["n_live"] < d["n"]:
@@ -364,77 +423,12 @@ class RaggedRecordingPass:
         st["side"].wait_stream(st["main"])
         with torch.cuda.stream(st["side"]):
             self._front_end(st, i)
-            preprocess.filtfilt_bank_ragged_dev(st["env"], d["env_tb"], self.bas, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
+            preprocess.filtfilt_bank_ragged_dev(st["env"], d["env_tb"], self.env_bank, y_t=st["ya"], work_t=st["worka"], ctx=ctx)
             engine.gather_windows_dev(st["ya"], d["env_start"], self.win, out_t=st["aw"], ctx=ctx)
-        preprocess.bandpass_bank_ragged_dev(st["raw"], d["eeg_tb"], self.bands, self.fs, n_ch=self.n_ch, y_t=st["y"],
+        preprocess.bandpass_bank_ragged_dev(st["raw"], d["eeg_tb"], self.eeg_bank, n_ch=self.n_ch, y_t=st["y"],
                                             work_t=st["work"], ctx=ctx)
         st["main"].wait_stream(st["side"])
         self._rows(st, i, self._rips_step(st, i, "one"))
-
-    def run(self, raw_packed_h, env_packed_h, rows_h=None):
-        """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
-        (n_rec, n_bands, 48), pinned, complete when the call returns."""
-        import torch
-        key, sec_off = self.second
-        assert raw_packed_h.numel() == self.n_ch * self.eeg_off[-1] and env_packed_h.numel() == sec_off[-1]
-        nb = len(self.bands)
-        if rows_h is None:
-            rows_h = torch.empty((self.n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
-        if self.correlations and self.corr_h is None:
-            self.corr_h = torch.empty((self.n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
-        raw_f, env_f = raw_packed_h.view(-1), env_packed_h.view(-1)
-        pend = []
-        for i, d in enumerate(self.shards):
-            st = self.set[i % self.n_sets]
-            r0, r1 = d["r0"], d["r1"]
-            with torch.cuda.stream(self.copy):
-                if i >= self.n_sets:                # the shard before in this buffer set has read it and its rows are out
-                    self.copy.wait_event(st["done"])
-                    self.copy.wait_event(st["down"])
-                e0, e1 = self.n_ch * int(self.eeg_off[r0]), self.n_ch * int(self.eeg_off[r1])
-                st["raw"][:e1 - e0].copy_(raw_f[e0:e1], non_blocking=True)
-                a0, a1 = int(sec_off[r0]), int(sec_off[r1])
-                st[key][:a1 - a0].copy_(env_f[a0:a1], non_blocking=True)
-                st["up"].record(self.copy)
-            with torch.cuda.stream(st["main"]):
-                st["main"].wait_event(st["up"])
-                self._shard_step(st, i)
-                st["done"].record(st["main"])
-            with torch.cuda.stream(self.back):
-                self.back.wait_event(st["done"])
-                rows_h[r0:r1].copy_(st["rows"][:d["n"]], non_blocking=True)
-                if self.correlations:
-                    self.corr_h[r0:r1].copy_(st["corr"][:d["n"]], non_blocking=True)
-                st["down"].record(self.back)
-            pend.append(i)
-            if len(pend) >= self.n_sets:
-                self._verify(pend.pop(0), rows_h)
-        while pend:
-            self._verify(pend.pop(0), rows_h)
-        self.back.synchronize()
-        return rows_h
-
-    def _verify(self, i, rows_h):
-        """As RecordingPass._verify: a shard that left a class-overflow flag is run again with the full ladder, and its rows
-        replace the ones already copied; any flag still left withholds the rows."""
-        import torch
-        st, d = self.set[i % self.n_sets], self.shards[i]
-        st["down"].synchronize()
-        if d["n_win"] == 0:
-            return
-        fl = st["views"][i].flags_host
-        if bool((fl & 2).any()):
-            self.repairs += 1
-            with torch.cuda.stream(st["main"]):
-                self._rows(st, i, self._rips_step(st, i, "auto"))
-                rows_h[d["r0"]:d["r1"]].copy_(st["rows"][:d["n"]])
-                if self.correlations:
-                    self.corr_h[d["r0"]:d["r1"]].copy_(st["corr"][:d["n"]])
-                fl.copy_(st["views"][i].seg_flags, non_blocking=True)
-                st["main"].synchronize()
-        if bool(fl.any()):
-            from ._lib import TdaError
-            raise TdaError(f"window status bits {int(np.bitwise_or.reduce(fl.numpy())):#x} left in shard {i}: rows withheld")
 
 
 class RaggedAudioRecordingPass(RaggedRecordingPass):
@@ -466,13 +460,12 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
         self.second = ("audio", self.audio_off)
         # the filter and Hilbert tables once; per shard its own length / offset tables (AudioPlan of the shard's lengths,
         # its filter designed for the longest audio of the whole set: the same taps in every shard)
-        self.lowpass = preprocess.envelope_lowpass(fs)
         for d in self.shards:
             d["audio"] = preprocess.AudioPlan(A.La[d["r0"]:d["r1"]], fs_audio, fs, n_in_max=int(A.La.max())).upload(self.dev)
         Ta = max((int(self.audio_off[d["r1"]] - self.audio_off[d["r0"]]) for d in self.shards), default=1)
         S = max((d["n"] for d in self.shards), default=1)
         Te = max((d["Te"] for d in self.shards), default=1)
-        edge_lp = 3 * max(len(b) for b in self.lowpass)
+        edge_lp = A.lowpass.edge
         for st in self.set:
             st["audio"] = torch.empty(Ta, dtype=torch.float64, device=self.dev)
             st["front"] = torch.empty(3 * Te + 2 * edge_lp * S, dtype=torch.float64, device=self.dev)
@@ -603,6 +596,7 @@ class ControlPass(RaggedRecordingPass):
     The 250 Hz envelopes are the upload (the _front_end hook is RaggedRecordingPass's)."""
 
     ROW_COLS = CONTROL_COLS
+    ROW_ZERO = slice(2, None)           # the pair counts
 
     def __init__(self, eeg_lengths, env_lengths=None, partner=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2,
                  ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
@@ -684,13 +678,10 @@ class ControlPass(RaggedRecordingPass):
             for st in self.set[1:]:                                      # a run before this one may still read the bank
                 self.bank_stream.wait_stream(st["main"])
             B["env"][:Tb].copy_(self.bank_stage[:Tb], non_blocking=True)
-            preprocess.filtfilt_bank_ragged_dev(B["env"][:Tb], self.bank_tb, self.bas, y_t=B["ya"], work_t=B["work"], ctx=ctx)
+            preprocess.filtfilt_bank_ragged_dev(B["env"][:Tb], self.bank_tb, self.env_bank, y_t=B["ya"], work_t=B["work"], ctx=ctx)
             engine.gather_windows_dev(B["ya"], self.bank_start, self.win, out_t=B["aw"], ctx=ctx)
-            ctx.set_h1_order(ctx.ORDER_DEFERRED)
-            try:                                                         # (the retry policy is the default: the full ladder)
+            with ctx.deferred():                                         # (the retry policy is the default: the full ladder)
                 self._audio_diagrams(B["aw"][:self.n_bank_win], self.bank_seg_off, B["tau_seg"], B["tau_win"], self.bank)
-            finally:
-                ctx.set_h1_order(ctx.ORDER_IN_CALL)
             self.bank_flags.copy_(self._or_bits(self.bank.status).view(1))
             self.bank_flags_host.copy_(self.bank_flags, non_blocking=True)
             self.bank_ready.record(self.bank_stream)
@@ -701,17 +692,10 @@ class ControlPass(RaggedRecordingPass):
         ctx, d, v = self.ctx, self.shards[i], st["views"][i]
         n_e, n_a = d["n_win"], d["n_win_a"]
         aud = st["caud"].head(n_a)
-        if retry != "auto":
-            ctx.set_retry_policy(ctx.RETRY_ONE_STEP)
-        ctx.set_h1_order(ctx.ORDER_DEFERRED)
-        try:
+        with ctx.deferred(retry):
             engine.eeg_window_ragged_dev(st["y"], d["eeg_start"], d["eeg_ld"], self.win, out=v.eeg, n_ch=v.eeg.h0_cap, ctx=ctx)
             if n_a:
                 self._audio_diagrams(st["aw"][:n_a], d["seg_off_a"], st["tau_seg"], st["tau_win"], aud)
-        finally:
-            ctx.set_h1_order(ctx.ORDER_IN_CALL)
-            if retry != "auto":
-                ctx.set_retry_policy(ctx.RETRY_AUTO)
         engine.diagram_finish_dev([(v.eeg.h1, v.eeg.c1, True, None)], ctx=ctx)
         torch.cuda.current_stream().wait_event(self.bank_ready)
         wm, sm, wx, sx = st["wm"][:n_e], st["sm"][:n_e], st["wx"][:n_e], st["sx"][:n_e]
@@ -727,16 +711,6 @@ class ControlPass(RaggedRecordingPass):
             v.flags_host.copy_(v.seg_flags, non_blocking=True)
         return res
 
-    def _rows(self, st, i, res):
-        """(n_bands * n_live, 4) band-major -> the shard's rows; recordings without an EEG window: NaN, no pairs."""
-        d = self.shards[i]
-        rows = st["rows"][:d["n"]]
-        if d["n_live"] < d["n"]:
-            rows.fill_(float("nan"))
-            rows[:, :, 2:] = 0.0
-        if d["n_live"]:
-            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], CONTROL_COLS).transpose(0, 1))
-
     def run(self, raw_packed_h, env_packed_h, rows_h=None):
         """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
         (n_rec, n_bands, 4) [w_matched, w_mismatched, n_matched, n_mismatched], pinned, complete when the call returns."""
@@ -745,6 +719,5 @@ class ControlPass(RaggedRecordingPass):
         rows_h = super().run(raw_packed_h, env_packed_h, rows_h)
         self.bank_ready.synchronize()
         if int(self.bank_flags_host[0]):
-            from ._lib import TdaError
             raise TdaError(f"window status bits {int(self.bank_flags_host[0]):#x} left in the partners' diagrams: rows withheld")
         return rows_h
