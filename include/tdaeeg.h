@@ -479,6 +479,45 @@ tda_status tda_cross_rows_dev(tda_ctx* ctx, const double* w_matched, const int* 
                               const double* w_mismatched, const int* status_mismatched, const int* seg_off_a,
                               int n_seg, double* out, const int* status_a, int* seg_flags, void* stream);
 
+/* ---- the match-mismatch matrix: every A group against every candidate column ------------
+ * compute_cross_wasserstein (mvm:86-95) of the EEG diagrams of every (recording, band) group against the audio diagrams
+ * of EVERY candidate recording, not only the own audio and one mismatched partner (mvm:134-145): the matched distance,
+ * the reference's mismatched column, a null distribution per recording and the rank of the true audio all come from
+ * this one matrix.
+ * A side: dgm_a (n_a, cap_a, 2), cnt_a (n_a), seg_off_a (n_seg_a + 1) int32, cls_a (n_seg_a) int32 = the class (band) of
+ * every group, 0 .. n_cls - 1; a group with another value has no entry anywhere (NaN, 0 pairs).  B side: dgm_b
+ * (n_b, cap_b, 2), cnt_b, status_b (n_b) and seg_off_b with n_cls * n_col + 1 entries: the B groups class-major, the
+ * group of (class k, column c) is k * n_col + c; an empty group is a column without audio.
+ * Entry (g, c) is what tda_wasserstein_cross_dev with partner_seg[g] = cls_a[g] * n_col + c followed by
+ * tda_cross_rows_dev gives for group g, bit for bit: out[g, c] the mean over the pairs (numpy's pairwise tree, a pair
+ * with a solver status counts as NaN; no pair: NaN), pairs[g, c] their number, flags[g, c] the OR of their solver
+ * status words without TDA_WIN_NO_PAIR and TDA_WIN_DEGENERATE.  The pairing rules are tda_wasserstein_cross_dev's;
+ * table entries that point outside the tables count as "no pair".  A group of more than 64 diagrams gets NaN, 0 pairs
+ * and TDA_WIN_TOO_LARGE in every column.
+ * out float64, pairs int32, flags int32, each (n_seg_a, n_col) row-major; every word is written by the call (nothing
+ * has to be cleared before it).  No per-pair array exists, on the host or the device.  Honours tda_set_launch_scheme
+ * as the other Wasserstein entry points.  Device pointers only, enqueue-only, no allocation (TDA_SCHEME_LISTS outside
+ * a capture may grow the per-stream lists to 65,536 entries once).                                        */
+tda_status tda_wasserstein_matrix_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                      const int* seg_off_a, int n_seg_a, const int* cls_a,
+                                      const double* dgm_b, const int* cnt_b, int cap_b, int n_b,
+                                      const int* seg_off_b, int n_cls, int n_col, const int* status_b,
+                                      double* out, int* pairs, int* flags, void* stream);
+
+/* ---- one row of the match-mismatch matrix per (recording, band) group ---------------------
+ * rows: (n_seg_a, 6) float64 = [ w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean ] from out / pairs / flags of
+ * tda_wasserstein_matrix_dev and own_col (n_seg_a) int32, the column of the group's own audio (mvm:136-137) or -1.
+ * w_own = out[g, own_col[g]] and n_own_pairs its pair count.  The others are the columns c != own_col[g] with a finite
+ * entry: n_valid their number, n_less / n_equal how many of them are < / == w_own (the midrank of the true audio among
+ * n_valid + 1 candidates is 1 + n_less + n_equal / 2), null_mean their mean (NaN without any; a sum of non-negative
+ * terms in the kernel's own order: within (n_valid + 1) * 2^-52 relative of numpy's).  Without an own column, or with
+ * a NaN there: w_own = NaN, n_less = n_equal = 0, n_valid and null_mean over all finite columns.
+ * status_a (nullable, with seg_off_a) / seg_flags (nullable): as tda_cross_rows_dev -- per group the OR of the row's
+ * flags and of the group's status_a words without TDA_WIN_NO_PAIR and TDA_WIN_DEGENERATE.                   */
+tda_status tda_match_rows_dev(tda_ctx* ctx, const double* out, const int* pairs, const int* flags,
+                              int n_seg_a, int n_col, const int* own_col, const int* status_a, const int* seg_off_a,
+                              double* rows, int* seg_flags, void* stream);
+
 /* ---- timing helper ------------------------------------------------------------
  * HIP-event timing on the stream the kernels are launched on (bench.py roofline). */
 tda_status tda_event_create(tda_ctx* ctx, void** ev);

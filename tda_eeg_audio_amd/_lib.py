@@ -94,6 +94,9 @@ SYMBOLS = {
     "tda_wasserstein_cross_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp,
                                        c_vp, c_vp, c_vp]),
     "tda_cross_rows_dev": (_I, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_wasserstein_matrix_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp]),
+    "tda_match_rows_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),

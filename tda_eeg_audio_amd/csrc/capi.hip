@@ -424,6 +424,36 @@ tda_status tda_cross_rows_dev(tda_ctx* ctx, const double* w_matched, const int* 
                              status_a, seg_flags, (hipStream_t)stream);
 }
 
+tda_status tda_wasserstein_matrix_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                      const int* seg_off_a, int n_seg_a, const int* cls_a, const double* dgm_b,
+                                      const int* cnt_b, int cap_b, int n_b, const int* seg_off_b, int n_cls, int n_col,
+                                      const int* status_b, double* out, int* pairs, int* flags, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_seg_a); CHECK_NONNEG(ctx, n_b); CHECK_NONNEG(ctx, n_cls);
+    CHECK_NONNEG(ctx, n_col);
+    if (n_seg_a == 0 || n_col == 0) return TDA_OK;
+    CHECK_PTR(ctx, seg_off_a); CHECK_PTR(ctx, cls_a); CHECK_PTR(ctx, out); CHECK_PTR(ctx, pairs); CHECK_PTR(ctx, flags);
+    if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if ((long long)n_cls * n_col >= 0x7fffffffll) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "more than 2^31 - 2 B groups");
+    if (n_b && n_cls) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, seg_off_b); CHECK_PTR(ctx, status_b); }
+    else { n_b = 0; n_cls = 0; }                                       // nothing to pair with: every entry is NaN with 0 pairs
+    return launch_wasserstein_matrix(ctx, dgm_a, cnt_a, cap_a, n_a, seg_off_a, n_seg_a, cls_a, dgm_b, cnt_b, cap_b, n_b,
+                                     seg_off_b, n_cls, n_col, status_b, out, pairs, flags, (hipStream_t)stream);
+}
+
+tda_status tda_match_rows_dev(tda_ctx* ctx, const double* out, const int* pairs, const int* flags, int n_seg_a, int n_col,
+                              const int* own_col, const int* status_a, const int* seg_off_a, double* rows, int* seg_flags,
+                              void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg_a); CHECK_NONNEG(ctx, n_col);
+    if (n_seg_a == 0) return TDA_OK;
+    CHECK_PTR(ctx, own_col); CHECK_PTR(ctx, rows);
+    if (n_col) { CHECK_PTR(ctx, out); CHECK_PTR(ctx, pairs); CHECK_PTR(ctx, flags); }
+    if (status_a) CHECK_PTR(ctx, seg_off_a);
+    return launch_match_rows(ctx, out, pairs, flags, n_seg_a, n_col, own_col, status_a, seg_off_a, rows, seg_flags,
+                             (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.

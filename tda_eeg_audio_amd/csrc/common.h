@@ -233,3 +233,7 @@ tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, in
                                     const int*, int, int, const int*, int, const int*, const int*, double*, int*, hipStream_t);
 tda_status launch_cross_rows(tda_ctx*, const double*, const int*, const double*, const int*, const int*, int, double*,
                              const int*, int*, hipStream_t);
+tda_status launch_wasserstein_matrix(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, const double*,
+                                     const int*, int, int, const int*, int, int, const int*, double*, int*, int*, hipStream_t);
+tda_status launch_match_rows(tda_ctx*, const double*, const int*, const int*, int, int, const int*, const int*, const int*,
+                             double*, int*, hipStream_t);

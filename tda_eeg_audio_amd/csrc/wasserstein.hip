@@ -108,6 +108,21 @@ struct ws_table_pairs {
     }
 };
 
+// ws_matrix_pairs: the pairs of ONE entry (A group g, candidate column c) of tda_wasserstein_matrix_dev; pr is the
+// position within the group.  The kernel has resolved the two groups (a0: first A diagram of g, b0 / len_b: the B group
+// of (class of g, column c)) and made sure that a0 + pr stays inside the A table for every position it asks for.
+struct ws_matrix_pairs {
+    const int* status_b; int a0, b0, len_b, n_b;
+    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
+    {
+        ia = a0 + pr;
+        if (pr >= len_b) return false;
+        ib = b0 + pr;
+        if (ib < 0 || ib >= n_b) return false;
+        return !(status_b[ib] & TDA_WIN_DEGENERATE);
+    }
+};
+
 // pair pr, by the one wave of the workgroup
 template <int CW, class SRC>
 __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
@@ -572,4 +587,208 @@ tda_status launch_wasserstein_cross(tda_ctx* ctx, const double* dgm_a, const int
 {
     const ws_table_pairs src{grp_a, seg_off_a, seg_off_b, partner_seg, status_b, n_seg_a, n_seg_b, n_b};
     return launch_wasserstein_src(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, n_a, out, status, st);
+}
+
+// ---------------------------------------------------------------------------------
+// The match-mismatch matrix (tda_wasserstein_matrix_dev): entry (g, c) = the row tda_wasserstein_cross_dev +
+// tda_cross_rows_dev give A group g against the B group of (class of g, column c) -- mean distance, pair count, flags --
+// without a per-pair array in HBM.
+// One workgroup of ONE wave per entry.  The wave takes the positions of the group one after the other through ws_solve
+// -- the solver as it is: its pair source is ws_matrix_pairs, and its `out` / `status` are the entry's result slots in
+// LDS, behind the solver's own region -- then lane 0 reduces the slots with cross_rows_kernel's arithmetic and writes
+// the entry's three words.  One wave, not four taking the positions in turn: ws_solve synchronises with workgroup
+// barriers that its early exits leave out, which is sound for one wave only; a launch has n_seg_a * n_col entries (1.7
+// million for a shard of the corpus), so the machine is full either way; a wave needs its own 4.3 KB of solver LDS in
+// both designs; and four-wave workgroups would idle three waves on the short groups.  (Not measured against the
+// four-wave form.)
+// The two-launch scheme is the pairs': the first launch has LDS for 64 x 64 points; an entry with a pair that does not
+// fit is put on the stream's list (TDA_SCHEME_LISTS, relative to the chunk of entries of the launch) or marked
+// WS_DEFERRED in flags (TDA_SCHEME_GRID) and redone as a whole by the launch sized by the capacities.
+// ---------------------------------------------------------------------------------
+#define WS_MATRIX_MAX_GROUP 64          // A diagrams per group: 768 B of result slots, 5,120 B of LDS per wave in the first launch
+struct ws_matrix_args {
+    const int* seg_off_a; const int* cls_a; const int* seg_off_b; const int* status_b;
+    int n_a, n_b, n_cls, n_col;
+    double* out; int* pairs; int* flags;
+};
+
+// numpy's sum of n <= 128 terms: eight interleaved accumulators (np_pairwise_leaf of features.hip, restated -- a header
+// shared with features.hip moved instructions in that file's kernels)
+template <class F>
+__device__ __forceinline__ double ws_np_sum(const F& f, int n)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res += f(i);
+        return res;
+    }
+    double r0 = f(0), r1 = f(1), r2 = f(2), r3 = f(3), r4 = f(4), r5 = f(5), r6 = f(6), r7 = f(7);
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8) {
+        r0 += f(i + 0); r1 += f(i + 1); r2 += f(i + 2); r3 += f(i + 3);
+        r4 += f(i + 4); r5 += f(i + 5); r6 += f(i + 6); r7 += f(i + 7);
+    }
+    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+    for (; i < n; ++i) res += f(i);
+    return res;
+}
+
+// smem: the solver's region (solver_bytes), then the slots
+template <int CW>
+__device__ __forceinline__ void ws_matrix_entry(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                                                const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                                                const ws_matrix_args& M, size_t e, int e_rel, int max_rows, int max_cols,
+                                                int solver_bytes, int mode, int* list, unsigned char* smem)
+{
+    const int lane = lane_id();
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const int g = (int)(e / (size_t)M.n_col), c = (int)(e % (size_t)M.n_col);
+    // the two groups; indices that leave a table: no pair
+    const int a0 = uni(M.seg_off_a[g]), a1 = uni(M.seg_off_a[g + 1]);
+    const int len = (a0 >= 0 && a1 >= a0 && a1 <= M.n_a) ? a1 - a0 : 0;
+    const int k = uni(M.cls_a[g]);
+    int b0 = 0, len_b = 0;
+    if (k >= 0 && k < M.n_cls) {
+        const size_t p = (size_t)k * M.n_col + c;
+        b0 = uni(M.seg_off_b[p]);
+        len_b = uni(M.seg_off_b[p + 1]) - b0;
+    }
+    if (len > WS_MATRIX_MAX_GROUP) {
+        if (lane == 0) { M.out[e] = qnan; M.pairs[e] = 0; M.flags[e] = TDA_WIN_TOO_LARGE; }
+        return;
+    }
+    double* xs = reinterpret_cast<double*>(smem + solver_bytes);
+    int* ss = reinterpret_cast<int*>(xs + WS_MATRIX_MAX_GROUP);
+    const ws_matrix_pairs src{M.status_b, a0, b0, len_b, M.n_b};
+    const int n_try = len < len_b ? len : len_b;
+    if (lane >= n_try && lane < len) { xs[lane] = qnan; ss[lane] = TDA_WIN_NO_PAIR; }      // positions past the B group
+    bool deferred = false;
+    for (int i = 0; i < n_try && !deferred; ++i) {
+        ws_solve<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, i, max_rows, max_cols, xs, ss, mode ? 1 : 0, nullptr, smem);
+        __syncthreads();
+        deferred = mode && uni(ss[i]) == WS_DEFERRED;
+    }
+    if (deferred) {                                                      // the whole entry again, in the wide launch
+        if (lane == 0) {
+            if (list) list[4 + atomicAdd(&list[0], 1)] = e_rel;
+            else M.flags[e] = WS_DEFERRED;
+        }
+        return;
+    }
+    __syncthreads();
+    if (lane == 0) {                                                     // cross_rows_kernel's arithmetic
+        int n = 0, cnt = 0, fl = 0;
+        for (int i = 0; i < len; ++i) n += (ss[i] & TDA_WIN_NO_PAIR) ? 0 : 1;
+        for (int i = 0; i < n; ++i) {
+            cnt += (ss[i] == 0 && xs[i] == xs[i]) ? 1 : 0;
+            fl |= ss[i];
+        }
+        auto val = [=](int j) { const double v = xs[j]; return (ss[j] == 0 && v == v) ? v : 0.0; };
+        const double sum = ws_np_sum(val, n);                             // (n <= 64: numpy's tree is its leaf)
+        M.out[e] = cnt > 0 ? sum / (double)cnt : qnan;
+        M.pairs[e] = n;
+        M.flags[e] = fl & ~(TDA_WIN_NO_PAIR | TDA_WIN_DEGENERATE);
+    }
+}
+
+// modes as wasserstein_kernel's: 1 = small first launch, 2 = the marked entries with the layout of the capacities,
+// 0 = one launch for everything.  Entries e0 .. e0 + n_e - 1.
+template <int CW>
+__global__ void __launch_bounds__(64)
+wasserstein_matrix_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                          const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                          const ws_matrix_args M, size_t e0, int n_e, int max_rows, int max_cols, int solver_bytes, int mode,
+                          int* list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if ((int)blockIdx.x >= n_e) return;
+    const size_t e = e0 + blockIdx.x;
+    if (mode == 2 && M.flags[e] != WS_DEFERRED) return;
+    ws_matrix_entry<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e, (int)blockIdx.x, max_rows, max_cols, solver_bytes,
+                        mode == 1, list, smem);
+}
+
+// the entries on the list of the small launch (the layout and the clearing of wasserstein_list_kernel's)
+template <int CW>
+__global__ void __launch_bounds__(64)
+wasserstein_matrix_list_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
+                               const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
+                               const ws_matrix_args M, size_t e0, int n_e, int max_rows, int max_cols, int solver_bytes,
+                               int* list)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int nl = uni(list[0]);
+    nl = nl < n_e ? nl : n_e;
+    for (int j = blockIdx.x; j < nl; j += gridDim.x) {
+        const int r = uni(list[4 + j]);
+        if (r >= 0 && r < n_e)
+            ws_matrix_entry<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0 + (size_t)r, r, max_rows, max_cols, solver_bytes, 0,
+                                nullptr, smem);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && atomicAdd(&list[1], 1) == (int)gridDim.x - 1) { list[0] = 0; list[1] = 0; }
+}
+
+#define WS_MATRIX_CHUNK (1 << 16)        // entries per launch under TDA_SCHEME_LISTS: the capacity asked of the stream's list
+#define WS_MATRIX_GRID_CHUNK (1 << 30)   // ... per launch otherwise (gridDim.x)
+#define WS_MATRIX_LIST_GRID 2048         // workgroups over a list: a listed entry is up to 64 wide solves, and 2,048 one-wave
+                                         // workgroups with the LDS of capacity 256 are what 256 CUs hold at once
+
+tda_status launch_wasserstein_matrix(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
+                                     const int* seg_off_a, int n_seg_a, const int* cls_a, const double* dgm_b,
+                                     const int* cnt_b, int cap_b, int n_b, const int* seg_off_b, int n_cls, int n_col,
+                                     const int* status_b, double* out, int* pairs, int* flags, hipStream_t st)
+{
+    const size_t n_ent = (size_t)n_seg_a * (size_t)n_col;
+    if (n_ent == 0) return TDA_OK;
+    if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
+    const int lo = cap_a < cap_b ? cap_a : cap_b, hi = cap_a < cap_b ? cap_b : cap_a;
+    const int max_rows = lo, max_cols = hi;
+    if (max_cols > 512) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "diagrams with more than 512 rows are not supported");
+    const ws_matrix_args M{seg_off_a, cls_a, seg_off_b, status_b, n_a, n_b, n_cls, n_col, out, pairs, flags};
+    // the solver's layouts (launch_wasserstein_src), each followed by the result slots of the entry
+    const size_t lds_res = (size_t)WS_MATRIX_MAX_GROUP * 12;
+    const int lds_solver = (4 * max_rows + 4 * max_cols + ((max_cols + 1) >> 1)) * 8;
+    const size_t lds_w = lds_solver + lds_res;
+    const int sr = max_rows < 64 ? max_rows : 64;
+    const int lds_solver_s = (4 * sr + 4 * 64 + 32) * 8;
+    const size_t lds_s = lds_solver_s + lds_res;
+    static const bool one_launch = getenv("TDA_WS_ONE_LAUNCH") != nullptr;
+    const int scheme = one_launch ? TDA_SCHEME_ONE : ctx->launch_scheme;
+    const int mode = (scheme != TDA_SCHEME_ONE && max_cols > 128) ? 2 : 0;
+    int* list = nullptr;
+    if (mode && scheme == TDA_SCHEME_LISTS) {
+        int slot = -1;
+        const tda_status rc = stream_lists_take(ctx, (int)(n_ent < WS_MATRIX_CHUNK ? n_ent : WS_MATRIX_CHUNK), st, &slot);
+        if (rc != TDA_OK) return rc;
+        if (slot >= 0) list = ctx->ws_list[slot];        // (else: no list of that size, the launch over the batch)
+    }
+    const size_t chunk = list ? WS_MATRIX_CHUNK : WS_MATRIX_GRID_CHUNK;
+    for (size_t e0 = 0; e0 < n_ent; e0 += chunk) {
+        const int n_e = (int)(n_ent - e0 < chunk ? n_ent - e0 : chunk);
+        if (mode)
+            hipLaunchKernelGGL(wasserstein_matrix_kernel<1>, dim3(n_e), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
+                               cap_b, M, e0, n_e, sr, 64, lds_solver_s, 1, list);
+#define WS_MATRIX_LAUNCH(CWV)                                                                                  \
+    do {                                                                                                       \
+        auto kern = wasserstein_matrix_kernel<CWV>;                                                            \
+        auto lkern = wasserstein_matrix_list_kernel<CWV>;                                                      \
+        if (lds_w > 48 * 1024)                                                                                 \
+            TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern)                       \
+                                                  : reinterpret_cast<const void*>(kern),                       \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));         \
+        if (list)                                                                                              \
+            hipLaunchKernelGGL(lkern, dim3(n_e < WS_MATRIX_LIST_GRID ? n_e : WS_MATRIX_LIST_GRID), dim3(64), lds_w, st,  \
+                               dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e, max_rows, max_cols, lds_solver, list); \
+        else                                                                                                   \
+            hipLaunchKernelGGL(kern, dim3(n_e), dim3(64), lds_w, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, \
+                               M, e0, n_e, max_rows, max_cols, lds_solver, mode, (int*)nullptr);               \
+    } while (0)
+        if (max_cols <= 128) WS_MATRIX_LAUNCH(2);
+        else if (max_cols <= 256) WS_MATRIX_LAUNCH(4);
+        else WS_MATRIX_LAUNCH(8);
+#undef WS_MATRIX_LAUNCH
+    }
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
 }

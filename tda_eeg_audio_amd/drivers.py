@@ -20,6 +20,8 @@ reference's on-disk formats.
                             cmp:145-157 and cmp:161-220 from the rows and correlations of a batched pass
                             (recordings.*RecordingPass(correlations=True)): the detailed table and the per-band statistics
                             of results/eeg_audio_tda_comparison.json
+  match_rows_host / match_mismatch_summary
+                            the per-band statistics of the match-mismatch matrix (recordings.MatchMismatchPass)
 """
 import hashlib
 from pathlib import Path
@@ -514,6 +516,79 @@ def control_summary(rows, subjects, conditions=None, bands=BANDS):
                          "direction": "matched < mismatched" if mean_m < mean_x else "matched > mismatched",
                          "p": float(p), "cohens_d": float(np.mean(diff) / (np.std(diff, ddof=1) + 1e-10)),
                          "n_matched_lower": n_lower, "pct_matched_lower": float(n_lower / n * 100)}
+    reject, pfdr = fdr_bh([results[b].get("p", 1.0) for b in bands])
+    for i, band in enumerate(bands):
+        if "p" in results[band]:
+            results[band]["p_fdr"] = float(pfdr[i])
+            results[band]["sig_fdr"] = bool(reject[i])
+    return results
+
+
+def match_rows_host(dist, own_col, keep=None):
+    """engine.match_rows_dev restated in numpy: dist (n_rec, n_bands, n_col), own_col (n_rec,) -> (n_rec, n_bands, 5)
+    [w_own, n_valid, n_less, n_equal, null_mean] (the device's rows without the pair count).  keep: optional bool
+    (n_rec, n_col), the columns that may count among the others of a recording (the own column never does)."""
+    dist = np.asarray(dist, dtype=np.float64)
+    n_rec, nb, n_col = dist.shape
+    out = np.full((n_rec, nb, 5), np.nan)
+    out[:, :, 1:4] = 0.0
+    for r in range(n_rec):
+        own = int(own_col[r]) if 0 <= own_col[r] < n_col else -1
+        others = np.ones(n_col, bool) if keep is None else np.asarray(keep[r], bool).copy()
+        if own >= 0:
+            others[own] = False
+        for b in range(nb):
+            v = dist[r, b, others & np.isfinite(dist[r, b])]
+            w = dist[r, b, own] if own >= 0 else np.nan
+            out[r, b, 0], out[r, b, 1] = w, len(v)
+            if not np.isnan(w):
+                out[r, b, 2], out[r, b, 3] = np.sum(v < w), np.sum(v == w)
+            if len(v):
+                out[r, b, 4] = v.mean()
+    return out
+
+
+def match_mismatch_summary(rows, dist, subjects, conditions=None, bands=BANDS, candidates=None, exclude_same_subject=False):
+    """Host only: the per-band statistics of the match-mismatch matrix of recordings.MatchMismatchPass.  rows
+    (n_rec, n_bands, 6) [w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean], dist (n_rec, n_bands, n_col), one
+    subject label per recording; candidates: the recording of every column (default: all, in order).  Per band, over the
+    recordings with a finite w_own and at least one other finite column:
+      n, top1 (share of recordings whose true audio has midrank 1 + n_less + n_equal / 2 = 1 among n_valid + 1
+      candidates), mean_percentile (mean of (n_less + n_equal / 2) / n_valid: 0 = always the closest, 0.5 = chance),
+      matched_mean, null_mean, Wilcoxon's p of w_own - null_mean across recordings (1.0 when all differences are zero),
+      Cohen's d of that paired difference -- control_summary's conventions (mvm:197-202); below 5 recordings
+      {"n", "status": "insufficient"} -- and Benjamini-Hochberg over the bands (fdr_bh, mvm:212-217).
+    exclude_same_subject=True: the counts and the null mean are taken again from dist with the columns of the
+    recording's own subject left out, the own column excepted (another recording of the same infant is no independent
+    mismatch).  conditions: accepted for symmetry with control_summary."""
+    from scipy.stats import wilcoxon
+    rows, dist = np.asarray(rows, dtype=np.float64), np.asarray(dist, dtype=np.float64)
+    subjects = np.asarray([str(s) for s in subjects])
+    bands = list(bands)
+    n_rec, nb, n_col = dist.shape
+    cand = np.arange(n_rec) if candidates is None else np.asarray(candidates, dtype=np.int64).ravel()
+    assert rows.shape == (n_rec, nb, 6) and len(subjects) == n_rec and nb == len(bands) and len(cand) == n_col
+    assert conditions is None or len(conditions) == n_rec
+    if exclude_same_subject:
+        own_col = np.full(n_rec, -1, np.int64)
+        own_col[cand] = np.arange(n_col)
+        m = match_rows_host(dist, own_col, keep=subjects[:, None] != subjects[cand][None, :])
+        w_own, n_valid, n_less, n_equal, null = (m[:, :, j] for j in range(5))
+    else:
+        w_own, n_valid, n_less, n_equal, null = (rows[:, :, j] for j in (0, 2, 3, 4, 5))
+    results = {}
+    for b, band in enumerate(bands):
+        ok = np.isfinite(w_own[:, b]) & (n_valid[:, b] > 0)
+        n = int(ok.sum())
+        if n < 5:
+            results[band] = {"n": n, "status": "insufficient"}
+            continue
+        below = n_less[ok, b] + 0.5 * n_equal[ok, b]
+        diff = w_own[ok, b] - null[ok, b]
+        p = wilcoxon(diff)[1] if np.any(diff != 0) else 1.0
+        results[band] = {"n": n, "top1": float(np.mean(1.0 + below == 1.0)), "mean_percentile": float(np.mean(below / n_valid[ok, b])),
+                         "matched_mean": float(w_own[ok, b].mean()), "null_mean": float(null[ok, b].mean()), "p": float(p),
+                         "cohens_d": float(np.mean(diff) / (np.std(diff, ddof=1) + 1e-10))}
     reject, pfdr = fdr_bh([results[b].get("p", 1.0) for b in bands])
     for i, band in enumerate(bands):
         if "p" in results[band]:

@@ -10,6 +10,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
                  from group tables (recordings.ControlPass).
+                 wasserstein_matrix_dev / match_rows_dev: every group against every candidate column
+                 (recordings.MatchMismatchPass).
 """
 import ctypes as C
 
@@ -579,3 +581,55 @@ def cross_rows_dev(w_m, st_m, w_x, st_x, seg_off_a, out_t=None, status_a=None, s
     ctx.check(ctx.lib.tda_cross_rows_dev(ctx.h, _tp(w_m), _tp(st_m), _tp(w_x), _tp(st_x), _tp(seg_off_a), n_seg, _tp(out_t),
                                          _tp(status_a), _tp(seg_flags), _stream()))
     return out_t
+
+
+MATCH_COLS = 6              # [w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean]
+
+
+def wasserstein_matrix_dev(rows_a, cnt_a, seg_off_a, cls_a, rows_b, cnt_b, seg_off_b, status_b, n_col, out_t=None,
+                           pairs_t=None, flags_t=None, ctx=None):
+    """mvm:86-95 of every A group against EVERY candidate column at once.  The B groups are class-major: the group of
+    (class k, column c) is k * n_col + c, so seg_off_b has n_cls * n_col + 1 entries; cls_a (n_seg_a,) names the class
+    (band) of every A group.  Returns out (n_seg_a, n_col) float64, pairs and flags (n_seg_a, n_col) int32: entry (g, c)
+    is the mismatched mean, pair count and flags that wasserstein_cross_dev with partner_seg[g] = cls_a[g] * n_col + c
+    and cross_rows_dev give, bit for bit.  All tables int32 device tensors."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_a, n_b = rows_a.shape[0], rows_b.shape[0]
+    n_seg_a, n_col = seg_off_a.numel() - 1, int(n_col)
+    n_cls = (seg_off_b.numel() - 1) // n_col if n_col else 0
+    for t in (seg_off_a, cls_a, seg_off_b, status_b):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert seg_off_b.numel() == n_cls * n_col + 1 and cls_a.numel() == n_seg_a
+    assert status_b.numel() >= n_b and cnt_a.numel() >= n_a and cnt_b.numel() >= n_b
+    if out_t is None:
+        out_t = torch.empty((n_seg_a, n_col), dtype=torch.float64, device=rows_a.device)
+    if pairs_t is None:
+        pairs_t = torch.empty((n_seg_a, n_col), dtype=torch.int32, device=rows_a.device)
+    if flags_t is None:
+        flags_t = torch.empty((n_seg_a, n_col), dtype=torch.int32, device=rows_a.device)
+    for t in (out_t, pairs_t, flags_t):
+        assert t.is_contiguous() and t.numel() >= n_seg_a * n_col
+    ctx.check(ctx.lib.tda_wasserstein_matrix_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], n_a, _tp(seg_off_a), n_seg_a,
+                                                 _tp(cls_a), _tp(rows_b), _tp(cnt_b), rows_b.shape[1], n_b, _tp(seg_off_b),
+                                                 n_cls, n_col, _tp(status_b), _tp(out_t), _tp(pairs_t), _tp(flags_t), _stream()))
+    return out_t, pairs_t, flags_t
+
+
+def match_rows_dev(out_t, pairs_t, flags_t, own_col, rows_t=None, status_a=None, seg_off_a=None, seg_flags=None, ctx=None):
+    """(n_seg_a, 6) rows [w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean] from the (n_seg_a, n_col) outputs of
+    wasserstein_matrix_dev and own_col (n_seg_a,) int32, the column of every group's own audio or -1.  seg_flags
+    (optional, (n_seg_a,) int32): per group, OR of the row's flags and of status_a over the group (seg_off_a), without
+    TDA_WIN_NO_PAIR / TDA_WIN_DEGENERATE."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_seg_a = own_col.numel()
+    n_col = out_t.numel() // n_seg_a if n_seg_a else 0
+    assert own_col.dtype == torch.int32 and out_t.is_contiguous() and pairs_t.is_contiguous() and flags_t.is_contiguous()
+    assert status_a is None or (seg_off_a is not None and seg_off_a.numel() == n_seg_a + 1)
+    if rows_t is None:
+        rows_t = torch.empty((n_seg_a, MATCH_COLS), dtype=torch.float64, device=own_col.device)
+    assert rows_t.is_contiguous() and rows_t.numel() >= MATCH_COLS * n_seg_a
+    ctx.check(ctx.lib.tda_match_rows_dev(ctx.h, _tp(out_t), _tp(pairs_t), _tp(flags_t), n_seg_a, n_col, _tp(own_col),
+                                         _tp(status_a), _tp(seg_off_a), _tp(rows_t), _tp(seg_flags), _stream()))
+    return rows_t

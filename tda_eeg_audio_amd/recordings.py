@@ -22,6 +22,7 @@ rows are withheld if any status bit is left.  The passes differ in how a shard i
     RaggedRecordingPass       recordings of different lengths, packed back to back (preprocess.pack_recordings)
     RaggedAudioRecordingPass  the same from the raw 44.1 kHz audio instead of the envelopes
     ControlPass               the matched-vs-mismatched control (scripts/matched_vs_mismatched.py)
+    MatchMismatchPass         the same control against the audio of EVERY candidate recording: the whole distance matrix
 The filter banks are designed and packed once per pass (preprocess.SosBank / BaBank) and handed to every shard's step.
 The rows equal pipeline.run_step on the stacked windows of the same band-passed signals bit for bit
 (tests/test_gpu_frontend.py::test_recording_pass_equals_stacked_windows).
@@ -52,7 +53,9 @@ class _ShardedPass:
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
       _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"])
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
-                                    without a window (nothing to verify)."""
+                                    without a window (nothing to verify)
+      _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
+                                    (non_blocking = nb)."""
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
@@ -113,6 +116,7 @@ class _ShardedPass:
                     rows_h[r0:r1].copy_(st["rows"][:r1 - r0], non_blocking=True)
                     if self.correlations:
                         self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0], non_blocking=True)
+                    self._more_back(st, r0, r1, True)
                     st["down"].record(self.back)
                 pend.append(i)
                 if len(pend) >= self.n_sets:        # (the GPU has the later shards to work on while the host looks at this
@@ -124,6 +128,9 @@ class _ShardedPass:
             raise
         self.back.synchronize()
         return rows_h
+
+    def _more_back(self, st, r0, r1, non_blocking):
+        pass
 
     def _verify(self, i, rows_h):
         """Verify, then publish: a shard whose step left a class-overflow flag (run_step copies the flags of its groups
@@ -144,6 +151,7 @@ class _ShardedPass:
                 rows_h[r0:r1].copy_(st["rows"][:r1 - r0])
                 if self.correlations:
                     self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0])
+                self._more_back(st, r0, r1, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
         if bool(fl.any()):
@@ -538,7 +546,7 @@ class ControlPlan(RaggedPlan):
         # RaggedPlan's names are the EEG's: a recording without an EEG window has no row (mvm:73)
         self.n_win, self.picks, self.k = self.n_win_e, self.picks_e, self.k_e
         self.empty = np.flatnonzero(self.k_e == 0)
-        self.U = np.unique(self.partner[self.partner >= 0])
+        self.U = self._bank_members()
         self.bank = self.U[self.k_a[self.U] > 0]
         self.bank_pos = np.full(self.n_rec, -1, np.int64)
         self.bank_pos[self.bank] = np.arange(len(self.bank))
@@ -549,6 +557,10 @@ class ControlPlan(RaggedPlan):
             np.zeros(0, np.int64)
         b1 = np.repeat(self.bank_off[:-1], kb) + pick_off
         self.bank_start = (np.arange(self.nb, dtype=np.int64)[:, None] * self.bank_off[-1] + b1[None, :]).ravel()
+
+    def _bank_members(self):
+        """The recordings whose audio diagrams the bank may hold, in the bank's order."""
+        return np.unique(self.partner[self.partner >= 0])
 
     def _shard_tables(self, r0, r1):
         t = super()._shard_tables(r0, r1)                                # the EEG side: k = k_e, picks = picks_e
@@ -600,15 +612,17 @@ class ControlPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, partner=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2,
                  ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 correlations=False):
+                 correlations=False, plan=None):
         import torch
         from ._lib import MAX_POINTS
         if correlations:
             # its EEG and audio windows are selected apart (mvm:44-49,74-78) and paired by position with two audios:
             # there is no series of (audio, EEG) window pairs in cmp's sense
-            raise ValueError("ControlPass has no temporal correlations (correlations=True): use RaggedRecordingPass")
-        plan = ControlPlan(eeg_lengths, env_lengths, partner, shard_samples, n_ch, len(dict(bands)), fs, window_sec, overlap,
-                           max_windows)
+            raise ValueError(f"{type(self).__name__} has no temporal correlations (correlations=True): use RaggedRecordingPass")
+        # plan: a ControlPlan made by a subclass (MatchMismatchPass)
+        if plan is None:
+            plan = ControlPlan(eeg_lengths, env_lengths, partner, shard_samples, n_ch, len(dict(bands)), fs, window_sec, overlap,
+                               max_windows)
         super().__init__(eeg_lengths, env_lengths, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
                          max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan)
         P, dev, nb = plan, self.dev, len(self.bands)
@@ -721,3 +735,154 @@ class ControlPass(RaggedRecordingPass):
         if int(self.bank_flags_host[0]):
             raise TdaError(f"window status bits {int(self.bank_flags_host[0]):#x} left in the partners' diagrams: rows withheld")
         return rows_h
+
+
+# ------------------------------------------------------------------------------------------------------------
+# match-mismatch: every recording's EEG against the audio of every candidate recording
+# ------------------------------------------------------------------------------------------------------------
+class MatchMismatchPlan(ControlPlan):
+    """The host plan of MatchMismatchPass, numpy only (tests/test_match_mismatch_plan.py checks it without a GPU): a
+    ControlPlan whose bank is the candidate list.  candidates: distinct recording indices whose audio forms the columns
+    of the matrix, in the order given (default: every recording, in order); column c is always candidates[c], and
+    own_col[r] is the position of r in `candidates` or -1.  The window selection is ControlPlan's (EEG windows from the
+    EEG's own count, audio windows from the envelope's own: mvm:44-49, 74-78).  The bank holds the candidates with an
+    audio window (k_a > 0) in the order of the columns, with ControlPlan's bank_off / seg_off_bank / bank_start; a
+    candidate without one keeps its column with an EMPTY group:
+      seg_off_col   (n_bands * n_col + 1) offsets into the bank's windows, band-major over the columns -- the group of
+                    (band b, column c) is b * n_col + c
+    and per shard, beside ControlPlan's tables:
+      cls_e         the band of every EEG group (seg_off_e is band-major over the live recordings)
+      own_col_e     the own column of every EEG group, -1 for a recording that is no candidate."""
+
+    def __init__(self, eeg_lengths, env_lengths=None, candidates=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_ch=47, n_bands=5,
+                 fs=250, window_sec=1.0, overlap=0.75, max_windows=MAX_WINDOWS):
+        n_rec = len(np.asarray(eeg_lengths).ravel())
+        self.candidates = np.arange(n_rec, dtype=np.int64) if candidates is None else np.asarray(candidates, dtype=np.int64).ravel()
+        assert ((self.candidates >= 0) & (self.candidates < n_rec)).all(), "candidates are recording indices"
+        assert len(np.unique(self.candidates)) == len(self.candidates), "a recording is a candidate once"
+        self.n_col = len(self.candidates)
+        self.own_col = np.full(n_rec, -1, np.int64)
+        self.own_col[self.candidates] = np.arange(self.n_col)
+        super().__init__(eeg_lengths, env_lengths, None, shard_samples, n_ch, n_bands, fs, window_sec, overlap, max_windows)
+        self.seg_off_col = np.concatenate([[0], np.cumsum(np.tile(self.k_a[self.candidates], self.nb))]).astype(np.int32)
+
+    def _bank_members(self):
+        return self.candidates
+
+    def _shard_tables(self, r0, r1):
+        t = super()._shard_tables(r0, r1)
+        live = t["live"]
+        t.update(cls_e=np.repeat(np.arange(self.nb), len(live)).astype(np.int32),
+                 own_col_e=np.tile(self.own_col[r0 + live], self.nb).astype(np.int32))
+        return t
+
+
+MATCH_COLS = engine.MATCH_COLS      # [w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean]
+
+
+class MatchMismatchPass(ControlPass):
+    """The control experiment against EVERY candidate audio, as a batched pass FROM HOST MEMORY: ControlPass's inputs and a
+    candidate list go in; per (recording r, band b) the mean H1 Wasserstein distance between the EEG diagrams of r and the
+    audio diagrams of every candidate c, paired by position (mvm:86-95), comes back as dist_h (n_rec, n_bands, n_col)
+    float64 with the pair counts pairs_h (int32), and `run` returns rows_h (n_rec, n_bands, 6) = [w_own, n_own_pairs,
+    n_valid, n_less, n_equal, null_mean] (engine.match_rows_dev): the matched distance (the own column, mvm:136-137), how
+    many of the other candidates with a finite distance lie below / at it (midrank of the true audio: 1 + n_less +
+    n_equal / 2 among n_valid + 1) and their mean.  The reference's mismatched column, any permutation null and the
+    match-mismatch score follow from dist_h without another run (drivers.match_mismatch_summary).
+    Phase 1, once per run, is ControlPass's with the candidates as the bank.  Phase 2, per shard: the shard driver's
+    upload of the EEG and its band-pass bank, the EEG diagrams (ControlPass's EEG stage), ONE
+    engine.wasserstein_matrix_dev launch against the bank and one engine.match_rows_dev launch.  The own audio is a
+    column of the bank, so no envelope is uploaded, filtered or taken through Rips per shard.  A recording without an EEG
+    window gets NaN, zero counts and zero pairs; a candidate without an audio window an all-NaN column with 0 pairs."""
+
+    ROW_COLS = MATCH_COLS
+    ROW_ZERO = slice(1, 5)              # the counts
+
+    def __init__(self, eeg_lengths, env_lengths=None, candidates=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES,
+                 n_sets=2, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
+                 overlap=0.75, correlations=False):
+        import torch
+        plan = MatchMismatchPlan(eeg_lengths, env_lengths, candidates, shard_samples, n_ch, len(dict(bands)), fs, window_sec,
+                                 overlap, max_windows)
+        super().__init__(eeg_lengths, env_lengths, None, device, shard_samples, n_sets, ctx, n_ch, fs, bands, max_windows,
+                         window_sec, overlap, correlations, plan=plan)
+        P, dev, nb = plan, self.dev, len(self.bands)
+        self.candidates, self.own_col, self.n_col = P.candidates, P.own_col, P.n_col
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)           # noqa: E731
+        for d, t in zip(self.shards, P.tables):
+            d.update(cls_e=up(t["cls_e"]), own_col_e=up(t["own_col_e"]))
+        self.col_seg_off = up(P.seg_off_col)
+        S = max((d["n"] for d in self.shards), default=1)
+        n_seg = max((nb * d["n_live"] for d in self.shards), default=0)
+        shape = (max(n_seg, 1), max(self.n_col, 1))
+        for st in self.set:
+            # the per-shard audio stage of ControlPass does not exist here: its buffers go
+            for key in ("env", "ya", "worka", "aw", "caud", "tau_seg", "tau_win", "wm", "wx", "sm", "sx"):
+                st[key] = None
+            st["mat"] = torch.empty(shape, dtype=torch.float64, device=dev)
+            st["mat_pairs"], st["mat_flags"] = (torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(2))
+            st["res"] = torch.empty((max(n_seg, 1), MATCH_COLS), dtype=torch.float64, device=dev)
+            st["dist"] = torch.empty((S, nb, self.n_col), dtype=torch.float64, device=dev)
+            st["pairs"] = torch.empty((S, nb, self.n_col), dtype=torch.int32, device=dev)
+        self.dist_h = self.pairs_h = None
+
+    def _upload(self, st, i, raw_packed_h, env_packed_h):
+        r0, r1 = self.ranges[i]
+        e0, e1 = self.n_ch * int(self.eeg_off[r0]), self.n_ch * int(self.eeg_off[r1])
+        st["raw"][:e1 - e0].copy_(raw_packed_h.view(-1)[e0:e1], non_blocking=True)
+
+    def _shard_step(self, st, i):
+        d = self.shards[i]
+        if d["n_win"] == 0:                                            # no recording of the shard has a window
+            self._rows(st, i, None)
+            return
+        preprocess.bandpass_bank_ragged_dev(st["raw"], d["eeg_tb"], self.eeg_bank, n_ch=self.n_ch, y_t=st["y"],
+                                            work_t=st["work"], ctx=self.ctx)
+        self._rows(st, i, self._rips_step(st, i, "one"))
+
+    def _rips_step(self, st, i, retry):
+        """The EEG's Rips stage of a shard, the matrix against the bank and its rows: (n_bands * n_live, 6)."""
+        import torch
+        ctx, d, v = self.ctx, self.shards[i], st["views"][i]
+        with ctx.deferred(retry):
+            engine.eeg_window_ragged_dev(st["y"], d["eeg_start"], d["eeg_ld"], self.win, out=v.eeg, n_ch=v.eeg.h0_cap, ctx=ctx)
+        engine.diagram_finish_dev([(v.eeg.h1, v.eeg.c1, True, None)], ctx=ctx)
+        torch.cuda.current_stream().wait_event(self.bank_ready)
+        n = v.n_seg * self.n_col
+        mat, mp, mf = (st[k].view(-1)[:n].view(v.n_seg, self.n_col) for k in ("mat", "mat_pairs", "mat_flags"))
+        engine.wasserstein_matrix_dev(v.eeg.h1, v.eeg.c1, v.seg_off, d["cls_e"], self.bank.h1, self.bank.c1, self.col_seg_off,
+                                      self.bank.status, self.n_col, out_t=mat, pairs_t=mp, flags_t=mf, ctx=ctx)
+        res = engine.match_rows_dev(mat, mp, mf, d["own_col_e"], rows_t=st["res"][:v.n_seg], status_a=v.eeg.status,
+                                    seg_off_a=v.seg_off, seg_flags=v.seg_flags, ctx=ctx)
+        if retry != "auto":
+            v.flags_host.copy_(v.seg_flags, non_blocking=True)
+        return res
+
+    def _rows(self, st, i, res):
+        """The rows as ControlPass scatters them, and the matrix of the shard, (n_bands * n_live, n_col) band-major, to
+        the recordings: dist NaN and 0 pairs for a recording without a window."""
+        super()._rows(st, i, res)
+        d, nb = self.shards[i], len(self.bands)
+        dist, pairs = st["dist"][:d["n"]], st["pairs"][:d["n"]]
+        if d["n_live"] < d["n"]:
+            dist.fill_(float("nan"))
+            pairs.zero_()
+        if d["n_live"] and self.n_col:
+            n = nb * d["n_live"] * self.n_col
+            for dst, key in ((dist, "mat"), (pairs, "mat_pairs")):
+                dst.index_copy_(0, d["live"], st[key].view(-1)[:n].view(nb, d["n_live"], self.n_col).transpose(0, 1))
+
+    def _more_back(self, st, r0, r1, non_blocking):
+        self.dist_h[r0:r1].copy_(st["dist"][:r1 - r0], non_blocking=non_blocking)
+        self.pairs_h[r0:r1].copy_(st["pairs"][:r1 - r0], non_blocking=non_blocking)
+
+    def run(self, raw_packed_h, env_packed_h, rows_h=None):
+        """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
+        (n_rec, n_bands, 6), pinned, and fills self.dist_h (n_rec, n_bands, n_col) float64 and self.pairs_h (the same shape,
+        int32), pinned, in list order; all complete when the call returns."""
+        import torch
+        shape = (self.n_rec, len(self.bands), self.n_col)
+        if self.dist_h is None:
+            self.dist_h = torch.empty(shape, dtype=torch.float64).pin_memory()
+            self.pairs_h = torch.empty(shape, dtype=torch.int32).pin_memory()
+        return super().run(raw_packed_h, env_packed_h, rows_h)
