@@ -363,6 +363,16 @@ tda_status tda_set_h1_order(tda_ctx* ctx, int policy);
 #define TDA_SCHEME_GRID  1
 #define TDA_SCHEME_ONE   2
 tda_status tda_set_launch_scheme(tda_ctx* ctx, int scheme);
+/* The Wasserstein entry points leave out work whose result is known before it is done: in a pair of diagrams with one
+ * common birth (two H0 diagrams) the points too short or too long to be matched with any point of the other diagram,
+ * and the whole assignment of a pair in which every point is nearer to the diagonal than to the other diagram.  The
+ * results do not depend on it, bit for bit; on = 0 runs the full computation, so that one process can hold the two
+ * against each other.  Default: on. */
+tda_status tda_set_wasserstein_pruning(tda_ctx* ctx, int on);
+/* dev_counters: NULL (default: nothing is counted) or a device u64[3] that the caller zeroes; every solved pair adds
+ * [0] 1 if it took the all-diagonal short cut, [1] the rows plus columns trimmed off its equal-birth recurrence,
+ * [2] 1.  Both stay 0 while pruning is off. */
+tda_status tda_set_wasserstein_counter(tda_ctx* ctx, unsigned long long* dev_counters);
 
 /* ---- per-recording aggregation -------------------------------------------------
  * replaces the mean/std over windows of process_file_features

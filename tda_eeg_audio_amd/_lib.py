@@ -78,6 +78,8 @@ SYMBOLS = {
     "tda_set_retry_counter": (_I, [c_vp, c_vp]),
     "tda_set_h1_order": (_I, [c_vp, _I]),
     "tda_set_launch_scheme": (_I, [c_vp, _I]),
+    "tda_set_wasserstein_pruning": (_I, [c_vp, _I]),
+    "tda_set_wasserstein_counter": (_I, [c_vp, c_vp]),
     "tda_diagram_finish_dev": (_I, [c_vp, c_vp, _I, _I, c_vp]),
     "tda_tau_batch": (_I, [c_vp, c_vp, _I, _I, _I, c_vp]),
     "tda_features_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp]),
@@ -200,6 +202,14 @@ class Context:
     def set_launch_scheme(self, scheme):
         """How the finishing pass and the Wasserstein launches split their work (include/tdaeeg.h); results do not change."""
         self.check(self.lib.tda_set_launch_scheme(self.h, int(scheme)))
+
+    def set_wasserstein_pruning(self, on=True):
+        """Leave out the Wasserstein work whose result is known in advance (include/tdaeeg.h); results do not change."""
+        self.check(self.lib.tda_set_wasserstein_pruning(self.h, 1 if on else 0))
+
+    def set_wasserstein_counter(self, dev_ptr):
+        """dev_ptr: device address of a zeroed u64[3] (or None): short cuts, rows + columns trimmed, pairs solved."""
+        self.check(self.lib.tda_set_wasserstein_counter(self.h, c_vp(dev_ptr) if dev_ptr else None))
 
     def set_retry_counter(self, dev_ptr):
         """dev_ptr: device address of a zeroed u64[4] (or None): windows redone by the widening passes."""

@@ -83,6 +83,20 @@ tda_status tda_set_launch_scheme(tda_ctx* ctx, int scheme)
     return TDA_OK;
 }
 
+tda_status tda_set_wasserstein_pruning(tda_ctx* ctx, int on)
+{
+    if (!ctx) return TDA_ERR_INVALID;
+    ctx->ws_prune = on ? 1 : 0;
+    return TDA_OK;
+}
+
+tda_status tda_set_wasserstein_counter(tda_ctx* ctx, unsigned long long* dev_counters)
+{
+    if (!ctx) return TDA_ERR_INVALID;
+    ctx->ws_ctr = dev_counters;
+    return TDA_OK;
+}
+
 tda_status tda_diagram_finish_dev(tda_ctx* ctx, const tda_diagram_set* sets, int n_sets, int n_dgm, void* stream)
 {
     if (!ctx) return TDA_ERR_INVALID;

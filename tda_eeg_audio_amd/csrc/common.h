@@ -19,6 +19,8 @@ struct tda_ctx {
     unsigned long long* total_scratch = nullptr;   // class vectors of the last rung of the Rips ladders (rips.hip: TOT_SLOTS x 8.3 MB)
     int h1_order = 0;       // TDA_ORDER_*
     int launch_scheme = 0;  // TDA_SCHEME_*
+    int ws_prune = 1;       // tda_set_wasserstein_pruning
+    unsigned long long* ws_ctr = nullptr;      // tda_set_wasserstein_counter: device u64[3]
     // Lists of the windows a widening pass has to redo (rips.hip: retry_collect): one buffer per STREAM -- the Rips calls
     // of a stream, eager or replayed from a HIP graph captured on it, run one after the other, so a stream's list is never
     // in use twice, while calls on different streams never share one.  TDA_RETRY_SLOTS buffers, allocated with the context

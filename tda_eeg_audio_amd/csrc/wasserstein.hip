@@ -72,6 +72,30 @@ __device__ __forceinline__ double ws_cost(double ab, double ad, double bb, doubl
     return sqrt_rn(d2);                         // (sqrt() bit for bit, six instructions less: common.h)
 }
 
+// What tda_set_wasserstein_pruning / tda_set_wasserstein_counter hand to the kernels.
+struct ws_opts {
+    unsigned long long* ctr;    // NULL, or device u64[3]: short cuts, rows + columns trimmed, pairs solved
+    int prune;
+};
+
+// ---- the margin of the pruning tests ----
+// ws_solve leaves out cells whose gain g = min(0, C - s - t) is known to be 0.  What has to be 0 is the COMPUTED
+// gain, (ws_cost() - s_c) - t_c in floating point; that holds whenever ws_cost() >= s_c + t_c as reals (rounding is
+// monotone and t_c is a float64: fl(C_c - s_c) >= t_c, so the second difference is >= 0).  The tests prove
+// L > s + t + m for a lower bound L on the true distance C; m has to cover what separates that from the computed
+// quantities.  With X = the largest |coordinate| of the pair and u = 2^-53:
+//   d2:  five products and five sums, each with relative error u, of terms that add up to at most
+//        |x|^2 + |y|^2 + 2|x.y| <= 2 (|x|^2 + |y|^2) <= 8 X^2: |d2_c - d2| <= 6u * 8 X^2 = E, and since
+//        sqrt(max(0, L^2 - E)) >= L - sqrt(E), the cancellation costs at most sqrt(48 u) X = 7.3e-8 X;
+//   sqrt_rn, s_c = fma(d, cos, -(b sin)), t_c, and the tests' own few operations: relative errors of a few u on
+//        values <= 3 X, below 1e-14 X together;
+//   underflow: an absolute 2^-1075 per product, 2^-1072 in d2, 2^-536 = 4.4e-162 after the square root.
+// m = 1e-6 X + 1e-150 is more than ten times the sum.  It moves the cut by a millionth of the coordinates' scale.
+// Pairs with X >= 1e150 are not pruned: their squares overflow and ws_cost() clamps NaNs to 0.
+#define WS_PRUNE_REL 1e-6
+#define WS_PRUNE_ABS 1e-150
+#define WS_PRUNE_MAX 1e150
+
 // Where workgroup pr finds its pair: the kernel's compile-time switch (one solver, two prologues).
 // ws_index_pairs: explicit index arrays (NULL = identity), every workgroup has a pair.  Two pointers, laid out as
 // the two kernel arguments they replace.
@@ -129,7 +153,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
                                          const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                                          const SRC& src, int pr, int max_rows, int max_cols,
                                          double* __restrict__ out, int* __restrict__ status, int mode, int* list,
-                                         unsigned char* smem)
+                                         const ws_opts& opt, unsigned char* smem)
 {
     const int lane = lane_id();
     unsigned long long wt0 = WCLK();
@@ -221,6 +245,14 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     __syncthreads();
     WPROF(0, WCLK() - wt0); wt0 = WCLK();
     WPROF(4, 1); WPROF(5, R); WPROF(6, Cn);
+    unsigned long long n_cut = 0, n_trim = 0;           // for opt.ctr
+    auto count = [&]() {
+        if (opt.ctr && lane == 0) {
+            if (n_cut) atomicAdd(&opt.ctr[0], n_cut);
+            if (n_trim) atomicAdd(&opt.ctr[1], n_trim);
+            atomicAdd(&opt.ctr[2], 1ull);
+        }
+    };
 
     // ---- 1-D fast path ------------------------------------------------------------------
     // If every point of both diagrams has the same birth (two H0 diagrams: births 0) the points lie
@@ -242,13 +274,52 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
             ok = ok && !__ballot(j < Cn && (cb[j] != b0 || (j + 1 < Cn && cd[j + 1] < cd[j])));
         }
         if (ok) {
+            // ---- live ranges ----
+            // With p = d - b0 the persistence of a row and q of a column, the true gain of a cell is at least
+            // max(p (1-c) - q (1+c), q (1-c) - p (1+c)), c = 1/sqrt 2 (|p - q| >= either difference): a column is dead
+            // for EVERY row if q (1+c) + m <= p_min (1-c) or q (1-c) >= p_max (1+c) + m, m the margin above.  Both tests
+            // are monotone in q and the deaths are sorted, so the dead columns are a prefix and a suffix, counted by
+            // ballots; then the same for the rows against the live columns.  F is 0 over a dead prefix and constant
+            // over a dead suffix, so the wavefront over the live ranges, zero boundary included, does what the full one
+            // does in every live cell: same operands, same order, same bits.
+            int ilo = 0, jlo = 0, Rl = R, Cl = Cn;
+            const double c1p = 1.0 + WS_CP, c1m = 1.0 - WS_CP;
+            double mx = WS_PRUNE_MAX;
+            if (opt.prune)
+                mx = fmax(fabs(b0), fmax(fmax(fabs(rd[0]), fabs(rd[R - 1])), fmax(fabs(cd[0]), fabs(cd[Cn - 1]))));
+            if (mx < WS_PRUNE_MAX) {
+                const double p_min = rd[0] - b0, p_max = rd[R - 1] - b0;
+                const double m = WS_PRUNE_REL * mx + WS_PRUNE_ABS;
+                const double lo_c = p_min * c1m - m, hi_c = p_max * c1p + m;
+                int n_lo = 0, n_hi = 0;
+                for (int j0 = 0; j0 < Cn; j0 += 64) {
+                    const int j = j0 + lane;
+                    const double q = cd[j < Cn ? j : Cn - 1] - b0;
+                    n_lo += __popcll(__ballot(j < Cn && q * c1p <= lo_c));
+                    n_hi += __popcll(__ballot(j < Cn && q * c1m >= hi_c));
+                }
+                jlo = n_lo;
+                const int jhi = Cn - n_hi > jlo ? Cn - n_hi : jlo;
+                Cl = jhi - jlo;
+                Rl = 0;
+                if (Cl > 0) {
+                    const double q_min = cd[jlo] - b0, q_max = cd[jhi - 1] - b0;
+                    const double lo_r = q_min * c1m - m, hi_r = q_max * c1p + m;
+                    const double p = rd[lane < R ? lane : R - 1] - b0;
+                    ilo = __popcll(__ballot(lane < R && p * c1p <= lo_r));
+                    const int ihi = R - __popcll(__ballot(lane < R && p * c1m >= hi_r));
+                    Rl = ihi > ilo ? ihi - ilo : 0;
+                }
+                n_trim = (unsigned long long)((R - Rl) + (Cn - Cl));
+            }
+            WPROF(8, 1); WPROF(9, Rl); WPROF(10, Cl);
             double cur = 0.0, nb1 = 0.0, nb2 = 0.0;      // own F, neighbour row's F one / two steps ago
-            const int nsteps1d = R + Cn - 1;
+            const int nsteps1d = (Rl > 0 && Cl > 0) ? Rl + Cl - 1 : 0;      // an empty live range: no wavefront, fbest = 0
             // gains on the fly: the row's part of sklearn's expansion is a per-lane constant, the column's |y|^2 is
             // tabulated once -- the same operations in the same order as ws_cost(), 40 instead of 58 instructions per cell
             for (int j = lane; j < Cn; j += 64) G[j] = cb[j] * cb[j] + cd[j] * cd[j];
             __syncthreads();
-            const int li = lane < R ? lane : 0;
+            const int li = lane < Rl ? ilo + lane : 0;                      // lane = live row index
             const double r_b = rb[li], r_d = rd[li], r_s = rs[li], r_n = r_b * r_b + r_d * r_d;
             // every birth equals b0: r_b * c_b is one constant; which diagram comes first in the sums is uniform per pair,
             // so the wavefront exists twice instead of selecting per cell (34 -> 29 instructions per cell)
@@ -262,14 +333,14 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
                     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(cur), 0x138, 0xF, 0xF, false);
                     nb2 = nb1;
                     nb1 = __hiloint2double(hi, lo);
-                    if (lane < R && j0 >= 0 && j0 < Cn) {
-                        const double c_d = cd[j0], c_n = G[j0];
+                    if (lane < Rl && j0 >= 0 && j0 < Cl) {
+                        const double c_d = cd[jlo + j0], c_n = G[jlo + j0];
                         const double dot = fma(r_d, c_d, bb);                   // = fma(ad, bd, ab * bb) either way round
                         double d2 = -2.0 * dot;
                         d2 += A_ROW ? r_n : c_n;                                // |x|^2 of the FIRST diagram's point, then the second's
                         d2 += A_ROW ? c_n : r_n;
                         if (!(d2 > 0.0)) d2 = 0.0;
-                        double g = sqrt_rn(d2) - r_s - ct[j0];
+                        double g = sqrt_rn(d2) - r_s - ct[jlo + j0];
                         g = g < 0.0 ? g : 0.0;
                         const double up = nb1;                          // F[row][j0+1] of the row above
                         const double dg = (j0 == 0 ? 0.0 : nb2) + g;    // F[row above][j0] + g
@@ -280,15 +351,65 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
                 }
             };
             if (a_is_row) wavefront(std::true_type{}); else wavefront(std::false_type{});
-            const double fbest = uni_f64(cur, R - 1);
+            const double fbest = nsteps1d ? uni_f64(cur, Rl - 1) : 0.0;
             double part = 0.0;
             for (int i = lane; i < R; i += 64) part += rs[i];
             for (int j = lane; j < Cn; j += 64) part += ct[j];
             const double total1d = wave_sum_f64(part) + fbest;
             if (lane == 0) { out[pr] = total1d; status[pr] = 0; }
+            count();
             return;
         }
     }
+
+    // ---- every cell dead? ---------------------------------------------------------------
+    // If every point is nearer to the diagonal than to any point of the other diagram (by the margin above), every
+    // gain clamps to 0: the row reduction finds u = 0, nothing is augmented, and the final summation adds every s and
+    // every t in its usual order.  Then that summation alone gives the same bits.  The test: the distance between the
+    // two bounding boxes against s_max + t_max (one compare), else each row's distance to the box of the columns
+    // against s_i + t_max.  A pair with a live cell runs the solver unchanged: compacting a partly live problem could
+    // break ties differently.
+    bool all_dead = false;
+    if (opt.prune) {
+        const double INFP = __longlong_as_double(0x7ff0000000000000ll);
+        double rb_lo = INFP, rb_hi = -INFP, rd_lo = INFP, rd_hi = -INFP, s_hi = -INFP;
+        double cb_lo = INFP, cb_hi = -INFP, cd_lo = INFP, cd_hi = -INFP, t_hi = -INFP;
+        for (int i = lane; i < R; i += 64) {
+            rb_lo = fmin(rb_lo, rb[i]); rb_hi = fmax(rb_hi, rb[i]);
+            rd_lo = fmin(rd_lo, rd[i]); rd_hi = fmax(rd_hi, rd[i]);
+            s_hi = fmax(s_hi, rs[i]);
+        }
+        for (int j = lane; j < Cn; j += 64) {
+            cb_lo = fmin(cb_lo, cb[j]); cb_hi = fmax(cb_hi, cb[j]);
+            cd_lo = fmin(cd_lo, cd[j]); cd_hi = fmax(cd_hi, cd[j]);
+            t_hi = fmax(t_hi, ct[j]);
+        }
+        rb_lo = wave_min_f64_dpp(rb_lo); rb_hi = wave_max_f64_dpp(rb_hi);
+        rd_lo = wave_min_f64_dpp(rd_lo); rd_hi = wave_max_f64_dpp(rd_hi);
+        cb_lo = wave_min_f64_dpp(cb_lo); cb_hi = wave_max_f64_dpp(cb_hi);
+        cd_lo = wave_min_f64_dpp(cd_lo); cd_hi = wave_max_f64_dpp(cd_hi);
+        s_hi = wave_max_f64_dpp(s_hi); t_hi = wave_max_f64_dpp(t_hi);
+        const double mx = fmax(fmax(fmax(fabs(rb_lo), fabs(rb_hi)), fmax(fabs(rd_lo), fabs(rd_hi))),
+                               fmax(fmax(fabs(cb_lo), fabs(cb_hi)), fmax(fabs(cd_lo), fabs(cd_hi))));
+        if (mx < WS_PRUNE_MAX) {
+            const double m = WS_PRUNE_REL * mx + WS_PRUNE_ABS;
+            const double gx = fmax(0.0, fmax(cb_lo - rb_hi, rb_lo - cb_hi));
+            const double gy = fmax(0.0, fmax(cd_lo - rd_hi, rd_lo - cd_hi));
+            all_dead = sqrt_rn(gx * gx + gy * gy) > s_hi + t_hi + m;
+            if (!all_dead) {
+                bool live = false;
+                for (int i0 = 0; i0 < R; i0 += 64) {
+                    const int i = i0 + lane < R ? i0 + lane : R - 1;
+                    const double dx = fmax(0.0, fmax(cb_lo - rb[i], rb[i] - cb_hi));
+                    const double dy = fmax(0.0, fmax(cd_lo - rd[i], rd[i] - cd_hi));
+                    live = live || __ballot(!(sqrt_rn(dx * dx + dy * dy) > rs[i] + t_hi + m)) != 0ull;
+                }
+                all_dead = !live;
+            }
+        }
+        if (all_dead) n_cut = 1;
+    }
+    WPROF(7, all_dead ? 1 : 0);
 
     // per-lane state, all in registers: column j = lane + 64*c holds v, minv, way, used, prow;
     // row i = lane + 64*c holds its dual u and the "row is in the alternating tree" flag.
@@ -306,7 +427,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     // ---- row-reduction start: u_i = min_j g_ij, v = 0 is dual feasible; every row whose arg-min
     // column is not claimed by a lower row is assigned at once (tight pair), the rest augment ----
     bool rowdone[CW];
-    {
+    if (!all_dead) {
         int myarg[CW];
         for (int j = lane; j < Cn; j += 64) owner[j] = 0x7fffffff;
         __syncthreads();
@@ -337,7 +458,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
             if (c < cw_used && j < Cn) { const int o = owner[j]; prow[c] = (o != 0x7fffffff) ? o : -1; }
         }
     }
-    for (int i = 0; i < R && !failed; ++i) {
+    for (int i = 0; i < R && !failed && !all_dead; ++i) {
         {
             int dn = 0;
 #pragma unroll
@@ -440,6 +561,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     }
     if (failed) {
         if (lane == 0) { out[pr] = __longlong_as_double(0x7ff8000000000000ll); status[pr] = TDA_WIN_NOT_CONVERGED; }
+        count();
         return;
     }
     WPROF(1, WCLK() - wt0); wt0 = WCLK();
@@ -467,6 +589,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
         if (ru[i] == 0.0) part += rs[i];
     const double total = wave_sum_f64(part);
     if (lane == 0) { out[pr] = total; status[pr] = 0; }
+    count();
     WPROF(2, WCLK() - wt0);
 }
 
@@ -476,7 +599,7 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
                    const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                    const SRC src, int n_pairs,
                    int max_rows, int max_cols,
-                   double* __restrict__ out, int* __restrict__ status, int mode, int* list)
+                   double* __restrict__ out, int* __restrict__ status, int mode, int* list, const ws_opts opt)
 {
     // mode 1: the SMALL first launch (LDS for 64 x 64 points whatever the capacities of the diagram buffers: four times
     // the workgroups per CU of a launch sized by a capacity of 256) leaves pairs that do not fit marked WS_DEFERRED and,
@@ -487,7 +610,7 @@ wasserstein_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt
     const int pr = blockIdx.x;
     if (pr >= n_pairs) return;
     if (mode == 2 && status[pr] != WS_DEFERRED) return;
-    ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, mode, list, smem);
+    ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, mode, list, opt, smem);
 }
 
 // The pairs on the list of the small launch, on a grid that does not depend on the batch: workgroup b takes entries b,
@@ -499,7 +622,7 @@ wasserstein_list_kernel(const double* __restrict__ dgm_a, const int* __restrict_
                         const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                         const SRC src, int n_pairs,
                         int max_rows, int max_cols,
-                        double* __restrict__ out, int* __restrict__ status, int* list)
+                        double* __restrict__ out, int* __restrict__ status, int* list, const ws_opts opt)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int nl = uni(list[0]);
@@ -507,7 +630,7 @@ wasserstein_list_kernel(const double* __restrict__ dgm_a, const int* __restrict_
     for (int j = blockIdx.x; j < nl; j += gridDim.x) {
         const int pr = uni(list[4 + j]);
         if (pr >= 0 && pr < n_pairs)
-            ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, 0, nullptr, smem);
+            ws_solve<CW, SRC>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, pr, max_rows, max_cols, out, status, 0, nullptr, opt, smem);
         __syncthreads();
     }
     if (threadIdx.x == 0 && atomicAdd(&list[1], 1) == (int)gridDim.x - 1) { list[0] = 0; list[1] = 0; }
@@ -524,6 +647,7 @@ static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, cons
     if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
     const int lo = cap_a < cap_b ? cap_a : cap_b, hi = cap_a < cap_b ? cap_b : cap_a;
     const int max_rows = lo, max_cols = hi;
+    const ws_opts opt{ctx->ws_ctr, ctx->ws_prune};
     if (max_cols > 512) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "diagrams with more than 512 rows are not supported");
     // No cost matrix in LDS: gains are evaluated where they are needed.  A per-pair matrix (16 KB for a 45 x 45 H1
     // pair) left room for 5-7 one-wave workgroups per CU; without it the H0 pairs of a pass take 1.7 instead of 2.9 ms
@@ -546,7 +670,7 @@ static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, cons
         const int sr = max_rows < 64 ? max_rows : 64;
         const size_t lds_s = (size_t)(4 * sr + 4 * 64 + 32) * 8;
         hipLaunchKernelGGL((wasserstein_kernel<1, SRC>), dim3(n_pairs), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
-                           cap_b, src, n_pairs, sr, 64, out, status, 1, list);
+                           cap_b, src, n_pairs, sr, 64, out, status, 1, list, opt);
     }
 #define WS_LAUNCH(CWV)                                                                                         \
     do {                                                                                                       \
@@ -558,10 +682,10 @@ static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, cons
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
         if (list)                                                                                              \
             hipLaunchKernelGGL(lkern, dim3(n_pairs < 256 ? n_pairs : 256), dim3(64), lds, st, dgm_a, cnt_a,    \
-                               cap_a, dgm_b, cnt_b, cap_b, src, n_pairs, max_rows, max_cols, out, status, list); \
+                               cap_a, dgm_b, cnt_b, cap_b, src, n_pairs, max_rows, max_cols, out, status, list, opt); \
         else                                                                                                   \
             hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,      \
-                               cap_b, src, n_pairs, max_rows, max_cols, out, status, mode, (int*)nullptr);     \
+                               cap_b, src, n_pairs, max_rows, max_cols, out, status, mode, (int*)nullptr, opt); \
     } while (0)
     if (max_cols <= 128) WS_LAUNCH(2);
     else if (max_cols <= 256) WS_LAUNCH(4);
@@ -638,7 +762,8 @@ template <int CW>
 __device__ __forceinline__ void ws_matrix_entry(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                                                 const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                                                 const ws_matrix_args& M, size_t e, int e_rel, int max_rows, int max_cols,
-                                                int solver_bytes, int mode, int* list, unsigned char* smem)
+                                                int solver_bytes, int mode, int* list, const ws_opts& opt,
+                                                unsigned char* smem)
 {
     const int lane = lane_id();
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
@@ -664,7 +789,7 @@ __device__ __forceinline__ void ws_matrix_entry(const double* __restrict__ dgm_a
     if (lane >= n_try && lane < len) { xs[lane] = qnan; ss[lane] = TDA_WIN_NO_PAIR; }      // positions past the B group
     bool deferred = false;
     for (int i = 0; i < n_try && !deferred; ++i) {
-        ws_solve<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, i, max_rows, max_cols, xs, ss, mode ? 1 : 0, nullptr, smem);
+        ws_solve<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, i, max_rows, max_cols, xs, ss, mode ? 1 : 0, nullptr, opt, smem);
         __syncthreads();
         deferred = mode && uni(ss[i]) == WS_DEFERRED;
     }
@@ -698,14 +823,14 @@ __global__ void __launch_bounds__(64)
 wasserstein_matrix_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                           const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                           const ws_matrix_args M, size_t e0, int n_e, int max_rows, int max_cols, int solver_bytes, int mode,
-                          int* list)
+                          int* list, const ws_opts opt)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((int)blockIdx.x >= n_e) return;
     const size_t e = e0 + blockIdx.x;
     if (mode == 2 && M.flags[e] != WS_DEFERRED) return;
     ws_matrix_entry<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e, (int)blockIdx.x, max_rows, max_cols, solver_bytes,
-                        mode == 1, list, smem);
+                        mode == 1, list, opt, smem);
 }
 
 // the entries on the list of the small launch (the layout and the clearing of wasserstein_list_kernel's)
@@ -714,7 +839,7 @@ __global__ void __launch_bounds__(64)
 wasserstein_matrix_list_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                                const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                                const ws_matrix_args M, size_t e0, int n_e, int max_rows, int max_cols, int solver_bytes,
-                               int* list)
+                               int* list, const ws_opts opt)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int nl = uni(list[0]);
@@ -723,7 +848,7 @@ wasserstein_matrix_list_kernel(const double* __restrict__ dgm_a, const int* __re
         const int r = uni(list[4 + j]);
         if (r >= 0 && r < n_e)
             ws_matrix_entry<CW>(dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0 + (size_t)r, r, max_rows, max_cols, solver_bytes, 0,
-                                nullptr, smem);
+                                nullptr, opt, smem);
         __syncthreads();
     }
     if (threadIdx.x == 0 && atomicAdd(&list[1], 1) == (int)gridDim.x - 1) { list[0] = 0; list[1] = 0; }
@@ -746,6 +871,7 @@ tda_status launch_wasserstein_matrix(tda_ctx* ctx, const double* dgm_a, const in
     const int max_rows = lo, max_cols = hi;
     if (max_cols > 512) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "diagrams with more than 512 rows are not supported");
     const ws_matrix_args M{seg_off_a, cls_a, seg_off_b, status_b, n_a, n_b, n_cls, n_col, out, pairs, flags};
+    const ws_opts opt{ctx->ws_ctr, ctx->ws_prune};
     // the solver's layouts (launch_wasserstein_src), each followed by the result slots of the entry
     const size_t lds_res = (size_t)WS_MATRIX_MAX_GROUP * 12;
     const int lds_solver = (4 * max_rows + 4 * max_cols + ((max_cols + 1) >> 1)) * 8;
@@ -768,7 +894,7 @@ tda_status launch_wasserstein_matrix(tda_ctx* ctx, const double* dgm_a, const in
         const int n_e = (int)(n_ent - e0 < chunk ? n_ent - e0 : chunk);
         if (mode)
             hipLaunchKernelGGL(wasserstein_matrix_kernel<1>, dim3(n_e), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
-                               cap_b, M, e0, n_e, sr, 64, lds_solver_s, 1, list);
+                               cap_b, M, e0, n_e, sr, 64, lds_solver_s, 1, list, opt);
 #define WS_MATRIX_LAUNCH(CWV)                                                                                  \
     do {                                                                                                       \
         auto kern = wasserstein_matrix_kernel<CWV>;                                                            \
@@ -779,10 +905,10 @@ tda_status launch_wasserstein_matrix(tda_ctx* ctx, const double* dgm_a, const in
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));         \
         if (list)                                                                                              \
             hipLaunchKernelGGL(lkern, dim3(n_e < WS_MATRIX_LIST_GRID ? n_e : WS_MATRIX_LIST_GRID), dim3(64), lds_w, st,  \
-                               dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e, max_rows, max_cols, lds_solver, list); \
+                               dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e, max_rows, max_cols, lds_solver, list, opt); \
         else                                                                                                   \
             hipLaunchKernelGGL(kern, dim3(n_e), dim3(64), lds_w, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, \
-                               M, e0, n_e, max_rows, max_cols, lds_solver, mode, (int*)nullptr);               \
+                               M, e0, n_e, max_rows, max_cols, lds_solver, mode, (int*)nullptr, opt);          \
     } while (0)
         if (max_cols <= 128) WS_MATRIX_LAUNCH(2);
         else if (max_cols <= 256) WS_MATRIX_LAUNCH(4);

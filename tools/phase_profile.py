@@ -41,7 +41,14 @@ aw = synth.audio_windows(256, "beta", seed=4)
 dist = engine.corr_dist_batch(W, want_corr=False, ctx=ctx)
 e0, ec0, e1, ec1, est = engine.rips_dm_batch(dist, ctx=ctx, raw=True)
 a0, ac0, a1, ac1, npts, ast = engine.takens_rips_batch(aw, 3, ctx=ctx, raw=True)
-for name, (x, cx, y, cy) in {"H0": (e0, ec0, a0, ac0), "H1": (e1, ec1, a1, ac1)}.items():
+pairs = {"H0 beta": (e0, ec0, a0, ac0), "H1 beta": (e1, ec1, a1, ac1)}
+for band in ("delta", "theta", "alpha", "gamma"):                 # trimmed sizes and short cuts per band
+    awb = synth.audio_windows(256, band, seed=4)
+    taub = int(engine.tau_batch(awb[:1], 125, ctx=ctx)[0])
+    b0_, bc0, b1_, bc1, _, _ = engine.takens_rips_batch(awb, taub, ctx=ctx, raw=True)
+    pairs["H0 " + band] = (e0, ec0, b0_, bc0)
+    pairs["H1 " + band] = (e1, ec1, b1_, bc1)
+for name, (x, cx, y, cy) in pairs.items():
     engine.wasserstein_batch(x, cx, y, cy, ctx=ctx)
     lib.tda_profile_read_ws(buf, 1)
     engine.wasserstein_batch(x, cx, y, cy, ctx=ctx)
@@ -49,3 +56,8 @@ for name, (x, cx, y, cy) in {"H0": (e0, ec0, a0, ac0), "H1": (e1, ec1, a1, ac1)}
     v = np.array(list(buf), dtype=np.float64); n = v[4]
     print(f"wasserstein {name}: pairs={int(n)} rows={v[5]/n:.1f} cols={v[6]/n:.1f} cycles/pair: setup={v[0]/n:.0f} "
           f"solve={v[1]/n:.0f} total={v[2]/n:.0f}; dijkstra steps/pair={v[3]/n:.1f} -> {v[1]/max(v[3],1):.0f} cycles/step")
+    if v[8]:
+        print(f"     pruning: 1-D pairs={int(v[8])} live rows={v[9]/v[8]:.1f} live cols={v[10]/v[8]:.1f} (wavefront steps "
+              f"{(v[9]+v[10])/v[8]-1:.1f} of {(v[5]+v[6])/n-1:.1f})")
+    if n - v[8]:
+        print(f"     pruning: all-diagonal short cuts={int(v[7])} of {int(n-v[8])} general pairs")
