@@ -1766,6 +1766,10 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
 #define TOT_NW 128                    // u64 words per class vector
 #define TOT_SLOTS 8                   // windows in flight = workgroups of the launch (8.3 MB of scratch each)
 #define TOT_SLOT_WORDS ((size_t)8128 * TOT_NW)
+// grids of the widening passes: what fits the chip at once (two workgroups per CU); the widest variants need a nearly
+// empty CU per workgroup and ask for few.  A workgroup takes entries b, b + grid, ... of the list of flagged windows
+#define RETRY_GRID 512
+#define RETRY_GRID_WIDE 64
 
 template <int NT, class KEYFN>
 __device__ __forceinline__ void rips_sweep_total(int n, int E, int Ev, const u16* rank, const u16* ord, float* bkey, unsigned char* misc,
@@ -2443,7 +2447,8 @@ __device__ __forceinline__ void eeg_one_window(unsigned char* smem, const SRC& s
 // AGPRs and mis-places the wait in front of the first v_accvgpr_read of one path (a proven compiler fault: see the
 // note in corr_dist_dev.h; the sweep and its LDS hand-overs are not involved -- the distance matrix itself comes out
 // wrong).  Every variant of this kernel stays at >= 2 waves per SIMD (no AGPRs: checked by a CPU test on the code
-// object) and tests/test_gpu_parity.py::test_fused_eeg_window_512_classes covers the widest one.
+// object); tests/test_gpu_parity.py::test_fused_eeg_window_512_classes covers the widest one on windows that need it, and
+// tests/test_gpu_retry_trips.py every RETRY variant with three windows per workgroup.
 #ifndef TDA_EEG_WIDE_WAVES
 #define TDA_EEG_WIDE_WAVES 2     // (tools/probes/wide_waves_repro.py builds with 1 to reproduce the fault)
 #endif
@@ -2612,7 +2617,7 @@ static tda_status launch_dm_t(tda_ctx* ctx, const double* dm, int n_win, int n, 
                                          hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
     // retry passes work off the list of flagged windows on a grid that fits the chip; the widest variant (240 VGPRs, > 80 KB LDS)
     // needs a nearly empty CU per workgroup, so it asks for few of them
-    const int rgrid = W >= 8 ? 64 : 512;
+    const int rgrid = W >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;
     const int grid = retry_only ? (n_win < rgrid ? n_win : rgrid) : n_win;
     if (retry_only) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
     {
@@ -2716,7 +2721,7 @@ static tda_status launch_eeg_t(tda_ctx* ctx, const SRC& win, int n_win, int n_ch
     if (L.total > 48 * 1024)
         TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    const int rgrid = W >= 8 ? 64 : 512;
+    const int rgrid = W >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;
     const int grid = RETRY ? (n_win < rgrid ? n_win : rgrid) : n_win;
     if (RETRY) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
     {
@@ -2826,7 +2831,7 @@ static tda_status launch_cloud_t(tda_ctx* ctx, const double* src, const int* aux
     if (L.total > 48 * 1024)
         TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    const int rgrid = W >= 2 ? 256 : 512;              // (what fits the chip at once: two / one workgroup per CU)
+    const int rgrid = W >= 2 ? RETRY_GRID / 2 : RETRY_GRID;      // (what fits the chip at once: one / two workgroups per CU)
     const int grid = retry_only ? (n_win < rgrid ? n_win : rgrid) : n_win;
     if (retry_only) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
     {
