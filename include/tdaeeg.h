@@ -456,6 +456,27 @@ tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* c
                                  const int* idx_a, const int* idx_b, int n_pairs,
                                  double* out, int* status);
 
+/* ---- Bottleneck distance between diagrams ---------------------------------------
+ * The largest matched cost under the best matching (the definition of Hera, GUDHI and persim.bottleneck).  The
+ * diagrams are cleaned as for the Wasserstein distance: rows with a non-finite entry are ignored and an empty diagram
+ * becomes {(0,0)} (utils.py:182-187).  Ground cost between points: L-infinity,
+ *     C_ij = fmax(fabs(a_b - b_b), fabs(a_d - b_d));
+ * a point may go to the diagonal at cost 0.5 * (d - b); diagonal to diagonal is free.  The result is the minimum over
+ * matchings of the largest matched cost.  Every cost is one correctly rounded float64 operation on the inputs and the
+ * result is one of them, chosen by comparisons only: it equals a CPU evaluation of this definition bit for bit.
+ * d >= b is assumed for every finite row (Rips never emits another one).
+ * Arguments as tda_wasserstein_batch[_dev].  out: (n_pairs) float64, NaN where status != 0; status: (n_pairs) int32.
+ * A pair with a diagram of more than 512 finite rows is TDA_WIN_NOT_CONVERGED (the buffers may be larger than that), as
+ * is a pair whose solver hit one of its loop bounds.  The _dev form only enqueues on `stream` and allocates nothing. */
+tda_status tda_bottleneck_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
+                                    const double* dgm_b, const int* cnt_b, int cap_b,
+                                    const int* idx_a, const int* idx_b, int n_pairs,
+                                    double* out, int* status, void* stream);
+tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                const int* idx_a, const int* idx_b, int n_pairs,
+                                double* out, int* status);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

@@ -231,6 +231,8 @@ tda_status launch_temporal_corr(tda_ctx*, const double*, const double*, int, con
                                 double*, hipStream_t);
 tda_status launch_wasserstein(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
                               const int*, int, double*, int*, hipStream_t);
+tda_status launch_bottleneck(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
+                             const int*, int, double*, int*, hipStream_t);
 tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, int, const int*, const int*, int, const double*,
                                     const int*, int, int, const int*, int, const int*, const int*, double*, int*, hipStream_t);
 tda_status launch_cross_rows(tda_ctx*, const double*, const int*, const double*, const int*, const int*, int, double*,

@@ -5,7 +5,8 @@ Every function here is a thin marshalling layer over one C-ABI entry point of
 include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU path.
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
-                 tau_batch, features_batch, aggregate_batch, wasserstein_batch, temporal_corr_batch
+                 tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch,
+                 temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -252,6 +253,26 @@ def wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=
     out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
     ctx.check(ctx.lib.tda_wasserstein_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
                                             ptr(ia), ptr(ib), n_pairs, ptr(out), ptr(st)))
+    return (out, st) if want_status else out
+
+
+def bottleneck_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=None, want_status=False):
+    """Bottleneck distance of diagram pairs (include/tdaeeg.h: L-infinity ground cost, (d - b) / 2 to the diagonal, the
+    largest matched cost under the best matching); arguments and results as wasserstein_batch."""
+    ctx = ctx or get_ctx()
+    ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
+    n_a, cap_a, _ = ra.shape
+    n_b, cap_b, _ = rb.shape
+    if idx_a is None and idx_b is None:
+        assert n_a == n_b
+        n_pairs = n_a
+    else:
+        n_pairs = len(idx_a if idx_a is not None else idx_b)
+    ia = None if idx_a is None else i32(idx_a)
+    ib = None if idx_b is None else i32(idx_b)
+    out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
+    ctx.check(ctx.lib.tda_bottleneck_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
+                                           ptr(ia), ptr(ib), n_pairs, ptr(out), ptr(st)))
     return (out, st) if want_status else out
 
 
@@ -530,6 +551,22 @@ def wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=
     ctx.check(ctx.lib.tda_wasserstein_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
                                                 _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
                                                 _tp(out_t), _tp(status_t), _stream()))
+    return out_t, status_t
+
+
+def bottleneck_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+    """bottleneck_batch on device tensors: one launch on torch's current stream, nothing allocated when out_t and
+    status_t are given.  out_t is NaN where status_t != 0."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
+    if out_t is None:
+        out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
+    if status_t is None:
+        status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
+    ctx.check(ctx.lib.tda_bottleneck_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
+                                               _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
+                                               _tp(out_t), _tp(status_t), _stream()))
     return out_t, status_t
 
 

@@ -17,13 +17,18 @@ from . import engine
 
 RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG features per recording-band
 CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
+BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
 
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
-    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False):
-        """correlations=True: run_step also fills `corr` (n_seg, 10): Spearman [r, p] of the five feature series of
+    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False):
+        """bottleneck=True: run_step also fills `b0` / `b1` (n_win), the bottleneck distances of the H0 / H1 diagram pairs
+        of every window (engine.bottleneck_dev; status words `bs0` / `bs1`), and `bott` (n_seg, 2): per group their
+        np.nanmean over the windows the Wasserstein means of `result` run over -- a window whose audio cloud is
+        degenerate (cmp:90-91) or whose pair has a solver status counts as NaN.  `result` is the same either way.
+        correlations=True: run_step also fills `corr` (n_seg, 10): Spearman [r, p] of the five feature series of
         engine.SPEARMAN_COLS, audio H1 against EEG H1, per group (cmp:104-114; engine.temporal_corr_dev).  `result` is
         the same either way."""
         import torch
@@ -50,6 +55,13 @@ class Workspace:
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
         self.corr = torch.empty((self.n_seg, CORR_COLS), **f64) if correlations else None
         self.corr_cols = torch.tensor(engine.SPEARMAN_COLS, dtype=torch.int32, device=device) if correlations else None
+        self.bottleneck = bool(bottleneck)
+        self.b0 = self.b1 = self.bs0 = self.bs1 = self.bott = None
+        if self.bottleneck:
+            self.b0 = torch.empty(n_win, **f64); self.b1 = torch.empty(n_win, **f64)
+            self.bs0 = torch.empty(n_win, dtype=torch.int32, device=device)
+            self.bs1 = torch.empty(n_win, dtype=torch.int32, device=device)
+            self.bott = torch.empty((self.n_seg, BOTT_COLS), **f64)
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -86,6 +98,10 @@ class Workspace:
             setattr(v, name, getattr(self, name)[:n_seg])
         v.dist = None if self.dist is None else self.dist[:n_win]
         v.corr = None if self.corr is None else self.corr[:n_seg]
+        if self.bottleneck:
+            for name in ("b0", "b1", "bs0", "bs1"):
+                setattr(v, name, getattr(self, name)[:n_win])
+            v.bott = self.bott[:n_seg]
         return v
 
 
@@ -112,6 +128,7 @@ def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="
 
 def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=None, eeg_table=None):
     import torch
+    from . import _lib
 
     def stage(name, fn):
         if timers is None or name not in timers:
@@ -162,6 +179,17 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
                                                            out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
     stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
                                                            out_t=ws.w1, status_t=ws.ws1, ctx=ctx))
+    if getattr(ws, "bottleneck", False):
+        stage("bottleneck_h0", lambda: engine.bottleneck_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
+                                                             out_t=ws.b0, status_t=ws.bs0, ctx=ctx))
+        stage("bottleneck_h1", lambda: engine.bottleneck_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
+                                                             out_t=ws.b1, status_t=ws.bs1, ctx=ctx))
+        # the means of recording_rows_dev's windows: masked on the device, then one nanmean launch per leg
+        out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
+        for col, (b, bs) in enumerate(((ws.b0, ws.bs0), (ws.b1, ws.bs1))):
+            seg_mean = engine.segment_nanmean_dev(torch.where(out | (bs != 0), nan, b), ws.seg_off, ctx=ctx)
+            ws.bott[:, col].copy_(seg_mean)
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -444,4 +472,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
-# (a Workspace(correlations=True) has one more, "temporal_corr", after "finish")
+# (a Workspace(correlations=True) has one more, "temporal_corr", after "finish"; a Workspace(bottleneck=True) two,
+# "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1")

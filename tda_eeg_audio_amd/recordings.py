@@ -30,6 +30,9 @@ With correlations=True the passes also return the third result of the script per
 the five H1 feature series, audio against EEG (cmp:104-114), computed on the device from the step's own feature matrices
 (engine.temporal_corr_dev) and downloaded beside the rows as corr_h (n_rec, 5, 10); drivers.comparison_rows /
 comparison_summary turn rows and corr_h into the script's table and statistics.
+With bottleneck=True RecordingPass and the ragged passes also return bott_h (n_rec, 5, 2): per (recording, band) the means
+of the bottleneck distances of the H0 and of the H1 diagram pairs (pipeline.Workspace(bottleneck=True)), over the
+windows the Wasserstein means of the rows run over.
 """
 import numpy as np
 
@@ -51,7 +54,7 @@ class _ShardedPass:
       _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
       _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
-      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"])
+      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"])
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
                                     without a window (nothing to verify)
       _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
@@ -59,11 +62,12 @@ class _ShardedPass:
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
-    def __init__(self, device, ctx, fs, bands, correlations):
+    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False):
         self.ctx = ctx or get_ctx()
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
         self.correlations, self.corr_h = bool(correlations), None
+        self.bottleneck, self.bott_h = bool(bottleneck), None
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -89,7 +93,7 @@ class _ShardedPass:
 
     def run(self, raw_h, second_h, rows_h=None):
         """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
-        call returns (and self.corr_h with correlations=True)."""
+        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True)."""
         import torch
         self.ranges = self._begin(raw_h, second_h)
         n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
@@ -97,6 +101,8 @@ class _ShardedPass:
             rows_h = torch.empty((n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
         if self.correlations and (self.corr_h is None or self.corr_h.shape[0] != n_rec):
             self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
+        if self.bottleneck and (self.bott_h is None or self.bott_h.shape[0] != n_rec):
+            self.bott_h = torch.empty((n_rec, nb, pipeline.BOTT_COLS), dtype=torch.float64).pin_memory()
         pend = []
         try:
             for i, (r0, r1) in enumerate(self.ranges):
@@ -116,6 +122,8 @@ class _ShardedPass:
                     rows_h[r0:r1].copy_(st["rows"][:r1 - r0], non_blocking=True)
                     if self.correlations:
                         self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0], non_blocking=True)
+                    if self.bottleneck:
+                        self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0], non_blocking=True)
                     self._more_back(st, r0, r1, True)
                     st["down"].record(self.back)
                 pend.append(i)
@@ -151,6 +159,8 @@ class _ShardedPass:
                 rows_h[r0:r1].copy_(st["rows"][:r1 - r0])
                 if self.correlations:
                     self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0])
+                if self.bottleneck:
+                    self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0])
                 self._more_back(st, r0, r1, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
@@ -164,13 +174,14 @@ class RecordingPass(_ShardedPass):
     their flags say nothing new)."""
 
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
-                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False):
+                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
         feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
-        drivers.DETAILED_COLUMNS[8:].  The rows are the same either way."""
+        drivers.DETAILED_COLUMNS[8:].  bottleneck=True: `run` also fills self.bott_h, pinned (n_rec, n_bands, 2): the means
+        [b_h0, b_h1] of the bottleneck distances per (recording, band).  The rows are the same either way."""
         import os
         import torch
-        super().__init__(device, ctx, fs, bands, correlations)
+        super().__init__(device, ctx, fs, bands, correlations, bottleneck)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -190,8 +201,10 @@ class RecordingPass(_ShardedPass):
             raw=torch.empty((S, n_ch, L), **f64), env=torch.empty((S, L), **f64),
             y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
             aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
-            ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations),
+            ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
+                                  bottleneck=self.bottleneck),
             corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
+            bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -236,6 +249,8 @@ class RecordingPass(_ShardedPass):
         st["rows"].copy_(res.view(nb, self.S, pipeline.RESULT_COLS).transpose(0, 1))
         if self.correlations:
             st["corr"].copy_(st["ws"].corr.view(nb, self.S, pipeline.CORR_COLS).transpose(0, 1))
+        if self.bottleneck:
+            st["bott"].copy_(st["ws"].bott.view(nb, self.S, pipeline.BOTT_COLS).transpose(0, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -331,12 +346,12 @@ class RaggedRecordingPass(_ShardedPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None, correlations=False):
+                 plan=None, correlations=False, bottleneck=False):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
-        recording without a window."""
+        recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2)."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
-                         correlations)
+                         correlations, bottleneck)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -372,9 +387,10 @@ class RaggedRecordingPass(_ShardedPass):
         def buffers():
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
-                                    n_ch=n_ch, correlations=self.correlations)
+                                    n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck)
             return dict(
                 corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
+                bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
@@ -418,6 +434,12 @@ class RaggedRecordingPass(_ShardedPass):
                 corr.fill_(float("nan"))
             if d["n_live"]:
                 corr.index_copy_(0, d["live"], st["views"][i].corr.view(len(self.bands), d["n_live"], pipeline.CORR_COLS).transpose(0, 1))
+        if self.bottleneck:
+            bott = st["bott"][:d["n"]]
+            if d["n_live"] < d["n"]:
+                bott.fill_(float("nan"))
+            if d["n_live"]:
+                bott.index_copy_(0, d["live"], st["views"][i].bott.view(len(self.bands), d["n_live"], pipeline.BOTT_COLS).transpose(0, 1))
 
     def _front_end(self, st, i):
         """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""
@@ -453,7 +475,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False):
+                 overlap=0.75, correlations=False, bottleneck=False):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -462,7 +484,8 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
         plan = RaggedPlan(eeg_lengths, A.n_out, n_ch=n_ch, n_bands=len(dict(bands)), fs=fs, window_sec=window_sec,
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
-                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations)
+                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
+                         bottleneck=bottleneck)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)

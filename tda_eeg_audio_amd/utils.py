@@ -142,6 +142,31 @@ def safe_wasserstein(dgm1, dgm2):
         return np.nan
 
 
+def _clean_pair_diagram(d):
+    """What safe_wasserstein hands to the solver: the diagram, or nothing for one that is not 2-D (utils.py:182-187; the
+    kernel drops the non-finite rows and substitutes {(0, 0)}).  Raises for anything that is not a (k, 2) table."""
+    d = np.asarray(d, dtype=np.float64)
+    if d.ndim != 2 or d.size == 0:
+        return np.zeros((0, 2))
+    if d.shape[1] != 2:
+        raise ValueError("a persistence diagram has two columns")
+    return d
+
+
+def safe_bottleneck(dgm1, dgm2):
+    """Bottleneck distance of two diagrams cleaned as safe_wasserstein cleans them (include/tdaeeg.h: L-infinity ground
+    cost, (d - b) / 2 to the diagonal, the largest matched cost of the best matching); NaN on any failure."""
+    if _ACTIVE is not None:
+        return _ACTIVE.add_bottleneck(dgm1, dgm2)
+    try:
+        ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+        rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+        out, st = engine.bottleneck_batch(ra, ca, rb, cb, want_status=True)
+        return float(out[0]) if st[0] == 0 else np.nan
+    except Exception:
+        return np.nan
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -188,7 +213,7 @@ class DeferredArray(_Deferred):
 
 
 class DeferredScalar(_Deferred):
-    """The value of a queued safe_wasserstein call."""
+    """The value of a queued safe_wasserstein or safe_bottleneck call."""
     __slots__ = ()
 
     def __float__(self):
@@ -233,14 +258,15 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein and extract_features queue their arguments and hand back deferred results,
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck and extract_features queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
-    clouds of all windows, the distance matrices of all windows, all Wasserstein pairs, all feature vectors.  Values,
+    clouds of all windows, the distance matrices of all windows, all Wasserstein pairs, all bottleneck pairs, all feature
+    vectors.  Values,
     error behaviour (NaN from safe_wasserstein, [[0, 0]] for degenerate clouds, ValueError for a non-square matrix) and
     result types after the block are those of the immediate calls."""
 
     def __init__(self):
-        self.clouds, self.dms, self.pairs, self.feats = [], [], [], []
+        self.clouds, self.dms, self.pairs, self.feats, self.bpairs = [], [], [], [], []
 
     def __enter__(self):
         global _ACTIVE
@@ -272,6 +298,11 @@ class batch:
         self.pairs.append((a, b, s))
         return s
 
+    def add_bottleneck(self, a, b):
+        s = DeferredScalar(self)
+        self.bpairs.append((a, b, s))
+        return s
+
     def add_features(self, dgm):
         f = DeferredFeatures(self)
         self.feats.append((dgm, f))
@@ -282,8 +313,8 @@ class batch:
         return x._value if isinstance(x, _Deferred) else x
 
     def flush(self):
-        clouds, dms, pairs, feats = self.clouds, self.dms, self.pairs, self.feats
-        self.clouds, self.dms, self.pairs, self.feats = [], [], [], []
+        clouds, dms, pairs, feats, bpairs = self.clouds, self.dms, self.pairs, self.feats, self.bpairs
+        self.clouds, self.dms, self.pairs, self.feats, self.bpairs = [], [], [], [], []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -315,6 +346,24 @@ class batch:
             except Exception:                       # utils.py:190-191: any failure -> NaN
                 for p in pairs:
                     p[2]._value = np.nan
+        if bpairs:
+            # one launch for every well-formed pair; a malformed one is NaN by itself
+            good = []
+            for p in bpairs:
+                p[2]._value = np.nan
+                try:
+                    good.append((_clean_pair_diagram(self._resolve(p[0])), _clean_pair_diagram(self._resolve(p[1])), p[2]))
+                except Exception:
+                    pass
+            try:
+                if good:
+                    ra, ca = engine.pack_diagrams([g[0] for g in good])
+                    rb, cb = engine.pack_diagrams([g[1] for g in good])
+                    out, st = engine.bottleneck_batch(ra, ca, rb, cb, want_status=True)
+                    for i, g in enumerate(good):
+                        g[2]._value = float(out[i]) if st[i] == 0 else np.nan
+            except Exception:
+                pass
         if feats:
             rows, cnt = engine.pack_diagrams([np.asarray(self._resolve(f[0]), dtype=np.float64) for f in feats])
             F = engine.features_batch(rows, cnt)
