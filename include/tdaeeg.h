@@ -477,6 +477,31 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
                                 const int* idx_a, const int* idx_b, int n_pairs,
                                 double* out, int* status);
 
+/* ---- Persistence landscapes and Betti curves, averaged per group ------------------
+ * A diagram has rows (b_i, d_i), i < min(cnt, cap), float64.  F is the set of rows with both values finite (the mask of
+ * tda_features_batch).  The grid is n_grid float64 values t_j, passed as an array: the caller computes them, the kernel
+ * never does.  There is no multiply-add anywhere in the definition.
+ *   tent_i(t)   = min(t - b_i, d_i - t), replaced by 0.0 where it is not > 0; each difference is one IEEE subtraction.
+ *   lambda_k(t), k = 1..K: the k-th largest value of the multiset {tent_i(t) : i in F} padded with K zeros.
+ *   beta(t)     = the number of rows i < min(cnt, cap) with b_i <= t < d_i, as float64; rows with d_i = +inf count.
+ *   V           = [lambda_1, ..., lambda_K, beta], shape (K + 1, n_grid): the vector of a diagram.
+ * Group mean, for the diagrams seg_off[g] <= w < seg_off[g + 1] in buffer order: diagrams whose status word has a bit of
+ * skip_mask are left out; s = V(first kept), then s = s + V(next kept) and so on, elementwise in that order; the result
+ * is s / n_kept, and NaN in every element when n_kept = 0.  This is np.mean(np.stack(kept), axis=0) (a plain sequential
+ * sum).  A group of one diagram is that diagram's own vector (x / 1): with seg_off = NULL every diagram is its own group
+ * and n_seg must be n_dgm.  The result does not depend on the order of the rows of a diagram.
+ * Limits: 1 <= n_levels <= TDA_MAX_LANDSCAPES, 1 <= n_grid <= TDA_MAX_GRID, cap >= 1; anything else is TDA_ERR_INVALID
+ * and nothing is launched.  Every operation is one correctly rounded float64 operation or an order-free selection: the
+ * output equals a CPU evaluation of this definition bit for bit.
+ * out: (n_seg, n_levels + 1, n_grid) float64.  The _dev form only enqueues on `stream` and allocates nothing. */
+#define TDA_MAX_LANDSCAPES 8
+#define TDA_MAX_GRID       256
+tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm,
+                                  const int* seg_off, int n_seg, const int* status, int skip_mask,
+                                  const double* grid, int n_grid, int n_levels, double* out, void* stream);
+tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
+                               const double* grid, int n_grid, int n_levels, double* out);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

@@ -26,6 +26,8 @@ TDA_WIN_NOT_CONVERGED = 8
 TDA_WIN_TOO_LARGE = 16
 TDA_WIN_NO_PAIR = 32          # tda_wasserstein_cross_dev: no partner at this position (mvm:89)
 N_FEATURES = 11
+MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
+MAX_GRID = 256              # TDA_MAX_GRID
 MAX_POINTS = 128
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
@@ -102,6 +104,8 @@ SYMBOLS = {
     "tda_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_bottleneck_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_bottleneck_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
+    "tda_landscape_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp]),
+    "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

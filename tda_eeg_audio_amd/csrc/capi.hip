@@ -422,6 +422,18 @@ tda_status tda_bottleneck_batch_dev(tda_ctx* ctx, const double* dgm_a, const int
                              (hipStream_t)stream);
 }
 
+tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
+                                  int n_seg, const int* status, int skip_mask, const double* grid, int n_grid,
+                                  int n_levels, double* out, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm); CHECK_NONNEG(ctx, n_seg);
+    if (!seg_off && n_seg != n_dgm) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); }
+    if (n_seg) { CHECK_PTR(ctx, grid); CHECK_PTR(ctx, out); }
+    return launch_landscape_mean(ctx, dgm, cnt, cap, n_dgm, seg_off, n_seg, status, skip_mask, grid, n_grid, n_levels, out,
+                                 (hipStream_t)stream);
+}
+
 tda_status tda_wasserstein_cross_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
                                      const int* grp_a, const int* seg_off_a, int n_seg_a, const double* dgm_b,
                                      const int* cnt_b, int cap_b, int n_b, const int* seg_off_b, int n_seg_b,
@@ -884,6 +896,28 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
     s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
     RET_IF(s.upload());
     RET_IF(tda_bottleneck_batch_dev(ctx, d_a, d_ca, cap_a, d_b, d_cb, cap_b, d_ia, d_ib, n_pairs, d_out, d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const double* grid,
+                               int n_grid, int n_levels, double* out)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm);
+    if (cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "cap must be >= 1");
+    if (n_levels < 1 || n_levels > TDA_MAX_LANDSCAPES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_levels must be 1..TDA_MAX_LANDSCAPES");
+    if (n_grid < 1 || n_grid > TDA_MAX_GRID) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_grid must be 1..TDA_MAX_GRID");
+    if (n_dgm == 0) return TDA_OK;
+    CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, out);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_dgm, *d_grid, *d_out; int* d_cnt;
+    s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16);
+    s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4);
+    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
+    s.add((void**)&d_out, nullptr, out, (size_t)n_dgm * (n_levels + 1) * n_grid * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_landscape_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
+                                  nullptr));
     return s.download();
 }
 

@@ -8,6 +8,8 @@ reference's on-disk formats.
         default_rng(md5(f"{dir}-{band}-{42}")[:8]).choice(n, size, replace=False)
                                                     scripts/tda_eeg_classification_v2.py:394-398
   process_file_features   scripts/tda_eeg_classification_v2.py:338-442  (220 features / recording)
+  landscapes_from_distances / landscape_names
+                          (not in the reference) mean persistence landscapes and Betti curves of the same groups
   get_eeg_diagrams        scripts/matched_vs_mismatched.py:66-85
   get_audio_diagrams_from_windows / compute_cross_wasserstein   mvm:43-63, 87-95
   process_recording_arrays  scripts/tda_eeg_audio_comparison.py:63-122 given the band-passed audio windows
@@ -116,6 +118,41 @@ def features_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
     f1 = engine.features_batch(h1, c1)
     seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
     return engine.aggregate_batch(f0, f1, seg)
+
+
+def landscapes_from_distances(dist_list, grid, levels, thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
+    per diagram set (H0, H1) that writes only the group means: (len(dist_list), 2, levels + 1, n_grid) float64, per group
+    the mean persistence landscape (levels 1..levels) and the mean Betti curve (last row) over its windows on `grid`
+    (include/tdaeeg.h; engine.landscape_mean_dev).  A group without a window is NaN."""
+    import torch
+    sizes = np.array([len(d) for d in dist_list])
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
+    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
+        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
+    check_status(st, "landscapes_from_distances")
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    grid_t = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float64)).to(dev)
+    out = torch.empty((2, len(dist_list), int(levels) + 1, grid_t.numel()), dtype=torch.float64, device=dev)
+    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
+        engine.landscape_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
+                                  grid_t, levels, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
+    return out.permute(1, 0, 2, 3).cpu().numpy().copy()
+
+
+def landscape_names(bands=BANDS, levels=5, grid=None):
+    """Column names of landscapes_from_distances(...)[r] of every band, flattened band by band: per band and diagram set
+    (h0, h1) the levels 1..levels and then the Betti curve, each at every grid point in order."""
+    n_grid = 64 if grid is None else len(grid)
+    names = []
+    for band in bands:
+        for h in ("h0", "h1"):
+            for lev in [f"landscape{k}" for k in range(1, int(levels) + 1)] + ["betti"]:
+                names += [f"{band}_{h}_{lev}_t{j}" for j in range(n_grid)]
+    return names
 
 
 def process_file_features(file_dir, freq_bands=BANDS, max_dim=1, max_edge_length=MAX_EDGE_LENGTH,

@@ -6,7 +6,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch,
-                 temporal_corr_batch
+                 landscape_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -274,6 +274,19 @@ def bottleneck_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=N
     ctx.check(ctx.lib.tda_bottleneck_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
                                            ptr(ia), ptr(ib), n_pairs, ptr(out), ptr(st)))
     return (out, st) if want_status else out
+
+
+def landscape_batch(rows, cnt, grid, levels, ctx=None):
+    """Persistence landscape and Betti curve of every diagram (include/tdaeeg.h): rows (n, cap, 2), cnt (n,), grid
+    (n_grid,) float64 -> (n, levels + 1, n_grid): levels 1..levels, then the Betti curve."""
+    ctx = ctx or get_ctx()
+    rows = f64(rows); cnt = i32(cnt); grid = f64(grid)
+    n, cap, _ = rows.shape
+    assert grid.ndim == 1
+    levels = int(levels)
+    out = np.empty((n, max(levels, 0) + 1, grid.shape[0]))
+    ctx.check(ctx.lib.tda_landscape_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(grid), grid.shape[0], levels, ptr(out)))
+    return out
 
 
 # ------------------------------------------------------------------ device-tensor API (torch)
@@ -568,6 +581,24 @@ def bottleneck_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=N
                                                _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
                                                _tp(out_t), _tp(status_t), _stream()))
     return out_t, status_t
+
+
+def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):
+    """Group means of [landscape levels 1..levels, Betti curve] of device diagrams (include/tdaeeg.h): one launch on
+    torch's current stream, nothing allocated when out_t is given.  seg_off_t (n_seg + 1,) int32, or None: every diagram
+    its own group.  Diagrams whose status_t word has a bit of skip_mask are left out; a group without a kept diagram is
+    NaN.  out_t: (n_seg, levels + 1, n_grid)."""
+    import torch
+    ctx = ctx or get_ctx()
+    n, cap, _ = rows_t.shape
+    n_seg = n if seg_off_t is None else seg_off_t.numel() - 1
+    n_grid, levels = grid_t.numel(), int(levels)
+    if out_t is None:
+        out_t = torch.empty((n_seg, max(levels, 0) + 1, n_grid), dtype=torch.float64, device=rows_t.device)
+    assert rows_t.is_contiguous() and out_t.is_contiguous() and grid_t.is_contiguous()
+    ctx.check(ctx.lib.tda_landscape_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
+                                             int(skip_mask), _tp(grid_t), n_grid, levels, _tp(out_t), _stream()))
+    return out_t
 
 
 def group_table(seg_off_t, n):

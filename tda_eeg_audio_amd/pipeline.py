@@ -18,13 +18,21 @@ from . import engine
 RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG features per recording-band
 CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
 BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
+LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
-    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False):
-        """bottleneck=True: run_step also fills `b0` / `b1` (n_win), the bottleneck distances of the H0 / H1 diagram pairs
+    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
+                 landscapes=None):
+        """landscapes=(grid, levels): run_step also fills `land` (n_seg, 3, levels + 1, n_grid): per group the mean
+        persistence landscape (levels 1..levels) and the mean Betti curve (last row) on the float64 grid, of the EEG H0, the
+        EEG H1 and the audio H1 diagrams of its windows (engine.landscape_mean_dev; include/tdaeeg.h has the definition).
+        The EEG sets average every window of the group, as the feature aggregation does (v2:429-436); the audio set leaves
+        out the windows whose cloud is degenerate or too large (cmp:90-91); a group without such a window is NaN.  The grid
+        is uploaded once, here.  `result` is the same either way.
+        bottleneck=True: run_step also fills `b0` / `b1` (n_win), the bottleneck distances of the H0 / H1 diagram pairs
         of every window (engine.bottleneck_dev; status words `bs0` / `bs1`), and `bott` (n_seg, 2): per group their
         np.nanmean over the windows the Wasserstein means of `result` run over -- a window whose audio cloud is
         degenerate (cmp:90-91) or whose pair has a solver status counts as NaN.  `result` is the same either way.
@@ -62,6 +70,19 @@ class Workspace:
             self.bs0 = torch.empty(n_win, dtype=torch.int32, device=device)
             self.bs1 = torch.empty(n_win, dtype=torch.int32, device=device)
             self.bott = torch.empty((self.n_seg, BOTT_COLS), **f64)
+        self.landscapes, self.land, self.land_grid, self.land_levels = None, None, None, 0
+        if landscapes is not None:
+            grid, levels = landscapes
+            grid = np.ascontiguousarray(grid, dtype=np.float64)
+            from . import _lib
+            if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID or not 1 <= int(levels) <= _lib.MAX_LANDSCAPES:
+                raise ValueError(f"landscapes=(grid, levels): a 1-D grid of 1..{_lib.MAX_GRID} points and 1..{_lib.MAX_LANDSCAPES} levels")
+            self.landscapes, self.land_levels = (grid, int(levels)), int(levels)
+            self.land_grid = torch.from_numpy(grid).to(device)
+            # stored set-major, one contiguous (n_seg, levels + 1, n_grid) block per launch; `land` is the same memory seen
+            # group-major
+            self.land_sets = torch.empty((LAND_SETS, self.n_seg, self.land_levels + 1, grid.shape[0]), **f64)
+            self.land = self.land_sets.permute(1, 0, 2, 3)
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -102,6 +123,9 @@ class Workspace:
             for name in ("b0", "b1", "bs0", "bs1"):
                 setattr(v, name, getattr(self, name)[:n_win])
             v.bott = self.bott[:n_seg]
+        if self.land is not None:
+            v.land_sets = self.land_sets[:, :n_seg]
+            v.land = v.land_sets.permute(1, 0, 2, 3)
         return v
 
 
@@ -175,6 +199,8 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         # temporal correlation of the H1 feature series over the windows that reach the distances (cmp:90-91,104-114)
         stage("temporal_corr", lambda: engine.temporal_corr_dev(ws.fa1, ws.fe1, ws.seg_off, ws.aud.status, cols=ws.corr_cols,
                                                                 out_t=ws.corr, ctx=ctx))
+    if getattr(ws, "land", None) is not None:
+        stage("landscape", lambda: _landscape_stage(ws, ctx, audio=True))
     stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
                                                            out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
     stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
@@ -197,6 +223,18 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     if retry != "auto":
         ws.flags_host.copy_(ws.seg_flags, non_blocking=True)
     return ws.result
+
+
+def _landscape_stage(ws, ctx, audio):
+    """ws.land of the step: one launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only its
+    (n_seg, levels + 1, n_grid) group means."""
+    from . import _lib
+    sets = [(ws.eeg.h0, ws.eeg.c0, None, 0), (ws.eeg.h1, ws.eeg.c1, None, 0)]
+    if audio:
+        sets.append((ws.aud.h1, ws.aud.c1, ws.aud.status, _lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE))
+    for s, (rows, cnt, status, mask) in enumerate(sets):
+        engine.landscape_mean_dev(rows, cnt, ws.land_grid, ws.land_levels, seg_off_t=ws.seg_off, status_t=status,
+                                  skip_mask=mask, out_t=ws.land_sets[s], ctx=ctx)
 
 
 class Batch:
@@ -465,6 +503,8 @@ def run_features_step(eeg_win, ws, ctx=None):
             engine.corr_dist_dev(eeg_win, ws.dist, None, ctx=ctx)
             engine.rips_dm_dev(ws.dist, ws.eeg, ctx=ctx)
     engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0), (ws.eeg.h1, ws.eeg.c1, True, ws.fe1)], ctx=ctx)
+    if getattr(ws, "land", None) is not None:            # the two EEG sets of ws.land; the audio set is not touched
+        _landscape_stage(ws, ctx, audio=False)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)
     engine.aggregate_dev(ws.fe0, ws.fe1, ws.seg_off, ws.feat44, ctx=ctx)
@@ -473,4 +513,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (a Workspace(correlations=True) has one more, "temporal_corr", after "finish"; a Workspace(bottleneck=True) two,
-# "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1")
+# "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1"; a Workspace(landscapes=(grid, levels)) one, "landscape",
+# after "finish" and "temporal_corr")

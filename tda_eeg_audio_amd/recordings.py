@@ -33,6 +33,9 @@ comparison_summary turn rows and corr_h into the script's table and statistics.
 With bottleneck=True RecordingPass and the ragged passes also return bott_h (n_rec, 5, 2): per (recording, band) the means
 of the bottleneck distances of the H0 and of the H1 diagram pairs (pipeline.Workspace(bottleneck=True)), over the
 windows the Wasserstein means of the rows run over.
+With landscapes=(grid, levels) the same passes also return land_h (n_rec, 5, 3, levels + 1, n_grid): per (recording, band)
+the mean persistence landscape and mean Betti curve of the EEG H0, EEG H1 and audio H1 diagrams of its windows
+(pipeline.Workspace(landscapes=...)); NaN for a recording without a window.
 """
 import numpy as np
 
@@ -54,7 +57,7 @@ class _ShardedPass:
       _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
       _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
-      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"])
+      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"])
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
                                     without a window (nothing to verify)
       _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
@@ -62,12 +65,15 @@ class _ShardedPass:
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
-    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False):
+    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None):
         self.ctx = ctx or get_ctx()
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
         self.correlations, self.corr_h = bool(correlations), None
         self.bottleneck, self.bott_h = bool(bottleneck), None
+        self.landscapes, self.land_h = None, None
+        if landscapes is not None:
+            self.landscapes = (np.ascontiguousarray(landscapes[0], dtype=np.float64), int(landscapes[1]))
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -91,9 +97,13 @@ class _ShardedPass:
                                                                        # for the compute of k, the upload of k + 1 must not)
         self.repairs = 0
 
+    def _land_shape(self):
+        """(3, levels + 1, n_grid): the landscape block of one (recording, band)."""
+        return (pipeline.LAND_SETS, self.landscapes[1] + 1, self.landscapes[0].shape[0])
+
     def run(self, raw_h, second_h, rows_h=None):
         """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
-        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True)."""
+        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=...)."""
         import torch
         self.ranges = self._begin(raw_h, second_h)
         n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
@@ -103,6 +113,8 @@ class _ShardedPass:
             self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
         if self.bottleneck and (self.bott_h is None or self.bott_h.shape[0] != n_rec):
             self.bott_h = torch.empty((n_rec, nb, pipeline.BOTT_COLS), dtype=torch.float64).pin_memory()
+        if self.landscapes is not None and (self.land_h is None or self.land_h.shape[0] != n_rec):
+            self.land_h = torch.empty((n_rec, nb) + self._land_shape(), dtype=torch.float64).pin_memory()
         pend = []
         try:
             for i, (r0, r1) in enumerate(self.ranges):
@@ -124,6 +136,8 @@ class _ShardedPass:
                         self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0], non_blocking=True)
                     if self.bottleneck:
                         self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0], non_blocking=True)
+                    if self.landscapes is not None:
+                        self.land_h[r0:r1].copy_(st["land"][:r1 - r0], non_blocking=True)
                     self._more_back(st, r0, r1, True)
                     st["down"].record(self.back)
                 pend.append(i)
@@ -161,6 +175,8 @@ class _ShardedPass:
                     self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0])
                 if self.bottleneck:
                     self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0])
+                if self.landscapes is not None:
+                    self.land_h[r0:r1].copy_(st["land"][:r1 - r0])
                 self._more_back(st, r0, r1, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
@@ -174,14 +190,17 @@ class RecordingPass(_ShardedPass):
     their flags say nothing new)."""
 
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
-                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False):
+                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
+                 landscapes=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
         feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
         drivers.DETAILED_COLUMNS[8:].  bottleneck=True: `run` also fills self.bott_h, pinned (n_rec, n_bands, 2): the means
-        [b_h0, b_h1] of the bottleneck distances per (recording, band).  The rows are the same either way."""
+        [b_h0, b_h1] of the bottleneck distances per (recording, band).  landscapes=(grid, levels): `run` also fills self.land_h,
+        pinned (n_rec, n_bands, 3, levels + 1, n_grid): the group means of pipeline.Workspace(landscapes=...).  The rows are
+        the same either way."""
         import os
         import torch
-        super().__init__(device, ctx, fs, bands, correlations, bottleneck)
+        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -202,9 +221,10 @@ class RecordingPass(_ShardedPass):
             y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
             aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
             ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
-                                  bottleneck=self.bottleneck),
+                                  bottleneck=self.bottleneck, landscapes=self.landscapes),
             corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
             bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
+            land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -251,6 +271,8 @@ class RecordingPass(_ShardedPass):
             st["corr"].copy_(st["ws"].corr.view(nb, self.S, pipeline.CORR_COLS).transpose(0, 1))
         if self.bottleneck:
             st["bott"].copy_(st["ws"].bott.view(nb, self.S, pipeline.BOTT_COLS).transpose(0, 1))
+        if self.landscapes is not None:
+            st["land"].copy_(st["ws"].land.unflatten(0, (nb, self.S)).transpose(0, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -346,12 +368,13 @@ class RaggedRecordingPass(_ShardedPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None, correlations=False, bottleneck=False):
+                 plan=None, correlations=False, bottleneck=False, landscapes=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
-        recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2)."""
+        recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2);
+        landscapes=(grid, levels): the same for self.land_h, pinned (n_rec, n_bands, 3, levels + 1, n_grid)."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
-                         correlations, bottleneck)
+                         correlations, bottleneck, landscapes)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -387,10 +410,12 @@ class RaggedRecordingPass(_ShardedPass):
         def buffers():
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
-                                    n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck)
+                                    n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
+                                    landscapes=self.landscapes)
             return dict(
                 corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                 bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
+                land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
@@ -440,6 +465,12 @@ class RaggedRecordingPass(_ShardedPass):
                 bott.fill_(float("nan"))
             if d["n_live"]:
                 bott.index_copy_(0, d["live"], st["views"][i].bott.view(len(self.bands), d["n_live"], pipeline.BOTT_COLS).transpose(0, 1))
+        if self.landscapes is not None:
+            land = st["land"][:d["n"]]
+            if d["n_live"] < d["n"]:
+                land.fill_(float("nan"))
+            if d["n_live"]:
+                land.index_copy_(0, d["live"], st["views"][i].land.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
 
     def _front_end(self, st, i):
         """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""
@@ -475,7 +506,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False, bottleneck=False):
+                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -485,7 +516,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
                          max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
-                         bottleneck=bottleneck)
+                         bottleneck=bottleneck, landscapes=landscapes)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)

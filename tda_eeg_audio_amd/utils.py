@@ -167,6 +167,50 @@ def safe_bottleneck(dgm1, dgm2):
         return np.nan
 
 
+def default_landscape_grid(n=64):
+    """The grid the landscape functions use when none is given: n points over the filtration, 0 .. MAX_EDGE_LENGTH."""
+    return np.linspace(0.0, MAX_EDGE_LENGTH, n)
+
+
+def _landscape_args(diagram, grid):
+    """The diagram as a (k, 2) float64 table (a queued one stays queued) and the grid as a 1-D float64 array."""
+    if not isinstance(diagram, _Deferred):
+        diagram = np.asarray(diagram, dtype=np.float64)
+        if diagram.ndim != 2 or diagram.shape[1] != 2:
+            raise ValueError("a persistence diagram is a (k, 2) table")
+    grid = default_landscape_grid() if grid is None else np.ascontiguousarray(grid, dtype=np.float64)
+    if grid.ndim != 1:
+        raise ValueError("the grid is a 1-D array")
+    return diagram, grid
+
+
+def _landscape_one(diagram, grid, levels):
+    if diagram.shape[0]:
+        rows, cnt = diagram[None], np.array([diagram.shape[0]], np.int32)
+    else:
+        rows, cnt = np.zeros((1, 1, 2)), np.zeros(1, np.int32)
+    return engine.landscape_batch(rows, cnt, grid, levels)[0]
+
+
+def persistence_landscape(diagram, grid=None, levels=5):
+    """The persistence landscape of one diagram on a grid (include/tdaeeg.h): (levels, n_grid) float64, level k the k-th
+    largest of the tents min(t - b, d - t) of the finite rows, 0 where there are fewer.  grid: default_landscape_grid().
+    Not in the reference; ValueError for a diagram that is not a (k, 2) table."""
+    diagram, grid = _landscape_args(diagram, grid)
+    if _ACTIVE is not None:
+        return _ACTIVE.add_landscape(diagram, grid, int(levels), False)
+    return _landscape_one(diagram, grid, levels)[:-1]
+
+
+def betti_curve(diagram, grid=None):
+    """The Betti curve of one diagram on a grid (include/tdaeeg.h): (n_grid,) float64, the number of rows with
+    b <= t < d (rows that never die count).  ValueError for a diagram that is not a (k, 2) table."""
+    diagram, grid = _landscape_args(diagram, grid)
+    if _ACTIVE is not None:
+        return _ACTIVE.add_landscape(diagram, grid, 1, True)
+    return _landscape_one(diagram, grid, 1)[-1]
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -210,6 +254,15 @@ class DeferredArray(_Deferred):
 
     def __repr__(self):
         return repr(self._get())
+
+
+class DeferredVector(DeferredArray):
+    """The Betti curve, (n_grid,) float64, of a queued betti_curve call."""
+    __slots__ = ()
+
+    @property
+    def ndim(self):
+        return 1
 
 
 class DeferredScalar(_Deferred):
@@ -258,15 +311,16 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck and extract_features queue their arguments and hand back deferred results,
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, extract_features, persistence_landscape and betti_curve
+    queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
     clouds of all windows, the distance matrices of all windows, all Wasserstein pairs, all bottleneck pairs, all feature
-    vectors.  Values,
+    vectors, all landscapes and Betti curves of one grid.  Values,
     error behaviour (NaN from safe_wasserstein, [[0, 0]] for degenerate clouds, ValueError for a non-square matrix) and
     result types after the block are those of the immediate calls."""
 
     def __init__(self):
-        self.clouds, self.dms, self.pairs, self.feats, self.bpairs = [], [], [], [], []
+        self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
 
     def __enter__(self):
         global _ACTIVE
@@ -308,13 +362,20 @@ class batch:
         self.feats.append((dgm, f))
         return f
 
+    def add_landscape(self, dgm, grid, levels, betti):
+        if not 1 <= levels <= engine._lib.MAX_LANDSCAPES or not 1 <= grid.shape[0] <= engine._lib.MAX_GRID:
+            raise TdaError("landscape levels must be 1..8 and the grid 1..256 points")
+        d = DeferredVector(self) if betti else DeferredArray(self)
+        self.lands.append((dgm, grid, levels, betti, d))
+        return d
+
     @staticmethod
     def _resolve(x):
         return x._value if isinstance(x, _Deferred) else x
 
     def flush(self):
-        clouds, dms, pairs, feats, bpairs = self.clouds, self.dms, self.pairs, self.feats, self.bpairs
-        self.clouds, self.dms, self.pairs, self.feats, self.bpairs = [], [], [], [], []
+        clouds, dms, pairs, feats, bpairs, lands = self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands
+        self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -372,3 +433,17 @@ class batch:
                 out["n_features"] = int(F[i][0])
                 out["n_essential"] = int(F[i][1])
                 f[1]._value = out
+        # ---- landscapes and Betti curves: one launch per distinct grid, at the most levels asked for on it (level k does
+        # not depend on how many levels are computed; the Betti curve is the last row)
+        for key in sorted({g[1].tobytes() for g in lands}):
+            grp = [g for g in lands if g[1].tobytes() == key]
+            dg = []
+            for g in grp:
+                d = np.asarray(self._resolve(g[0]), dtype=np.float64)
+                if d.ndim != 2 or d.shape[1] != 2:
+                    raise ValueError("a persistence diagram is a (k, 2) table")
+                dg.append(d)
+            rows, cnt = engine.pack_diagrams(dg)
+            V = engine.landscape_batch(rows, cnt, grp[0][1], max(g[2] for g in grp))
+            for i, g in enumerate(grp):
+                g[4]._value = V[i, -1].copy() if g[3] else V[i, :g[2]].copy()
