@@ -502,6 +502,45 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
                                const double* grid, int n_grid, int n_levels, double* out);
 
+/* ---- Persistence images, averaged per group -----------------------------------------
+ * The image of a diagram is the bivariate normal density with covariance sigma^2 I, placed on every point of the diagram in
+ * birth/persistence coordinates, weighted by a power of the persistence and integrated over every pixel of a grid.  This
+ * is how persim's PersistenceImager is understood; persim is not installed anywhere this project runs, so no parity with
+ * it is claimed.  The contract is this text.
+ * A diagram has rows (b_i, d_i), i < min(cnt, cap), float64.
+ *   Rows used.    F is the set of rows with both values finite (the mask of tda_features_batch).  Essential classes never
+ *                 enter an image.
+ *   Coordinates.  A point sits at (b_i, p_i) with p_i = d_i - b_i, one IEEE subtraction.
+ *   Edges.        xe holds n_x + 1 birth edges and ye holds n_y + 1 persistence edges, float64 arrays passed by the
+ *                 caller.  The kernel never computes an edge.
+ *   Width.        sigma is a float64 > 0.  s = sigma * 1.4142135623730951, one multiplication.
+ *   Weight.       power is in {0, 1, 2}.  The weight w_i is 1.0, p_i or p_i * p_i.
+ *   CDF.          Phi(e, c) = 0.5 * erfc(-((e - c) / s)).
+ *   Factors.      fx_i[c] = Phi(xe[c+1], b_i) - Phi(xe[c], b_i)
+ *                 fy_i[r] = Phi(ye[r+1], p_i) - Phi(ye[r], p_i)
+ *   Image.        I[r, c] = sum over i in F of (w_i * fy_i[r]) * fx_i[c], shape (n_y, n_x).  Row r is the persistence
+ *                 axis.  An empty F gives all zeros.
+ * Group mean, for the diagrams seg_off[g] <= w < seg_off[g + 1]: diagrams whose status word has a bit of skip_mask are
+ * left out; the result is (sum of the kept diagrams' images) / n_kept, and NaN in every element when n_kept = 0.  With
+ * seg_off = NULL every diagram is its own group and n_seg must be n_dgm.  Table entries are clamped to [0, n_dgm], as in
+ * tda_landscape_mean_dev.
+ * Order of additions.  d >= b holds for Rips rows, so every term is non-negative and the order of the additions is not
+ * part of the contract.  It is deterministic: no atomics; the additions that make a pixel depend only on the group's own
+ * diagrams and the parameters, not on the launch shape or on the other groups.  A recording alone and the same recording
+ * inside a shard give the same bytes.
+ * erfc is the device library's: the result agrees with a CPU evaluation of this text to rounding, not bit for bit.
+ * Limits: 1 <= n_x, n_y <= TDA_MAX_IMAGE_SIDE; sigma finite and > 0; power in {0, 1, 2}; cap >= 1; anything else is
+ * TDA_ERR_INVALID and nothing is launched.  The host form also rejects edges that are not finite and strictly ascending;
+ * the _dev form cannot see the edges and applies the formula as written.
+ * out: (n_seg, n_y, n_x) float64.  The _dev form only enqueues on `stream` and allocates nothing. */
+#define TDA_MAX_IMAGE_SIDE 32
+tda_status tda_image_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm,
+                              const int* seg_off, int n_seg, const int* status, int skip_mask,
+                              const double* xe, int n_x, const double* ye, int n_y, double sigma, int power,
+                              double* out, void* stream);
+tda_status tda_image_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
+                           const double* xe, int n_x, const double* ye, int n_y, double sigma, int power, double* out);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

@@ -28,6 +28,7 @@ TDA_WIN_NO_PAIR = 32          # tda_wasserstein_cross_dev: no partner at this po
 N_FEATURES = 11
 MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
 MAX_GRID = 256              # TDA_MAX_GRID
+MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 MAX_POINTS = 128
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
@@ -106,6 +107,8 @@ SYMBOLS = {
     "tda_bottleneck_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_landscape_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp]),
     "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
+    "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),
+    "tda_image_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

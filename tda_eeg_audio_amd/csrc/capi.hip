@@ -2,6 +2,7 @@
 // host-pointer twins (stage -> launch -> copy back) and timing helpers.
 #include "common.h"
 #include <string.h>
+#include <cmath>
 #include <vector>
 
 static thread_local std::string g_create_err;
@@ -432,6 +433,18 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
     if (n_seg) { CHECK_PTR(ctx, grid); CHECK_PTR(ctx, out); }
     return launch_landscape_mean(ctx, dgm, cnt, cap, n_dgm, seg_off, n_seg, status, skip_mask, grid, n_grid, n_levels, out,
                                  (hipStream_t)stream);
+}
+
+tda_status tda_image_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
+                              int n_seg, const int* status, int skip_mask, const double* xe, int n_x, const double* ye,
+                              int n_y, double sigma, int power, double* out, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm); CHECK_NONNEG(ctx, n_seg);
+    if (!seg_off && n_seg != n_dgm) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); }
+    if (n_seg) { CHECK_PTR(ctx, xe); CHECK_PTR(ctx, ye); CHECK_PTR(ctx, out); }
+    return launch_image_mean(ctx, dgm, cnt, cap, n_dgm, seg_off, n_seg, status, skip_mask, xe, n_x, ye, n_y, sigma, power,
+                             out, (hipStream_t)stream);
 }
 
 tda_status tda_wasserstein_cross_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a, int n_a,
@@ -918,6 +931,41 @@ tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, 
     RET_IF(s.upload());
     RET_IF(tda_landscape_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
                                   nullptr));
+    return s.download();
+}
+
+static bool image_edges_ok(const double* e, int n)
+{
+    for (int i = 0; i <= n; ++i)
+        if (!std::isfinite(e[i]) || (i && !(e[i] > e[i - 1]))) return false;
+    return true;
+}
+
+tda_status tda_image_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const double* xe, int n_x,
+                           const double* ye, int n_y, double sigma, int power, double* out)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm);
+    if (cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "cap must be >= 1");
+    if (n_x < 1 || n_x > TDA_MAX_IMAGE_SIDE || n_y < 1 || n_y > TDA_MAX_IMAGE_SIDE)
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "n_x and n_y must be 1..TDA_MAX_IMAGE_SIDE");
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) TDA_FAIL(ctx, TDA_ERR_INVALID, "sigma must be finite and > 0");
+    if (power < 0 || power > 2) TDA_FAIL(ctx, TDA_ERR_INVALID, "power must be 0, 1 or 2");
+    CHECK_PTR(ctx, xe); CHECK_PTR(ctx, ye);
+    if (!image_edges_ok(xe, n_x) || !image_edges_ok(ye, n_y))
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "image edges must be finite and strictly ascending");
+    if (n_dgm == 0) return TDA_OK;
+    CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, out);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_dgm, *d_xe, *d_ye, *d_out; int* d_cnt;
+    s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16);
+    s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4);
+    s.add((void**)&d_xe, xe, nullptr, (size_t)(n_x + 1) * 8);
+    s.add((void**)&d_ye, ye, nullptr, (size_t)(n_y + 1) * 8);
+    s.add((void**)&d_out, nullptr, out, (size_t)n_dgm * n_y * n_x * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_image_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_xe, n_x, d_ye, n_y, sigma, power,
+                              d_out, nullptr));
     return s.download();
 }
 

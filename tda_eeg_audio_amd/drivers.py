@@ -10,6 +10,8 @@ reference's on-disk formats.
   process_file_features   scripts/tda_eeg_classification_v2.py:338-442  (220 features / recording)
   landscapes_from_distances / landscape_names
                           (not in the reference) mean persistence landscapes and Betti curves of the same groups
+  images_from_distances / image_names
+                          (not in the reference) mean persistence images of the same groups
   get_eeg_diagrams        scripts/matched_vs_mismatched.py:66-85
   get_audio_diagrams_from_windows / compute_cross_wasserstein   mvm:43-63, 87-95
   process_recording_arrays  scripts/tda_eeg_audio_comparison.py:63-122 given the band-passed audio windows
@@ -153,6 +155,36 @@ def landscape_names(bands=BANDS, levels=5, grid=None):
             for lev in [f"landscape{k}" for k in range(1, int(levels) + 1)] + ["betti"]:
                 names += [f"{band}_{h}_{lev}_t{j}" for j in range(n_grid)]
     return names
+
+
+def images_from_distances(dist_list, xe, ye, sigma, power=1, thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
+    per diagram set (H0, H1) that writes only the group means: (len(dist_list), 2, n_y, n_x) float64, per group the mean
+    persistence image over its windows on the birth edges xe and the persistence edges ye (include/tdaeeg.h;
+    engine.image_mean_dev).  A group without a window is NaN.  ValueError for bad edges, sigma or power."""
+    import torch
+    xe, ye, sigma, power = engine.image_args(xe, ye, sigma, power)
+    sizes = np.array([len(d) for d in dist_list])
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
+    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
+        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
+    check_status(st, "images_from_distances")
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    xe_t, ye_t = torch.from_numpy(xe).to(dev), torch.from_numpy(ye).to(dev)
+    out = torch.empty((2, len(dist_list), ye.shape[0] - 1, xe.shape[0] - 1), dtype=torch.float64, device=dev)
+    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
+        engine.image_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
+                              xe_t, ye_t, sigma, power, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
+    return out.permute(1, 0, 2, 3).cpu().numpy().copy()
+
+
+def image_names(bands=BANDS, n_x=20, n_y=20):
+    """Column names of images_from_distances(...)[r] of every band, flattened band by band: per band and diagram set
+    (h0, h1) the pixels row by row, r the persistence index and c the birth index."""
+    return [f"{band}_{h}_image_r{r}_c{c}" for band in bands for h in ("h0", "h1") for r in range(int(n_y)) for c in range(int(n_x))]
 
 
 def process_file_features(file_dir, freq_bands=BANDS, max_dim=1, max_edge_length=MAX_EDGE_LENGTH,

@@ -6,7 +6,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch,
-                 landscape_batch, temporal_corr_batch
+                 landscape_batch, image_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -286,6 +286,47 @@ def landscape_batch(rows, cnt, grid, levels, ctx=None):
     levels = int(levels)
     out = np.empty((n, max(levels, 0) + 1, grid.shape[0]))
     ctx.check(ctx.lib.tda_landscape_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(grid), grid.shape[0], levels, ptr(out)))
+    return out
+
+
+def image_args(xe, ye, sigma, power):
+    """The parameters of a persistence image as the kernels take them: (xe, ye) contiguous 1-D float64, float sigma, int
+    power.  ValueError, before any GPU call, for edges that are not finite and strictly ascending or give a side outside
+    1..MAX_IMAGE_SIDE, a sigma that is not finite and > 0, a power outside {0, 1, 2}."""
+    edges = []
+    for name, e in (("xe", xe), ("ye", ye)):
+        try:
+            e = np.ascontiguousarray(e, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: the edges are a 1-D float64 array") from None
+        if e.ndim != 1 or not 2 <= e.shape[0] <= _lib.MAX_IMAGE_SIDE + 1:
+            raise ValueError(f"{name}: 2..{_lib.MAX_IMAGE_SIDE + 1} edges (1..{_lib.MAX_IMAGE_SIDE} pixels) in a 1-D array")
+        if not np.isfinite(e).all() or not (np.diff(e) > 0).all():
+            raise ValueError(f"{name}: the edges must be finite and strictly ascending")
+        edges.append(e)
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError("sigma must be a finite number > 0") from None
+    if not np.isfinite(sigma) or not sigma > 0:
+        raise ValueError("sigma must be a finite number > 0")
+    if isinstance(power, bool) or power not in (0, 1, 2):
+        raise ValueError("power must be 0, 1 or 2")
+    return edges[0], edges[1], sigma, int(power)
+
+
+def image_batch(rows, cnt, xe, ye, sigma, power=1, ctx=None):
+    """Persistence image of every diagram (include/tdaeeg.h): rows (n, cap, 2), cnt (n,), xe (n_x + 1,) birth edges, ye
+    (n_y + 1,) persistence edges, float64 -> (n, n_y, n_x).  Edges that are not finite and strictly ascending, a sigma that
+    is not finite and > 0 or a power outside {0, 1, 2} are a TdaError."""
+    ctx = ctx or get_ctx()
+    rows = f64(rows); cnt = i32(cnt); xe = f64(xe); ye = f64(ye)
+    n, cap, _ = rows.shape
+    assert xe.ndim == 1 and ye.ndim == 1
+    n_x, n_y = xe.shape[0] - 1, ye.shape[0] - 1
+    out = np.empty((n, max(n_y, 0), max(n_x, 0)))
+    ctx.check(ctx.lib.tda_image_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(xe), n_x, ptr(ye), n_y, float(sigma), int(power),
+                                      ptr(out)))
     return out
 
 
@@ -598,6 +639,25 @@ def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=N
     assert rows_t.is_contiguous() and out_t.is_contiguous() and grid_t.is_contiguous()
     ctx.check(ctx.lib.tda_landscape_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
                                              int(skip_mask), _tp(grid_t), n_grid, levels, _tp(out_t), _stream()))
+    return out_t
+
+
+def image_mean_dev(rows_t, cnt_t, xe_t, ye_t, sigma, power, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):
+    """Group means of the persistence images of device diagrams (include/tdaeeg.h): one launch on torch's current stream,
+    nothing allocated when out_t is given.  xe_t (n_x + 1,), ye_t (n_y + 1,) float64 edges on the device; seg_off_t
+    (n_seg + 1,) int32, or None: every diagram its own group.  Diagrams whose status_t word has a bit of skip_mask are left
+    out; a group without a kept diagram is NaN.  out_t: (n_seg, n_y, n_x)."""
+    import torch
+    ctx = ctx or get_ctx()
+    n, cap, _ = rows_t.shape
+    n_seg = n if seg_off_t is None else seg_off_t.numel() - 1
+    n_x, n_y = xe_t.numel() - 1, ye_t.numel() - 1
+    if out_t is None:
+        out_t = torch.empty((n_seg, max(n_y, 0), max(n_x, 0)), dtype=torch.float64, device=rows_t.device)
+    assert rows_t.is_contiguous() and out_t.is_contiguous() and xe_t.is_contiguous() and ye_t.is_contiguous()
+    ctx.check(ctx.lib.tda_image_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
+                                         int(skip_mask), _tp(xe_t), n_x, _tp(ye_t), n_y, float(sigma), int(power),
+                                         _tp(out_t), _stream()))
     return out_t
 
 

@@ -20,13 +20,18 @@ CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).co
 BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 
+IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None):
-        """landscapes=(grid, levels): run_step also fills `land` (n_seg, 3, levels + 1, n_grid): per group the mean
+                 landscapes=None, images=None):
+        """images=(xe, ye, sigma, power): run_step also fills `img` (n_seg, 3, n_y, n_x): per group the mean persistence
+        image of the EEG H0, the EEG H1 and the audio H1 diagrams of its windows on the float64 birth edges xe (n_x + 1) and
+        persistence edges ye (n_y + 1) (engine.image_mean_dev; include/tdaeeg.h has the definition).  Windows and the audio
+        mask are those of `land`.  The edges are uploaded once, here.  `result` is the same either way.
+        landscapes=(grid, levels): run_step also fills `land` (n_seg, 3, levels + 1, n_grid): per group the mean
         persistence landscape (levels 1..levels) and the mean Betti curve (last row) on the float64 grid, of the EEG H0, the
         EEG H1 and the audio H1 diagrams of its windows (engine.landscape_mean_dev; include/tdaeeg.h has the definition).
         The EEG sets average every window of the group, as the feature aggregation does (v2:429-436); the audio set leaves
@@ -83,6 +88,14 @@ class Workspace:
             # group-major
             self.land_sets = torch.empty((LAND_SETS, self.n_seg, self.land_levels + 1, grid.shape[0]), **f64)
             self.land = self.land_sets.permute(1, 0, 2, 3)
+        self.images, self.img, self.img_sets = None, None, None
+        if images is not None:
+            xe, ye, sigma, power = engine.image_args(*images)
+            self.images = (xe, ye, sigma, power)
+            self.img_xe, self.img_ye = torch.from_numpy(xe).to(device), torch.from_numpy(ye).to(device)
+            # set-major like land_sets: one contiguous (n_seg, n_y, n_x) block per launch; `img` is the group-major view
+            self.img_sets = torch.empty((IMG_SETS, self.n_seg, ye.shape[0] - 1, xe.shape[0] - 1), **f64)
+            self.img = self.img_sets.permute(1, 0, 2, 3)
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -126,6 +139,9 @@ class Workspace:
         if self.land is not None:
             v.land_sets = self.land_sets[:, :n_seg]
             v.land = v.land_sets.permute(1, 0, 2, 3)
+        if self.img is not None:
+            v.img_sets = self.img_sets[:, :n_seg]
+            v.img = v.img_sets.permute(1, 0, 2, 3)
         return v
 
 
@@ -201,6 +217,8 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
                                                                 out_t=ws.corr, ctx=ctx))
     if getattr(ws, "land", None) is not None:
         stage("landscape", lambda: _landscape_stage(ws, ctx, audio=True))
+    if getattr(ws, "img", None) is not None:
+        stage("image", lambda: _image_stage(ws, ctx, audio=True))
     stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
                                                            out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
     stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
@@ -235,6 +253,19 @@ def _landscape_stage(ws, ctx, audio):
     for s, (rows, cnt, status, mask) in enumerate(sets):
         engine.landscape_mean_dev(rows, cnt, ws.land_grid, ws.land_levels, seg_off_t=ws.seg_off, status_t=status,
                                   skip_mask=mask, out_t=ws.land_sets[s], ctx=ctx)
+
+
+def _image_stage(ws, ctx, audio):
+    """ws.img of the step: one launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only its
+    (n_seg, n_y, n_x) group means."""
+    from . import _lib
+    _, _, sigma, power = ws.images
+    sets = [(ws.eeg.h0, ws.eeg.c0, None, 0), (ws.eeg.h1, ws.eeg.c1, None, 0)]
+    if audio:
+        sets.append((ws.aud.h1, ws.aud.c1, ws.aud.status, _lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE))
+    for s, (rows, cnt, status, mask) in enumerate(sets):
+        engine.image_mean_dev(rows, cnt, ws.img_xe, ws.img_ye, sigma, power, seg_off_t=ws.seg_off, status_t=status,
+                              skip_mask=mask, out_t=ws.img_sets[s], ctx=ctx)
 
 
 class Batch:
@@ -505,6 +536,8 @@ def run_features_step(eeg_win, ws, ctx=None):
     engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0), (ws.eeg.h1, ws.eeg.c1, True, ws.fe1)], ctx=ctx)
     if getattr(ws, "land", None) is not None:            # the two EEG sets of ws.land; the audio set is not touched
         _landscape_stage(ws, ctx, audio=False)
+    if getattr(ws, "img", None) is not None:             # the same for ws.img
+        _image_stage(ws, ctx, audio=False)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)
     engine.aggregate_dev(ws.fe0, ws.fe1, ws.seg_off, ws.feat44, ctx=ctx)
@@ -514,4 +547,4 @@ def run_features_step(eeg_win, ws, ctx=None):
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (a Workspace(correlations=True) has one more, "temporal_corr", after "finish"; a Workspace(bottleneck=True) two,
 # "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1"; a Workspace(landscapes=(grid, levels)) one, "landscape",
-# after "finish" and "temporal_corr")
+# after "finish" and "temporal_corr"; a Workspace(images=(xe, ye, sigma, power)) one, "image", after "landscape")

@@ -36,6 +36,8 @@ windows the Wasserstein means of the rows run over.
 With landscapes=(grid, levels) the same passes also return land_h (n_rec, 5, 3, levels + 1, n_grid): per (recording, band)
 the mean persistence landscape and mean Betti curve of the EEG H0, EEG H1 and audio H1 diagrams of its windows
 (pipeline.Workspace(landscapes=...)); NaN for a recording without a window.
+With images=(xe, ye, sigma, power) they also return img_h (n_rec, 5, 3, n_y, n_x): per (recording, band) the mean persistence
+image of the same three diagram sets (pipeline.Workspace(images=...)); NaN for a recording without a window.
 """
 import numpy as np
 
@@ -57,7 +59,7 @@ class _ShardedPass:
       _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
       _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
-      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"])
+      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"], st["img"])
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
                                     without a window (nothing to verify)
       _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
@@ -65,7 +67,7 @@ class _ShardedPass:
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
-    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None):
+    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None, images=None):
         self.ctx = ctx or get_ctx()
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
@@ -74,6 +76,10 @@ class _ShardedPass:
         self.landscapes, self.land_h = None, None
         if landscapes is not None:
             self.landscapes = (np.ascontiguousarray(landscapes[0], dtype=np.float64), int(landscapes[1]))
+        self.images, self.img_h = None, None
+        if images is not None:
+            from . import engine
+            self.images = engine.image_args(*images)
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -101,9 +107,13 @@ class _ShardedPass:
         """(3, levels + 1, n_grid): the landscape block of one (recording, band)."""
         return (pipeline.LAND_SETS, self.landscapes[1] + 1, self.landscapes[0].shape[0])
 
+    def _img_shape(self):
+        """(3, n_y, n_x): the image block of one (recording, band)."""
+        return (pipeline.IMG_SETS, self.images[1].shape[0] - 1, self.images[0].shape[0] - 1)
+
     def run(self, raw_h, second_h, rows_h=None):
         """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
-        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=...)."""
+        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=..., self.img_h with images=...)."""
         import torch
         self.ranges = self._begin(raw_h, second_h)
         n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
@@ -115,6 +125,8 @@ class _ShardedPass:
             self.bott_h = torch.empty((n_rec, nb, pipeline.BOTT_COLS), dtype=torch.float64).pin_memory()
         if self.landscapes is not None and (self.land_h is None or self.land_h.shape[0] != n_rec):
             self.land_h = torch.empty((n_rec, nb) + self._land_shape(), dtype=torch.float64).pin_memory()
+        if self.images is not None and (self.img_h is None or self.img_h.shape[0] != n_rec):
+            self.img_h = torch.empty((n_rec, nb) + self._img_shape(), dtype=torch.float64).pin_memory()
         pend = []
         try:
             for i, (r0, r1) in enumerate(self.ranges):
@@ -138,6 +150,8 @@ class _ShardedPass:
                         self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0], non_blocking=True)
                     if self.landscapes is not None:
                         self.land_h[r0:r1].copy_(st["land"][:r1 - r0], non_blocking=True)
+                    if self.images is not None:
+                        self.img_h[r0:r1].copy_(st["img"][:r1 - r0], non_blocking=True)
                     self._more_back(st, r0, r1, True)
                     st["down"].record(self.back)
                 pend.append(i)
@@ -177,6 +191,8 @@ class _ShardedPass:
                     self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0])
                 if self.landscapes is not None:
                     self.land_h[r0:r1].copy_(st["land"][:r1 - r0])
+                if self.images is not None:
+                    self.img_h[r0:r1].copy_(st["img"][:r1 - r0])
                 self._more_back(st, r0, r1, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
@@ -191,16 +207,17 @@ class RecordingPass(_ShardedPass):
 
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
                  max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
-                 landscapes=None):
+                 landscapes=None, images=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
         feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
         drivers.DETAILED_COLUMNS[8:].  bottleneck=True: `run` also fills self.bott_h, pinned (n_rec, n_bands, 2): the means
         [b_h0, b_h1] of the bottleneck distances per (recording, band).  landscapes=(grid, levels): `run` also fills self.land_h,
-        pinned (n_rec, n_bands, 3, levels + 1, n_grid): the group means of pipeline.Workspace(landscapes=...).  The rows are
-        the same either way."""
+        pinned (n_rec, n_bands, 3, levels + 1, n_grid): the group means of pipeline.Workspace(landscapes=...).
+        images=(xe, ye, sigma, power): `run` also fills self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x): the group means of
+        pipeline.Workspace(images=...).  The rows are the same either way."""
         import os
         import torch
-        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes)
+        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -221,10 +238,11 @@ class RecordingPass(_ShardedPass):
             y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
             aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
             ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
-                                  bottleneck=self.bottleneck, landscapes=self.landscapes),
+                                  bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images),
             corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
             bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
             land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
+            img=torch.empty((S, nb) + self._img_shape(), **f64) if self.images is not None else None,
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -273,6 +291,8 @@ class RecordingPass(_ShardedPass):
             st["bott"].copy_(st["ws"].bott.view(nb, self.S, pipeline.BOTT_COLS).transpose(0, 1))
         if self.landscapes is not None:
             st["land"].copy_(st["ws"].land.unflatten(0, (nb, self.S)).transpose(0, 1))
+        if self.images is not None:
+            st["img"].copy_(st["ws"].img.unflatten(0, (nb, self.S)).transpose(0, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -368,13 +388,14 @@ class RaggedRecordingPass(_ShardedPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None, correlations=False, bottleneck=False, landscapes=None):
+                 plan=None, correlations=False, bottleneck=False, landscapes=None, images=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
         recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2);
-        landscapes=(grid, levels): the same for self.land_h, pinned (n_rec, n_bands, 3, levels + 1, n_grid)."""
+        landscapes=(grid, levels): the same for self.land_h, pinned (n_rec, n_bands, 3, levels + 1, n_grid);
+        images=(xe, ye, sigma, power): the same for self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x)."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
-                         correlations, bottleneck, landscapes)
+                         correlations, bottleneck, landscapes, images)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -411,11 +432,12 @@ class RaggedRecordingPass(_ShardedPass):
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
                                     n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
-                                    landscapes=self.landscapes)
+                                    landscapes=self.landscapes, images=self.images)
             return dict(
                 corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                 bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
                 land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
+                img=torch.empty((S, nb) + self._img_shape(), **f64) if self.images is not None else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
@@ -471,6 +493,12 @@ class RaggedRecordingPass(_ShardedPass):
                 land.fill_(float("nan"))
             if d["n_live"]:
                 land.index_copy_(0, d["live"], st["views"][i].land.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
+        if self.images is not None:
+            img = st["img"][:d["n"]]
+            if d["n_live"] < d["n"]:
+                img.fill_(float("nan"))
+            if d["n_live"]:
+                img.index_copy_(0, d["live"], st["views"][i].img.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
 
     def _front_end(self, st, i):
         """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""
@@ -506,7 +534,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None):
+                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None, images=None):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -516,7 +544,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
                          max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
-                         bottleneck=bottleneck, landscapes=landscapes)
+                         bottleneck=bottleneck, landscapes=landscapes, images=images)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)

@@ -211,6 +211,34 @@ def betti_curve(diagram, grid=None):
     return _landscape_one(diagram, grid, 1)[-1]
 
 
+def default_image_edges(n_x=20, n_y=20, birth_range=(0.0, MAX_EDGE_LENGTH), pers_range=(0.0, MAX_EDGE_LENGTH)):
+    """(xe, ye): n_x + 1 evenly spaced birth edges over birth_range and n_y + 1 persistence edges over pers_range; by
+    default both span the filtration, 0 .. MAX_EDGE_LENGTH."""
+    return (np.linspace(float(birth_range[0]), float(birth_range[1]), int(n_x) + 1),
+            np.linspace(float(pers_range[0]), float(pers_range[1]), int(n_y) + 1))
+
+
+def persistence_image(dgm, xe, ye, sigma, power=1):
+    """The persistence image of one diagram (include/tdaeeg.h): (n_y, n_x) float64, row r the persistence axis; every
+    finite row (b, d) is a normal density of width sigma at (b, d - b), weighted by (d - b) ** power and integrated over
+    the pixels between the birth edges xe (n_x + 1) and the persistence edges ye (n_y + 1).  Not in the reference.
+    ValueError, before any GPU call, for a diagram that is not a (k, 2) table, for edges that are not finite and strictly
+    ascending (or more than MAX_IMAGE_SIDE pixels a side), for a sigma that is not finite and > 0 and for a power outside
+    {0, 1, 2}."""
+    if not isinstance(dgm, _Deferred):
+        dgm = np.asarray(dgm, dtype=np.float64)
+        if dgm.ndim != 2 or dgm.shape[1] != 2:
+            raise ValueError("a persistence diagram is a (k, 2) table")
+    xe, ye, sigma, power = engine.image_args(xe, ye, sigma, power)
+    if _ACTIVE is not None:
+        return _ACTIVE.add_image(dgm, xe, ye, sigma, power)
+    if dgm.shape[0]:
+        rows, cnt = dgm[None], np.array([dgm.shape[0]], np.int32)
+    else:
+        rows, cnt = np.zeros((1, 1, 2)), np.zeros(1, np.int32)
+    return engine.image_batch(rows, cnt, xe, ye, sigma, power)[0]
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -311,16 +339,18 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, extract_features, persistence_landscape and betti_curve
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, extract_features, persistence_landscape, betti_curve and
+    persistence_image
     queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
     clouds of all windows, the distance matrices of all windows, all Wasserstein pairs, all bottleneck pairs, all feature
-    vectors, all landscapes and Betti curves of one grid.  Values,
+    vectors, all landscapes and Betti curves of one grid, all images of one (xe, ye, sigma, power).  Values,
     error behaviour (NaN from safe_wasserstein, [[0, 0]] for degenerate clouds, ValueError for a non-square matrix) and
     result types after the block are those of the immediate calls."""
 
     def __init__(self):
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
+        self.imgs = []
 
     def __enter__(self):
         global _ACTIVE
@@ -369,6 +399,11 @@ class batch:
         self.lands.append((dgm, grid, levels, betti, d))
         return d
 
+    def add_image(self, dgm, xe, ye, sigma, power):
+        d = DeferredArray(self)
+        self.imgs.append((dgm, (xe.tobytes(), ye.tobytes(), sigma, power), (xe, ye), d))
+        return d
+
     @staticmethod
     def _resolve(x):
         return x._value if isinstance(x, _Deferred) else x
@@ -376,6 +411,7 @@ class batch:
     def flush(self):
         clouds, dms, pairs, feats, bpairs, lands = self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
+        imgs, self.imgs = self.imgs, []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -447,3 +483,16 @@ class batch:
             V = engine.landscape_batch(rows, cnt, grp[0][1], max(g[2] for g in grp))
             for i, g in enumerate(grp):
                 g[4]._value = V[i, -1].copy() if g[3] else V[i, :g[2]].copy()
+        # ---- persistence images: one launch per distinct (xe, ye, sigma, power)
+        for key in sorted({g[1] for g in imgs}):
+            grp = [g for g in imgs if g[1] == key]
+            dg = []
+            for g in grp:
+                d = np.asarray(self._resolve(g[0]), dtype=np.float64)
+                if d.ndim != 2 or d.shape[1] != 2:
+                    raise ValueError("a persistence diagram is a (k, 2) table")
+                dg.append(d)
+            rows, cnt = engine.pack_diagrams(dg)
+            V = engine.image_batch(rows, cnt, grp[0][2][0], grp[0][2][1], key[2], key[3])
+            for i, g in enumerate(grp):
+                g[3]._value = V[i].copy()
