@@ -308,7 +308,10 @@ tda_status tda_hilbert_envelope_ragged_dev(tda_ctx* ctx, const double* x, int n_
                                            const long long* g_off, double* env, void* stream);
 
 /* ---- delay from the first zero crossing of the autocorrelation ---------------
- * replaces compute_tau (scripts/utils.py:92-104). max_lag < 0 = None (len/4).         */
+ * replaces compute_tau (scripts/utils.py:92-104). max_lag < 0 = None (len/4).
+ * n_t: 2 <= n_t <= 8192 (the centred window is held in LDS, 8 n_t bytes); anything else is
+ * TDA_ERR_UNSUPPORTED.  max_lag: any value; as in the reference it is cut to n_t - 1.  The same
+ * limits hold for tda_tau_segments_dev.                                                */
 tda_status tda_tau_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag,
                              int* tau, void* stream);
 tda_status tda_tau_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int* tau);

@@ -115,7 +115,8 @@ __device__ __forceinline__ double np_pairwise_sum_uniform(const double* a, int n
 
 // ---------------------------------------------------------------------------------
 // compute_tau: first lag k in [1, min(max_lag, len)) whose autocorrelation is <= 0.
-// One wave per window; lane l owns lags l+1 and l+65 (max_lag <= 128), each a
+// One wave per window; the lags are walked in chunks of 64, lane l owning lag k0 + l of the chunk that starts at k0
+// (any max_lag: the loop ends with the first chunk that holds a lag with ac <= 0), each lag a
 // sequential fma chain over t (the order oracle/tda_oracle.c::orc_compute_tau fixes).
 // ---------------------------------------------------------------------------------
 // seg_off != nullptr: workgroup g handles the FIRST window of group g (tda_eeg_audio_comparison.py:83: tau is
