@@ -480,6 +480,46 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
                                 const int* idx_a, const int* idx_b, int n_pairs,
                                 double* out, int* status);
 
+/* ---- Sliced Wasserstein distance between diagrams ---------------------------------
+ * Carriere, Cuturi, Oudot 2017 (what persim.sliced_wasserstein computes): project both diagrams onto a handful of
+ * directions, sort each projection, take the L1 difference of the sorted lists, average over the directions.  persim is
+ * not installed anywhere this project runs, so no parity with it is claimed.  The contract is this text.
+ *   Cleaning.     As for the Wasserstein distance: rows with a non-finite entry are ignored, an empty diagram becomes
+ *                 {(0,0)}.  A has m rows (b, d) after cleaning, B has n, and N = m + n.
+ *   Images.       For a row, h = 0.5 * (b + d) (one addition, one exact multiplication); its image is the point (h, h).
+ *   Lists.        A' is the rows of A followed by the images of the rows of B; B' is the rows of B followed by the images
+ *                 of the rows of A.  Both have N points.
+ *   Directions.   dirs is an (n_dirs, 2) float64 table (c_k, s_k) passed by the caller.  The kernel never evaluates a
+ *                 trigonometric function and never normalises a direction.
+ *   Projection.   For every point (x, y) of A' and B', the images included: p = (c * x) + (s * y) -- two rounded
+ *                 multiplications and one rounded addition, no multiply-add.  The same formula applies to the images; it
+ *                 is not (c + s) * h.
+ *   Per direction. u is the N projections of A' in ascending order, v those of B'; t_i = fabs(u_i - v_i), i < N; L_k is
+ *                 the sum of the t_i.  Sorting is an order-free selection: ties and -0.0 do not change any t_i.
+ *   Result.       SW = (sum over k of L_k) / n_dirs.
+ * Order of additions.  Every t_i is the same float64 on the GPU and in a CPU evaluation of this text.  Every term is
+ * non-negative, so the order of the additions is not part of the contract.  It is deterministic: no atomics; the order
+ * depends only on the rank index i and the direction index k; a pair alone and the same pair inside a batch give the same
+ * bytes; SW(A, B) and SW(B, A) give the same bytes.
+ * Tolerance.  Any two summation orders of n non-negative terms agree within 2 (n - 1) 2^-53 relative, to first order;
+ * applied to the inner and the outer sum, the GPU value agrees with any CPU evaluation of this text within
+ * (N + n_dirs + 1) * 2^-52 * value, and exactly where the value is 0.
+ * Limits: 1 <= n_dirs <= TDA_MAX_DIRECTIONS and cap >= 1; anything else is TDA_ERR_INVALID and nothing is launched.  A pair
+ * with N > TDA_SW_MAX_POINTS gets NaN and TDA_WIN_TOO_LARGE.  The host form also rejects directions that are not finite; the
+ * _dev form cannot see them and applies the formula as written.
+ * Arguments as tda_wasserstein_batch[_dev] (idx_a / idx_b NULL = identity), plus dirs.  out: (n_pairs) float64, NaN where
+ * status != 0; status: (n_pairs) int32.  The _dev form only enqueues on `stream` and allocates nothing. */
+#define TDA_MAX_DIRECTIONS 128
+#define TDA_SW_MAX_POINTS  512
+tda_status tda_sliced_wasserstein_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
+                                            const double* dgm_b, const int* cnt_b, int cap_b,
+                                            const int* idx_a, const int* idx_b, int n_pairs,
+                                            const double* dirs, int n_dirs, double* out, int* status, void* stream);
+tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                        const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                        const int* idx_a, const int* idx_b, int n_pairs,
+                                        const double* dirs, int n_dirs, double* out, int* status);
+
 /* ---- Persistence landscapes and Betti curves, averaged per group ------------------
  * A diagram has rows (b_i, d_i), i < min(cnt, cap), float64.  F is the set of rows with both values finite (the mask of
  * tda_features_batch).  The grid is n_grid float64 values t_j, passed as an array: the caller computes them, the kernel

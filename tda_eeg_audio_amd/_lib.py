@@ -30,6 +30,8 @@ MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
 MAX_GRID = 256              # TDA_MAX_GRID
 MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 MAX_POINTS = 128
+MAX_DIRECTIONS = 128        # TDA_MAX_DIRECTIONS
+SW_MAX_POINTS = 512         # TDA_SW_MAX_POINTS
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -105,6 +107,10 @@ SYMBOLS = {
     "tda_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_bottleneck_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_bottleneck_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
+    "tda_sliced_wasserstein_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp,
+                                              c_vp]),
+    "tda_sliced_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, _I, c_vp,
+                                          c_vp]),
     "tda_landscape_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp]),
     "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
     "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),

@@ -6,6 +6,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch,
+                 sliced_wasserstein_batch, sliced_wasserstein_gram,
                  landscape_batch, image_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
@@ -328,6 +329,56 @@ def image_batch(rows, cnt, xe, ye, sigma, power=1, ctx=None):
     ctx.check(ctx.lib.tda_image_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(xe), n_x, ptr(ye), n_y, float(sigma), int(power),
                                       ptr(out)))
     return out
+
+
+def _directions(dirs):
+    """The (M, 2) float64 direction table of the sliced Wasserstein entry points, validated on the host."""
+    d = np.asarray(dirs, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 2:
+        raise _lib.TdaError("libtdaeeg error 1: dirs must have shape (M, 2)")
+    if not 1 <= d.shape[0] <= _lib.MAX_DIRECTIONS:
+        raise _lib.TdaError("libtdaeeg error 1: 1 <= M <= TDA_MAX_DIRECTIONS directions")
+    if not np.isfinite(d).all():
+        raise _lib.TdaError("libtdaeeg error 1: directions must be finite")
+    return np.ascontiguousarray(d)
+
+
+def sliced_wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, dirs, idx_a=None, idx_b=None, ctx=None, want_status=False):
+    """Sliced Wasserstein distance of diagram pairs over the (M, 2) direction table `dirs` (include/tdaeeg.h: both diagrams
+    augmented with the other's diagonal images, projected as (c * x) + (s * y), sorted, L1 difference, mean over the
+    directions); the other arguments and the results as wasserstein_batch.  A pair with more than TDA_SW_MAX_POINTS
+    points in all is NaN with status TDA_WIN_TOO_LARGE."""
+    ctx = ctx or get_ctx()
+    d = _directions(dirs)
+    ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
+    n_a, cap_a, _ = ra.shape
+    n_b, cap_b, _ = rb.shape
+    if idx_a is None and idx_b is None:
+        assert n_a == n_b
+        n_pairs = n_a
+    else:
+        n_pairs = len(idx_a if idx_a is not None else idx_b)
+    ia = None if idx_a is None else i32(idx_a)
+    ib = None if idx_b is None else i32(idx_b)
+    out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
+    ctx.check(ctx.lib.tda_sliced_wasserstein_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
+                                                   ptr(ia), ptr(ib), n_pairs, ptr(d), d.shape[0], ptr(out), ptr(st)))
+    return (out, st) if want_status else out
+
+
+def sliced_wasserstein_gram(rows, cnt, dirs, ctx=None):
+    """(n, n) symmetric matrix of the sliced Wasserstein distances of one set of diagrams: the pairs i < j in one batched
+    call, mirrored; the diagonal is 0.0.  NaN where a pair has a status."""
+    n = len(cnt)
+    iu, ju = np.triu_indices(n, 1)
+    G = np.zeros((n, n))
+    if len(iu):
+        d = sliced_wasserstein_batch(rows, cnt, rows, cnt, dirs, idx_a=iu, idx_b=ju, ctx=ctx)
+        G[iu, ju] = d
+        G[ju, iu] = d
+    else:
+        _directions(dirs)
+    return G
 
 
 # ------------------------------------------------------------------ device-tensor API (torch)
@@ -659,6 +710,25 @@ def image_mean_dev(rows_t, cnt_t, xe_t, ye_t, sigma, power, seg_off_t=None, stat
                                          int(skip_mask), _tp(xe_t), n_x, _tp(ye_t), n_y, float(sigma), int(power),
                                          _tp(out_t), _stream()))
     return out_t
+
+
+def sliced_wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, dirs_t, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+    """sliced_wasserstein_batch on device tensors (dirs_t: (M, 2) float64, resident): one launch on torch's current stream,
+    nothing allocated when out_t and status_t are given.  out_t is NaN where status_t != 0.  The directions cannot be
+    looked at here: validate them on the host before the upload."""
+    import torch
+    ctx = ctx or get_ctx()
+    if dirs_t.dim() != 2 or dirs_t.shape[1] != 2 or dirs_t.dtype != torch.float64 or not dirs_t.is_contiguous():
+        raise _lib.TdaError("libtdaeeg error 1: dirs_t must be a contiguous (M, 2) float64 tensor")
+    n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
+    if out_t is None:
+        out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
+    if status_t is None:
+        status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
+    ctx.check(ctx.lib.tda_sliced_wasserstein_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
+                                                       _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
+                                                       _tp(dirs_t), dirs_t.shape[0], _tp(out_t), _tp(status_t), _stream()))
+    return out_t, status_t
 
 
 def group_table(seg_off_t, n):

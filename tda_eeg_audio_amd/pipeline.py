@@ -18,6 +18,7 @@ from . import engine
 RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG features per recording-band
 CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
 BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
+SLC_COLS = 2              # Workspace(sliced=dirs).slc: [s_h0, s_h1], the means of the sliced Wasserstein distances
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
@@ -26,8 +27,14 @@ class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None):
-        """images=(xe, ye, sigma, power): run_step also fills `img` (n_seg, 3, n_y, n_x): per group the mean persistence
+                 landscapes=None, images=None, sliced=None):
+        """sliced=dirs, an (M, 2) array-like of directions (c_k, s_k), 1 <= M <= TDA_MAX_DIRECTIONS, finite: run_step also
+        fills `s0` / `s1` (n_win), the sliced Wasserstein distances of the H0 / H1 diagram pairs of every window over
+        these directions (engine.sliced_wasserstein_dev; include/tdaeeg.h has the definition; status words `ss0` / `ss1`),
+        and `slc` (n_seg, 2): per group their np.nanmean under the rule of `bott` -- a window whose audio cloud is
+        degenerate or too large, or whose pair has a status, counts as NaN.  The table is validated and uploaded once,
+        here.  `result` is the same either way.
+        images=(xe, ye, sigma, power): run_step also fills `img` (n_seg, 3, n_y, n_x): per group the mean persistence
         image of the EEG H0, the EEG H1 and the audio H1 diagrams of its windows on the float64 birth edges xe (n_x + 1) and
         persistence edges ye (n_y + 1) (engine.image_mean_dev; include/tdaeeg.h has the definition).  Windows and the audio
         mask are those of `land`.  The edges are uploaded once, here.  `result` is the same either way.
@@ -75,6 +82,15 @@ class Workspace:
             self.bs0 = torch.empty(n_win, dtype=torch.int32, device=device)
             self.bs1 = torch.empty(n_win, dtype=torch.int32, device=device)
             self.bott = torch.empty((self.n_seg, BOTT_COLS), **f64)
+        self.sliced, self.sliced_dirs = None, None
+        self.s0 = self.s1 = self.ss0 = self.ss1 = self.slc = None
+        if sliced is not None:
+            self.sliced = engine._directions(sliced)
+            self.sliced_dirs = torch.from_numpy(self.sliced).to(device)
+            self.s0 = torch.empty(n_win, **f64); self.s1 = torch.empty(n_win, **f64)
+            self.ss0 = torch.empty(n_win, dtype=torch.int32, device=device)
+            self.ss1 = torch.empty(n_win, dtype=torch.int32, device=device)
+            self.slc = torch.empty((self.n_seg, SLC_COLS), **f64)
         self.landscapes, self.land, self.land_grid, self.land_levels = None, None, None, 0
         if landscapes is not None:
             grid, levels = landscapes
@@ -136,6 +152,10 @@ class Workspace:
             for name in ("b0", "b1", "bs0", "bs1"):
                 setattr(v, name, getattr(self, name)[:n_win])
             v.bott = self.bott[:n_seg]
+        if self.sliced is not None:
+            for name in ("s0", "s1", "ss0", "ss1"):
+                setattr(v, name, getattr(self, name)[:n_win])
+            v.slc = self.slc[:n_seg]
         if self.land is not None:
             v.land_sets = self.land_sets[:, :n_seg]
             v.land = v.land_sets.permute(1, 0, 2, 3)
@@ -234,6 +254,17 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         for col, (b, bs) in enumerate(((ws.b0, ws.bs0), (ws.b1, ws.bs1))):
             seg_mean = engine.segment_nanmean_dev(torch.where(out | (bs != 0), nan, b), ws.seg_off, ctx=ctx)
             ws.bott[:, col].copy_(seg_mean)
+    if getattr(ws, "sliced", None) is not None:
+        stage("sliced_h0", lambda: engine.sliced_wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0, ws.sliced_dirs,
+                                                                 out_t=ws.s0, status_t=ws.ss0, ctx=ctx))
+        stage("sliced_h1", lambda: engine.sliced_wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1, ws.sliced_dirs,
+                                                                 out_t=ws.s1, status_t=ws.ss1, ctx=ctx))
+        # the rule of ws.bott: masked on the device, then one nanmean launch per leg
+        out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
+        for col, (d, ds) in enumerate(((ws.s0, ws.ss0), (ws.s1, ws.ss1))):
+            seg_mean = engine.segment_nanmean_dev(torch.where(out | (ds != 0), nan, d), ws.seg_off, ctx=ctx)
+            ws.slc[:, col].copy_(seg_mean)
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -547,4 +578,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (a Workspace(correlations=True) has one more, "temporal_corr", after "finish"; a Workspace(bottleneck=True) two,
 # "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1"; a Workspace(landscapes=(grid, levels)) one, "landscape",
-# after "finish" and "temporal_corr"; a Workspace(images=(xe, ye, sigma, power)) one, "image", after "landscape")
+# after "finish" and "temporal_corr"; a Workspace(images=(xe, ye, sigma, power)) one, "image", after "landscape"; a
+# Workspace(sliced=dirs) two, "sliced_h0" and "sliced_h1", after the bottleneck stages)

@@ -36,6 +36,9 @@ windows the Wasserstein means of the rows run over.
 With landscapes=(grid, levels) the same passes also return land_h (n_rec, 5, 3, levels + 1, n_grid): per (recording, band)
 the mean persistence landscape and mean Betti curve of the EEG H0, EEG H1 and audio H1 diagrams of its windows
 (pipeline.Workspace(landscapes=...)); NaN for a recording without a window.
+With sliced=dirs, an (M, 2) table of directions, they also return slc_h (n_rec, 5, 2): per (recording, band) the means of the
+sliced Wasserstein distances of the H0 and of the H1 diagram pairs (pipeline.Workspace(sliced=dirs)), over the same windows
+as bott_h; NaN for a recording without a window.
 With images=(xe, ye, sigma, power) they also return img_h (n_rec, 5, 3, n_y, n_x): per (recording, band) the mean persistence
 image of the same three diagram sets (pipeline.Workspace(images=...)); NaN for a recording without a window.
 """
@@ -59,7 +62,7 @@ class _ShardedPass:
       _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
       _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
-      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"], st["img"])
+      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"], st["img"], st["slc"])
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
                                     without a window (nothing to verify)
       _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
@@ -67,7 +70,7 @@ class _ShardedPass:
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
-    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None, images=None):
+    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None, images=None, sliced=None):
         self.ctx = ctx or get_ctx()
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
@@ -80,6 +83,10 @@ class _ShardedPass:
         if images is not None:
             from . import engine
             self.images = engine.image_args(*images)
+        self.sliced, self.slc_h = None, None
+        if sliced is not None:
+            from . import engine
+            self.sliced = engine._directions(sliced)
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -113,7 +120,7 @@ class _ShardedPass:
 
     def run(self, raw_h, second_h, rows_h=None):
         """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
-        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=..., self.img_h with images=...)."""
+        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=..., self.img_h with images=..., self.slc_h with sliced=...)."""
         import torch
         self.ranges = self._begin(raw_h, second_h)
         n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
@@ -127,6 +134,8 @@ class _ShardedPass:
             self.land_h = torch.empty((n_rec, nb) + self._land_shape(), dtype=torch.float64).pin_memory()
         if self.images is not None and (self.img_h is None or self.img_h.shape[0] != n_rec):
             self.img_h = torch.empty((n_rec, nb) + self._img_shape(), dtype=torch.float64).pin_memory()
+        if self.sliced is not None and (self.slc_h is None or self.slc_h.shape[0] != n_rec):
+            self.slc_h = torch.empty((n_rec, nb, pipeline.SLC_COLS), dtype=torch.float64).pin_memory()
         pend = []
         try:
             for i, (r0, r1) in enumerate(self.ranges):
@@ -152,6 +161,8 @@ class _ShardedPass:
                         self.land_h[r0:r1].copy_(st["land"][:r1 - r0], non_blocking=True)
                     if self.images is not None:
                         self.img_h[r0:r1].copy_(st["img"][:r1 - r0], non_blocking=True)
+                    if self.sliced is not None:
+                        self.slc_h[r0:r1].copy_(st["slc"][:r1 - r0], non_blocking=True)
                     self._more_back(st, r0, r1, True)
                     st["down"].record(self.back)
                 pend.append(i)
@@ -193,6 +204,8 @@ class _ShardedPass:
                     self.land_h[r0:r1].copy_(st["land"][:r1 - r0])
                 if self.images is not None:
                     self.img_h[r0:r1].copy_(st["img"][:r1 - r0])
+                if self.sliced is not None:
+                    self.slc_h[r0:r1].copy_(st["slc"][:r1 - r0])
                 self._more_back(st, r0, r1, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
@@ -207,17 +220,19 @@ class RecordingPass(_ShardedPass):
 
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
                  max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
-                 landscapes=None, images=None):
+                 landscapes=None, images=None, sliced=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
         feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
         drivers.DETAILED_COLUMNS[8:].  bottleneck=True: `run` also fills self.bott_h, pinned (n_rec, n_bands, 2): the means
         [b_h0, b_h1] of the bottleneck distances per (recording, band).  landscapes=(grid, levels): `run` also fills self.land_h,
         pinned (n_rec, n_bands, 3, levels + 1, n_grid): the group means of pipeline.Workspace(landscapes=...).
         images=(xe, ye, sigma, power): `run` also fills self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x): the group means of
-        pipeline.Workspace(images=...).  The rows are the same either way."""
+        pipeline.Workspace(images=...).  sliced=dirs ((M, 2) directions): `run` also fills self.slc_h, pinned
+        (n_rec, n_bands, 2): the means [s_h0, s_h1] of the sliced Wasserstein distances per (recording, band).  The rows are
+        the same either way."""
         import os
         import torch
-        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images)
+        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images, sliced)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -238,7 +253,9 @@ class RecordingPass(_ShardedPass):
             y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
             aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
             ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
-                                  bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images),
+                                  bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images,
+                                  sliced=self.sliced),
+            slc=torch.empty((S, nb, pipeline.SLC_COLS), **f64) if self.sliced is not None else None,
             corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
             bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
             land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
@@ -293,6 +310,8 @@ class RecordingPass(_ShardedPass):
             st["land"].copy_(st["ws"].land.unflatten(0, (nb, self.S)).transpose(0, 1))
         if self.images is not None:
             st["img"].copy_(st["ws"].img.unflatten(0, (nb, self.S)).transpose(0, 1))
+        if self.sliced is not None:
+            st["slc"].copy_(st["ws"].slc.view(nb, self.S, pipeline.SLC_COLS).transpose(0, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -388,14 +407,15 @@ class RaggedRecordingPass(_ShardedPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None, correlations=False, bottleneck=False, landscapes=None, images=None):
+                 plan=None, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None):
         """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
         recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2);
         landscapes=(grid, levels): the same for self.land_h, pinned (n_rec, n_bands, 3, levels + 1, n_grid);
-        images=(xe, ye, sigma, power): the same for self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x)."""
+        images=(xe, ye, sigma, power): the same for self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x);
+        sliced=dirs ((M, 2) directions): the same for self.slc_h, pinned (n_rec, n_bands, 2)."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
-                         correlations, bottleneck, landscapes, images)
+                         correlations, bottleneck, landscapes, images, sliced)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -432,8 +452,9 @@ class RaggedRecordingPass(_ShardedPass):
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
                                     n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
-                                    landscapes=self.landscapes, images=self.images)
+                                    landscapes=self.landscapes, images=self.images, sliced=self.sliced)
             return dict(
+                slc=torch.empty((S, nb, pipeline.SLC_COLS), **f64) if self.sliced is not None else None,
                 corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
                 bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
                 land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
@@ -481,6 +502,12 @@ class RaggedRecordingPass(_ShardedPass):
                 corr.fill_(float("nan"))
             if d["n_live"]:
                 corr.index_copy_(0, d["live"], st["views"][i].corr.view(len(self.bands), d["n_live"], pipeline.CORR_COLS).transpose(0, 1))
+        if self.sliced is not None:
+            slc = st["slc"][:d["n"]]
+            if d["n_live"] < d["n"]:
+                slc.fill_(float("nan"))
+            if d["n_live"]:
+                slc.index_copy_(0, d["live"], st["views"][i].slc.view(len(self.bands), d["n_live"], pipeline.SLC_COLS).transpose(0, 1))
         if self.bottleneck:
             bott = st["bott"][:d["n"]]
             if d["n_live"] < d["n"]:
@@ -534,7 +561,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None, images=None):
+                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -544,7 +571,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
                          max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
-                         bottleneck=bottleneck, landscapes=landscapes, images=images)
+                         bottleneck=bottleneck, landscapes=landscapes, images=images, sliced=sliced)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)

@@ -239,6 +239,37 @@ def persistence_image(dgm, xe, ye, sigma, power=1):
     return engine.image_batch(rows, cnt, xe, ye, sigma, power)[0]
 
 
+def default_directions(M=50):
+    """(M, 2) float64 table (cos theta_k, sin theta_k), theta_k = -pi/2 + k * pi / M: the directions of
+    persim.sliced_wasserstein, computed by numpy on the host (the kernel never evaluates a trigonometric function)."""
+    M = int(M)
+    if M < 1:
+        raise ValueError("M must be >= 1")
+    theta = -np.pi / 2 + np.arange(M) * np.pi / M
+    return np.stack([np.cos(theta), np.sin(theta)], axis=1)
+
+
+def sliced_wasserstein_kernel(d, sigma=1.0):
+    """exp(-d / (2 * sigma**2)) of a sliced Wasserstein distance or Gram matrix d (engine.sliced_wasserstein_gram): the
+    positive-definite kernel on diagrams of Carriere, Cuturi and Oudot (2017), for SVMs and kernel PCA.  Plain numpy."""
+    return np.exp(-np.asarray(d, dtype=np.float64) / (2.0 * float(sigma) ** 2))
+
+
+def safe_sliced_wasserstein(dgm1, dgm2, dirs=None, M=50):
+    """Sliced Wasserstein distance of two diagrams cleaned as safe_wasserstein cleans them (include/tdaeeg.h) over the
+    (M, 2) direction table dirs; dirs=None means default_directions(M).  NaN on any failure."""
+    if _ACTIVE is not None:
+        return _ACTIVE.add_sliced(dgm1, dgm2, dirs, M)
+    try:
+        d = default_directions(M) if dirs is None else dirs
+        ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+        rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+        out, st = engine.sliced_wasserstein_batch(ra, ca, rb, cb, d, want_status=True)
+        return float(out[0]) if st[0] == 0 else np.nan
+    except Exception:
+        return np.nan
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -294,7 +325,7 @@ class DeferredVector(DeferredArray):
 
 
 class DeferredScalar(_Deferred):
-    """The value of a queued safe_wasserstein or safe_bottleneck call."""
+    """The value of a queued safe_wasserstein, safe_bottleneck or safe_sliced_wasserstein call."""
     __slots__ = ()
 
     def __float__(self):
@@ -339,7 +370,7 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, extract_features, persistence_landscape, betti_curve and
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_sliced_wasserstein, extract_features, persistence_landscape, betti_curve and
     persistence_image
     queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
@@ -351,6 +382,7 @@ class batch:
     def __init__(self):
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
         self.imgs = []
+        self.spairs = []              # safe_sliced_wasserstein: (dgm1, dgm2, direction table, deferred value)
 
     def __enter__(self):
         global _ACTIVE
@@ -387,6 +419,15 @@ class batch:
         self.bpairs.append((a, b, s))
         return s
 
+    def add_sliced(self, a, b, dirs, M):
+        s = DeferredScalar(self)
+        try:
+            d = np.ascontiguousarray(default_directions(M) if dirs is None else dirs, dtype=np.float64)
+        except Exception:
+            d = None                                # a malformed table: NaN for this pair alone
+        self.spairs.append((a, b, d, s))
+        return s
+
     def add_features(self, dgm):
         f = DeferredFeatures(self)
         self.feats.append((dgm, f))
@@ -412,6 +453,7 @@ class batch:
         clouds, dms, pairs, feats, bpairs, lands = self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
         imgs, self.imgs = self.imgs, []
+        spairs, self.spairs = self.spairs, []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -461,6 +503,25 @@ class batch:
                         g[2]._value = float(out[i]) if st[i] == 0 else np.nan
             except Exception:
                 pass
+        if spairs:
+            # one launch per direction table; a malformed pair or table is NaN by itself
+            groups = {}
+            for p in spairs:
+                p[3]._value = np.nan
+                try:
+                    g = (_clean_pair_diagram(self._resolve(p[0])), _clean_pair_diagram(self._resolve(p[1])), p[3])
+                    groups.setdefault((p[2].shape, p[2].tobytes()), (p[2], []))[1].append(g)
+                except Exception:
+                    pass
+            for d, good in groups.values():
+                try:
+                    ra, ca = engine.pack_diagrams([g[0] for g in good])
+                    rb, cb = engine.pack_diagrams([g[1] for g in good])
+                    out, st = engine.sliced_wasserstein_batch(ra, ca, rb, cb, d, want_status=True)
+                    for i, g in enumerate(good):
+                        g[2]._value = float(out[i]) if st[i] == 0 else np.nan
+                except Exception:
+                    pass
         if feats:
             rows, cnt = engine.pack_diagrams([np.asarray(self._resolve(f[0]), dtype=np.float64) for f in feats])
             F = engine.features_batch(rows, cnt)
