@@ -148,7 +148,7 @@ extern "C" __attribute__((visibility("default"))) int tda_profile_read(unsigned 
 
 struct SweepShared {
     u64 alive[8];
-    int k0, merges, status, clen, k1, nk, more;
+    int cov_min[2], status, spare, k1, nk, more;     // cov_min: the coverage scan's minimum, a word per round parity
 };
 
 typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
@@ -1674,7 +1674,7 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         }
         if (tid < 256) adjc[tid] = 0ull;
         if (tid == 0) {
-            lcnt[0] = 0u; lcnt[1] = 0xffffffffu; lcnt[2] = 0u; shared->clen = 0x7fffffff;
+            lcnt[0] = 0u; lcnt[1] = 0xffffffffu; lcnt[2] = 0u; shared->cov_min[0] = 0x7fffffff;
             if (lcnt[3]) shared->status = TDA_WIN_NOT_CONVERGED;          // (sampled by ONE thread: the verdict is uniform)
         }
         __syncthreads();
@@ -1683,44 +1683,65 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         // (adjacency only grows) at its own time.  Then no remaining edge is a candidate: no component can merge,
         // no class can be born, and with nothing alive nothing can die -- the rest of the filtration adds no row.
         if (quiet) {
-            const int from = r0 + clen;
-            bool covered = true;
+            int from = r0 + clen;                 // the adjacency rows hold exactly the edges of rank below `from`
             // every thread walks its own residue class of the remaining edges and remembers where it stopped: an edge
             // that is covered stays covered, so no edge is looked at twice over all the checks of a window
             int rr = (NT & (NT - 1)) == 0 ? from + ((tid - from) & (NT - 1)) : from + (((tid - from) % NT) + NT) % NT;
             rr = rr > cov_next ? rr : cov_next;
-            while (rr < Ev) {
-                const u32 pk = ord[rr];
-                const int ea = (int)(pk >> 8), eb = (int)(pk & 255u);
-                u64 common = adj[2 * ea] & adj[2 * eb];
-                if (NVW == 2) common |= adj[2 * ea + 1] & adj[2 * eb + 1];
-                if (common == 0ull) { covered = false; break; }
-                rr += NT;
-            }
-            cov_next = rr;
-            // the FIRST edge without a common neighbour, over the whole workgroup (every residue class stopped at its
-            // own first one): nothing can happen before it
-            {
-                const u32 wmin = wave_min_u32_dpp(covered ? 0x7fffffffu : (u32)rr);
-                if (lane == 0 && wmin != 0x7fffffffu) atomicMin(reinterpret_cast<unsigned int*>(&shared->clen), wmin);
-            }
-            __syncthreads();
-            const int ru = uni(shared->clen);
-            if (ru >= Ev) { PROF_COUNT(25, 1); PROF_MARK(7); break; }
-            // ... so the edges up to it only join the adjacency rows, and the next chunk starts AT it: whole chunks of
-            // the long-edge tail that hold no candidate are never swept
-            if (ru > from) {
+            int ru;
+            for (int round = 0;; ++round) {
+                PROF_COUNT(41, 1);
+                bool covered = true;
+                while (rr < Ev) {
+                    const u32 pk = ord[rr];
+                    const int ea = (int)(pk >> 8), eb = (int)(pk & 255u);
+                    u64 common = adj[2 * ea] & adj[2 * eb];
+                    if (NVW == 2) common |= adj[2 * ea + 1] & adj[2 * eb + 1];
+                    if (common == 0ull) { covered = false; break; }
+                    rr += NT;
+                }
+                // the FIRST edge without a common neighbour, over the whole workgroup (every residue class stopped at
+                // its own first one): nothing can happen before it.  The rounds alternate between two words: the one
+                // of the next round is reset between this round's two barriers, after its last reader passed the
+                // second barrier of the round before
+                int* cmin = &shared->cov_min[round & 1];
+                {
+                    const u32 wmin = wave_min_u32_dpp(covered ? 0x7fffffffu : (u32)rr);
+                    if (lane == 0 && wmin != 0x7fffffffu) atomicMin(reinterpret_cast<unsigned int*>(cmin), wmin);
+                }
+                __syncthreads();
+                ru = uni(*cmin);
+                // ru == from: the rows held every edge before ru when its owner tested it, so the test was exact for
+                // ru's own time -- a true candidate (a merge or a birth), and the next chunk starts AT it
+                if (ru >= Ev || ru == from) break;
+                if (tid == 0) shared->cov_min[(round + 1) & 1] = 0x7fffffff;     // (only a round that goes on has a next one)
+                // ... otherwise the rows were stale for ru: the edges in front of it only join the adjacency rows (whole
+                // chunks of the long-edge tail that hold no candidate are never swept), and ru -- like every other stop,
+                // all of them behind it -- is tested again against rows that now hold every edge before it.  An edge
+                // that the skipped ones cover is a false alarm, and the minimum moves on without a chunk
                 for (int r2 = from + tid; r2 < ru; r2 += NT) {
                     const u32 pk = ord[r2];
                     const int ea = (int)(pk >> 8), eb = (int)(pk & 255u);
                     atomicOr(reinterpret_cast<unsigned long long*>(&adj[2 * ea + (eb >> 6)]), 1ull << (eb & 63));
                     atomicOr(reinterpret_cast<unsigned long long*>(&adj[2 * eb + (ea >> 6)]), 1ull << (ea & 63));
-                    // NARROW: no chunk will clear the vectors of the edges that are skipped (ord[r2] is read: dead now)
-                    if constexpr (NARROW) { if (r2 < ((psi_bytes - 2 * (E - ru)) >> 2)) psi[r2] = pzero<W, WT>(); }
                 }
                 PROF_COUNT(35, ru - from);
-                clen = ru - r0;                                  // (the loop advances r0 by clen)
+                from = ru;
                 __syncthreads();
+                if (round == 31) break;       // (every round moves ru on, so this ends anyway; a chunk at ru is always right)
+            }
+            cov_next = rr;
+            if (ru >= Ev) { PROF_COUNT(25, 1); PROF_MARK(7); break; }
+            PROF_COUNT(42, 1);
+            if (from > r0 + clen) {
+                // NARROW: no chunk will clear the vectors of the edges that were skipped (their ord entries are dead
+                // now): cleared against the cap of the chunk that starts at `from`
+                if constexpr (NARROW) {
+                    const int cap = (psi_bytes - 2 * (E - from)) >> 2;
+                    for (int r2 = r0 + clen + tid; r2 < (from < cap ? from : cap); r2 += NT) psi[r2] = pzero<W, WT>();
+                    __syncthreads();
+                }
+                clen = from - r0;                                // (the loop advances r0 by clen)
             }
         }
         PROF_MARK(7);
