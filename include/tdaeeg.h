@@ -656,6 +656,62 @@ tda_status tda_match_rows_dev(tda_ctx* ctx, const double* out, const int* pairs,
                               int n_seg_a, int n_col, const int* own_col, const int* status_a, const int* seg_off_a,
                               double* rows, int* seg_flags, void* stream);
 
+/* ---- Sliced Wasserstein distance from prepared diagrams: sort once, merge per pair ----
+ * The definition is the sliced Wasserstein text above, unchanged.  For a pair (A, B) and a direction, the sorted
+ * projections of A' are the merge of two lists that depend on one diagram each: the sorted projections of A's rows and
+ * the sorted projections of B's diagonal images.  tda_sliced_prepare_dev makes both lists of every diagram and direction
+ * once; the other two entry points merge them per pair.  A merge of two sorted lists is the sorted list of their union,
+ * so every u_i, v_i and t_i is the float64 of tda_sliced_wasserstein_batch_dev, and the additions are made in that
+ * kernel's order (rank e = 64 r + lane belongs to `lane`; a lane adds its ranks r = 0, 1, .. in turn, only those with
+ * e < N; the lanes are combined by the butterfly lane ^ 1, 2, .., 32; one wave adds the L_k as k = lane, lane + 64, the
+ * same butterfly, then divides by n_dirs): a prepared pair returns the BYTES tda_sliced_wasserstein_batch_dev returns
+ * for the same pair and directions.
+ *
+ * tda_sliced_prepare_dev.  dgm (n_dgm, cap, 2), cnt (n_dgm), dirs (n_dirs, 2) as above.  Per diagram: cnt is clamped to
+ * [0, cap], rows with a non-finite entry are dropped, an empty diagram becomes {(0, 0)}; m rows remain.  For every
+ * direction k two ascending lists of m float64 are written: kind 0, the projections (c * b) + (s * d) of the rows; kind 1,
+ * the projections (c * h) + (s * h) of the images, h = 0.5 * (b + d) -- the formula of the text above, no multiply-add and
+ * not (c + s) * h.
+ * Table.  slot_off is (n_dgm + 1) int64, made by the caller, non-decreasing: diagram i owns the slot
+ * [slot_off[i], slot_off[i + 1]) of s_i rows.  Its region of `table` starts at double 2 * n_dirs * slot_off[i]; element
+ * ((2 k + kind) * s_i + rank) of the region is the value of direction k, kind and rank.  Only the ranks < m are defined;
+ * the rest of a region is not written.  `table` holds 2 * n_dirs * table_rows doubles.  All index arithmetic is size_t.
+ * m_clean (n_dgm) int32: m for a diagram that was prepared; -1 where m > TDA_SW_MAX_POINTS, m > s_i, slot_off[i + 1] >
+ * table_rows or the slot is not a slot (negative start or length): such a diagram writes nothing to the table.
+ * Limits: 1 <= n_dirs <= TDA_MAX_DIRECTIONS and cap >= 1; anything else is TDA_ERR_INVALID and nothing is launched.
+ *
+ * tda_sliced_prepared_pairs_dev.  Two prepared sets (table, slot_off, m_clean, number of diagrams), made with the SAME
+ * direction table of n_dirs rows; idx_a / idx_b (n_pairs) int32, NULL = identity.  out (n_pairs) float64, NaN where
+ * status != 0; status (n_pairs) int32.  A pair with m_clean < 0 on either side or N = m + n > TDA_SW_MAX_POINTS gets NaN
+ * and TDA_WIN_TOO_LARGE.  An index outside [0, n_a) / [0, n_b): tda_sliced_wasserstein_batch_dev does not look at its
+ * indices (it is not told n_a and n_b; only the host form rejects them), so such an index is the caller's error there and
+ * here.  This entry point knows the sizes and does not read outside the tables for it: the pair gets NaN and
+ * TDA_WIN_NO_PAIR.  1 <= n_dirs <= TDA_MAX_DIRECTIONS, or TDA_ERR_INVALID.
+ *
+ * tda_sliced_matrix_dev.  tda_wasserstein_matrix_dev with the sliced distance in the place of the Wasserstein distance:
+ * the same tables (seg_off_a / cls_a over the A diagrams, the B groups class-major in seg_off_b, status_b), the same
+ * pairing rules (by position within a group; no pair where the B group is shorter, the B diagram carries
+ * TDA_WIN_DEGENERATE, the class is out of range or a table entry points outside its table) and the same entry: out[g, c]
+ * the mean over the pairs (numpy's pairwise tree; the pairs of an entry are its first `pairs` positions, a pair with a
+ * status counts as NaN; no pair: NaN), pairs[g, c] their number, flags[g, c] the OR of their status words without
+ * TDA_WIN_NO_PAIR and TDA_WIN_DEGENERATE.  The value of a pair is tda_sliced_prepared_pairs_dev's, bit for bit.  A group of
+ * more than 64 diagrams gets NaN, 0 pairs and TDA_WIN_TOO_LARGE in every column.  out float64, pairs int32, flags int32,
+ * each (n_seg_a, n_col) row-major; every word is written by exactly one workgroup of the call, nothing has to be cleared
+ * before it, no atomics, no per-pair array.
+ * All three: device pointers only, enqueue-only on `stream`, no allocation. */
+tda_status tda_sliced_prepare_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm,
+                                  const double* dirs, int n_dirs, const long long* slot_off,
+                                  double* table, long long table_rows, int* m_clean, void* stream);
+tda_status tda_sliced_prepared_pairs_dev(tda_ctx* ctx, const double* table_a, const long long* slot_off_a, const int* m_a,
+                                         int n_a, const double* table_b, const long long* slot_off_b, const int* m_b,
+                                         int n_b, const int* idx_a, const int* idx_b, int n_pairs, int n_dirs,
+                                         double* out, int* status, void* stream);
+tda_status tda_sliced_matrix_dev(tda_ctx* ctx, const double* table_a, const long long* slot_off_a, const int* m_a, int n_a,
+                                 const int* seg_off_a, int n_seg_a, const int* cls_a,
+                                 const double* table_b, const long long* slot_off_b, const int* m_b, int n_b,
+                                 const int* seg_off_b, int n_cls, int n_col, const int* status_b, int n_dirs,
+                                 double* out, int* pairs, int* flags, void* stream);
+
 /* ---- timing helper ------------------------------------------------------------
  * HIP-event timing on the stream the kernels are launched on (bench.py roofline). */
 tda_status tda_event_create(tda_ctx* ctx, void** ev);

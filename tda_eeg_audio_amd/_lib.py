@@ -111,6 +111,11 @@ SYMBOLS = {
                                               c_vp]),
     "tda_sliced_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, _I, c_vp,
                                           c_vp]),
+    "tda_sliced_prepare_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp, C.c_longlong, c_vp, c_vp]),
+    "tda_sliced_prepared_pairs_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, c_vp,
+                                           c_vp]),
+    "tda_sliced_matrix_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, _I, _I, c_vp, _I,
+                                   c_vp, c_vp, c_vp, c_vp]),
     "tda_landscape_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp]),
     "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
     "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),

@@ -516,6 +516,49 @@ tda_status tda_match_rows_dev(tda_ctx* ctx, const double* out, const int* pairs,
                              (hipStream_t)stream);
 }
 
+tda_status tda_sliced_prepare_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const double* dirs,
+                                  int n_dirs, const long long* slot_off, double* table, long long table_rows, int* m_clean,
+                                  void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm); CHECK_NONNEG(ctx, table_rows);
+    if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, dirs); CHECK_PTR(ctx, slot_off); CHECK_PTR(ctx, m_clean);
+                 if (table_rows) CHECK_PTR(ctx, table); }
+    return launch_sliced_prepare(ctx, dgm, cnt, cap, n_dgm, dirs, n_dirs, slot_off, table, table_rows, m_clean,
+                                 (hipStream_t)stream);
+}
+
+tda_status tda_sliced_prepared_pairs_dev(tda_ctx* ctx, const double* table_a, const long long* slot_off_a, const int* m_a,
+                                         int n_a, const double* table_b, const long long* slot_off_b, const int* m_b, int n_b,
+                                         const int* idx_a, const int* idx_b, int n_pairs, int n_dirs, double* out, int* status,
+                                         void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_b);
+    if (n_pairs) { CHECK_PTR(ctx, out); CHECK_PTR(ctx, status); }
+    if (n_pairs && n_a) { CHECK_PTR(ctx, table_a); CHECK_PTR(ctx, slot_off_a); CHECK_PTR(ctx, m_a); }
+    if (n_pairs && n_b) { CHECK_PTR(ctx, table_b); CHECK_PTR(ctx, slot_off_b); CHECK_PTR(ctx, m_b); }
+    return launch_sliced_prepared_pairs(ctx, table_a, slot_off_a, m_a, n_a, table_b, slot_off_b, m_b, n_b, idx_a, idx_b,
+                                        n_pairs, n_dirs, out, status, (hipStream_t)stream);
+}
+
+tda_status tda_sliced_matrix_dev(tda_ctx* ctx, const double* table_a, const long long* slot_off_a, const int* m_a, int n_a,
+                                 const int* seg_off_a, int n_seg_a, const int* cls_a, const double* table_b,
+                                 const long long* slot_off_b, const int* m_b, int n_b, const int* seg_off_b, int n_cls,
+                                 int n_col, const int* status_b, int n_dirs, double* out, int* pairs, int* flags, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_seg_a); CHECK_NONNEG(ctx, n_b); CHECK_NONNEG(ctx, n_cls);
+    CHECK_NONNEG(ctx, n_col);
+    if (n_dirs < 1 || n_dirs > TDA_MAX_DIRECTIONS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_dirs must be 1..TDA_MAX_DIRECTIONS");
+    if (n_seg_a == 0 || n_col == 0) return TDA_OK;
+    CHECK_PTR(ctx, seg_off_a); CHECK_PTR(ctx, cls_a); CHECK_PTR(ctx, out); CHECK_PTR(ctx, pairs); CHECK_PTR(ctx, flags);
+    if (n_a) { CHECK_PTR(ctx, table_a); CHECK_PTR(ctx, slot_off_a); CHECK_PTR(ctx, m_a); }
+    if ((long long)n_cls * n_col >= 0x7fffffffll) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "more than 2^31 - 2 B groups");
+    if (n_b && n_cls) { CHECK_PTR(ctx, table_b); CHECK_PTR(ctx, slot_off_b); CHECK_PTR(ctx, m_b); CHECK_PTR(ctx, seg_off_b);
+                        CHECK_PTR(ctx, status_b); }
+    else { n_b = 0; n_cls = 0; }                                       // nothing to pair with: every entry is NaN with 0 pairs
+    return launch_sliced_matrix(ctx, table_a, slot_off_a, m_a, n_a, seg_off_a, n_seg_a, cls_a, table_b, slot_off_b, m_b, n_b,
+                                seg_off_b, n_cls, n_col, status_b, n_dirs, out, pairs, flags, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.

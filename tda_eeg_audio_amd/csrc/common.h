@@ -235,6 +235,14 @@ tda_status launch_bottleneck(tda_ctx*, const double*, const int*, int, const dou
                              const int*, int, double*, int*, hipStream_t);
 tda_status launch_sliced(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*, const int*,
                          int, const double*, int, double*, int*, hipStream_t);
+tda_status launch_sliced_prepare(tda_ctx*, const double*, const int*, int, int, const double*, int, const long long*, double*,
+                                 long long, int*, hipStream_t);
+tda_status launch_sliced_prepared_pairs(tda_ctx*, const double*, const long long*, const int*, int, const double*,
+                                        const long long*, const int*, int, const int*, const int*, int, int, double*, int*,
+                                        hipStream_t);
+tda_status launch_sliced_matrix(tda_ctx*, const double*, const long long*, const int*, int, const int*, int, const int*,
+                                const double*, const long long*, const int*, int, const int*, int, int, const int*, int, double*,
+                                int*, int*, hipStream_t);
 tda_status launch_landscape_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int,
                                  const double*, int, int, double*, hipStream_t);
 tda_status launch_image_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int, const double*,

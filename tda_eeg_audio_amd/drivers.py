@@ -620,7 +620,8 @@ def match_rows_host(dist, own_col, keep=None):
 def match_mismatch_summary(rows, dist, subjects, conditions=None, bands=BANDS, candidates=None, exclude_same_subject=False):
     """Host only: the per-band statistics of the match-mismatch matrix of recordings.MatchMismatchPass.  rows
     (n_rec, n_bands, 6) [w_own, n_own_pairs, n_valid, n_less, n_equal, null_mean], dist (n_rec, n_bands, n_col), one
-    subject label per recording; candidates: the recording of every column (default: all, in order).  Per band, over the
+    subject label per recording; candidates: the recording of every column (default: all, in order).  The sliced matrix of
+    MatchMismatchPass(sliced=dirs) is a valid input as well: rows = slc_rows_h, dist = slc_dist_h.  Per band, over the
     recordings with a finite w_own and at least one other finite column:
       n, top1 (share of recordings whose true audio has midrank 1 + n_less + n_equal / 2 = 1 among n_valid + 1
       candidates), mean_percentile (mean of (n_less + n_equal / 2) / n_valid: 0 = always the closest, 0.5 = chance),

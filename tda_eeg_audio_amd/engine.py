@@ -14,6 +14,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  from group tables (recordings.ControlPass).
                  wasserstein_matrix_dev / match_rows_dev: every group against every candidate column
                  (recordings.MatchMismatchPass).
+                 sliced_prepare_dev / sliced_wasserstein_prepared_dev / sliced_wasserstein_gram_dev / sliced_matrix_dev:
+                 the sliced Wasserstein distance with every diagram sorted once (MatchMismatchPass(sliced=dirs)).
 """
 import ctypes as C
 
@@ -831,3 +833,123 @@ def match_rows_dev(out_t, pairs_t, flags_t, own_col, rows_t=None, status_a=None,
     ctx.check(ctx.lib.tda_match_rows_dev(ctx.h, _tp(out_t), _tp(pairs_t), _tp(flags_t), n_seg_a, n_col, _tp(own_col),
                                          _tp(status_a), _tp(seg_off_a), _tp(rows_t), _tp(seg_flags), _stream()))
     return rows_t
+
+
+# ------------------------------------------------------------------ sliced Wasserstein from prepared diagrams
+class SlicedTable:
+    """What sliced_prepare_dev leaves on the device: `table` (flat float64, 2 * n_dirs doubles per slot row), `slot_off`
+    ((n_dgm + 1,) int64), `m` ((n_dgm,) int32: rows after cleaning, -1 where a diagram was not prepared) and n_dirs.  Two
+    tables can meet in sliced_wasserstein_prepared_dev / sliced_matrix_dev when they were made with the same directions."""
+
+    def __init__(self, table, slot_off, m, n_dirs):
+        self.table, self.slot_off, self.m, self.n_dirs = table, slot_off, m, int(n_dirs)
+
+    @property
+    def n_dgm(self):
+        return self.m.numel()
+
+
+def sliced_slots_dev(cnt, cap, out=None):
+    """(n_dgm + 1,) int64 slot table of sliced_prepare_dev: the exclusive scan of max(min(cnt, cap), 1), made on the device
+    without a host synchronisation.  Its last element is the number of table rows the diagrams need.  out: a contiguous
+    int64 tensor of n_dgm + 1 elements to fill."""
+    import torch
+    slot_off = torch.empty(cnt.numel() + 1, dtype=torch.int64, device=cnt.device) if out is None else out
+    assert slot_off.dtype == torch.int64 and slot_off.numel() == cnt.numel() + 1 and slot_off.is_contiguous()
+    slot_off[:1] = 0
+    torch.cumsum(torch.clamp(cnt, 1, int(cap)), 0, out=slot_off[1:])
+    return slot_off
+
+
+def sliced_prepare_dev(rows, cnt, dirs_t, table_t=None, slot_off=None, m_t=None, ctx=None):
+    """Sort every diagram once for the sliced Wasserstein distance (tda_sliced_prepare_dev): per diagram and direction of
+    dirs_t ((M, 2) float64, resident, validated on the host before the upload) the ascending projections of its rows and of
+    its diagonal images.  One launch on torch's current stream.  slot_off: (n_dgm + 1,) int64 (default sliced_slots_dev:
+    packed, as many rows as a diagram can have after cleaning); table_t: flat float64 of 2 * M doubles per row (default:
+    n_dgm * cap rows, which holds any slot table of this kind without a look at its total).  Returns a SlicedTable."""
+    import torch
+    ctx = ctx or get_ctx()
+    if dirs_t.dim() != 2 or dirs_t.shape[1] != 2 or dirs_t.dtype != torch.float64 or not dirs_t.is_contiguous():
+        raise _lib.TdaError("libtdaeeg error 1: dirs_t must be a contiguous (M, 2) float64 tensor")
+    n_dgm, cap, n_dirs = rows.shape[0], rows.shape[1], dirs_t.shape[0]
+    assert rows.is_contiguous() and cnt.dtype == torch.int32 and cnt.numel() >= n_dgm
+    if slot_off is None:
+        slot_off = sliced_slots_dev(cnt[:n_dgm], cap)
+    assert slot_off.dtype == torch.int64 and slot_off.is_contiguous() and slot_off.numel() == n_dgm + 1
+    if table_t is None:
+        table_t = torch.empty(2 * n_dirs * n_dgm * cap, dtype=torch.float64, device=rows.device)
+    assert table_t.dtype == torch.float64 and table_t.is_contiguous()
+    table_rows = table_t.numel() // (2 * n_dirs) if n_dirs else 0
+    if m_t is None:
+        m_t = torch.empty(n_dgm, dtype=torch.int32, device=rows.device)
+    assert m_t.dtype == torch.int32 and m_t.is_contiguous() and m_t.numel() >= n_dgm
+    ctx.check(ctx.lib.tda_sliced_prepare_dev(ctx.h, _tp(rows), _tp(cnt), cap, n_dgm, _tp(dirs_t), n_dirs, _tp(slot_off),
+                                             _tp(table_t), table_rows, _tp(m_t), _stream()))
+    return SlicedTable(table_t, slot_off, m_t[:n_dgm], n_dirs)
+
+
+def sliced_wasserstein_prepared_dev(ta, tb, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+    """The sliced Wasserstein distance of pairs of prepared diagrams (SlicedTable ta, tb of the same directions): two
+    merges and a sum per pair and direction, the bytes sliced_wasserstein_dev gives for the same pair.  idx_a / idx_b:
+    int32 device tensors or None (identity).  out_t is NaN where status_t != 0."""
+    import torch
+    ctx = ctx or get_ctx()
+    if ta.n_dirs != tb.n_dirs:
+        raise _lib.TdaError("libtdaeeg error 1: the two tables were prepared with different numbers of directions")
+    n_pairs = ta.n_dgm if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
+    for t in (idx_a, idx_b):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n_pairs)
+    dev = ta.table.device
+    if out_t is None:
+        out_t = torch.empty(n_pairs, dtype=torch.float64, device=dev)
+    if status_t is None:
+        status_t = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.tda_sliced_prepared_pairs_dev(ctx.h, _tp(ta.table), _tp(ta.slot_off), _tp(ta.m), ta.n_dgm, _tp(tb.table),
+                                                    _tp(tb.slot_off), _tp(tb.m), tb.n_dgm, _tp(idx_a), _tp(idx_b), n_pairs,
+                                                    ta.n_dirs, _tp(out_t), _tp(status_t), _stream()))
+    return out_t, status_t
+
+
+def sliced_wasserstein_gram_dev(rows, cnt, dirs_t, ctx=None):
+    """sliced_wasserstein_gram on device tensors by the prepared route: one sliced_prepare_dev, the pairs i < j through
+    sliced_wasserstein_prepared_dev with index lists built on the device, mirrored, zero diagonal; an (n, n) float64
+    device tensor equal to sliced_wasserstein_gram bit for bit (NaN where a pair has a status)."""
+    import torch
+    n = rows.shape[0]
+    G = torch.zeros((n, n), dtype=torch.float64, device=rows.device)
+    t = sliced_prepare_dev(rows, cnt, dirs_t, ctx=ctx)
+    if n > 1:
+        iu = torch.triu_indices(n, n, 1, device=rows.device)
+        d, _ = sliced_wasserstein_prepared_dev(t, t, iu[0].to(torch.int32).contiguous(), iu[1].to(torch.int32).contiguous(), ctx=ctx)
+        G[iu[0], iu[1]] = d
+        G[iu[1], iu[0]] = d
+    return G
+
+
+def sliced_matrix_dev(ta, seg_off_a, cls_a, tb, seg_off_b, status_b, n_col, out_t=None, pairs_t=None, flags_t=None, ctx=None):
+    """wasserstein_matrix_dev with the sliced Wasserstein distance, from prepared diagrams (SlicedTable ta: the A side, tb:
+    the bank): the same tables, pairing rules and entries -- out (n_seg_a, n_col) float64 the mean over the pairs of
+    (group g, column c), pairs and flags int32 -- and the value of a pair is sliced_wasserstein_prepared_dev's."""
+    import torch
+    ctx = ctx or get_ctx()
+    if ta.n_dirs != tb.n_dirs:
+        raise _lib.TdaError("libtdaeeg error 1: the two tables were prepared with different numbers of directions")
+    n_seg_a, n_col = seg_off_a.numel() - 1, int(n_col)
+    n_cls = (seg_off_b.numel() - 1) // n_col if n_col else 0
+    for t in (seg_off_a, cls_a, seg_off_b, status_b):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert seg_off_b.numel() == n_cls * n_col + 1 and cls_a.numel() == n_seg_a and status_b.numel() >= tb.n_dgm
+    dev = ta.table.device
+    if out_t is None:
+        out_t = torch.empty((n_seg_a, n_col), dtype=torch.float64, device=dev)
+    if pairs_t is None:
+        pairs_t = torch.empty((n_seg_a, n_col), dtype=torch.int32, device=dev)
+    if flags_t is None:
+        flags_t = torch.empty((n_seg_a, n_col), dtype=torch.int32, device=dev)
+    for t in (out_t, pairs_t, flags_t):
+        assert t.is_contiguous() and t.numel() >= n_seg_a * n_col
+    ctx.check(ctx.lib.tda_sliced_matrix_dev(ctx.h, _tp(ta.table), _tp(ta.slot_off), _tp(ta.m), ta.n_dgm, _tp(seg_off_a), n_seg_a,
+                                            _tp(cls_a), _tp(tb.table), _tp(tb.slot_off), _tp(tb.m), tb.n_dgm, _tp(seg_off_b),
+                                            n_cls, n_col, _tp(status_b), ta.n_dirs, _tp(out_t), _tp(pairs_t), _tp(flags_t),
+                                            _stream()))
+    return out_t, pairs_t, flags_t

@@ -902,14 +902,23 @@ class MatchMismatchPass(ControlPass):
     upload of the EEG and its band-pass bank, the EEG diagrams (ControlPass's EEG stage), ONE
     engine.wasserstein_matrix_dev launch against the bank and one engine.match_rows_dev launch.  The own audio is a
     column of the bank, so no envelope is uploaded, filtered or taken through Rips per shard.  A recording without an EEG
-    window gets NaN, zero counts and zero pairs; a candidate without an audio window an all-NaN column with 0 pairs."""
+    window gets NaN, zero counts and zero pairs; a candidate without an audio window an all-NaN column with 0 pairs.
+    sliced=dirs, an (M, 2) table of directions (engine._directions validates it; utils.default_directions makes one): the
+    same matrix with the sliced Wasserstein distance (include/tdaeeg.h) in the place of the Wasserstein distance, by the
+    prepared route: after phase 1 the bank's H1 diagrams are sorted once per run (engine.sliced_prepare_dev; the table is
+    sized from one host read of the slot scan's total), and per shard, inside the step the repair redoes, the shard's EEG
+    H1 diagrams are prepared into the buffer set's table, one engine.sliced_matrix_dev launch makes the matrix and one
+    engine.match_rows_dev launch its rows.  `run` then also fills slc_dist_h (n_rec, n_bands, n_col) float64, slc_pairs_h
+    (the same shape, int32) and slc_rows_h (n_rec, n_bands, 6), pinned, with the meaning of dist_h / pairs_h / rows_h.  A
+    status bit of a sliced entry withholds the rows as one of a Wasserstein entry does.  Off by default: rows_h, dist_h and
+    pairs_h are the same bytes with and without it."""
 
     ROW_COLS = MATCH_COLS
     ROW_ZERO = slice(1, 5)              # the counts
 
     def __init__(self, eeg_lengths, env_lengths=None, candidates=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES,
                  n_sets=2, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False):
+                 overlap=0.75, correlations=False, sliced=None):
         import torch
         plan = MatchMismatchPlan(eeg_lengths, env_lengths, candidates, shard_samples, n_ch, len(dict(bands)), fs, window_sec,
                                  overlap, max_windows)
@@ -934,6 +943,43 @@ class MatchMismatchPass(ControlPass):
             st["dist"] = torch.empty((S, nb, self.n_col), dtype=torch.float64, device=dev)
             st["pairs"] = torch.empty((S, nb, self.n_col), dtype=torch.int32, device=dev)
         self.dist_h = self.pairs_h = None
+        # sliced=dirs: the direction table once, per buffer set the EEG side's table and the second matrix
+        self.slc_dirs, self.slc_dirs_t, self.slc_bank, self.slc_bank_table = None, None, None, None
+        self.slc_dist_h = self.slc_pairs_h = self.slc_rows_h = None
+        if sliced is not None:
+            self.slc_dirs = engine._directions(sliced)
+            self.slc_dirs_t = torch.from_numpy(self.slc_dirs).to(dev)
+            self.slc_ready = torch.cuda.Event()
+            M = self.slc_dirs.shape[0]
+            n_e = max((d["n_win"] for d in self.shards), default=0)
+            for st in self.set:
+                cap = st["ws"].eeg.h1_cap
+                st["slc_table"] = torch.empty(2 * M * max(n_e, 1) * cap, dtype=torch.float64, device=dev)
+                st["slc_slot"] = torch.zeros(max(n_e, 1) + 1, dtype=torch.int64, device=dev)
+                st["slc_m"] = torch.empty(max(n_e, 1), dtype=torch.int32, device=dev)
+                st["slc_mat"] = torch.empty(shape, dtype=torch.float64, device=dev)
+                st["slc_mat_pairs"], st["slc_mat_flags"] = (torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(2))
+                st["slc_res"] = torch.empty((max(n_seg, 1), MATCH_COLS), dtype=torch.float64, device=dev)
+                st["slc_seg_flags"] = torch.zeros(max(n_seg, 1), dtype=torch.int32, device=dev)
+                st["slc_dist"] = torch.empty((S, nb, self.n_col), dtype=torch.float64, device=dev)
+                st["slc_pairs"] = torch.empty((S, nb, self.n_col), dtype=torch.int32, device=dev)
+                st["slc_rows"] = torch.empty((S, nb, MATCH_COLS), dtype=torch.float64, device=dev)
+
+    def _phase1(self, env_f):
+        """ControlPass's bank; with sliced=dirs its H1 diagrams are then sorted once (one host read: the rows of the table)."""
+        import torch
+        super()._phase1(env_f)
+        if self.slc_dirs is None:
+            return
+        with torch.cuda.stream(self.bank_stream):
+            M, cap = self.slc_dirs.shape[0], self.bank.h1.shape[1]
+            slot_off = engine.sliced_slots_dev(self.bank.c1, cap)
+            need = 2 * M * int(slot_off[-1])                             # (the read: once per run, not per shard)
+            if self.slc_bank_table is None or self.slc_bank_table.numel() < need:
+                self.slc_bank_table = torch.empty(max(need, 1), dtype=torch.float64, device=self.dev)
+            self.slc_bank = engine.sliced_prepare_dev(self.bank.h1, self.bank.c1, self.slc_dirs_t, table_t=self.slc_bank_table,
+                                                      slot_off=slot_off, ctx=self.ctx)
+            self.slc_ready.record(self.bank_stream)
 
     def _upload(self, st, i, raw_packed_h, env_packed_h):
         r0, r1 = self.ranges[i]
@@ -963,6 +1009,19 @@ class MatchMismatchPass(ControlPass):
                                       self.bank.status, self.n_col, out_t=mat, pairs_t=mp, flags_t=mf, ctx=ctx)
         res = engine.match_rows_dev(mat, mp, mf, d["own_col_e"], rows_t=st["res"][:v.n_seg], status_a=v.eeg.status,
                                     seg_off_a=v.seg_off, seg_flags=v.seg_flags, ctx=ctx)
+        if self.slc_dirs is not None:
+            # the same matrix with the sliced distance: the shard's EEG diagrams sorted once, then merges against the bank
+            torch.cuda.current_stream().wait_event(self.slc_ready)
+            n_e = v.eeg.h1.shape[0]
+            slot = engine.sliced_slots_dev(v.eeg.c1[:n_e], v.eeg.h1.shape[1], out=st["slc_slot"][:n_e + 1])
+            ta = engine.sliced_prepare_dev(v.eeg.h1, v.eeg.c1, self.slc_dirs_t, table_t=st["slc_table"], slot_off=slot,
+                                           m_t=st["slc_m"], ctx=ctx)
+            smat, smp, smf = (st[k].view(-1)[:n].view(v.n_seg, self.n_col) for k in ("slc_mat", "slc_mat_pairs", "slc_mat_flags"))
+            engine.sliced_matrix_dev(ta, v.seg_off, d["cls_e"], self.slc_bank, self.col_seg_off, self.bank.status, self.n_col,
+                                     out_t=smat, pairs_t=smp, flags_t=smf, ctx=ctx)
+            sfl = st["slc_seg_flags"][:v.n_seg]
+            engine.match_rows_dev(smat, smp, smf, d["own_col_e"], rows_t=st["slc_res"][:v.n_seg], seg_flags=sfl, ctx=ctx)
+            v.seg_flags.bitwise_or_(sfl)                                 # a flagged sliced entry withholds the rows too
         if retry != "auto":
             v.flags_host.copy_(v.seg_flags, non_blocking=True)
         return res
@@ -980,18 +1039,41 @@ class MatchMismatchPass(ControlPass):
             n = nb * d["n_live"] * self.n_col
             for dst, key in ((dist, "mat"), (pairs, "mat_pairs")):
                 dst.index_copy_(0, d["live"], st[key].view(-1)[:n].view(nb, d["n_live"], self.n_col).transpose(0, 1))
+        if self.slc_dirs is None:
+            return
+        sdist, spairs, srows = st["slc_dist"][:d["n"]], st["slc_pairs"][:d["n"]], st["slc_rows"][:d["n"]]
+        if d["n_live"] < d["n"]:
+            sdist.fill_(float("nan"))
+            spairs.zero_()
+            srows.fill_(float("nan"))
+            srows[:, :, self.ROW_ZERO] = 0.0
+        if d["n_live"] and res is not None:
+            srows.index_copy_(0, d["live"], st["slc_res"][:nb * d["n_live"]].view(nb, d["n_live"], MATCH_COLS).transpose(0, 1))
+            if self.n_col:
+                n = nb * d["n_live"] * self.n_col
+                for dst, key in ((sdist, "slc_mat"), (spairs, "slc_mat_pairs")):
+                    dst.index_copy_(0, d["live"], st[key].view(-1)[:n].view(nb, d["n_live"], self.n_col).transpose(0, 1))
 
     def _more_back(self, st, r0, r1, non_blocking):
         self.dist_h[r0:r1].copy_(st["dist"][:r1 - r0], non_blocking=non_blocking)
         self.pairs_h[r0:r1].copy_(st["pairs"][:r1 - r0], non_blocking=non_blocking)
+        if self.slc_dirs is not None:
+            self.slc_dist_h[r0:r1].copy_(st["slc_dist"][:r1 - r0], non_blocking=non_blocking)
+            self.slc_pairs_h[r0:r1].copy_(st["slc_pairs"][:r1 - r0], non_blocking=non_blocking)
+            self.slc_rows_h[r0:r1].copy_(st["slc_rows"][:r1 - r0], non_blocking=non_blocking)
 
     def run(self, raw_packed_h, env_packed_h, rows_h=None):
         """raw_packed_h: flat pinned float64, n_ch * sum(L); env_packed_h: flat pinned float64, sum(Le).  Returns rows_h
         (n_rec, n_bands, 6), pinned, and fills self.dist_h (n_rec, n_bands, n_col) float64 and self.pairs_h (the same shape,
-        int32), pinned, in list order; all complete when the call returns."""
+        int32), pinned, in list order -- with sliced=dirs also self.slc_dist_h, self.slc_pairs_h and self.slc_rows_h; all
+        complete when the call returns."""
         import torch
         shape = (self.n_rec, len(self.bands), self.n_col)
         if self.dist_h is None:
             self.dist_h = torch.empty(shape, dtype=torch.float64).pin_memory()
             self.pairs_h = torch.empty(shape, dtype=torch.int32).pin_memory()
+        if self.slc_dirs is not None and self.slc_dist_h is None:
+            self.slc_dist_h = torch.empty(shape, dtype=torch.float64).pin_memory()
+            self.slc_pairs_h = torch.empty(shape, dtype=torch.int32).pin_memory()
+            self.slc_rows_h = torch.empty((self.n_rec, len(self.bands), MATCH_COLS), dtype=torch.float64).pin_memory()
         return super().run(raw_packed_h, env_packed_h, rows_h)
