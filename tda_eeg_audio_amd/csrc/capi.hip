@@ -909,11 +909,17 @@ tda_status tda_temporal_corr_batch(tda_ctx* ctx, const double* fa, const double*
     return s.download();
 }
 
-tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
-                                 const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
-                                 const int* idx_b, int n_pairs, double* out, int* status)
+// The host-pointer twins of the pair distances from their own argument checks on: pointer and size checks, the pair
+// indices, staging (with the direction table when dirs is given) and `dev`, a call of the _dev entry point on the staged
+// PairDev pointers.
+struct PairDev { double *a, *b, *dirs = nullptr, *out; int *ca, *cb, *ia = nullptr, *ib = nullptr, *st; };
+
+extern "C++" {                      // (a template inside the extern "C" block of the ABI)
+template <class Dev>
+static tda_status pair_batch_host(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a, const double* dgm_b,
+                                  const int* cnt_b, int n_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
+                                  const double* dirs, int n_dirs, double* out, int* status, Dev dev)
 {
-    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
     if (n_pairs == 0) return TDA_OK;
     CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, out);
     CHECK_PTR(ctx, status);
@@ -924,18 +930,30 @@ tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* c
     }
     TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_a, *d_b, *d_out; int *d_ca, *d_cb, *d_ia = nullptr, *d_ib = nullptr, *d_st;
-    s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16);
-    s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4);
-    s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16);
-    s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4);
-    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
+    PairDev d;
+    s.add((void**)&d.a, dgm_a, nullptr, (size_t)n_a * cap_a * 16);
+    s.add((void**)&d.ca, cnt_a, nullptr, (size_t)n_a * 4);
+    s.add((void**)&d.b, dgm_b, nullptr, (size_t)n_b * cap_b * 16);
+    s.add((void**)&d.cb, cnt_b, nullptr, (size_t)n_b * 4);
+    if (idx_a) s.add((void**)&d.ia, idx_a, nullptr, (size_t)n_pairs * 4);
+    if (idx_b) s.add((void**)&d.ib, idx_b, nullptr, (size_t)n_pairs * 4);
+    if (dirs) s.add((void**)&d.dirs, dirs, nullptr, (size_t)n_dirs * 16);
+    s.add((void**)&d.out, nullptr, out, (size_t)n_pairs * 8);
+    s.add((void**)&d.st, nullptr, status, (size_t)n_pairs * 4);
     RET_IF(s.upload());
-    RET_IF(tda_wasserstein_batch_dev(ctx, d_a, d_ca, cap_a, d_b, d_cb, cap_b, d_ia, d_ib, n_pairs, d_out, d_st, nullptr));
+    RET_IF(dev(d));
     return s.download();
+}
+}
+
+tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                 const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                 const int* idx_b, int n_pairs, double* out, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
+    return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
+        [&](const PairDev& d) { return tda_wasserstein_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
+                                                                 d.out, d.st, nullptr); });
 }
 
 tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -943,28 +961,9 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
                                 const int* idx_b, int n_pairs, double* out, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
-    if (n_pairs == 0) return TDA_OK;
-    CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, out);
-    CHECK_PTR(ctx, status);
-    if (n_a < 1 || n_b < 1 || cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
-    for (int i = 0; i < n_pairs; ++i) {
-        const int a = idx_a ? idx_a[i] : i, b = idx_b ? idx_b[i] : i;
-        if (a < 0 || a >= n_a || b < 0 || b >= n_b) TDA_FAIL(ctx, TDA_ERR_INVALID, "pair index out of range");
-    }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
-    Stage s(ctx);
-    double *d_a, *d_b, *d_out; int *d_ca, *d_cb, *d_ia = nullptr, *d_ib = nullptr, *d_st;
-    s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16);
-    s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4);
-    s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16);
-    s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4);
-    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_bottleneck_batch_dev(ctx, d_a, d_ca, cap_a, d_b, d_cb, cap_b, d_ia, d_ib, n_pairs, d_out, d_st, nullptr));
-    return s.download();
+    return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
+        [&](const PairDev& d) { return tda_bottleneck_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
+                                                                d.out, d.st, nullptr); });
 }
 
 tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -978,30 +977,9 @@ tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const
     CHECK_PTR(ctx, dirs);
     for (int k = 0; k < 2 * n_dirs; ++k)
         if (!std::isfinite(dirs[k])) TDA_FAIL(ctx, TDA_ERR_INVALID, "directions must be finite");
-    if (n_pairs == 0) return TDA_OK;
-    CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, out);
-    CHECK_PTR(ctx, status);
-    if (n_a < 1 || n_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
-    for (int i = 0; i < n_pairs; ++i) {
-        const int a = idx_a ? idx_a[i] : i, b = idx_b ? idx_b[i] : i;
-        if (a < 0 || a >= n_a || b < 0 || b >= n_b) TDA_FAIL(ctx, TDA_ERR_INVALID, "pair index out of range");
-    }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
-    Stage s(ctx);
-    double *d_a, *d_b, *d_dirs, *d_out; int *d_ca, *d_cb, *d_ia = nullptr, *d_ib = nullptr, *d_st;
-    s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16);
-    s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4);
-    s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16);
-    s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4);
-    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    s.add((void**)&d_dirs, dirs, nullptr, (size_t)n_dirs * 16);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_sliced_wasserstein_batch_dev(ctx, d_a, d_ca, cap_a, d_b, d_cb, cap_b, d_ia, d_ib, n_pairs, d_dirs, n_dirs,
-                                            d_out, d_st, nullptr));
-    return s.download();
+    return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, dirs, n_dirs, out, status,
+        [&](const PairDev& d) { return tda_sliced_wasserstein_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
+                                                                        d.dirs, n_dirs, d.out, d.st, nullptr); });
 }
 
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const double* grid,

@@ -241,8 +241,8 @@ def temporal_corr_batch(feat_a, feat_b, seg_off, status_b=None, cols=SPEARMAN_CO
     return out
 
 
-def wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=None, want_status=False):
-    ctx = ctx or get_ctx()
+def _pair_batch(entry, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status, *extra):
+    """The marshalling of the host-array pair distances: the entry point `entry` with `extra` arguments before out / status."""
     ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
     n_a, cap_a, _ = ra.shape
     n_b, cap_b, _ = rb.shape
@@ -254,29 +254,21 @@ def wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=
     ia = None if idx_a is None else i32(idx_a)
     ib = None if idx_b is None else i32(idx_b)
     out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
-    ctx.check(ctx.lib.tda_wasserstein_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
-                                            ptr(ia), ptr(ib), n_pairs, ptr(out), ptr(st)))
+    ctx.check(entry(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b, ptr(ia), ptr(ib), n_pairs, *extra, ptr(out),
+                    ptr(st)))
     return (out, st) if want_status else out
+
+
+def wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=None, want_status=False):
+    ctx = ctx or get_ctx()
+    return _pair_batch(ctx.lib.tda_wasserstein_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status)
 
 
 def bottleneck_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=None, want_status=False):
     """Bottleneck distance of diagram pairs (include/tdaeeg.h: L-infinity ground cost, (d - b) / 2 to the diagonal, the
     largest matched cost under the best matching); arguments and results as wasserstein_batch."""
     ctx = ctx or get_ctx()
-    ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
-    n_a, cap_a, _ = ra.shape
-    n_b, cap_b, _ = rb.shape
-    if idx_a is None and idx_b is None:
-        assert n_a == n_b
-        n_pairs = n_a
-    else:
-        n_pairs = len(idx_a if idx_a is not None else idx_b)
-    ia = None if idx_a is None else i32(idx_a)
-    ib = None if idx_b is None else i32(idx_b)
-    out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
-    ctx.check(ctx.lib.tda_bottleneck_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
-                                           ptr(ia), ptr(ib), n_pairs, ptr(out), ptr(st)))
-    return (out, st) if want_status else out
+    return _pair_batch(ctx.lib.tda_bottleneck_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status)
 
 
 def landscape_batch(rows, cnt, grid, levels, ctx=None):
@@ -352,20 +344,8 @@ def sliced_wasserstein_batch(rows_a, cnt_a, rows_b, cnt_b, dirs, idx_a=None, idx
     points in all is NaN with status TDA_WIN_TOO_LARGE."""
     ctx = ctx or get_ctx()
     d = _directions(dirs)
-    ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
-    n_a, cap_a, _ = ra.shape
-    n_b, cap_b, _ = rb.shape
-    if idx_a is None and idx_b is None:
-        assert n_a == n_b
-        n_pairs = n_a
-    else:
-        n_pairs = len(idx_a if idx_a is not None else idx_b)
-    ia = None if idx_a is None else i32(idx_a)
-    ib = None if idx_b is None else i32(idx_b)
-    out = np.empty(n_pairs); st = np.empty(n_pairs, np.int32)
-    ctx.check(ctx.lib.tda_sliced_wasserstein_batch(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b,
-                                                   ptr(ia), ptr(ib), n_pairs, ptr(d), d.shape[0], ptr(out), ptr(st)))
-    return (out, st) if want_status else out
+    return _pair_batch(ctx.lib.tda_sliced_wasserstein_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status, ptr(d),
+                       d.shape[0])
 
 
 def sliced_wasserstein_gram(rows, cnt, dirs, ctx=None):
@@ -647,34 +627,29 @@ def segment_nanmean_dev(x_t, seg_off_t, out_t=None, ctx=None):
     return out_t
 
 
-def wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+def _pair_dev(entry, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx, *extra):
+    """The marshalling of the device-tensor pair distances: the entry point `entry` with `extra` arguments before out / status."""
     import torch
-    ctx = ctx or get_ctx()
     n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
     if out_t is None:
         out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
     if status_t is None:
         status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
-    ctx.check(ctx.lib.tda_wasserstein_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
-                                                _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
-                                                _tp(out_t), _tp(status_t), _stream()))
+    ctx.check(entry(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b), _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b),
+                    n_pairs, *extra, _tp(out_t), _tp(status_t), _stream()))
     return out_t, status_t
+
+
+def wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+    ctx = ctx or get_ctx()
+    return _pair_dev(ctx.lib.tda_wasserstein_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx)
 
 
 def bottleneck_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
     """bottleneck_batch on device tensors: one launch on torch's current stream, nothing allocated when out_t and
     status_t are given.  out_t is NaN where status_t != 0."""
-    import torch
     ctx = ctx or get_ctx()
-    n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
-    if out_t is None:
-        out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
-    if status_t is None:
-        status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
-    ctx.check(ctx.lib.tda_bottleneck_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
-                                               _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
-                                               _tp(out_t), _tp(status_t), _stream()))
-    return out_t, status_t
+    return _pair_dev(ctx.lib.tda_bottleneck_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx)
 
 
 def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):
@@ -722,15 +697,8 @@ def sliced_wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, dirs_t, idx_a=None, idx
     ctx = ctx or get_ctx()
     if dirs_t.dim() != 2 or dirs_t.shape[1] != 2 or dirs_t.dtype != torch.float64 or not dirs_t.is_contiguous():
         raise _lib.TdaError("libtdaeeg error 1: dirs_t must be a contiguous (M, 2) float64 tensor")
-    n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
-    if out_t is None:
-        out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
-    if status_t is None:
-        status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
-    ctx.check(ctx.lib.tda_sliced_wasserstein_batch_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[1], _tp(rows_b),
-                                                       _tp(cnt_b), rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
-                                                       _tp(dirs_t), dirs_t.shape[0], _tp(out_t), _tp(status_t), _stream()))
-    return out_t, status_t
+    return _pair_dev(ctx.lib.tda_sliced_wasserstein_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx,
+                     _tp(dirs_t), dirs_t.shape[0])
 
 
 def group_table(seg_off_t, n):

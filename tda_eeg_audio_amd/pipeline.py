@@ -11,6 +11,9 @@ process_file_features (scripts/tda_eeg_classification_v2.py:429-436).
 Everything stays in HBM; each stage is one C-ABI launch on torch's current stream.  torch is
 only the allocator / stream owner here.
 """
+import collections
+import functools
+
 import numpy as np
 
 from . import engine
@@ -20,37 +23,63 @@ CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).co
 BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
 SLC_COLS = 2              # Workspace(sliced=dirs).slc: [s_h0, s_h1], the means of the sliced Wasserstein distances
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
-
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
+
+Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
+
+
+def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None):
+    """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
+    one, in the fixed order corr, bott, land, img, slc.  numpy only.  Workspace, the shard driver and the passes of
+    recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
+      corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
+            against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
+      bott  bottleneck=True: (BOTT_COLS,) np.nanmean of the bottleneck distances of the H0 / H1 diagram pairs
+            (engine.bottleneck_dev) over the windows the Wasserstein means of `result` run over -- a window whose audio
+            cloud is degenerate or too large (cmp:90-91), or whose pair has a status, counts as NaN
+      land  landscapes=(grid, levels): (LAND_SETS, levels + 1, n_grid) mean persistence landscape (levels 1..levels) and
+            mean Betti curve (last row) on the float64 grid, of the EEG H0, the EEG H1 and the audio H1 diagrams
+            (engine.landscape_mean_dev).  The EEG sets average every window of the group, as the feature aggregation does
+            (v2:429-436); the audio set leaves out the windows whose cloud is degenerate or too large; a group without
+            such a window is NaN.  ValueError unless the grid is 1-D with 1..MAX_GRID points and 1 <= levels <= MAX_LANDSCAPES
+      img   images=(xe, ye, sigma, power): (IMG_SETS, n_y, n_x) mean persistence image of the same sets, windows and audio
+            mask on the birth edges xe (n_x + 1) and persistence edges ye (n_y + 1) (engine.image_mean_dev; engine.image_args)
+      slc   sliced=dirs, (M, 2) finite directions, 1 <= M <= TDA_MAX_DIRECTIONS (engine._directions): (SLC_COLS,) np.nanmean
+            of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`"""
+    from . import _lib
+    out = []
+    if correlations:
+        out.append(Output("corr", (CORR_COLS,), None))
+    if bottleneck:
+        out.append(Output("bott", (BOTT_COLS,), None))
+    if landscapes is not None:
+        grid, levels = landscapes
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID or not 1 <= int(levels) <= _lib.MAX_LANDSCAPES:
+            raise ValueError(f"landscapes=(grid, levels): a 1-D grid of 1..{_lib.MAX_GRID} points and 1..{_lib.MAX_LANDSCAPES} levels")
+        out.append(Output("land", (LAND_SETS, int(levels) + 1, grid.shape[0]), (grid, int(levels))))
+    if images is not None:
+        xe, ye, sigma, power = engine.image_args(*images)
+        out.append(Output("img", (IMG_SETS, ye.shape[0] - 1, xe.shape[0] - 1), (xe, ye, sigma, power)))
+    if sliced is not None:
+        out.append(Output("slc", (SLC_COLS,), engine._directions(sliced)))
+    return out
+
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
+    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1")    # per window: two distances, two status words
+    # the buffers and resident tables of the optional outputs: None where the output is off
+    corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
+    land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
+
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None):
-        """sliced=dirs, an (M, 2) array-like of directions (c_k, s_k), 1 <= M <= TDA_MAX_DIRECTIONS, finite: run_step also
-        fills `s0` / `s1` (n_win), the sliced Wasserstein distances of the H0 / H1 diagram pairs of every window over
-        these directions (engine.sliced_wasserstein_dev; include/tdaeeg.h has the definition; status words `ss0` / `ss1`),
-        and `slc` (n_seg, 2): per group their np.nanmean under the rule of `bott` -- a window whose audio cloud is
-        degenerate or too large, or whose pair has a status, counts as NaN.  The table is validated and uploaded once,
-        here.  `result` is the same either way.
-        images=(xe, ye, sigma, power): run_step also fills `img` (n_seg, 3, n_y, n_x): per group the mean persistence
-        image of the EEG H0, the EEG H1 and the audio H1 diagrams of its windows on the float64 birth edges xe (n_x + 1) and
-        persistence edges ye (n_y + 1) (engine.image_mean_dev; include/tdaeeg.h has the definition).  Windows and the audio
-        mask are those of `land`.  The edges are uploaded once, here.  `result` is the same either way.
-        landscapes=(grid, levels): run_step also fills `land` (n_seg, 3, levels + 1, n_grid): per group the mean
-        persistence landscape (levels 1..levels) and the mean Betti curve (last row) on the float64 grid, of the EEG H0, the
-        EEG H1 and the audio H1 diagrams of its windows (engine.landscape_mean_dev; include/tdaeeg.h has the definition).
-        The EEG sets average every window of the group, as the feature aggregation does (v2:429-436); the audio set leaves
-        out the windows whose cloud is degenerate or too large (cmp:90-91); a group without such a window is NaN.  The grid
-        is uploaded once, here.  `result` is the same either way.
-        bottleneck=True: run_step also fills `b0` / `b1` (n_win), the bottleneck distances of the H0 / H1 diagram pairs
-        of every window (engine.bottleneck_dev; status words `bs0` / `bs1`), and `bott` (n_seg, 2): per group their
-        np.nanmean over the windows the Wasserstein means of `result` run over -- a window whose audio cloud is
-        degenerate (cmp:90-91) or whose pair has a solver status counts as NaN.  `result` is the same either way.
-        correlations=True: run_step also fills `corr` (n_seg, 10): Spearman [r, p] of the five feature series of
-        engine.SPEARMAN_COLS, audio H1 against EEG H1, per group (cmp:104-114; engine.temporal_corr_dev).  `result` is
-        the same either way."""
+        """correlations .. sliced: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+        the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
+        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2) -- and with `bott` / `slc` the distances of every window, `b0` / `b1` and
+        `s0` / `s1` (n_win), status words `bs0` / `bs1` and `ss0` / `ss1`.  Grid, edges and directions are uploaded once, here."""
         import torch
         self.n_win, self.device = n_win, device
         seg_off = np.asarray(seg_off, np.int32)
@@ -73,45 +102,31 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.corr = torch.empty((self.n_seg, CORR_COLS), **f64) if correlations else None
-        self.corr_cols = torch.tensor(engine.SPEARMAN_COLS, dtype=torch.int32, device=device) if correlations else None
-        self.bottleneck = bool(bottleneck)
-        self.b0 = self.b1 = self.bs0 = self.bs1 = self.bott = None
+        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced)
+        par = {o.name: o.params for o in self.outputs}
+        self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
+        for o in self.outputs:
+            if len(o.shape) == 1:
+                setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
+            else:
+                # a block per diagram set: stored set-major, one contiguous (n_seg, ...) block per launch (land_sets,
+                # img_sets); `land` / `img` are the same memory seen group-major
+                sets = torch.empty((o.shape[0], self.n_seg) + o.shape[1:], **f64)
+                setattr(self, o.name + "_sets", sets)
+                setattr(self, o.name, sets.permute(1, 0, 2, 3))
+        # the tables of the enabled outputs, uploaded once, and the per-window buffers of the two pair distances
+        pair = (torch.float64, torch.float64, torch.int32, torch.int32)
+        if "corr" in par:
+            self.corr_cols = torch.tensor(engine.SPEARMAN_COLS, dtype=torch.int32, device=device)
         if self.bottleneck:
-            self.b0 = torch.empty(n_win, **f64); self.b1 = torch.empty(n_win, **f64)
-            self.bs0 = torch.empty(n_win, dtype=torch.int32, device=device)
-            self.bs1 = torch.empty(n_win, dtype=torch.int32, device=device)
-            self.bott = torch.empty((self.n_seg, BOTT_COLS), **f64)
-        self.sliced, self.sliced_dirs = None, None
-        self.s0 = self.s1 = self.ss0 = self.ss1 = self.slc = None
-        if sliced is not None:
-            self.sliced = engine._directions(sliced)
+            self.b0, self.b1, self.bs0, self.bs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.sliced is not None:
             self.sliced_dirs = torch.from_numpy(self.sliced).to(device)
-            self.s0 = torch.empty(n_win, **f64); self.s1 = torch.empty(n_win, **f64)
-            self.ss0 = torch.empty(n_win, dtype=torch.int32, device=device)
-            self.ss1 = torch.empty(n_win, dtype=torch.int32, device=device)
-            self.slc = torch.empty((self.n_seg, SLC_COLS), **f64)
-        self.landscapes, self.land, self.land_grid, self.land_levels = None, None, None, 0
-        if landscapes is not None:
-            grid, levels = landscapes
-            grid = np.ascontiguousarray(grid, dtype=np.float64)
-            from . import _lib
-            if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID or not 1 <= int(levels) <= _lib.MAX_LANDSCAPES:
-                raise ValueError(f"landscapes=(grid, levels): a 1-D grid of 1..{_lib.MAX_GRID} points and 1..{_lib.MAX_LANDSCAPES} levels")
-            self.landscapes, self.land_levels = (grid, int(levels)), int(levels)
-            self.land_grid = torch.from_numpy(grid).to(device)
-            # stored set-major, one contiguous (n_seg, levels + 1, n_grid) block per launch; `land` is the same memory seen
-            # group-major
-            self.land_sets = torch.empty((LAND_SETS, self.n_seg, self.land_levels + 1, grid.shape[0]), **f64)
-            self.land = self.land_sets.permute(1, 0, 2, 3)
-        self.images, self.img, self.img_sets = None, None, None
-        if images is not None:
-            xe, ye, sigma, power = engine.image_args(*images)
-            self.images = (xe, ye, sigma, power)
-            self.img_xe, self.img_ye = torch.from_numpy(xe).to(device), torch.from_numpy(ye).to(device)
-            # set-major like land_sets: one contiguous (n_seg, n_y, n_x) block per launch; `img` is the group-major view
-            self.img_sets = torch.empty((IMG_SETS, self.n_seg, ye.shape[0] - 1, xe.shape[0] - 1), **f64)
-            self.img = self.img_sets.permute(1, 0, 2, 3)
+            self.s0, self.s1, self.ss0, self.ss1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.landscapes is not None:
+            self.land_grid, self.land_levels = torch.from_numpy(self.landscapes[0]).to(device), self.landscapes[1]
+        if self.images is not None:
+            self.img_xe, self.img_ye = (torch.from_numpy(e).to(device) for e in self.images[:2])
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -142,26 +157,18 @@ class Workspace:
         v.first_idx = torch.from_numpy(seg_off[:-1].astype(np.int64)).to(self.device)
         v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
         v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
-        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1"):
-            setattr(v, name, getattr(self, name)[:n_win])
+        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist") + self.PAIR_BUFFERS:
+            buf = getattr(self, name)
+            setattr(v, name, None if buf is None else buf[:n_win])
         for name in ("tau_seg", "seg_flags", "flags_host", "result"):
             setattr(v, name, getattr(self, name)[:n_seg])
-        v.dist = None if self.dist is None else self.dist[:n_win]
-        v.corr = None if self.corr is None else self.corr[:n_seg]
-        if self.bottleneck:
-            for name in ("b0", "b1", "bs0", "bs1"):
-                setattr(v, name, getattr(self, name)[:n_win])
-            v.bott = self.bott[:n_seg]
-        if self.sliced is not None:
-            for name in ("s0", "s1", "ss0", "ss1"):
-                setattr(v, name, getattr(self, name)[:n_win])
-            v.slc = self.slc[:n_seg]
-        if self.land is not None:
-            v.land_sets = self.land_sets[:, :n_seg]
-            v.land = v.land_sets.permute(1, 0, 2, 3)
-        if self.img is not None:
-            v.img_sets = self.img_sets[:, :n_seg]
-            v.img = v.img_sets.permute(1, 0, 2, 3)
+        for o in self.outputs:
+            if len(o.shape) == 1:
+                setattr(v, o.name, getattr(self, o.name)[:n_seg])
+            else:
+                sets = getattr(self, o.name + "_sets")[:, :n_seg]
+                setattr(v, o.name + "_sets", sets)
+                setattr(v, o.name, sets.permute(1, 0, 2, 3))
         return v
 
 
@@ -235,36 +242,32 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         # temporal correlation of the H1 feature series over the windows that reach the distances (cmp:90-91,104-114)
         stage("temporal_corr", lambda: engine.temporal_corr_dev(ws.fa1, ws.fe1, ws.seg_off, ws.aud.status, cols=ws.corr_cols,
                                                                 out_t=ws.corr, ctx=ctx))
-    if getattr(ws, "land", None) is not None:
+    if ws.land is not None:
         stage("landscape", lambda: _landscape_stage(ws, ctx, audio=True))
-    if getattr(ws, "img", None) is not None:
+    if ws.img is not None:
         stage("image", lambda: _image_stage(ws, ctx, audio=True))
+
     stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
                                                            out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
     stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
                                                            out_t=ws.w1, status_t=ws.ws1, ctx=ctx))
-    if getattr(ws, "bottleneck", False):
-        stage("bottleneck_h0", lambda: engine.bottleneck_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
-                                                             out_t=ws.b0, status_t=ws.bs0, ctx=ctx))
-        stage("bottleneck_h1", lambda: engine.bottleneck_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
-                                                             out_t=ws.b1, status_t=ws.bs1, ctx=ctx))
-        # the means of recording_rows_dev's windows: masked on the device, then one nanmean launch per leg
+
+    def pair_means(name, launch, d, ds, means):
+        """Stages name_h0 / name_h1: the H0 and the H1 diagram pairs of every window through `launch` (d[k], status ds[k]);
+        then means[:, k], the means of recording_rows_dev's windows: masked on the device, one nanmean launch per leg."""
+        legs = ((ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0), (ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1))
+        for k, leg in enumerate(legs):
+            stage(f"{name}_h{k}", lambda: launch(*leg, out_t=d[k], status_t=ds[k], ctx=ctx))
         out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
         nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
-        for col, (b, bs) in enumerate(((ws.b0, ws.bs0), (ws.b1, ws.bs1))):
-            seg_mean = engine.segment_nanmean_dev(torch.where(out | (bs != 0), nan, b), ws.seg_off, ctx=ctx)
-            ws.bott[:, col].copy_(seg_mean)
-    if getattr(ws, "sliced", None) is not None:
-        stage("sliced_h0", lambda: engine.sliced_wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0, ws.sliced_dirs,
-                                                                 out_t=ws.s0, status_t=ws.ss0, ctx=ctx))
-        stage("sliced_h1", lambda: engine.sliced_wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1, ws.sliced_dirs,
-                                                                 out_t=ws.s1, status_t=ws.ss1, ctx=ctx))
-        # the rule of ws.bott: masked on the device, then one nanmean launch per leg
-        out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
-        nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
-        for col, (d, ds) in enumerate(((ws.s0, ws.ss0), (ws.s1, ws.ss1))):
-            seg_mean = engine.segment_nanmean_dev(torch.where(out | (ds != 0), nan, d), ws.seg_off, ctx=ctx)
-            ws.slc[:, col].copy_(seg_mean)
+        for k in range(2):
+            seg_mean = engine.segment_nanmean_dev(torch.where(out | (ds[k] != 0), nan, d[k]), ws.seg_off, ctx=ctx)
+            means[:, k].copy_(seg_mean)
+    if ws.bottleneck:
+        pair_means("bottleneck", engine.bottleneck_dev, (ws.b0, ws.b1), (ws.bs0, ws.bs1), ws.bott)
+    if ws.sliced is not None:
+        pair_means("sliced", functools.partial(engine.sliced_wasserstein_dev, dirs_t=ws.sliced_dirs), (ws.s0, ws.s1),
+                   (ws.ss0, ws.ss1), ws.slc)
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -274,29 +277,27 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     return ws.result
 
 
-def _landscape_stage(ws, ctx, audio):
-    """ws.land of the step: one launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only its
-    (n_seg, levels + 1, n_grid) group means."""
+def _set_means_stage(ws, ctx, audio, launch, out_sets):
+    """One launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only the group means of its set,
+    out_sets[s]; launch: engine.landscape_mean_dev or engine.image_mean_dev with the output's own parameters bound."""
     from . import _lib
     sets = [(ws.eeg.h0, ws.eeg.c0, None, 0), (ws.eeg.h1, ws.eeg.c1, None, 0)]
     if audio:
         sets.append((ws.aud.h1, ws.aud.c1, ws.aud.status, _lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE))
     for s, (rows, cnt, status, mask) in enumerate(sets):
-        engine.landscape_mean_dev(rows, cnt, ws.land_grid, ws.land_levels, seg_off_t=ws.seg_off, status_t=status,
-                                  skip_mask=mask, out_t=ws.land_sets[s], ctx=ctx)
+        launch(rows, cnt, seg_off_t=ws.seg_off, status_t=status, skip_mask=mask, out_t=out_sets[s], ctx=ctx)
+
+
+def _landscape_stage(ws, ctx, audio):
+    """ws.land of the step, (n_seg, levels + 1, n_grid) per set."""
+    _set_means_stage(ws, ctx, audio, functools.partial(engine.landscape_mean_dev, grid_t=ws.land_grid, levels=ws.land_levels),
+                     ws.land_sets)
 
 
 def _image_stage(ws, ctx, audio):
-    """ws.img of the step: one launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only its
-    (n_seg, n_y, n_x) group means."""
-    from . import _lib
-    _, _, sigma, power = ws.images
-    sets = [(ws.eeg.h0, ws.eeg.c0, None, 0), (ws.eeg.h1, ws.eeg.c1, None, 0)]
-    if audio:
-        sets.append((ws.aud.h1, ws.aud.c1, ws.aud.status, _lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE))
-    for s, (rows, cnt, status, mask) in enumerate(sets):
-        engine.image_mean_dev(rows, cnt, ws.img_xe, ws.img_ye, sigma, power, seg_off_t=ws.seg_off, status_t=status,
-                              skip_mask=mask, out_t=ws.img_sets[s], ctx=ctx)
+    """ws.img of the step, (n_seg, n_y, n_x) per set."""
+    _set_means_stage(ws, ctx, audio, functools.partial(engine.image_mean_dev, xe_t=ws.img_xe, ye_t=ws.img_ye,
+                                                       sigma=ws.images[2], power=ws.images[3]), ws.img_sets)
 
 
 class Batch:
@@ -565,9 +566,9 @@ def run_features_step(eeg_win, ws, ctx=None):
             engine.corr_dist_dev(eeg_win, ws.dist, None, ctx=ctx)
             engine.rips_dm_dev(ws.dist, ws.eeg, ctx=ctx)
     engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0), (ws.eeg.h1, ws.eeg.c1, True, ws.fe1)], ctx=ctx)
-    if getattr(ws, "land", None) is not None:            # the two EEG sets of ws.land; the audio set is not touched
+    if ws.land is not None:                              # the two EEG sets of ws.land; the audio set is not touched
         _landscape_stage(ws, ctx, audio=False)
-    if getattr(ws, "img", None) is not None:             # the same for ws.img
+    if ws.img is not None:                               # the same for ws.img
         _image_stage(ws, ctx, audio=False)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)
@@ -576,7 +577,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
-# (a Workspace(correlations=True) has one more, "temporal_corr", after "finish"; a Workspace(bottleneck=True) two,
-# "bottleneck_h0" and "bottleneck_h1", after "wasserstein_h1"; a Workspace(landscapes=(grid, levels)) one, "landscape",
-# after "finish" and "temporal_corr"; a Workspace(images=(xe, ye, sigma, power)) one, "image", after "landscape"; a
-# Workspace(sliced=dirs) two, "sliced_h0" and "sliced_h1", after the bottleneck stages)
+# (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
+# "bottleneck_h1", "sliced_h0" and "sliced_h1", in this order after "wasserstein_h1")

@@ -26,21 +26,12 @@ rows are withheld if any status bit is left.  The passes differ in how a shard i
 The filter banks are designed and packed once per pass (preprocess.SosBank / BaBank) and handed to every shard's step.
 The rows equal pipeline.run_step on the stacked windows of the same band-passed signals bit for bit
 (tests/test_gpu_frontend.py::test_recording_pass_equals_stacked_windows).
-With correlations=True the passes also return the third result of the script per (recording, band): Spearman r and p of
-the five H1 feature series, audio against EEG (cmp:104-114), computed on the device from the step's own feature matrices
-(engine.temporal_corr_dev) and downloaded beside the rows as corr_h (n_rec, 5, 10); drivers.comparison_rows /
+RecordingPass and the ragged passes take the optional outputs of pipeline.step_outputs (correlations, bottleneck,
+landscapes, images, sliced: each is described there) and return each enabled one per (recording, band) beside the rows, in
+pinned host memory: corr_h (n_rec, 5, 10), bott_h (n_rec, 5, 2), land_h (n_rec, 5, 3, levels + 1, n_grid), img_h
+(n_rec, 5, 3, n_y, n_x), slc_h (n_rec, 5, 2) -- the group's block of the step's Workspace, NaN for a recording without a
+window.  They are computed on the device from the step's own diagrams and feature matrices; drivers.comparison_rows /
 comparison_summary turn rows and corr_h into the script's table and statistics.
-With bottleneck=True RecordingPass and the ragged passes also return bott_h (n_rec, 5, 2): per (recording, band) the means
-of the bottleneck distances of the H0 and of the H1 diagram pairs (pipeline.Workspace(bottleneck=True)), over the
-windows the Wasserstein means of the rows run over.
-With landscapes=(grid, levels) the same passes also return land_h (n_rec, 5, 3, levels + 1, n_grid): per (recording, band)
-the mean persistence landscape and mean Betti curve of the EEG H0, EEG H1 and audio H1 diagrams of its windows
-(pipeline.Workspace(landscapes=...)); NaN for a recording without a window.
-With sliced=dirs, an (M, 2) table of directions, they also return slc_h (n_rec, 5, 2): per (recording, band) the means of the
-sliced Wasserstein distances of the H0 and of the H1 diagram pairs (pipeline.Workspace(sliced=dirs)), over the same windows
-as bott_h; NaN for a recording without a window.
-With images=(xe, ye, sigma, power) they also return img_h (n_rec, 5, 3, n_y, n_x): per (recording, band) the mean persistence
-image of the same three diagram sets (pipeline.Workspace(images=...)); NaN for a recording without a window.
 """
 import numpy as np
 
@@ -62,7 +53,8 @@ class _ShardedPass:
       _upload(st, i, raw_h, second_h)   shard i into buffer set st (on the copy stream)
       _shard_step(st, i)            everything between the upload and st["rows"] (on st["main"]; filters on st["side"])
       _rips_step(st, i, retry)      the part of the step that a flagged shard repeats with retry="auto"
-      _rows(st, i, res)             the result of _rips_step -> st["rows"] (and st["corr"], st["bott"], st["land"], st["img"], st["slc"])
+      _rows(st, i, res)             the result of _rips_step -> st["rows"], and the Workspace's block of every output of
+                                    self.outputs -> st[name]
       _flags_ws(st, i)              the Workspace (or view) whose seg_flags / flags_host are shard i's; None for a shard
                                     without a window (nothing to verify)
       _more_back(st, r0, r1, nb)    optional: further per-recording outputs of the shard to the host beside the rows
@@ -74,19 +66,13 @@ class _ShardedPass:
         self.ctx = ctx or get_ctx()
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
-        self.correlations, self.corr_h = bool(correlations), None
-        self.bottleneck, self.bott_h = bool(bottleneck), None
-        self.landscapes, self.land_h = None, None
-        if landscapes is not None:
-            self.landscapes = (np.ascontiguousarray(landscapes[0], dtype=np.float64), int(landscapes[1]))
-        self.images, self.img_h = None, None
-        if images is not None:
-            from . import engine
-            self.images = engine.image_args(*images)
-        self.sliced, self.slc_h = None, None
-        if sliced is not None:
-            from . import engine
-            self.sliced = engine._directions(sliced)
+        # the optional outputs (pipeline.step_outputs: self.outputs is the table, validated here); host buffer of `name`:
+        # self.<name>_h, made by `run`
+        self.outputs = pipeline.step_outputs(correlations, bottleneck, landscapes, images, sliced)
+        par = {o.name: o.params for o in self.outputs}
+        self.correlations, self.bottleneck = "corr" in par, "bott" in par
+        self.landscapes, self.images, self.sliced = par.get("land"), par.get("img"), par.get("slc")
+        self.corr_h = self.bott_h = self.land_h = self.img_h = self.slc_h = None
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -96,12 +82,15 @@ class _ShardedPass:
         filters, step, download of consecutive shards overlap).  A stream pair per set: the filters of shard k + 1 (chains
         of dependent operations on few waves) run beside the Rips kernels of shard k (which fill the vector units).  Which
         hardware queue a stream lands on depends on how many were made before it, and a pass' speed on that: the order
-        stays per set the Workspace's own, main, side; then copy, then back."""
+        stays per set the Workspace's own, main, side; then copy, then back.  st[name] (rows of st["rows"], bands, the
+        output's shape) of every output of self.outputs is made here."""
         import torch
         self.n_sets = int(n_sets)
         self.set = []
         for _ in range(self.n_sets):
             st = buffers()
+            for o in self.outputs:
+                st[o.name] = torch.empty(st["rows"].shape[:2] + o.shape, dtype=torch.float64, device=self.dev)
             st.update(main=torch.cuda.Stream(device=self.dev), side=torch.cuda.Stream(device=self.dev),
                       up=torch.cuda.Event(), done=torch.cuda.Event(), down=torch.cuda.Event())
             self.set.append(st)
@@ -110,32 +99,17 @@ class _ShardedPass:
                                                                        # for the compute of k, the upload of k + 1 must not)
         self.repairs = 0
 
-    def _land_shape(self):
-        """(3, levels + 1, n_grid): the landscape block of one (recording, band)."""
-        return (pipeline.LAND_SETS, self.landscapes[1] + 1, self.landscapes[0].shape[0])
-
-    def _img_shape(self):
-        """(3, n_y, n_x): the image block of one (recording, band)."""
-        return (pipeline.IMG_SETS, self.images[1].shape[0] - 1, self.images[0].shape[0] - 1)
-
     def run(self, raw_h, second_h, rows_h=None):
         """The two pinned float64 host inputs of the pass -> rows_h (n_rec, n_bands, ROW_COLS), pinned, complete when the
-        call returns (and self.corr_h with correlations=True, self.bott_h with bottleneck=True, self.land_h with landscapes=..., self.img_h with images=..., self.slc_h with sliced=...)."""
+        call returns; so is self.<name>_h, pinned (n_rec, n_bands) + shape, of every output of self.outputs."""
         import torch
         self.ranges = self._begin(raw_h, second_h)
         n_rec, nb = self.ranges[-1][1] if self.ranges else 0, len(self.bands)
         if rows_h is None:
             rows_h = torch.empty((n_rec, nb, self.ROW_COLS), dtype=torch.float64).pin_memory()
-        if self.correlations and (self.corr_h is None or self.corr_h.shape[0] != n_rec):
-            self.corr_h = torch.empty((n_rec, nb, pipeline.CORR_COLS), dtype=torch.float64).pin_memory()
-        if self.bottleneck and (self.bott_h is None or self.bott_h.shape[0] != n_rec):
-            self.bott_h = torch.empty((n_rec, nb, pipeline.BOTT_COLS), dtype=torch.float64).pin_memory()
-        if self.landscapes is not None and (self.land_h is None or self.land_h.shape[0] != n_rec):
-            self.land_h = torch.empty((n_rec, nb) + self._land_shape(), dtype=torch.float64).pin_memory()
-        if self.images is not None and (self.img_h is None or self.img_h.shape[0] != n_rec):
-            self.img_h = torch.empty((n_rec, nb) + self._img_shape(), dtype=torch.float64).pin_memory()
-        if self.sliced is not None and (self.slc_h is None or self.slc_h.shape[0] != n_rec):
-            self.slc_h = torch.empty((n_rec, nb, pipeline.SLC_COLS), dtype=torch.float64).pin_memory()
+        for o in self.outputs:
+            if getattr(self, o.name + "_h") is None or getattr(self, o.name + "_h").shape[0] != n_rec:
+                setattr(self, o.name + "_h", torch.empty((n_rec, nb) + o.shape, dtype=torch.float64).pin_memory())
         pend = []
         try:
             for i, (r0, r1) in enumerate(self.ranges):
@@ -152,18 +126,7 @@ class _ShardedPass:
                     st["done"].record(st["main"])
                 with torch.cuda.stream(self.back):
                     self.back.wait_event(st["done"])
-                    rows_h[r0:r1].copy_(st["rows"][:r1 - r0], non_blocking=True)
-                    if self.correlations:
-                        self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0], non_blocking=True)
-                    if self.bottleneck:
-                        self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0], non_blocking=True)
-                    if self.landscapes is not None:
-                        self.land_h[r0:r1].copy_(st["land"][:r1 - r0], non_blocking=True)
-                    if self.images is not None:
-                        self.img_h[r0:r1].copy_(st["img"][:r1 - r0], non_blocking=True)
-                    if self.sliced is not None:
-                        self.slc_h[r0:r1].copy_(st["slc"][:r1 - r0], non_blocking=True)
-                    self._more_back(st, r0, r1, True)
+                    self._back(st, r0, r1, rows_h, True)
                     st["down"].record(self.back)
                 pend.append(i)
                 if len(pend) >= self.n_sets:        # (the GPU has the later shards to work on while the host looks at this
@@ -176,13 +139,20 @@ class _ShardedPass:
         self.back.synchronize()
         return rows_h
 
+    def _back(self, st, r0, r1, rows_h, non_blocking):
+        """The rows of a shard, its block of every output and what the _more_back hook adds, to the host on the current stream."""
+        rows_h[r0:r1].copy_(st["rows"][:r1 - r0], non_blocking=non_blocking)
+        for o in self.outputs:
+            getattr(self, o.name + "_h")[r0:r1].copy_(st[o.name][:r1 - r0], non_blocking=non_blocking)
+        self._more_back(st, r0, r1, non_blocking)
+
     def _more_back(self, st, r0, r1, non_blocking):
         pass
 
     def _verify(self, i, rows_h):
         """Verify, then publish: a shard whose step left a class-overflow flag (run_step copies the flags of its groups
         to pinned memory) is run again with the full ladder -- rare -- and its rows replace the ones already copied; any
-        status bit still left withholds the rows."""
+        status bit still left withholds the rows (and every output: they take the path of the rows)."""
         import torch
         st = self.set[i % self.n_sets]
         r0, r1 = self.ranges[i]
@@ -195,18 +165,7 @@ class _ShardedPass:
             self.repairs += 1
             with torch.cuda.stream(st["main"]):
                 self._rows(st, i, self._rips_step(st, i, "auto"))
-                rows_h[r0:r1].copy_(st["rows"][:r1 - r0])
-                if self.correlations:
-                    self.corr_h[r0:r1].copy_(st["corr"][:r1 - r0])
-                if self.bottleneck:
-                    self.bott_h[r0:r1].copy_(st["bott"][:r1 - r0])
-                if self.landscapes is not None:
-                    self.land_h[r0:r1].copy_(st["land"][:r1 - r0])
-                if self.images is not None:
-                    self.img_h[r0:r1].copy_(st["img"][:r1 - r0])
-                if self.sliced is not None:
-                    self.slc_h[r0:r1].copy_(st["slc"][:r1 - r0])
-                self._more_back(st, r0, r1, False)
+                self._back(st, r0, r1, rows_h, False)
                 fl.copy_(ws.seg_flags, non_blocking=True)
                 st["main"].synchronize()
         if bool(fl.any()):
@@ -221,15 +180,8 @@ class RecordingPass(_ShardedPass):
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
                  max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None):
-        """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10): Spearman [r, p] of the five H1
-        feature series of engine.SPEARMAN_COLS per (recording, band) (cmp:104-114), the order of
-        drivers.DETAILED_COLUMNS[8:].  bottleneck=True: `run` also fills self.bott_h, pinned (n_rec, n_bands, 2): the means
-        [b_h0, b_h1] of the bottleneck distances per (recording, band).  landscapes=(grid, levels): `run` also fills self.land_h,
-        pinned (n_rec, n_bands, 3, levels + 1, n_grid): the group means of pipeline.Workspace(landscapes=...).
-        images=(xe, ye, sigma, power): `run` also fills self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x): the group means of
-        pipeline.Workspace(images=...).  sliced=dirs ((M, 2) directions): `run` also fills self.slc_h, pinned
-        (n_rec, n_bands, 2): the means [s_h0, s_h1] of the sliced Wasserstein distances per (recording, band).  The rows are
-        the same either way."""
+        """correlations .. sliced: the optional outputs (pipeline.step_outputs); `run` also fills self.<name>_h of each
+        (_ShardedPass.run).  corr_h is in the order of drivers.DETAILED_COLUMNS[8:].  The rows are the same either way."""
         import os
         import torch
         super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images, sliced)
@@ -255,11 +207,6 @@ class RecordingPass(_ShardedPass):
             ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
                                   bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images,
                                   sliced=self.sliced),
-            slc=torch.empty((S, nb, pipeline.SLC_COLS), **f64) if self.sliced is not None else None,
-            corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
-            bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
-            land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
-            img=torch.empty((S, nb) + self._img_shape(), **f64) if self.images is not None else None,
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -299,19 +246,9 @@ class RecordingPass(_ShardedPass):
         self._rows(st, i, self._rips_step(st, i, "one"))
 
     def _rows(self, st, i, res):
-        """(nb * S, 48) band-major groups -> the shard's rows (and, with correlations, the same for the workspace's corr)."""
-        nb = len(self.bands)
-        st["rows"].copy_(res.view(nb, self.S, pipeline.RESULT_COLS).transpose(0, 1))
-        if self.correlations:
-            st["corr"].copy_(st["ws"].corr.view(nb, self.S, pipeline.CORR_COLS).transpose(0, 1))
-        if self.bottleneck:
-            st["bott"].copy_(st["ws"].bott.view(nb, self.S, pipeline.BOTT_COLS).transpose(0, 1))
-        if self.landscapes is not None:
-            st["land"].copy_(st["ws"].land.unflatten(0, (nb, self.S)).transpose(0, 1))
-        if self.images is not None:
-            st["img"].copy_(st["ws"].img.unflatten(0, (nb, self.S)).transpose(0, 1))
-        if self.sliced is not None:
-            st["slc"].copy_(st["ws"].slc.view(nb, self.S, pipeline.SLC_COLS).transpose(0, 1))
+        """(nb * S, 48) band-major groups -> the shard's rows; the same for the Workspace's block of every output."""
+        for dst, src in [(st["rows"], res)] + [(st[o.name], getattr(st["ws"], o.name)) for o in self.outputs]:
+            dst.copy_(src.unflatten(0, (len(self.bands), self.S)).transpose(0, 1))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -408,11 +345,7 @@ class RaggedRecordingPass(_ShardedPass):
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
                  plan=None, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None):
-        """correlations=True: `run` also fills self.corr_h, pinned (n_rec, n_bands, 10), as RecordingPass does; NaN for a
-        recording without a window.  bottleneck=True: the same for self.bott_h, pinned (n_rec, n_bands, 2);
-        landscapes=(grid, levels): the same for self.land_h, pinned (n_rec, n_bands, 3, levels + 1, n_grid);
-        images=(xe, ye, sigma, power): the same for self.img_h, pinned (n_rec, n_bands, 3, n_y, n_x);
-        sliced=dirs ((M, 2) directions): the same for self.slc_h, pinned (n_rec, n_bands, 2)."""
+        """correlations .. sliced: the optional outputs, as RecordingPass takes them; NaN for a recording without a window."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
                          correlations, bottleneck, landscapes, images, sliced)
@@ -454,11 +387,6 @@ class RaggedRecordingPass(_ShardedPass):
                                     n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
                                     landscapes=self.landscapes, images=self.images, sliced=self.sliced)
             return dict(
-                slc=torch.empty((S, nb, pipeline.SLC_COLS), **f64) if self.sliced is not None else None,
-                corr=torch.empty((S, nb, pipeline.CORR_COLS), **f64) if self.correlations else None,
-                bott=torch.empty((S, nb, pipeline.BOTT_COLS), **f64) if self.bottleneck else None,
-                land=torch.empty((S, nb) + self._land_shape(), **f64) if self.landscapes is not None else None,
-                img=torch.empty((S, nb) + self._img_shape(), **f64) if self.images is not None else None,
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
                 work=torch.empty(nb * n_ch * (T + 2 * self.edge * S), **f64), worka=torch.empty(nb * (Te + 2 * self.edge_a * S), **f64),
@@ -488,44 +416,22 @@ class RaggedRecordingPass(_ShardedPass):
 
     def _rows(self, st, i, res):
         """(n_bands * n_live, ROW_COLS) band-major -> the shard's rows; recordings without a window: NaN, with 0 in the
-        columns ROW_ZERO."""
+        columns ROW_ZERO.  The same (all NaN) for the block of every output in the shard's view."""
+        self._scatter(i, st["rows"], res, self.ROW_ZERO)
+        for o in self.outputs:
+            self._scatter(i, st[o.name], getattr(st["views"][i], o.name))
+
+    def _scatter(self, i, dst, src, zero=None):
+        """src, band-major over the live recordings of shard i, to the recordings in dst; NaN (0 in the columns `zero`) for
+        the ones without a window."""
         d = self.shards[i]
-        rows = st["rows"][:d["n"]]
+        dst = dst[:d["n"]]
         if d["n_live"] < d["n"]:
-            rows.fill_(float("nan"))
-            rows[:, :, self.ROW_ZERO] = 0.0
+            dst.fill_(float("nan"))
+            if zero is not None:
+                dst[:, :, zero] = 0.0
         if d["n_live"]:
-            rows.index_copy_(0, d["live"], res.view(len(self.bands), d["n_live"], self.ROW_COLS).transpose(0, 1))
-        if self.correlations:
-            corr = st["corr"][:d["n"]]
-            if d["n_live"] < d["n"]:
-                corr.fill_(float("nan"))
-            if d["n_live"]:
-                corr.index_copy_(0, d["live"], st["views"][i].corr.view(len(self.bands), d["n_live"], pipeline.CORR_COLS).transpose(0, 1))
-        if self.sliced is not None:
-            slc = st["slc"][:d["n"]]
-            if d["n_live"] < d["n"]:
-                slc.fill_(float("nan"))
-            if d["n_live"]:
-                slc.index_copy_(0, d["live"], st["views"][i].slc.view(len(self.bands), d["n_live"], pipeline.SLC_COLS).transpose(0, 1))
-        if self.bottleneck:
-            bott = st["bott"][:d["n"]]
-            if d["n_live"] < d["n"]:
-                bott.fill_(float("nan"))
-            if d["n_live"]:
-                bott.index_copy_(0, d["live"], st["views"][i].bott.view(len(self.bands), d["n_live"], pipeline.BOTT_COLS).transpose(0, 1))
-        if self.landscapes is not None:
-            land = st["land"][:d["n"]]
-            if d["n_live"] < d["n"]:
-                land.fill_(float("nan"))
-            if d["n_live"]:
-                land.index_copy_(0, d["live"], st["views"][i].land.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
-        if self.images is not None:
-            img = st["img"][:d["n"]]
-            if d["n_live"] < d["n"]:
-                img.fill_(float("nan"))
-            if d["n_live"]:
-                img.index_copy_(0, d["live"], st["views"][i].img.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
+            dst.index_copy_(0, d["live"], src.unflatten(0, (len(self.bands), d["n_live"])).transpose(0, 1))
 
     def _front_end(self, st, i):
         """Whatever makes st["env"] from the upload, on the side stream (here the envelopes ARE the upload)."""

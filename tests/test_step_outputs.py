@@ -1,0 +1,63 @@
+"""
+pipeline.step_outputs, the table of the optional per-group outputs of a step (no GPU): the records it returns, their
+fixed order, and that the arguments pipeline.Workspace rejects are rejected here with the same exception types.
+"""
+import numpy as np
+import pytest
+
+from tda_eeg_audio_amd import pipeline, utils
+from tda_eeg_audio_amd._lib import TdaError
+
+GRID, LEVELS = np.linspace(0.0, 1.5, 16), 2
+IMAGES = (np.linspace(0.0, 1.0, 5), np.linspace(0.0, 1.0, 6), 0.1, 1)        # 4 x 5 pixels
+DIRS = utils.default_directions(4)
+ALL = dict(correlations=True, bottleneck=True, landscapes=(GRID, LEVELS), images=IMAGES, sliced=DIRS)
+
+
+def test_everything_off_is_an_empty_table():
+    assert pipeline.step_outputs() == []
+    assert pipeline.step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None) == []
+
+
+@pytest.mark.parametrize("option,name,shape", [
+    ("correlations", "corr", (10,)),
+    ("bottleneck", "bott", (2,)),
+    ("landscapes", "land", (3, 3, 16)),
+    ("images", "img", (3, 5, 4)),
+    ("sliced", "slc", (2,)),
+])
+def test_each_output_alone(option, name, shape):
+    (o,) = pipeline.step_outputs(**{option: ALL[option]})
+    assert (o.name, o.shape) == (name, shape)
+
+
+def test_validated_parameters():
+    par = {o.name: o.params for o in pipeline.step_outputs(**ALL)}
+    grid, levels = par["land"]
+    assert grid.dtype == np.float64 and np.array_equal(grid, GRID) and levels == LEVELS and isinstance(levels, int)
+    xe, ye, sigma, power = par["img"]
+    assert np.array_equal(xe, IMAGES[0]) and np.array_equal(ye, IMAGES[1]) and (sigma, power) == (0.1, 1)
+    assert par["slc"].dtype == np.float64 and par["slc"].flags.c_contiguous and np.array_equal(par["slc"], DIRS)
+
+
+def test_all_on_in_the_fixed_order():
+    assert [o.name for o in pipeline.step_outputs(**ALL)] == ["corr", "bott", "land", "img", "slc"]
+    assert [o.shape for o in pipeline.step_outputs(**ALL)] == [(pipeline.CORR_COLS,), (pipeline.BOTT_COLS,), (pipeline.LAND_SETS, 3, 16),
+                                                               (pipeline.IMG_SETS, 5, 4), (pipeline.SLC_COLS,)]
+    # the order is the table's, not the caller's
+    assert [o.name for o in pipeline.step_outputs(sliced=DIRS, bottleneck=True)] == ["bott", "slc"]
+
+
+@pytest.mark.parametrize("kw,exc", [
+    (dict(landscapes=(GRID, 0)), ValueError),
+    (dict(landscapes=(GRID, 9)), ValueError),
+    (dict(landscapes=(np.zeros(0), LEVELS)), ValueError),
+    (dict(landscapes=(np.linspace(0.0, 1.0, 257), LEVELS)), ValueError),
+    (dict(images=(np.array([0.0, 0.5, 0.25, 1.0]), IMAGES[1], 0.1, 1)), ValueError),
+    (dict(images=(IMAGES[0], IMAGES[1], 0.0, 1)), ValueError),
+    (dict(sliced=np.zeros((2, 3))), TdaError),
+    (dict(sliced=[[np.nan, 1.0]]), TdaError),
+])
+def test_invalid_arguments(kw, exc):
+    with pytest.raises(exc):
+        pipeline.step_outputs(**kw)
