@@ -480,6 +480,50 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
                                 const int* idx_a, const int* idx_b, int n_pairs,
                                 double* out, int* status);
 
+/* ---- Wasserstein distances of order 1 and 2, L2 or L-infinity ground metric ---------
+ * What Hera, GUDHI and giotto-tda call wasserstein_distance: order 2 (the metric of Frechet means on diagram space) and
+ * the L-infinity ground metric with (d - b) / 2 to the diagonal (the convention of the bottleneck distance above), beside
+ * persim's L2 with (d - b) / sqrt 2.
+ *   Arguments.   As tda_wasserstein_batch[_dev].
+ *   Parameters.  order is 1 or 2; ground is TDA_GROUND_L2 or TDA_GROUND_LINF.  Anything else is TDA_ERR_INVALID and
+ *                nothing is launched.  All four combinations are accepted.
+ *   Cleaning.    As for the Wasserstein distance: rows with a non-finite entry are ignored, an empty diagram becomes
+ *                {(0,0)}.
+ *   Costs.       Every line is one correctly rounded float64 operation; there is no multiply-add.
+ *                  dx = fabs(a_b - b_b), dy = fabs(a_d - b_d), p = d - b.
+ *                  L2:         e = (dx * dx) + (dy * dy).
+ *                    order 1:  point cost sqrt(e), diagonal cost p * 0.7071067811865476.
+ *                    order 2:  point cost e (no root), diagonal cost 0.5 * (p * p).
+ *                  L-infinity: m = fmax(dx, dy), h = 0.5 * p.
+ *                    order 1:  point cost m, diagonal cost h.
+ *                    order 2:  point cost m * m, diagonal cost h * h.
+ *   Value.       V is the minimum over partial matchings of the sum of the matched point costs plus the diagonal costs of
+ *                every unmatched point of both diagrams; diagonal to diagonal is free.  The result is V for order 1 and
+ *                sqrt(V), correctly rounded, for order 2.
+ *   Exactness.   Every cost is the same float64 on the GPU and in a CPU evaluation of this text.  The result differs from
+ *                such an evaluation only by the order of the additions and by which of several equally good matchings was
+ *                summed.  Two diagrams whose points all share one birth are summed as (all diagonal costs) + (the gains
+ *                C - s - t of the matched pairs); a V that comes out below 0 there is returned as 0.  d >= b is assumed
+ *                for every finite row.  A pair alone and the same pair inside a batch give the same bytes.
+ *   Status.      A pair with a diagram of more than 512 finite rows is TDA_WIN_NOT_CONVERGED with NaN (the buffers may be
+ *                larger than that), as is a pair whose solver hit one of its loop bounds.  No other status occurs.
+ *   The _dev form only enqueues on `stream` and allocates nothing.  tda_set_wasserstein_pruning and
+ *   tda_set_wasserstein_counter apply as they do to tda_wasserstein_batch: the short cuts never change a byte.
+ * Relation to tda_wasserstein_batch.  (order 1, TDA_GROUND_L2) is the same mathematical quantity, not the same float:
+ * that entry follows sklearn's |x|^2 - 2 x.y + |y|^2 expansion, whose error is bounded at 7.3e-8 X per point cost (X the
+ * largest |coordinate| of the pair; csrc/wasserstein.hip), so the two may differ by up to about min(M, N) times that.
+ * tda_wasserstein_batch stays the drop-in for the reference; this entry is not a replacement for it. */
+#define TDA_GROUND_L2   0
+#define TDA_GROUND_LINF 1
+tda_status tda_wasserstein_q_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
+                                       const double* dgm_b, const int* cnt_b, int cap_b,
+                                       const int* idx_a, const int* idx_b, int n_pairs,
+                                       int order, int ground, double* out, int* status, void* stream);
+tda_status tda_wasserstein_q_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                   const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                   const int* idx_a, const int* idx_b, int n_pairs,
+                                   int order, int ground, double* out, int* status);
+
 /* ---- Sliced Wasserstein distance between diagrams ---------------------------------
  * Carriere, Cuturi, Oudot 2017 (what persim.sliced_wasserstein computes): project both diagrams onto a handful of
  * directions, sort each projection, take the L1 difference of the sorted lists, average over the directions.  persim is

@@ -32,6 +32,8 @@ MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 MAX_POINTS = 128
 MAX_DIRECTIONS = 128        # TDA_MAX_DIRECTIONS
 SW_MAX_POINTS = 512         # TDA_SW_MAX_POINTS
+TDA_GROUND_L2 = 0           # tda_wasserstein_q_batch: (d - b) / sqrt 2 to the diagonal
+TDA_GROUND_LINF = 1         # ... (d - b) / 2, the convention of the bottleneck distance
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -107,6 +109,8 @@ SYMBOLS = {
     "tda_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
     "tda_bottleneck_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_bottleneck_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp]),
+    "tda_wasserstein_q_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_wasserstein_q_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, _I, c_vp, c_vp]),
     "tda_sliced_wasserstein_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp,
                                               c_vp]),
     "tda_sliced_wasserstein_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, _I, c_vp,

@@ -423,6 +423,18 @@ tda_status tda_bottleneck_batch_dev(tda_ctx* ctx, const double* dgm_a, const int
                              (hipStream_t)stream);
 }
 
+tda_status tda_wasserstein_q_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
+                                       const double* dgm_b, const int* cnt_b, int cap_b, const int* idx_a,
+                                       const int* idx_b, int n_pairs, int order, int ground, double* out, int* status,
+                                       void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
+    if (n_pairs) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b);
+                   CHECK_PTR(ctx, out); CHECK_PTR(ctx, status); }
+    return launch_wasserstein_q(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, idx_a, idx_b, n_pairs, order, ground, out,
+                                status, (hipStream_t)stream);
+}
+
 tda_status tda_sliced_wasserstein_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int cap_a,
                                             const double* dgm_b, const int* cnt_b, int cap_b, const int* idx_a,
                                             const int* idx_b, int n_pairs, const double* dirs, int n_dirs, double* out,
@@ -964,6 +976,18 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
         [&](const PairDev& d) { return tda_bottleneck_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
                                                                 d.out, d.st, nullptr); });
+}
+
+tda_status tda_wasserstein_q_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                   const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                   const int* idx_b, int n_pairs, int order, int ground, double* out, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
+    if ((order != 1 && order != 2) || (ground != TDA_GROUND_L2 && ground != TDA_GROUND_LINF))
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "order must be 1 or 2 and ground TDA_GROUND_L2 or TDA_GROUND_LINF");
+    return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
+        [&](const PairDev& d) { return tda_wasserstein_q_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
+                                                                   order, ground, d.out, d.st, nullptr); });
 }
 
 tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,

@@ -233,6 +233,8 @@ tda_status launch_wasserstein(tda_ctx*, const double*, const int*, int, const do
                               const int*, int, double*, int*, hipStream_t);
 tda_status launch_bottleneck(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
                              const int*, int, double*, int*, hipStream_t);
+tda_status launch_wasserstein_q(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*,
+                                const int*, int, int order, int ground, double*, int*, hipStream_t);
 tda_status launch_sliced(tda_ctx*, const double*, const int*, int, const double*, const int*, int, const int*, const int*,
                          int, const double*, int, double*, int*, hipStream_t);
 tda_status launch_sliced_prepare(tda_ctx*, const double*, const int*, int, int, const double*, int, const long long*, double*,

@@ -5,7 +5,7 @@ Every function here is a thin marshalling layer over one C-ABI entry point of
 include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU path.
 
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
-                 tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch,
+                 tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch, wasserstein_q_batch,
                  sliced_wasserstein_batch, sliced_wasserstein_gram,
                  landscape_batch, image_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
@@ -269,6 +269,27 @@ def bottleneck_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, ctx=N
     largest matched cost under the best matching); arguments and results as wasserstein_batch."""
     ctx = ctx or get_ctx()
     return _pair_batch(ctx.lib.tda_bottleneck_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status)
+
+
+GROUNDS = {"l2": _lib.TDA_GROUND_L2, "linf": _lib.TDA_GROUND_LINF}
+
+
+def wasserstein_q_args(order, ground):
+    """(order, ground constant) of a Wasserstein distance as the kernels take them: order 1 or 2, ground "l2" or "linf".
+    TdaError, before any GPU call, for anything else."""
+    if isinstance(order, bool) or order not in (1, 2):
+        raise _lib.TdaError(f"wasserstein_q: order must be 1 or 2, not {order!r}")
+    if not isinstance(ground, str) or ground not in GROUNDS:
+        raise _lib.TdaError(f"wasserstein_q: ground must be 'l2' or 'linf', not {ground!r}")
+    return int(order), GROUNDS[ground]
+
+
+def wasserstein_q_batch(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, order=2, ground="l2", ctx=None, want_status=False):
+    """Wasserstein distance of order 1 or 2 of diagram pairs with the L2 ((d - b) / sqrt 2 to the diagonal) or the
+    L-infinity ((d - b) / 2) ground metric (include/tdaeeg.h); arguments and results as wasserstein_batch."""
+    order, ground = wasserstein_q_args(order, ground)
+    ctx = ctx or get_ctx()
+    return _pair_batch(ctx.lib.tda_wasserstein_q_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status, order, ground)
 
 
 def landscape_batch(rows, cnt, grid, levels, ctx=None):
@@ -650,6 +671,16 @@ def bottleneck_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, out_t=N
     status_t are given.  out_t is NaN where status_t != 0."""
     ctx = ctx or get_ctx()
     return _pair_dev(ctx.lib.tda_bottleneck_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx)
+
+
+def wasserstein_q_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, order=2, ground="l2", out_t=None, status_t=None,
+                      ctx=None):
+    """wasserstein_q_batch on device tensors: one launch on torch's current stream, nothing allocated when out_t and
+    status_t are given.  out_t is NaN where status_t != 0."""
+    order, ground = wasserstein_q_args(order, ground)
+    ctx = ctx or get_ctx()
+    return _pair_dev(ctx.lib.tda_wasserstein_q_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx, order,
+                     ground)
 
 
 def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):

@@ -22,15 +22,16 @@ RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG fea
 CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
 BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
 SLC_COLS = 2              # Workspace(sliced=dirs).slc: [s_h0, s_h1], the means of the sliced Wasserstein distances
+WQ_COLS = 2               # Workspace(wasserstein_q=(order, ground)).wq: [q_h0, q_h1], the means of that Wasserstein distance
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
-def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None):
+def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -45,7 +46,9 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
       img   images=(xe, ye, sigma, power): (IMG_SETS, n_y, n_x) mean persistence image of the same sets, windows and audio
             mask on the birth edges xe (n_x + 1) and persistence edges ye (n_y + 1) (engine.image_mean_dev; engine.image_args)
       slc   sliced=dirs, (M, 2) finite directions, 1 <= M <= TDA_MAX_DIRECTIONS (engine._directions): (SLC_COLS,) np.nanmean
-            of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`"""
+            of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`
+      wq    wasserstein_q=(order, ground), order 1 or 2 and ground "l2" or "linf": (WQ_COLS,) np.nanmean of that Wasserstein
+            distance of the H0 / H1 pairs (engine.wasserstein_q_dev) under the rule of `bott`.  ValueError for anything else"""
     from . import _lib
     out = []
     if correlations:
@@ -63,23 +66,33 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
         out.append(Output("img", (IMG_SETS, ye.shape[0] - 1, xe.shape[0] - 1), (xe, ye, sigma, power)))
     if sliced is not None:
         out.append(Output("slc", (SLC_COLS,), engine._directions(sliced)))
+    if wasserstein_q is not None:
+        try:
+            order, ground = wasserstein_q
+            engine.wasserstein_q_args(order, ground)
+        except (TypeError, ValueError, _lib.TdaError):
+            raise ValueError("wasserstein_q=(order, ground): order 1 or 2, ground 'l2' or 'linf'") from None
+        out.append(Output("wq", (WQ_COLS,), (int(order), ground)))
     return out
 
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
-    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1")    # per window: two distances, two status words
+    # per window: two distances, two status words
+    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1")
     # the buffers and resident tables of the optional outputs: None where the output is off
     corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
     land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
+    wq = wasserstein_q = q0 = q1 = qs0 = qs1 = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None):
-        """correlations .. sliced: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 landscapes=None, images=None, sliced=None, wasserstein_q=None):
+        """correlations .. wasserstein_q: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
-        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2) -- and with `bott` / `slc` the distances of every window, `b0` / `b1` and
-        `s0` / `s1` (n_win), status words `bs0` / `bs1` and `ss0` / `ss1`.  Grid, edges and directions are uploaded once, here."""
+        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2) -- and with `bott` / `slc` / `wq` the distances of every
+        window, `b0` / `b1`, `s0` / `s1` and `q0` / `q1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1` and `qs0` / `qs1`.
+        Grid, edges and directions are uploaded once, here."""
         import torch
         self.n_win, self.device = n_win, device
         seg_off = np.asarray(seg_off, np.int32)
@@ -102,9 +115,10 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced)
+        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
+        self.wasserstein_q = par.get("wq")
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
@@ -123,6 +137,8 @@ class Workspace:
         if self.sliced is not None:
             self.sliced_dirs = torch.from_numpy(self.sliced).to(device)
             self.s0, self.s1, self.ss0, self.ss1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.wasserstein_q is not None:
+            self.q0, self.q1, self.qs0, self.qs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.landscapes is not None:
             self.land_grid, self.land_levels = torch.from_numpy(self.landscapes[0]).to(device), self.landscapes[1]
         if self.images is not None:
@@ -268,6 +284,10 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     if ws.sliced is not None:
         pair_means("sliced", functools.partial(engine.sliced_wasserstein_dev, dirs_t=ws.sliced_dirs), (ws.s0, ws.s1),
                    (ws.ss0, ws.ss1), ws.slc)
+    if ws.wasserstein_q is not None:
+        order, ground = ws.wasserstein_q
+        pair_means("wasserstein_q", functools.partial(engine.wasserstein_q_dev, order=order, ground=ground), (ws.q0, ws.q1),
+                   (ws.qs0, ws.qs1), ws.wq)
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -578,4 +598,4 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0" and "sliced_h1", in this order after "wasserstein_h1")
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0" and "wasserstein_q_h1", in this order after "wasserstein_h1")

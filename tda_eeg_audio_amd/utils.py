@@ -167,6 +167,20 @@ def safe_bottleneck(dgm1, dgm2):
         return np.nan
 
 
+def safe_wasserstein_q(dgm1, dgm2, order=2, ground="l2"):
+    """Wasserstein distance of order 1 or 2 of two diagrams cleaned as safe_wasserstein cleans them, with the "l2"
+    ((d - b) / sqrt 2 to the diagonal) or the "linf" ((d - b) / 2) ground metric (include/tdaeeg.h); NaN on any failure."""
+    if _ACTIVE is not None:
+        return _ACTIVE.add_wasserstein_q(dgm1, dgm2, order, ground)
+    try:
+        ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+        rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+        out, st = engine.wasserstein_q_batch(ra, ca, rb, cb, order=order, ground=ground, want_status=True)
+        return float(out[0]) if st[0] == 0 else np.nan
+    except Exception:
+        return np.nan
+
+
 def default_landscape_grid(n=64):
     """The grid the landscape functions use when none is given: n points over the filtration, 0 .. MAX_EDGE_LENGTH."""
     return np.linspace(0.0, MAX_EDGE_LENGTH, n)
@@ -325,7 +339,7 @@ class DeferredVector(DeferredArray):
 
 
 class DeferredScalar(_Deferred):
-    """The value of a queued safe_wasserstein, safe_bottleneck or safe_sliced_wasserstein call."""
+    """The value of a queued safe_wasserstein, safe_bottleneck, safe_wasserstein_q or safe_sliced_wasserstein call."""
     __slots__ = ()
 
     def __float__(self):
@@ -370,7 +384,7 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_sliced_wasserstein, extract_features, persistence_landscape, betti_curve and
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_wasserstein_q, safe_sliced_wasserstein, extract_features, persistence_landscape, betti_curve and
     persistence_image
     queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
@@ -383,6 +397,7 @@ class batch:
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
         self.imgs = []
         self.spairs = []              # safe_sliced_wasserstein: (dgm1, dgm2, direction table, deferred value)
+        self.qpairs = []              # safe_wasserstein_q: (dgm1, dgm2, (order, ground), deferred value)
 
     def __enter__(self):
         global _ACTIVE
@@ -417,6 +432,11 @@ class batch:
     def add_bottleneck(self, a, b):
         s = DeferredScalar(self)
         self.bpairs.append((a, b, s))
+        return s
+
+    def add_wasserstein_q(self, a, b, order, ground):
+        s = DeferredScalar(self)
+        self.qpairs.append((a, b, (order, ground), s))
         return s
 
     def add_sliced(self, a, b, dirs, M):
@@ -454,6 +474,7 @@ class batch:
         self.clouds, self.dms, self.pairs, self.feats, self.bpairs, self.lands = [], [], [], [], [], []
         imgs, self.imgs = self.imgs, []
         spairs, self.spairs = self.spairs, []
+        qpairs, self.qpairs = self.qpairs, []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -518,6 +539,25 @@ class batch:
                     ra, ca = engine.pack_diagrams([g[0] for g in good])
                     rb, cb = engine.pack_diagrams([g[1] for g in good])
                     out, st = engine.sliced_wasserstein_batch(ra, ca, rb, cb, d, want_status=True)
+                    for i, g in enumerate(good):
+                        g[2]._value = float(out[i]) if st[i] == 0 else np.nan
+                except Exception:
+                    pass
+        if qpairs:
+            # one launch per (order, ground); a malformed pair or a bad (order, ground) is NaN by itself
+            groups = {}
+            for p in qpairs:
+                p[3]._value = np.nan
+                try:
+                    g = (_clean_pair_diagram(self._resolve(p[0])), _clean_pair_diagram(self._resolve(p[1])), p[3])
+                    groups.setdefault(p[2], []).append(g)
+                except Exception:
+                    pass
+            for (order, ground), good in groups.items():
+                try:
+                    ra, ca = engine.pack_diagrams([g[0] for g in good])
+                    rb, cb = engine.pack_diagrams([g[1] for g in good])
+                    out, st = engine.wasserstein_q_batch(ra, ca, rb, cb, order=order, ground=ground, want_status=True)
                     for i, g in enumerate(good):
                         g[2]._value = float(out[i]) if st[i] == 0 else np.nan
                 except Exception:
