@@ -24,7 +24,7 @@
 // and TDA_WIN_NOT_CONVERGED.
 // Which pair a wavefront solves is a template parameter of the kernel (resolve(pr, ia, ib), the shape of
 // wasserstein.hip's pair sources).
-#include "common.h"
+#include "assign_dev.h"         // ws_index_pairs, the pair source of the explicit index arrays
 
 #ifdef TDA_PROFILE
 // cycles: [0] load, [1] bounds, [2] candidate scans, [3] adjacency builds, [4] cover searches; counts: [5] pairs,
@@ -48,17 +48,6 @@ extern "C" __attribute__((visibility("default"))) int tda_profile_read_bn(unsign
 
 #define BN_MAX_POINTS 512       // points per diagram the kernel has LDS and lanes for (8 per lane)
 #define BN_MAX_PROBES 64        // one per bit of the pattern of a non-negative double
-
-// explicit index arrays (NULL = identity): every workgroup has a pair
-struct bn_index_pairs {
-    const int* idx_a; const int* idx_b;
-    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
-    {
-        ia = idx_a ? idx_a[pr] : pr;
-        ib = idx_b ? idx_b[pr] : pr;
-        return true;
-    }
-};
 
 // the same bits whichever diagram x comes from: fabs(x - y) == fabs(y - x)
 __device__ __forceinline__ double bn_cost(double xb, double xd, double yb, double yd)
@@ -373,6 +362,6 @@ tda_status launch_bottleneck(tda_ctx* ctx, const double* dgm_a, const int* cnt_a
                              const int* cnt_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
                              double* out, int* status, hipStream_t st)
 {
-    return launch_bottleneck_src(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, bn_index_pairs{idx_a, idx_b}, n_pairs, out,
+    return launch_bottleneck_src(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, ws_index_pairs{idx_a, idx_b}, n_pairs, out,
                                  status, st);
 }

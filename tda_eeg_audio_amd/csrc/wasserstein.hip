@@ -14,10 +14,12 @@
 // pair per wavefront: columns live on lanes (CW per lane), one Dijkstra step = CW LDS reads
 // per lane + one wave min-reduction.  At most R(R+1)/2 steps for R rows.
 // The returned value re-sums the ORIGINAL costs (C_ij, s_i, t_j) of the optimal matching.
+// The pair prologue, the solver and the re-summation are assign_dev.h's, shared with wasserstein_q.hip; this file
+// keeps what is order 1's own: the cost, the pruning margin and tests, the equal-birth wavefront, the pair sources
+// other than index arrays, the matrix kernels and the two-launch scheme.
 // Which pair a wavefront solves is a template parameter of the kernel: explicit index arrays (tda_wasserstein_batch)
 // or group tables read on the device (tda_wasserstein_cross_dev: scripts/matched_vs_mismatched.py:86-95).
-#include "common.h"
-#include <type_traits>
+#include "assign_dev.h"
 
 #ifdef TDA_PROFILE
 __device__ unsigned long long g_prof_ws[16];
@@ -41,23 +43,6 @@ extern "C" __attribute__((visibility("default"))) int tda_profile_read_ws(unsign
 #define WS_CP 0.7071067811865476   // np.cos(np.pi/4)
 #define WS_SP 0.7071067811865475   // np.sin(np.pi/4)
 
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_min_f64_ws(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // C(a_i, b_j) with a from the FIRST diagram and b from the SECOND, independent of which one
 // plays the row role (mirrors oracle/tda_oracle.c::orc_wasserstein)
 __device__ __forceinline__ double ws_cost(double ab, double ad, double bb, double bd)
@@ -71,12 +56,6 @@ __device__ __forceinline__ double ws_cost(double ab, double ad, double bb, doubl
     if (!(d2 > 0.0)) d2 = 0.0;
     return sqrt_rn(d2);                         // (sqrt() bit for bit, six instructions less: common.h)
 }
-
-// What tda_set_wasserstein_pruning / tda_set_wasserstein_counter hand to the kernels.
-struct ws_opts {
-    unsigned long long* ctr;    // NULL, or device u64[3]: short cuts, rows + columns trimmed, pairs solved
-    int prune;
-};
 
 // ---- the margin of the pruning tests ----
 // ws_solve leaves out cells whose gain g = min(0, C - s - t) is known to be 0.  What has to be 0 is the COMPUTED
@@ -96,18 +75,8 @@ struct ws_opts {
 #define WS_PRUNE_ABS 1e-150
 #define WS_PRUNE_MAX 1e150
 
-// Where workgroup pr finds its pair: the kernel's compile-time switch (one solver, two prologues).
-// ws_index_pairs: explicit index arrays (NULL = identity), every workgroup has a pair.  Two pointers, laid out as
-// the two kernel arguments they replace.
-struct ws_index_pairs {
-    const int* idx_a; const int* idx_b;
-    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
-    {
-        ia = idx_a ? idx_a[pr] : pr;
-        ib = idx_b ? idx_b[pr] : pr;
-        return true;
-    }
-};
+// Where workgroup pr finds its pair: the kernel's compile-time switch (one solver, three sources).
+// ws_index_pairs (assign_dev.h): explicit index arrays, every workgroup has a pair.
 // ws_table_pairs: grouped diagrams paired by position (mvm:89-93).  A diagram pr, at position i of its group g =
 // grp_a[pr], is paired with B diagram seg_off_b[p] + i of the group p = partner_seg[g] -- if g has a partner, the
 // partner's group is that long, and that B diagram is a diagram at all (mvm:60 leaves out clouds with < 3 points).
@@ -158,43 +127,21 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     const int lane = lane_id();
     unsigned long long wt0 = WCLK();
     (void)wt0;
-    // LDS: row points (b,d,s) | u[rows] | col points (b,d,t) | owner[cols] | |y|^2 of the columns (1-D path)
-    double* rb = reinterpret_cast<double*>(smem);
-    double* rd = rb + max_rows;
-    double* rs = rd + max_rows;
-    double* ru = rs + max_rows;
-    double* cb = ru + max_rows;
-    double* cd = cb + max_cols;
-    double* ct = cd + max_cols;
-    int* owner = reinterpret_cast<int*>(ct + max_cols);                 // max_cols ints (padded to 8 B)
-    double* G = ct + max_cols + ((max_cols + 1) >> 1);                  // max_cols doubles
+    // LDS: the solver's arrays (assign_dev.h) | |y|^2 of the columns (1-D path)
+    const assign_lds L(smem, max_rows, max_cols);
+    double* const rb = L.rb; double* const rd = L.rd; double* const rs = L.rs;
+    double* const cb = L.cb; double* const cd = L.cd; double* const ct = L.ct;
+    double* G = L.end();                                                // max_cols doubles
 
     int ia, ib;
     if (!src.resolve(pr, ia, ib)) {                                     // no pair: leave before the solver
         if (lane == 0) { out[pr] = __longlong_as_double(0x7ff8000000000000ll); status[pr] = TDA_WIN_NO_PAIR; }
         return;
     }
-    const double* A = dgm_a + (size_t)ia * cap_a * 2;
-    const double* B = dgm_b + (size_t)ib * cap_b * 2;
-    int ka = cnt_a[ia]; ka = ka < cap_a ? ka : cap_a; ka = ka < 0 ? 0 : ka;
-    int kb = cnt_b[ib]; kb = kb < cap_b ? kb : cap_b; kb = kb < 0 ? 0 : kb;
-    // count finite rows (utils.py:185-186)
-    int M = 0, N = 0;
-    for (int i0 = 0; i0 < ka; i0 += 64) {
-        const int i = i0 + lane;
-        M += __popcll(__ballot(i < ka && isfinite(A[2 * i]) && isfinite(A[2 * i + 1])));
-    }
-    for (int i0 = 0; i0 < kb; i0 += 64) {
-        const int i = i0 + lane;
-        N += __popcll(__ballot(i < kb && isfinite(B[2 * i]) && isfinite(B[2 * i + 1])));
-    }
-    const int Me = M > 0 ? M : 1, Ne = N > 0 ? N : 1;    // empty -> {(0,0)}  (utils.py:184,187)
-    // rows = smaller diagram
-    const bool a_is_row = Me <= Ne;
-    const int R = a_is_row ? Me : Ne, Cn = a_is_row ? Ne : Me;
-    const int cw_used = (Cn + 63) >> 6;                // column slots per lane actually in use
-    if (R > max_rows || Cn > max_cols || Cn > 64 * CW) {
-        if (lane == 0) {
+    assign_shape S;
+    auto diag = [](double b, double d) -> double { return fma(d, WS_CP, -(b * WS_SP)); };
+    if (!assign_load_pair<CW>(dgm_a, cnt_a, cap_a, ia, dgm_b, cnt_b, cap_b, ib, L, diag, S)) {
+        if (lane == 0) {                                                // does not fit this launch
             if (mode == 1) {
                 status[pr] = WS_DEFERRED;
                 if (list) list[4 + atomicAdd(&list[0], 1)] = pr;        // (one wave and one pair per workgroup: nothing to aggregate)
@@ -203,36 +150,8 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
         }
         return;
     }
-    // load finite points, preserving order
-    {
-        double* pb = a_is_row ? rb : cb; double* pd = a_is_row ? rd : cd; double* pc = a_is_row ? rs : ct;
-        int m = 0;
-        for (int i0 = 0; i0 < ka; i0 += 64) {
-            const int i = i0 + lane;
-            double b = 0, d = 0; bool fin = false;
-            if (i < ka) { b = A[2 * i]; d = A[2 * i + 1]; fin = isfinite(b) && isfinite(d); }
-            const u64 bal = __ballot(fin);
-            const int pos = m + __popcll(bal & ((1ull << lane) - 1ull));
-            if (fin) { pb[pos] = b; pd[pos] = d; pc[pos] = fma(d, WS_CP, -(b * WS_SP)); }
-            m += __popcll(bal);
-        }
-        if (M == 0 && lane == 0) { pb[0] = 0.0; pd[0] = 0.0; pc[0] = 0.0; }
-    }
-    {
-        double* pb = a_is_row ? cb : rb; double* pd = a_is_row ? cd : rd; double* pc = a_is_row ? ct : rs;
-        int m = 0;
-        for (int i0 = 0; i0 < kb; i0 += 64) {
-            const int i = i0 + lane;
-            double b = 0, d = 0; bool fin = false;
-            if (i < kb) { b = B[2 * i]; d = B[2 * i + 1]; fin = isfinite(b) && isfinite(d); }
-            const u64 bal = __ballot(fin);
-            const int pos = m + __popcll(bal & ((1ull << lane) - 1ull));
-            if (fin) { pb[pos] = b; pd[pos] = d; pc[pos] = fma(d, WS_CP, -(b * WS_SP)); }
-            m += __popcll(bal);
-        }
-        if (N == 0 && lane == 0) { pb[0] = 0.0; pd[0] = 0.0; pc[0] = 0.0; }
-    }
-    __syncthreads();
+    const bool a_is_row = S.a_is_row;
+    const int R = S.R, Cn = S.Cn;
 
     auto cfull = [&](int i, int j) -> double {   // original point-to-point cost of row i, col j
         return a_is_row ? ws_cost(rb[i], rd[i], cb[j], cd[j]) : ws_cost(cb[j], cd[j], rb[i], rd[i]);
@@ -241,8 +160,6 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
         const double g = cfull(i, j) - rs[i] - ct[j];
         return g < 0.0 ? g : 0.0;
     };
-    for (int i = lane; i < R; i += 64) ru[i] = 0.0;
-    __syncthreads();
     WPROF(0, WCLK() - wt0); wt0 = WCLK();
     WPROF(4, 1); WPROF(5, R); WPROF(6, Cn);
     unsigned long long n_cut = 0, n_trim = 0;           // for opt.ctr
@@ -263,17 +180,8 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     // hundreds of Dijkstra steps.  Same gains g_ij as the general solver (so the same rounding of
     // C_ij); the value differs from the assignment optimum by at most the rounding noise of C.
     {
-        bool ok = R <= 64;
         const double b0 = rb[0];
-        for (int i0 = 0; i0 < R; i0 += 64) {
-            const int i = i0 + lane;
-            ok = ok && !__ballot(i < R && (rb[i] != b0 || (i + 1 < R && rd[i + 1] < rd[i])));
-        }
-        for (int j0 = 0; j0 < Cn; j0 += 64) {
-            const int j = j0 + lane;
-            ok = ok && !__ballot(j < Cn && (cb[j] != b0 || (j + 1 < Cn && cd[j + 1] < cd[j])));
-        }
-        if (ok) {
+        if (assign_on_sorted_line(S, L)) {
             // ---- live ranges ----
             // With p = d - b0 the persistence of a row and q of a column, the true gain of a cell is at least
             // max(p (1-c) - q (1+c), q (1-c) - p (1+c)), c = 1/sqrt 2 (|p - q| >= either difference): a column is dead
@@ -371,24 +279,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     // break ties differently.
     bool all_dead = false;
     if (opt.prune) {
-        const double INFP = __longlong_as_double(0x7ff0000000000000ll);
-        double rb_lo = INFP, rb_hi = -INFP, rd_lo = INFP, rd_hi = -INFP, s_hi = -INFP;
-        double cb_lo = INFP, cb_hi = -INFP, cd_lo = INFP, cd_hi = -INFP, t_hi = -INFP;
-        for (int i = lane; i < R; i += 64) {
-            rb_lo = fmin(rb_lo, rb[i]); rb_hi = fmax(rb_hi, rb[i]);
-            rd_lo = fmin(rd_lo, rd[i]); rd_hi = fmax(rd_hi, rd[i]);
-            s_hi = fmax(s_hi, rs[i]);
-        }
-        for (int j = lane; j < Cn; j += 64) {
-            cb_lo = fmin(cb_lo, cb[j]); cb_hi = fmax(cb_hi, cb[j]);
-            cd_lo = fmin(cd_lo, cd[j]); cd_hi = fmax(cd_hi, cd[j]);
-            t_hi = fmax(t_hi, ct[j]);
-        }
-        rb_lo = wave_min_f64_dpp(rb_lo); rb_hi = wave_max_f64_dpp(rb_hi);
-        rd_lo = wave_min_f64_dpp(rd_lo); rd_hi = wave_max_f64_dpp(rd_hi);
-        cb_lo = wave_min_f64_dpp(cb_lo); cb_hi = wave_max_f64_dpp(cb_hi);
-        cd_lo = wave_min_f64_dpp(cd_lo); cd_hi = wave_max_f64_dpp(cd_hi);
-        s_hi = wave_max_f64_dpp(s_hi); t_hi = wave_max_f64_dpp(t_hi);
+        const auto [rb_lo, rb_hi, rd_lo, rd_hi, s_hi, cb_lo, cb_hi, cd_lo, cd_hi, t_hi] = assign_box_stats(S, L);
         const double mx = fmax(fmax(fmax(fabs(rb_lo), fabs(rb_hi)), fmax(fabs(rd_lo), fabs(rd_hi))),
                                fmax(fmax(fabs(cb_lo), fabs(cb_hi)), fmax(fabs(cd_lo), fabs(cd_hi))));
         if (mx < WS_PRUNE_MAX) {
@@ -411,155 +302,8 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     }
     WPROF(7, all_dead ? 1 : 0);
 
-    // per-lane state, all in registers: column j = lane + 64*c holds v, minv, way, used, prow;
-    // row i = lane + 64*c holds its dual u and the "row is in the alternating tree" flag.
-    // The Dijkstra step therefore touches LDS only for the cost row (one read per column slot).
-    double v[CW], minv[CW], u[CW];
-    int prow[CW], way[CW];
-    bool used[CW], rowin[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) { v[c] = 0.0; u[c] = 0.0; prow[c] = -1; way[c] = -1; }
-
-    const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    bool failed = false;
-    int nsteps = 0;
-    (void)nsteps;
-    // ---- row-reduction start: u_i = min_j g_ij, v = 0 is dual feasible; every row whose arg-min
-    // column is not claimed by a lower row is assigned at once (tight pair), the rest augment ----
-    bool rowdone[CW];
-    if (!all_dead) {
-        int myarg[CW];
-        for (int j = lane; j < Cn; j += 64) owner[j] = 0x7fffffff;
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            const int r = lane + 64 * c;
-            myarg[c] = -1; rowdone[c] = false;
-            if (c < cw_used && r < R) {
-                // scan starts at column r (rotated): rows whose gains tie (typically all zero: the
-                // point prefers the diagonal) then claim DIFFERENT columns instead of all column 0
-                double mn = INF; int arg = 0;
-                int j = r < Cn ? r : 0;
-#pragma unroll 4
-                for (int t = 0; t < Cn; ++t) {
-                    const double g = gain(r, j);
-                    if (g < mn) { mn = g; arg = j; }
-                    j = (j + 1 == Cn) ? 0 : j + 1;
-                }
-                u[c] = mn; myarg[c] = arg;
-                atomicMin(&owner[arg], r);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            if (myarg[c] >= 0) rowdone[c] = owner[myarg[c]] == lane + 64 * c;
-            const int j = lane + 64 * c;
-            if (c < cw_used && j < Cn) { const int o = owner[j]; prow[c] = (o != 0x7fffffff) ? o : -1; }
-        }
-    }
-    for (int i = 0; i < R && !failed && !all_dead; ++i) {
-        {
-            int dn = 0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (i >> 6)) dn = (int)rl32((u32)(rowdone[c] ? 1 : 0), i & 63);
-            if (dn) continue;
-        }
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { minv[c] = INF; used[c] = false; rowin[c] = (lane + 64 * c) == i; }
-        int i0 = i, j0 = -1;            // j0 = -1 is the virtual start column holding row i
-        int steps = 0;
-        while (true) {
-            double ui0 = 0.0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (i0 >> 6)) ui0 = uni_f64(u[c], i0 & 63);
-            // branch-free column update: all cost reads are issued first, invalid / used columns
-            // carry +inf candidates
-            double best = INF, gg[CW];
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                const int j = lane + 64 * c;
-                const int jc = j < Cn ? j : Cn - 1;
-                gg[c] = gain(i0, jc);
-            }
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                const bool open = (lane + 64 * c) < Cn && !used[c];
-                const double cur = gg[c] - ui0 - v[c];
-                const bool upd = open && cur < minv[c];
-                minv[c] = upd ? cur : minv[c];
-                way[c] = upd ? j0 : way[c];
-                const double cnd = open ? minv[c] : INF;
-                best = cnd < best ? cnd : best;
-            }
-            const double delta = wave_min_f64_dpp(best);
-            ++nsteps;
-            // a column attaining delta; ties go to an unassigned column (ends the path at once),
-            // the rule scipy's linear_sum_assignment uses too
-            int j1 = -1, j1free = -1;
-#pragma unroll
-            for (int c = CW - 1; c >= 0; --c) {
-                if (c >= cw_used) continue;
-                const int j = lane + 64 * c;
-                const bool at = j < Cn && !used[c] && minv[c] == delta;
-                const u64 bal = __ballot(at);
-                const u64 balf = __ballot(at && prow[c] < 0);
-                if (bal) j1 = 64 * c + __builtin_ctzll(bal);
-                if (balf) j1free = 64 * c + __builtin_ctzll(balf);
-            }
-            if (j1free >= 0) j1 = j1free;
-            if (j1 < 0 || !(delta < INF) || ++steps > Cn + 2) { failed = true; break; }
-            // dual update: rows in the tree, used / unused columns
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                if (rowin[c]) u[c] += delta;
-                if (used[c]) v[c] -= delta;
-                else minv[c] -= delta;
-            }
-            // mark j1 used, continue from its row
-            const int c1 = j1 >> 6, l1 = j1 & 63;
-            int p1 = -1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c1) {
-                    p1 = (int)rl32((u32)prow[c], l1);
-                    if (lane == l1) used[c] = true;
-                }
-            j0 = j1;
-            if (p1 < 0) break;          // free column reached: augment
-            i0 = p1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (p1 >> 6) && lane == (p1 & 63)) rowin[c] = true;
-        }
-        if (failed) break;
-        // augment along way[] back to the virtual column
-        int guard = 0;
-        while (j0 >= 0 && guard++ < Cn + 2) {
-            const int c0 = j0 >> 6, l0 = j0 & 63;
-            int jprev = -1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c0) jprev = (int)rl32((u32)way[c], l0);
-            int newrow = i;
-            if (jprev >= 0) {
-                const int cp = jprev >> 6, lp = jprev & 63;
-#pragma unroll
-                for (int c = 0; c < CW; ++c)
-                    if (c == cp) newrow = (int)rl32((u32)prow[c], lp);
-            }
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c0 && lane == l0) prow[c] = newrow;
-            j0 = jprev;
-        }
-    }
-    if (failed) {
+    int prow[CW], nsteps = 0;
+    if (!assign_solve<CW>(S, L, gain, all_dead, prow, nsteps)) {
         if (lane == 0) { out[pr] = __longlong_as_double(0x7ff8000000000000ll); status[pr] = TDA_WIN_NOT_CONVERGED; }
         count();
         return;
@@ -567,27 +311,7 @@ __device__ __forceinline__ void ws_solve(const double* __restrict__ dgm_a, const
     WPROF(1, WCLK() - wt0); wt0 = WCLK();
     WPROF(3, nsteps);
     // total = sum over real matches of C_ij + unmatched rows' s + unmatched cols' t
-    double part = 0.0;
-    __syncthreads();
-    // reuse ru[] as "row is really matched" flag
-    for (int i = lane; i < R; i += 64) ru[i] = 0.0;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = lane + 64 * c;
-        if (j < Cn) {
-            bool real = false;
-            if (prow[c] >= 0) {
-                const double cf = cfull(prow[c], j);
-                if (cf - rs[prow[c]] - ct[j] < 0.0) { real = true; part += cf; ru[prow[c]] = 1.0; }
-            }
-            if (!real) part += ct[j];
-        }
-    }
-    __syncthreads();
-    for (int i = lane; i < R; i += 64)
-        if (ru[i] == 0.0) part += rs[i];
-    const double total = wave_sum_f64(part);
+    const double total = assign_resum<CW>(S, L, cfull, prow);
     if (lane == 0) { out[pr] = total; status[pr] = 0; }
     count();
     WPROF(2, WCLK() - wt0);
@@ -672,25 +396,22 @@ static tda_status launch_wasserstein_src(tda_ctx* ctx, const double* dgm_a, cons
         hipLaunchKernelGGL((wasserstein_kernel<1, SRC>), dim3(n_pairs), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
                            cap_b, src, n_pairs, sr, 64, out, status, 1, list, opt);
     }
-#define WS_LAUNCH(CWV)                                                                                         \
-    do {                                                                                                       \
-        auto kern = wasserstein_kernel<CWV, SRC>;                                                              \
-        auto lkern = wasserstein_list_kernel<CWV, SRC>;                                                        \
-        if (lds > 48 * 1024)                                                                                   \
-            TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern)                       \
-                                                  : reinterpret_cast<const void*>(kern),                       \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        if (list)                                                                                              \
-            hipLaunchKernelGGL(lkern, dim3(n_pairs < 256 ? n_pairs : 256), dim3(64), lds, st, dgm_a, cnt_a,    \
-                               cap_a, dgm_b, cnt_b, cap_b, src, n_pairs, max_rows, max_cols, out, status, list, opt); \
-        else                                                                                                   \
-            hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,      \
-                               cap_b, src, n_pairs, max_rows, max_cols, out, status, mode, (int*)nullptr, opt); \
-    } while (0)
-    if (max_cols <= 128) WS_LAUNCH(2);
-    else if (max_cols <= 256) WS_LAUNCH(4);
-    else WS_LAUNCH(8);
-#undef WS_LAUNCH
+    const tda_status rc = assign_with_cw(max_cols, [&](auto cw) -> tda_status {
+        constexpr int CWV = decltype(cw)::value;
+        auto kern = wasserstein_kernel<CWV, SRC>;
+        auto lkern = wasserstein_list_kernel<CWV, SRC>;
+        if (lds > 48 * 1024)
+            TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern) : reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (list)
+            hipLaunchKernelGGL(lkern, dim3(n_pairs < 256 ? n_pairs : 256), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
+                               cap_b, src, n_pairs, max_rows, max_cols, out, status, list, opt);
+        else
+            hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, n_pairs,
+                               max_rows, max_cols, out, status, mode, (int*)nullptr, opt);
+        return TDA_OK;
+    });
+    if (rc != TDA_OK) return rc;
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
@@ -895,25 +616,22 @@ tda_status launch_wasserstein_matrix(tda_ctx* ctx, const double* dgm_a, const in
         if (mode)
             hipLaunchKernelGGL(wasserstein_matrix_kernel<1>, dim3(n_e), dim3(64), lds_s, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b,
                                cap_b, M, e0, n_e, sr, 64, lds_solver_s, 1, list, opt);
-#define WS_MATRIX_LAUNCH(CWV)                                                                                  \
-    do {                                                                                                       \
-        auto kern = wasserstein_matrix_kernel<CWV>;                                                            \
-        auto lkern = wasserstein_matrix_list_kernel<CWV>;                                                      \
-        if (lds_w > 48 * 1024)                                                                                 \
-            TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern)                       \
-                                                  : reinterpret_cast<const void*>(kern),                       \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));         \
-        if (list)                                                                                              \
-            hipLaunchKernelGGL(lkern, dim3(n_e < WS_MATRIX_LIST_GRID ? n_e : WS_MATRIX_LIST_GRID), dim3(64), lds_w, st,  \
-                               dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e, max_rows, max_cols, lds_solver, list, opt); \
-        else                                                                                                   \
-            hipLaunchKernelGGL(kern, dim3(n_e), dim3(64), lds_w, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, \
-                               M, e0, n_e, max_rows, max_cols, lds_solver, mode, (int*)nullptr, opt);          \
-    } while (0)
-        if (max_cols <= 128) WS_MATRIX_LAUNCH(2);
-        else if (max_cols <= 256) WS_MATRIX_LAUNCH(4);
-        else WS_MATRIX_LAUNCH(8);
-#undef WS_MATRIX_LAUNCH
+        const tda_status rc = assign_with_cw(max_cols, [&](auto cw) -> tda_status {
+            constexpr int CWV = decltype(cw)::value;
+            auto kern = wasserstein_matrix_kernel<CWV>;
+            auto lkern = wasserstein_matrix_list_kernel<CWV>;
+            if (lds_w > 48 * 1024)
+                TDA_HIP(ctx, hipFuncSetAttribute(list ? reinterpret_cast<const void*>(lkern) : reinterpret_cast<const void*>(kern),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));
+            if (list)
+                hipLaunchKernelGGL(lkern, dim3(n_e < WS_MATRIX_LIST_GRID ? n_e : WS_MATRIX_LIST_GRID), dim3(64), lds_w, st, dgm_a,
+                                   cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e, max_rows, max_cols, lds_solver, list, opt);
+            else
+                hipLaunchKernelGGL(kern, dim3(n_e), dim3(64), lds_w, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, M, e0, n_e,
+                                   max_rows, max_cols, lds_solver, mode, (int*)nullptr, opt);
+            return TDA_OK;
+        });
+        if (rc != TDA_OK) return rc;
     }
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;

@@ -10,49 +10,22 @@
 // (order 1) or sqrt(V) (order 2).  The costs are symmetric in the two diagrams (fabs), so which one plays the row role
 // does not change a bit of any cost.
 //
-// The solver is the one of wasserstein.hip, restated here (that file is not touched, and nothing of it moved into a
-// header: a shared header has moved instructions in existing kernels before): the rectangular assignment with gains
-// g_ij = min(0, C_ij - s_i - t_j), rows = the smaller diagram, points and diagonal costs in LDS and no cost matrix,
-// duals and column state in registers across the lanes (CW column slots per lane), shortest augmenting paths after a
-// row-reduction start, and a returned value that re-sums the ORIGINAL costs of the optimal matching.  Two diagrams
-// whose points all have one birth and ascending deaths take the anti-diagonal recurrence instead (below).
+// The pair prologue, the solver and the re-summation are assign_dev.h's, the ones wasserstein.hip runs: the rectangular
+// assignment with gains g_ij = min(0, C_ij - s_i - t_j), rows = the smaller diagram, points and diagonal costs in LDS
+// and no cost matrix, shortest augmenting paths after a row-reduction start, and a returned value that re-sums the
+// ORIGINAL costs of the optimal matching.  This file hands in its costs and keeps its own pruning tests and its own
+// equal-birth recurrence: two diagrams whose points all have one birth and ascending deaths take that instead (below).
 // Order and ground metric are template parameters: a cell of the order-2 L2 solver has no root and no select.
 //
 // One launch, sized by the capacities of the two buffers (launch_bottleneck_src's): the small-launch-plus-list scheme
 // of the order-1 kernel is not part of this.
 //
-// Loop bounds, all known before the loop starts: rows to augment <= R; Dijkstra steps per row <= C + 2; path flips
-// <= C + 2; wavefront steps = live rows + live columns - 1.  A bound that is hit gives NaN and TDA_WIN_NOT_CONVERGED.
-#include "common.h"
-#include <type_traits>
+// Loop bounds: the solver's are in assign_dev.h; wavefront steps = live rows + live columns - 1.  A bound that is hit
+// gives NaN and TDA_WIN_NOT_CONVERGED.
+#include "assign_dev.h"
 
 #define WQ_MAX_POINTS 512       // points per diagram the kernel has LDS and lanes for (8 per lane)
 #define WQ_CP 0.7071067811865476
-
-// explicit index arrays (NULL = identity): every workgroup has a pair
-struct wq_index_pairs {
-    const int* idx_a; const int* idx_b;
-    __device__ __forceinline__ bool resolve(int pr, int& ia, int& ib) const
-    {
-        ia = idx_a ? idx_a[pr] : pr;
-        ib = idx_b ? idx_b[pr] : pr;
-        return true;
-    }
-};
-
-// What tda_set_wasserstein_pruning / tda_set_wasserstein_counter hand to the kernel.
-struct wq_opts {
-    unsigned long long* ctr;    // NULL, or device u64[3]: short cuts, rows + columns trimmed, pairs that had a pair to
-                                // solve (those that end with TDA_WIN_NOT_CONVERGED included)
-    int prune;
-};
-
-__device__ __forceinline__ double wq_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // the point cost from the two coordinate differences (both >= 0)
 template <int ORDER, int GROUND>
@@ -141,71 +114,32 @@ template <int CW, int ORDER, int GROUND, class SRC>
 __device__ __forceinline__ void wq_solve(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                                          const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                                          const SRC& src, int pr, int max_rows, int max_cols,
-                                         double* __restrict__ out, int* __restrict__ status, const wq_opts& opt,
+                                         double* __restrict__ out, int* __restrict__ status, const ws_opts& opt,
                                          unsigned char* smem)
 {
     const int lane = lane_id();
     const double QNAN = __longlong_as_double(0x7ff8000000000000ll);
-    const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    // LDS: row points (b,d,s) | u[rows] | col points (b,d,t) | owner[cols]
-    double* rb = reinterpret_cast<double*>(smem);
-    double* rd = rb + max_rows;
-    double* rs = rd + max_rows;
-    double* ru = rs + max_rows;
-    double* cb = ru + max_rows;
-    double* cd = cb + max_cols;
-    double* ct = cd + max_cols;
-    int* owner = reinterpret_cast<int*>(ct + max_cols);                 // max_cols ints (padded to 8 B)
+    const assign_lds L(smem, max_rows, max_cols);
+    double* const rb = L.rb; double* const rd = L.rd; double* const rs = L.rs;
+    double* const cb = L.cb; double* const cd = L.cd; double* const ct = L.ct;
 
     int ia, ib;
-    // (wq_index_pairs, the one source today, always has a pair: the branch is for a source that reads group tables, as
+    // (ws_index_pairs, the one source today, always has a pair: the branch is for a source that reads group tables, as
     // ws_table_pairs does, and no test can reach it until there is one)
     if (!src.resolve(pr, ia, ib)) {                                     // no pair: leave before the solver
         if (lane == 0) { out[pr] = QNAN; status[pr] = TDA_WIN_NO_PAIR; }
         return;
     }
-    const double* A = dgm_a + (size_t)ia * cap_a * 2;
-    const double* B = dgm_b + (size_t)ib * cap_b * 2;
-    int ka = uni(cnt_a[ia]); ka = ka < cap_a ? ka : cap_a; ka = ka < 0 ? 0 : ka;
-    int kb = uni(cnt_b[ib]); kb = kb < cap_b ? kb : cap_b; kb = kb < 0 ? 0 : kb;
-    int M = 0, N = 0;                                                   // finite rows (utils.py:185-186)
-    for (int i0 = 0; i0 < ka; i0 += 64) {
-        const int i = i0 + lane;
-        M += __popcll(__ballot(i < ka && isfinite(A[2 * i]) && isfinite(A[2 * i + 1])));
-    }
-    for (int i0 = 0; i0 < kb; i0 += 64) {
-        const int i = i0 + lane;
-        N += __popcll(__ballot(i < kb && isfinite(B[2 * i]) && isfinite(B[2 * i + 1])));
-    }
-    const int Me = M > 0 ? M : 1, Ne = N > 0 ? N : 1;                   // empty -> {(0,0)}  (utils.py:184,187)
-    const bool a_is_row = Me <= Ne;                                     // rows = the smaller diagram
-    const int R = a_is_row ? Me : Ne, Cn = a_is_row ? Ne : Me;
-    const int cw_used = (Cn + 63) >> 6;                                 // column slots per lane actually in use
-    if (R > max_rows || Cn > max_cols || Cn > 64 * CW) {                // more points than the launch has room for
-        if (lane == 0) {
+    assign_shape S;
+    auto diag = [](double b, double d) -> double { return wq_diag<ORDER, GROUND>(b, d); };
+    if (!assign_load_pair<CW>(dgm_a, cnt_a, cap_a, ia, dgm_b, cnt_b, cap_b, ib, L, diag, S)) {
+        if (lane == 0) {                                                // more points than the launch has room for
             out[pr] = QNAN; status[pr] = TDA_WIN_NOT_CONVERGED;
             if (opt.ctr) atomicAdd(&opt.ctr[2], 1ull);                  // counted like a pair whose solver hit a bound
         }
         return;
     }
-    // finite points, order kept, with their diagonal costs
-    auto load = [&](const double* __restrict__ P, int k, int n_fin, double* pb, double* pd, double* pc) {
-        int m = 0;
-        for (int i0 = 0; i0 < k; i0 += 64) {
-            const int i = i0 + lane;
-            double b = 0, d = 0; bool fin = false;
-            if (i < k) { b = P[2 * i]; d = P[2 * i + 1]; fin = isfinite(b) && isfinite(d); }
-            const u64 bal = __ballot(fin);
-            const int pos = m + __popcll(bal & ((1ull << lane) - 1ull));
-            if (fin) { pb[pos] = b; pd[pos] = d; pc[pos] = wq_diag<ORDER, GROUND>(b, d); }
-            m += __popcll(bal);
-        }
-        if (n_fin == 0 && lane == 0) { pb[0] = 0.0; pd[0] = 0.0; pc[0] = 0.0; }
-    };
-    if (a_is_row) { load(A, ka, M, rb, rd, rs); load(B, kb, N, cb, cd, ct); }
-    else { load(A, ka, M, cb, cd, ct); load(B, kb, N, rb, rd, rs); }
-    for (int i = lane; i < R; i += 64) ru[i] = 0.0;
-    __syncthreads();
+    const int R = S.R, Cn = S.Cn;
 
     auto cfull = [&](int i, int j) -> double {   // original point-to-point cost of row i, col j
         return wq_cost<ORDER, GROUND>(rb[i], rd[i], cb[j], cd[j]);
@@ -232,17 +166,8 @@ __device__ __forceinline__ void wq_solve(const double* __restrict__ dgm_a, const
     // over death-sorted diagrams: an anti-diagonal wavefront with one row per lane, R + C - 1 steps instead of hundreds
     // of Dijkstra steps.  Same gains g_ij as the general solver: dx is +0.0 here, and wq_cost_line() gives wq_cost()'s bits.
     {
-        bool ok = R <= 64;
         const double b0 = rb[0];
-        for (int i0 = 0; i0 < R; i0 += 64) {
-            const int i = i0 + lane;
-            ok = ok && !__ballot(i < R && (rb[i] != b0 || (i + 1 < R && rd[i + 1] < rd[i])));
-        }
-        for (int j0 = 0; j0 < Cn; j0 += 64) {
-            const int j = j0 + lane;
-            ok = ok && !__ballot(j < Cn && (cb[j] != b0 || (j + 1 < Cn && cd[j + 1] < cd[j])));
-        }
-        if (ok) {
+        if (assign_on_sorted_line(S, L)) {
             // ---- live ranges ----
             // With p the persistence of a row and q of a column, a cell with p >= cut q or q >= cut p (by the margins
             // above) has a computed gain of 0.  A column with cut q + abs <= p_min or q >= cut p_max + abs is dead for
@@ -305,7 +230,7 @@ __device__ __forceinline__ void wq_solve(const double* __restrict__ dgm_a, const
             double part = 0.0;
             for (int i = lane; i < R; i += 64) part += rs[i];
             for (int j = lane; j < Cn; j += 64) part += ct[j];
-            double total1d = wq_wave_sum(part) + fbest;
+            double total1d = wave_sum_f64(part) + fbest;
             // V >= 0; the sum of the diagonal costs and the sum of the gains are rounded separately, so a V of 0 may come
             // out a few ulps of the diagonal costs below it
             if (total1d < 0.0) total1d = 0.0;
@@ -323,23 +248,7 @@ __device__ __forceinline__ void wq_solve(const double* __restrict__ dgm_a, const
     // live cell runs the solver unchanged: compacting a partly live problem could break ties differently.
     bool all_dead = false;
     if (opt.prune) {
-        double rb_lo = INF, rb_hi = -INF, rd_lo = INF, rd_hi = -INF, s_hi = -INF;
-        double cb_lo = INF, cb_hi = -INF, cd_lo = INF, cd_hi = -INF, t_hi = -INF;
-        for (int i = lane; i < R; i += 64) {
-            rb_lo = fmin(rb_lo, rb[i]); rb_hi = fmax(rb_hi, rb[i]);
-            rd_lo = fmin(rd_lo, rd[i]); rd_hi = fmax(rd_hi, rd[i]);
-            s_hi = fmax(s_hi, rs[i]);
-        }
-        for (int j = lane; j < Cn; j += 64) {
-            cb_lo = fmin(cb_lo, cb[j]); cb_hi = fmax(cb_hi, cb[j]);
-            cd_lo = fmin(cd_lo, cd[j]); cd_hi = fmax(cd_hi, cd[j]);
-            t_hi = fmax(t_hi, ct[j]);
-        }
-        rb_lo = wave_min_f64_dpp(rb_lo); rb_hi = wave_max_f64_dpp(rb_hi);
-        rd_lo = wave_min_f64_dpp(rd_lo); rd_hi = wave_max_f64_dpp(rd_hi);
-        cb_lo = wave_min_f64_dpp(cb_lo); cb_hi = wave_max_f64_dpp(cb_hi);
-        cd_lo = wave_min_f64_dpp(cd_lo); cd_hi = wave_max_f64_dpp(cd_hi);
-        s_hi = wave_max_f64_dpp(s_hi); t_hi = wave_max_f64_dpp(t_hi);
+        const auto [rb_lo, rb_hi, rd_lo, rd_hi, s_hi, cb_lo, cb_hi, cd_lo, cd_hi, t_hi] = assign_box_stats(S, L);
         const double k = 1.0 + WQ_PRUNE_REL;
         const double gx = fmax(0.0, fmax(cb_lo - rb_hi, rb_lo - cb_hi));
         const double gy = fmax(0.0, fmax(cd_lo - rd_hi, rd_lo - cd_hi));
@@ -357,180 +266,14 @@ __device__ __forceinline__ void wq_solve(const double* __restrict__ dgm_a, const
         if (all_dead) n_cut = 1;
     }
 
-    // per-lane state, all in registers: column j = lane + 64*c holds v, minv, way, used, prow;
-    // row i = lane + 64*c holds its dual u and the "row is in the alternating tree" flag.
-    // The Dijkstra step therefore touches LDS only for the cost row (one read per column slot).
-    double v[CW], minv[CW], u[CW];
-    int prow[CW], way[CW];
-    bool used[CW], rowin[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) { v[c] = 0.0; u[c] = 0.0; prow[c] = -1; way[c] = -1; }
-
-    bool failed = false;
-    // ---- row-reduction start: u_i = min_j g_ij, v = 0 is dual feasible; every row whose arg-min
-    // column is not claimed by a lower row is assigned at once (tight pair), the rest augment ----
-    bool rowdone[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) rowdone[c] = false;
-    if (!all_dead) {
-        int myarg[CW];
-        for (int j = lane; j < Cn; j += 64) owner[j] = 0x7fffffff;
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            const int r = lane + 64 * c;
-            myarg[c] = -1;
-            if (c < cw_used && r < R) {
-                // scan starts at column r (rotated): rows whose gains tie (typically all zero: the
-                // point prefers the diagonal) then claim DIFFERENT columns instead of all column 0
-                double mn = INF; int arg = 0;
-                int j = r < Cn ? r : 0;
-#pragma unroll 4
-                for (int t = 0; t < Cn; ++t) {
-                    const double g = gain(r, j);
-                    if (g < mn) { mn = g; arg = j; }
-                    j = (j + 1 == Cn) ? 0 : j + 1;
-                }
-                u[c] = mn; myarg[c] = arg;
-                atomicMin(&owner[arg], r);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            if (myarg[c] >= 0) rowdone[c] = owner[myarg[c]] == lane + 64 * c;
-            const int j = lane + 64 * c;
-            if (c < cw_used && j < Cn) { const int o = owner[j]; prow[c] = (o != 0x7fffffff) ? o : -1; }
-        }
-    }
-    for (int i = 0; i < R && !failed && !all_dead; ++i) {
-        {
-            int dn = 0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (i >> 6)) dn = (int)rl32((u32)(rowdone[c] ? 1 : 0), i & 63);
-            if (dn) continue;
-        }
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { minv[c] = INF; used[c] = false; rowin[c] = (lane + 64 * c) == i; }
-        int i0 = i, j0 = -1;            // j0 = -1 is the virtual start column holding row i
-        int steps = 0;
-        while (true) {
-            double ui0 = 0.0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (i0 >> 6)) ui0 = uni_f64(u[c], i0 & 63);
-            // branch-free column update: all cost reads are issued first, invalid / used columns
-            // carry +inf candidates
-            double best = INF, gg[CW];
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                const int j = lane + 64 * c;
-                const int jc = j < Cn ? j : Cn - 1;
-                gg[c] = gain(i0, jc);
-            }
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                const bool open = (lane + 64 * c) < Cn && !used[c];
-                const double cur = gg[c] - ui0 - v[c];
-                const bool upd = open && cur < minv[c];
-                minv[c] = upd ? cur : minv[c];
-                way[c] = upd ? j0 : way[c];
-                const double cnd = open ? minv[c] : INF;
-                best = cnd < best ? cnd : best;
-            }
-            const double delta = wave_min_f64_dpp(best);
-            // a column attaining delta; ties go to an unassigned column (ends the path at once),
-            // the rule scipy's linear_sum_assignment uses too
-            int j1 = -1, j1free = -1;
-#pragma unroll
-            for (int c = CW - 1; c >= 0; --c) {
-                if (c >= cw_used) continue;
-                const int j = lane + 64 * c;
-                const bool at = j < Cn && !used[c] && minv[c] == delta;
-                const u64 bal = __ballot(at);
-                const u64 balf = __ballot(at && prow[c] < 0);
-                if (bal) j1 = 64 * c + __builtin_ctzll(bal);
-                if (balf) j1free = 64 * c + __builtin_ctzll(balf);
-            }
-            if (j1free >= 0) j1 = j1free;
-            if (j1 < 0 || !(delta < INF) || ++steps > Cn + 2) { failed = true; break; }
-            // dual update: rows in the tree, used / unused columns
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                if (c >= cw_used) break;
-                if (rowin[c]) u[c] += delta;
-                if (used[c]) v[c] -= delta;
-                else minv[c] -= delta;
-            }
-            // mark j1 used, continue from its row
-            const int c1 = j1 >> 6, l1 = j1 & 63;
-            int p1 = -1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c1) {
-                    p1 = (int)rl32((u32)prow[c], l1);
-                    if (lane == l1) used[c] = true;
-                }
-            j0 = j1;
-            if (p1 < 0) break;          // free column reached: augment
-            i0 = p1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == (p1 >> 6) && lane == (p1 & 63)) rowin[c] = true;
-        }
-        if (failed) break;
-        // augment along way[] back to the virtual column
-        int guard = 0;
-        while (j0 >= 0 && guard++ < Cn + 2) {
-            const int c0 = j0 >> 6, l0 = j0 & 63;
-            int jprev = -1;
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c0) jprev = (int)rl32((u32)way[c], l0);
-            int newrow = i;
-            if (jprev >= 0) {
-                const int cp = jprev >> 6, lp = jprev & 63;
-#pragma unroll
-                for (int c = 0; c < CW; ++c)
-                    if (c == cp) newrow = (int)rl32((u32)prow[c], lp);
-            }
-#pragma unroll
-            for (int c = 0; c < CW; ++c)
-                if (c == c0 && lane == l0) prow[c] = newrow;
-            j0 = jprev;
-        }
-        if (j0 >= 0) failed = true;     // the flips ran into their bound
-    }
-    if (failed) {
+    int prow[CW], nsteps = 0;
+    if (!assign_solve<CW>(S, L, gain, all_dead, prow, nsteps)) {
         if (lane == 0) { out[pr] = QNAN; status[pr] = TDA_WIN_NOT_CONVERGED; }
         count();
         return;
     }
     // V = sum over real matches of C_ij + unmatched rows' s + unmatched cols' t
-    double part = 0.0;
-    __syncthreads();
-    // reuse ru[] as "row is really matched" flag
-    for (int i = lane; i < R; i += 64) ru[i] = 0.0;
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = lane + 64 * c;
-        if (j < Cn) {
-            bool real = false;
-            if (prow[c] >= 0) {
-                const double cf = cfull(prow[c], j);
-                if (cf - rs[prow[c]] - ct[j] < 0.0) { real = true; part += cf; ru[prow[c]] = 1.0; }
-            }
-            if (!real) part += ct[j];
-        }
-    }
-    __syncthreads();
-    for (int i = lane; i < R; i += 64)
-        if (ru[i] == 0.0) part += rs[i];
-    const double total = wq_wave_sum(part);
+    const double total = assign_resum<CW>(S, L, cfull, prow);
     if (lane == 0) { out[pr] = finish(total); status[pr] = 0; }
     count();
 }
@@ -540,7 +283,7 @@ __global__ void __launch_bounds__(64)
 wasserstein_q_kernel(const double* __restrict__ dgm_a, const int* __restrict__ cnt_a, int cap_a,
                      const double* __restrict__ dgm_b, const int* __restrict__ cnt_b, int cap_b,
                      const SRC src, int n_pairs, int max_rows, int max_cols,
-                     double* __restrict__ out, int* __restrict__ status, const wq_opts opt)
+                     double* __restrict__ out, int* __restrict__ status, const ws_opts opt)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int pr = blockIdx.x;
@@ -559,19 +302,15 @@ static tda_status launch_wq_src(tda_ctx* ctx, const double* dgm_a, const int* cn
 {
     const int max_a = cap_a < WQ_MAX_POINTS ? cap_a : WQ_MAX_POINTS, max_b = cap_b < WQ_MAX_POINTS ? cap_b : WQ_MAX_POINTS;
     const int max_rows = max_a < max_b ? max_a : max_b, max_cols = max_a < max_b ? max_b : max_a;
-    const wq_opts opt{ctx->ws_ctr, ctx->ws_prune};
-    // rows: b, d, s, u; columns: b, d, t, owner (ints, padded to 8 B).  30.5 KB at 512 x 512.
+    const ws_opts opt{ctx->ws_ctr, ctx->ws_prune};
+    // assign_lds: rows b, d, s, u; columns b, d, t, owner (ints, padded to 8 B).  30.5 KB at 512 x 512.
     const size_t lds = (size_t)(4 * max_rows + 3 * max_cols + ((max_cols + 1) >> 1)) * 8;
-#define WQ_LAUNCH(CWV)                                                                                         \
-    do {                                                                                                       \
-        auto kern = wasserstein_q_kernel<CWV, ORDER, GROUND, SRC>;                                             \
-        hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b,   \
-                           src, n_pairs, max_rows, max_cols, out, status, opt);                                \
-    } while (0)
-    if (max_cols <= 128) WQ_LAUNCH(2);
-    else if (max_cols <= 256) WQ_LAUNCH(4);
-    else WQ_LAUNCH(8);
-#undef WQ_LAUNCH
+    assign_with_cw(max_cols, [&](auto cw) -> tda_status {
+        auto kern = wasserstein_q_kernel<decltype(cw)::value, ORDER, GROUND, SRC>;
+        hipLaunchKernelGGL(kern, dim3(n_pairs), dim3(64), lds, st, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, n_pairs,
+                           max_rows, max_cols, out, status, opt);
+        return TDA_OK;
+    });
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
@@ -584,7 +323,7 @@ tda_status launch_wasserstein_q(tda_ctx* ctx, const double* dgm_a, const int* cn
         TDA_FAIL(ctx, TDA_ERR_INVALID, "order must be 1 or 2 and ground TDA_GROUND_L2 or TDA_GROUND_LINF");
     if (n_pairs == 0) return TDA_OK;
     if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
-    const wq_index_pairs src{idx_a, idx_b};
+    const ws_index_pairs src{idx_a, idx_b};
 #define WQ_VARIANT(O, G) launch_wq_src<O, G>(ctx, dgm_a, cnt_a, cap_a, dgm_b, cnt_b, cap_b, src, n_pairs, out, status, st)
     if (ground == TDA_GROUND_L2) return order == 1 ? WQ_VARIANT(1, TDA_GROUND_L2) : WQ_VARIANT(2, TDA_GROUND_L2);
     return order == 1 ? WQ_VARIANT(1, TDA_GROUND_LINF) : WQ_VARIANT(2, TDA_GROUND_LINF);

@@ -9,6 +9,11 @@ data, which move whenever a kernel is added anywhere in the file).  No GPU neede
 An instantiation whose template arguments grew since REV is paired with its counterpart through RENAMED (mangled
 prefix at REV -> mangled prefix now):
     python3 tools/isa_diff.py --files wasserstein --match wasserstein_kernel
+--resources: for a change that is expected to move instructions.  One table row per kernel -- instructions, VGPRs,
+SGPRs, scratch bytes and spills (the code object's metadata note) at REV -> now -- and the exit status is 1 only if a
+kernel's scratch grew, a spill count left 0, or the waves per SIMD its VGPRs allow, floor(512 / (VGPRs rounded up to
+8)), changed:
+    python3 tools/isa_diff.py --resources --files wasserstein wasserstein_q --match wasserstein
 """
 import argparse
 import os
@@ -24,7 +29,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-
 
 
 # wasserstein_kernel<CW> became wasserstein_kernel<CW, SRC>; the pairs from index arrays are SRC = ws_index_pairs
-RENAMED = [(re.compile(r"^_Z18wasserstein_kernelILi(\d+)EEv"), r"_Z18wasserstein_kernelILi\g<1>E14ws_index_pairsEv")]
+RENAMED = [(re.compile(r"^_Z18wasserstein_kernelILi(\d+)EEv"), r"_Z18wasserstein_kernelILi\g<1>E14ws_index_pairsEv"),
+           # wq_index_pairs and wq_opts became the ws_index_pairs and ws_opts of assign_dev.h
+           (re.compile(r"^(_Z20wasserstein_q_kernelILi\d+ELi\d+ELi\d+E14)wq(_index_pairsEv)"), r"\g<1>ws\g<2>")]
 
 
 def counterpart(old_name, new):
@@ -62,7 +69,24 @@ def disasm(src_dir, name, tmp, tag):
         else:
             after_pc = 2 if ins.startswith("s_getpc_b64") else 0
         cur.append(ins)
-    return funcs
+    return funcs, resources(elf)
+
+
+RES_KEYS = ["vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count"]
+
+
+def resources(elf):
+    """{kernel: {key: int}} from the metadata note (the keys of a kernel come sorted, `.name` among them)."""
+    text = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-readelf", "--notes", elf]).decode()
+    out = {}
+    for block in re.split(r"^  - (?=\.agpr_count:)", text, flags=re.M)[1:]:
+        name = re.search(r"^\s+\.name:\s+(\S+)", block, re.M).group(1)
+        out[name] = {k: int(re.search(rf"^\s*\.{k}:\s+(\d+)", block, re.M).group(1)) for k in RES_KEYS}
+    return out
+
+
+def waves(r):
+    return 512 // ((r["vgpr_count"] + r["agpr_count"] + 7) // 8 * 8)
 
 
 def main():
@@ -70,6 +94,7 @@ def main():
     ap.add_argument("--rev", default="HEAD")
     ap.add_argument("--files", nargs="+", default=["filters", "rips"])
     ap.add_argument("--match", default=r"sos_pipe_kernel|ba_pipe_kernel|eeg_window_kernel")
+    ap.add_argument("--resources", action="store_true")
     a = ap.parse_args()
     pat, bad = re.compile(a.match), 0
     with tempfile.TemporaryDirectory() as tmp:
@@ -88,11 +113,27 @@ def main():
         os.makedirs(os.path.dirname(old_csrc))
         os.rename(old_dir, old_csrc)
         for name in a.files:
-            old, new = disasm(old_csrc, name, tmp, "old"), disasm(CSRC, name, tmp, "new")
+            (old, old_res), (new, new_res) = disasm(old_csrc, name, tmp, "old"), disasm(CSRC, name, tmp, "new")
             for k in sorted(old):
                 if not pat.search(k):
                     continue
                 k2 = counterpart(k, new)
+                if a.resources:
+                    if k2 is None:
+                        bad += 1
+                        print(f"MISSING  {k}")
+                        continue
+                    o, n = old_res[k], new_res[k2]
+                    spills = lambda r: r["vgpr_spill_count"] + r["sgpr_spill_count"]
+                    ok = (n["private_segment_fixed_size"] <= o["private_segment_fixed_size"] and waves(o) == waves(n)
+                          and not (spills(o) == 0 and spills(n) != 0))
+                    bad += not ok
+                    print(f"{'ok  ' if ok else 'FAIL'}  instr {len(old[k]):5d} -> {len(new[k2]):5d} ({100.0 * (len(new[k2]) - len(old[k])) / len(old[k]):+5.1f} %)"
+                          f"  vgpr {o['vgpr_count']:3d} -> {n['vgpr_count']:3d}  agpr {o['agpr_count']} -> {n['agpr_count']}"
+                          f"  sgpr {o['sgpr_count']:3d} -> {n['sgpr_count']:3d}  scratch {o['private_segment_fixed_size']:3d} -> "
+                          f"{n['private_segment_fixed_size']:3d} B  spills {spills(o)} -> {spills(n)}  waves/SIMD {waves(o)} -> {waves(n)}"
+                          f"  {k}" + (f"  ->  {k2}" if k2 != k else ""))
+                    continue
                 same = k2 is not None and new[k2] == old[k]
                 bad += not same
                 print(f"{'same' if same else 'DIFFERENT' if k2 else 'MISSING'}  {len(old[k]):6d} instructions  {k}"
