@@ -589,6 +589,68 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
                                const double* grid, int n_grid, int n_levels, double* out);
 
+/* ---- Frechet means of diagrams, per group ---------------------------------------------
+ * The mean diagram of a group in the order-2 Wasserstein metric and the group's variance around it: the algorithm of
+ * Turner, Mileyko, Mukherjee and Harer (2014), with the update rule of GUDHI's lagrangian_barycenter.  The contract is this
+ * text; tests/frechet_ref.py evaluates it on the CPU.
+ *   Input.    A group is the diagrams seg_off[g] <= w < seg_off[g + 1], in buffer order.  Diagrams whose status_in word has
+ *             a bit of skip_mask are left out, as in tda_landscape_mean_dev (status_in may be NULL).  The kept ones are
+ *             X_1 .. X_m, in buffer order.  Of every diagram only the rows i < min(cnt, cap) with both values finite
+ *             count, in row order.  An empty diagram stays empty: it is not replaced by {(0,0)}.  The two are equivalent
+ *             for this cost (a point on the diagonal has diagonal cost 0 and no negative gain), so nothing is lost.
+ *   Costs.    Those of tda_wasserstein_q_batch with order 2 and TDA_GROUND_L2, operation for operation, no multiply-add:
+ *               dx = fabs(y_b - x_b), dy = fabs(y_d - x_d), C = (dx * dx) + (dy * dy);
+ *               diagonal cost 0.5 * (p * p) with p = d - b;
+ *               gain g = min(0, (C - s) - t), where s is the diagonal cost of the point of the diagram with FEWER rows
+ *               (the row role; Y on a tie) and t that of the other point.
+ *             A matched cell is a real match iff its computed gain is < 0.
+ *   Start.    Y^0 is the finite rows of X_1, in row order.
+ *   One iteration on Y = Y^t with n rows:
+ *     1. For i = 1..m an optimal partial matching of Y and X_i (the minimum of the summed gains; with n = 0 or X_i empty
+ *        nothing is matched).  V_i is its value from the original costs: a term per row j of Y (C of its real match, else
+ *        its diagonal cost) and a term per row of X_i without a real match (its diagonal cost).  The terms are added into
+ *        64 partial sums -- the Y terms to sum (j mod 64) in ascending j, then the X terms to sum (row mod 64) in
+ *        ascending row -- and the 64 sums are folded pairwise at distances 32, 16, 8, 4, 2, 1 (a[l] + a[l xor distance]).
+ *        F_t = V_1 + V_2 + ... in the order of i, starting from 0.
+ *     2. For every row j of Y: k_j is the number of i in which j has a real match, sb_j and sd_j the sums of the matched
+ *        births and deaths, added in ascending i, starting from 0.
+ *     3. A row with k_j = 0 is dropped.  Otherwise wb = sb / k, wd = sd / k; if k = m the new row is (wb, wd), else
+ *        h = 0.5 * (wb + wd) and the new row is (((k * wb) + ((m - k) * h)) / m, ((k * wd) + ((m - k) * h)) / m).
+ *     4. Every row x of every X_i without a real match spawns one row by the same formula with k = 1, wb = x_b, wd = x_d.
+ *     5. Y^{t+1} is the surviving rows in the order of j, then the spawned rows in the order (i, row).
+ *   Stop.     Converged at t if Y^{t+1} has the row count and the bytes of Y^t (the new rows depend only on the matchings
+ *             and the X_i, so an unchanged matching gives unchanged bytes).  The loop runs for t = 0 .. max_iter - 1,
+ *             1 <= max_iter <= TDA_FM_MAX_ITER.  The output is always the last iterate that was matched, Y^t with its own
+ *             energy, never an unmatched Y^{t+1}.  Without convergence within the bound the group carries
+ *             TDA_WIN_NOT_CONVERGED and keeps its output.
+ *   Outputs per group.  mean (cap_out, 2): the rows of Y^t (rows beyond the count are not written); mean_cnt: the true
+ *             row count; var = F_t / m, the Frechet variance of the output; iters = t + 1; status.
+ *   Limits.   m = 0: count 0, var NaN, iters 0, status 0.  m > 64, a diagram with more than TDA_FM_MAX_POINTS finite rows,
+ *             or a Y^{t+1} formed with more than TDA_FM_MAX_POINTS rows (in the last iteration too): TDA_WIN_TOO_LARGE,
+ *             count 0, var NaN.  A solver loop bound hit: TDA_WIN_NOT_CONVERGED, count 0, var NaN.  count > cap_out:
+ *             TDA_WIN_H1_TRUNCATED, the true count, the first cap_out rows, var and iters valid.
+ *             cap >= 1, cap_out >= 1, 1 <= max_iter <= TDA_FM_MAX_ITER, and n_seg = n_dgm when seg_off is NULL; anything
+ *             else is TDA_ERR_INVALID and nothing is launched.  Table entries are clamped to [0, n_dgm].
+ *   Bounds.   Every loop of the kernel has a bound known before it starts: max_iter, the group's size, the row limits and
+ *             the solver's own bounds.  Nothing can spin.
+ *   Exactness.  Every cost and every update is one correctly rounded float64 operation of this text and the sums run in
+ *             the stated orders.  Where every optimal matching met along the way is unique, the output equals a CPU
+ *             evaluation of this text bit for bit; otherwise both are valid runs of the same algorithm.
+ *   Determinism.  No atomics on floating point.  A group alone and the same group inside a batch give the same bytes.  With
+ *             seg_off = NULL every diagram is its own group; the mean of a diagram whose rows all have d > b is then its
+ *             finite rows, with var 0 and iters 1.
+ * The _dev form only enqueues on `stream` and allocates nothing.  mean (n_seg, cap_out, 2) float64; mean_cnt, iters, status
+ * (n_seg) int32; var (n_seg) float64. */
+#define TDA_FM_MAX_ITER   64
+#define TDA_FM_MAX_POINTS 512
+tda_status tda_frechet_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm,
+                                const int* seg_off, int n_seg, const int* status_in, int skip_mask, int max_iter,
+                                double* mean, int* mean_cnt, int cap_out, double* var, int* iters, int* status,
+                                void* stream);
+tda_status tda_frechet_mean_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
+                                  const int* seg_off, int n_seg, const int* status_in, int skip_mask, int max_iter,
+                                  double* mean, int* mean_cnt, int cap_out, double* var, int* iters, int* status);
+
 /* ---- Persistence images, averaged per group -----------------------------------------
  * The image of a diagram is the bivariate normal density with covariance sigma^2 I, placed on every point of the diagram in
  * birth/persistence coordinates, weighted by a power of the persistence and integrated over every pixel of a grid.  This

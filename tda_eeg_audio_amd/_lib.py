@@ -32,6 +32,8 @@ MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 MAX_POINTS = 128
 MAX_DIRECTIONS = 128        # TDA_MAX_DIRECTIONS
 SW_MAX_POINTS = 512         # TDA_SW_MAX_POINTS
+FM_MAX_ITER = 64            # TDA_FM_MAX_ITER
+FM_MAX_POINTS = 512         # TDA_FM_MAX_POINTS
 TDA_GROUND_L2 = 0           # tda_wasserstein_q_batch: (d - b) / sqrt 2 to the diagonal
 TDA_GROUND_LINF = 1         # ... (d - b) / 2, the convention of the bottleneck distance
 
@@ -124,6 +126,8 @@ SYMBOLS = {
     "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
     "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),
     "tda_image_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp]),
+    "tda_frechet_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_frechet_mean_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

@@ -459,6 +459,18 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
                                  (hipStream_t)stream);
 }
 
+tda_status tda_frechet_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
+                                int n_seg, const int* status_in, int skip_mask, int max_iter, double* mean, int* mean_cnt,
+                                int cap_out, double* var, int* iters, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm); CHECK_NONNEG(ctx, n_seg);
+    if (!seg_off && n_seg != n_dgm) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); }
+    if (n_seg) { CHECK_PTR(ctx, mean); CHECK_PTR(ctx, mean_cnt); CHECK_PTR(ctx, var); CHECK_PTR(ctx, iters); CHECK_PTR(ctx, status); }
+    return launch_frechet_mean(ctx, dgm, cnt, cap, n_dgm, seg_off, n_seg, status_in, skip_mask, max_iter, mean, mean_cnt,
+                               cap_out, var, iters, status, (hipStream_t)stream);
+}
+
 tda_status tda_image_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
                               int n_seg, const int* status, int skip_mask, const double* xe, int n_x, const double* ye,
                               int n_y, double sigma, int power, double* out, void* stream)
@@ -1025,6 +1037,34 @@ tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, 
     RET_IF(s.upload());
     RET_IF(tda_landscape_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
                                   nullptr));
+    return s.download();
+}
+
+tda_status tda_frechet_mean_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const int* seg_off,
+                                  int n_seg, const int* status_in, int skip_mask, int max_iter, double* mean, int* mean_cnt,
+                                  int cap_out, double* var, int* iters, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_dgm); CHECK_NONNEG(ctx, n_seg);
+    if (cap < 1 || cap_out < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "cap and cap_out must be >= 1");
+    if (max_iter < 1 || max_iter > TDA_FM_MAX_ITER) TDA_FAIL(ctx, TDA_ERR_INVALID, "max_iter must be 1..TDA_FM_MAX_ITER");
+    if (!seg_off && n_seg != n_dgm) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_seg == 0) return TDA_OK;
+    if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); }
+    CHECK_PTR(ctx, mean); CHECK_PTR(ctx, mean_cnt); CHECK_PTR(ctx, var); CHECK_PTR(ctx, iters); CHECK_PTR(ctx, status);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_dgm = nullptr, *d_mean, *d_var; int *d_cnt = nullptr, *d_off = nullptr, *d_sin = nullptr, *d_mc, *d_it, *d_st;
+    if (n_dgm) { s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16); s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4); }
+    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
+    if (status_in && n_dgm) s.add((void**)&d_sin, status_in, nullptr, (size_t)n_dgm * 4);
+    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * cap_out * 16);
+    s.add((void**)&d_mc, nullptr, mean_cnt, (size_t)n_seg * 4);
+    s.add((void**)&d_var, nullptr, var, (size_t)n_seg * 8);
+    s.add((void**)&d_it, nullptr, iters, (size_t)n_seg * 4);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_seg * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_frechet_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, d_off, n_seg, d_sin, skip_mask, max_iter, d_mean, d_mc, cap_out,
+                                d_var, d_it, d_st, nullptr));
     return s.download();
 }
 

@@ -245,6 +245,8 @@ tda_status launch_sliced_prepared_pairs(tda_ctx*, const double*, const long long
 tda_status launch_sliced_matrix(tda_ctx*, const double*, const long long*, const int*, int, const int*, int, const int*,
                                 const double*, const long long*, const int*, int, const int*, int, int, const int*, int, double*,
                                 int*, int*, hipStream_t);
+tda_status launch_frechet_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int, int, double*,
+                               int*, int, double*, int*, int*, hipStream_t);
 tda_status launch_landscape_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int,
                                  const double*, int, int, double*, hipStream_t);
 tda_status launch_image_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int, const double*,

@@ -145,6 +145,32 @@ def landscapes_from_distances(dist_list, grid, levels, thresh=MAX_EDGE_LENGTH):
     return out.permute(1, 0, 2, 3).cpu().numpy().copy()
 
 
+def frechet_means_from_distances(dist_list, thresh=MAX_EDGE_LENGTH, max_iter=32):
+    """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
+    per diagram set (H0, H1): per group the Frechet mean of its windows' diagrams in the order-2 Wasserstein metric and
+    their Frechet variance around it (include/tdaeeg.h; engine.frechet_mean_dev).  Returns a list over the groups of
+    {"h0": (mean (k, 2), variance, iterations, status), "h1": ...}; a group without a window has an empty mean and a NaN
+    variance.  status is the group's word: TDA_WIN_NOT_CONVERGED keeps its mean, any other bit has none."""
+    import torch
+    sizes = np.array([len(d) for d in dist_list])
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
+    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
+        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
+    check_status(st, "frechet_means_from_distances")
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    out = [dict() for _ in dist_list]
+    for name, rows, cnt in (("h0", h0, c0), ("h1", h1, c1)):
+        res = engine.frechet_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
+                                      seg_off_t=seg_t, max_iter=max_iter, ctx=ctx)
+        mean, mc, var, it, fst = (t.cpu().numpy() for t in res)
+        for g in range(len(dist_list)):
+            out[g][name] = (mean[g, :mc[g]].copy(), float(var[g]), int(it[g]), int(fst[g]))
+    return out
+
+
 def landscape_names(bands=BANDS, levels=5, grid=None):
     """Column names of landscapes_from_distances(...)[r] of every band, flattened band by band: per band and diagram set
     (h0, h1) the levels 1..levels and then the Betti curve, each at every grid point in order."""

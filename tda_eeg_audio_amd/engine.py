@@ -7,7 +7,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch, wasserstein_q_batch,
                  sliced_wasserstein_batch, sliced_wasserstein_gram,
-                 landscape_batch, image_batch, temporal_corr_batch
+                 landscape_batch, image_batch, frechet_mean_batch, temporal_corr_batch
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -344,6 +344,36 @@ def image_batch(rows, cnt, xe, ye, sigma, power=1, ctx=None):
     ctx.check(ctx.lib.tda_image_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(xe), n_x, ptr(ye), n_y, float(sigma), int(power),
                                       ptr(out)))
     return out
+
+
+def frechet_args(cap_out, max_iter):
+    """(cap_out, max_iter) of a Frechet mean as the kernel takes them: cap_out >= 1, 1 <= max_iter <= FM_MAX_ITER.
+    TdaError, before any GPU call, for anything else."""
+    for name, v, hi in (("cap_out", cap_out, None), ("max_iter", max_iter, _lib.FM_MAX_ITER)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or (hi is not None and v > hi):
+            raise _lib.TdaError(f"frechet_mean: {name} must be an integer >= 1{'' if hi is None else f' and <= {hi}'}, not {v!r}")
+    return int(cap_out), int(max_iter)
+
+
+def frechet_mean_batch(rows, cnt, seg_off=None, status=None, skip_mask=0, max_iter=32, cap_out=None, ctx=None):
+    """Frechet mean and Frechet variance of every group of diagrams in the order-2 Wasserstein metric (include/tdaeeg.h):
+    rows (n, cap, 2), cnt (n,), seg_off (n_seg + 1,) int32 or None (every diagram its own group); diagrams whose status
+    word has a bit of skip_mask are left out.  Returns mean (n_seg, cap_out, 2) with NaN beyond the count, count, variance,
+    iters and status, (n_seg,) each.  cap_out defaults to FM_MAX_POINTS."""
+    cap_out, max_iter = frechet_args(_lib.FM_MAX_POINTS if cap_out is None else cap_out, max_iter)
+    ctx = ctx or get_ctx()
+    rows = f64(rows); cnt = i32(cnt)
+    n, cap, _ = rows.shape
+    off = None if seg_off is None else i32(seg_off)
+    st_in = None if status is None else i32(status)
+    assert st_in is None or st_in.shape == (n,)
+    n_seg = n if off is None else len(off) - 1
+    mean = np.empty((n_seg, cap_out, 2)); mc = np.empty(n_seg, np.int32); var = np.empty(n_seg)
+    it = np.empty(n_seg, np.int32); st = np.empty(n_seg, np.int32)
+    ctx.check(ctx.lib.tda_frechet_mean_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(off), n_seg, ptr(st_in), int(skip_mask),
+                                             max_iter, ptr(mean), ptr(mc), cap_out, ptr(var), ptr(it), ptr(st)))
+    mean[np.arange(cap_out)[None, :] >= mc[:, None]] = np.nan
+    return mean, mc, var, it, st
 
 
 def _directions(dirs):
@@ -699,6 +729,30 @@ def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=N
     ctx.check(ctx.lib.tda_landscape_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
                                              int(skip_mask), _tp(grid_t), n_grid, levels, _tp(out_t), _stream()))
     return out_t
+
+
+def frechet_mean_dev(rows_t, cnt_t, seg_off_t=None, status_t=None, skip_mask=0, max_iter=32, cap_out=None, out=None, ctx=None):
+    """frechet_mean_batch on device tensors: one launch on torch's current stream, nothing allocated when out is given.
+    out: the tensors (mean (n_seg, cap_out, 2) float64, count, variance float64, iters, status) -- int32 where not said
+    otherwise; the rows of mean beyond the count are left as they were (the NaN padding is the caller's).  Returns out."""
+    import torch
+    ctx = ctx or get_ctx()
+    n, cap, _ = rows_t.shape
+    n_seg = n if seg_off_t is None else seg_off_t.numel() - 1
+    if out is None:
+        cap_out, max_iter = frechet_args(_lib.FM_MAX_POINTS if cap_out is None else cap_out, max_iter)
+        dev = rows_t.device
+        out = (torch.full((n_seg, cap_out, 2), float("nan"), dtype=torch.float64, device=dev),
+               torch.empty(n_seg, dtype=torch.int32, device=dev), torch.empty(n_seg, dtype=torch.float64, device=dev),
+               torch.empty(n_seg, dtype=torch.int32, device=dev), torch.empty(n_seg, dtype=torch.int32, device=dev))
+    else:
+        cap_out, max_iter = frechet_args(out[0].shape[1], max_iter)
+    mean_t, mc_t, var_t, it_t, st_t = out
+    assert rows_t.is_contiguous() and all(o.is_contiguous() for o in out)
+    ctx.check(ctx.lib.tda_frechet_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
+                                           int(skip_mask), max_iter, _tp(mean_t), _tp(mc_t), cap_out, _tp(var_t), _tp(it_t),
+                                           _tp(st_t), _stream()))
+    return out
 
 
 def image_mean_dev(rows_t, cnt_t, xe_t, ye_t, sigma, power, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):

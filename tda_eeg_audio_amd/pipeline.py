@@ -25,13 +25,15 @@ SLC_COLS = 2              # Workspace(sliced=dirs).slc: [s_h0, s_h1], the means 
 WQ_COLS = 2               # Workspace(wasserstein_q=(order, ground)).wq: [q_h0, q_h1], the means of that Wasserstein distance
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
+FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram sets, in the same order
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
-def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None):
+def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
+                 frechet=None):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq, fm.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -48,7 +50,11 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
       slc   sliced=dirs, (M, 2) finite directions, 1 <= M <= TDA_MAX_DIRECTIONS (engine._directions): (SLC_COLS,) np.nanmean
             of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`
       wq    wasserstein_q=(order, ground), order 1 or 2 and ground "l2" or "linf": (WQ_COLS,) np.nanmean of that Wasserstein
-            distance of the H0 / H1 pairs (engine.wasserstein_q_dev) under the rule of `bott`.  ValueError for anything else"""
+            distance of the H0 / H1 pairs (engine.wasserstein_q_dev) under the rule of `bott`.  ValueError for anything else
+      fm    frechet=(cap, max_iter), 1 <= cap <= FM_MAX_POINTS and 1 <= max_iter <= FM_MAX_ITER: (FM_SETS, cap + 2, 2), per
+            diagram set of `land` (same windows, same audio mask) the Frechet mean of the group's diagrams in the order-2
+            Wasserstein metric (engine.frechet_mean_dev): rows 0..cap-1 the mean, NaN beyond its count; row cap
+            [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else"""
     from . import _lib
     out = []
     if correlations:
@@ -73,6 +79,16 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
         except (TypeError, ValueError, _lib.TdaError):
             raise ValueError("wasserstein_q=(order, ground): order 1 or 2, ground 'l2' or 'linf'") from None
         out.append(Output("wq", (WQ_COLS,), (int(order), ground)))
+    if frechet is not None:
+        try:
+            cap, max_iter = frechet
+            cap, max_iter = engine.frechet_args(cap, max_iter)
+            if cap > _lib.FM_MAX_POINTS:
+                raise ValueError
+        except (TypeError, ValueError, _lib.TdaError):
+            raise ValueError(f"frechet=(cap, max_iter): integers, 1 <= cap <= {_lib.FM_MAX_POINTS}, "
+                             f"1 <= max_iter <= {_lib.FM_MAX_ITER}") from None
+        out.append(Output("fm", (FM_SETS, cap + 2, 2), (cap, max_iter)))
     return out
 
 
@@ -85,12 +101,13 @@ class Workspace:
     corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
     land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
     wq = wasserstein_q = q0 = q1 = qs0 = qs1 = None
+    fm = fm_sets = frechet = fm_out = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None, wasserstein_q=None):
-        """correlations .. wasserstein_q: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None):
+        """correlations .. frechet: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
-        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2) -- and with `bott` / `slc` / `wq` the distances of every
+        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2) -- and with `bott` / `slc` / `wq` the distances of every
         window, `b0` / `b1`, `s0` / `s1` and `q0` / `q1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1` and `qs0` / `qs1`.
         Grid, edges and directions are uploaded once, here."""
         import torch
@@ -115,10 +132,10 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q)
+        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
-        self.wasserstein_q = par.get("wq")
+        self.wasserstein_q, self.frechet = par.get("wq"), par.get("fm")
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
@@ -139,6 +156,11 @@ class Workspace:
             self.s0, self.s1, self.ss0, self.ss1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.wasserstein_q is not None:
             self.q0, self.q1, self.qs0, self.qs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.frechet is not None:
+            # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
+            i32 = dict(dtype=torch.int32, device=device)
+            self.fm_out = (torch.empty((self.n_seg, self.frechet[0], 2), **f64), torch.empty(self.n_seg, **i32),
+                           torch.empty(self.n_seg, **f64), torch.empty(self.n_seg, **i32), torch.empty(self.n_seg, **i32))
         if self.landscapes is not None:
             self.land_grid, self.land_levels = torch.from_numpy(self.landscapes[0]).to(device), self.landscapes[1]
         if self.images is not None:
@@ -185,6 +207,8 @@ class Workspace:
                 sets = getattr(self, o.name + "_sets")[:, :n_seg]
                 setattr(v, o.name + "_sets", sets)
                 setattr(v, o.name, sets.permute(1, 0, 2, 3))
+        if self.fm_out is not None:
+            v.fm_out = tuple(t[:n_seg] for t in self.fm_out)
         return v
 
 
@@ -288,6 +312,8 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         order, ground = ws.wasserstein_q
         pair_means("wasserstein_q", functools.partial(engine.wasserstein_q_dev, order=order, ground=ground), (ws.q0, ws.q1),
                    (ws.qs0, ws.qs1), ws.wq)
+    if ws.fm is not None:
+        stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -318,6 +344,22 @@ def _image_stage(ws, ctx, audio):
     """ws.img of the step, (n_seg, n_y, n_x) per set."""
     _set_means_stage(ws, ctx, audio, functools.partial(engine.image_mean_dev, xe_t=ws.img_xe, ye_t=ws.img_ye,
                                                        sigma=ws.images[2], power=ws.images[3]), ws.img_sets)
+
+
+def _frechet_stage(ws, ctx, audio):
+    """ws.fm of the step, (n_seg, cap + 2, 2) per set: one launch per diagram set into ws.fm_out, then the set's block --
+    the mean with NaN beyond its count, [count, variance], [iterations, status]."""
+    import torch
+    cap, max_iter = ws.frechet
+
+    def launch(rows, cnt, seg_off_t, status_t, skip_mask, out_t, ctx):
+        mean, mc, var, it, st = engine.frechet_mean_dev(rows, cnt, seg_off_t=seg_off_t, status_t=status_t, skip_mask=skip_mask,
+                                                        max_iter=max_iter, out=ws.fm_out, ctx=ctx)
+        live = torch.arange(cap, device=ws.device)[None, :, None] < mc[:, None, None]
+        out_t[:, :cap] = torch.where(live, mean, torch.full((), float("nan"), dtype=torch.float64, device=ws.device))
+        out_t[:, cap, 0] = mc; out_t[:, cap, 1] = var
+        out_t[:, cap + 1, 0] = it; out_t[:, cap + 1, 1] = st
+    _set_means_stage(ws, ctx, audio, launch, ws.fm_sets)
 
 
 class Batch:
@@ -590,6 +632,8 @@ def run_features_step(eeg_win, ws, ctx=None):
         _landscape_stage(ws, ctx, audio=False)
     if ws.img is not None:                               # the same for ws.img
         _image_stage(ws, ctx, audio=False)
+    if ws.fm is not None:                                # the same for ws.fm
+        _frechet_stage(ws, ctx, audio=False)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)
     engine.aggregate_dev(ws.fe0, ws.fe1, ws.seg_off, ws.feat44, ctx=ctx)
@@ -598,4 +642,4 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0" and "wasserstein_q_h1", in this order after "wasserstein_h1")
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1" and "frechet", in this order after "wasserstein_h1")

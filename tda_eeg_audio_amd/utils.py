@@ -253,6 +253,34 @@ def persistence_image(dgm, xe, ye, sigma, power=1):
     return engine.image_batch(rows, cnt, xe, ye, sigma, power)[0]
 
 
+def frechet_mean(dgms, max_iter=32):
+    """The Frechet mean of a group of diagrams in the order-2 Wasserstein metric with the L2 ground metric
+    (include/tdaeeg.h: the algorithm of Turner et al. 2014, started at the first diagram) and the group's Frechet variance
+    around it: (mean (k, 2) float64, variance, iterations, converged).  Rows with a non-finite entry do not count.  At
+    most 64 diagrams of at most FM_MAX_POINTS finite rows each; converged is False when max_iter (1..FM_MAX_ITER)
+    iterations did not reach a fixed point -- the mean is then the last iterate, with its own variance.  An empty group
+    gives ((0, 2), NaN, 0, True).  Runs at once, also inside a `batch`.  Not in the reference; ValueError for a diagram that
+    is not a (k, 2) table, TdaError for a group the kernel has no room for."""
+    tabs = []
+    for d in dgms:
+        d = np.asarray(d, dtype=np.float64)
+        if d.ndim != 2 or d.shape[1] != 2:
+            if d.size:
+                raise ValueError("a persistence diagram is a (k, 2) table")
+            d = np.zeros((0, 2))
+        tabs.append(d)
+    cap = max([len(d) for d in tabs] + [1])
+    rows = np.zeros((max(len(tabs), 1), cap, 2)); cnt = np.zeros(max(len(tabs), 1), np.int32)
+    for i, d in enumerate(tabs):
+        rows[i, :len(d)] = d
+        cnt[i] = len(d)
+    mean, mc, var, it, st = engine.frechet_mean_batch(rows, cnt, seg_off=np.array([0, len(tabs)], np.int32), max_iter=max_iter)
+    if st[0] & ~engine._lib.TDA_WIN_NOT_CONVERGED:
+        raise TdaError(f"frechet_mean: status {int(st[0]):#x} (more than 64 diagrams, more than {engine._lib.FM_MAX_POINTS} points "
+                            "in a diagram or in the mean, or a solver bound)")
+    return mean[0, :mc[0]].copy(), float(var[0]), int(it[0]), not st[0] & engine._lib.TDA_WIN_NOT_CONVERGED
+
+
 def default_directions(M=50):
     """(M, 2) float64 table (cos theta_k, sin theta_k), theta_k = -pi/2 + k * pi / M: the directions of
     persim.sliced_wasserstein, computed by numpy on the host (the kernel never evaluates a trigonometric function)."""
