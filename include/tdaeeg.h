@@ -690,6 +690,74 @@ tda_status tda_image_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, i
 tda_status tda_image_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
                            const double* xe, int n_x, const double* ye, int n_y, double sigma, int power, double* out);
 
+/* ---- Kernels on diagrams: persistence scale-space and weighted Gaussian ----------------
+ * The persistence scale-space kernel (PSSK; Reininghaus, Huber, Bauer, Kwitt 2015; GUDHI's PersistenceScaleSpaceKernel) and
+ * the persistence weighted Gaussian kernel (PWGK; Kusano, Fukumizu, Hiraoka 2016; GUDHI's PersistenceWeightedGaussianKernel),
+ * between pairs of diagrams and between the mean embeddings of groups of diagrams.  GUDHI is not installed anywhere this
+ * project runs, so no parity with it is claimed.  The contract is this text; tests/diagram_kernel_ref.py evaluates it.
+ *   Rows.       A diagram has rows (b_i, d_i), i < min(cnt, cap), float64.  F is the set of rows with both values finite:
+ *               the (0, inf) row of every H0 diagram never enters.  An empty F is the zero measure; it is NOT replaced by
+ *               {(0,0)}.
+ *   Parameters. All computed by the caller: ninv finite and < 0; mirror 0 or 1; scale finite; weight TDA_KW_ONE,
+ *               TDA_KW_PERS or TDA_KW_ATAN; wc finite, used by TDA_KW_ATAN only.  The device never divides by sigma and
+ *               never computes pi.
+ *   Weights.    Once per row, never once per pair: p_i = d_i - b_i; w_i = 1.0 (TDA_KW_ONE), p_i (TDA_KW_PERS) or
+ *               atan(wc * p_i) (TDA_KW_ATAN).  A weight that is not finite (a persistence that overflows) is outside
+ *               the contract.
+ *   Terms.      No multiply-add anywhere.  For i in F_A and j in F_B:
+ *                 dx = b_i - b_j; dy = d_i - d_j; a1 = (dx * dx + dy * dy) * ninv; E1 = exp(a1)
+ *                 ex = b_i - d_j; ey = d_i - b_j; a2 = (ex * ex + ey * ey) * ninv; E2 = exp(a2)      (mirror = 1 only)
+ *                 t_ij = (w_i * w_j) * (E1 - E2), or (w_i * w_j) * E1 when mirror is 0.
+ *               S(A, B) is the sum of all t_ij and K(A, B) = scale * S(A, B).  a1 and a2 are the same float64 on the GPU
+ *               and in a CPU evaluation; only exp, atan and the order of the additions differ.  A row on the diagonal
+ *               (b = d) has a1 = a2 bit for bit and adds exactly 0.0 when mirror is 1.
+ *   Named.      PSSK(sigma): ninv = -1 / (8 sigma), mirror = 1, scale = 1 / (8 pi sigma), TDA_KW_ONE.
+ *               PWGK(sigma, c): ninv = -1 / (2 sigma^2), mirror = 0, scale = 1, TDA_KW_ATAN with wc = c.
+ *   Pairs.      k_ab = K(A, B), k_aa = K(A, A), k_bb = K(B, B); s = k_aa + k_bb; t = k_ab + k_ab; d2 = s - t;
+ *               out = sqrt(d2 > 0 ? d2 : 0), the distance the kernel induces.  kvals (n_pairs, 3), nullable, receives
+ *               [k_ab, k_aa, k_bb].  A pair index outside [0, n_a) or [0, n_b) gives NaN (in kvals too) and
+ *               TDA_WIN_NO_PAIR, as tda_sliced_prepared_pairs_dev does; every other pair has status 0.  There is no limit
+ *               on the rows of a diagram: the loops run over chunks.
+ *   Gram.       The groups of set A are seg_off_a[g] <= w < seg_off_a[g + 1], those of set B likewise; seg_off = NULL makes
+ *               every diagram its own group (n_seg must then be the number of diagrams); table entries are clamped to
+ *               [0, n].  The kept diagrams of a group are those whose status word has no bit of skip_mask (status may be
+ *               NULL); n_g of them.  G[g, h] = (scale * S_gh) / (double)(n_g * n_h), where S_gh runs over all finite rows of
+ *               all kept diagrams of g against those of h: the kernel between the groups' mean embeddings.  NaN when n_g or
+ *               n_h is 0.  out is (n_seg_a, n_seg_b).  With dgm_b = NULL the second set is the first (the other B arguments
+ *               are ignored), out is (n_seg_a, n_seg_a), only the tiles h >= g are computed and G[h, g] is a copy of
+ *               G[g, h]: symmetric as bytes.
+ *   Determinism.  No atomics.  A pair alone and the same pair inside a batch, a group alone and the same group inside a
+ *               batch, give the same bytes.  The order of the additions is not otherwise part of the contract; the terms
+ *               are non-negative (d >= b) up to the rounding of exp.
+ *   Tolerance.  Against a CPU evaluation of this text, with A = |scale| * sum |w_i w_j| (E1 + mirror * E2) (divided by
+ *               n_g n_h for a Gram entry) and N_t the number of terms: DESIGN.md 3.15.
+ *   Limits.     A bad ninv, scale, mirror, weight or wc, or cap < 1, is TDA_ERR_INVALID and nothing is launched.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  out (n_pairs) float64, status (n_pairs) int32. */
+#define TDA_KW_ONE  0
+#define TDA_KW_PERS 1
+#define TDA_KW_ATAN 2
+tda_status tda_diagram_kernel_pairs_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                        const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                        const int* idx_a, const int* idx_b, int n_pairs,
+                                        double ninv, int mirror, double scale, int weight, double wc,
+                                        double* out, double* kvals, int* status, void* stream);
+tda_status tda_diagram_kernel_pairs(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                    const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                    const int* idx_a, const int* idx_b, int n_pairs,
+                                    double ninv, int mirror, double scale, int weight, double wc,
+                                    double* out, double* kvals, int* status);
+tda_status tda_diagram_kernel_gram_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                       const int* seg_off_a, int n_seg_a, const int* status_a,
+                                       const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                       const int* seg_off_b, int n_seg_b, const int* status_b, int skip_mask,
+                                       double ninv, int mirror, double scale, int weight, double wc,
+                                       double* out, void* stream);
+tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                   const int* seg_off_a, int n_seg_a, const int* status_a,
+                                   const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                   const int* seg_off_b, int n_seg_b, const int* status_b, int skip_mask,
+                                   double ninv, int mirror, double scale, int weight, double wc, double* out);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

@@ -36,6 +36,9 @@ FM_MAX_ITER = 64            # TDA_FM_MAX_ITER
 FM_MAX_POINTS = 512         # TDA_FM_MAX_POINTS
 TDA_GROUND_L2 = 0           # tda_wasserstein_q_batch: (d - b) / sqrt 2 to the diagonal
 TDA_GROUND_LINF = 1         # ... (d - b) / 2, the convention of the bottleneck distance
+TDA_KW_ONE = 0              # tda_diagram_kernel_*: row weight 1.0
+TDA_KW_PERS = 1             # ... the persistence d - b
+TDA_KW_ATAN = 2             # ... atan(wc * (d - b))
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -128,6 +131,14 @@ SYMBOLS = {
     "tda_image_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp]),
     "tda_frechet_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_frechet_mean_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_diagram_kernel_pairs_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, _I, _D, _I, _D, c_vp,
+                                          c_vp, c_vp, c_vp]),
+    "tda_diagram_kernel_pairs": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, _I, _D, _I, _D, c_vp, c_vp,
+                                      c_vp]),
+    "tda_diagram_kernel_gram_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I,
+                                         _D, _I, _D, c_vp, c_vp]),
+    "tda_diagram_kernel_gram": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, _D,
+                                     _I, _D, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

@@ -583,6 +583,38 @@ tda_status tda_sliced_matrix_dev(tda_ctx* ctx, const double* table_a, const long
                                 seg_off_b, n_cls, n_col, status_b, n_dirs, out, pairs, flags, (hipStream_t)stream);
 }
 
+tda_status tda_diagram_kernel_pairs_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                        const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                        const int* idx_b, int n_pairs, double ninv, int mirror, double scale, int weight,
+                                        double wc, double* out, double* kvals, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_b);
+    if (n_pairs) { CHECK_PTR(ctx, out); CHECK_PTR(ctx, status); }
+    if (n_pairs && n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (n_pairs && n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
+    return launch_diagram_kernel_pairs(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, ninv,
+                                       mirror, scale, weight, wc, out, kvals, status, (hipStream_t)stream);
+}
+
+tda_status tda_diagram_kernel_gram_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                       const int* seg_off_a, int n_seg_a, const int* status_a, const double* dgm_b,
+                                       const int* cnt_b, int n_b, int cap_b, const int* seg_off_b, int n_seg_b,
+                                       const int* status_b, int skip_mask, double ninv, int mirror, double scale, int weight,
+                                       double wc, double* out, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_seg_a);
+    if (!seg_off_a && n_seg_a != n_a) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (dgm_b) {
+        CHECK_NONNEG(ctx, n_b); CHECK_NONNEG(ctx, n_seg_b); CHECK_PTR(ctx, cnt_b);
+        if (!seg_off_b && n_seg_b != n_b) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    }
+    if (n_seg_a && (!dgm_b || n_seg_b)) CHECK_PTR(ctx, out);
+    return launch_diagram_kernel_gram(ctx, dgm_a, cnt_a, cap_a, n_a, seg_off_a, n_seg_a, status_a, dgm_b, cnt_b, cap_b, n_b,
+                                      seg_off_b, n_seg_b, status_b, skip_mask, ninv, mirror, scale, weight, wc, out,
+                                      (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.
@@ -1016,6 +1048,83 @@ tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, dirs, n_dirs, out, status,
         [&](const PairDev& d) { return tda_sliced_wasserstein_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
                                                                         d.dirs, n_dirs, d.out, d.st, nullptr); });
+}
+
+// the parameter checks of the diagram kernels, before anything is staged (the launch repeats them)
+static bool diagram_kernel_params_ok(double ninv, int mirror, double scale, int weight, double wc)
+{
+    return std::isfinite(ninv) && ninv < 0.0 && (mirror == 0 || mirror == 1) && std::isfinite(scale) &&
+           (weight == TDA_KW_ONE || weight == TDA_KW_PERS || (weight == TDA_KW_ATAN && std::isfinite(wc)));
+}
+
+tda_status tda_diagram_kernel_pairs(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                    const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                    const int* idx_b, int n_pairs, double ninv, int mirror, double scale, int weight, double wc,
+                                    double* out, double* kvals, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_b);
+    if (!diagram_kernel_params_ok(ninv, mirror, scale, weight, wc))
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "ninv finite and < 0, mirror 0 or 1, scale finite, weight TDA_KW_*, wc finite");
+    if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
+    if (n_pairs == 0) return TDA_OK;
+    CHECK_PTR(ctx, out); CHECK_PTR(ctx, status);
+    if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_a = nullptr, *d_b = nullptr, *d_out, *d_kv = nullptr;
+    int *d_ca = nullptr, *d_cb = nullptr, *d_ia = nullptr, *d_ib = nullptr, *d_st;
+    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
+    if (n_b) { s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16); s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4); }
+    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
+    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
+    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
+    if (kvals) s.add((void**)&d_kv, nullptr, kvals, (size_t)n_pairs * 24);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_diagram_kernel_pairs_dev(ctx, d_a, d_ca, n_a, cap_a, d_b, d_cb, n_b, cap_b, d_ia, d_ib, n_pairs, ninv, mirror, scale,
+                                        weight, wc, d_out, d_kv, d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                   const int* seg_off_a, int n_seg_a, const int* status_a, const double* dgm_b,
+                                   const int* cnt_b, int n_b, int cap_b, const int* seg_off_b, int n_seg_b,
+                                   const int* status_b, int skip_mask, double ninv, int mirror, double scale, int weight,
+                                   double wc, double* out)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_seg_a);
+    const bool sym = dgm_b == nullptr;
+    if (sym) { n_b = n_a; n_seg_b = n_seg_a; }
+    CHECK_NONNEG(ctx, n_b); CHECK_NONNEG(ctx, n_seg_b);
+    if (!diagram_kernel_params_ok(ninv, mirror, scale, weight, wc))
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "ninv finite and < 0, mirror 0 or 1, scale finite, weight TDA_KW_*, wc finite");
+    if (cap_a < 1 || (!sym && cap_b < 1)) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
+    if ((!seg_off_a && n_seg_a != n_a) || (!sym && !seg_off_b && n_seg_b != n_b))
+        TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every diagram is a group: n_seg != n_dgm");
+    if (n_seg_a == 0 || n_seg_b == 0) return TDA_OK;
+    CHECK_PTR(ctx, out);
+    if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (!sym) CHECK_PTR(ctx, cnt_b);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_a = nullptr, *d_b = nullptr, *d_out;
+    int *d_ca = nullptr, *d_cb = nullptr, *d_oa = nullptr, *d_ob = nullptr, *d_sa = nullptr, *d_sb = nullptr;
+    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
+    if (seg_off_a) s.add((void**)&d_oa, seg_off_a, nullptr, (size_t)(n_seg_a + 1) * 4);
+    if (status_a && n_a) s.add((void**)&d_sa, status_a, nullptr, (size_t)n_a * 4);
+    if (!sym) {
+        // (an empty second set still needs a non-NULL buffer to be told from the symmetric form: 16 bytes of its own)
+        s.add((void**)&d_b, n_b ? dgm_b : nullptr, nullptr, n_b ? (size_t)n_b * cap_b * 16 : 16);
+        s.add((void**)&d_cb, n_b ? cnt_b : nullptr, nullptr, n_b ? (size_t)n_b * 4 : 4);
+        if (seg_off_b) s.add((void**)&d_ob, seg_off_b, nullptr, (size_t)(n_seg_b + 1) * 4);
+        if (status_b && n_b) s.add((void**)&d_sb, status_b, nullptr, (size_t)n_b * 4);
+    }
+    s.add((void**)&d_out, nullptr, out, (size_t)n_seg_a * n_seg_b * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_diagram_kernel_gram_dev(ctx, d_a, d_ca, n_a, cap_a, d_oa, n_seg_a, d_sa, d_b, d_cb, n_b, cap_b, d_ob, n_seg_b, d_sb,
+                                       skip_mask, ninv, mirror, scale, weight, wc, d_out, nullptr));
+    return s.download();
 }
 
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const double* grid,

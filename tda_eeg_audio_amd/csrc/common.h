@@ -251,6 +251,12 @@ tda_status launch_landscape_mean(tda_ctx*, const double*, const int*, int, int, 
                                  const double*, int, int, double*, hipStream_t);
 tda_status launch_image_mean(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, int, const double*,
                              int, const double*, int, double, int, double*, hipStream_t);
+tda_status launch_diagram_kernel_pairs(tda_ctx*, const double*, const int*, int, int, const double*, const int*, int, int,
+                                       const int*, const int*, int, double ninv, int mirror, double scale, int weight, double wc,
+                                       double*, double*, int*, hipStream_t);
+tda_status launch_diagram_kernel_gram(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, const double*,
+                                      const int*, int, int, const int*, int, const int*, int, double ninv, int mirror,
+                                      double scale, int weight, double wc, double*, hipStream_t);
 tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, int, const int*, const int*, int, const double*,
                                     const int*, int, int, const int*, int, const int*, const int*, double*, int*, hipStream_t);
 tda_status launch_cross_rows(tda_ctx*, const double*, const int*, const double*, const int*, const int*, int, double*,

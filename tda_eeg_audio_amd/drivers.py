@@ -171,6 +171,32 @@ def frechet_means_from_distances(dist_list, thresh=MAX_EDGE_LENGTH, max_iter=32)
     return out
 
 
+def diagram_kernel_gram_from_distances(dist_list, kernel=("pss", 0.1), thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it, one group of window distance matrices per recording.  The same Rips
+    launch with the same status checks, then one launch per diagram set (H0, H1): the (2, n_rec, n_rec) float64 Gram
+    matrices of the kernel on diagrams `kernel` -- ("pss", sigma) or ("pwg", sigma, c), engine.diagram_kernel_args --
+    between the recordings' mean embeddings (include/tdaeeg.h; engine.diagram_kernel_gram_dev): entry [g, h] is the average
+    of the kernel over all pairs of a window of g and a window of h.  Symmetric as bytes, ready for
+    SVC(kernel="precomputed"); the row and column of a recording without a window are NaN.  TdaError for a bad kernel."""
+    import torch
+    par = engine.diagram_kernel_args(kernel)
+    sizes = np.array([len(d) for d in dist_list])
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
+    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
+        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
+    check_status(st, "diagram_kernel_gram_from_distances")
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    out = torch.empty((2, len(dist_list), len(dist_list)), dtype=torch.float64, device=dev)
+    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
+        engine.diagram_kernel_gram_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev),
+                                       torch.from_numpy(np.ascontiguousarray(cnt)).to(dev), par, seg_off_a=seg_t, out_t=out[s],
+                                       ctx=ctx)
+    return out.cpu().numpy()
+
+
 def landscape_names(bands=BANDS, levels=5, grid=None):
     """Column names of landscapes_from_distances(...)[r] of every band, flattened band by band: per band and diagram set
     (h0, h1) the levels 1..levels and then the Betti curve, each at every grid point in order."""

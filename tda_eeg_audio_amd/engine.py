@@ -414,6 +414,109 @@ def sliced_wasserstein_gram(rows, cnt, dirs, ctx=None):
     return G
 
 
+def diagram_kernel_args(kernel):
+    """(ninv, mirror, scale, weight, wc) of a kernel on diagrams as the entry points take them (include/tdaeeg.h):
+      ("pss", sigma)     persistence scale-space kernel: ninv = -1 / (8 sigma), mirror 1, scale 1 / (8 pi sigma), weight 1
+      ("pwg", sigma, c)  persistence weighted Gaussian kernel: ninv = -1 / (2 sigma^2), mirror 0, scale 1, weight
+                         atan(c * persistence)
+    sigma and c are finite numbers > 0.  TdaError, before any GPU call, for anything else."""
+    def num(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) and v > 0
+    bad = _lib.TdaError(f"diagram kernel: ('pss', sigma) or ('pwg', sigma, c) with finite sigma, c > 0, not {kernel!r}")
+    if not isinstance(kernel, (tuple, list)) or len(kernel) < 2 or not isinstance(kernel[0], str) or not all(num(v) for v in kernel[1:]):
+        raise bad
+    try:
+        if kernel[0] == "pss" and len(kernel) == 2:
+            sigma = float(kernel[1])
+            args = (-1.0 / (8.0 * sigma), 1, 1.0 / (8.0 * np.pi * sigma), _lib.TDA_KW_ONE, 0.0)
+        elif kernel[0] == "pwg" and len(kernel) == 3:
+            sigma, c = float(kernel[1]), float(kernel[2])
+            args = (-1.0 / (2.0 * sigma * sigma), 0, 1.0, _lib.TDA_KW_ATAN, c)
+        else:
+            raise bad
+    except ZeroDivisionError:                        # sigma * sigma underflows
+        raise bad from None
+    if not (np.isfinite(args[0]) and args[0] < 0 and np.isfinite(args[2])):
+        raise bad                                    # a sigma so small or so large that ninv or scale is not a finite number < 0
+    return args
+
+
+def _kernel_params(kernel):
+    """`kernel` as the five parameters: a named kernel through diagram_kernel_args, or the five values themselves
+    (ninv, mirror, scale, weight, wc), which the library checks."""
+    if isinstance(kernel, (tuple, list)) and len(kernel) == 5 and not isinstance(kernel[0], str):
+        ninv, mirror, scale, weight, wc = kernel
+        return float(ninv), int(mirror), float(scale), int(weight), float(wc)
+    return diagram_kernel_args(kernel)
+
+
+def diagram_kernel_batch(rows_a, cnt_a, rows_b, cnt_b, kernel, idx_a=None, idx_b=None, ctx=None, want_status=False):
+    """Kernel values and kernel-induced distances of diagram pairs (include/tdaeeg.h): `kernel` as diagram_kernel_args
+    takes it (or the five raw parameters); the other arguments as wasserstein_batch.  Returns (dist (n_pairs,), kvals
+    (n_pairs, 3) = [k_ab, k_aa, k_bb]) and, with want_status, the status words: a pair whose index is outside its set is
+    NaN with TDA_WIN_NO_PAIR."""
+    par = _kernel_params(kernel)
+    ctx = ctx or get_ctx()
+    ra = f64(rows_a); rb = f64(rows_b); ca = i32(cnt_a); cb = i32(cnt_b)
+    n_a, cap_a, _ = ra.shape
+    n_b, cap_b, _ = rb.shape
+    if idx_a is None and idx_b is None:
+        assert n_a == n_b
+        n_pairs = n_a
+    else:
+        n_pairs = len(idx_a if idx_a is not None else idx_b)
+    ia = None if idx_a is None else i32(idx_a)
+    ib = None if idx_b is None else i32(idx_b)
+    out = np.empty(n_pairs); kv = np.empty((n_pairs, 3)); st = np.empty(n_pairs, np.int32)
+    ctx.check(ctx.lib.tda_diagram_kernel_pairs(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(rb), ptr(cb), n_b, cap_b, ptr(ia), ptr(ib),
+                                               n_pairs, *par, ptr(out), ptr(kv), ptr(st)))
+    return (out, kv, st) if want_status else (out, kv)
+
+
+def diagram_kernel_gram(rows_a, cnt_a, kernel, seg_off_a=None, status_a=None, rows_b=None, cnt_b=None, seg_off_b=None,
+                        status_b=None, skip_mask=0, ctx=None):
+    """Gram matrix of the mean embeddings of groups of diagrams (include/tdaeeg.h): G[g, h] = the average of the kernel
+    over all pairs of a kept diagram of group g and one of group h; NaN for a group without a kept diagram.  seg_off
+    (n_seg + 1,) int32 or None (every diagram its own group); diagrams whose status word has a bit of skip_mask are left
+    out.  Without rows_b the matrix of set A against itself, symmetric as bytes; with it the (n_seg_a, n_seg_b) cross
+    matrix."""
+    par = _kernel_params(kernel)
+    ctx = ctx or get_ctx()
+    ra = f64(rows_a); ca = i32(cnt_a)
+    n_a, cap_a, _ = ra.shape
+    oa = None if seg_off_a is None else i32(seg_off_a)
+    sa = None if status_a is None else i32(status_a)
+    n_ga = n_a if oa is None else len(oa) - 1
+    if rows_b is None:
+        rb = cb = ob = sb = None
+        n_b = cap_b = n_gb = 0
+        out = np.empty((n_ga, n_ga))
+    else:
+        rb = f64(rows_b); cb = i32(cnt_b)
+        n_b, cap_b, _ = rb.shape
+        ob = None if seg_off_b is None else i32(seg_off_b)
+        sb = None if status_b is None else i32(status_b)
+        n_gb = n_b if ob is None else len(ob) - 1
+        out = np.empty((n_ga, n_gb))
+        if n_b == 0:                                 # nothing on the B side: every group of it is empty
+            diagram_kernel_check(par, cap_a)
+            out.fill(np.nan)
+            return out
+    ctx.check(ctx.lib.tda_diagram_kernel_gram(ctx.h, ptr(ra), ptr(ca), n_a, cap_a, ptr(oa), n_ga, ptr(sa), ptr(rb), ptr(cb), n_b,
+                                              cap_b, ptr(ob), n_gb, ptr(sb), int(skip_mask), *par, ptr(out)))
+    return out
+
+
+def diagram_kernel_check(par, *caps):
+    """The library's own refusals for five raw parameters and diagram capacities, for a call that launches nothing."""
+    ninv, mirror, scale, weight, wc = par
+    ok = np.isfinite(ninv) and ninv < 0 and mirror in (0, 1) and np.isfinite(scale) and (
+        weight in (_lib.TDA_KW_ONE, _lib.TDA_KW_PERS) or (weight == _lib.TDA_KW_ATAN and np.isfinite(wc)))
+    if not ok or any(c < 1 for c in caps):
+        raise _lib.TdaError("libtdaeeg error 1: ninv finite and < 0, mirror 0 or 1, scale finite, weight TDA_KW_*, wc finite, "
+                            "cap >= 1")
+
+
 # ------------------------------------------------------------------ device-tensor API (torch)
 def _tp(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
@@ -784,6 +887,54 @@ def sliced_wasserstein_dev(rows_a, cnt_a, rows_b, cnt_b, dirs_t, idx_a=None, idx
         raise _lib.TdaError("libtdaeeg error 1: dirs_t must be a contiguous (M, 2) float64 tensor")
     return _pair_dev(ctx.lib.tda_sliced_wasserstein_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx,
                      _tp(dirs_t), dirs_t.shape[0])
+
+
+def diagram_kernel_dev(rows_a, cnt_a, rows_b, cnt_b, kernel, idx_a=None, idx_b=None, out_t=None, status_t=None, kvals_t=None,
+                       ctx=None):
+    """diagram_kernel_batch on device tensors: one launch on torch's current stream, nothing allocated when out_t and
+    status_t are given.  kvals_t: an optional (n_pairs, 3) float64 tensor for [k_ab, k_aa, k_bb].  Returns (out_t,
+    status_t); out_t is NaN where status_t != 0."""
+    import torch
+    par = _kernel_params(kernel)
+    ctx = ctx or get_ctx()
+    n_pairs = rows_a.shape[0] if idx_a is None and idx_b is None else (idx_a if idx_a is not None else idx_b).numel()
+    if out_t is None:
+        out_t = torch.empty(n_pairs, dtype=torch.float64, device=rows_a.device)
+    if status_t is None:
+        status_t = torch.empty(n_pairs, dtype=torch.int32, device=rows_a.device)
+    assert rows_a.is_contiguous() and rows_b.is_contiguous() and (kvals_t is None or kvals_t.is_contiguous())
+    ctx.check(ctx.lib.tda_diagram_kernel_pairs_dev(ctx.h, _tp(rows_a), _tp(cnt_a), rows_a.shape[0], rows_a.shape[1], _tp(rows_b),
+                                                   _tp(cnt_b), rows_b.shape[0], rows_b.shape[1], _tp(idx_a), _tp(idx_b), n_pairs,
+                                                   *par, _tp(out_t), _tp(kvals_t), _tp(status_t), _stream()))
+    return out_t, status_t
+
+
+def diagram_kernel_gram_dev(rows_a, cnt_a, kernel, seg_off_a=None, status_a=None, rows_b=None, cnt_b=None, seg_off_b=None,
+                            status_b=None, skip_mask=0, out_t=None, ctx=None):
+    """diagram_kernel_gram on device tensors: one launch on torch's current stream, nothing allocated when out_t is given.
+    out_t: (n_seg_a, n_seg_a) without rows_b, (n_seg_a, n_seg_b) with it."""
+    import torch
+    par = _kernel_params(kernel)
+    ctx = ctx or get_ctx()
+    n_a, cap_a, _ = rows_a.shape
+    n_ga = n_a if seg_off_a is None else seg_off_a.numel() - 1
+    n_b = cap_b = 0
+    n_gb = n_ga
+    if rows_b is not None:
+        n_b, cap_b, _ = rows_b.shape
+        n_gb = n_b if seg_off_b is None else seg_off_b.numel() - 1
+    if out_t is None:
+        out_t = torch.empty((n_ga, n_gb), dtype=torch.float64, device=rows_a.device)
+    assert rows_a.is_contiguous() and out_t.is_contiguous() and tuple(out_t.shape) == (n_ga, n_gb)
+    if rows_b is not None and n_b == 0:              # nothing on the B side: every group of it is empty
+        diagram_kernel_check(par, cap_a)
+        return out_t.fill_(float("nan"))
+    assert rows_b is None or rows_b.is_contiguous()
+    ctx.check(ctx.lib.tda_diagram_kernel_gram_dev(ctx.h, _tp(rows_a), _tp(cnt_a), n_a, cap_a, _tp(seg_off_a), n_ga, _tp(status_a),
+                                                  _tp(rows_b), _tp(cnt_b), n_b, cap_b, _tp(seg_off_b),
+                                                  n_gb if rows_b is not None else 0, _tp(status_b), int(skip_mask), *par,
+                                                  _tp(out_t), _stream()))
+    return out_t
 
 
 def group_table(seg_off_t, n):

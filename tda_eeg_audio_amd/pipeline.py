@@ -26,14 +26,15 @@ WQ_COLS = 2               # Workspace(wasserstein_q=(order, ground)).wq: [q_h0, 
 LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
 FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram sets, in the same order
+KD_COLS = 2               # Workspace(kernel_distance=kernel).kd: [k_h0, k_h1], the means of the kernel-induced distances
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
 def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None):
+                 frechet=None, kernel_distance=None):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq, fm.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -54,7 +55,10 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
       fm    frechet=(cap, max_iter), 1 <= cap <= FM_MAX_POINTS and 1 <= max_iter <= FM_MAX_ITER: (FM_SETS, cap + 2, 2), per
             diagram set of `land` (same windows, same audio mask) the Frechet mean of the group's diagrams in the order-2
             Wasserstein metric (engine.frechet_mean_dev): rows 0..cap-1 the mean, NaN beyond its count; row cap
-            [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else"""
+            [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else
+      kd    kernel_distance=("pss", sigma) or ("pwg", sigma, c) (engine.diagram_kernel_args): (KD_COLS,) np.nanmean of the
+            distance that kernel on diagrams induces between the H0 / H1 pairs (engine.diagram_kernel_dev) under the rule of
+            `bott`.  ValueError for anything else"""
     from . import _lib
     out = []
     if correlations:
@@ -89,6 +93,12 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
             raise ValueError(f"frechet=(cap, max_iter): integers, 1 <= cap <= {_lib.FM_MAX_POINTS}, "
                              f"1 <= max_iter <= {_lib.FM_MAX_ITER}") from None
         out.append(Output("fm", (FM_SETS, cap + 2, 2), (cap, max_iter)))
+    if kernel_distance is not None:
+        try:
+            engine.diagram_kernel_args(kernel_distance)
+        except _lib.TdaError:
+            raise ValueError("kernel_distance=('pss', sigma) or ('pwg', sigma, c): finite sigma, c > 0") from None
+        out.append(Output("kd", (KD_COLS,), (kernel_distance[0],) + tuple(float(v) for v in kernel_distance[1:])))
     return out
 
 
@@ -96,19 +106,21 @@ class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
     # per window: two distances, two status words
-    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1")
+    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1", "k0", "k1", "ks0", "ks1")
     # the buffers and resident tables of the optional outputs: None where the output is off
     corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
     land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
     wq = wasserstein_q = q0 = q1 = qs0 = qs1 = None
     fm = fm_sets = frechet = fm_out = None
+    kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None):
-        """correlations .. frechet: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None):
+        """correlations .. kernel_distance: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
-        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2) -- and with `bott` / `slc` / `wq` the distances of every
-        window, `b0` / `b1`, `s0` / `s1` and `q0` / `q1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1` and `qs0` / `qs1`.
+        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` the distances of every
+        window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1` and `k0` / `k1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`, `qs0` / `qs1`
+        and `ks0` / `ks1`.
         Grid, edges and directions are uploaded once, here."""
         import torch
         self.n_win, self.device = n_win, device
@@ -132,10 +144,10 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet)
+        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
-        self.wasserstein_q, self.frechet = par.get("wq"), par.get("fm")
+        self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
@@ -156,6 +168,8 @@ class Workspace:
             self.s0, self.s1, self.ss0, self.ss1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.wasserstein_q is not None:
             self.q0, self.q1, self.qs0, self.qs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.kernel_distance is not None:
+            self.k0, self.k1, self.ks0, self.ks1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.frechet is not None:
             # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
             i32 = dict(dtype=torch.int32, device=device)
@@ -312,6 +326,9 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         order, ground = ws.wasserstein_q
         pair_means("wasserstein_q", functools.partial(engine.wasserstein_q_dev, order=order, ground=ground), (ws.q0, ws.q1),
                    (ws.qs0, ws.qs1), ws.wq)
+    if ws.kernel_distance is not None:
+        pair_means("kernel_distance", functools.partial(engine.diagram_kernel_dev, kernel=ws.kernel_distance), (ws.k0, ws.k1),
+                   (ws.ks0, ws.ks1), ws.kd)
     if ws.fm is not None:
         stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
@@ -642,4 +659,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1" and "frechet", in this order after "wasserstein_h1")
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1" and "frechet", in this order after
+# "wasserstein_h1")

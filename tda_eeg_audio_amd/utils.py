@@ -312,6 +312,45 @@ def safe_sliced_wasserstein(dgm1, dgm2, dirs=None, M=50):
         return np.nan
 
 
+def diagram_kernel(dgm1, dgm2, kernel=("pss", 0.1)):
+    """The value of a kernel on diagrams for two diagrams (include/tdaeeg.h): kernel = ("pss", sigma), the persistence
+    scale-space kernel of Reininghaus et al. (2015), or ("pwg", sigma, c), the persistence weighted Gaussian kernel of
+    Kusano et al. (2016) with weight atan(c * persistence).  Rows with a non-finite entry do not count; an empty diagram is
+    the zero measure and gives 0.0.  Runs at once, also inside a `batch`.  Not in the reference; TdaError for a bad kernel,
+    ValueError for a diagram that is not a (k, 2) table."""
+    par = engine.diagram_kernel_args(kernel)
+    ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+    rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+    _, kv = engine.diagram_kernel_batch(ra, ca, rb, cb, par)
+    return float(kv[0, 0])
+
+
+def kernel_distance(dgm1, dgm2, kernel=("pss", 0.1)):
+    """The distance a kernel on diagrams induces, sqrt(k(A, A) + k(B, B) - 2 k(A, B)) (include/tdaeeg.h), for the kernels
+    of diagram_kernel.  It needs no matching.  NaN on any failure, as safe_wasserstein."""
+    if _ACTIVE is not None:
+        return _ACTIVE.add_kernel_distance(dgm1, dgm2, kernel)
+    try:
+        ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+        rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+        out, _, st = engine.diagram_kernel_batch(ra, ca, rb, cb, engine.diagram_kernel_args(kernel), want_status=True)
+        return float(out[0]) if st[0] == 0 else np.nan
+    except Exception:
+        return np.nan
+
+
+def diagram_kernel_gram(dgms, kernel=("pss", 0.1)):
+    """(n, n) Gram matrix of a kernel on diagrams over a list of diagrams, symmetric as bytes, ready for
+    SVC(kernel="precomputed") or kernel PCA.  TdaError for a bad kernel, ValueError for a diagram that is not a (k, 2)
+    table."""
+    par = engine.diagram_kernel_args(kernel)
+    tabs = [_clean_pair_diagram(d) for d in dgms]
+    if not tabs:
+        return np.zeros((0, 0))
+    rows, cnt = engine.pack_diagrams(tabs)
+    return engine.diagram_kernel_gram(rows, cnt, par)
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -412,7 +451,7 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_wasserstein_q, safe_sliced_wasserstein, extract_features, persistence_landscape, betti_curve and
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_wasserstein_q, safe_sliced_wasserstein, kernel_distance, extract_features, persistence_landscape, betti_curve and
     persistence_image
     queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
@@ -426,6 +465,7 @@ class batch:
         self.imgs = []
         self.spairs = []              # safe_sliced_wasserstein: (dgm1, dgm2, direction table, deferred value)
         self.qpairs = []              # safe_wasserstein_q: (dgm1, dgm2, (order, ground), deferred value)
+        self.kpairs = []              # kernel_distance: (dgm1, dgm2, kernel, deferred value)
 
     def __enter__(self):
         global _ACTIVE
@@ -476,6 +516,15 @@ class batch:
         self.spairs.append((a, b, d, s))
         return s
 
+    def add_kernel_distance(self, a, b, kernel):
+        s = DeferredScalar(self)
+        try:
+            par = engine.diagram_kernel_args(kernel)
+        except Exception:
+            par = None                              # a bad kernel: NaN for this pair alone
+        self.kpairs.append((a, b, par, s))
+        return s
+
     def add_features(self, dgm):
         f = DeferredFeatures(self)
         self.feats.append((dgm, f))
@@ -503,6 +552,7 @@ class batch:
         imgs, self.imgs = self.imgs, []
         spairs, self.spairs = self.spairs, []
         qpairs, self.qpairs = self.qpairs, []
+        kpairs, self.kpairs = self.kpairs, []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -586,6 +636,26 @@ class batch:
                     ra, ca = engine.pack_diagrams([g[0] for g in good])
                     rb, cb = engine.pack_diagrams([g[1] for g in good])
                     out, st = engine.wasserstein_q_batch(ra, ca, rb, cb, order=order, ground=ground, want_status=True)
+                    for i, g in enumerate(good):
+                        g[2]._value = float(out[i]) if st[i] == 0 else np.nan
+                except Exception:
+                    pass
+        if kpairs:
+            # one launch per kernel; a malformed pair or a bad kernel is NaN by itself
+            groups = {}
+            for p in kpairs:
+                p[3]._value = np.nan
+                try:
+                    g = (_clean_pair_diagram(self._resolve(p[0])), _clean_pair_diagram(self._resolve(p[1])), p[3])
+                    if p[2] is not None:
+                        groups.setdefault(p[2], []).append(g)
+                except Exception:
+                    pass
+            for par, good in groups.items():
+                try:
+                    ra, ca = engine.pack_diagrams([g[0] for g in good])
+                    rb, cb = engine.pack_diagrams([g[1] for g in good])
+                    out, _, st = engine.diagram_kernel_batch(ra, ca, rb, cb, par, want_status=True)
                     for i, g in enumerate(good):
                         g[2]._value = float(out[i]) if st[i] == 0 else np.nan
                 except Exception:
