@@ -286,6 +286,46 @@ __device__ __forceinline__ int wave_incl_scan_i32(int v)
     return v;
 }
 
+// the value of the lane below (lane 0: zero), on the DPP network; every lane of the wave must be active
+__device__ __forceinline__ u32 wave_shr1_u32(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true); }    // wave_shr:1
+
+// Items of a work list in owner order, one per lane (own1 = owner + 1; 0 = no item): the last non-zero vector among the
+// items of the same owner in the up to 8 lanes below (zero when there is none; row_shr reaches the 16 lanes of a DPP row
+// only, so a run of items that crosses a row is cut there).  Every lane of the wave must be active.
+template <int W, typename WT>
+__device__ __forceinline__ Psi<W, WT> last_nonzero_of_owner(Psi<W, WT> y, u32 own1)
+{
+    constexpr int H = (int)sizeof(WT) / 4;
+    u32 x[W * H];
+    {   // the item below, if it is the owner's
+        const bool mine = wave_shr1_u32(own1) == own1;
+#pragma unroll
+        for (int i = 0; i < W * H; ++i) {
+            const u32 below = wave_shr1_u32((u32)((u64)y.w[i / H] >> (32 * (i % H))));
+            x[i] = mine ? below : 0u;
+        }
+    }
+#define TDA_STEP_(CTRL)                                                                                              \
+    {                                                                                                                \
+        u32 any = 0u;                                                                                                \
+        _Pragma("unroll") for (int i = 0; i < W * H; ++i) any |= x[i];                                               \
+        const bool take = any == 0u && (u32)__builtin_amdgcn_update_dpp(0, (int)own1, CTRL, 0xF, 0xF, true) == own1; \
+        _Pragma("unroll") for (int i = 0; i < W * H; ++i) {                                                          \
+            const u32 o = (u32)__builtin_amdgcn_update_dpp(0, (int)x[i], CTRL, 0xF, 0xF, true);                      \
+            x[i] = take ? o : x[i];                                                                                  \
+        }                                                                                                            \
+    }
+    TDA_STEP_(0x111) TDA_STEP_(0x112) TDA_STEP_(0x114)     // row_shr:1, 2, 4
+#undef TDA_STEP_
+    Psi<W, WT> r;
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+        if constexpr (H == 2) r.w[c] = (WT)(((u64)x[2 * c + 1] << 32) | x[2 * c]);
+        else r.w[c] = (WT)x[c];
+    }
+    return r;
+}
+
 __device__ __forceinline__ int edge_flat(u32 pk) { return tri2((int)(pk >> 8)) + (int)(pk & 255u); }
 
 // monotone map from a sortable key in [kmin, teff] to a bucket in [0, NB)
@@ -702,6 +742,11 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
     constexpr int WB = 8 * (int)sizeof(WT);          // class bits per word
     float* bkey = reinterpret_cast<float*>(misc + MISC_BRANK + 4 * WB * W);
     u64* adjc = reinterpret_cast<u64*>(misc + MISC_ADJC);    // adjc[2*v + w]: neighbours of v through edges of this chunk
+    // phase d, sums over the waves: [w] = the counts of the waves before w, [8] = the total.  tcum: triangles to test;
+    // ecum: entries of a trip, two sets used alternately.  (Behind the ballots and offsets of phase b in the comp block.)
+    int* tcum = reinterpret_cast<int*>(misc + MISC_COMP + 256);
+    int* ecum = reinterpret_cast<int*>(misc + MISC_COMP + 320);
+    int eset = 0;
 
     if constexpr (!NARROW) for (int e = tid0; e < E; e += NT) psi[e] = pzero<W, WT>();
     for (int i = tid0; i < WB * W; i += NT) { brank[i] = -1; bkey[i] = 0.f; }
@@ -855,6 +900,7 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
             if (lane == 0) { cand[wave] = bal; zbal[wave] = zb; }
         }
         done[tid] = 0;
+        if (tid < 9) tcum[tid] = 0;                  // (phase d's sum of triangles: zero a barrier ahead of its atomics)
         __syncthreads();
         PROF_MARK(21);
         PROF_STOPC(12, out_k0 = k0; out_k1 = k1; out_status = 0);
@@ -1236,25 +1282,42 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         // trivial and the list is complete.  The psi table is rewritten ONCE per chunk with the
         // composed substitution.  If the list does not fit, only its earliest entry is processed and
         // the chunk is listed again.
-        const int ta_ = tri2(a), tb_ = tri2(b);
         constexpr int ES = 4 + W * (int)sizeof(WT);                  // list entry: key, vector
-        // One class word: wave 0 puts the list into the order of the killing edges first (counting sort on the lane
-        // that listed the entry: every thread leaves its number of entries in hist[], entry keys carry their index
-        // within the thread in bits 24..31), so that "the earliest non-zero vector" is a ballot and a count of
-        // trailing zeros instead of a reduction over the wave.  Entries of ONE edge may come in any order: the
-        // classes they kill and the images of those classes depend on their span only.
+        // The list stands in the order of the killing edges (owner, then v: see the listing loop), so with one class
+        // word "the earliest non-zero vector" is a ballot and a count of trailing zeros instead of a reduction over
+        // the wave.  Entries of ONE edge may come in any order: the classes they kill and the images of those classes
+        // depend on their span only.
         constexpr bool SORTED = W == 1;
-        constexpr int HISTN = (NT + 255) & ~255;                     // (counters beyond NT stay zero: the scan reads whole words)
-        constexpr int HIST_BYTES = SORTED ? HISTN + 8 : 0;           // u8 hist[NT] behind the entries (8-byte aligned)
-        constexpr int LMAX = SORTED ? 255 : 256;                     // (sorted: offsets are bytes)
+        constexpr int HISTN = (NT + 255) & ~255;
+        constexpr int HIST_BYTES = SORTED ? HISTN + 8 : 0;           // (the capacity of the list when wave 0 still sorted it: kept)
+        constexpr int LMAX = SORTED ? 255 : 256;
         constexpr int LCAP = ((MISC_LIST_BYTES - HIST_BYTES) / ES) < LMAX ? ((MISC_LIST_BYTES - HIST_BYTES) / ES) : LMAX;
         constexpr int LPL = (LCAP + 63) / 64;
         // class-indexed image table (one Psi per class) when it fits the list area; else kill records
         constexpr bool FTAB = WB * W * (int)sizeof(Psi<W, WT>) <= MISC_LIST_BYTES;
         constexpr int KMAX = FTAB ? 64 : LCAP;                       // kills per reduction round
         unsigned char* list = misc + MISC_LIST;
-        unsigned char* hist = list + ((LCAP * ES + 7) & ~7);
-        const u32 mws[4] = {m0, m1, m2, m3};
+        // The triangles to test, as a work list in owner order: every owner counts the bits of its mask, an exclusive
+        // prefix over the workgroup gives it the index of its first triangle (the masks stand for the whole chunk, so
+        // this is done once), and per trip of NT triangles the owners write one code each, (owner << 8) | v in ascending
+        // v, and then EVERY lane tests one.  (Before, only the owner walked its mask, four triangles per trip of 8 rank
+        // and 8 dependent vector look-ups that the whole wave executed for its busiest lane.)
+        // Scratch: tlist = the rows of the chunk's own edges (last read in phase a, cleared at the chunk end).
+        // Sums over the waves (tcum, ecum: see their declaration): wave w adds its count to the words of the waves behind
+        // it and to the total with ONE LDS atomic of nine lanes; after the barrier a wave reads its own word and the total.
+        u32* tlist = reinterpret_cast<u32*>(adjc);
+        static_assert(4 * NT <= 128 * 16 && NT / 64 <= 8, "the work list lives in adjc; nine words per sum");
+        const bool cum_lane = lane == 8 || (lane < 8 && lane > wave);
+        const int ntri = __builtin_popcount(m0) + __builtin_popcount(m1) + __builtin_popcount(m2) + __builtin_popcount(m3);
+        int tstart, ttot;                                            // my first triangle; triangles of the chunk
+        const int incl_ = wave_incl_scan_i32(ntri);                  // (rem is zero in lanes that own no apparent edge)
+        const int wtri = __builtin_amdgcn_readlane(incl_, 63);
+        {
+            if (wtri != 0 && cum_lane) atomicAdd(&tcum[lane], wtri);
+            __syncthreads();
+            tstart = tcum[wave] + incl_ - ntri;
+            ttot = uni(tcum[8]);
+        }
 #ifdef TDA_PROFILE
         {   // diagnostic: triangles left to test after the link closure, and apparent edges
             const int ntri = __builtin_popcount(m0) + __builtin_popcount(m1) + __builtin_popcount(m2) + __builtin_popcount(m3);
@@ -1267,83 +1330,89 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
 #endif
         int list_rounds = 0;
         while (true) {
-            if (list_rounds > 0) {                     // the first listing finds the header reset (chunk end)
-                if (tid == 0) { lcnt[0] = 0u; lcnt[1] = 0xffffffffu; }
-                __syncthreads();
+            // (a round that lists the chunk again comes from the barrier behind the rewrite of the table)
+            u64 left[NVW];                                           // my triangles not yet on the work list
+            left[0] = (u64)m0 | ((u64)m1 << 32);
+            if (NVW == 2) left[NVW - 1] = (u64)m2 | ((u64)m3 << 32);
+            int nxt = tstart;                                        // index of the next of them
+            int lbase = 0;                                           // entries listed by the trips so far
+#ifdef TDA_PROFILE
+            {   // diagnostic, per list round: trips of a lane, triangles, waves that own any
+                PROF_COUNT(43, (ttot + NT - 1) / NT); PROF_COUNT(44, ttot); PROF_COUNT(47, 1);
+#ifndef TDA_PROFILE_STOPS_ONLY
+                if (wtri != 0 && lane == 0) atomicAdd(&prof_lds[45], 1ull);
+#endif
             }
-            u32 firstkey = 0xffffffffu;
-            Psi<W, WT> firsty = pzero<W, WT>();
-            u32 mycnt = 0u;                                          // entries of this thread in this round
-            if (apparent) {
-                base = psi[slot];
-                Psi<W, WT> prev = pzero<W, WT>();                    // a repeated vector reduces to zero: skip it
-                // (64 vertices per word: the four triangles of a trip may come from anywhere in it)
+#endif
+            for (int t0 = 0; t0 < ttot; t0 += NT) {
+                // this trip's sums of entries: the set of two trips ago, whose last reader is past a barrier since
+                int* ec = ecum + 16 * eset;
+                eset ^= 1;
+                if (tid < 9) ec[tid] = 0;
+                // the owners' codes of triangles t0 .. t0 + NT - 1 (the last readers of the trip before are past its
+                // second barrier): a bit scan and a store per triangle
 #pragma unroll
                 for (int wi = 0; wi < NVW; ++wi) {
-                    u64 mm = (u64)mws[2 * wi] | ((u64)mws[2 * wi + 1] << 32);
-                    const int vbase = 64 * wi;
-                    while (mm) {
-                        const int v0 = vbase + __builtin_ctzll(mm); mm &= mm - 1ull;
-                        const bool ok1 = mm != 0ull; const int v1 = ok1 ? vbase + __builtin_ctzll(mm) : v0; mm &= mm - 1ull;
-                        const bool ok2 = mm != 0ull; const int v2 = ok2 ? vbase + __builtin_ctzll(mm) : v0; mm &= mm - 1ull;
-                        const bool ok3 = mm != 0ull; const int v3 = ok3 ? vbase + __builtin_ctzll(mm) : v0; mm &= mm - 1ull;
-#define TDA_IDX_(v, ja, jb)                                                       \
-                        const int t##ja = (int)(__umul24((u32)(v), (u32)((v) - 1)) >> 1); \
-                        const int f##ja = (v) < a ? ta_ + (v) : t##ja + a;                 \
-                        const int f##jb = (v) < b ? tb_ + (v) : t##ja + b;                 \
-                        const int ja = NARROW ? (int)rank[f##ja] : f##ja;                  \
-                        const int jb = NARROW ? (int)rank[f##jb] : f##jb;
-                        TDA_IDX_(v0, ja0, jb0) TDA_IDX_(v1, ja1, jb1) TDA_IDX_(v2, ja2, jb2) TDA_IDX_(v3, ja3, jb3)
-#undef TDA_IDX_
-                        const Psi<W, WT> p0 = psi[ja0], q0 = psi[jb0], p1 = psi[ja1], q1_ = psi[jb1];
-                        const Psi<W, WT> p2 = psi[ja2], q2_ = psi[jb2], p3 = psi[ja3], q3 = psi[jb3];
-                        const Psi<W, WT> ys[4] = {pxor(pxor(p0, q0), base), pxor(pxor(p1, q1_), base),
-                                                  pxor(pxor(p2, q2_), base), pxor(pxor(p3, q3), base)};
-                        const bool oks[4] = {true, ok1, ok2, ok3};
-                        const int vs[4] = {v0, v1, v2, v3};
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (!oks[k] || !pnz(ys[k]) || !pnz(pxor(ys[k], prev))) continue;
-                            prev = ys[k];
-                            const u32 key = ((u32)tid << 8) | (u32)vs[k];
-                            if (firstkey == 0xffffffffu) { firstkey = key; firsty = ys[k]; }
-                            const u32 idx = atomicAdd(&lcnt[0], 1u);
-                            if (idx < (u32)LCAP) {
-                                *reinterpret_cast<u32*>(list + ES * idx) = SORTED ? key | (mycnt << 24) : key;
-#pragma unroll
-                                for (int c = 0; c < W; ++c)
-                                    *reinterpret_cast<WT*>(list + ES * idx + 4 + c * (int)sizeof(WT)) = ys[k].w[c];
-                            }
-                            ++mycnt;
-                        }
+                    while (left[wi] != 0ull && (u32)(nxt - t0) < (u32)NT) {
+                        const int v = 64 * wi + __builtin_ctzll(left[wi]);
+                        left[wi] &= left[wi] - 1ull;
+                        tlist[nxt - t0] = ((u32)tid << 8) | (u32)v;
+                        ++nxt;
                     }
                 }
+                __syncthreads();
+                // one triangle per lane: the owner's edge from ord, its vector, the two sides of the triangle (a wave
+                // beyond the last triangle of the trip has nothing to test and nothing to list)
+                u32 code = 0u;
+                Psi<W, WT> y = pzero<W, WT>();
+                bool keep = false;
+                u64 kb = 0ull;
+                if (t0 + (wave << 6) < ttot) {
+                    const bool item = t0 + tid < ttot;
+                    if (item) {
+                        code = tlist[tid];
+                        const int op = (int)(code >> 8), v = (int)(code & 255u);
+                        const u32 pk = ord[r0 + op];
+                        const int oa = (int)(pk >> 8), ob = (int)(pk & 255u);
+                        const int ta_ = tri2(oa), tb_ = tri2(ob);
+                        const int tv = (int)(__umul24((u32)v, (u32)(v - 1)) >> 1);
+                        const int fa = v < oa ? ta_ + v : tv + oa;
+                        const int fb = v < ob ? tb_ + v : tv + ob;
+                        const int ja = NARROW ? (int)rank[fa] : fa;
+                        const int jb = NARROW ? (int)rank[fb] : fb;
+                        y = pxor(pxor(psi[ja], psi[jb]), psi[NARROW ? r0 + op : ta_ + ob]);
+                    }
+                    // a zero vector is dropped, and so is a repetition of the owner's last non-zero vector (it reduces to
+                    // zero once that one has been dealt with).  Missing one only makes the list longer.
+                    const Psi<W, WT> pv = last_nonzero_of_owner(y, item ? (code >> 8) + 1u : 0u);
+                    keep = pnz(y) && pnz(pxor(y, pv));
+                    // entries placed by prefix: the list stands in (owner, v) order
+                    kb = __ballot(keep);
+                }
+                if (kb != 0ull && cum_lane) atomicAdd(&ec[lane], __builtin_popcountll(kb));
+                __syncthreads();
+                const int pos = lbase + ec[wave] + (int)__builtin_amdgcn_mbcnt_hi((u32)(kb >> 32), __builtin_amdgcn_mbcnt_lo((u32)kb, 0u));
+                lbase += uni(ec[8]);
+                if (keep && pos < LCAP) {
+                    *reinterpret_cast<u32*>(list + ES * pos) = code;
+#pragma unroll
+                    for (int c = 0; c < W; ++c)
+                        *reinterpret_cast<WT*>(list + ES * pos + 4 + c * (int)sizeof(WT)) = y.w[c];
+                }
             }
-            if (SORTED) {
-                hist[tid] = (unsigned char)mycnt;
-                if (NT < HISTN && tid < HISTN - NT) hist[NT + tid] = 0;
-            }
-            {
-                const u32 wmin = wave_min_u32_dpp(firstkey);
-                if (lane == 0 && wmin != 0xffffffffu) atomicMin(&lcnt[1], wmin);
+            if (lbase == 0) {                                        // (uniform: nothing listed, nothing to wait for)
+                PROF_MARK(17);
+                PROF_STOPC(17, out_k0 = k0; out_k1 = k1; out_status = 0);
+                break;
             }
             __syncthreads();
             PROF_MARK(17);
             PROF_STOPC(17, out_k0 = k0; out_k1 = k1; out_status = 0);
-            const u32 cnt = (u32)uni((int)lcnt[0]);
-            if (cnt == 0u) break;
-            const bool complete = cnt <= (u32)LCAP;
+            const u32 cnt = (u32)lbase;                              // the total, also when it exceeds LCAP
+            const bool complete = cnt <= (u32)LCAP;                  // (else only entry 0, the earliest, is processed)
             PROF_COUNT(11, 1);
             PROF_COUNT(12, cnt);
-            if (!complete) {
-                PROF_COUNT(13, 1);
-                if (firstkey == lcnt[1]) {                            // exactly one lane: keys are unique
-                    *reinterpret_cast<u32*>(list) = firstkey;
-#pragma unroll
-                    for (int c = 0; c < W; ++c) *reinterpret_cast<WT*>(list + 4 + c * (int)sizeof(WT)) = firsty.w[c];
-                }
-                __syncthreads();
-            }
+            if (!complete) PROF_COUNT(13, 1);
             WT alive_before[W];                                      // wave 0 updates `alive` while it reduces
 #pragma unroll
             for (int c = 0; c < W; ++c) alive_before[c] = alive[c];
@@ -1361,34 +1430,6 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
 #pragma unroll
                         for (int c = 0; c < W; ++c)
                             ev[q].w[c] = *reinterpret_cast<const WT*>(list + ES * idx + 4 + c * (int)sizeof(WT));
-                    }
-                }
-                if (SORTED && complete) {
-                    // exclusive prefix over hist[] (HW packed words of four counts per lane; at most 255 entries, so
-                    // bytes never carry), entries written back at offset-of-thread + index-in-thread, reloaded
-                    constexpr int HW = HISTN / 256;
-                    u32* hw = reinterpret_cast<u32*>(hist) + HW * lane;
-                    const u32 x0 = hw[0], x1 = HW == 2 ? hw[HW - 1] : 0u;
-                    const u32 s0 = __builtin_amdgcn_sad_u8(x0, 0u, 0u);
-                    const u32 tot = HW == 2 ? __builtin_amdgcn_sad_u8(x1, 0u, s0) : s0;
-                    const u32 before = (u32)wave_incl_scan_i32((int)tot) - tot;
-                    hw[0] = x0 * 0x01010101u - x0 + before * 0x01010101u;
-                    if (HW == 2) hw[HW - 1] = x1 * 0x01010101u - x1 + (before + s0) * 0x01010101u;
-#pragma unroll
-                    for (int q = 0; q < LPL; ++q) {
-                        if (lane + 64 * q < nl) {
-                            const int pos = (int)hist[(ek[q] >> 8) & 0xffffu] + (int)(ek[q] >> 24);
-                            *reinterpret_cast<u32*>(list + ES * pos) = ek[q] & 0x00ffffffu;
-                            *reinterpret_cast<WT*>(list + ES * pos + 4) = ev[q].w[0];
-                        }
-                    }
-#pragma unroll
-                    for (int q = 0; q < LPL; ++q) {
-                        const int idx = lane + 64 * q;
-                        if (idx < nl) {
-                            ek[q] = *reinterpret_cast<const u32*>(list + ES * idx);
-                            ev[q].w[0] = *reinterpret_cast<const WT*>(list + ES * idx + 4);
-                        }
                     }
                 }
                 // birth rank / length of the classes: lane i keeps bit i of every word
