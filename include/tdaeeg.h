@@ -758,6 +758,49 @@ tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int*
                                    const int* seg_off_b, int n_seg_b, const int* status_b, int skip_mask,
                                    double ninv, int mirror, double scale, int weight, double wc, double* out);
 
+/* ---- Persistence Fisher distance between diagrams ---------------------------------------
+ * The Fisher information metric distance between two persistence diagrams (Le and Yamada, NeurIPS 2018; the exact route of
+ * GUDHI's PersistenceFisherDistance, without kernel_approx), on which the persistence Fisher kernel exp(-t * out) is built;
+ * the kernel is formed by the Python layer, not on the device.  GUDHI is not installed anywhere this project runs, so no
+ * parity with it is claimed.  The contract is this text; tests/fisher_ref.py evaluates it.
+ *   Inputs.     Rows (b_i, d_i), i < min(max(cnt, 0), cap), float64.  F_A / F_B are the rows of A / B with both values
+ *               finite, in their stored order; m = |F_A|, n = |F_B|, N = m + n.  The diagonal image of a row is (h, h)
+ *               with h = 0.5 * (b + d), the formula of the sliced Wasserstein text.  The caller passes
+ *               ninv = -1 / (2 sigma^2): the device never divides by sigma.
+ *   Lists.      P = F_A followed by the images of F_B, N points.  Q = F_B followed by the images of F_A, N points.
+ *               Theta = P followed by Q, 2N points with multiplicity.
+ *   Values.     For x in Theta and u in a list: dx = x1 - u1; dy = x2 - u2; g = exp((dx * dx + dy * dy) * ninv).  No
+ *               multiply-add anywhere.
+ *                 r_P(x) = sum over u in P of g;  r_Q(x) likewise over Q
+ *                 Z_P = sum over x in Theta of r_P(x);  Z_Q likewise
+ *                 a_x = sqrt(r_P(x) / Z_P);  b_x = sqrt(r_Q(x) / Z_Q)
+ *                 c2 = sum over x in Theta of (a_x - b_x)^2
+ *                 out = 2 * asin(min(0.5 * sqrt(c2), 1))
+ *               N = 0 gives out = 0.  The arguments of exp are the same float64 on the GPU and in a CPU evaluation; only
+ *               exp, sqrt, asin and the order of the additions differ.
+ *   Form.       out is the angle acos(sum over x of sqrt(rho_P(x) rho_Q(x))) of the paper, rho = r / Z, written through the
+ *               chord between the unit vectors a and b.  The acos form loses half the digits near 0 and does not return 0
+ *               for a diagram against itself; the chord form is well conditioned on all of [0, pi / 2], the range of out.
+ *   Status.     N > TDA_PF_MAX_POINTS gives NaN and TDA_WIN_TOO_LARGE.  A pair index outside [0, n_a) or [0, n_b) gives
+ *               NaN and TDA_WIN_NO_PAIR.  Every other pair has status 0; out is NaN wherever status is not 0.
+ *   Limits.     A ninv that is not finite and < 0, or cap < 1, is TDA_ERR_INVALID and nothing is launched.
+ *   Determinism.  No atomics.  The order of the additions is not part of the contract, with two exceptions that are.  A pair
+ *               alone and the same pair inside a batch give the same bytes: nothing about the arithmetic depends on
+ *               anything but that pair's own m and n.  And r_P and r_Q, and Z_P and Z_Q, are accumulated by the same code
+ *               in the same order over their lists: two diagrams with the same finite rows in the same order give
+ *               out == 0.0 exactly, wherever their non-finite rows sit.
+ *   Tolerance.  Against a CPU evaluation of this text: (C + 8 N) * 2^-53 absolute, DESIGN.md 3.16.
+ * The _dev form only enqueues on `stream` and allocates nothing.  out (n_pairs) float64, status (n_pairs) int32. */
+#define TDA_PF_MAX_POINTS 512
+tda_status tda_persistence_fisher_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                            const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                            const int* idx_a, const int* idx_b, int n_pairs, double ninv,
+                                            double* out, int* status, void* stream);
+tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                        const double* dgm_b, const int* cnt_b, int n_b, int cap_b,
+                                        const int* idx_a, const int* idx_b, int n_pairs, double ninv,
+                                        double* out, int* status);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

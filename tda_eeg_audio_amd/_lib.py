@@ -39,6 +39,7 @@ TDA_GROUND_LINF = 1         # ... (d - b) / 2, the convention of the bottleneck 
 TDA_KW_ONE = 0              # tda_diagram_kernel_*: row weight 1.0
 TDA_KW_PERS = 1             # ... the persistence d - b
 TDA_KW_ATAN = 2             # ... atan(wc * (d - b))
+PF_MAX_POINTS = 512         # TDA_PF_MAX_POINTS
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -139,6 +140,8 @@ SYMBOLS = {
                                          _D, _I, _D, c_vp, c_vp]),
     "tda_diagram_kernel_gram": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, _D,
                                      _I, _D, c_vp]),
+    "tda_persistence_fisher_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, c_vp, c_vp, c_vp]),
+    "tda_persistence_fisher_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

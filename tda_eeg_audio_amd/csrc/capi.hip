@@ -615,6 +615,19 @@ tda_status tda_diagram_kernel_gram_dev(tda_ctx* ctx, const double* dgm_a, const 
                                       (hipStream_t)stream);
 }
 
+tda_status tda_persistence_fisher_batch_dev(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                            const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                            const int* idx_b, int n_pairs, double ninv, double* out, int* status,
+                                            void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_b);
+    if (n_pairs) { CHECK_PTR(ctx, out); CHECK_PTR(ctx, status); }
+    if (n_pairs && n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (n_pairs && n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
+    return launch_persistence_fisher(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, ninv, out,
+                                     status, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.
@@ -1124,6 +1137,34 @@ tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int*
     RET_IF(s.upload());
     RET_IF(tda_diagram_kernel_gram_dev(ctx, d_a, d_ca, n_a, cap_a, d_oa, n_seg_a, d_sa, d_b, d_cb, n_b, cap_b, d_ob, n_seg_b, d_sb,
                                        skip_mask, ninv, mirror, scale, weight, wc, d_out, nullptr));
+    return s.download();
+}
+
+// (its own staging, not pair_batch_host: an index outside its set is a status of that pair, not a refusal of the call)
+tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
+                                        const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
+                                        const int* idx_b, int n_pairs, double ninv, double* out, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs); CHECK_NONNEG(ctx, n_a); CHECK_NONNEG(ctx, n_b);
+    if (!std::isfinite(ninv) || !(ninv < 0.0)) TDA_FAIL(ctx, TDA_ERR_INVALID, "ninv must be finite and < 0");
+    if (cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "diagram capacity must be >= 1");
+    if (n_pairs == 0) return TDA_OK;
+    CHECK_PTR(ctx, out); CHECK_PTR(ctx, status);
+    if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
+    if (n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_a = nullptr, *d_b = nullptr, *d_out;
+    int *d_ca = nullptr, *d_cb = nullptr, *d_ia = nullptr, *d_ib = nullptr, *d_st;
+    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
+    if (n_b) { s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16); s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4); }
+    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
+    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
+    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_persistence_fisher_batch_dev(ctx, d_a, d_ca, n_a, cap_a, d_b, d_cb, n_b, cap_b, d_ia, d_ib, n_pairs, ninv, d_out,
+                                            d_st, nullptr));
     return s.download();
 }
 

@@ -257,6 +257,8 @@ tda_status launch_diagram_kernel_pairs(tda_ctx*, const double*, const int*, int,
 tda_status launch_diagram_kernel_gram(tda_ctx*, const double*, const int*, int, int, const int*, int, const int*, const double*,
                                       const int*, int, int, const int*, int, const int*, int, double ninv, int mirror,
                                       double scale, int weight, double wc, double*, hipStream_t);
+tda_status launch_persistence_fisher(tda_ctx*, const double*, const int*, int, int, const double*, const int*, int, int,
+                                     const int*, const int*, int, double ninv, double*, int*, hipStream_t);
 tda_status launch_wasserstein_cross(tda_ctx*, const double*, const int*, int, int, const int*, const int*, int, const double*,
                                     const int*, int, int, const int*, int, const int*, const int*, double*, int*, hipStream_t);
 tda_status launch_cross_rows(tda_ctx*, const double*, const int*, const double*, const int*, const int*, int, double*,

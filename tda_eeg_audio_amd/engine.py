@@ -517,6 +517,48 @@ def diagram_kernel_check(par, *caps):
                             "cap >= 1")
 
 
+def fisher_args(sigma):
+    """ninv = -1 / (2 sigma^2) of the persistence Fisher distance as the entry points take it (include/tdaeeg.h): sigma a
+    finite number > 0.  TdaError, before any GPU call, for anything else (a sigma whose ninv is not a finite number < 0
+    included)."""
+    bad = _lib.TdaError(f"persistence Fisher: sigma must be a finite number > 0, not {sigma!r}")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not np.isfinite(sigma) \
+            or not sigma > 0:
+        raise bad
+    s = float(sigma)
+    if s * s == 0.0:                                 # sigma * sigma underflows
+        raise bad
+    ninv = -1.0 / (2.0 * s * s)
+    if not (np.isfinite(ninv) and ninv < 0):
+        raise bad
+    return ninv
+
+
+def persistence_fisher_batch(rows_a, cnt_a, rows_b, cnt_b, sigma, idx_a=None, idx_b=None, ctx=None, want_status=False):
+    """Persistence Fisher distance of diagram pairs (include/tdaeeg.h: the Fisher information metric between the two
+    diagrams smoothed by Gaussians of width sigma on both diagrams and their diagonal images; in [0, pi / 2], exactly 0
+    for a diagram against itself); arguments and results as wasserstein_batch.  A pair with more than PF_MAX_POINTS finite
+    rows in all is NaN with TDA_WIN_TOO_LARGE, a pair whose index is outside its set NaN with TDA_WIN_NO_PAIR."""
+    ninv = fisher_args(sigma)
+    ctx = ctx or get_ctx()
+    return _pair_batch(ctx.lib.tda_persistence_fisher_batch, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, ctx, want_status, ninv)
+
+
+def persistence_fisher_gram(rows, cnt, sigma, ctx=None):
+    """(n, n) matrix of the persistence Fisher distances of one set of diagrams: the pairs i <= j in one batched call,
+    mirrored, so symmetric as bytes; the diagonal is computed, not set (it is 0.0 by the contract).  NaN where a pair has
+    a status."""
+    fisher_args(sigma)
+    n = len(cnt)
+    iu, ju = np.triu_indices(n)
+    G = np.zeros((n, n))
+    if len(iu):
+        d = persistence_fisher_batch(rows, cnt, rows, cnt, sigma, idx_a=iu, idx_b=ju, ctx=ctx)
+        G[iu, ju] = d
+        G[ju, iu] = d
+    return G
+
+
 # ------------------------------------------------------------------ device-tensor API (torch)
 def _tp(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
@@ -814,6 +856,35 @@ def wasserstein_q_dev(rows_a, cnt_a, rows_b, cnt_b, idx_a=None, idx_b=None, orde
     ctx = ctx or get_ctx()
     return _pair_dev(ctx.lib.tda_wasserstein_q_batch_dev, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx, order,
                      ground)
+
+
+def persistence_fisher_dev(rows_a, cnt_a, rows_b, cnt_b, sigma, idx_a=None, idx_b=None, out_t=None, status_t=None, ctx=None):
+    """persistence_fisher_batch on device tensors: one launch on torch's current stream, nothing allocated when out_t and
+    status_t are given.  out_t is NaN where status_t != 0."""
+    ninv = fisher_args(sigma)
+    ctx = ctx or get_ctx()
+    n_a, n_b = rows_a.shape[0], rows_b.shape[0]
+    assert rows_a.is_contiguous() and rows_b.is_contiguous()
+
+    def entry(h, a, ca, cap_a, b, cb, cap_b, *rest):     # the entry point also takes the sizes of the two sets
+        return ctx.lib.tda_persistence_fisher_batch_dev(h, a, ca, n_a, cap_a, b, cb, n_b, cap_b, *rest)
+    return _pair_dev(entry, rows_a, cnt_a, rows_b, cnt_b, idx_a, idx_b, out_t, status_t, ctx, ninv)
+
+
+def persistence_fisher_gram_dev(rows, cnt, sigma, ctx=None):
+    """persistence_fisher_gram on device tensors: the pairs i <= j in one launch with index lists built on the device,
+    mirrored; an (n, n) float64 device tensor equal to persistence_fisher_gram bit for bit."""
+    import torch
+    fisher_args(sigma)
+    n = rows.shape[0]
+    G = torch.zeros((n, n), dtype=torch.float64, device=rows.device)
+    if n:
+        iu = torch.triu_indices(n, n, 0, device=rows.device)
+        d, _ = persistence_fisher_dev(rows, cnt, rows, cnt, sigma, iu[0].to(torch.int32).contiguous(),
+                                      iu[1].to(torch.int32).contiguous(), ctx=ctx)
+        G[iu[0], iu[1]] = d
+        G[iu[1], iu[0]] = d
+    return G
 
 
 def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=None, skip_mask=0, out_t=None, ctx=None):

@@ -27,14 +27,15 @@ LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG
 IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
 FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram sets, in the same order
 KD_COLS = 2               # Workspace(kernel_distance=kernel).kd: [k_h0, k_h1], the means of the kernel-induced distances
+PF_COLS = 2               # Workspace(fisher=sigma).pf: [f_h0, f_h1], the means of the persistence Fisher distances
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
 def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None):
+                 frechet=None, kernel_distance=None, fisher=None):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -58,7 +59,9 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
             [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else
       kd    kernel_distance=("pss", sigma) or ("pwg", sigma, c) (engine.diagram_kernel_args): (KD_COLS,) np.nanmean of the
             distance that kernel on diagrams induces between the H0 / H1 pairs (engine.diagram_kernel_dev) under the rule of
-            `bott`.  ValueError for anything else"""
+            `bott`.  ValueError for anything else
+      pf    fisher=sigma, a finite number > 0 (engine.fisher_args): (PF_COLS,) np.nanmean of the persistence Fisher distances
+            of the H0 / H1 pairs (engine.persistence_fisher_dev) under the rule of `bott`.  ValueError for anything else"""
     from . import _lib
     out = []
     if correlations:
@@ -99,6 +102,12 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
         except _lib.TdaError:
             raise ValueError("kernel_distance=('pss', sigma) or ('pwg', sigma, c): finite sigma, c > 0") from None
         out.append(Output("kd", (KD_COLS,), (kernel_distance[0],) + tuple(float(v) for v in kernel_distance[1:])))
+    if fisher is not None:
+        try:
+            engine.fisher_args(fisher)
+        except _lib.TdaError:
+            raise ValueError("fisher=sigma: a finite number > 0") from None
+        out.append(Output("pf", (PF_COLS,), float(fisher)))
     return out
 
 
@@ -106,21 +115,24 @@ class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
     # per window: two distances, two status words
-    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1", "k0", "k1", "ks0", "ks1")
+    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1", "f0", "f1", "fs0", "fs1",
+                    "k0", "k1", "ks0", "ks1")
     # the buffers and resident tables of the optional outputs: None where the output is off
     corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
     land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
     wq = wasserstein_q = q0 = q1 = qs0 = qs1 = None
     fm = fm_sets = frechet = fm_out = None
     kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
+    pf = fisher = f0 = f1 = fs0 = fs1 = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None):
-        """correlations .. kernel_distance: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
+                 fisher=None):
+        """correlations .. fisher: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
-        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` the distances of every
-        window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1` and `k0` / `k1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`, `qs0` / `qs1`
-        and `ks0` / `ks1`.
+        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2), `pf` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` / `pf` the distances of every
+        window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1`, `k0` / `k1` and `f0` / `f1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`,
+        `qs0` / `qs1`, `ks0` / `ks1` and `fs0` / `fs1`.
         Grid, edges and directions are uploaded once, here."""
         import torch
         self.n_win, self.device = n_win, device
@@ -144,10 +156,12 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance)
+        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
+                                    fisher)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
         self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
+        self.fisher = par.get("pf")
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
@@ -170,6 +184,8 @@ class Workspace:
             self.q0, self.q1, self.qs0, self.qs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.kernel_distance is not None:
             self.k0, self.k1, self.ks0, self.ks1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.fisher is not None:
+            self.f0, self.f1, self.fs0, self.fs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.frechet is not None:
             # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
             i32 = dict(dtype=torch.int32, device=device)
@@ -329,6 +345,9 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     if ws.kernel_distance is not None:
         pair_means("kernel_distance", functools.partial(engine.diagram_kernel_dev, kernel=ws.kernel_distance), (ws.k0, ws.k1),
                    (ws.ks0, ws.ks1), ws.kd)
+    if ws.fisher is not None:
+        pair_means("fisher", functools.partial(engine.persistence_fisher_dev, sigma=ws.fisher), (ws.f0, ws.f1),
+                   (ws.fs0, ws.fs1), ws.pf)
     if ws.fm is not None:
         stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
@@ -659,5 +678,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1" and "frechet", in this order after
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1" and "frechet", in this order after
 # "wasserstein_h1")

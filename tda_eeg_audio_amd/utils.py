@@ -351,6 +351,46 @@ def diagram_kernel_gram(dgms, kernel=("pss", 0.1)):
     return engine.diagram_kernel_gram(rows, cnt, par)
 
 
+def persistence_fisher_distance(dgm1, dgm2, sigma=1.0):
+    """The persistence Fisher distance of Le and Yamada (2018) between two diagrams (include/tdaeeg.h): both diagrams,
+    each with the other's diagonal images, smoothed by Gaussians of width sigma into two probability vectors on the
+    points of both, and the Fisher information metric (the angle between their square roots) between them.  In
+    [0, pi / 2], exactly 0.0 for a diagram against itself; rows with a non-finite entry do not count.  It needs no
+    matching.  NaN on any failure (a bad sigma, more than PF_MAX_POINTS finite rows in all), as kernel_distance."""
+    if _ACTIVE is not None:
+        return _ACTIVE.add_fisher_distance(dgm1, dgm2, sigma)
+    try:
+        ra, ca = engine.pack_diagrams([_clean_pair_diagram(dgm1)])
+        rb, cb = engine.pack_diagrams([_clean_pair_diagram(dgm2)])
+        out, st = engine.persistence_fisher_batch(ra, ca, rb, cb, sigma, want_status=True)
+        return float(out[0]) if st[0] == 0 else np.nan
+    except Exception:
+        return np.nan
+
+
+def persistence_fisher_kernel(dgm1, dgm2, sigma=1.0, t=1.0):
+    """The persistence Fisher kernel exp(-t * persistence_fisher_distance(dgm1, dgm2, sigma)); NaN where the distance is."""
+    return np.exp(-t * float(persistence_fisher_distance(dgm1, dgm2, sigma)))
+
+
+def persistence_fisher_distances(dgms, sigma=1.0):
+    """(n, n) matrix of the persistence Fisher distances over a list of diagrams, symmetric as bytes, its diagonal 0.0;
+    NaN where a pair has more than PF_MAX_POINTS finite rows in all.  (0, 0) for an empty list.  TdaError for a bad sigma,
+    ValueError for a diagram that is not a (k, 2) table."""
+    engine.fisher_args(sigma)
+    tabs = [_clean_pair_diagram(d) for d in dgms]
+    if not tabs:
+        return np.zeros((0, 0))
+    rows, cnt = engine.pack_diagrams(tabs)
+    return engine.persistence_fisher_gram(rows, cnt, sigma)
+
+
+def persistence_fisher_gram(dgms, sigma=1.0, t=1.0):
+    """(n, n) Gram matrix exp(-t * D) of the persistence Fisher kernel over a list of diagrams, D as
+    persistence_fisher_distances gives it: symmetric as bytes, ready for SVC(kernel="precomputed")."""
+    return np.exp(-t * persistence_fisher_distances(dgms, sigma))
+
+
 # --------------------------------------------------------------------------------------------
 # batch(): the reference's per-window loop, unchanged, at one launch per stage
 # --------------------------------------------------------------------------------------------
@@ -451,7 +491,7 @@ _ACTIVE = None
 class batch:
     """``with utils.batch():`` around the reference's per-window loop (scripts/tda_eeg_audio_comparison.py:88-99,
     scripts/matched_vs_mismatched.py:57-63,87-95) -- the loop stays as it is; compute_audio_persistence,
-    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_wasserstein_q, safe_sliced_wasserstein, kernel_distance, extract_features, persistence_landscape, betti_curve and
+    compute_eeg_persistence, safe_wasserstein, safe_bottleneck, safe_wasserstein_q, safe_sliced_wasserstein, kernel_distance, persistence_fisher_distance, extract_features, persistence_landscape, betti_curve and
     persistence_image
     queue their arguments and hand back deferred results,
     and on leaving the block (or at the first use of a value) everything queued runs as ONE launch per stage: the point
@@ -466,6 +506,7 @@ class batch:
         self.spairs = []              # safe_sliced_wasserstein: (dgm1, dgm2, direction table, deferred value)
         self.qpairs = []              # safe_wasserstein_q: (dgm1, dgm2, (order, ground), deferred value)
         self.kpairs = []              # kernel_distance: (dgm1, dgm2, kernel, deferred value)
+        self.fpairs = []              # persistence_fisher_distance: (dgm1, dgm2, sigma, deferred value)
 
     def __enter__(self):
         global _ACTIVE
@@ -525,6 +566,16 @@ class batch:
         self.kpairs.append((a, b, par, s))
         return s
 
+    def add_fisher_distance(self, a, b, sigma):
+        s = DeferredScalar(self)
+        try:
+            engine.fisher_args(sigma)
+            sigma = float(sigma)
+        except Exception:
+            sigma = None                            # a bad sigma: NaN for this pair alone
+        self.fpairs.append((a, b, sigma, s))
+        return s
+
     def add_features(self, dgm):
         f = DeferredFeatures(self)
         self.feats.append((dgm, f))
@@ -553,6 +604,7 @@ class batch:
         spairs, self.spairs = self.spairs, []
         qpairs, self.qpairs = self.qpairs, []
         kpairs, self.kpairs = self.kpairs, []
+        fpairs, self.fpairs = self.fpairs, []
         # ---- stage 1: all Rips calls (one launch per kernel flavour, threshold and matrix size)
         for th in sorted({c[1] for c in clouds}):
             grp = [c for c in clouds if c[1] == th]
@@ -656,6 +708,26 @@ class batch:
                     ra, ca = engine.pack_diagrams([g[0] for g in good])
                     rb, cb = engine.pack_diagrams([g[1] for g in good])
                     out, _, st = engine.diagram_kernel_batch(ra, ca, rb, cb, par, want_status=True)
+                    for i, g in enumerate(good):
+                        g[2]._value = float(out[i]) if st[i] == 0 else np.nan
+                except Exception:
+                    pass
+        if fpairs:
+            # one launch per sigma; a malformed pair or a bad sigma is NaN by itself
+            groups = {}
+            for p in fpairs:
+                p[3]._value = np.nan
+                try:
+                    g = (_clean_pair_diagram(self._resolve(p[0])), _clean_pair_diagram(self._resolve(p[1])), p[3])
+                    if p[2] is not None:
+                        groups.setdefault(p[2], []).append(g)
+                except Exception:
+                    pass
+            for sigma, good in groups.items():
+                try:
+                    ra, ca = engine.pack_diagrams([g[0] for g in good])
+                    rb, cb = engine.pack_diagrams([g[1] for g in good])
+                    out, st = engine.persistence_fisher_batch(ra, ca, rb, cb, sigma, want_status=True)
                     for i, g in enumerate(good):
                         g[2]._value = float(out[i]) if st[i] == 0 else np.nan
                 except Exception:
