@@ -801,6 +801,69 @@ tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const
                                         const int* idx_a, const int* idx_b, int n_pairs, double ninv,
                                         double* out, int* status);
 
+/* ---- Landmark Rips: greedy permutation (furthest-point sampling) in front of the cloud Rips ----------------
+ * ripser(X, n_perm=k) for clouds above TDA_MAX_POINTS points: k landmarks chosen by the greedy permutation, Rips on the
+ * landmarks alone, and the covering radius r_cover.  For each of H0 and H1 the landmark diagram lies within bottleneck
+ * distance 2 * r_cover of the diagram of the whole cloud.  The selection is upstream ripser.py's __get_greedy_perm, stated
+ * from knowledge of upstream.  The contract is this text; tests/landmark_ref.py evaluates it.
+ *   Cloud.      X, P points in dim coordinates.  Takens form: rows s[i * subsample + k * tau], k < dim, with
+ *               P = ceil((n_t - (dim - 1) * tau) / subsample) (0 when the numerator is <= 0), as tda_takens_rips_batch
+ *               builds it, always normalised.  Cloud form: the first n_pts[w] rows of pc[w], (n_win, p_cap, dim).  With
+ *               normalise, X is first min-max normalised per column over the whole cloud: (x - min) / range, range 0
+ *               replaced by 1 (utils.py:127-130).
+ *   Distance.   To a pivot p, for i != p:
+ *                 d(i, p) = sqrt(max(((-2 * dot(x_i, x_p)) + |x_i|^2) + |x_p|^2, 0)),   d(p, p) = 0
+ *               with dot = fma(.., fma(.., x0 * y0)), |x|^2 the left-to-right sum of the products without fma, and a
+ *               correctly rounded sqrt: column p of the distance matrix the cloud Rips ranks, kept in float64.
+ *   Selection.  For P > n_perm:  idx[0] = 0 and ds = d(., 0).  For t = 1 .. n_perm - 1: idx[t] = the LOWEST index at which
+ *               ds attains its maximum (values compared after the square root, as np.argmax does);
+ *               lambda[t - 1] = ds[idx[t]];  ds = min(ds, d(., idx[t])).  Last, lambda[n_perm - 1] = max(ds) = r_cover.
+ *               n_lm = n_perm.  The text is followed literally: once every point is covered at distance 0, index 0 is
+ *               picked again and the landmark cloud has duplicate rows.
+ *   Identity.   For P <= n_perm nothing is selected: idx = 0 .. P - 1, n_lm = P, lambda[0 .. P - 1] = 0, r_cover = 0.
+ *   Outputs.    lm (n_win, n_perm, dim) float64: the landmark rows X[idx[t]] (normalised when X is), in selection order;
+ *               lm_idx (n_win, n_perm) int32;  lm_lambda (n_win, n_perm) float64, may be null;  r_cover (n_win) float64;
+ *               n_lm (n_win) int32;  n_full (n_win) int32 = P.  Rows and entries from n_lm on are left untouched.
+ *   Refused windows.  tau < 1 in the Takens form, or P > TDA_LM_MAX_POINTS (cloud form: P > min(p_cap,
+ *               TDA_LM_MAX_POINTS)): n_lm = TDA_MAX_POINTS + 1 -- a count no landmark set can have --, r_cover = NaN,
+ *               n_full = P, nothing else written.  A negative n_pts counts as 0.
+ *   Diagrams.   tda_takens_rips_landmarks runs the selection into the caller's landmark buffers and then
+ *               tda_cloud_rips_batch on (lm, n_lm) with normalise = 0: its diagrams ARE the diagrams of the cloud path on
+ *               the landmark rows, by composition; retry policy and widening ladder apply to that second stage unchanged.
+ *               P < 3 ends as TDA_WIN_DEGENERATE with [[0,0]],[[0,0]], a refused window as TDA_WIN_TOO_LARGE with counts
+ *               0 (the cloud stage flags the count above TDA_MAX_POINTS itself).  n_points (nullable) receives n_lm.
+ *               h0_cap >= n_perm.
+ *   Limits.     3 <= n_perm <= TDA_MAX_POINTS, 1 <= dim <= TDA_MAX_DIM, subsample >= 1, 1 <= n_t <= TDA_LM_MAX_SAMPLES,
+ *               1 <= p_cap <= TDA_LM_MAX_POINTS; anything else is TDA_ERR_INVALID and nothing is launched.
+ *   Non-finite samples give unspecified landmarks (indices stay inside the cloud, the loop has a fixed trip count).
+ *   Determinism.  No atomics; a window alone and inside a batch give the same bytes.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage the output buffers in both
+ * directions, so "left untouched" holds for them too. */
+#define TDA_LM_MAX_POINTS 1024
+#define TDA_LM_MAX_SAMPLES 4096
+tda_status tda_takens_landmarks_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                    int subsample, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                    double* r_cover, int* n_lm, int* n_full, void* stream);
+tda_status tda_takens_landmarks(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                int subsample, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                double* r_cover, int* n_lm, int* n_full);
+tda_status tda_cloud_landmarks_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                   int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                   double* r_cover, int* n_lm, int* n_full, void* stream);
+tda_status tda_cloud_landmarks(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                               int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                               double* r_cover, int* n_lm, int* n_full);
+tda_status tda_takens_rips_landmarks_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                         int subsample, int n_perm, double thresh, double* lm, int* lm_idx,
+                                         double* lm_lambda, double* r_cover, int* n_lm, int* n_full,
+                                         double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt,
+                                         int* n_points, int* status, void* stream);
+tda_status tda_takens_rips_landmarks(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                     int subsample, int n_perm, double thresh, double* lm, int* lm_idx,
+                                     double* lm_lambda, double* r_cover, int* n_lm, int* n_full,
+                                     double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt,
+                                     int* n_points, int* status);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

@@ -40,6 +40,8 @@ TDA_KW_ONE = 0              # tda_diagram_kernel_*: row weight 1.0
 TDA_KW_PERS = 1             # ... the persistence d - b
 TDA_KW_ATAN = 2             # ... atan(wc * (d - b))
 PF_MAX_POINTS = 512         # TDA_PF_MAX_POINTS
+LM_MAX_POINTS = 1024        # TDA_LM_MAX_POINTS: largest cloud the greedy permutation (n_perm) takes
+LM_MAX_SAMPLES = 4096       # TDA_LM_MAX_SAMPLES
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -142,6 +144,14 @@ SYMBOLS = {
                                      _I, _D, c_vp]),
     "tda_persistence_fisher_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, c_vp, c_vp, c_vp]),
     "tda_persistence_fisher_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, _I, _D, c_vp, c_vp]),
+    "tda_takens_landmarks_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_takens_landmarks": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_cloud_landmarks_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_cloud_landmarks": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_takens_rips_landmarks_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, _D, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_takens_rips_landmarks": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, _D, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

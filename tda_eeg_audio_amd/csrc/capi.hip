@@ -229,6 +229,49 @@ tda_status tda_cloud_rips_batch_dev(tda_ctx* ctx, const double* pc, const int* n
                              h1_cap, h1_cnt, nullptr, status, (hipStream_t)stream);
 }
 
+#define CHECK_LM_PTRS(ctx) do { CHECK_PTR(ctx, lm); CHECK_PTR(ctx, lm_idx); CHECK_PTR(ctx, r_cover); CHECK_PTR(ctx, n_lm); \
+                                CHECK_PTR(ctx, n_full); } while (0)
+
+tda_status tda_takens_landmarks_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                    int subsample, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                    double* r_cover, int* n_lm, int* n_full, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx); }
+    return launch_landmarks(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, n_perm, lm, lm_idx, lm_lambda, r_cover, n_lm,
+                            n_full, (hipStream_t)stream);
+}
+
+tda_status tda_cloud_landmarks_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                   int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                   double* r_cover, int* n_lm, int* n_full, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_LM_PTRS(ctx); }
+    return launch_landmarks(ctx, pc, n_pts, n_win, p_cap, dim, 1, 1, normalise, n_perm, lm, lm_idx, lm_lambda, r_cover,
+                            n_lm, n_full, (hipStream_t)stream);
+}
+
+tda_status tda_takens_rips_landmarks_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                         int subsample, int n_perm, double thresh, double* lm, int* lm_idx,
+                                         double* lm_lambda, double* r_cover, int* n_lm, int* n_full,
+                                         double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt,
+                                         int* n_points, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt);
+                 CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status); }
+    // everything the second stage would refuse is refused here, before the first one is launched
+    if (h1_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "h1_cap must be >= 1");
+    if (n_perm >= 3 && h0_cap < n_perm) TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_cap must be >= n_perm");
+    tda_status rc = launch_landmarks(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, n_perm, lm, lm_idx, lm_lambda,
+                                     r_cover, n_lm, n_full, (hipStream_t)stream);
+    if (rc != TDA_OK) return rc;
+    // the landmark rows are normalised already; a refused window carries a count above TDA_MAX_POINTS
+    return launch_rips_cloud(ctx, lm, n_lm, n_win, n_perm, dim, 1, 1, 0, thresh, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt,
+                             n_points, status, (hipStream_t)stream);
+}
+
 tda_status tda_sosfiltfilt_dev(tda_ctx* ctx, const double* x, int n_sig, int n_samples, const double* sos,
                                const double* zi, int n_sections, int edge, double* y, double* work, void* stream)
 {
@@ -795,6 +838,97 @@ tda_status tda_cloud_rips_batch(tda_ctx* ctx, const double* pc, const int* n_pts
     RET_IF(s.upload());
     RET_IF(tda_cloud_rips_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d_h0, h0_cap, d_c0, d_h1,
                                     h1_cap, d_c1, d_st, nullptr));
+    return s.download();
+}
+
+// The landmark outputs of a host call: staged in BOTH directions, so what the kernel leaves untouched stays the caller's.
+struct LmStage {
+    double *lm, *lambda, *rc; int *idx, *n_lm, *n_full;
+    void add(Stage& s, int n_win, int n_perm, int dim, double* h_lm, int* h_idx, double* h_lambda, double* h_rc, int* h_nlm,
+             int* h_nfull)
+    {
+        const size_t nw = (size_t)n_win;
+        lambda = nullptr;
+        s.add((void**)&lm, h_lm, h_lm, nw * n_perm * dim * 8);
+        s.add((void**)&idx, h_idx, h_idx, nw * n_perm * 4);
+        if (h_lambda) s.add((void**)&lambda, h_lambda, h_lambda, nw * n_perm * 8);
+        s.add((void**)&rc, h_rc, h_rc, nw * 8);
+        s.add((void**)&n_lm, h_nlm, h_nlm, nw * 4);
+        s.add((void**)&n_full, h_nfull, h_nfull, nw * 4);
+    }
+};
+#define CHECK_LM_LIMITS(ctx, cap_ok)                                                                                   \
+    do { if (n_perm < 3 || n_perm > TDA_MAX_POINTS || dim < 1 || dim > TDA_MAX_DIM || !(cap_ok))                      \
+             TDA_FAIL(ctx, TDA_ERR_INVALID, "landmarks: n_perm, dim or a size outside its limits"); } while (0)
+
+tda_status tda_takens_landmarks(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                int subsample, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                                double* r_cover, int* n_lm, int* n_full)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    CHECK_LM_LIMITS(ctx, subsample >= 1 && n_t >= 1 && n_t <= TDA_LM_MAX_SAMPLES);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double* d_win; int* d_tau; LmStage o;
+    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
+    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
+    o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
+    RET_IF(s.upload());
+    RET_IF(tda_takens_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, o.lm, o.idx, o.lambda, o.rc,
+                                    o.n_lm, o.n_full, nullptr));
+    return s.download();
+}
+
+tda_status tda_cloud_landmarks(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                               int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                               double* r_cover, int* n_lm, int* n_full)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    CHECK_LM_LIMITS(ctx, p_cap >= 1 && p_cap <= TDA_LM_MAX_POINTS);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_LM_PTRS(ctx);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double* d_pc; int* d_n; LmStage o;
+    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
+    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
+    o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
+    RET_IF(s.upload());
+    RET_IF(tda_cloud_landmarks_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, n_perm, o.lm, o.idx, o.lambda, o.rc,
+                                   o.n_lm, o.n_full, nullptr));
+    return s.download();
+}
+
+tda_status tda_takens_rips_landmarks(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                     int subsample, int n_perm, double thresh, double* lm, int* lm_idx,
+                                     double* lm_lambda, double* r_cover, int* n_lm, int* n_full,
+                                     double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt,
+                                     int* n_points, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    CHECK_LM_LIMITS(ctx, subsample >= 1 && n_t >= 1 && n_t <= TDA_LM_MAX_SAMPLES && h1_cap >= 1 && h0_cap >= n_perm);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt);
+    CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_win, *d_h0, *d_h1; int *d_tau, *d_c0, *d_c1, *d_np = nullptr, *d_st; LmStage o;
+    const size_t nw = (size_t)n_win;
+    s.add((void**)&d_win, win, nullptr, nw * n_t * 8);
+    s.add((void**)&d_tau, tau, nullptr, nw * 4);
+    o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
+    s.add((void**)&d_h0, nullptr, h0, nw * h0_cap * 16);
+    s.add((void**)&d_h1, nullptr, h1, nw * h1_cap * 16);
+    s.add((void**)&d_c0, nullptr, h0_cnt, nw * 4);
+    s.add((void**)&d_c1, nullptr, h1_cnt, nw * 4);
+    if (n_points) s.add((void**)&d_np, nullptr, n_points, nw * 4);
+    s.add((void**)&d_st, nullptr, status, nw * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_takens_rips_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, thresh, o.lm, o.idx,
+                                         o.lambda, o.rc, o.n_lm, o.n_full, d_h0, h0_cap, d_c0, d_h1, h1_cap, d_c1, d_np,
+                                         d_st, nullptr));
     return s.download();
 }
 

@@ -200,6 +200,10 @@ tda_status launch_eeg_sliding(tda_ctx*, const double*, int, int, int, int, int, 
 tda_status launch_rips_cloud(tda_ctx*, const double* win_or_pc, const int* tau_or_npts, int n_win, int n_t_or_pcap,
                              int dim, int subsample, int mode, int normalise, double thresh, double*, int, int*,
                              double*, int, int*, int* n_points, int*, hipStream_t);
+// (landmarks.hip) mode 0: Takens windows + tau; mode 1: explicit clouds + n_pts.  Checks the limits of the header itself.
+tda_status launch_landmarks(tda_ctx*, const double* win_or_pc, const int* tau_or_npts, int n_win, int n_t_or_pcap, int dim,
+                            int subsample, int mode, int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
+                            double* r_cover, int* n_lm, int* n_full, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,
                               hipStream_t, int n_filt = 1);
 tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, const double*, const double*, int, int, double*,

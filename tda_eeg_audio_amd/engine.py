@@ -7,7 +7,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
   host arrays  : corr_dist_batch, rips_dm_batch, takens_rips_batch, cloud_rips_batch,
                  tau_batch, features_batch, aggregate_batch, wasserstein_batch, bottleneck_batch, wasserstein_q_batch,
                  sliced_wasserstein_batch, sliced_wasserstein_gram,
-                 landscape_batch, image_batch, frechet_mean_batch, temporal_corr_batch
+                 landscape_batch, image_batch, frechet_mean_batch, temporal_corr_batch,
+                 takens_landmarks_batch, cloud_landmarks_batch (greedy permutation, ripser's n_perm)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -16,6 +17,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  (recordings.MatchMismatchPass).
                  sliced_prepare_dev / sliced_wasserstein_prepared_dev / sliced_wasserstein_gram_dev / sliced_matrix_dev:
                  the sliced Wasserstein distance with every diagram sorted once (MatchMismatchPass(sliced=dirs)).
+                 takens_landmarks_dev / cloud_landmarks_dev / takens_rips_landmarks_dev: Rips on greedy landmarks for clouds
+                 above 128 points (Workspace(takens=(dim, subsample, n_perm))).
 """
 import ctypes as C
 
@@ -130,6 +133,49 @@ def cloud_rips_batch(clouds, n_pts=None, normalise=True, thresh=MAX_EDGE_LENGTH,
     if raw:
         return h0, c0, h1, c1, st
     return _diagrams(h0, c0, h0_cap), _diagrams(h1, c1, h1_cap), st
+
+
+def landmark_args(n_perm, dim, subsample=1):
+    """The parameters of the greedy permutation as the kernel takes them (include/tdaeeg.h, "Landmark Rips"): ints, with
+    3 <= n_perm <= MAX_POINTS, 1 <= dim <= 4, subsample >= 1.  TdaError, before any GPU call, for anything else."""
+    for name, v, lo, hi in (("n_perm", n_perm, 3, _lib.MAX_POINTS), ("dim", dim, 1, 4), ("subsample", subsample, 1, None)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise _lib.TdaError(f"landmarks: {name} must be an integer in [{lo}, {'...' if hi is None else hi}], not {v!r}")
+    return int(n_perm), int(dim), int(subsample)
+
+
+def _landmark_out(n_win, n_perm, dim):
+    """Host output buffers of a landmark call; rows and entries from n_lm on keep these zeros."""
+    return (np.zeros((n_win, n_perm, dim)), np.zeros((n_win, n_perm), np.int32), np.zeros((n_win, n_perm)),
+            np.zeros(n_win), np.zeros(n_win, np.int32), np.zeros(n_win, np.int32))
+
+
+def takens_landmarks_batch(windows, taus, n_perm, dim=3, subsample=1, ctx=None):
+    """Greedy permutation (ripser's n_perm) of the normalised Takens cloud of every window: (lm (n_win, n_perm, dim),
+    lm_idx, lm_lambda, r_cover, n_lm, n_full), include/tdaeeg.h "Landmark Rips".  A refused window (tau < 1, more than
+    LM_MAX_POINTS points) has n_lm = MAX_POINTS + 1 and r_cover NaN."""
+    n_perm, dim, subsample = landmark_args(n_perm, dim, subsample)
+    ctx = ctx or get_ctx()
+    w = f64(windows)
+    n_win, n_t = w.shape
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    lm, idx, lam, rc, n_lm, n_full = _landmark_out(n_win, n_perm, dim)
+    ctx.check(ctx.lib.tda_takens_landmarks(ctx.h, ptr(w), ptr(tau), n_win, n_t, dim, subsample, n_perm, ptr(lm), ptr(idx),
+                                           ptr(lam), ptr(rc), ptr(n_lm), ptr(n_full)))
+    return lm, idx, lam, rc, n_lm, n_full
+
+
+def cloud_landmarks_batch(clouds, n_perm, n_pts=None, normalise=True, ctx=None):
+    """The same from explicit clouds (n_win, p_cap, dim) with n_pts rows each, p_cap <= LM_MAX_POINTS."""
+    ctx = ctx or get_ctx()
+    pc = f64(clouds)
+    n_win, p_cap, dim = pc.shape
+    n_perm, dim, _ = landmark_args(n_perm, dim)
+    n_pts = i32(np.full(n_win, p_cap) if n_pts is None else n_pts)
+    lm, idx, lam, rc, n_lm, n_full = _landmark_out(n_win, n_perm, dim)
+    ctx.check(ctx.lib.tda_cloud_landmarks(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)), n_perm,
+                                          ptr(lm), ptr(idx), ptr(lam), ptr(rc), ptr(n_lm), ptr(n_full)))
+    return lm, idx, lam, rc, n_lm, n_full
 
 
 def tau_batch(windows, max_lag=None, ctx=None):
@@ -700,6 +746,91 @@ def takens_rips_dev(win_t, tau_t, out=None, dim=3, subsample=2, thresh=MAX_EDGE_
                                                 out.h1_cap, _tp(out.c1), _tp(out.n_points), _tp(out.status),
                                                 _stream()))
     return out
+
+
+class DeviceLandmarks:
+    """Landmark rows, indices, insertion radii and covering radius of a batch of windows, resident in HBM (include/tdaeeg.h,
+    "Landmark Rips").  Allocated zeroed: rows and entries from n_lm on are never written."""
+
+    def __init__(self, n_win, n_perm, dim, device):
+        import torch
+        n_perm, dim, _ = landmark_args(n_perm, dim)
+        kw = dict(device=device)
+        self.lm = torch.zeros((n_win, n_perm, dim), dtype=torch.float64, **kw)
+        self.idx = torch.zeros((n_win, n_perm), dtype=torch.int32, **kw)
+        self.lam = torch.zeros((n_win, n_perm), dtype=torch.float64, **kw)
+        self.r_cover = torch.zeros(n_win, dtype=torch.float64, **kw)
+        self.n_lm = torch.zeros(n_win, dtype=torch.int32, **kw)
+        self.n_full = torch.zeros(n_win, dtype=torch.int32, **kw)
+        self.n_win, self.n_perm, self.dim = n_win, n_perm, dim
+
+    def head(self, n_win):
+        """The same buffers for the first n_win windows only (a view: nothing is copied)."""
+        v = object.__new__(DeviceLandmarks)
+        for name in ("lm", "idx", "lam", "r_cover", "n_lm", "n_full"):
+            setattr(v, name, getattr(self, name)[:n_win])
+        v.n_win, v.n_perm, v.dim = n_win, self.n_perm, self.dim
+        return v
+
+    def _args(self):
+        return (self.n_perm, _tp(self.lm), _tp(self.idx), _tp(self.lam), _tp(self.r_cover), _tp(self.n_lm), _tp(self.n_full))
+
+
+def _landmark_dev_out(lm, n_win, n_perm, dim, device):
+    lm = lm or DeviceLandmarks(n_win, n_perm, dim, device)
+    assert lm.n_win == n_win and lm.dim == dim, "landmark buffers of another shape"
+    return lm
+
+
+def takens_landmarks_dev(win_t, tau_t, lm=None, dim=3, subsample=1, n_perm=128, ctx=None):
+    """Greedy permutation of the normalised Takens cloud of every window, into lm (a DeviceLandmarks; n_perm is lm's when
+    lm is given).  Enqueue only."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    _, dim, subsample = landmark_args(lm.n_perm if lm else n_perm, dim, subsample)
+    lm = _landmark_dev_out(lm, n_win, n_perm, dim, win_t.device)
+    n_perm, *bufs = lm._args()
+    ctx.check(ctx.lib.tda_takens_landmarks_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, dim, subsample, n_perm, *bufs,
+                                               _stream()))
+    return lm
+
+
+def cloud_landmarks_dev(pc_t, n_pts_t, lm=None, normalise=True, n_perm=128, ctx=None):
+    """The same from explicit clouds pc_t (n_win, p_cap, dim) float64 with n_pts_t (n_win) int32 rows each."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert pc_t.is_cuda and pc_t.dtype == torch.float64 and pc_t.is_contiguous() and pc_t.dim() == 3
+    assert n_pts_t.dtype == torch.int32 and n_pts_t.is_cuda
+    n_win, p_cap, dim = pc_t.shape
+    landmark_args(lm.n_perm if lm else n_perm, dim)
+    lm = _landmark_dev_out(lm, n_win, n_perm, dim, pc_t.device)
+    n_perm, *bufs = lm._args()
+    ctx.check(ctx.lib.tda_cloud_landmarks_dev(ctx.h, _tp(pc_t), _tp(n_pts_t), n_win, p_cap, dim, int(bool(normalise)), n_perm,
+                                              *bufs, _stream()))
+    return lm
+
+
+def takens_rips_landmarks_dev(win_t, tau_t, out=None, lm=None, dim=3, subsample=1, n_perm=128, thresh=MAX_EDGE_LENGTH,
+                              h1_cap=DEFAULT_H1_CAP, ctx=None):
+    """takens_rips_dev for clouds of up to LM_MAX_POINTS points: the landmarks into lm, then the cloud Rips on them into
+    out (out.n_points receives n_lm).  Returns (out, lm)."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    _, dim, subsample = landmark_args(lm.n_perm if lm else n_perm, dim, subsample)
+    lm = _landmark_dev_out(lm, n_win, n_perm, dim, win_t.device)
+    out = out or DeviceDiagrams(n_win, _lib.MAX_POINTS, h1_cap, win_t.device)
+    assert out.n_win == n_win
+    n_perm, *bufs = lm._args()
+    ctx.check(ctx.lib.tda_takens_rips_landmarks_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, dim, subsample, n_perm,
+                                                    float(thresh), *bufs, _tp(out.h0), out.h0_cap, _tp(out.c0), _tp(out.h1),
+                                                    out.h1_cap, _tp(out.c1), _tp(out.n_points), _tp(out.status), _stream()))
+    return out, lm
 
 
 def tau_dev(win_t, max_lag=None, tau_t=None, ctx=None):

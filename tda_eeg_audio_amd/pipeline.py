@@ -124,18 +124,29 @@ class Workspace:
     fm = fm_sets = frechet = fm_out = None
     kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
     pf = fisher = f0 = f1 = fs0 = fs1 = None
+    lm = takens = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None):
+                 fisher=None, takens=None):
         """correlations .. fisher: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
         `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2), `pf` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` / `pf` the distances of every
         window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1`, `k0` / `k1` and `f0` / `f1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`,
         `qs0` / `qs1`, `ks0` / `ks1` and `fs0` / `fs1`.
-        Grid, edges and directions are uploaded once, here."""
+        Grid, edges and directions are uploaded once, here.
+        takens=None: the audio stage as the reference runs it (dim 3, subsample 2, every point; at most 128 points).
+        takens=(dim, subsample, n_perm): the audio stage embeds with these and runs Rips on n_perm greedy landmarks
+        (engine.takens_rips_landmarks_dev), for clouds of up to LM_MAX_POINTS points; `lm` (an engine.DeviceLandmarks,
+        allocated here) then holds the landmarks of every window, lm.r_cover their covering radius and lm.n_full the size
+        of the whole cloud.  No column of `result` changes meaning.  TdaError for parameters outside their limits."""
         import torch
         self.n_win, self.device = n_win, device
+        if takens is not None:
+            dim, subsample, n_perm = takens
+            n_perm, dim, subsample = engine.landmark_args(n_perm, dim, subsample)
+            self.takens = (dim, subsample, n_perm)
+            self.lm = engine.DeviceLandmarks(n_win, n_perm, dim, device)
         seg_off = np.asarray(seg_off, np.int32)
         assert seg_off[0] == 0 and seg_off[-1] == n_win
         self.n_seg = len(seg_off) - 1
@@ -225,6 +236,7 @@ class Workspace:
         v.first_idx = torch.from_numpy(seg_off[:-1].astype(np.int64)).to(self.device)
         v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
         v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
+        v.lm = None if self.lm is None else self.lm.head(n_win)
         for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist") + self.PAIR_BUFFERS:
             buf = getattr(self, name)
             setattr(v, name, None if buf is None else buf[:n_win])
@@ -300,7 +312,12 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
             stage("rips_eeg", lambda: engine.rips_dm_dev(ws.dist, ws.eeg, ctx=ctx))
     # tau from the first selected window of each recording-band (cmp:83), written per group and per window
     stage("tau", lambda: engine.tau_segments_dev(audio_win, ws.seg_off, max_lag, ws.tau_seg, ws.tau_win, ctx=ctx))
-    stage("rips_audio", lambda: engine.takens_rips_dev(audio_win, ws.tau_win, ws.aud, ctx=ctx))
+    if ws.takens is None:
+        stage("rips_audio", lambda: engine.takens_rips_dev(audio_win, ws.tau_win, ws.aud, ctx=ctx))
+    else:
+        dim, subsample, _ = ws.takens
+        stage("rips_audio", lambda: engine.takens_rips_landmarks_dev(audio_win, ws.tau_win, ws.aud, ws.lm, dim=dim,
+                                                                     subsample=subsample, ctx=ctx))
     if ws.overlap:
         main.wait_stream(side)
     # H1 rows of both Rips stages into ripser's order + extract_features of EEG H0 / EEG H1 / audio H1

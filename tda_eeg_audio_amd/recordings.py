@@ -63,8 +63,10 @@ class _ShardedPass:
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
     def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None, images=None, sliced=None,
-                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None):
+                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None, takens=None):
         self.ctx = ctx or get_ctx()
+        # takens=(dim, subsample, n_perm): the audio stage of every Workspace runs on greedy landmarks (pipeline.Workspace)
+        self.takens = None if takens is None else tuple(int(v) for v in takens)
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
         # the optional outputs (pipeline.step_outputs: self.outputs is the table, validated here); host buffer of `name`:
@@ -184,13 +186,15 @@ class RecordingPass(_ShardedPass):
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
                  max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None):
+                 fisher=None, takens=None):
         """correlations .. fisher: the optional outputs (pipeline.step_outputs); `run` also fills self.<name>_h of each
-        (_ShardedPass.run).  corr_h is in the order of drivers.DETAILED_COLUMNS[8:].  The rows are the same either way."""
+        (_ShardedPass.run).  corr_h is in the order of drivers.DETAILED_COLUMNS[8:].  The rows are the same either way.
+        takens=(dim, subsample, n_perm): handed to every pipeline.Workspace -- the audio diagrams come from n_perm greedy
+        landmarks of the (dim, subsample) Takens cloud; the columns of the rows keep their meaning."""
         import os
         import torch
         super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet,
-                         kernel_distance, fisher)
+                         kernel_distance, fisher, takens)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -213,7 +217,7 @@ class RecordingPass(_ShardedPass):
             ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
                                   bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images,
                                   sliced=self.sliced, wasserstein_q=self.wasserstein_q, frechet=self.frechet,
-                                  kernel_distance=self.kernel_distance, fisher=self.fisher),
+                                  kernel_distance=self.kernel_distance, fisher=self.fisher, takens=self.takens),
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -352,13 +356,13 @@ class RaggedRecordingPass(_ShardedPass):
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
                  plan=None, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None, fisher=None):
+                 frechet=None, kernel_distance=None, fisher=None, takens=None):
         """correlations .. fisher: the optional outputs, as RecordingPass takes them; NaN for a recording without a
-        window."""
+        window.  takens=(dim, subsample, n_perm): as RecordingPass takes it."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
                          correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
-                         fisher)
+                         fisher, takens)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -397,7 +401,7 @@ class RaggedRecordingPass(_ShardedPass):
                                     n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
                                     landscapes=self.landscapes, images=self.images, sliced=self.sliced,
                                     wasserstein_q=self.wasserstein_q, frechet=self.frechet,
-                                    kernel_distance=self.kernel_distance, fisher=self.fisher)
+                                    kernel_distance=self.kernel_distance, fisher=self.fisher, takens=self.takens)
             return dict(
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
@@ -480,7 +484,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
                  overlap=0.75, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None,
-                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None):
+                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None, takens=None):
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -492,7 +496,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
                          max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
                          bottleneck=bottleneck, landscapes=landscapes, images=images, sliced=sliced,
                          wasserstein_q=wasserstein_q, frechet=frechet, kernel_distance=kernel_distance,
-                         fisher=fisher)
+                         fisher=fisher, takens=takens)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)
@@ -635,7 +639,9 @@ class ControlPass(RaggedRecordingPass):
     engine.wasserstein_cross_dev launches that resolve their pairs on the device from the plan's tables (own audio,
     then the bank) and engine.cross_rows_dev.  No index array is built per shard and nothing synchronises with the host
     between the Rips stages and the rows.
-    The 250 Hz envelopes are the upload (the _front_end hook is RaggedRecordingPass's)."""
+    The 250 Hz envelopes are the upload (the _front_end hook is RaggedRecordingPass's).
+    The pass keeps an audio bank of its own, embedded as the reference embeds it (dim 3, subsample 2, every point): the
+    landmark route (takens=, RecordingPass) is not offered here."""
 
     ROW_COLS = CONTROL_COLS
     ROW_ZERO = slice(2, None)           # the pair counts
@@ -832,7 +838,8 @@ class MatchMismatchPass(ControlPass):
     engine.match_rows_dev launch its rows.  `run` then also fills slc_dist_h (n_rec, n_bands, n_col) float64, slc_pairs_h
     (the same shape, int32) and slc_rows_h (n_rec, n_bands, 6), pinned, with the meaning of dist_h / pairs_h / rows_h.  A
     status bit of a sliced entry withholds the rows as one of a Wasserstein entry does.  Off by default: rows_h, dist_h and
-    pairs_h are the same bytes with and without it."""
+    pairs_h are the same bytes with and without it.
+    As ControlPass, the pass embeds its audio bank as the reference does; the landmark route (takens=) is not offered."""
 
     ROW_COLS = MATCH_COLS
     ROW_ZERO = slice(1, 5)              # the counts

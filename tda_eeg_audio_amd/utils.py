@@ -15,7 +15,7 @@ permute_labels_by_subject (utils.py:198-215, statistics).
 import numpy as np
 
 from . import engine
-from ._lib import TdaError
+from ._lib import LM_MAX_POINTS, TdaError
 
 # ── TDA parameters ── (scripts/utils.py:24-27)
 MAX_DIM = 1
@@ -76,12 +76,48 @@ def _check_dim(max_dim):
         raise NotImplementedError("the HIP engine computes H0 and H1 (maxdim=1), as the reference does")
 
 
-def compute_audio_persistence(point_cloud, max_dim=MAX_DIM, max_edge_length=MAX_EDGE_LENGTH):
-    """scripts/utils.py:123-132 -- [H0, H1] of a point cloud (min-max normalised, Rips)."""
+_NO_BATCH_N_PERM = ("n_perm is not recorded by utils.batch (its add_cloud normalises, and the landmark route must not "
+                    "normalise twice): call engine.cloud_landmarks_batch / engine.takens_rips_landmarks_dev directly")
+
+
+def greedy_landmarks(point_cloud, n_perm, normalise=True):
+    """ripser's greedy permutation (n_perm) of one (P, dim) cloud of up to 1024 rows: (idx_perm, lambdas, r_cover), the
+    furthest-point order from point 0, the insertion radii and the covering radius (include/tdaeeg.h, "Landmark Rips").
+    P <= n_perm: every point, in its own order, with radii 0."""
+    if _ACTIVE is not None:
+        raise NotImplementedError(_NO_BATCH_N_PERM)
+    pc = np.asarray(point_cloud, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[0] < 1:
+        raise ValueError("greedy_landmarks: a (P, dim) cloud with P >= 1")
+    if pc.shape[0] > LM_MAX_POINTS:
+        raise TdaError(f"more than {LM_MAX_POINTS} points: not supported by the landmark kernel")
+    _, idx, lam, rc, n_lm, _ = engine.cloud_landmarks_batch(pc[None], n_perm, normalise=normalise)
+    k = int(n_lm[0])
+    return idx[0, :k].copy(), lam[0, :k].copy(), float(rc[0])
+
+
+def _landmark_persistence(point_cloud, max_edge_length, n_perm):
+    if point_cloud.shape[0] > LM_MAX_POINTS:
+        raise TdaError(f"more than {LM_MAX_POINTS} points: not supported by the landmark kernel")
+    lm, _, _, _, n_lm, _ = engine.cloud_landmarks_batch(point_cloud[None], n_perm)
+    # the landmark rows are normalised already: the cloud path takes them as they are
+    h0, h1, st = engine.cloud_rips_batch(lm, n_pts=n_lm, normalise=False, thresh=max_edge_length, h1_cap=_h1_cap(int(n_lm[0])))
+    _check_status(st[0])
+    return [h0[0], h1[0]]
+
+
+def compute_audio_persistence(point_cloud, max_dim=MAX_DIM, max_edge_length=MAX_EDGE_LENGTH, n_perm=None):
+    """scripts/utils.py:123-132 -- [H0, H1] of a point cloud (min-max normalised, Rips).  n_perm (ripser's keyword): Rips
+    on n_perm greedy landmarks, for clouds of up to 1024 rows; each diagram then lies within bottleneck distance
+    2 * r_cover (greedy_landmarks) of the whole cloud's."""
     _check_dim(max_dim)
     point_cloud = np.asarray(point_cloud, dtype=np.float64)
+    if n_perm is not None and _ACTIVE is not None:
+        raise NotImplementedError(_NO_BATCH_N_PERM)
     if len(point_cloud) < 3:
         return [np.array([[0, 0]]), np.array([[0, 0]])]
+    if n_perm is not None:
+        return _landmark_persistence(point_cloud, max_edge_length, n_perm)
     if _ACTIVE is not None:
         return _ACTIVE.add_cloud(point_cloud, max_edge_length)
     h0, h1, st = engine.cloud_rips_batch(point_cloud[None], thresh=max_edge_length, h1_cap=_h1_cap(len(point_cloud)))
