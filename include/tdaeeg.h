@@ -52,6 +52,7 @@ typedef enum {
 #define TDA_WIN_TOO_LARGE     16  /* more than TDA_MAX_POINTS points (tau < 1?): no diagram    */
 #define TDA_WIN_NO_PAIR       32  /* tda_wasserstein_cross_dev: this diagram has no partner at
                                      its position (mvm:89); the distance is NaN and is no member of the group's mean */
+#define TDA_WIN_NOT_FINITE    64  /* tda_sublevel_batch: the signal has a sample that is not finite; count 0, no rows */
 
 #define TDA_N_FEATURES 11         /* scripts/utils.py:166-177 key order */
 #define TDA_MAX_POINTS 128        /* vertices per Rips complex (reference needs <= 124)        */
@@ -863,6 +864,43 @@ tda_status tda_takens_rips_landmarks(tda_ctx* ctx, const double* win, const int*
                                      double* lm_lambda, double* r_cover, int* n_lm, int* n_full,
                                      double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt,
                                      int* n_points, int* status);
+
+/* ---- Sublevel-set persistence of time series: H0 of the lower-star filtration of a 1-D signal ----------------
+ * What ripser's lower_star example, a cubical complex on a 1-D array and persistence-based peak detection compute: every
+ * local minimum paired with the local maximum at which its basin merges into a deeper one.  Superlevel sets: pass -x.
+ * None of those libraries is installed where this project runs, so no parity with them is claimed.  The contract is this
+ * text; tests/sublevel_ref.py evaluates it.
+ *   Signal.     x[0 .. n_t - 1], float64, all finite.  Vertices are totally ordered by (x[i], i).  Vertex i enters the
+ *               filtration at x[i], edge (i, i + 1) at the later of its ends.
+ *   Rows.       The vertices are processed in that order with union-find.  When two components meet at vertex v, the one
+ *               whose minimum is larger in the total order dies (elder rule): the row (birth, death) =
+ *               (x[min of the dying component], x[v]) with indices (argmin, v).  Rows with birth == death are dropped.  The
+ *               component of the global minimum g gives the last row, (x[g], +inf), indices (g, -1).
+ *   Order.      The finite rows ascend in (death, birth, death index): ripser's H0 order.  At most
+ *               TDA_SL_ROWS(n_t) = (n_t + 1) / 2 rows.  Births and deaths are input values, copied bit for bit.
+ *   Equivalent form, the one the kernel evaluates (no sequential sweep; tests/test_sublevel_model.py holds the two
+ *               together).  Each interior vertex p above both neighbours in the total order gives one row.  ml is the
+ *               minimum, in the total order, of the maximal run of vertices left of p that are below p, mr the same to the
+ *               right, y the larger of ml and mr: the row is (x[y], x[p], y, p).  Every maximum is independent of the others.
+ *   Addressing. Signal s = w * n_ch + c starts at element win_start[w] + c * win_ld[w] of sig, the tables of
+ *               tda_eeg_window_ragged_dev (device int64, n_win entries each).  Both NULL: the windows are stacked,
+ *               (n_win, n_ch, n_t).  One of them NULL is TDA_ERR_INVALID.
+ *   Outputs.    dgm (n_win * n_ch, cap, 2) float64;  cnt and status (n_win * n_ch) int32;  idx nullable,
+ *               (n_win * n_ch, cap, 2) int32.  Only rows [0, cnt) of a signal's own block are written.
+ *   Status.     A signal with a sample that is not finite has cnt = 0 and TDA_WIN_NOT_FINITE, and no row of it is written;
+ *               the other signals of the batch are unaffected.  Every other signal has status 0.
+ *   Limits.     1 <= n_t <= TDA_SL_MAX_SAMPLES, n_ch >= 1, cap >= TDA_SL_ROWS(n_t); anything else is TDA_ERR_INVALID and
+ *               nothing is launched.
+ *   Determinism.  No atomics; a signal alone and inside a batch give the same bytes.
+ * The _dev form only enqueues on `stream` and allocates nothing.  The host form stages the output buffers in both
+ * directions, so "only rows [0, cnt)" holds for it too; its tables are host arrays. */
+#define TDA_SL_MAX_SAMPLES 4096
+#define TDA_SL_ROWS(n) (((n) + 1) / 2)
+tda_status tda_sublevel_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                  int n_win, int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status,
+                                  void* stream);
+tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                              int n_win, int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status);
 
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:

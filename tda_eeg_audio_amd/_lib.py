@@ -25,6 +25,7 @@ TDA_WIN_DEGENERATE = 4
 TDA_WIN_NOT_CONVERGED = 8
 TDA_WIN_TOO_LARGE = 16
 TDA_WIN_NO_PAIR = 32          # tda_wasserstein_cross_dev: no partner at this position (mvm:89)
+TDA_WIN_NOT_FINITE = 64       # tda_sublevel_batch: a sample of the signal is not finite
 N_FEATURES = 11
 MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
 MAX_GRID = 256              # TDA_MAX_GRID
@@ -42,6 +43,7 @@ TDA_KW_ATAN = 2             # ... atan(wc * (d - b))
 PF_MAX_POINTS = 512         # TDA_PF_MAX_POINTS
 LM_MAX_POINTS = 1024        # TDA_LM_MAX_POINTS: largest cloud the greedy permutation (n_perm) takes
 LM_MAX_SAMPLES = 4096       # TDA_LM_MAX_SAMPLES
+SL_MAX_SAMPLES = 4096       # TDA_SL_MAX_SAMPLES: longest signal of the sublevel-set persistence
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -152,6 +154,8 @@ SYMBOLS = {
                                            c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_takens_rips_landmarks": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _I, _D, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_sublevel_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_sublevel_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

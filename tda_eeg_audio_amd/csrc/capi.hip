@@ -671,6 +671,15 @@ tda_status tda_persistence_fisher_batch_dev(tda_ctx* ctx, const double* dgm_a, c
                                      status, (hipStream_t)stream);
 }
 
+tda_status tda_sublevel_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                  int n_win, int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status,
+                                  void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, sig); CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, status); }
+    return launch_sublevel(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, dgm, cap, cnt, idx, status, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.
@@ -1299,6 +1308,44 @@ tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const
     RET_IF(s.upload());
     RET_IF(tda_persistence_fisher_batch_dev(ctx, d_a, d_ca, n_a, cap_a, d_b, d_cb, n_b, cap_b, d_ia, d_ib, n_pairs, ninv, d_out,
                                             d_st, nullptr));
+    return s.download();
+}
+
+// (the outputs are staged in both directions: the kernel writes only rows [0, cnt) of a signal's block)
+tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                              int n_win, int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_t < 1 || n_t > TDA_SL_MAX_SAMPLES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be in [1, TDA_SL_MAX_SAMPLES]");
+    if (n_ch < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_ch must be >= 1");
+    if (cap < TDA_SL_ROWS(n_t)) TDA_FAIL(ctx, TDA_ERR_INVALID, "cap must be >= TDA_SL_ROWS(n_t)");
+    if ((win_start == nullptr) != (win_ld == nullptr)) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_start and win_ld go together");
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, sig); CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, status);
+    // the elements of sig the tables reach
+    long long n_el = (long long)n_win * n_ch * n_t;
+    if (win_start) {
+        n_el = 0;
+        for (int w = 0; w < n_win; ++w) {
+            if (win_start[w] < 0 || win_ld[w] < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative window table entry");
+            const long long end = win_start[w] + (long long)(n_ch - 1) * win_ld[w] + n_t;
+            n_el = end > n_el ? end : n_el;
+        }
+    }
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    const size_t n_sig = (size_t)n_win * n_ch;
+    double *d_sig, *d_dgm;
+    long long *d_ws = nullptr, *d_wl = nullptr;
+    int *d_cnt, *d_idx = nullptr, *d_st;
+    s.add((void**)&d_sig, sig, nullptr, (size_t)n_el * 8);
+    if (win_start) { s.add((void**)&d_ws, win_start, nullptr, (size_t)n_win * 8); s.add((void**)&d_wl, win_ld, nullptr, (size_t)n_win * 8); }
+    s.add((void**)&d_dgm, dgm, dgm, n_sig * cap * 16);
+    if (idx) s.add((void**)&d_idx, idx, idx, n_sig * cap * 8);
+    s.add((void**)&d_cnt, nullptr, cnt, n_sig * 4);
+    s.add((void**)&d_st, nullptr, status, n_sig * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_sublevel_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_dgm, cap, d_cnt, d_idx, d_st, nullptr));
     return s.download();
 }
 

@@ -204,6 +204,9 @@ tda_status launch_rips_cloud(tda_ctx*, const double* win_or_pc, const int* tau_o
 tda_status launch_landmarks(tda_ctx*, const double* win_or_pc, const int* tau_or_npts, int n_win, int n_t_or_pcap, int dim,
                             int subsample, int mode, int normalise, int n_perm, double* lm, int* lm_idx, double* lm_lambda,
                             double* r_cover, int* n_lm, int* n_full, hipStream_t);
+// (sublevel.hip) H0 of the sublevel-set filtration of n_win * n_ch signals.  Checks the limits of the header itself.
+tda_status launch_sublevel(tda_ctx*, const double* sig, const long long* win_start, const long long* win_ld, int n_win,
+                           int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,
                               hipStream_t, int n_filt = 1);
 tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, const double*, const double*, int, int, double*,

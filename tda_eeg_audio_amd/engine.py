@@ -9,6 +9,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  sliced_wasserstein_batch, sliced_wasserstein_gram,
                  landscape_batch, image_batch, frechet_mean_batch, temporal_corr_batch,
                  takens_landmarks_batch, cloud_landmarks_batch (greedy permutation, ripser's n_perm)
+                 sublevel_batch (H0 of the sublevel-set filtration of 1-D signals)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -19,6 +20,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  the sliced Wasserstein distance with every diagram sorted once (MatchMismatchPass(sliced=dirs)).
                  takens_landmarks_dev / cloud_landmarks_dev / takens_rips_landmarks_dev: Rips on greedy landmarks for clouds
                  above 128 points (Workspace(takens=(dim, subsample, n_perm))).
+                 sublevel_dev / sublevel_features_dev: sublevel-set diagrams of signals read stacked or in place, and
+                 their 11 features through a bounded scratch (Workspace(sublevel=True)).
 """
 import ctypes as C
 
@@ -176,6 +179,45 @@ def cloud_landmarks_batch(clouds, n_perm, n_pts=None, normalise=True, ctx=None):
     ctx.check(ctx.lib.tda_cloud_landmarks(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)), n_perm,
                                           ptr(lm), ptr(idx), ptr(lam), ptr(rc), ptr(n_lm), ptr(n_full)))
     return lm, idx, lam, rc, n_lm, n_full
+
+
+def sublevel_rows(n_t):
+    """TDA_SL_ROWS(n_t): the most rows the sublevel-set diagram of n_t samples can have, the essential one included."""
+    return (int(n_t) + 1) // 2
+
+
+def sublevel_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, cap=None, dgm=None, idx=None, ctx=None):
+    """H0 of the sublevel-set filtration of 1-D signals (include/tdaeeg.h, "Sublevel-set persistence of time series"):
+    (dgm (n_sig, cap, 2), cnt (n_sig), idx (n_sig, cap, 2) int32, status (n_sig)).  sig (n_sig, n_t), or (n_win, n_ch, n_t)
+    with signal w * n_ch + c; or, with the int64 tables win_start / win_ld (n_win each) and n_ch, n_t, a flat array whose
+    signal w * n_ch + c starts at element win_start[w] + c * win_ld[w].  Only rows [0, cnt) are written: the rest of dgm /
+    idx keeps what the caller's buffers hold (NaN / -1 in the ones made here).  A signal with a sample that is not finite has
+    cnt 0 and status TDA_WIN_NOT_FINITE.  TdaError for n_t outside [1, SL_MAX_SAMPLES], n_ch < 1 or cap < sublevel_rows(n_t)."""
+    ctx = ctx or get_ctx()
+    s = f64(sig)
+    if win_start is None and win_ld is None:
+        if s.ndim == 2:
+            s = s[:, None, :]
+        n_win, n_ch, n_t = s.shape
+        ws = wl = None
+    else:
+        ws, wl = (np.ascontiguousarray(t, dtype=np.int64) for t in (win_start, win_ld))
+        assert ws.shape == wl.shape and ws.ndim == 1 and n_ch is not None and n_t is not None
+        n_win, n_ch, n_t = ws.shape[0], int(n_ch), int(n_t)
+        if n_win and n_ch >= 1 and n_t >= 1:
+            assert ws.min() >= 0 and wl.min() >= 0 and int((ws + (n_ch - 1) * wl).max()) + n_t <= s.size, "table past the end of sig"
+    cap = sublevel_rows(n_t) if cap is None else int(cap)
+    n_sig = n_win * max(n_ch, 0)
+    rows = max(cap, 0)
+    dgm = np.full((n_sig, rows, 2), np.nan) if dgm is None else dgm
+    idx = np.full((n_sig, rows, 2), -1, np.int32) if idx is None else idx
+    assert dgm.dtype == np.float64 and dgm.flags.c_contiguous and dgm.shape == (n_sig, rows, 2)
+    assert idx.dtype == np.int32 and idx.flags.c_contiguous and idx.shape == (n_sig, rows, 2)
+    cnt = np.zeros(n_sig, np.int32)
+    status = np.zeros(n_sig, np.int32)
+    ctx.check(ctx.lib.tda_sublevel_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(dgm), cap, ptr(cnt), ptr(idx),
+                                         ptr(status)))
+    return dgm, cnt, idx, status
 
 
 def tau_batch(windows, max_lag=None, ctx=None):
@@ -831,6 +873,104 @@ def takens_rips_landmarks_dev(win_t, tau_t, out=None, lm=None, dim=3, subsample=
                                                     float(thresh), *bufs, _tp(out.h0), out.h0_cap, _tp(out.c0), _tp(out.h1),
                                                     out.h1_cap, _tp(out.c1), _tp(out.n_points), _tp(out.status), _stream()))
     return out, lm
+
+
+def _sublevel_shape(sig_t, n_t, win_start_t, win_ld_t, n_ch):
+    """(n_win, n_ch, n_t) of a sublevel call on device tensors: stacked (n_sig, n_t) / (n_win, n_ch, n_t), or tables."""
+    import torch
+    assert sig_t.is_cuda and sig_t.dtype == torch.float64 and sig_t.is_contiguous()
+    if win_start_t is None and win_ld_t is None:
+        assert sig_t.dim() in (2, 3)
+        return (sig_t.shape[0], 1, sig_t.shape[1]) if sig_t.dim() == 2 else tuple(sig_t.shape)
+    assert win_start_t.dtype == torch.int64 and win_ld_t.dtype == torch.int64 and win_start_t.numel() == win_ld_t.numel()
+    assert win_start_t.is_contiguous() and win_ld_t.is_contiguous() and n_ch is not None and n_t is not None
+    return int(win_start_t.numel()), int(n_ch), int(n_t)
+
+
+def sublevel_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, cap=None, dgm_t=None, cnt_t=None, idx_t=None,
+                 status_t=None, want_index=False, ctx=None):
+    """sublevel_batch on device tensors: one launch on torch's current stream, nothing allocated when dgm_t, cnt_t and
+    status_t (and idx_t, if indices are wanted) are given.  win_start_t / win_ld_t: optional int64 device tables, the ones of
+    eeg_window_ragged_dev.  Returns (dgm_t, cnt_t, idx_t or None, status_t); buffers made here are NaN / -1 outside rows
+    [0, cnt)."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_win, n_ch, n_t = _sublevel_shape(sig_t, n_t, win_start_t, win_ld_t, n_ch)
+    n_sig = n_win * max(n_ch, 0)
+    if cap is None:
+        cap = dgm_t.shape[1] if dgm_t is not None else sublevel_rows(n_t)
+    dev = sig_t.device
+    if dgm_t is None:
+        dgm_t = torch.full((n_sig, max(cap, 0), 2), float("nan"), dtype=torch.float64, device=dev)
+    if idx_t is None and want_index:
+        idx_t = torch.full((n_sig, max(cap, 0), 2), -1, dtype=torch.int32, device=dev)
+    cnt_t = torch.zeros(n_sig, dtype=torch.int32, device=dev) if cnt_t is None else cnt_t
+    status_t = torch.zeros(n_sig, dtype=torch.int32, device=dev) if status_t is None else status_t
+    assert dgm_t.is_contiguous() and dgm_t.dtype == torch.float64 and dgm_t.numel() >= n_sig * max(cap, 0) * 2
+    assert idx_t is None or (idx_t.is_contiguous() and idx_t.dtype == torch.int32 and idx_t.numel() >= n_sig * max(cap, 0) * 2)
+    assert cnt_t.numel() >= n_sig and status_t.numel() >= n_sig and cnt_t.dtype == status_t.dtype == torch.int32
+    ctx.check(ctx.lib.tda_sublevel_batch_dev(ctx.h, _tp(sig_t), _tp(win_start_t), _tp(win_ld_t), n_win, n_ch, n_t, _tp(dgm_t),
+                                             int(cap), _tp(cnt_t), _tp(idx_t), _tp(status_t), _stream()))
+    return dgm_t, cnt_t, idx_t, status_t
+
+
+SL_SCRATCH_BYTES = 128 << 20      # sublevel_features_dev: bound of the diagram rows of one chunk (DESIGN.md 3.18)
+
+
+class SublevelScratch:
+    """The bounded scratch of sublevel_features_dev: the diagram rows and counts of ONE chunk of windows.  The diagrams of
+    47 channels come to 95 KB per window of 250 samples, 10 GB for 106,200 windows, so the features are taken chunk by
+    chunk: chunk_windows = the windows whose rows fit into max_bytes (at least one), fixed here, and with it the number of
+    launches for any given number of windows -- a captured graph of the calls holds."""
+
+    def __init__(self, n_ch, n_t, device, max_bytes=SL_SCRATCH_BYTES, n_win=None):
+        import torch
+        self.n_ch, self.n_t, self.cap = int(n_ch), int(n_t), sublevel_rows(n_t)
+        per_win = self.n_ch * self.cap * 16
+        self.chunk_windows = max(1, int(max_bytes) // per_win)
+        if n_win is not None:                        # never more than the caller's batch
+            self.chunk_windows = max(1, min(self.chunk_windows, int(n_win)))
+        n = self.chunk_windows * self.n_ch
+        self.dgm = torch.empty((n, self.cap, 2), dtype=torch.float64, device=device)
+        self.cnt = torch.empty(n, dtype=torch.int32, device=device)
+
+    def n_chunks(self, n_win):
+        return -(-int(n_win) // self.chunk_windows)
+
+
+def sublevel_features_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, out_t=None, status_t=None, scratch=None,
+                          max_bytes=SL_SCRATCH_BYTES, ctx=None):
+    """The 11 extract_features values of the sublevel-set diagram of every signal, (n_win, n_ch, 11) float64: per chunk of
+    scratch.chunk_windows windows one sublevel launch into the scratch and one tda_features_batch_dev launch on it, on
+    torch's current stream; the rows never exist for more than a chunk.  A signal with a sample that is not finite is NaN
+    (status_t, (n_win, n_ch) int32, holds its TDA_WIN_NOT_FINITE).  Arguments as sublevel_dev; scratch: a SublevelScratch
+    of this (n_ch, n_t), made here from max_bytes when None.  Nothing is allocated when out_t, status_t and scratch are
+    given, but the NaN mask."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_win, n_ch, n_t = _sublevel_shape(sig_t, n_t, win_start_t, win_ld_t, n_ch)
+    dev = sig_t.device
+    scratch = scratch or SublevelScratch(n_ch, n_t, dev, max_bytes, n_win=n_win)
+    assert (scratch.n_ch, scratch.n_t) == (n_ch, n_t), "scratch of another signal shape"
+    if out_t is None:
+        out_t = torch.empty((n_win, n_ch, _lib.N_FEATURES), dtype=torch.float64, device=dev)
+    if status_t is None:
+        status_t = torch.empty((n_win, n_ch), dtype=torch.int32, device=dev)
+    assert out_t.is_contiguous() and out_t.shape == (n_win, n_ch, _lib.N_FEATURES) and out_t.dtype == torch.float64
+    assert status_t.is_contiguous() and status_t.shape == (n_win, n_ch) and status_t.dtype == torch.int32
+    cw = scratch.chunk_windows
+    stacked = sig_t.view(n_win, n_ch, n_t) if win_start_t is None else None
+    for w0 in range(0, n_win, cw):
+        w1 = min(w0 + cw, n_win)
+        if stacked is not None:
+            sublevel_dev(stacked[w0:w1], dgm_t=scratch.dgm, cnt_t=scratch.cnt, status_t=status_t[w0:w1], ctx=ctx)
+        else:
+            sublevel_dev(sig_t, n_t, win_start_t[w0:w1], win_ld_t[w0:w1], n_ch, dgm_t=scratch.dgm, cnt_t=scratch.cnt,
+                         status_t=status_t[w0:w1], ctx=ctx)
+        n = (w1 - w0) * n_ch
+        features_dev(scratch.dgm[:n], scratch.cnt[:n], out_t[w0:w1], ctx=ctx)
+    out_t.masked_fill_((status_t != 0).unsqueeze(-1), float("nan"))
+    return out_t
 
 
 def tau_dev(win_t, max_lag=None, tau_t=None, ctx=None):

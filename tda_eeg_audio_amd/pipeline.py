@@ -28,14 +28,15 @@ IMG_SETS = 3              # Workspace(images=...).img: the same three diagram se
 FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram sets, in the same order
 KD_COLS = 2               # Workspace(kernel_distance=kernel).kd: [k_h0, k_h1], the means of the kernel-induced distances
 PF_COLS = 2               # Workspace(fisher=sigma).pf: [f_h0, f_h1], the means of the persistence Fisher distances
+SL_COLS = 22              # Workspace(sublevel=True).sl: the 11 features of the audio window's sublevel-set diagram, then of the EEG channels'
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
 def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None, fisher=None):
+                 frechet=None, kernel_distance=None, fisher=None, sublevel=False):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf, sl.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -61,7 +62,13 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
             distance that kernel on diagrams induces between the H0 / H1 pairs (engine.diagram_kernel_dev) under the rule of
             `bott`.  ValueError for anything else
       pf    fisher=sigma, a finite number > 0 (engine.fisher_args): (PF_COLS,) np.nanmean of the persistence Fisher distances
-            of the H0 / H1 pairs (engine.persistence_fisher_dev) under the rule of `bott`.  ValueError for anything else"""
+            of the H0 / H1 pairs (engine.persistence_fisher_dev) under the rule of `bott`.  ValueError for anything else
+      sl    sublevel=True: (SL_COLS,) from the sublevel-set (lower-star) H0 diagrams of the signals themselves
+            (engine.sublevel_features_dev; include/tdaeeg.h).  Columns 0..10: np.nanmean over the group's windows of the 11
+            extract_features values of the audio window's diagram.  Columns 11..21: np.nanmean over the windows of the
+            np.mean over the channels of the same 11 values of the EEG channels' diagrams, one diagram per channel.  A
+            signal with a sample that is not finite counts as NaN.  Every window of the group takes part: no Rips status
+            is looked at"""
     from . import _lib
     out = []
     if correlations:
@@ -108,6 +115,8 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
         except _lib.TdaError:
             raise ValueError("fisher=sigma: a finite number > 0") from None
         out.append(Output("pf", (PF_COLS,), float(fisher)))
+    if sublevel:
+        out.append(Output("sl", (SL_COLS,), None))
     return out
 
 
@@ -124,17 +133,22 @@ class Workspace:
     fm = fm_sets = frechet = fm_out = None
     kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
     pf = fisher = f0 = f1 = fs0 = fs1 = None
+    sl = sl_fa = sl_fe = sl_sa = sl_se = sl_cols = sl_scratch = None; sublevel = False
     lm = takens = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None, takens=None):
-        """correlations .. fisher: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 fisher=None, takens=None, sublevel=False, sublevel_bytes=engine.SL_SCRATCH_BYTES):
+        """correlations .. fisher, sublevel: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
         `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2), `pf` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` / `pf` the distances of every
         window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1`, `k0` / `k1` and `f0` / `f1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`,
         `qs0` / `qs1`, `ks0` / `ks1` and `fs0` / `fs1`.
         Grid, edges and directions are uploaded once, here.
+        sublevel=True: `sl` (n_seg, 22), and per window the features it averages, `sl_fa` (n_win, 11) of the audio window and
+        `sl_fe` (n_win, n_ch, 11) of the EEG channels (NaN where `sl_sa` / `sl_se` flag the signal).  The diagrams themselves
+        exist only chunk by chunk, in scratch of at most sublevel_bytes of rows per signal kind (engine.SublevelScratch,
+        made at the first step, when the window length is known).
         takens=None: the audio stage as the reference runs it (dim 3, subsample 2, every point; at most 128 points).
         takens=(dim, subsample, n_perm): the audio stage embeds with these and runs Rips on n_perm greedy landmarks
         (engine.takens_rips_landmarks_dev), for clouds of up to LM_MAX_POINTS points; `lm` (an engine.DeviceLandmarks,
@@ -168,11 +182,12 @@ class Workspace:
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
         self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
-                                    fisher)
+                                    fisher, sublevel)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
         self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
         self.fisher = par.get("pf")
+        self.sublevel, self.sublevel_bytes, self.n_ch = "sl" in par, int(sublevel_bytes), n_ch
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
@@ -197,6 +212,12 @@ class Workspace:
             self.k0, self.k1, self.ks0, self.ks1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
         if self.fisher is not None:
             self.f0, self.f1, self.fs0, self.fs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
+        if self.sublevel:
+            i32 = dict(dtype=torch.int32, device=device)
+            self.sl_fa, self.sl_fe = torch.empty((n_win, 1, 11), **f64), torch.empty((n_win, n_ch, 11), **f64)
+            self.sl_sa, self.sl_se = torch.empty((n_win, 1), **i32), torch.empty((n_win, n_ch), **i32)
+            self.sl_cols = torch.empty(SL_COLS * n_win, **f64)       # the 22 per-window series, one contiguous row each
+            self.sl_scratch, self.sl_n_win = {}, n_win               # (n_ch, n_t) -> engine.SublevelScratch, shared by views
         if self.frechet is not None:
             # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
             i32 = dict(dtype=torch.int32, device=device)
@@ -237,7 +258,8 @@ class Workspace:
         v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
         v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
         v.lm = None if self.lm is None else self.lm.head(n_win)
-        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist") + self.PAIR_BUFFERS:
+        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist", "sl_fa", "sl_fe", "sl_sa", "sl_se") \
+                + self.PAIR_BUFFERS:
             buf = getattr(self, name)
             setattr(v, name, None if buf is None else buf[:n_win])
         for name in ("tau_seg", "seg_flags", "flags_host", "result"):
@@ -367,6 +389,8 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
                    (ws.fs0, ws.fs1), ws.pf)
     if ws.fm is not None:
         stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
+    if ws.sublevel:
+        stage("sublevel", lambda: _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table))
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -397,6 +421,42 @@ def _image_stage(ws, ctx, audio):
     """ws.img of the step, (n_seg, n_y, n_x) per set."""
     _set_means_stage(ws, ctx, audio, functools.partial(engine.image_mean_dev, xe_t=ws.img_xe, ye_t=ws.img_ye,
                                                        sigma=ws.images[2], power=ws.images[3]), ws.img_sets)
+
+
+def _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table):
+    """ws.sl of the step: the features of the sublevel-set diagrams of the audio windows and of the EEG channels (read where
+    the step's EEG kernel reads them: stacked, or in place through the window table, which for eeg_sliding is derived here,
+    on the device, from its arguments), then the 22 group means."""
+    import torch
+    n_win, n_ch = ws.n_win, ws.n_ch
+
+    def scratch(ch, n_t):
+        if (ch, n_t) not in ws.sl_scratch:
+            ws.sl_scratch[(ch, n_t)] = engine.SublevelScratch(ch, n_t, ws.device, ws.sublevel_bytes, n_win=ws.sl_n_win)
+        return ws.sl_scratch[(ch, n_t)]
+
+    engine.sublevel_features_dev(audio_win.view(n_win, 1, -1), out_t=ws.sl_fa, status_t=ws.sl_sa,
+                                 scratch=scratch(1, audio_win.shape[-1]), ctx=ctx)
+    if eeg_table is not None:
+        sig_t, start_t, ld_t, win_len = eeg_table
+        tab = dict(n_t=int(win_len), win_start_t=start_t, win_ld_t=ld_t, n_ch=n_ch)
+    elif eeg_sliding is not None:
+        sig_t, win_len, step, sel_t = eeg_sliding
+        n_rec, ch, L = sig_t.shape
+        assert ch == n_ch
+        per_rec = (L - win_len) // step + 1 if L >= win_len else 0
+        sel = torch.arange(n_rec * per_rec, device=ws.device) if sel_t is None else sel_t.to(torch.int64)
+        start_t = torch.div(sel, max(per_rec, 1), rounding_mode="floor") * (n_ch * L) + (sel % max(per_rec, 1)) * step
+        tab = dict(n_t=int(win_len), win_start_t=start_t.contiguous(), win_ld_t=torch.full_like(start_t, L), n_ch=n_ch)
+    else:
+        sig_t, tab = eeg_win, {}
+    n_t = tab["n_t"] if tab else eeg_win.shape[-1]
+    engine.sublevel_features_dev(sig_t, out_t=ws.sl_fe, status_t=ws.sl_se, scratch=scratch(n_ch, n_t), ctx=ctx, **tab)
+    cols = ws.sl_cols[:SL_COLS * n_win].view(SL_COLS, n_win)
+    cols[:11].copy_(ws.sl_fa.view(n_win, 11).t())
+    cols[11:].copy_(ws.sl_fe.mean(dim=1).t())                        # np.mean over the channels: NaN if any is flagged
+    for k in range(SL_COLS):
+        ws.sl[:, k].copy_(engine.segment_nanmean_dev(cols[k], ws.seg_off, ctx=ctx))
 
 
 def _frechet_stage(ws, ctx, audio):
@@ -695,5 +755,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1" and "frechet", in this order after
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1", "frechet" and "sublevel", in this order after
 # "wasserstein_h1")

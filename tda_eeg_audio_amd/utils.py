@@ -139,6 +139,25 @@ def compute_eeg_persistence(dist_matrix, max_dim=MAX_DIM, max_edge_length=MAX_ED
     return [h0[0], h1[0]]
 
 
+def compute_sublevel_persistence(x, return_index=False):
+    """H0 of the sublevel-set (lower-star) filtration of a time series (include/tdaeeg.h, "Sublevel-set persistence of time
+    series"; ripser's lower_star example on a 1-D signal): an (m, 2) array like dgms[0], every local minimum paired with
+    the local maximum at which its basin merges into a deeper one, finite rows in ripser's H0 order, the global minimum's
+    (x[g], inf) last.  return_index=True: (diagram, (m, 2) int32 indices of the birth and death samples, -1 for the
+    essential death).  A 2-D input (n_signals, n_t) gives a list, one launch for all.  Superlevel sets: pass -x.  Not
+    recorded by utils.batch(): it launches at once.  ValueError for samples that are not finite; TdaError for more than
+    SL_MAX_SAMPLES samples."""
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim not in (1, 2) or a.shape[-1] < 1:
+        raise ValueError("compute_sublevel_persistence: a signal of at least one sample, or an (n_signals, n_t) array")
+    dgm, cnt, idx, st = engine.sublevel_batch(a.reshape(-1, a.shape[-1]))
+    if st.any():
+        raise ValueError("compute_sublevel_persistence: the signal has samples that are not finite")
+    out = [(dgm[i, :cnt[i]].copy(), idx[i, :cnt[i]].copy()) if return_index else dgm[i, :cnt[i]].copy()
+           for i in range(dgm.shape[0])]
+    return out[0] if a.ndim == 1 else out
+
+
 def _h1_cap(n):
     return max(256, n * (n - 1) // 2 - (n - 1)) if n <= 64 else 1024
 
