@@ -52,7 +52,8 @@ typedef enum {
 #define TDA_WIN_TOO_LARGE     16  /* more than TDA_MAX_POINTS points (tau < 1?): no diagram    */
 #define TDA_WIN_NO_PAIR       32  /* tda_wasserstein_cross_dev: this diagram has no partner at
                                      its position (mvm:89); the distance is NaN and is no member of the group's mean */
-#define TDA_WIN_NOT_FINITE    64  /* tda_sublevel_batch: the signal has a sample that is not finite; count 0, no rows */
+#define TDA_WIN_NOT_FINITE    64  /* tda_sublevel_batch: the signal has a sample that is not finite; count 0, no rows
+                                     tda_plv_dist_batch: the same for a window; its plv and dist blocks are NaN */
 
 #define TDA_N_FEATURES 11         /* scripts/utils.py:166-177 key order */
 #define TDA_MAX_POINTS 128        /* vertices per Rips complex (reference needs <= 124)        */
@@ -901,6 +902,44 @@ tda_status tda_sublevel_batch_dev(tda_ctx* ctx, const double* sig, const long lo
                                   void* stream);
 tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
                               int n_win, int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status);
+
+/* ---- Phase-locking value: phase synchrony of the channels of a window, and its distance matrix ----------------
+ * The PLV of Lachaux et al. (1999): the length of the mean phasor of the phase difference of two channels over the window;
+ * it ignores amplitude.  The second connectivity beside Pearson correlation (tda_corr_dist_batch); Rips on the result is
+ * tda_rips_dm_batch[_dev].  The contract is this text; tests/plv_ref.py evaluates it.
+ *   Window.     x[c][t], float64, c < n_ch, t < n_t.
+ *   Analytic signal.  h[c][t] = sum_m x[c][m] * g[(t - m) mod n_t], g = imag(ifft(h_hilbert)) of length n_t, tabulated by
+ *               the host as scipy.signal.hilbert builds its multiplier (preprocess._hilbert_g); z = x + i h is
+ *               scipy.signal.hilbert(x, axis=-1) of the WINDOW ITSELF.  Phases taken from a Hilbert transform of the whole
+ *               recording are out of scope: transform the recording first and this call has nothing to offer.
+ *   Unit phasor.  m = sqrt(x*x + h*h), u = (x / m, h / m); where the computed m is 0, u = (1, 0) (np.angle(0) is 0).
+ *   PLV.        plv[i][j] = sqrt(R*R + I*I) / n_t, R + iI = sum_t u_i[t] * conj(u_j[t]), for i != j; plv[i][i] = 1.0
+ *               exactly.  Pair (i, j), i < j, is computed once and stored at both places: symmetric as bytes.
+ *   Distance.   dist = correlation_to_distance(plv, method), the four methods of tda_corr_to_dist_batch (clip, formula,
+ *               clamp at 0); method 0, sqrt(2 (1 - p)), keeps the meaning of the Rips threshold of the EEG step.  The
+ *               diagonal is exactly 0, the matrix symmetric as bytes.
+ *   Sums.       float64 fused multiply-adds in an order that is the kernel's, not the contract's: agreement with the
+ *               definition is to rounding (tests/plv_ref.py: PLV_BAR), not bit for bit.
+ *   Status.     A window with a sample that is not finite gets TDA_WIN_NOT_FINITE and its plv and dist blocks are NaN; the
+ *               other windows are unaffected.  Every other window has status 0.
+ *   Addressing. As tda_sublevel_batch_dev: row c of window w starts at element win_start[w] + c * win_ld[w] of sig (device
+ *               int64 tables, n_win entries each).  Both NULL: stacked windows (n_win, n_ch, n_t).  One NULL is
+ *               TDA_ERR_INVALID.
+ *   Outputs.    dist (n_win, n_ch, n_ch) float64; plv the same, nullable (nothing of it is touched then); status (n_win).
+ *   Limits.     2 <= n_ch <= TDA_PLV_MAX_CHANNELS, 2 <= n_t <= TDA_PLV_MAX_SAMPLES (the window, the table and a tile of at
+ *               least 16 samples' phasors share the 160 KiB of LDS of a CU), method in 0..3; anything else is
+ *               TDA_ERR_INVALID and nothing is launched.
+ *   Determinism.  No atomics; a window alone and inside a batch give the same bytes.
+ * The _dev form only enqueues on `stream` and allocates nothing (g: device, n_t doubles).  The host form stages every
+ * buffer; its tables and g are host arrays. */
+#define TDA_PLV_MAX_CHANNELS 64
+#define TDA_PLV_MAX_SAMPLES 256
+tda_status tda_plv_dist_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                  int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
+                                  int* status, void* stream);
+tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                              int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
+                              int* status);
 
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:

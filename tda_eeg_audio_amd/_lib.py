@@ -25,7 +25,7 @@ TDA_WIN_DEGENERATE = 4
 TDA_WIN_NOT_CONVERGED = 8
 TDA_WIN_TOO_LARGE = 16
 TDA_WIN_NO_PAIR = 32          # tda_wasserstein_cross_dev: no partner at this position (mvm:89)
-TDA_WIN_NOT_FINITE = 64       # tda_sublevel_batch: a sample of the signal is not finite
+TDA_WIN_NOT_FINITE = 64       # tda_sublevel_batch / tda_plv_dist_batch: a sample of the signal / window is not finite
 N_FEATURES = 11
 MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
 MAX_GRID = 256              # TDA_MAX_GRID
@@ -44,6 +44,8 @@ PF_MAX_POINTS = 512         # TDA_PF_MAX_POINTS
 LM_MAX_POINTS = 1024        # TDA_LM_MAX_POINTS: largest cloud the greedy permutation (n_perm) takes
 LM_MAX_SAMPLES = 4096       # TDA_LM_MAX_SAMPLES
 SL_MAX_SAMPLES = 4096       # TDA_SL_MAX_SAMPLES: longest signal of the sublevel-set persistence
+PLV_MAX_CHANNELS = 64       # TDA_PLV_MAX_CHANNELS: most channels of a phase-locking value window
+PLV_MAX_SAMPLES = 256       # TDA_PLV_MAX_SAMPLES: longest one
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -156,6 +158,8 @@ SYMBOLS = {
                                        c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_sublevel_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_sublevel_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_plv_dist_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_plv_dist_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),
@@ -230,8 +234,11 @@ class Context:
 
     RETRY_AUTO, RETRY_FIRST_PASS, RETRY_ONLY, RETRY_ONE_STEP, RETRY_LAST_RUNG = 0, 1, 2, 3, 4
 
+    retry_policy = 0          # the policy last set here (RETRY_AUTO is the library's default): callers save and put it back
+
     def set_retry_policy(self, policy):
         self.check(self.lib.tda_set_retry_policy(self.h, int(policy)))
+        self.retry_policy = int(policy)
 
     ORDER_IN_CALL, ORDER_DEFERRED = 0, 1
 

@@ -680,6 +680,15 @@ tda_status tda_sublevel_batch_dev(tda_ctx* ctx, const double* sig, const long lo
     return launch_sublevel(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, dgm, cap, cnt, idx, status, (hipStream_t)stream);
 }
 
+tda_status tda_plv_dist_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                  int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
+                                  int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, sig); CHECK_PTR(ctx, g); CHECK_PTR(ctx, dist); CHECK_PTR(ctx, status); }
+    return launch_plv_dist(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, method, dist, plv, status, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.
@@ -1346,6 +1355,44 @@ tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* 
     s.add((void**)&d_st, nullptr, status, n_sig * 4);
     RET_IF(s.upload());
     RET_IF(tda_sublevel_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_dgm, cap, d_cnt, d_idx, d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                              int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
+                              int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_ch < 2 || n_ch > TDA_PLV_MAX_CHANNELS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_ch must be in [2, TDA_PLV_MAX_CHANNELS]");
+    if (n_t < 2 || n_t > TDA_PLV_MAX_SAMPLES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be in [2, TDA_PLV_MAX_SAMPLES]");
+    if (method < 0 || method > 3) TDA_FAIL(ctx, TDA_ERR_INVALID, "Unknown method");
+    if ((win_start == nullptr) != (win_ld == nullptr)) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_start and win_ld go together");
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, sig); CHECK_PTR(ctx, g); CHECK_PTR(ctx, dist); CHECK_PTR(ctx, status);
+    // the elements of sig the tables reach
+    long long n_el = (long long)n_win * n_ch * n_t;
+    if (win_start) {
+        n_el = 0;
+        for (int w = 0; w < n_win; ++w) {
+            if (win_start[w] < 0 || win_ld[w] < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative window table entry");
+            const long long end = win_start[w] + (long long)(n_ch - 1) * win_ld[w] + n_t;
+            n_el = end > n_el ? end : n_el;
+        }
+    }
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    const size_t nn = (size_t)n_win * n_ch * n_ch;
+    double *d_sig, *d_g, *d_dist, *d_plv = nullptr;
+    long long *d_ws = nullptr, *d_wl = nullptr;
+    int* d_st;
+    s.add((void**)&d_sig, sig, nullptr, (size_t)n_el * 8);
+    s.add((void**)&d_g, g, nullptr, (size_t)n_t * 8);
+    if (win_start) { s.add((void**)&d_ws, win_start, nullptr, (size_t)n_win * 8); s.add((void**)&d_wl, win_ld, nullptr, (size_t)n_win * 8); }
+    s.add((void**)&d_dist, nullptr, dist, nn * 8);
+    if (plv) s.add((void**)&d_plv, nullptr, plv, nn * 8);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_plv_dist_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_g, method, d_dist, d_plv, d_st, nullptr));
     return s.download();
 }
 

@@ -207,6 +207,9 @@ tda_status launch_landmarks(tda_ctx*, const double* win_or_pc, const int* tau_or
 // (sublevel.hip) H0 of the sublevel-set filtration of n_win * n_ch signals.  Checks the limits of the header itself.
 tda_status launch_sublevel(tda_ctx*, const double* sig, const long long* win_start, const long long* win_ld, int n_win,
                            int n_ch, int n_t, double* dgm, int cap, int* cnt, int* idx, int* status, hipStream_t);
+// (plv.hip) phase-locking value matrix of every window and its distance matrix.  Checks the limits of the header itself.
+tda_status launch_plv_dist(tda_ctx*, const double* sig, const long long* win_start, const long long* win_ld, int n_win,
+                           int n_ch, int n_t, const double* g, int method, double* dist, double* plv, int* status, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,
                               hipStream_t, int n_filt = 1);
 tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, const double*, const double*, int, int, double*,

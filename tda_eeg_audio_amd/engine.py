@@ -10,6 +10,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  landscape_batch, image_batch, frechet_mean_batch, temporal_corr_batch,
                  takens_landmarks_batch, cloud_landmarks_batch (greedy permutation, ripser's n_perm)
                  sublevel_batch (H0 of the sublevel-set filtration of 1-D signals)
+                 plv_dist_batch (phase-locking value matrix of a window's channels and its distance matrix)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -22,6 +23,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  above 128 points (Workspace(takens=(dim, subsample, n_perm))).
                  sublevel_dev / sublevel_features_dev: sublevel-set diagrams of signals read stacked or in place, and
                  their 11 features through a bounded scratch (Workspace(sublevel=True)).
+                 plv_dist_dev: phase-locking value distance matrices of windows read stacked or in place, ready for
+                 rips_dm_dev (Workspace(phase_locking=method)).
 """
 import ctypes as C
 
@@ -77,6 +80,7 @@ def corr_dist_sliding_dev(sig_t, win_len=250, step=62, dist_t=None, corr_t=None,
 
 
 DIST_METHODS = {"euclidean": 0, "abs": 1, "standard": 2, "sqrt": 3}     # nb2:107-116
+METHOD_NAMES = ("euclidean", "abs", "standard", "sqrt")                 # the names by number
 
 
 def corr_to_dist_batch(corr, method="euclidean", ctx=None):
@@ -218,6 +222,48 @@ def sublevel_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, cap=No
     ctx.check(ctx.lib.tda_sublevel_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(dgm), cap, ptr(cnt), ptr(idx),
                                          ptr(status)))
     return dgm, cnt, idx, status
+
+
+def plv_method(method):
+    """The method number of a phase-locking distance: one of DIST_METHODS' names, or True for "euclidean".  ValueError for
+    anything else."""
+    if method is True:
+        return 0
+    if not isinstance(method, str) or method not in DIST_METHODS:
+        raise ValueError(f"phase_locking: one of {sorted(DIST_METHODS)} or True, not {method!r}")
+    return DIST_METHODS[method]
+
+
+def plv_dist_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, method="euclidean", want_plv=True, ctx=None):
+    """Phase-locking value of the channels of every window (include/tdaeeg.h, "Phase-locking value") and its distance
+    matrix: (dist (n_win, n_ch, n_ch), plv the same or None, status (n_win)).  sig (n_win, n_ch, n_t) or one window
+    (n_ch, n_t); or, with the int64 tables win_start / win_ld (n_win each) and n_ch, n_t, a flat array whose row c of window w
+    starts at element win_start[w] + c * win_ld[w].  The Hilbert transform is the window's own (scipy.signal.hilbert of the
+    window).  A window with a sample that is not finite has NaN blocks and status TDA_WIN_NOT_FINITE.  ValueError for an
+    unknown method, TdaError for n_ch outside [2, PLV_MAX_CHANNELS] or n_t outside [2, PLV_MAX_SAMPLES]."""
+    from .preprocess import _hilbert_g
+    m = plv_method(method)
+    ctx = ctx or get_ctx()
+    s = f64(sig)
+    if win_start is None and win_ld is None:
+        if s.ndim == 2:
+            s = s[None]
+        n_win, n_ch, n_t = s.shape
+        ws = wl = None
+    else:
+        ws, wl = (np.ascontiguousarray(t, dtype=np.int64) for t in (win_start, win_ld))
+        assert ws.shape == wl.shape and ws.ndim == 1 and n_ch is not None and n_t is not None
+        n_win, n_ch, n_t = ws.shape[0], int(n_ch), int(n_t)
+        if n_win and n_ch >= 1 and n_t >= 1:
+            assert ws.min() >= 0 and wl.min() >= 0 and int((ws + (n_ch - 1) * wl).max()) + n_t <= s.size, "table past the end of sig"
+    nc = max(n_ch, 0)
+    dist = np.empty((n_win, nc, nc))
+    plv = np.empty((n_win, nc, nc)) if want_plv else None
+    status = np.zeros(n_win, np.int32)
+    g = _hilbert_g(n_t) if n_t >= 1 else np.zeros(1)
+    ctx.check(ctx.lib.tda_plv_dist_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(g), m, ptr(dist), ptr(plv),
+                                         ptr(status)))
+    return dist, plv, status
 
 
 def tau_batch(windows, max_lag=None, ctx=None):
@@ -971,6 +1017,55 @@ def sublevel_features_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch
         features_dev(scratch.dgm[:n], scratch.cnt[:n], out_t[w0:w1], ctx=ctx)
     out_t.masked_fill_((status_t != 0).unsqueeze(-1), float("nan"))
     return out_t
+
+
+_PLV_G = {}                 # (n_t, device) -> the resident Hilbert table of plv_dist_dev
+
+
+def plv_g_table(n_t, device):
+    """preprocess._hilbert_g(n_t) resident on `device`: uploaded once per (n_t, device) and kept (the first call copies from
+    the host, so it stays out of a graph capture: run a step eagerly once, as pipeline.Lanes does)."""
+    import torch
+    from .preprocess import _hilbert_g
+    device = torch.device(device)
+    key = (int(n_t), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _PLV_G:
+        _PLV_G[key] = torch.from_numpy(_hilbert_g(int(n_t))).to(device)
+    return _PLV_G[key]
+
+
+def plv_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, method="euclidean", out=None, plv_t=None,
+                 status_t=None, want_plv=False, ctx=None):
+    """plv_dist_batch on device tensors: one launch on torch's current stream.  sig_t (n_win, n_ch, n_t), or flat with the
+    int64 device tables win_start_t / win_ld_t (those of eeg_window_ragged_dev) and n_ch, n_t.  out: the (n_win, n_ch, n_ch)
+    distance matrices; plv_t: the PLV matrices (made when want_plv; not touched when absent).  Nothing is allocated when
+    out and status_t are given and the table of this (n_t, device) is resident (plv_g_table).  Returns
+    (out, plv_t or None, status_t)."""
+    import torch
+    m = plv_method(method)
+    ctx = ctx or get_ctx()
+    assert sig_t.is_cuda and sig_t.dtype == torch.float64 and sig_t.is_contiguous()
+    if win_start_t is None and win_ld_t is None:
+        assert sig_t.dim() == 3
+        n_win, n_ch, n_t = sig_t.shape
+    else:
+        assert win_start_t.dtype == torch.int64 and win_ld_t.dtype == torch.int64 and win_start_t.numel() == win_ld_t.numel()
+        assert win_start_t.is_contiguous() and win_ld_t.is_contiguous() and n_ch is not None and n_t is not None
+        n_win, n_ch, n_t = int(win_start_t.numel()), int(n_ch), int(n_t)
+    dev = sig_t.device
+    nc = max(n_ch, 0)
+    if out is None:
+        out = torch.empty((n_win, nc, nc), dtype=torch.float64, device=dev)
+    if plv_t is None and want_plv:
+        plv_t = torch.empty((n_win, nc, nc), dtype=torch.float64, device=dev)
+    status_t = torch.zeros(n_win, dtype=torch.int32, device=dev) if status_t is None else status_t
+    assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() >= n_win * nc * nc
+    assert plv_t is None or (plv_t.is_contiguous() and plv_t.dtype == torch.float64 and plv_t.numel() >= n_win * nc * nc)
+    assert status_t.numel() >= n_win and status_t.dtype == torch.int32 and status_t.is_contiguous()
+    g_t = plv_g_table(max(n_t, 1), dev)
+    ctx.check(ctx.lib.tda_plv_dist_batch_dev(ctx.h, _tp(sig_t), _tp(win_start_t), _tp(win_ld_t), n_win, n_ch, n_t, _tp(g_t), m,
+                                             _tp(out), _tp(plv_t), _tp(status_t), _stream()))
+    return out, plv_t, status_t
 
 
 def tau_dev(win_t, max_lag=None, tau_t=None, ctx=None):

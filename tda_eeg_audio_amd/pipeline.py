@@ -29,14 +29,15 @@ FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram se
 KD_COLS = 2               # Workspace(kernel_distance=kernel).kd: [k_h0, k_h1], the means of the kernel-induced distances
 PF_COLS = 2               # Workspace(fisher=sigma).pf: [f_h0, f_h1], the means of the persistence Fisher distances
 SL_COLS = 22              # Workspace(sublevel=True).sl: the 11 features of the audio window's sublevel-set diagram, then of the EEG channels'
+PL_COLS = 24              # Workspace(phase_locking=method).pl: the 11 features of H0, then of H1, of the PLV-distance Rips complex, then [w_h0, w_h1]
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
 def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None, fisher=None, sublevel=False):
+                 frechet=None, kernel_distance=None, fisher=None, sublevel=False, phase_locking=None):
     """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf, sl.  numpy only.  Workspace, the shard driver and the passes of
+    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf, sl, pl.  numpy only.  Workspace, the shard driver and the passes of
     recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
       corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
             against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
@@ -68,7 +69,14 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
             extract_features values of the audio window's diagram.  Columns 11..21: np.nanmean over the windows of the
             np.mean over the channels of the same 11 values of the EEG channels' diagrams, one diagram per channel.  A
             signal with a sample that is not finite counts as NaN.  Every window of the group takes part: no Rips status
-            is looked at"""
+            is looked at
+      pl    phase_locking=method, one of "euclidean", "abs", "standard", "sqrt" (True: "euclidean"; the parameter kept is
+            the method number): (PL_COLS,) from the Rips diagrams of the phase-locking distance of the EEG window's channels
+            (engine.plv_dist_dev -> rips_dm_dev; include/tdaeeg.h, "Phase-locking value").  Columns 0..10: np.nanmean over
+            the group's windows of the 11 extract_features values of H0; columns 11..21: the same for H1; every window of
+            the group takes part, as for the EEG sets.  Columns 22, 23: np.nanmean of the reference's Wasserstein distance
+            (engine.wasserstein_dev) between that diagram and the audio diagram of the same window, H0 and H1, under the
+            rule of `bott`.  A window with a PLV or Rips status counts as NaN.  ValueError for anything else"""
     from . import _lib
     out = []
     if correlations:
@@ -117,6 +125,8 @@ def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=N
         out.append(Output("pf", (PF_COLS,), float(fisher)))
     if sublevel:
         out.append(Output("sl", (SL_COLS,), None))
+    if phase_locking is not None and phase_locking is not False:
+        out.append(Output("pl", (PL_COLS,), engine.plv_method(phase_locking)))
     return out
 
 
@@ -134,12 +144,13 @@ class Workspace:
     kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
     pf = fisher = f0 = f1 = fs0 = fs1 = None
     sl = sl_fa = sl_fe = sl_sa = sl_se = sl_cols = sl_scratch = None; sublevel = False
+    pl = phase_locking = pl_dist = pl_st = pl_dgm = pl_f0 = pl_f1 = pl_w0 = pl_w1 = pl_ws0 = pl_ws1 = pl_cols = pl_line = None
     lm = takens = None
 
     def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
                  landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None, takens=None, sublevel=False, sublevel_bytes=engine.SL_SCRATCH_BYTES):
-        """correlations .. fisher, sublevel: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
+                 fisher=None, takens=None, sublevel=False, sublevel_bytes=engine.SL_SCRATCH_BYTES, phase_locking=None):
+        """correlations .. fisher, sublevel, phase_locking: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
         the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
         `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2), `pf` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` / `pf` the distances of every
         window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1`, `k0` / `k1` and `f0` / `f1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`,
@@ -149,6 +160,11 @@ class Workspace:
         `sl_fe` (n_win, n_ch, 11) of the EEG channels (NaN where `sl_sa` / `sl_se` flag the signal).  The diagrams themselves
         exist only chunk by chunk, in scratch of at most sublevel_bytes of rows per signal kind (engine.SublevelScratch,
         made at the first step, when the window length is known).
+        phase_locking=method: `pl` (n_seg, 24), and per window what it averages: `pl_f0` / `pl_f1` (n_win, 11), the features
+        of the H0 / H1 diagram `pl_dgm` (an engine.DeviceDiagrams) of the phase-locking distance matrix `pl_dist`
+        (n_win, n_ch, n_ch), `pl_w0` / `pl_w1` (n_win), its Wasserstein distances to the audio diagram, with the status words
+        `pl_st` (the PLV kernel's), `pl_dgm.status` (Rips) and `pl_ws0` / `pl_ws1` (the distances').  A window flagged by the
+        PLV kernel is handed to Rips as points on a line (`pl_line`), its NaN block in `pl_dist` replaced, and counts as NaN.
         takens=None: the audio stage as the reference runs it (dim 3, subsample 2, every point; at most 128 points).
         takens=(dim, subsample, n_perm): the audio stage embeds with these and runs Rips on n_perm greedy landmarks
         (engine.takens_rips_landmarks_dev), for clouds of up to LM_MAX_POINTS points; `lm` (an engine.DeviceLandmarks,
@@ -182,7 +198,7 @@ class Workspace:
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
         self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
-                                    fisher, sublevel)
+                                    fisher, sublevel, phase_locking)
         par = {o.name: o.params for o in self.outputs}
         self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
         self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
@@ -218,6 +234,17 @@ class Workspace:
             self.sl_sa, self.sl_se = torch.empty((n_win, 1), **i32), torch.empty((n_win, n_ch), **i32)
             self.sl_cols = torch.empty(SL_COLS * n_win, **f64)       # the 22 per-window series, one contiguous row each
             self.sl_scratch, self.sl_n_win = {}, n_win               # (n_ch, n_t) -> engine.SublevelScratch, shared by views
+        if "pl" in par:
+            i32 = dict(dtype=torch.int32, device=device)
+            self.phase_locking = par["pl"]
+            self.pl_dist = torch.empty((n_win, n_ch, n_ch), **f64)
+            self.pl_dgm = engine.DeviceDiagrams(n_win, n_ch, h1_cap, device)
+            self.pl_f0, self.pl_f1 = torch.empty((n_win, 11), **f64), torch.empty((n_win, 11), **f64)
+            self.pl_w0, self.pl_w1 = torch.empty(n_win, **f64), torch.empty(n_win, **f64)
+            self.pl_st, self.pl_ws0, self.pl_ws1 = (torch.empty(n_win, **i32) for _ in range(3))
+            self.pl_cols = torch.empty(PL_COLS * n_win, **f64)       # the 24 per-window series, one contiguous row each
+            k = torch.arange(n_ch, **f64)
+            self.pl_line = (k[:, None] - k[None, :]).abs() / n_ch    # what Rips gets for a window the PLV kernel flagged
         if self.frechet is not None:
             # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
             i32 = dict(dtype=torch.int32, device=device)
@@ -258,7 +285,9 @@ class Workspace:
         v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
         v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
         v.lm = None if self.lm is None else self.lm.head(n_win)
-        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist", "sl_fa", "sl_fe", "sl_sa", "sl_se") \
+        v.pl_dgm = None if self.pl_dgm is None else self.pl_dgm.head(n_win)
+        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist", "sl_fa", "sl_fe", "sl_sa", "sl_se",
+                     "pl_dist", "pl_st", "pl_f0", "pl_f1", "pl_w0", "pl_w1", "pl_ws0", "pl_ws1") \
                 + self.PAIR_BUFFERS:
             buf = getattr(self, name)
             setattr(v, name, None if buf is None else buf[:n_win])
@@ -391,6 +420,8 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
         stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
     if ws.sublevel:
         stage("sublevel", lambda: _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table))
+    if ws.pl is not None:
+        stage("phase_locking", lambda: _phase_locking_stage(ws, ctx, eeg_win, eeg_sliding, eeg_table))
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -423,6 +454,62 @@ def _image_stage(ws, ctx, audio):
                                                        sigma=ws.images[2], power=ws.images[3]), ws.img_sets)
 
 
+def _eeg_window_table(ws, eeg_win, eeg_sliding, eeg_table):
+    """Where the step's EEG kernel reads its windows, for the kernels that take a window table: (sig_t, the table keywords of
+    engine.sublevel_features_dev / plv_dist_dev -- none for stacked windows --, n_t).  For eeg_sliding the table is derived
+    here, on the device, from its arguments."""
+    import torch
+    n_ch = ws.n_ch
+    if eeg_table is not None:
+        sig_t, start_t, ld_t, win_len = eeg_table
+        tab = dict(n_t=int(win_len), win_start_t=start_t, win_ld_t=ld_t, n_ch=n_ch)
+    elif eeg_sliding is not None:
+        sig_t, win_len, step, sel_t = eeg_sliding
+        n_rec, ch, L = sig_t.shape
+        assert ch == n_ch
+        per_rec = (L - win_len) // step + 1 if L >= win_len else 0
+        sel = torch.arange(n_rec * per_rec, device=ws.device) if sel_t is None else sel_t.to(torch.int64)
+        start_t = torch.div(sel, max(per_rec, 1), rounding_mode="floor") * (n_ch * L) + (sel % max(per_rec, 1)) * step
+        tab = dict(n_t=int(win_len), win_start_t=start_t.contiguous(), win_ld_t=torch.full_like(start_t, L), n_ch=n_ch)
+    else:
+        sig_t, tab = eeg_win, {}
+    return sig_t, tab, (tab["n_t"] if tab else eeg_win.shape[-1])
+
+
+def _phase_locking_stage(ws, ctx, eeg_win, eeg_sliding, eeg_table):
+    """ws.pl of the step: the phase-locking distance matrix of every EEG window (read where the step's EEG kernel reads it),
+    Rips on it, the finishing pass (H1 rows into ripser's order, the features of H0 and H1), the Wasserstein distances to the
+    audio diagrams, then the 24 group means.  The Rips call runs its whole ladder whatever the step's retry policy (the
+    policy is put back afterwards): it is exact by itself, so no class-overflow bit of it has to travel to the host."""
+    import torch
+    from . import _lib
+    n_win = ws.n_win
+    sig_t, tab, _ = _eeg_window_table(ws, eeg_win, eeg_sliding, eeg_table)
+    engine.plv_dist_dev(sig_t, method=engine.METHOD_NAMES[ws.phase_locking], out=ws.pl_dist, status_t=ws.pl_st, ctx=ctx, **tab)
+    bad = ws.pl_st != 0
+    torch.where(bad[:, None, None], ws.pl_line, ws.pl_dist, out=ws.pl_dist)
+    policy = ctx.retry_policy
+    ctx.set_retry_policy(ctx.RETRY_AUTO)
+    try:
+        engine.rips_dm_dev(ws.pl_dist, ws.pl_dgm, ctx=ctx)
+    finally:
+        ctx.set_retry_policy(policy)
+    engine.diagram_finish_dev([(ws.pl_dgm.h0, ws.pl_dgm.c0, False, ws.pl_f0), (ws.pl_dgm.h1, ws.pl_dgm.c1, True, ws.pl_f1)],
+                              ctx=ctx)
+    engine.wasserstein_dev(ws.pl_dgm.h0, ws.pl_dgm.c0, ws.aud.h0, ws.aud.c0, out_t=ws.pl_w0, status_t=ws.pl_ws0, ctx=ctx)
+    engine.wasserstein_dev(ws.pl_dgm.h1, ws.pl_dgm.c1, ws.aud.h1, ws.aud.c1, out_t=ws.pl_w1, status_t=ws.pl_ws1, ctx=ctx)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
+    bad = bad | (ws.pl_dgm.status != 0)
+    out = bad | ((ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0)
+    cols = ws.pl_cols[:PL_COLS * n_win].view(PL_COLS, n_win)
+    cols[:11].copy_(torch.where(bad[:, None], nan, ws.pl_f0).t())
+    cols[11:22].copy_(torch.where(bad[:, None], nan, ws.pl_f1).t())
+    cols[22].copy_(torch.where(out | (ws.pl_ws0 != 0), nan, ws.pl_w0))
+    cols[23].copy_(torch.where(out | (ws.pl_ws1 != 0), nan, ws.pl_w1))
+    for k in range(PL_COLS):
+        ws.pl[:, k].copy_(engine.segment_nanmean_dev(cols[k], ws.seg_off, ctx=ctx))
+
+
 def _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table):
     """ws.sl of the step: the features of the sublevel-set diagrams of the audio windows and of the EEG channels (read where
     the step's EEG kernel reads them: stacked, or in place through the window table, which for eeg_sliding is derived here,
@@ -437,20 +524,7 @@ def _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table):
 
     engine.sublevel_features_dev(audio_win.view(n_win, 1, -1), out_t=ws.sl_fa, status_t=ws.sl_sa,
                                  scratch=scratch(1, audio_win.shape[-1]), ctx=ctx)
-    if eeg_table is not None:
-        sig_t, start_t, ld_t, win_len = eeg_table
-        tab = dict(n_t=int(win_len), win_start_t=start_t, win_ld_t=ld_t, n_ch=n_ch)
-    elif eeg_sliding is not None:
-        sig_t, win_len, step, sel_t = eeg_sliding
-        n_rec, ch, L = sig_t.shape
-        assert ch == n_ch
-        per_rec = (L - win_len) // step + 1 if L >= win_len else 0
-        sel = torch.arange(n_rec * per_rec, device=ws.device) if sel_t is None else sel_t.to(torch.int64)
-        start_t = torch.div(sel, max(per_rec, 1), rounding_mode="floor") * (n_ch * L) + (sel % max(per_rec, 1)) * step
-        tab = dict(n_t=int(win_len), win_start_t=start_t.contiguous(), win_ld_t=torch.full_like(start_t, L), n_ch=n_ch)
-    else:
-        sig_t, tab = eeg_win, {}
-    n_t = tab["n_t"] if tab else eeg_win.shape[-1]
+    sig_t, tab, n_t = _eeg_window_table(ws, eeg_win, eeg_sliding, eeg_table)
     engine.sublevel_features_dev(sig_t, out_t=ws.sl_fe, status_t=ws.sl_se, scratch=scratch(n_ch, n_t), ctx=ctx, **tab)
     cols = ws.sl_cols[:SL_COLS * n_win].view(SL_COLS, n_win)
     cols[:11].copy_(ws.sl_fa.view(n_win, 11).t())
@@ -755,5 +829,5 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
 # (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1", "frechet" and "sublevel", in this order after
+# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1", "frechet", "sublevel" and "phase_locking", in this order after
 # "wasserstein_h1")

@@ -158,6 +158,38 @@ def compute_sublevel_persistence(x, return_index=False):
     return out[0] if a.ndim == 1 else out
 
 
+def _plv_window(window):
+    a = np.asarray(window, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 2 or a.shape[1] < 2:
+        raise ValueError("a window (n_ch, n_t) of at least two channels and two samples")
+    return a
+
+
+def compute_plv_matrix(window):
+    """The phase-locking value of every pair of channels of a window (n_ch, n_t) (include/tdaeeg.h, "Phase-locking value";
+    Lachaux et al. 1999): an (n_ch, n_ch) symmetric matrix in [0, 1] with ones on the diagonal, the phases those of
+    scipy.signal.hilbert of the window itself.  Not recorded by utils.batch(): it launches at once.  ValueError for samples
+    that are not finite; TdaError for more than PLV_MAX_CHANNELS channels or PLV_MAX_SAMPLES samples."""
+    _, plv, st = engine.plv_dist_batch(_plv_window(window)[None])
+    if st.any():
+        raise ValueError("compute_plv_matrix: the window has samples that are not finite")
+    return plv[0]
+
+
+def compute_plv_persistence(window, method="euclidean", max_dim=MAX_DIM, max_edge_length=MAX_EDGE_LENGTH):
+    """[H0, H1] of the Rips complex on the phase-locking distance of a window's channels, in the format of
+    compute_eeg_persistence: correlation_to_distance(compute_plv_matrix(window), method) through the Rips call of
+    compute_eeg_persistence.  Not recorded by utils.batch(): it launches at once.  ValueError for an unknown method or
+    samples that are not finite."""
+    _check_dim(max_dim)
+    dist, _, st = engine.plv_dist_batch(_plv_window(window)[None], method=method, want_plv=False)
+    if st.any():
+        raise ValueError("compute_plv_persistence: the window has samples that are not finite")
+    h0, h1, rst = engine.rips_dm_batch(dist, thresh=max_edge_length, symmetrise=True, h1_cap=_h1_cap(dist.shape[1]))
+    _check_status(rst[0])
+    return [h0[0], h1[0]]
+
+
 def _h1_cap(n):
     return max(256, n * (n - 1) // 2 - (n - 1)) if n <= 64 else 1024
 
