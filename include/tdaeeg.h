@@ -941,6 +941,52 @@ tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* 
                               int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
                               int* status);
 
+/* ---- Two-sample permutation sums: within- and between-group sums of a matrix under many relabellings ----------------
+ * The arithmetic of the permutation test of Robinson and Turner (2017, "Hypothesis testing for topological data analysis")
+ * on a distance matrix between diagrams, and of its kernel twin, the MMD / energy two-sample test on a Gram matrix: the
+ * sums of the matrix over the pairs inside group 0, inside group 1 and between the groups, for every relabelling of a
+ * batch at once.  The statistics and p-values made of them are the host's (utils.two_sample_statistic).  The reference
+ * compares groups with a random forest on scalars and has no counterpart.  The contract is this text;
+ * tests/permutation_ref.py evaluates it literally.
+ *   Matrices.   D (n_mat, n, ld) float64, ld >= n: entry (i, j) of matrix m is D[(m * n + i) * ld + j].  Only entries with
+ *               i < j are read; the diagonal, the lower triangle and the columns from n on are never touched.
+ *   Labels.     lab (TDA_PT_WORDS(n_perm), n) uint64: bit (p % 64) of lab[p / 64][j] is the label, 0 or 1, of item j under
+ *               relabelling p (engine.pack_labels).  The bits of the last word past n_perm are ignored.
+ *   Row sums.   For relabelling p and row i:  same = +0.0, diff = +0.0;  for j = i + 1, ..., n - 1 in this order:
+ *               same = same + D[i][j] if label[j] == label[i], else diff = diff + D[i][j].  An entry is added to one of the
+ *               two and not at all to the other.
+ *   Blocks.     Rows are taken in blocks of TDA_PT_ROW_BLOCK: block b = rows [b R, min((b + 1) R, n)), TDA_PT_BLOCKS(n)
+ *               of them.  Per block p00 = p11 = p01 = +0.0;  for i ascending in the block:
+ *               (label[i] == 0 ? p00 : p11) += same_i;  p01 += diff_i.
+ *   Sums.       S00 = S11 = S01 = +0.0;  for b ascending:  S00 += p00_b;  S11 += p11_b;  S01 += p01_b.
+ *               So S00 (S11) is the sum of D[i][j], i < j, over the pairs with both labels 0 (1), S01 over the pairs with
+ *               different labels, each in one written order that is a function of n alone: it does not depend on n_perm, on
+ *               the place of a relabelling in the batch, on n_mat or on how the work is launched.  The order treats the two
+ *               classes alike: S00 under a labelling has the bytes of S11 under its complement, and S01 the same bytes
+ *               under both.  No partial sum is ever -0.0 (they start at +0.0), so adding an empty row or block changes
+ *               nothing.
+ *   Non-finite entries follow IEEE: an Inf or NaN at (i, j), i < j, reaches exactly the one sum whose class holds the pair.
+ *   Outputs.    out (n_mat, 3, n_perm) float64: S00, S11, S01.  n1 (n_perm) int32, nullable: the number of items labelled 1.
+ *   Work.       work: device, at least TDA_PT_WORK_DOUBLES(n_mat, n, n_perm) doubles, the block partials; the call reads
+ *               nothing it has not written there.
+ *   Limits.     2 <= n <= TDA_PT_MAX_ITEMS, 1 <= n_perm <= TDA_PT_MAX_PERM, 0 <= n_mat <= TDA_PT_MAX_MATRICES, ld >= n;
+ *               anything else is TDA_ERR_INVALID with a message in tda_last_error, and nothing is launched or written.
+ *   Determinism.  No atomics; one lane per relabelling; results are the bytes of the definition.
+ * The _dev form only enqueues on `stream` (two launches) and allocates nothing.  The host form stages every buffer and
+ * takes its work space from the context. */
+#define TDA_PT_ROW_BLOCK 64
+#define TDA_PT_MAX_ITEMS 4096
+#define TDA_PT_MAX_PERM 1048576
+#define TDA_PT_MAX_MATRICES 4096
+#define TDA_PT_WORDS(n_perm) (((n_perm) + 63) / 64)
+#define TDA_PT_BLOCKS(n) (((n) + TDA_PT_ROW_BLOCK - 1) / TDA_PT_ROW_BLOCK)
+#define TDA_PT_WORK_DOUBLES(n_mat, n, n_perm) \
+    ((long long)(n_mat) * TDA_PT_BLOCKS(n) * 3 * 64 * TDA_PT_WORDS(n_perm))
+tda_status tda_perm_sums_batch_dev(tda_ctx* ctx, const double* D, int n_mat, int n, int ld, const unsigned long long* lab,
+                                   int n_perm, double* work, long long work_doubles, double* out, int* n1, void* stream);
+tda_status tda_perm_sums_batch(tda_ctx* ctx, const double* D, int n_mat, int n, int ld, const unsigned long long* lab,
+                               int n_perm, double* out, int* n1);
+
 /* ---- Wasserstein distances between GROUPED diagrams, paired by position -------------
  * replaces compute_cross_wasserstein (scripts/matched_vs_mismatched.py:86-95) for every (recording, band) at once:
  * the diagrams of A group g are paired, position by position, with those of B group partner_seg[g] (mvm:89:

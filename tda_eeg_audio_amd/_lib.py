@@ -46,6 +46,26 @@ LM_MAX_SAMPLES = 4096       # TDA_LM_MAX_SAMPLES
 SL_MAX_SAMPLES = 4096       # TDA_SL_MAX_SAMPLES: longest signal of the sublevel-set persistence
 PLV_MAX_CHANNELS = 64       # TDA_PLV_MAX_CHANNELS: most channels of a phase-locking value window
 PLV_MAX_SAMPLES = 256       # TDA_PLV_MAX_SAMPLES: longest one
+PT_ROW_BLOCK = 64           # TDA_PT_ROW_BLOCK: rows per block of the permutation sums' written order
+PT_MAX_ITEMS = 4096         # TDA_PT_MAX_ITEMS: largest matrix side of tda_perm_sums_batch
+PT_MAX_PERM = 1048576       # TDA_PT_MAX_PERM: most relabellings of a call
+PT_MAX_MATRICES = 4096      # TDA_PT_MAX_MATRICES: most matrices of a call
+
+
+def pt_words(n_perm):
+    """TDA_PT_WORDS: 64-bit label words per item."""
+    return (int(n_perm) + 63) // 64
+
+
+def pt_blocks(n):
+    """TDA_PT_BLOCKS: row blocks of an n x n matrix."""
+    return (int(n) + PT_ROW_BLOCK - 1) // PT_ROW_BLOCK
+
+
+def pt_work_doubles(n_mat, n, n_perm):
+    """TDA_PT_WORK_DOUBLES: doubles of device work space tda_perm_sums_batch_dev needs."""
+    return int(n_mat) * pt_blocks(n) * 3 * 64 * pt_words(n_perm)
+
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
@@ -160,6 +180,8 @@ SYMBOLS = {
     "tda_sublevel_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_plv_dist_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_plv_dist_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_perm_sums_batch_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, C.c_longlong, c_vp, c_vp, c_vp]),
+    "tda_perm_sums_batch": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),
     "tda_event_record": (_I, [c_vp, c_vp, c_vp]),
     "tda_event_elapsed_ms": (_I, [c_vp, c_vp, c_vp, C.POINTER(C.c_float)]),

@@ -689,6 +689,14 @@ tda_status tda_plv_dist_batch_dev(tda_ctx* ctx, const double* sig, const long lo
     return launch_plv_dist(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, method, dist, plv, status, (hipStream_t)stream);
 }
 
+tda_status tda_perm_sums_batch_dev(tda_ctx* ctx, const double* D, int n_mat, int n, int ld, const unsigned long long* lab,
+                                   int n_perm, double* work, long long work_doubles, double* out, int* n1, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_PTR(ctx, lab);
+    if (n_mat > 0) { CHECK_PTR(ctx, D); CHECK_PTR(ctx, work); CHECK_PTR(ctx, out); }
+    return launch_perm_sums(ctx, D, n_mat, n, ld, lab, n_perm, work, work_doubles, out, n1, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------- host-pointer twins
 // A bump allocator over the context workspace; everything is staged, launched on the
 // default stream, copied back and synchronised.
@@ -1393,6 +1401,36 @@ tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* 
     s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
     RET_IF(s.upload());
     RET_IF(tda_plv_dist_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_g, method, d_dist, d_plv, d_st, nullptr));
+    return s.download();
+}
+
+// (the limits are checked before anything is staged; of the last row of D only its n entries are copied)
+tda_status tda_perm_sums_batch(tda_ctx* ctx, const double* D, int n_mat, int n, int ld, const unsigned long long* lab,
+                               int n_perm, double* out, int* n1)
+{
+    CHECK_CTX(ctx);
+    if (n < 2 || n > TDA_PT_MAX_ITEMS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [2, TDA_PT_MAX_ITEMS]");
+    if (n_perm < 1 || n_perm > TDA_PT_MAX_PERM) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_perm must be in [1, TDA_PT_MAX_PERM]");
+    if (n_mat < 0 || n_mat > TDA_PT_MAX_MATRICES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_mat must be in [0, TDA_PT_MAX_MATRICES]");
+    if (ld < n) TDA_FAIL(ctx, TDA_ERR_INVALID, "ld must be >= n");
+    CHECK_PTR(ctx, lab);
+    if (n_mat) { CHECK_PTR(ctx, D); CHECK_PTR(ctx, out); }
+    if (n_mat == 0 && !n1) return TDA_OK;
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    const long long wd = TDA_PT_WORK_DOUBLES(n_mat, n, n_perm);
+    double *d_D = nullptr, *d_work = nullptr, *d_out = nullptr;
+    unsigned long long* d_lab;
+    int* d_n1 = nullptr;
+    if (n_mat) {
+        s.add((void**)&d_D, D, nullptr, (((size_t)n_mat * n - 1) * ld + n) * 8);
+        s.add((void**)&d_work, nullptr, nullptr, (size_t)wd * 8);
+        s.add((void**)&d_out, nullptr, out, (size_t)n_mat * 3 * n_perm * 8);
+    }
+    s.add((void**)&d_lab, lab, nullptr, (size_t)TDA_PT_WORDS(n_perm) * n * 8);
+    if (n1) s.add((void**)&d_n1, nullptr, n1, (size_t)n_perm * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_perm_sums_batch_dev(ctx, d_D, n_mat, n, ld, d_lab, n_perm, d_work, wd, d_out, d_n1, nullptr));
     return s.download();
 }
 

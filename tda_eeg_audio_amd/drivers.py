@@ -26,6 +26,8 @@ reference's on-disk formats.
                             of results/eeg_audio_tda_comparison.json
   match_rows_host / match_mismatch_summary
                             the per-band statistics of the match-mismatch matrix (recordings.MatchMismatchPass)
+  two_sample_from_diagrams  (not in the reference) the two-sample permutation test of Robinson and Turner between two groups
+                            of recordings, on a sliced Wasserstein, persistence Fisher or kernel matrix of their diagrams
 """
 import hashlib
 from pathlib import Path
@@ -829,3 +831,39 @@ def run_comparison(pass_, raw_h, second_h, filenames, conditions, out_csv=None, 
         with open(out_json, "w") as f:
             json.dump(doc, f, indent=2)
     return rows, corr, table, summary
+
+
+def two_sample_from_diagrams(dgms, y, subjects=None, metric=("sliced", None), ctx=None, **kw):
+    """(not in the reference) The two-sample permutation test of utils.two_sample_permutation_test on the recordings'
+    diagrams: is the topology of group y == 1 different from that of group y == 0?  The (n_rec, n_rec) matrix is built on
+    the device by the existing Gram calls and goes to the permutation kernel without leaving it.
+      metric = ("sliced", dirs)     dgms: one diagram per recording; sliced Wasserstein distances over the (M, 2) direction
+                                    table dirs (None: utils.default_directions()); statistic "joint_loss"
+      metric = ("fisher", sigma)    the same with the persistence Fisher distance; "joint_loss"
+      metric = ("kernel", kernel)   dgms: per recording a LIST of diagrams (its windows); the Gram matrix of the recordings'
+                                    mean embeddings under a kernel of engine.diagram_kernel_args, e.g. ("pss", 0.1); "mmd"
+    statistic=..., n_permutations, seed and labels go on to two_sample_permutation_test, whose dict comes back."""
+    import torch
+    from . import utils
+    from ._lib import get_ctx
+    ctx = ctx or get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    kind, par = metric
+    if kind == "kernel":
+        flat = [utils._clean_pair_diagram(d) for rec in dgms for d in rec]
+        seg_off = np.concatenate([[0], np.cumsum([len(rec) for rec in dgms])]).astype(np.int32)
+    elif kind in ("sliced", "fisher"):
+        flat = [utils._clean_pair_diagram(d) for d in dgms]
+    else:
+        raise ValueError(f"Unknown metric: {kind!r}")
+    rows, cnt = engine.pack_diagrams(flat)
+    rows_t, cnt_t = torch.from_numpy(rows).to(dev), torch.from_numpy(cnt).to(dev)
+    if kind == "sliced":
+        dirs = engine._directions(utils.default_directions() if par is None else par)
+        G = engine.sliced_wasserstein_gram_dev(rows_t, cnt_t, torch.from_numpy(dirs).to(dev), ctx=ctx)
+    elif kind == "fisher":
+        G = engine.persistence_fisher_gram_dev(rows_t, cnt_t, par, ctx=ctx)
+    else:
+        G = engine.diagram_kernel_gram_dev(rows_t, cnt_t, par, seg_off_a=torch.from_numpy(seg_off).to(dev), ctx=ctx)
+    kw.setdefault("statistic", "mmd" if kind == "kernel" else "joint_loss")
+    return utils.two_sample_permutation_test(G, y, subjects=subjects, ctx=ctx, **kw)

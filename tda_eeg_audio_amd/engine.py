@@ -11,6 +11,7 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  takens_landmarks_batch, cloud_landmarks_batch (greedy permutation, ripser's n_perm)
                  sublevel_batch (H0 of the sublevel-set filtration of 1-D signals)
                  plv_dist_batch (phase-locking value matrix of a window's channels and its distance matrix)
+                 pack_labels / permutation_sums_batch (within- and between-group sums of matrices under relabellings)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -25,6 +26,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  their 11 features through a bounded scratch (Workspace(sublevel=True)).
                  plv_dist_dev: phase-locking value distance matrices of windows read stacked or in place, ready for
                  rips_dm_dev (Workspace(phase_locking=method)).
+                 permutation_sums_dev: the sums of a two-sample permutation test on matrices that never leave the device
+                 (utils.two_sample_permutation_test, drivers.two_sample_from_diagrams).
 """
 import ctypes as C
 
@@ -264,6 +267,45 @@ def plv_dist_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, method
     ctx.check(ctx.lib.tda_plv_dist_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(g), m, ptr(dist), ptr(plv),
                                          ptr(status)))
     return dist, plv, status
+
+
+def pack_labels(labels):
+    """(n_perm, n) labels in {0, 1} -> the (TDA_PT_WORDS(n_perm), n) uint64 layout of tda_perm_sums_batch: bit p % 64 of
+    word [p // 64][j] is labels[p][j]; the bits past n_perm are 0."""
+    lab = np.asarray(labels)
+    assert lab.ndim == 2, "labels must be (n_perm, n)"
+    assert ((lab == 0) | (lab == 1)).all(), "labels must be 0 or 1"
+    n_perm, n = lab.shape
+    nw = _lib.pt_words(n_perm)
+    bits = np.zeros((nw * 64, n), np.uint8)
+    bits[:n_perm] = lab
+    by = np.packbits(bits.reshape(nw, 8, 8, n), axis=2, bitorder="little")[:, :, 0, :]     # (nw, 8, n): byte k = bits 8k..8k+7
+    return np.ascontiguousarray(by.transpose(0, 2, 1)).view("<u8").reshape(nw, n)
+
+
+def _perm_shape(shape, n):
+    assert len(shape) in (2, 3), "D must be (n_mat, n, ld) or (n, ld)"
+    n_mat, rows, ld = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    assert rows == n, "D has another number of rows than the labels have items"
+    return int(n_mat), int(ld)
+
+
+def permutation_sums_batch(D, labels, ctx=None):
+    """The sums of include/tdaeeg.h, "Two-sample permutation sums": D (n_mat, n, ld) float64 with ld >= n (or one matrix,
+    (n, ld)), of which only the entries i < j < n are read; labels (n_perm, n) in {0, 1}.  Returns
+    (sums (n_mat, 3, n_perm): S00, S11, S01 as the bytes of the written order; n1 (n_perm) int32).  TdaError for n outside
+    [2, PT_MAX_ITEMS], no relabelling or more than PT_MAX_PERM."""
+    ctx = ctx or get_ctx()
+    lab = np.asarray(labels)
+    assert lab.ndim == 2, "labels must be (n_perm, n)"
+    n_perm, n = lab.shape
+    d = f64(D)
+    n_mat, ld = _perm_shape(d.shape, n)
+    packed = pack_labels(lab) if n_perm else np.zeros((1, n), np.uint64)
+    out = np.empty((n_mat, 3, n_perm))
+    n1 = np.empty(n_perm, np.int32)
+    ctx.check(ctx.lib.tda_perm_sums_batch(ctx.h, ptr(d), n_mat, n, ld, ptr(packed), n_perm, ptr(out), ptr(n1)))
+    return out, n1
 
 
 def tau_batch(windows, max_lag=None, ctx=None):
@@ -1066,6 +1108,39 @@ def plv_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, me
     ctx.check(ctx.lib.tda_plv_dist_batch_dev(ctx.h, _tp(sig_t), _tp(win_start_t), _tp(win_ld_t), n_win, n_ch, n_t, _tp(g_t), m,
                                              _tp(out), _tp(plv_t), _tp(status_t), _stream()))
     return out, plv_t, status_t
+
+
+def permutation_sums_dev(D_t, lab_t, out_t=None, n1_t=None, ctx=None, n_perm=None, work_t=None):
+    """permutation_sums_batch on device tensors: two launches on torch's current stream, no synchronisation.  D_t
+    (n_mat, n, ld) or (n, ld) float64, contiguous; lab_t the packed labels (pack_labels, viewed as int64), (n_words, n).
+    n_perm: the relabellings of lab_t that count (default: those of out_t, else all 64 * n_words bits).  out_t
+    (n_mat, 3, n_perm) float64, n1_t (n_perm) int32 and work_t (at least _lib.pt_work_doubles(n_mat, n, n_perm) float64) are
+    made when absent; with all three given nothing is allocated.  Returns (out_t, n1_t)."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert D_t.is_cuda and D_t.dtype == torch.float64 and D_t.is_contiguous()
+    assert lab_t.is_cuda and lab_t.dtype == torch.int64 and lab_t.is_contiguous() and lab_t.dim() == 2
+    n_words, n = (int(x) for x in lab_t.shape)
+    n_mat, ld = _perm_shape(tuple(D_t.shape), n)
+    if n_perm is None:
+        n_perm = int(out_t.shape[-1]) if out_t is not None else 64 * n_words
+    n_perm = int(n_perm)
+    assert _lib.pt_words(max(n_perm, 1)) <= n_words, "lab_t has fewer words than n_perm needs"
+    dev = D_t.device
+    if out_t is None:
+        out_t = torch.empty((n_mat, 3, max(n_perm, 0)), dtype=torch.float64, device=dev)
+    if n1_t is None:
+        n1_t = torch.empty(max(n_perm, 0), dtype=torch.int32, device=dev)
+    need = _lib.pt_work_doubles(n_mat, n, max(n_perm, 0))
+    if work_t is None:
+        work_t = torch.empty(max(need, 1), dtype=torch.float64, device=dev)
+    assert out_t.is_contiguous() and out_t.dtype == torch.float64 and out_t.numel() >= n_mat * 3 * n_perm
+    assert n1_t.is_contiguous() and n1_t.dtype == torch.int32 and n1_t.numel() >= n_perm
+    assert work_t.is_contiguous() and work_t.dtype == torch.float64
+    # the kernel takes the words of relabelling group g at lab + g * n: a lab_t with more words than n_perm needs is fine
+    ctx.check(ctx.lib.tda_perm_sums_batch_dev(ctx.h, _tp(D_t), n_mat, n, ld, _tp(lab_t), n_perm, _tp(work_t),
+                                              int(work_t.numel()), _tp(out_t), _tp(n1_t), _stream()))
+    return out_t, n1_t
 
 
 def tau_dev(win_t, max_lag=None, tau_t=None, ctx=None):

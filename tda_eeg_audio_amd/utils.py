@@ -9,8 +9,10 @@ the same calls into one launch per stage (see class batch); for throughput use t
 which keep whole batches resident in HBM.
 
 Not provided here (host-side preparation in front of the path):
-load_audio, compute_envelope, bandpass_filter, resample_audio (utils.py:47-79) and
-permute_labels_by_subject (utils.py:198-215, statistics).
+load_audio, compute_envelope, bandpass_filter, resample_audio (utils.py:47-79).
+
+Beyond the reference: permute_labels_by_subject (utils.py:198-215) feeds subject_permutations and
+two_sample_permutation_test, the permutation test of Robinson and Turner on distance / Gram matrices between recordings.
 """
 import numpy as np
 
@@ -476,6 +478,140 @@ def persistence_fisher_gram(dgms, sigma=1.0, t=1.0):
     """(n, n) Gram matrix exp(-t * D) of the persistence Fisher kernel over a list of diagrams, D as
     persistence_fisher_distances gives it: symmetric as bytes, ready for SVC(kernel="precomputed")."""
     return np.exp(-t * persistence_fisher_distances(dgms, sigma))
+
+
+# --------------------------------------------------------------------------------------------
+# two-sample permutation test on distance / Gram matrices between recordings
+# --------------------------------------------------------------------------------------------
+def permute_labels_by_subject(y, subjects, rng):
+    """scripts/utils.py:198-215: one draw of a subject-level relabelling.  Every subject carries the label of its first
+    recording; rng.permutation shuffles those labels over the sorted unique subjects, and every recording takes its
+    subject's new label.  One call of rng.permutation per draw, on an array of one label per subject in np.unique order, so
+    the stream of a Generator is consumed exactly as by the reference's function."""
+    y = np.asarray(y)
+    _, first, inverse = np.unique(np.asarray(subjects), return_index=True, return_inverse=True)
+    return rng.permutation(y[first])[inverse.reshape(-1)].astype(y.dtype, copy=False)
+
+
+def subject_permutations(y, subjects=None, n_permutations=10000, seed=42):
+    """(n_permutations + 1, n) uint8 labellings for two_sample_permutation_test: row 0 is y, row k the k-th draw of
+    permute_labels_by_subject(y, subjects, rng) from ONE rng = default_rng(seed) (rng.permutation(y) when subjects is
+    None).  y must hold 0 / 1."""
+    y = np.asarray(y)
+    assert y.ndim == 1 and ((y == 0) | (y == 1)).all(), "y must be a vector of 0 / 1 labels"
+    rng = np.random.default_rng(seed)
+    out = np.empty((int(n_permutations) + 1, y.shape[0]), np.uint8)
+    out[0] = y
+    if subjects is None:
+        for k in range(1, out.shape[0]):
+            out[k] = rng.permutation(y)
+        return out
+    _, first, inverse = np.unique(np.asarray(subjects), return_index=True, return_inverse=True)
+    per_subject, inverse = y[first], inverse.reshape(-1)
+    for k in range(1, out.shape[0]):
+        out[k] = rng.permutation(per_subject)[inverse]
+    return out
+
+
+TWO_SAMPLE_STATISTICS = {"joint_loss": -1, "energy": 1, "mmd": 1}      # the side of the null that counts as extreme
+
+
+def two_sample_statistic(sums, n1, n, statistic):
+    """The statistic of a two-sample test from the sums of engine.permutation_sums_batch: sums (..., 3, P) = S00, S11, S01,
+    n1 (P,) the items labelled 1, n the items in all; returns (..., P).  With n0 = n - n1, a = S00 / (n0 (n0 - 1)),
+    b = S11 / (n1 (n1 - 1)), c = S01 / (n0 n1), each one float64 division by an exact integer product:
+      "joint_loss"  a + b            the joint loss of Robinson and Turner (2017), half the mean within-group distance of
+                                     each group, added; SMALL means separated
+      "mmd"         (2a + 2b) - 2c   the unbiased MMD^2 of a Gram matrix; LARGE means separated
+      "energy"      2c - (2a + 2b)   the energy distance of a distance matrix, the negative of "mmd" as bytes; LARGE means
+                                     separated
+    A relabelling with a group of fewer than 2 items gives NaN.  a + b is symmetric in the two groups, so a labelling and
+    its complement give the same bytes."""
+    if statistic not in TWO_SAMPLE_STATISTICS:
+        raise ValueError(f"Unknown statistic: {statistic!r}")
+    s = np.asarray(sums, dtype=np.float64)
+    n1 = np.asarray(n1).astype(np.int64)
+    n0 = int(n) - n1
+    ok = (n0 >= 2) & (n1 >= 2)
+    d0 = np.where(ok, n0 * (n0 - 1), 1).astype(np.float64)
+    d1 = np.where(ok, n1 * (n1 - 1), 1).astype(np.float64)
+    d01 = np.where(ok, n0 * n1, 1).astype(np.float64)
+    a, b, c = s[..., 0, :] / d0, s[..., 1, :] / d1, s[..., 2, :] / d01
+    with np.errstate(invalid="ignore"):
+        if statistic == "joint_loss":
+            t = a + b
+        elif statistic == "mmd":
+            t = (2.0 * a + 2.0 * b) - 2.0 * c
+        else:
+            t = 2.0 * c - (2.0 * a + 2.0 * b)
+    return np.where(ok, t, np.nan)
+
+
+def permutation_p_values(stat, finite, statistic):
+    """p and p_family of two_sample_permutation_test from stat (n_mat, P + 1), column 0 the observed labelling, and finite
+    (n_mat,) bool (see there)."""
+    sign = TWO_SAMPLE_STATISTICS[statistic]
+    n_mat, cols = stat.shape
+    with np.errstate(invalid="ignore", divide="ignore"):
+        e = sign * stat                                                    # large = extreme (exact: a sign flip)
+        p = (1 + (e[:, 1:] >= e[:, :1]).sum(axis=1)) / cols
+        p = np.where(finite & ~np.isnan(stat[:, 0]), p, np.nan)
+        # (row by row: the mean and standard deviation of a matrix are those of its own contiguous vector of null values)
+        null = [np.ascontiguousarray(e[m, 1:]) for m in range(n_mat)]
+        mu = np.array([v.mean() if cols > 1 else np.nan for v in null]).reshape(n_mat, 1)
+        sd = np.array([v.std() if cols > 1 else np.nan for v in null]).reshape(n_mat, 1)
+        z = (e - mu) / sd
+        use = finite & np.isfinite(mu[:, 0]) & (sd[:, 0] > 0)
+        zmax = np.full(cols, -np.inf)
+        for m in np.flatnonzero(use):
+            zmax = np.fmax(zmax, z[m])
+        pf = np.array([(1 + (zmax[1:] >= z[m, 0]).sum()) / cols if use[m] and not np.isnan(z[m, 0]) else np.nan
+                       for m in range(n_mat)], dtype=np.float64)
+    return p, pf
+
+
+def two_sample_permutation_test(D, y, subjects=None, n_permutations=10000, statistic="joint_loss", seed=42, labels=None,
+                                ctx=None):
+    """The two-sample permutation test of Robinson and Turner (2017) on distance matrices between diagrams (statistic
+    "joint_loss", or "energy"), and its kernel twin on Gram matrices ("mmd"): is group y == 1 different from group y == 0?
+    D: (n_mat, n, n) or one (n, n) matrix, a numpy array or a float64 torch tensor on the GPU (it stays there); only its
+    upper triangle is read.  The relabellings are subject_permutations(y, subjects, n_permutations, seed), or `labels`
+    ((n_permutations + 1, n) of 0 / 1, row 0 the observed labelling) when given.  The sums of every (matrix, relabelling)
+    come from ONE call of the HIP kernel (include/tdaeeg.h, "Two-sample permutation sums"), so every number below is a
+    fixed function of the inputs.  Returns a dict:
+      observed (n_mat,)            the statistic under y
+      null (n_mat, n_permutations) under the relabellings
+      p (n_mat,)                   (1 + #{k: null[m, k] at least as extreme as observed[m]}) / (n_permutations + 1); ties count
+                                   as extreme, the convention of drivers.comparison_summary; a NaN null value (a relabelling
+                                   with a group below 2 items) is never extreme
+      p_family (n_mat,)            the max-statistic correction for testing the n_mat matrices at once.  With e = the
+                                   statistic signed so that large is extreme, mu_m and sd_m the mean and the (population)
+                                   standard deviation of matrix m's null values, z[m, k] = (e[m, k] - mu_m) / sd_m for the
+                                   observed labelling (k = 0) and every relabelling, and zmax[k] = max over m of z[m, k]:
+                                   p_family[m] = (1 + #{k >= 1: zmax[k] >= z[m, 0]}) / (n_permutations + 1).  Matrices with
+                                   p = NaN, a NaN null value or sd_m = 0 take no part and get NaN.  For n_mat = 1 it is p (z is monotone in e).
+      n1 (n_permutations + 1,)     items labelled 1 under every relabelling
+    A matrix with a non-finite value in its upper triangle has p = p_family = NaN (its observed sums show it: every pair is
+    in one of them)."""
+    if statistic not in TWO_SAMPLE_STATISTICS:
+        raise ValueError(f"Unknown statistic: {statistic!r}")
+    lab = subject_permutations(y, subjects, n_permutations, seed) if labels is None else np.asarray(labels)
+    assert lab.ndim == 2 and lab.shape[0] >= 1, "labels must be (n_permutations + 1, n)"
+    n = lab.shape[1]
+    if not getattr(D, "is_cuda", False):
+        d = np.asarray(D, dtype=np.float64)
+        sums, n1 = engine.permutation_sums_batch(d[None] if d.ndim == 2 else d, lab, ctx=ctx)
+    else:
+        import torch
+        packed = torch.from_numpy(engine.pack_labels(lab).view(np.int64)).to(D.device)
+        d = D if D.is_contiguous() else D.contiguous()
+        out_t, n1_t = engine.permutation_sums_dev(d, packed, n_perm=lab.shape[0], ctx=ctx)
+        sums, n1 = out_t.cpu().numpy(), n1_t.cpu().numpy()
+    stat = two_sample_statistic(sums, n1, n, statistic)                   # (n_mat, P + 1)
+    finite = np.isfinite(sums[:, :, 0]).all(axis=1)
+    p, pf = permutation_p_values(stat, finite, statistic)
+    return {"observed": stat[:, 0].copy(), "null": stat[:, 1:].copy(), "p": p, "p_family": pf, "n1": n1,
+            "statistic": statistic}
 
 
 # --------------------------------------------------------------------------------------------
