@@ -108,20 +108,35 @@ def feature_names(bands=BANDS):
     return names
 
 
-def features_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
-    """dist_list: list of (k_i, n, n) arrays, one per (recording, band) group, windows already
-    selected.  One Rips launch + two feature launches + one aggregation launch for all groups.
-    Returns (len(dist_list), 44) float64."""
+def _rips_of_groups(dist_list, thresh, what):
+    """The shared opening of the *_from_distances family: the windows of every group through ONE Rips launch -- once more,
+    large enough, where a window has more H1 rows than the default capacity -- and the status check.  Returns the raw
+    diagrams (h0, c0, h1, c1) and the int32 segment table of the groups."""
     sizes = np.array([len(d) for d in dist_list])
     allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
     h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
     if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
         h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
-    check_status(st, "features_from_distances")
-    f0 = engine.features_batch(h0, c0)
-    f1 = engine.features_batch(h1, c1)
-    seg = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    return engine.aggregate_batch(f0, f1, seg)
+    check_status(st, what)
+    return h0, c0, h1, c1, np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
+
+def _upload_sets(h0, c0, h1, c1, seg):
+    """(ctx, device, (rows_t, counts_t) of H0 and then of H1, seg_t): the segment table on the device, and the two diagram
+    sets, each uploaded when the caller's loop comes to it."""
+    import torch
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    return ctx, dev, ((up(rows), up(cnt)) for rows, cnt in ((h0, c0), (h1, c1))), up(seg)
+
+
+def features_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
+    """dist_list: list of (k_i, n, n) arrays, one per (recording, band) group, windows already
+    selected.  One Rips launch + two feature launches + one aggregation launch for all groups.
+    Returns (len(dist_list), 44) float64."""
+    h0, c0, h1, c1, seg = _rips_of_groups(dist_list, thresh, "features_from_distances")
+    return engine.aggregate_batch(engine.features_batch(h0, c0), engine.features_batch(h1, c1), seg)
 
 
 def landscapes_from_distances(dist_list, grid, levels, thresh=MAX_EDGE_LENGTH):
@@ -130,20 +145,11 @@ def landscapes_from_distances(dist_list, grid, levels, thresh=MAX_EDGE_LENGTH):
     the mean persistence landscape (levels 1..levels) and the mean Betti curve (last row) over its windows on `grid`
     (include/tdaeeg.h; engine.landscape_mean_dev).  A group without a window is NaN."""
     import torch
-    sizes = np.array([len(d) for d in dist_list])
-    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
-    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
-    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
-        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
-    check_status(st, "landscapes_from_distances")
-    ctx = engine.get_ctx()
-    dev = torch.device("cuda", ctx.device)
-    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    ctx, dev, sets, seg_t = _upload_sets(*_rips_of_groups(dist_list, thresh, "landscapes_from_distances"))
     grid_t = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float64)).to(dev)
     out = torch.empty((2, len(dist_list), int(levels) + 1, grid_t.numel()), dtype=torch.float64, device=dev)
-    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
-        engine.landscape_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
-                                  grid_t, levels, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
+    for s, (rows_t, cnt_t) in enumerate(sets):
+        engine.landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
     return out.permute(1, 0, 2, 3).cpu().numpy().copy()
 
 
@@ -153,20 +159,10 @@ def frechet_means_from_distances(dist_list, thresh=MAX_EDGE_LENGTH, max_iter=32)
     their Frechet variance around it (include/tdaeeg.h; engine.frechet_mean_dev).  Returns a list over the groups of
     {"h0": (mean (k, 2), variance, iterations, status), "h1": ...}; a group without a window has an empty mean and a NaN
     variance.  status is the group's word: TDA_WIN_NOT_CONVERGED keeps its mean, any other bit has none."""
-    import torch
-    sizes = np.array([len(d) for d in dist_list])
-    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
-    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
-    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
-        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
-    check_status(st, "frechet_means_from_distances")
-    ctx = engine.get_ctx()
-    dev = torch.device("cuda", ctx.device)
-    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    ctx, _, sets, seg_t = _upload_sets(*_rips_of_groups(dist_list, thresh, "frechet_means_from_distances"))
     out = [dict() for _ in dist_list]
-    for name, rows, cnt in (("h0", h0, c0), ("h1", h1, c1)):
-        res = engine.frechet_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
-                                      seg_off_t=seg_t, max_iter=max_iter, ctx=ctx)
+    for name, (rows_t, cnt_t) in zip(("h0", "h1"), sets):
+        res = engine.frechet_mean_dev(rows_t, cnt_t, seg_off_t=seg_t, max_iter=max_iter, ctx=ctx)
         mean, mc, var, it, fst = (t.cpu().numpy() for t in res)
         for g in range(len(dist_list)):
             out[g][name] = (mean[g, :mc[g]].copy(), float(var[g]), int(it[g]), int(fst[g]))
@@ -182,20 +178,10 @@ def diagram_kernel_gram_from_distances(dist_list, kernel=("pss", 0.1), thresh=MA
     SVC(kernel="precomputed"); the row and column of a recording without a window are NaN.  TdaError for a bad kernel."""
     import torch
     par = engine.diagram_kernel_args(kernel)
-    sizes = np.array([len(d) for d in dist_list])
-    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
-    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
-    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
-        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
-    check_status(st, "diagram_kernel_gram_from_distances")
-    ctx = engine.get_ctx()
-    dev = torch.device("cuda", ctx.device)
-    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    ctx, dev, sets, seg_t = _upload_sets(*_rips_of_groups(dist_list, thresh, "diagram_kernel_gram_from_distances"))
     out = torch.empty((2, len(dist_list), len(dist_list)), dtype=torch.float64, device=dev)
-    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
-        engine.diagram_kernel_gram_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev),
-                                       torch.from_numpy(np.ascontiguousarray(cnt)).to(dev), par, seg_off_a=seg_t, out_t=out[s],
-                                       ctx=ctx)
+    for s, (rows_t, cnt_t) in enumerate(sets):
+        engine.diagram_kernel_gram_dev(rows_t, cnt_t, par, seg_off_a=seg_t, out_t=out[s], ctx=ctx)
     return out.cpu().numpy()
 
 
@@ -218,20 +204,11 @@ def images_from_distances(dist_list, xe, ye, sigma, power=1, thresh=MAX_EDGE_LEN
     engine.image_mean_dev).  A group without a window is NaN.  ValueError for bad edges, sigma or power."""
     import torch
     xe, ye, sigma, power = engine.image_args(xe, ye, sigma, power)
-    sizes = np.array([len(d) for d in dist_list])
-    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
-    h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True)
-    if (st & 1).any():                         # more H1 rows than the default capacity: once more, large enough
-        h0, c0, h1, c1, st = engine.rips_dm_batch(allw, thresh=thresh, raw=True, h1_cap=int(c1.max()))
-    check_status(st, "images_from_distances")
-    ctx = engine.get_ctx()
-    dev = torch.device("cuda", ctx.device)
-    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    ctx, dev, sets, seg_t = _upload_sets(*_rips_of_groups(dist_list, thresh, "images_from_distances"))
     xe_t, ye_t = torch.from_numpy(xe).to(dev), torch.from_numpy(ye).to(dev)
     out = torch.empty((2, len(dist_list), ye.shape[0] - 1, xe.shape[0] - 1), dtype=torch.float64, device=dev)
-    for s, (rows, cnt) in enumerate(((h0, c0), (h1, c1))):
-        engine.image_mean_dev(torch.from_numpy(np.ascontiguousarray(rows)).to(dev), torch.from_numpy(np.ascontiguousarray(cnt)).to(dev),
-                              xe_t, ye_t, sigma, power, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
+    for s, (rows_t, cnt_t) in enumerate(sets):
+        engine.image_mean_dev(rows_t, cnt_t, xe_t, ye_t, sigma, power, seg_off_t=seg_t, out_t=out[s], ctx=ctx)
     return out.permute(1, 0, 2, 3).cpu().numpy().copy()
 
 

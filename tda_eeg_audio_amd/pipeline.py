@@ -13,158 +13,51 @@ only the allocator / stream owner here.
 """
 import collections
 import functools
+import inspect
 
 import numpy as np
 
-from . import engine
+from . import _lib, engine
 
 RESULT_COLS = 4 + 44      # [w_h0, w_h1, tau, n_windows] + 44 aggregated EEG features per recording-band
-CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # Workspace(correlations=True).corr: [r, p] of the five series (cmp:104-114)
-BOTT_COLS = 2             # Workspace(bottleneck=True).bott: [b_h0, b_h1], the means of the bottleneck distances
-SLC_COLS = 2              # Workspace(sliced=dirs).slc: [s_h0, s_h1], the means of the sliced Wasserstein distances
-WQ_COLS = 2               # Workspace(wasserstein_q=(order, ground)).wq: [q_h0, q_h1], the means of that Wasserstein distance
-LAND_SETS = 3             # Workspace(landscapes=...).land: the diagram sets EEG H0, EEG H1, audio H1, in this order
-IMG_SETS = 3              # Workspace(images=...).img: the same three diagram sets, in the same order
-FM_SETS = 3               # Workspace(frechet=...).fm: the same three diagram sets, in the same order
-KD_COLS = 2               # Workspace(kernel_distance=kernel).kd: [k_h0, k_h1], the means of the kernel-induced distances
-PF_COLS = 2               # Workspace(fisher=sigma).pf: [f_h0, f_h1], the means of the persistence Fisher distances
-SL_COLS = 22              # Workspace(sublevel=True).sl: the 11 features of the audio window's sublevel-set diagram, then of the EEG channels'
-PL_COLS = 24              # Workspace(phase_locking=method).pl: the 11 features of H0, then of H1, of the PLV-distance Rips complex, then [w_h0, w_h1]
+# a group's block of each optional output (OUTPUTS, below, describes them)
+CORR_COLS = 2 * len(engine.SPEARMAN_COLS)      # corr: [r, p] of the five series (cmp:104-114)
+BOTT_COLS = 2             # bott: [b_h0, b_h1], the means of the bottleneck distances
+SLC_COLS = 2              # slc: [s_h0, s_h1], the means of the sliced Wasserstein distances
+WQ_COLS = 2               # wq: [q_h0, q_h1], the means of that Wasserstein distance
+LAND_SETS = 3             # land: the diagram sets EEG H0, EEG H1, audio H1, in this order
+IMG_SETS = 3              # img: the same three diagram sets, in the same order
+FM_SETS = 3               # fm: the same three diagram sets, in the same order
+KD_COLS = 2               # kd: [k_h0, k_h1], the means of the kernel-induced distances
+PF_COLS = 2               # pf: [f_h0, f_h1], the means of the persistence Fisher distances
+SL_COLS = 22              # sl: the 11 features of the audio window's sublevel-set diagram, then of the EEG channels'
+PL_COLS = 24              # pl: the 11 features of H0, then of H1, of the PLV-distance Rips complex, then [w_h0, w_h1]
 
 Output = collections.namedtuple("Output", "name shape params")      # a record of step_outputs
 
 
-def step_outputs(correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None, fisher=None, sublevel=False, phase_locking=None):
-    """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated params) per enabled
-    one, in the fixed order corr, bott, land, img, slc, wq, fm, kd, pf, sl, pl.  numpy only.  Workspace, the shard driver and the passes of
-    recordings.py size, slice, scatter and copy every optional output from this table; `result` is the same either way.
-      corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
-            against EEG H1 (cmp:104-114; engine.temporal_corr_dev)
-      bott  bottleneck=True: (BOTT_COLS,) np.nanmean of the bottleneck distances of the H0 / H1 diagram pairs
-            (engine.bottleneck_dev) over the windows the Wasserstein means of `result` run over -- a window whose audio
-            cloud is degenerate or too large (cmp:90-91), or whose pair has a status, counts as NaN
-      land  landscapes=(grid, levels): (LAND_SETS, levels + 1, n_grid) mean persistence landscape (levels 1..levels) and
-            mean Betti curve (last row) on the float64 grid, of the EEG H0, the EEG H1 and the audio H1 diagrams
-            (engine.landscape_mean_dev).  The EEG sets average every window of the group, as the feature aggregation does
-            (v2:429-436); the audio set leaves out the windows whose cloud is degenerate or too large; a group without
-            such a window is NaN.  ValueError unless the grid is 1-D with 1..MAX_GRID points and 1 <= levels <= MAX_LANDSCAPES
-      img   images=(xe, ye, sigma, power): (IMG_SETS, n_y, n_x) mean persistence image of the same sets, windows and audio
-            mask on the birth edges xe (n_x + 1) and persistence edges ye (n_y + 1) (engine.image_mean_dev; engine.image_args)
-      slc   sliced=dirs, (M, 2) finite directions, 1 <= M <= TDA_MAX_DIRECTIONS (engine._directions): (SLC_COLS,) np.nanmean
-            of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`
-      wq    wasserstein_q=(order, ground), order 1 or 2 and ground "l2" or "linf": (WQ_COLS,) np.nanmean of that Wasserstein
-            distance of the H0 / H1 pairs (engine.wasserstein_q_dev) under the rule of `bott`.  ValueError for anything else
-      fm    frechet=(cap, max_iter), 1 <= cap <= FM_MAX_POINTS and 1 <= max_iter <= FM_MAX_ITER: (FM_SETS, cap + 2, 2), per
-            diagram set of `land` (same windows, same audio mask) the Frechet mean of the group's diagrams in the order-2
-            Wasserstein metric (engine.frechet_mean_dev): rows 0..cap-1 the mean, NaN beyond its count; row cap
-            [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else
-      kd    kernel_distance=("pss", sigma) or ("pwg", sigma, c) (engine.diagram_kernel_args): (KD_COLS,) np.nanmean of the
-            distance that kernel on diagrams induces between the H0 / H1 pairs (engine.diagram_kernel_dev) under the rule of
-            `bott`.  ValueError for anything else
-      pf    fisher=sigma, a finite number > 0 (engine.fisher_args): (PF_COLS,) np.nanmean of the persistence Fisher distances
-            of the H0 / H1 pairs (engine.persistence_fisher_dev) under the rule of `bott`.  ValueError for anything else
-      sl    sublevel=True: (SL_COLS,) from the sublevel-set (lower-star) H0 diagrams of the signals themselves
-            (engine.sublevel_features_dev; include/tdaeeg.h).  Columns 0..10: np.nanmean over the group's windows of the 11
-            extract_features values of the audio window's diagram.  Columns 11..21: np.nanmean over the windows of the
-            np.mean over the channels of the same 11 values of the EEG channels' diagrams, one diagram per channel.  A
-            signal with a sample that is not finite counts as NaN.  Every window of the group takes part: no Rips status
-            is looked at
-      pl    phase_locking=method, one of "euclidean", "abs", "standard", "sqrt" (True: "euclidean"; the parameter kept is
-            the method number): (PL_COLS,) from the Rips diagrams of the phase-locking distance of the EEG window's channels
-            (engine.plv_dist_dev -> rips_dm_dev; include/tdaeeg.h, "Phase-locking value").  Columns 0..10: np.nanmean over
-            the group's windows of the 11 extract_features values of H0; columns 11..21: the same for H1; every window of
-            the group takes part, as for the EEG sets.  Columns 22, 23: np.nanmean of the reference's Wasserstein distance
-            (engine.wasserstein_dev) between that diagram and the audio diagram of the same window, H0 and H1, under the
-            rule of `bott`.  A window with a PLV or Rips status counts as NaN.  ValueError for anything else"""
-    from . import _lib
-    out = []
-    if correlations:
-        out.append(Output("corr", (CORR_COLS,), None))
-    if bottleneck:
-        out.append(Output("bott", (BOTT_COLS,), None))
-    if landscapes is not None:
-        grid, levels = landscapes
-        grid = np.ascontiguousarray(grid, dtype=np.float64)
-        if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID or not 1 <= int(levels) <= _lib.MAX_LANDSCAPES:
-            raise ValueError(f"landscapes=(grid, levels): a 1-D grid of 1..{_lib.MAX_GRID} points and 1..{_lib.MAX_LANDSCAPES} levels")
-        out.append(Output("land", (LAND_SETS, int(levels) + 1, grid.shape[0]), (grid, int(levels))))
-    if images is not None:
-        xe, ye, sigma, power = engine.image_args(*images)
-        out.append(Output("img", (IMG_SETS, ye.shape[0] - 1, xe.shape[0] - 1), (xe, ye, sigma, power)))
-    if sliced is not None:
-        out.append(Output("slc", (SLC_COLS,), engine._directions(sliced)))
-    if wasserstein_q is not None:
-        try:
-            order, ground = wasserstein_q
-            engine.wasserstein_q_args(order, ground)
-        except (TypeError, ValueError, _lib.TdaError):
-            raise ValueError("wasserstein_q=(order, ground): order 1 or 2, ground 'l2' or 'linf'") from None
-        out.append(Output("wq", (WQ_COLS,), (int(order), ground)))
-    if frechet is not None:
-        try:
-            cap, max_iter = frechet
-            cap, max_iter = engine.frechet_args(cap, max_iter)
-            if cap > _lib.FM_MAX_POINTS:
-                raise ValueError
-        except (TypeError, ValueError, _lib.TdaError):
-            raise ValueError(f"frechet=(cap, max_iter): integers, 1 <= cap <= {_lib.FM_MAX_POINTS}, "
-                             f"1 <= max_iter <= {_lib.FM_MAX_ITER}") from None
-        out.append(Output("fm", (FM_SETS, cap + 2, 2), (cap, max_iter)))
-    if kernel_distance is not None:
-        try:
-            engine.diagram_kernel_args(kernel_distance)
-        except _lib.TdaError:
-            raise ValueError("kernel_distance=('pss', sigma) or ('pwg', sigma, c): finite sigma, c > 0") from None
-        out.append(Output("kd", (KD_COLS,), (kernel_distance[0],) + tuple(float(v) for v in kernel_distance[1:])))
-    if fisher is not None:
-        try:
-            engine.fisher_args(fisher)
-        except _lib.TdaError:
-            raise ValueError("fisher=sigma: a finite number > 0") from None
-        out.append(Output("pf", (PF_COLS,), float(fisher)))
-    if sublevel:
-        out.append(Output("sl", (SL_COLS,), None))
-    if phase_locking is not None and phase_locking is not False:
-        out.append(Output("pl", (PL_COLS,), engine.plv_method(phase_locking)))
-    return out
+def _head(buf, n):
+    """The first n windows (or groups) of a buffer: a tensor, a tuple of tensors or an engine.DeviceDiagrams / DeviceLandmarks."""
+    if buf is None:
+        return None
+    if isinstance(buf, tuple):
+        return tuple(t[:n] for t in buf)
+    return buf.head(n) if hasattr(buf, "head") else buf[:n]
 
 
 class Workspace:
     """Pre-allocated device buffers for a batch of n_win windows grouped into recordings."""
 
-    # per window: two distances, two status words
-    PAIR_BUFFERS = ("b0", "b1", "bs0", "bs1", "s0", "s1", "ss0", "ss1", "q0", "q1", "qs0", "qs1", "f0", "f1", "fs0", "fs1",
-                    "k0", "k1", "ks0", "ks1")
-    # the buffers and resident tables of the optional outputs: None where the output is off
-    corr = corr_cols = bott = b0 = b1 = bs0 = bs1 = slc = sliced_dirs = s0 = s1 = ss0 = ss1 = None
-    land = land_sets = land_grid = img = img_sets = img_xe = img_ye = None; land_levels = 0
-    wq = wasserstein_q = q0 = q1 = qs0 = qs1 = None
-    fm = fm_sets = frechet = fm_out = None
-    kd = kernel_distance = k0 = k1 = ks0 = ks1 = None
-    pf = fisher = f0 = f1 = fs0 = fs1 = None
-    sl = sl_fa = sl_fe = sl_sa = sl_se = sl_cols = sl_scratch = None; sublevel = False
-    pl = phase_locking = pl_dist = pl_st = pl_dgm = pl_f0 = pl_f1 = pl_w0 = pl_w1 = pl_ws0 = pl_ws1 = pl_cols = pl_line = None
     lm = takens = None
+    # (the attributes of the optional outputs, None where the output is off, are set from OUTPUTS, below)
 
-    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None, takens=None, sublevel=False, sublevel_bytes=engine.SL_SCRATCH_BYTES, phase_locking=None):
-        """correlations .. fisher, sublevel, phase_locking: the optional outputs of step_outputs (`outputs` keeps the table).  run_step also fills
-        the enabled ones, the group in front: `corr` (n_seg, 10), `bott` (n_seg, 2), `land` (n_seg, 3, levels + 1, n_grid),
-        `img` (n_seg, 3, n_y, n_x), `slc` (n_seg, 2), `wq` (n_seg, 2), `fm` (n_seg, 3, cap + 2, 2), `kd` (n_seg, 2), `pf` (n_seg, 2) -- and with `bott` / `slc` / `wq` / `kd` / `pf` the distances of every
-        window, `b0` / `b1`, `s0` / `s1`, `q0` / `q1`, `k0` / `k1` and `f0` / `f1` (n_win), status words `bs0` / `bs1`, `ss0` / `ss1`,
-        `qs0` / `qs1`, `ks0` / `ks1` and `fs0` / `fs1`.
-        Grid, edges and directions are uploaded once, here.
-        sublevel=True: `sl` (n_seg, 22), and per window the features it averages, `sl_fa` (n_win, 11) of the audio window and
-        `sl_fe` (n_win, n_ch, 11) of the EEG channels (NaN where `sl_sa` / `sl_se` flag the signal).  The diagrams themselves
-        exist only chunk by chunk, in scratch of at most sublevel_bytes of rows per signal kind (engine.SublevelScratch,
-        made at the first step, when the window length is known).
-        phase_locking=method: `pl` (n_seg, 24), and per window what it averages: `pl_f0` / `pl_f1` (n_win, 11), the features
-        of the H0 / H1 diagram `pl_dgm` (an engine.DeviceDiagrams) of the phase-locking distance matrix `pl_dist`
-        (n_win, n_ch, n_ch), `pl_w0` / `pl_w1` (n_win), its Wasserstein distances to the audio diagram, with the status words
-        `pl_st` (the PLV kernel's), `pl_dgm.status` (Rips) and `pl_ws0` / `pl_ws1` (the distances').  A window flagged by the
-        PLV kernel is handed to Rips as points on a line (`pl_line`), its NaN block in `pl_dist` replaced, and counts as NaN.
+    def __init__(self, n_win, seg_off, device, n_ch=47, h1_cap=engine.DEFAULT_H1_CAP, *, takens=None,
+                 sublevel_bytes=engine.SL_SCRATCH_BYTES, **outputs):
+        """**outputs: the keywords of step_outputs, validated there (TypeError for any other keyword); `outputs` keeps its
+        table.  run_step also fills every enabled output, the group in front: `<name>` (n_seg,) + shape.  What else a
+        record of OUTPUTS allocates here -- per-window buffers, tables uploaded once -- stands in its paragraph of
+        step_outputs' docstring; its validated parameters are the attribute named like its keyword.
+        sublevel_bytes: the bound on the scratch of the `sl` output.
         takens=None: the audio stage as the reference runs it (dim 3, subsample 2, every point; at most 128 points).
         takens=(dim, subsample, n_perm): the audio stage embeds with these and runs Rips on n_perm greedy landmarks
         (engine.takens_rips_landmarks_dev), for clouds of up to LM_MAX_POINTS points; `lm` (an engine.DeviceLandmarks,
@@ -197,63 +90,21 @@ class Workspace:
         self.fe0 = torch.empty((n_win, 11), **f64); self.fe1 = torch.empty((n_win, 11), **f64)
         self.fa1 = torch.empty((n_win, 11), **f64)
         self.result = torch.empty((self.n_seg, RESULT_COLS), **f64)
-        self.outputs = step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
-                                    fisher, sublevel, phase_locking)
-        par = {o.name: o.params for o in self.outputs}
-        self.bottleneck, self.sliced, self.landscapes, self.images = "bott" in par, par.get("slc"), par.get("land"), par.get("img")
-        self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
-        self.fisher = par.get("pf")
-        self.sublevel, self.sublevel_bytes, self.n_ch = "sl" in par, int(sublevel_bytes), n_ch
+        self.outputs = step_outputs(**outputs)
+        self.sublevel_bytes, self.n_ch = int(sublevel_bytes), n_ch
         for o in self.outputs:
+            spec = OUTPUT_BY_NAME[o.name]
+            setattr(self, spec.keyword, True if o.params is None else o.params)
             if len(o.shape) == 1:
                 setattr(self, o.name, torch.empty((self.n_seg,) + o.shape, **f64))
             else:
-                # a block per diagram set: stored set-major, one contiguous (n_seg, ...) block per launch (land_sets,
-                # img_sets); `land` / `img` are the same memory seen group-major
+                # a block per diagram set: stored set-major, one contiguous (n_seg, ...) block per launch (<name>_sets);
+                # `<name>` is the same memory seen group-major
                 sets = torch.empty((o.shape[0], self.n_seg) + o.shape[1:], **f64)
                 setattr(self, o.name + "_sets", sets)
                 setattr(self, o.name, sets.permute(1, 0, 2, 3))
-        # the tables of the enabled outputs, uploaded once, and the per-window buffers of the two pair distances
-        pair = (torch.float64, torch.float64, torch.int32, torch.int32)
-        if "corr" in par:
-            self.corr_cols = torch.tensor(engine.SPEARMAN_COLS, dtype=torch.int32, device=device)
-        if self.bottleneck:
-            self.b0, self.b1, self.bs0, self.bs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
-        if self.sliced is not None:
-            self.sliced_dirs = torch.from_numpy(self.sliced).to(device)
-            self.s0, self.s1, self.ss0, self.ss1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
-        if self.wasserstein_q is not None:
-            self.q0, self.q1, self.qs0, self.qs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
-        if self.kernel_distance is not None:
-            self.k0, self.k1, self.ks0, self.ks1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
-        if self.fisher is not None:
-            self.f0, self.f1, self.fs0, self.fs1 = (torch.empty(n_win, dtype=dt, device=device) for dt in pair)
-        if self.sublevel:
-            i32 = dict(dtype=torch.int32, device=device)
-            self.sl_fa, self.sl_fe = torch.empty((n_win, 1, 11), **f64), torch.empty((n_win, n_ch, 11), **f64)
-            self.sl_sa, self.sl_se = torch.empty((n_win, 1), **i32), torch.empty((n_win, n_ch), **i32)
-            self.sl_cols = torch.empty(SL_COLS * n_win, **f64)       # the 22 per-window series, one contiguous row each
-            self.sl_scratch, self.sl_n_win = {}, n_win               # (n_ch, n_t) -> engine.SublevelScratch, shared by views
-        if "pl" in par:
-            i32 = dict(dtype=torch.int32, device=device)
-            self.phase_locking = par["pl"]
-            self.pl_dist = torch.empty((n_win, n_ch, n_ch), **f64)
-            self.pl_dgm = engine.DeviceDiagrams(n_win, n_ch, h1_cap, device)
-            self.pl_f0, self.pl_f1 = torch.empty((n_win, 11), **f64), torch.empty((n_win, 11), **f64)
-            self.pl_w0, self.pl_w1 = torch.empty(n_win, **f64), torch.empty(n_win, **f64)
-            self.pl_st, self.pl_ws0, self.pl_ws1 = (torch.empty(n_win, **i32) for _ in range(3))
-            self.pl_cols = torch.empty(PL_COLS * n_win, **f64)       # the 24 per-window series, one contiguous row each
-            k = torch.arange(n_ch, **f64)
-            self.pl_line = (k[:, None] - k[None, :]).abs() / n_ch    # what Rips gets for a window the PLV kernel flagged
-        if self.frechet is not None:
-            # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
-            i32 = dict(dtype=torch.int32, device=device)
-            self.fm_out = (torch.empty((self.n_seg, self.frechet[0], 2), **f64), torch.empty(self.n_seg, **i32),
-                           torch.empty(self.n_seg, **f64), torch.empty(self.n_seg, **i32), torch.empty(self.n_seg, **i32))
-        if self.landscapes is not None:
-            self.land_grid, self.land_levels = torch.from_numpy(self.landscapes[0]).to(device), self.landscapes[1]
-        if self.images is not None:
-            self.img_xe, self.img_ye = (torch.from_numpy(e).to(device) for e in self.images[:2])
+            for attr, make in {**spec.per_window, **spec.per_group, **spec.tables}.items():
+                setattr(self, attr, make(self))             # its further buffers, and its tables, uploaded once
         self.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(device)
         self.side_stream = torch.cuda.Stream(device=device)
         import os
@@ -283,16 +134,12 @@ class Workspace:
         v.rec_id = torch.from_numpy(np.repeat(np.arange(n_seg), np.diff(seg_off)).astype(np.int64)).to(self.device)
         v.first_idx = torch.from_numpy(seg_off[:-1].astype(np.int64)).to(self.device)
         v.n_win_seg = torch.from_numpy(np.diff(seg_off).astype(np.float64)).to(self.device)
-        v.eeg, v.aud = self.eeg.head(n_win), self.aud.head(n_win)
-        v.lm = None if self.lm is None else self.lm.head(n_win)
-        v.pl_dgm = None if self.pl_dgm is None else self.pl_dgm.head(n_win)
-        for name in ("tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist", "sl_fa", "sl_fe", "sl_sa", "sl_se",
-                     "pl_dist", "pl_st", "pl_f0", "pl_f1", "pl_w0", "pl_w1", "pl_ws0", "pl_ws1") \
-                + self.PAIR_BUFFERS:
-            buf = getattr(self, name)
-            setattr(v, name, None if buf is None else buf[:n_win])
-        for name in ("tau_seg", "seg_flags", "flags_host", "result"):
-            setattr(v, name, getattr(self, name)[:n_seg])
+        on = [OUTPUT_BY_NAME[o.name] for o in self.outputs]
+        for name in ["eeg", "aud", "lm", "tau_win", "w0", "w1", "ws0", "ws1", "fe0", "fe1", "fa1", "dist",
+                     *(a for spec in on for a in spec.per_window)]:
+            setattr(v, name, _head(getattr(self, name), n_win))
+        for name in ["tau_seg", "seg_flags", "flags_host", "result", *(a for spec in on for a in spec.per_group)]:
+            setattr(v, name, _head(getattr(self, name), n_seg))
         for o in self.outputs:
             if len(o.shape) == 1:
                 setattr(v, o.name, getattr(self, o.name)[:n_seg])
@@ -300,8 +147,6 @@ class Workspace:
                 sets = getattr(self, o.name + "_sets")[:, :n_seg]
                 setattr(v, o.name + "_sets", sets)
                 setattr(v, o.name, sets.permute(1, 0, 2, 3))
-        if self.fm_out is not None:
-            v.fm_out = tuple(t[:n_seg] for t in self.fm_out)
         return v
 
 
@@ -320,7 +165,6 @@ def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="
     left are copied to ws.flags_host (pinned) at the end of the step and the caller re-runs the step with
     retry="auto" if any is set (pipeline.Lanes does: verify, then publish)."""
     import torch
-    from . import _lib
     ctx = ctx or _lib.get_ctx()
     with ctx.deferred(retry):                    # one finishing pass for the three diagram sets of the batch
         return _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding, eeg_table)
@@ -328,7 +172,6 @@ def run_step(eeg_win, audio_win, ws, ctx=None, max_lag=125, timers=None, retry="
 
 def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=None, eeg_table=None):
     import torch
-    from . import _lib
 
     def stage(name, fn):
         if timers is None or name not in timers:
@@ -376,52 +219,17 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     stage("finish", lambda: engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0),
                                                         (ws.eeg.h1, ws.eeg.c1, True, ws.fe1),
                                                         (ws.aud.h1, ws.aud.c1, True, ws.fa1)], ctx=ctx))
-    if ws.corr is not None:
-        # temporal correlation of the H1 feature series over the windows that reach the distances (cmp:90-91,104-114)
-        stage("temporal_corr", lambda: engine.temporal_corr_dev(ws.fa1, ws.fe1, ws.seg_off, ws.aud.status, cols=ws.corr_cols,
-                                                                out_t=ws.corr, ctx=ctx))
-    if ws.land is not None:
-        stage("landscape", lambda: _landscape_stage(ws, ctx, audio=True))
-    if ws.img is not None:
-        stage("image", lambda: _image_stage(ws, ctx, audio=True))
-
-    stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
-                                                           out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
-    stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
-                                                           out_t=ws.w1, status_t=ws.ws1, ctx=ctx))
-
-    def pair_means(name, launch, d, ds, means):
-        """Stages name_h0 / name_h1: the H0 and the H1 diagram pairs of every window through `launch` (d[k], status ds[k]);
-        then means[:, k], the means of recording_rows_dev's windows: masked on the device, one nanmean launch per leg."""
-        legs = ((ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0), (ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1))
-        for k, leg in enumerate(legs):
-            stage(f"{name}_h{k}", lambda: launch(*leg, out_t=d[k], status_t=ds[k], ctx=ctx))
-        out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
-        nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
-        for k in range(2):
-            seg_mean = engine.segment_nanmean_dev(torch.where(out | (ds[k] != 0), nan, d[k]), ws.seg_off, ctx=ctx)
-            means[:, k].copy_(seg_mean)
-    if ws.bottleneck:
-        pair_means("bottleneck", engine.bottleneck_dev, (ws.b0, ws.b1), (ws.bs0, ws.bs1), ws.bott)
-    if ws.sliced is not None:
-        pair_means("sliced", functools.partial(engine.sliced_wasserstein_dev, dirs_t=ws.sliced_dirs), (ws.s0, ws.s1),
-                   (ws.ss0, ws.ss1), ws.slc)
-    if ws.wasserstein_q is not None:
-        order, ground = ws.wasserstein_q
-        pair_means("wasserstein_q", functools.partial(engine.wasserstein_q_dev, order=order, ground=ground), (ws.q0, ws.q1),
-                   (ws.qs0, ws.qs1), ws.wq)
-    if ws.kernel_distance is not None:
-        pair_means("kernel_distance", functools.partial(engine.diagram_kernel_dev, kernel=ws.kernel_distance), (ws.k0, ws.k1),
-                   (ws.ks0, ws.ks1), ws.kd)
-    if ws.fisher is not None:
-        pair_means("fisher", functools.partial(engine.persistence_fisher_dev, sigma=ws.fisher), (ws.f0, ws.f1),
-                   (ws.fs0, ws.fs1), ws.pf)
-    if ws.fm is not None:
-        stage("frechet", lambda: _frechet_stage(ws, ctx, audio=True))
-    if ws.sublevel:
-        stage("sublevel", lambda: _sublevel_stage(ws, ctx, eeg_win, audio_win, eeg_sliding, eeg_table))
-    if ws.pl is not None:
-        stage("phase_locking", lambda: _phase_locking_stage(ws, ctx, eeg_win, eeg_sliding, eeg_table))
+    # the optional outputs that are on, in LAUNCH_ORDER around the two Wasserstein stages of `result`
+    on = {o.name for o in ws.outputs}
+    inputs = (eeg_win, audio_win, eeg_sliding, eeg_table)
+    for name in LAUNCH_ORDER:
+        if name is None:
+            stage("wasserstein_h0", lambda: engine.wasserstein_dev(ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0,
+                                                                   out_t=ws.w0, status_t=ws.ws0, ctx=ctx))
+            stage("wasserstein_h1", lambda: engine.wasserstein_dev(ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1,
+                                                                   out_t=ws.w1, status_t=ws.ws1, ctx=ctx))
+        elif name in on:
+            OUTPUT_BY_NAME[name].launch(ws, ctx, stage, inputs)
     # per recording-band rows: nanmean of the distances (cmp:117-118), tau, window count, mean/std of the EEG
     # features (v2:429-436) -- one launch
     stage("reduce", lambda: engine.recording_rows_dev(ws.w0, ws.w1, ws.tau_seg, ws.fe0, ws.fe1, ws.seg_off, ws.result,
@@ -431,27 +239,28 @@ def _run_step(eeg_win, audio_win, ws, ctx, max_lag, timers, retry, eeg_sliding=N
     return ws.result
 
 
+def pair_means(ws, ctx, stage, name, launch, d, ds, means):
+    """Stages name_h0 / name_h1: the H0 and the H1 diagram pairs of every window through `launch` (d[k], status ds[k]);
+    then means[:, k], the means of recording_rows_dev's windows: masked on the device, one nanmean launch per leg."""
+    import torch
+    legs = ((ws.eeg.h0, ws.eeg.c0, ws.aud.h0, ws.aud.c0), (ws.eeg.h1, ws.eeg.c1, ws.aud.h1, ws.aud.c1))
+    for k, leg in enumerate(legs):
+        stage(f"{name}_h{k}", lambda: launch(*leg, out_t=d[k], status_t=ds[k], ctx=ctx))
+    out = (ws.aud.status & (_lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE)) != 0
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=ws.device)
+    for k in range(2):
+        seg_mean = engine.segment_nanmean_dev(torch.where(out | (ds[k] != 0), nan, d[k]), ws.seg_off, ctx=ctx)
+        means[:, k].copy_(seg_mean)
+
+
 def _set_means_stage(ws, ctx, audio, launch, out_sets):
     """One launch per diagram set, EEG H0, EEG H1 and (audio=True) audio H1, each writing only the group means of its set,
-    out_sets[s]; launch: engine.landscape_mean_dev or engine.image_mean_dev with the output's own parameters bound."""
-    from . import _lib
+    out_sets[s]; launch: the engine's launcher with the output's own parameters bound."""
     sets = [(ws.eeg.h0, ws.eeg.c0, None, 0), (ws.eeg.h1, ws.eeg.c1, None, 0)]
     if audio:
         sets.append((ws.aud.h1, ws.aud.c1, ws.aud.status, _lib.TDA_WIN_DEGENERATE | _lib.TDA_WIN_TOO_LARGE))
     for s, (rows, cnt, status, mask) in enumerate(sets):
         launch(rows, cnt, seg_off_t=ws.seg_off, status_t=status, skip_mask=mask, out_t=out_sets[s], ctx=ctx)
-
-
-def _landscape_stage(ws, ctx, audio):
-    """ws.land of the step, (n_seg, levels + 1, n_grid) per set."""
-    _set_means_stage(ws, ctx, audio, functools.partial(engine.landscape_mean_dev, grid_t=ws.land_grid, levels=ws.land_levels),
-                     ws.land_sets)
-
-
-def _image_stage(ws, ctx, audio):
-    """ws.img of the step, (n_seg, n_y, n_x) per set."""
-    _set_means_stage(ws, ctx, audio, functools.partial(engine.image_mean_dev, xe_t=ws.img_xe, ye_t=ws.img_ye,
-                                                       sigma=ws.images[2], power=ws.images[3]), ws.img_sets)
 
 
 def _eeg_window_table(ws, eeg_win, eeg_sliding, eeg_table):
@@ -482,7 +291,6 @@ def _phase_locking_stage(ws, ctx, eeg_win, eeg_sliding, eeg_table):
     audio diagrams, then the 24 group means.  The Rips call runs its whole ladder whatever the step's retry policy (the
     policy is put back afterwards): it is exact by itself, so no class-overflow bit of it has to travel to the host."""
     import torch
-    from . import _lib
     n_win = ws.n_win
     sig_t, tab, _ = _eeg_window_table(ws, eeg_win, eeg_sliding, eeg_table)
     engine.plv_dist_dev(sig_t, method=engine.METHOD_NAMES[ws.phase_locking], out=ws.pl_dist, status_t=ws.pl_st, ctx=ctx, **tab)
@@ -547,6 +355,247 @@ def _frechet_stage(ws, ctx, audio):
         out_t[:, cap, 0] = mc; out_t[:, cap, 1] = var
         out_t[:, cap + 1, 0] = it; out_t[:, cap + 1, 1] = st
     _set_means_stage(ws, ctx, audio, launch, ws.fm_sets)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the optional outputs: one record each.  What is particular to an output stands in its record and in the functions the
+# record names, nowhere else: Workspace, run_step, run_features_step and the passes of recordings.py go through OUTPUTS
+# ------------------------------------------------------------------------------------------------------------
+# A record of OUTPUTS:
+#   name, keyword  the Workspace attribute of its block (n_seg,) + shape, and the keyword that turns it on; the Workspace
+#                  attribute named like the keyword keeps the validated parameters (True if it has none), `off` otherwise
+#   doc, validate(v)   its paragraph of step_outputs' docstring; for v other than None: None if v leaves it off, else
+#                  (shape of a group's block, validated parameters)
+#   stages, launch(ws, ctx, stage, inputs)   its part of run_step, timed under these names by stage(name, fn); inputs =
+#                  (eeg_win, audio_win, eeg_sliding, eeg_table).  Parameters and tables are read from `ws` at step time
+#   set_stage(ws, ctx, audio)   of a set mean: its launches; run_features_step runs it with audio=False (the EEG sets alone)
+#   arg(params)    a value of the keyword that validates to these parameters again (recordings.py hands it to Workspace)
+#   per_window, per_group, tables   {attribute: make(ws)} of what else it owns in a Workspace, None while it is off: buffers
+#                  with a row per window, tuples of buffers with a row per group (Workspace.view slices both), and tables,
+#                  parameters and scratch that views share
+OutputSpec = collections.namedtuple(
+    "OutputSpec", "name keyword doc validate stages launch off set_stage arg per_window per_group tables",
+    defaults=(None, None, lambda params: True if params is None else params, {}, {}, {}))
+
+
+def _empty(dtype, ws, *shape):
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=ws.device)
+
+
+_f64, _i32 = functools.partial(_empty, "float64"), functools.partial(_empty, "int32")
+
+
+def _dev(ws, array):
+    import torch
+    return torch.from_numpy(array).to(ws.device)
+
+
+def _switch(*shape):
+    """validate of an output without parameters."""
+    return lambda value: (shape, None) if value else None
+
+
+def _pair_distance(name, keyword, doc, validate, prefix, stage_name, launcher, extra=lambda ws: {}, **more):
+    """A distance between the H0 / H1 diagram pairs of every window and its group means (pair_means): the engine's
+    `launcher` with the further keywords extra(ws); per window the distances <prefix>0 / <prefix>1 and their status words
+    <prefix>s0 / <prefix>s1."""
+    d, ds = (prefix + "0", prefix + "1"), (prefix + "s0", prefix + "s1")
+
+    def launch(ws, ctx, stage, inputs):
+        pair_means(ws, ctx, stage, stage_name, functools.partial(launcher, **extra(ws)), [getattr(ws, a) for a in d],
+                   [getattr(ws, a) for a in ds], getattr(ws, name))
+    doc += f".\n            Workspace: the distances of every window `{d[0]}` / `{d[1]}` (n_win), status words `{ds[0]}` / `{ds[1]}`"
+    per_window = {**{a: lambda ws: _f64(ws, ws.n_win) for a in d}, **{a: lambda ws: _i32(ws, ws.n_win) for a in ds}}
+    return OutputSpec(name, keyword, doc, validate, (stage_name + "_h0", stage_name + "_h1"), launch, per_window=per_window,
+                      **more)
+
+
+def _set_means(name, keyword, doc, validate, stage_name, launcher=None, extra=None, set_stage=None, **more):
+    """Group means over the three diagram sets, the EEG sets alone in run_features_step: set_stage(ws, ctx, audio), by
+    default _set_means_stage with the engine's `launcher` and the further keywords extra(ws)."""
+    if set_stage is None:
+        def set_stage(ws, ctx, audio):
+            _set_means_stage(ws, ctx, audio, functools.partial(launcher, **extra(ws)), getattr(ws, name + "_sets"))
+    return OutputSpec(name, keyword, doc, validate, (stage_name,),
+                      lambda ws, ctx, stage, inputs: stage(stage_name, lambda: set_stage(ws, ctx, audio=True)),
+                      set_stage=set_stage, **more)
+
+
+def _landscapes(value):
+    grid, levels = value
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID or not 1 <= int(levels) <= _lib.MAX_LANDSCAPES:
+        raise ValueError(f"landscapes=(grid, levels): a 1-D grid of 1..{_lib.MAX_GRID} points and 1..{_lib.MAX_LANDSCAPES} levels")
+    return (LAND_SETS, int(levels) + 1, grid.shape[0]), (grid, int(levels))
+
+
+def _images(value):
+    xe, ye, sigma, power = engine.image_args(*value)
+    return (IMG_SETS, ye.shape[0] - 1, xe.shape[0] - 1), (xe, ye, sigma, power)
+
+
+def _frechet(value):
+    try:
+        cap, max_iter = value
+        cap, max_iter = engine.frechet_args(cap, max_iter)
+        if cap > _lib.FM_MAX_POINTS:
+            raise ValueError
+    except (TypeError, ValueError, _lib.TdaError):
+        raise ValueError(f"frechet=(cap, max_iter): integers, 1 <= cap <= {_lib.FM_MAX_POINTS}, "
+                         f"1 <= max_iter <= {_lib.FM_MAX_ITER}") from None
+    return (FM_SETS, cap + 2, 2), (cap, max_iter)
+
+
+def _engine_checked(check, message, shape, params, catch=_lib.TdaError):
+    """validate through an argument check of the engine: what it raises of `catch` becomes ValueError(message)."""
+    def validate(value):
+        try:
+            check(value)
+        except catch:
+            raise ValueError(message) from None
+        return shape, params(value)
+    return validate
+
+
+OUTPUTS = [
+    OutputSpec("corr", "correlations", """\
+      corr  correlations=True: (CORR_COLS,) Spearman [r, p] of the five feature series of engine.SPEARMAN_COLS, audio H1
+            against EEG H1 (cmp:104-114; engine.temporal_corr_dev)""",
+               _switch(CORR_COLS), ("temporal_corr",),
+               # over the windows that reach the distances (cmp:90-91,104-114)
+               lambda ws, ctx, stage, inputs: stage("temporal_corr", lambda: engine.temporal_corr_dev(
+                   ws.fa1, ws.fe1, ws.seg_off, ws.aud.status, cols=ws.corr_cols, out_t=ws.corr, ctx=ctx)), off=False,
+               tables=dict(corr_cols=lambda ws: _dev(ws, np.array(engine.SPEARMAN_COLS, np.int32)))),
+    _pair_distance("bott", "bottleneck", """\
+      bott  bottleneck=True: (BOTT_COLS,) np.nanmean of the bottleneck distances of the H0 / H1 diagram pairs
+            (engine.bottleneck_dev) over the windows the Wasserstein means of `result` run over -- a window whose audio
+            cloud is degenerate or too large (cmp:90-91), or whose pair has a status, counts as NaN""",
+                   _switch(BOTT_COLS), "b", "bottleneck", engine.bottleneck_dev, off=False),
+    _set_means("land", "landscapes", """\
+      land  landscapes=(grid, levels): (LAND_SETS, levels + 1, n_grid) mean persistence landscape (levels 1..levels) and
+            mean Betti curve (last row) on the float64 grid, of the EEG H0, the EEG H1 and the audio H1 diagrams
+            (engine.landscape_mean_dev).  The EEG sets average every window of the group, as the feature aggregation does
+            (v2:429-436); the audio set leaves out the windows whose cloud is degenerate or too large; a group without
+            such a window is NaN.  ValueError unless the grid is 1-D with 1..MAX_GRID points and 1 <= levels <= MAX_LANDSCAPES""",
+               _landscapes, "landscape", engine.landscape_mean_dev, lambda ws: dict(grid_t=ws.land_grid, levels=ws.land_levels),
+               tables=dict(land_grid=lambda ws: _dev(ws, ws.landscapes[0]), land_levels=lambda ws: ws.landscapes[1])),
+    _set_means("img", "images", """\
+      img   images=(xe, ye, sigma, power): (IMG_SETS, n_y, n_x) mean persistence image of the same sets, windows and audio
+            mask on the birth edges xe (n_x + 1) and persistence edges ye (n_y + 1) (engine.image_mean_dev; engine.image_args)""",
+               _images, "image", engine.image_mean_dev,
+               lambda ws: dict(xe_t=ws.img_xe, ye_t=ws.img_ye, sigma=ws.images[2], power=ws.images[3]),
+               tables=dict(img_xe=lambda ws: _dev(ws, ws.images[0]), img_ye=lambda ws: _dev(ws, ws.images[1]))),
+    _pair_distance("slc", "sliced", """\
+      slc   sliced=dirs, (M, 2) finite directions, 1 <= M <= TDA_MAX_DIRECTIONS (engine._directions): (SLC_COLS,) np.nanmean
+            of the sliced Wasserstein distances of the H0 / H1 pairs (engine.sliced_wasserstein_dev) under the rule of `bott`;
+            the directions are uploaded once (`sliced_dirs`)""",
+                   lambda value: ((SLC_COLS,), engine._directions(value)), "s", "sliced", engine.sliced_wasserstein_dev,
+                   lambda ws: dict(dirs_t=ws.sliced_dirs), tables=dict(sliced_dirs=lambda ws: _dev(ws, ws.sliced))),
+    _pair_distance("wq", "wasserstein_q", """\
+      wq    wasserstein_q=(order, ground), order 1 or 2 and ground "l2" or "linf": (WQ_COLS,) np.nanmean of that Wasserstein
+            distance of the H0 / H1 pairs (engine.wasserstein_q_dev) under the rule of `bott`.  ValueError for anything else""",
+                   _engine_checked(lambda value: engine.wasserstein_q_args(*value),
+                                   "wasserstein_q=(order, ground): order 1 or 2, ground 'l2' or 'linf'", (WQ_COLS,),
+                                   lambda value: (int(value[0]), value[1]), catch=(TypeError, ValueError, _lib.TdaError)),
+                   "q", "wasserstein_q", engine.wasserstein_q_dev,
+                   lambda ws: dict(order=ws.wasserstein_q[0], ground=ws.wasserstein_q[1])),
+    _set_means("fm", "frechet", """\
+      fm    frechet=(cap, max_iter), 1 <= cap <= FM_MAX_POINTS and 1 <= max_iter <= FM_MAX_ITER: (FM_SETS, cap + 2, 2), per
+            diagram set of `land` (same windows, same audio mask) the Frechet mean of the group's diagrams in the order-2
+            Wasserstein metric (engine.frechet_mean_dev): rows 0..cap-1 the mean, NaN beyond its count; row cap
+            [count, Frechet variance]; row cap + 1 [iterations, status word].  ValueError for anything else""",
+               _frechet, "frechet", set_stage=_frechet_stage,
+               # what the kernel writes for one diagram set, packed into the set's float64 block after its launch
+               per_group=dict(fm_out=lambda ws: (_f64(ws, ws.n_seg, ws.frechet[0], 2), _i32(ws, ws.n_seg), _f64(ws, ws.n_seg),
+                                                 _i32(ws, ws.n_seg), _i32(ws, ws.n_seg)))),
+    _pair_distance("kd", "kernel_distance", """\
+      kd    kernel_distance=("pss", sigma) or ("pwg", sigma, c) (engine.diagram_kernel_args): (KD_COLS,) np.nanmean of the
+            distance that kernel on diagrams induces between the H0 / H1 pairs (engine.diagram_kernel_dev) under the rule of
+            `bott`.  ValueError for anything else""",
+                   _engine_checked(engine.diagram_kernel_args,
+                                   "kernel_distance=('pss', sigma) or ('pwg', sigma, c): finite sigma, c > 0", (KD_COLS,),
+                                   lambda value: (value[0],) + tuple(float(v) for v in value[1:])),
+                   "k", "kernel_distance", engine.diagram_kernel_dev, lambda ws: dict(kernel=ws.kernel_distance)),
+    _pair_distance("pf", "fisher", """\
+      pf    fisher=sigma, a finite number > 0 (engine.fisher_args): (PF_COLS,) np.nanmean of the persistence Fisher distances
+            of the H0 / H1 pairs (engine.persistence_fisher_dev) under the rule of `bott`.  ValueError for anything else""",
+                   _engine_checked(engine.fisher_args, "fisher=sigma: a finite number > 0", (PF_COLS,), float),
+                   "f", "fisher", engine.persistence_fisher_dev, lambda ws: dict(sigma=ws.fisher)),
+    OutputSpec("sl", "sublevel", """\
+      sl    sublevel=True: (SL_COLS,) from the sublevel-set (lower-star) H0 diagrams of the signals themselves
+            (engine.sublevel_features_dev; include/tdaeeg.h).  Columns 0..10: np.nanmean over the group's windows of the 11
+            extract_features values of the audio window's diagram.  Columns 11..21: np.nanmean over the windows of the
+            np.mean over the channels of the same 11 values of the EEG channels' diagrams, one diagram per channel.  A
+            signal with a sample that is not finite counts as NaN.  Every window of the group takes part: no Rips status
+            is looked at.
+            Workspace: per window the features it averages, `sl_fa` (n_win, 1, 11) of the audio window and `sl_fe`
+            (n_win, n_ch, 11) of the EEG channels (NaN where `sl_sa` / `sl_se` flag the signal).  The diagrams exist only
+            chunk by chunk, in scratch of at most sublevel_bytes of rows per signal kind (engine.SublevelScratch, made at
+            the first step, when the window length is known)""",
+               _switch(SL_COLS), ("sublevel",),
+               lambda ws, ctx, stage, inputs: stage("sublevel", lambda: _sublevel_stage(ws, ctx, *inputs)), off=False,
+               per_window=dict(sl_fa=lambda ws: _f64(ws, ws.n_win, 1, 11), sl_fe=lambda ws: _f64(ws, ws.n_win, ws.n_ch, 11),
+                               sl_sa=lambda ws: _i32(ws, ws.n_win, 1), sl_se=lambda ws: _i32(ws, ws.n_win, ws.n_ch)),
+               # the 22 per-window series, one contiguous row each; (n_ch, n_t) -> engine.SublevelScratch, shared by views
+               tables=dict(sl_cols=lambda ws: _f64(ws, SL_COLS * ws.n_win), sl_scratch=lambda ws: {},
+                           sl_n_win=lambda ws: ws.n_win)),
+    OutputSpec("pl", "phase_locking", """\
+      pl    phase_locking=method, one of "euclidean", "abs", "standard", "sqrt" (True: "euclidean"; the parameter kept is
+            the method number): (PL_COLS,) from the Rips diagrams of the phase-locking distance of the EEG window's channels
+            (engine.plv_dist_dev -> rips_dm_dev; include/tdaeeg.h, "Phase-locking value").  Columns 0..10: np.nanmean over
+            the group's windows of the 11 extract_features values of H0; columns 11..21: the same for H1; every window of
+            the group takes part, as for the EEG sets.  Columns 22, 23: np.nanmean of the reference's Wasserstein distance
+            (engine.wasserstein_dev) between that diagram and the audio diagram of the same window, H0 and H1, under the
+            rule of `bott`.  A window with a PLV or Rips status counts as NaN.  ValueError for anything else.
+            Workspace: per window what it averages: `pl_f0` / `pl_f1` (n_win, 11), the features of the H0 / H1 diagram
+            `pl_dgm` (an engine.DeviceDiagrams) of the phase-locking distance matrix `pl_dist` (n_win, n_ch, n_ch), `pl_w0` /
+            `pl_w1` (n_win), its Wasserstein distances to the audio diagram, with the status words `pl_st` (the PLV
+            kernel's), `pl_dgm.status` (Rips) and `pl_ws0` / `pl_ws1` (the distances').  A window flagged by the PLV kernel is
+            handed to Rips as points on a line (`pl_line`), its NaN block in `pl_dist` replaced, and counts as NaN""",
+               lambda value: None if value is False else ((PL_COLS,), engine.plv_method(value)), ("phase_locking",),
+               lambda ws, ctx, stage, inputs: stage("phase_locking",
+                                                    lambda: _phase_locking_stage(ws, ctx, inputs[0], inputs[2], inputs[3])),
+               arg=lambda method: engine.METHOD_NAMES[method],
+               per_window=dict(pl_dist=lambda ws: _f64(ws, ws.n_win, ws.n_ch, ws.n_ch), pl_st=lambda ws: _i32(ws, ws.n_win),
+                               pl_dgm=lambda ws: engine.DeviceDiagrams(ws.n_win, ws.n_ch, ws.eeg.h1_cap, ws.device),
+                               pl_f0=lambda ws: _f64(ws, ws.n_win, 11), pl_f1=lambda ws: _f64(ws, ws.n_win, 11),
+                               pl_w0=lambda ws: _f64(ws, ws.n_win), pl_w1=lambda ws: _f64(ws, ws.n_win),
+                               pl_ws0=lambda ws: _i32(ws, ws.n_win), pl_ws1=lambda ws: _i32(ws, ws.n_win)),
+               # pl_cols: the 24 per-window series, one contiguous row each; pl_line: |j - k| / n_ch, points on a line
+               tables=dict(pl_cols=lambda ws: _f64(ws, PL_COLS * ws.n_win),
+                           pl_line=lambda ws: _dev(ws, np.abs(np.subtract.outer(np.arange(ws.n_ch), np.arange(ws.n_ch))) / ws.n_ch))),
+]
+OUTPUT_BY_NAME = {spec.name: spec for spec in OUTPUTS}
+# The launches of a step do not come in the table's order but in this one, the outputs that are on; None stands for the
+# two Wasserstein stages of `result`.  Captured graphs and the stage timers depend on it
+LAUNCH_ORDER = ("corr", "land", "img", None, "bott", "slc", "wq", "kd", "pf", "fm", "sl", "pl")
+# (kept for its readers: the per-window buffers of the pair distances, in the order in which the distances were added)
+Workspace.PAIR_BUFFERS = tuple(a for name in ("bott", "slc", "wq", "pf", "kd") for a in OUTPUT_BY_NAME[name].per_window)
+for _spec in OUTPUTS:                                       # everything an output owns is None while it is off
+    for _attr in (_spec.name, _spec.name + "_sets", *_spec.per_window, *_spec.per_group, *_spec.tables):
+        setattr(Workspace, _attr, None)
+    setattr(Workspace, _spec.keyword, _spec.off)
+
+
+def step_outputs(*args, **kw):
+    given = _KEYWORDS.bind(*args, **kw).arguments           # TypeError for an unknown keyword
+    out = []
+    for spec in OUTPUTS:
+        value = given.get(spec.keyword)
+        checked = None if value is None else spec.validate(value)
+        if checked is not None:
+            out.append(Output(spec.name, *checked))
+    return out
+
+
+step_outputs.__signature__ = _KEYWORDS = inspect.Signature(
+    [inspect.Parameter(spec.keyword, inspect.Parameter.POSITIONAL_OR_KEYWORD, default=spec.off) for spec in OUTPUTS])
+step_outputs.__doc__ = """The optional per-group outputs of a step: one Output(name, shape of a group's block, validated
+    params) per enabled one, in the fixed order of OUTPUTS (%s), which is also the order of the positional arguments.
+    numpy only.  Workspace, the shard driver and the passes of recordings.py size, slice, scatter and copy every optional
+    output from this table; `result` is the same either way.
+%s""" % (", ".join(OUTPUT_BY_NAME), "\n".join(s.doc for s in OUTPUTS))
 
 
 class Batch:
@@ -804,7 +853,6 @@ def run_features_step(eeg_win, ws, ctx=None):
     BASELINE.json configs[2]): corr->dist -> Rips -> 11 features of H0 and of H1 -> mean/std over the windows of
     every (recording, band) group.  Returns ws.feat44 (n_seg, 44)."""
     import torch
-    from . import _lib
     ctx = ctx or _lib.get_ctx()
     with ctx.deferred():
         if ws.fused and eeg_win.shape[2] <= 256:
@@ -815,12 +863,10 @@ def run_features_step(eeg_win, ws, ctx=None):
             engine.corr_dist_dev(eeg_win, ws.dist, None, ctx=ctx)
             engine.rips_dm_dev(ws.dist, ws.eeg, ctx=ctx)
     engine.diagram_finish_dev([(ws.eeg.h0, ws.eeg.c0, False, ws.fe0), (ws.eeg.h1, ws.eeg.c1, True, ws.fe1)], ctx=ctx)
-    if ws.land is not None:                              # the two EEG sets of ws.land; the audio set is not touched
-        _landscape_stage(ws, ctx, audio=False)
-    if ws.img is not None:                               # the same for ws.img
-        _image_stage(ws, ctx, audio=False)
-    if ws.fm is not None:                                # the same for ws.fm
-        _frechet_stage(ws, ctx, audio=False)
+    on = {o.name for o in ws.outputs}
+    for name in LAUNCH_ORDER:                            # the two EEG sets of the set means; the audio set is not touched
+        if name in on and OUTPUT_BY_NAME[name].set_stage is not None:
+            OUTPUT_BY_NAME[name].set_stage(ws, ctx, audio=False)
     if not hasattr(ws, "feat44"):
         ws.feat44 = torch.empty((ws.n_seg, 44), dtype=torch.float64, device=ws.device)
     engine.aggregate_dev(ws.fe0, ws.fe1, ws.seg_off, ws.feat44, ctx=ctx)
@@ -828,6 +874,4 @@ def run_features_step(eeg_win, ws, ctx=None):
 
 
 STAGES = ["eeg_window", "corr_dist", "rips_eeg", "tau", "rips_audio", "finish", "wasserstein_h0", "wasserstein_h1", "reduce"]
-# (the optional outputs add "temporal_corr", "landscape" and "image", in this order after "finish", and "bottleneck_h0",
-# "bottleneck_h1", "sliced_h0", "sliced_h1", "wasserstein_q_h0", "wasserstein_q_h1", "kernel_distance_h0", "kernel_distance_h1", "fisher_h0", "fisher_h1", "frechet", "sublevel" and "phase_locking", in this order after
-# "wasserstein_h1")
+# (every optional output adds the stages of its record of OUTPUTS, at its place in LAUNCH_ORDER)

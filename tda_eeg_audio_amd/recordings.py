@@ -26,10 +26,9 @@ rows are withheld if any status bit is left.  The passes differ in how a shard i
 The filter banks are designed and packed once per pass (preprocess.SosBank / BaBank) and handed to every shard's step.
 The rows equal pipeline.run_step on the stacked windows of the same band-passed signals bit for bit
 (tests/test_gpu_frontend.py::test_recording_pass_equals_stacked_windows).
-RecordingPass and the ragged passes take the optional outputs of pipeline.step_outputs (correlations, bottleneck,
-landscapes, images, sliced, wasserstein_q, frechet, kernel_distance, fisher, sublevel, phase_locking: each is described there) and return each enabled one per (recording, band) beside the rows, in
-pinned host memory: corr_h (n_rec, 5, 10), bott_h (n_rec, 5, 2), land_h (n_rec, 5, 3, levels + 1, n_grid), img_h
-(n_rec, 5, 3, n_y, n_x), slc_h (n_rec, 5, 2), wq_h (n_rec, 5, 2), fm_h (n_rec, 5, 3, cap + 2, 2), kd_h (n_rec, 5, 2), pf_h (n_rec, 5, 2), sl_h (n_rec, 5, 22), pl_h (n_rec, 5, 24) -- the group's block of the step's Workspace, NaN for a recording without a
+RecordingPass and the ragged passes take the optional outputs of pipeline.step_outputs, by its keywords (each is
+described there), and return each enabled one per (recording, band) beside the rows, in pinned host memory: <name>_h
+(n_rec, 5) + shape, e.g. corr_h (n_rec, 5, 10) -- the group's block of the step's Workspace, NaN for a recording without a
 window.  They are computed on the device from the step's own diagrams and feature matrices; drivers.comparison_rows /
 comparison_summary turn rows and corr_h into the script's table and statistics.
 """
@@ -62,26 +61,21 @@ class _ShardedPass:
 
     ROW_COLS = pipeline.RESULT_COLS     # width of a row
 
-    def __init__(self, device, ctx, fs, bands, correlations, bottleneck=False, landscapes=None, images=None, sliced=None,
-                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None, takens=None, sublevel=False,
-                 phase_locking=None):
+    def __init__(self, device, ctx, fs, bands, takens=None, **outputs):
         self.ctx = ctx or get_ctx()
         # takens=(dim, subsample, n_perm): the audio stage of every Workspace runs on greedy landmarks (pipeline.Workspace)
         self.takens = None if takens is None else tuple(int(v) for v in takens)
         self.dev, self.fs = device, fs
         self.bands = list(dict(bands).values())
-        # the optional outputs (pipeline.step_outputs: self.outputs is the table, validated here); host buffer of `name`:
+        # the optional outputs (pipeline.step_outputs: self.outputs is the table, validated here, once); output_kw: the
+        # enabled ones as keywords for every pipeline.Workspace, each also an attribute; host buffer of `name`:
         # self.<name>_h, made by `run`
-        self.outputs = pipeline.step_outputs(correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet,
-                                             kernel_distance, fisher, sublevel, phase_locking)
-        par = {o.name: o.params for o in self.outputs}
-        self.correlations, self.bottleneck = "corr" in par, "bott" in par
-        self.landscapes, self.images, self.sliced = par.get("land"), par.get("img"), par.get("slc")
-        self.wasserstein_q, self.frechet, self.kernel_distance = par.get("wq"), par.get("fm"), par.get("kd")
-        self.fisher, self.sublevel = par.get("pf"), "sl" in par
-        self.phase_locking = engine.METHOD_NAMES[par["pl"]] if "pl" in par else None
-        self.corr_h = self.bott_h = self.land_h = self.img_h = self.slc_h = self.wq_h = self.fm_h = self.kd_h = self.pf_h = None
-        self.sl_h = self.pl_h = None
+        self.outputs = pipeline.step_outputs(**outputs)
+        self.output_kw = {pipeline.OUTPUT_BY_NAME[o.name].keyword: pipeline.OUTPUT_BY_NAME[o.name].arg(o.params)
+                          for o in self.outputs}
+        for spec in pipeline.OUTPUTS:
+            setattr(self, spec.keyword, self.output_kw.get(spec.keyword, spec.off))
+            setattr(self, spec.name + "_h", None)
         # the filter banks, designed and packed once: the EEG's band-passes (nb1:209-233) and the envelopes' (utils.py:66-74)
         self.eeg_bank = preprocess.SosBank.bandpass(self.bands, fs, preprocess.FILTER_ORDER)
         self.env_bank = preprocess.BaBank(preprocess.envelope_bandpass(self.bands, fs))
@@ -187,17 +181,14 @@ class RecordingPass(_ShardedPass):
     their flags say nothing new)."""
 
     def __init__(self, n_samples, shard, device, ctx=None, n_ch=47, fs=250, bands=preprocess.FREQ_BANDS,
-                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, correlations=False, bottleneck=False,
-                 landscapes=None, images=None, sliced=None, wasserstein_q=None, frechet=None, kernel_distance=None,
-                 fisher=None, takens=None, sublevel=False, phase_locking=None):
-        """correlations .. fisher, sublevel, phase_locking: the optional outputs (pipeline.step_outputs); `run` also fills self.<name>_h of each
+                 max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75, n_sets=None, takens=None, **outputs):
+        """**outputs: the optional outputs, by the keywords of pipeline.step_outputs; `run` also fills self.<name>_h of each
         (_ShardedPass.run).  corr_h is in the order of drivers.DETAILED_COLUMNS[8:].  The rows are the same either way.
         takens=(dim, subsample, n_perm): handed to every pipeline.Workspace -- the audio diagrams come from n_perm greedy
         landmarks of the (dim, subsample) Takens cloud; the columns of the rows keep their meaning."""
         import os
         import torch
-        super().__init__(device, ctx, fs, bands, correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet,
-                         kernel_distance, fisher, takens, sublevel, phase_locking)
+        super().__init__(device, ctx, fs, bands, takens, **outputs)
         self.S, self.L, self.n_ch = int(shard), int(n_samples), n_ch
         self.win = int(window_sec * fs)
         self.step = int(self.win * (1 - overlap))                      # cmp:57-58: 62
@@ -217,11 +208,7 @@ class RecordingPass(_ShardedPass):
             raw=torch.empty((S, n_ch, L), **f64), env=torch.empty((S, L), **f64),
             y=torch.empty((nb, S * n_ch, L), **f64), ya=torch.empty((nb, S, L), **f64),
             aw=torch.empty((nb * S * k, self.win), **f64), rows=torch.empty((S, nb, pipeline.RESULT_COLS), **f64),
-            ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, correlations=self.correlations,
-                                  bottleneck=self.bottleneck, landscapes=self.landscapes, images=self.images,
-                                  sliced=self.sliced, wasserstein_q=self.wasserstein_q, frechet=self.frechet,
-                                  kernel_distance=self.kernel_distance, fisher=self.fisher, takens=self.takens,
-                                  sublevel=self.sublevel, phase_locking=self.phase_locking),
+            ws=pipeline.Workspace(nb * S * k, seg_off, device, n_ch=n_ch, takens=self.takens, **self.output_kw),
             work=torch.empty((nb, S * n_ch, L + 2 * edge), **f64), worka=torch.empty((nb, S, L + 2 * edge_a), **f64)))
 
     def _begin(self, raw_h, env_h):
@@ -359,14 +346,12 @@ class RaggedRecordingPass(_ShardedPass):
 
     def __init__(self, eeg_lengths, env_lengths=None, device=None, shard_samples=DEFAULT_SHARD_SAMPLES, n_sets=2, ctx=None,
                  n_ch=47, fs=250, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0, overlap=0.75,
-                 plan=None, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None, wasserstein_q=None,
-                 frechet=None, kernel_distance=None, fisher=None, takens=None, sublevel=False, phase_locking=None):
-        """correlations .. fisher, sublevel, phase_locking: the optional outputs, as RecordingPass takes them; NaN for a recording without a
-        window.  takens=(dim, subsample, n_perm): as RecordingPass takes it."""
+                 plan=None, takens=None, **outputs):
+        """**outputs: the optional outputs (pipeline.step_outputs), as RecordingPass takes them; NaN for a recording without
+        a window.  takens=(dim, subsample, n_perm): as RecordingPass takes it."""
         import torch
         super().__init__(device if device is not None else torch.device("cuda", torch.cuda.current_device()), ctx, fs, bands,
-                         correlations, bottleneck, landscapes, images, sliced, wasserstein_q, frechet, kernel_distance,
-                         fisher, takens, sublevel, phase_locking)
+                         takens, **outputs)
         self.n_ch = n_ch
         nb = len(self.bands)
         # plan: a RaggedPlan made by a subclass (RaggedAudioRecordingPass plans its shards by bytes)
@@ -402,11 +387,7 @@ class RaggedRecordingPass(_ShardedPass):
         def buffers():
             # the Workspace of a buffer set is sized by the largest shard; each shard gets a view with its own seg tables
             ws = pipeline.Workspace(n_win, np.concatenate([np.zeros(n_seg, np.int32), [n_win]]).astype(np.int32), self.dev,
-                                    n_ch=n_ch, correlations=self.correlations, bottleneck=self.bottleneck,
-                                    landscapes=self.landscapes, images=self.images, sliced=self.sliced,
-                                    wasserstein_q=self.wasserstein_q, frechet=self.frechet,
-                                    kernel_distance=self.kernel_distance, fisher=self.fisher, takens=self.takens,
-                                    sublevel=self.sublevel, phase_locking=self.phase_locking)
+                                    n_ch=n_ch, takens=self.takens, **self.output_kw)
             return dict(
                 raw=torch.empty(n_ch * T, **f64), env=torch.empty(Te, **f64),
                 y=torch.empty(nb * n_ch * T, **f64), ya=torch.empty(nb * Te, **f64),
@@ -488,9 +469,8 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
 
     def __init__(self, eeg_lengths, audio_lengths, device=None, shard_bytes=DEFAULT_SHARD_BYTES, n_sets=2, ctx=None, n_ch=47,
                  fs=250, fs_audio=preprocess.FS_AUDIO, bands=preprocess.FREQ_BANDS, max_windows=MAX_WINDOWS, window_sec=1.0,
-                 overlap=0.75, correlations=False, bottleneck=False, landscapes=None, images=None, sliced=None,
-                 wasserstein_q=None, frechet=None, kernel_distance=None, fisher=None, takens=None, sublevel=False,
-                 phase_locking=None):
+                 overlap=0.75, takens=None, **outputs):
+        """**outputs, takens: as RaggedRecordingPass takes them (pipeline.step_outputs lists the optional outputs)."""
         import torch
         A = preprocess.AudioPlan(audio_lengths, fs_audio, fs)
         long_ = np.flatnonzero(A.n_out > preprocess.HILBERT_RAGGED_MAX)
@@ -499,10 +479,7 @@ class RaggedAudioRecordingPass(RaggedRecordingPass):
         plan = RaggedPlan(eeg_lengths, A.n_out, n_ch=n_ch, n_bands=len(dict(bands)), fs=fs, window_sec=window_sec,
                           overlap=overlap, max_windows=max_windows, shard_bytes=shard_bytes, audio_lengths=A.La)
         super().__init__(eeg_lengths, A.n_out, device, n_sets=n_sets, ctx=ctx, n_ch=n_ch, fs=fs, bands=bands,
-                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, correlations=correlations,
-                         bottleneck=bottleneck, landscapes=landscapes, images=images, sliced=sliced,
-                         wasserstein_q=wasserstein_q, frechet=frechet, kernel_distance=kernel_distance,
-                         fisher=fisher, takens=takens, sublevel=sublevel, phase_locking=phase_locking)
+                         max_windows=max_windows, window_sec=window_sec, overlap=overlap, plan=plan, takens=takens, **outputs)
         self.audio_plan = A
         self.audio_off = np.concatenate([[0], np.cumsum(A.La)]).astype(np.int64)
         self.second = ("audio", self.audio_off)

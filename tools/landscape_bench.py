@@ -70,7 +70,7 @@ def main():
     for _ in range(steps):
         a, b = ev()
         a.record()
-        pipeline._landscape_stage(ws, ctx, audio=True)
+        pipeline.OUTPUT_BY_NAME["land"].set_stage(ws, ctx, audio=True)
         b.record()
         torch.cuda.synchronize()
         alone.append(a.elapsed_time(b))
