@@ -153,8 +153,12 @@ tda_status tda_rips_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, d
  * replaces, per window, compute_correlation_matrix + correlation_to_distance (nb2:86-122; the loop of
  * process_file_graphs, nb2:198-207) followed by compute_eeg_persistence (scripts/utils.py:135-141): the distance
  * matrix stays in LDS, 95.1 KB of HBM traffic per window instead of 129.4.  Same arithmetic, operation for
- * operation, as tda_corr_dist_batch_dev + tda_rips_dm_batch_dev(symmetrise = 1): identical diagrams.
- * win: (n_win, n_ch, n_t) float64, 33 <= n_ch <= 48 (the reference has 47), n_t <= 256 (250).
+ * operation, as tda_corr_dist_batch_dev + tda_rips_dm_batch_dev(symmetrise = 1): identical diagrams.  Its ladder of
+ * class widths (32 / 64 -> 128 -> 512 bits in LDS) ends, like that of tda_rips_dm_batch_dev, in a pass without a
+ * capacity limit (class vectors in HBM): 512 bits hold the 506 classes that 47 channels can have alive at once, not
+ * the 529 of 48.  TDA_RETRY_LAST_RUNG runs that pass alone on the windows whose status carries
+ * TDA_WIN_CLASS_OVERFLOW.
+ * win: (n_win, n_ch, n_t) float64, 33 <= n_ch <= 48 (the reference has 47), 2 <= n_t <= 256 (250).
  * dist / corr (nullable; corr needs dist): the matrices as tda_corr_dist_batch writes them, for callers that also
  * want the graphs/<cond>/<rec>/<band>_distances.npy hand-off file.  Device pointers only. */
 tda_status tda_eeg_window_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_ch, int n_t, double thresh,

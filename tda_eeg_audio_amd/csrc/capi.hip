@@ -137,8 +137,9 @@ tda_status tda_corr_dist_batch_dev(tda_ctx* ctx, const double* win, int n_win, i
 tda_status tda_corr_dist_sliding_dev(tda_ctx* ctx, const double* sig, int n_ch, int n_samples, int win_len, int step,
                                      double* dist, double* corr, int* n_win, void* stream)
 {
-    CHECK_CTX(ctx); CHECK_PTR(ctx, sig); CHECK_PTR(ctx, dist);
+    CHECK_CTX(ctx); CHECK_PTR(ctx, sig);
     CHECK_NONNEG(ctx, n_samples);
+    if (n_samples >= win_len) CHECK_PTR(ctx, dist);     // (a recording shorter than the window has no matrix to write)
     return launch_corr_dist_sliding(ctx, sig, n_ch, n_samples, win_len, step, dist, corr, n_win, (hipStream_t)stream);
 }
 

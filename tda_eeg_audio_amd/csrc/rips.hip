@@ -2451,10 +2451,12 @@ struct RaggedWindowSource {
     __device__ __forceinline__ int ld_of(int w) const { return (int)ld[w]; }
 };
 
-template <int NB, bool RES, int W, typename WT, class SRC>
+// TOTAL: the last rung (rips_sweep_total, class vectors in psi_g) behind the same keys
+template <int NB, bool RES, int W, typename WT, bool TOTAL = false, class SRC>
 __device__ __forceinline__ void eeg_one_window(unsigned char* smem, const SRC& src, int w, int n_ch,
                                                int n_t, float thresh, const RipsLayout& L, const RipsOut& out,
-                                               double* __restrict__ dist, double* __restrict__ corr)
+                                               double* __restrict__ dist, double* __restrict__ corr,
+                                               u64* __restrict__ psi_g = nullptr)
 {
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6;
     PROF_BEGIN();
@@ -2500,7 +2502,7 @@ __device__ __forceinline__ void eeg_one_window(unsigned char* smem, const SRC& s
     }
     __syncthreads();
     PROF_MARK(0);
-    rips_dm_rest<256, 1, W, WT>(smem, w, n_ch, thresh, vmax, kmin_thread, L, out);
+    rips_dm_rest<256, TOTAL ? 2 : 1, W, WT, TOTAL>(smem, w, n_ch, thresh, vmax, kmin_thread, L, out, psi_g);
 }
 
 // RETRY = false: one window per workgroup and NO loop over windows -- with the loop the compiler hoists the address
@@ -2510,7 +2512,8 @@ __device__ __forceinline__ void eeg_one_window(unsigned char* smem, const SRC& s
 // note in corr_dist_dev.h; the sweep and its LDS hand-overs are not involved -- the distance matrix itself comes out
 // wrong).  Every variant of this kernel stays at >= 2 waves per SIMD (no AGPRs: checked by a CPU test on the code
 // object); tests/test_gpu_parity.py::test_fused_eeg_window_512_classes covers the widest one on windows that need it, and
-// tests/test_gpu_retry_trips.py every RETRY variant with three windows per workgroup.
+// tests/test_gpu_retry_trips.py every RETRY variant with three windows per workgroup; the last rung behind it
+// (eeg_window_total_kernel) on 48-channel windows with 529 classes: tests/test_gpu_eeg_shapes.py.
 #ifndef TDA_EEG_WIDE_WAVES
 #define TDA_EEG_WIDE_WAVES 2     // (tools/probes/wide_waves_repro.py builds with 1 to reproduce the fault)
 #endif
@@ -2552,6 +2555,22 @@ eeg_window_ragged_kernel(RaggedWindowSource windows, int n_win, int n_ch, int n_
             eeg_one_window<NB, RES, W, WT>(smem, windows, win, n_ch, n_t, thresh, L, out, dist, corr);
         RETRY_SCAN_END()
     }
+}
+// The last rung of the fused ladder (as rips_dm_total_kernel): TOT_SLOTS workgroups redo what the 512-bit pass still
+// flags -- 48 channels admit (24 - 1)(24 - 1) = 529 classes alive at once -- from the samples, with the class vectors
+// in HBM.  Two waves per SIMD like every other variant of the fused kernel (no AGPRs: see above).
+template <int NB, bool RES, class SRC>
+__global__ void __launch_bounds__(256, 2)
+eeg_window_total_kernel(SRC windows, int n_win, int n_ch, int n_t, float thresh, RipsLayout L, RipsOut out,
+                        double* __restrict__ dist, double* __restrict__ corr, u64* __restrict__ scratch,
+                        unsigned long long* __restrict__ retry_ctr)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u64* psi_g = scratch + (size_t)blockIdx.x * TOT_SLOT_WORDS;
+    RETRY_SCAN_BEGIN(256, out, n_win)
+        if (retry_ctr && threadIdx.x == 0) atomicAdd(retry_ctr + 2, 1ull);
+        eeg_one_window<NB, RES, 1, u32, true>(smem, windows, win, n_ch, n_t, thresh, L, out, dist, corr, psi_g);
+    RETRY_SCAN_END()
 }
 // the kernel of a window source
 template <int NB, bool RES, int W, bool RETRY, typename WT>
@@ -2795,17 +2814,35 @@ static tda_status launch_eeg_t(tda_ctx* ctx, const SRC& win, int n_win, int n_ch
     return TDA_OK;
 }
 
+// the last rung of the fused ladder (as launch_dm_total)
+template <bool RES, class SRC>
+static tda_status launch_eeg_total(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float thresh, RipsOut out,
+                                   double* dist, double* corr, hipStream_t st)
+{
+    RipsLayout L = total_layout(n_ch, n_ch * (n_ch - 1) / 2 * 4, 256);
+    if ((size_t)L.total < CdLayout<3>::BYTES) { L.total = (int)((CdLayout<3>::BYTES + 15) & ~(size_t)15); L.guard[4] = L.total; }
+    auto kern = eeg_window_total_kernel<3, RES, SRC>;
+    if (L.total > 48 * 1024)
+        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
+    hipLaunchKernelGGL(kern, dim3(TOT_SLOTS), dim3(256), L.total, st, win, n_win, n_ch, n_t, thresh, L, out, dist, corr,
+                       ctx->total_scratch, ctx->retry_ctr);
+    TDA_HIP(ctx, hipGetLastError());
+    return TDA_OK;
+}
+
 template <bool RES, class SRC>
 static tda_status launch_eeg_ladder(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float th, RipsOut out,
                                     double* dist, double* corr, hipStream_t st)
 {
-    if (ctx->retry_policy == TDA_RETRY_LAST_RUNG) return TDA_OK;     // (512 bits cover every complex on 48 points: no such rung here)
-    const bool do_first = ctx->retry_policy != TDA_RETRY_ONLY, do_ladder = ctx->retry_policy != TDA_RETRY_FIRST_PASS;
+    const bool last_only = ctx->retry_policy == TDA_RETRY_LAST_RUNG;
+    const bool do_first = ctx->retry_policy != TDA_RETRY_ONLY && !last_only;
+    const bool do_ladder = ctx->retry_policy != TDA_RETRY_FIRST_PASS && !last_only;
     const bool one_step = ctx->retry_policy == TDA_RETRY_ONE_STEP;
     tda_status rc = TDA_OK;
-    // ladder of the fused kernel: 32 (words_dm = 0) -> 64 -> 128 -> 512 class bits; every wider pass recomputes the
-    // flagged windows from the samples (the matrix was never stored); 512 covers the theoretical maximum of 506
-    // classes alive at once for 47 points
+    // ladder of the fused kernel: 32 (words_dm = 0) -> 64 -> 128 -> 512 class bits -> the last rung; every wider pass
+    // recomputes the flagged windows from the samples (the matrix was never stored).  512 bits cover the theoretical
+    // maximum of 506 classes alive at once for 47 points, not the 529 of 48: those go on to the last rung
     const int first = ctx->words_dm >= 2 ? 2 : ctx->words_dm;       // 0, 1 or 2
     if (do_first) {
         if (first == 0) rc = launch_eeg_t<3, RES, 1, false, u32>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
@@ -2819,6 +2856,10 @@ static tda_status launch_eeg_ladder(tda_ctx* ctx, const SRC& win, int n_win, int
         rc = launch_eeg_t<3, RES, 2, true>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
     if (do_ladder && rc == TDA_OK && !(one_step && rung++ >= 1))
         rc = launch_eeg_t<3, RES, 8, true>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
+    // the last rung, under the conditions of launch_rips_dm: whatever is still flagged (more than 512 classes alive at
+    // once: 48 channels only) is redone with the class vectors in HBM
+    if (rc == TDA_OK && ((do_ladder && !one_step) || last_only))
+        rc = launch_eeg_total<RES>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
     return rc;
 }
 

@@ -76,7 +76,7 @@ def test_retry_grids_are_named_and_every_case_makes_three_trips():
     assert len(exprs) == 3, exprs                       # launch_dm_t, launch_eeg_t, launch_cloud_t
     for e in exprs:
         assert "RETRY_GRID" in e and not re.search(r"\b(64|512)\b", e), e
-    assert len(re.findall(r"dim3\(TOT_SLOTS\)", src)) == 2          # both last-rung launches
+    assert len(re.findall(r"dim3\(TOT_SLOTS\)", src)) == 3          # all three last-rung launches (matrices, fused EEG, clouds)
     for grid in (g, gw, slots):
         for pattern in PATTERNS:
             f = _flags(grid, pattern)
@@ -388,6 +388,52 @@ def test_last_rung_clouds_three_trips(ctx, pattern):
     for w in _sample(f):
         (o, _) = port.audio_persistence(aw[w], int(tau[w]))
         _equals_oracle(got, w, o, pattern)
+
+
+# ------------------------------------------------------------------ g2. last rung, fused EEG kernel
+@gpu
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("source", ["stacked", "sliding", "table"])
+def test_last_rung_fused_three_trips(ctx, source, pattern):
+    """eeg_window_total_kernel behind each window source: TOT_SLOTS workgroups recompute 2 TOT_SLOTS + 1 windows flagged by
+    hand from the samples (48 channels, white noise and EEG-like in turn), each with the MFMA accumulator image, the
+    keys and the bit maps of the last rung in the LDS that its earlier window left behind; the matrices are written for
+    the flagged windows only."""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    _, _, slots = _grids()
+    flagged = _flags(slots, pattern)
+    n = len(flagged)
+    f = np.nonzero(flagged)[0]
+    assert len(f) >= 2 * slots + 1
+    m = n + (n & 1)                                                 # recordings of two windows each
+    W = synth.eeg_windows(m, seed=21, n_ch=48, kind="white")
+    W[1::2] = synth.eeg_windows(m, seed=22, n_ch=48, windows_per_recording=5)[1::2]
+    sig = np.ascontiguousarray(W.reshape(m // 2, 2, 48, 250).transpose(0, 2, 1, 3).reshape(m // 2, 48, 500))
+    sig_t = torch.from_numpy(sig).to(dev)
+    if source == "stacked":
+        wt = torch.from_numpy(W[:n]).to(dev)
+        call = lambda o, **kw: engine.eeg_window_dev(wt, o, ctx=ctx, **kw)
+    elif source == "sliding":
+        sel_t = torch.arange(n, dtype=torch.int32, device=dev)
+        call = lambda o, **kw: engine.eeg_window_sliding_dev(sig_t, 250, 250, sel_t=sel_t, out=o, ctx=ctx, **kw)[0]
+    else:
+        w = np.arange(n)
+        start_t = torch.from_numpy((48 * 500 * (w // 2) + 250 * (w % 2)).astype(np.int64)).to(dev)
+        ld_t = torch.full((n,), 500, dtype=torch.int64, device=dev)
+        call = lambda o, **kw: engine.eeg_window_ragged_dev(sig_t.reshape(-1), start_t, ld_t, 250, out=o, n_ch=48, ctx=ctx, **kw)
+    oc, od = port.corr_dist_batch(W[:n])
+    ref = _ref_of(call(engine.DeviceDiagrams(n, 48, engine.DEFAULT_H1_CAP, dev)))
+    d2 = torch.full((n, 48, 48), POISON, dtype=torch.float64, device=dev)
+    c2 = torch.full_like(d2, POISON)
+    out = engine.DeviceDiagrams(n, 48, engine.DEFAULT_H1_CAP, dev)
+    counters = _redo(ctx, lambda o: call(o, dist_t=d2, corr_t=c2), out, flagged, ctx.RETRY_LAST_RUNG, None)
+    got = _check(out, ref, flagged, counters, 2, True, (source, pattern))
+    d2, c2 = d2.cpu().numpy(), c2.cpu().numpy()
+    assert np.array_equal(d2[f], od[f]) and np.array_equal(c2[f], oc[f])
+    assert (d2[~flagged] == POISON).all() and (c2[~flagged] == POISON).all()
+    for w in _sample(f):
+        _equals_oracle(got, w, port.rips_dm(od[w]), (source, pattern))
 
 
 # ------------------------------------------------------------------ h. the rungs reached because the windows need them
