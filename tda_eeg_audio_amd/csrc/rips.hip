@@ -1082,6 +1082,9 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         PROF_MARK(22);
         PROF_STOPC(13, out_k0 = k0; out_k1 = k1; out_status = 0);
         clen = uni(offs[19]);                                 // (workgroup-uniform values read from LDS: to SGPRs)
+        // (a shortened chunk is followed by a new chunk at the cut, phase a and all.  Staying in the chunk and sending
+        // only the lanes behind the cut through phases b, c and d again saves that phase a but keeps its masks, apex
+        // and ranks alive through phase d: measured slower)
         if (clen == 0) status |= TDA_WIN_CLASS_OVERFLOW;      // not even the first edge of the chunk fits
         if (clen < NT) PROF_COUNT(14, 1);
         bool mrg = is_cand && ((mbal[wave] >> lane) & 1ull);
@@ -1280,19 +1283,22 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         // earliest non-zero vector kills the YOUNGEST class in it (elder rule) and is substituted into
         // the remaining vectors; the substitutions are linear, so triangles that were trivial stay
         // trivial and the list is complete.  The psi table is rewritten ONCE per chunk with the
-        // composed substitution.  If the list does not fit, only its earliest entry is processed and
-        // the chunk is listed again.
+        // composed substitution.  If the list does not fit, the LCAP entries that were stored are reduced and
+        // the chunk is listed again: they are the FIRST LCAP of the ordered list (placed by prefix), a sequential
+        // reduction of a prefix does not depend on the suffix, and every entry that was processed is zero under the
+        // composed substitution, so the next listing holds the suffix only.
         constexpr int ES = 4 + W * (int)sizeof(WT);                  // list entry: key, vector
         // The list stands in the order of the killing edges (owner, then v: see the listing loop), so with one class
         // word "the earliest non-zero vector" is a ballot and a count of trailing zeros instead of a reduction over
         // the wave.  Entries of ONE edge may come in any order: the classes they kill and the images of those classes
         // depend on their span only.
         constexpr bool SORTED = W == 1;
-        constexpr int HISTN = (NT + 255) & ~255;
-        constexpr int HIST_BYTES = SORTED ? HISTN + 8 : 0;           // (the capacity of the list when wave 0 still sorted it: kept)
-        constexpr int LMAX = SORTED ? 255 : 256;
-        constexpr int LCAP = ((MISC_LIST_BYTES - HIST_BYTES) / ES) < LMAX ? ((MISC_LIST_BYTES - HIST_BYTES) / ES) : LMAX;
+        // SORTED: wave 0 takes the list a block of 64 at a time, so the list holds what its area holds (416 entries with
+        // a 32-bit class word, 277 with a 64-bit one); else all blocks stand in registers at once: four of them at most
+        constexpr int LMAX = SORTED ? MISC_LIST_BYTES / ES : 256;
+        constexpr int LCAP = (MISC_LIST_BYTES / ES) < LMAX ? (MISC_LIST_BYTES / ES) : LMAX;
         constexpr int LPL = (LCAP + 63) / 64;
+        static_assert(LCAP * ES <= MISC_LIST_BYTES, "the list stays inside its area");
         // class-indexed image table (one Psi per class) when it fits the list area; else kill records
         constexpr bool FTAB = WB * W * (int)sizeof(Psi<W, WT>) <= MISC_LIST_BYTES;
         constexpr int KMAX = FTAB ? 64 : LCAP;                       // kills per reduction round
@@ -1409,29 +1415,33 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
             PROF_MARK(17);
             PROF_STOPC(17, out_k0 = k0; out_k1 = k1; out_status = 0);
             const u32 cnt = (u32)lbase;                              // the total, also when it exceeds LCAP
-            const bool complete = cnt <= (u32)LCAP;                  // (else only entry 0, the earliest, is processed)
+            const bool complete = cnt <= (u32)LCAP;                  // (else the LCAP entries that were stored: a prefix)
             PROF_COUNT(11, 1);
             PROF_COUNT(12, cnt);
             if (!complete) PROF_COUNT(13, 1);
+            if (cnt > 2u * (u32)LCAP) PROF_COUNT(46, 1);
             WT alive_before[W];                                      // wave 0 updates `alive` while it reduces
 #pragma unroll
             for (int c = 0; c < W; ++c) alive_before[c] = alive[c];
             if (wave == 0) {
                 TDA_SOLO_BEGIN();
-                const int nl = complete ? (int)cnt : 1;
-                u32 ek[LPL];
-                Psi<W, WT> ev[LPL];
-#pragma unroll
-                for (int q = 0; q < LPL; ++q) {
+                const int nl = complete ? (int)cnt : LCAP;
+                // SORTED: a block is loaded when its turn comes (one block ahead), not all of them up front
+                constexpr int LREG = SORTED ? 1 : LPL;
+                u32 ek[LREG];
+                Psi<W, WT> ev[LREG];
+                auto load_block = [&](int q, u32& k, Psi<W, WT>& x) {
                     const int idx = lane + 64 * q;
-                    ek[q] = 0xffffffffu; ev[q] = pzero<W, WT>();
+                    k = 0xffffffffu; x = pzero<W, WT>();
                     if (idx < nl) {
-                        ek[q] = *reinterpret_cast<const u32*>(list + ES * idx);
+                        k = *reinterpret_cast<const u32*>(list + ES * idx);
 #pragma unroll
                         for (int c = 0; c < W; ++c)
-                            ev[q].w[c] = *reinterpret_cast<const WT*>(list + ES * idx + 4 + c * (int)sizeof(WT));
+                            x.w[c] = *reinterpret_cast<const WT*>(list + ES * idx + 4 + c * (int)sizeof(WT));
                     }
-                }
+                };
+#pragma unroll
+                for (int q = 0; q < LREG; ++q) load_block(q, ek[q], ev[q]);
                 // birth rank / length of the classes: lane i keeps bit i of every word
                 const int lb = lane & (WB - 1);
                 int brk[W];
@@ -1462,11 +1472,12 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
                     // wave that issues one vector instruction every eight cycles, profiles/r03_valu_rate.txt)
                     WT cm = lane < nalive0 ? (WT)1 << ordcls : (WT)0;
                     bool stop = false;
-#pragma unroll
-                    for (int q = 0; q < LPL; ++q) {
-                        if (q >= nq || stop) break;
-                        WT v = ev[q].w[0];
-                        const u32 myk = ek[q];
+                    for (int q = 0; q < nq && !stop; ++q) {
+                        WT v = ev[0].w[0];
+                        const u32 myk = ek[0];
+                        // the next block is fetched while this one is reduced (the image table goes over the list
+                        // only behind the loop, after the last block has been read)
+                        if (q + 1 < nq) load_block(q + 1, ek[0], ev[0]);
                         for (int k = 0; k < nk; ++k) {                 // the kills so far, in their order
                             const WT m = (WT)1 << rl32(mycode, k);
                             const WT w = sizeof(WT) == 8 ? (WT)rl64((u64)kvec, k) : (WT)rl32((u32)kvec, k);

@@ -15,7 +15,8 @@ def tri_list(v):
     """the listing rounds of phase d (counters 43-47): every round, also those that end with an empty list"""
     r = max(v[47], 1)
     return (f"\n     listing rounds/win={v[47]/v[8]:.2f}: trips of the busiest lane/round={v[43]/r:.2f} "
-            f"triangles/round={v[44]/r:.1f} waves with triangles/round={v[45]/r:.2f}")
+            f"triangles/round={v[44]/r:.1f} waves with triangles/round={v[45]/r:.2f} "
+            f"rounds that listed more than twice the capacity/win={v[46]/v[8]:.3f}")
 NW = int(sys.argv[1]) if len(sys.argv) > 1 else 256      # 256 = one workgroup per CU (latency); 4096: CUs shared
 if os.environ.get("TDA_CLASS_WORDS"):                      # e.g. "1,1": the first-pass widths bench.py uses
     ctx.set_class_words(*[int(x) for x in os.environ["TDA_CLASS_WORDS"].split(",")])
