@@ -39,9 +39,11 @@
 //         exactly once per H1 class that ever dies (tens per window).  All non-trivial triangles of a
 //         chunk are listed at once; wave 0 reduces the list in registers (the substitutions are
 //         linear maps) and the psi table is rewritten once per chunk through a class -> image table.
-//      Chunks in which no class is alive and none is born skip c and d (every psi entry is zero); once, in that
-//      state, every remaining edge already has a common neighbour, nothing can happen any more and the sweep
-//      stops.  Candidate-rich chunks decide b by Boruvka rounds of the whole workgroup.
+//      Chunks in which no class is alive and none is born (quiet chunks) skip c and d (every psi entry is zero).
+//      Every chunk that ENDS with no class alive -- a quiet one, or a busy one in which the last class died -- is
+//      followed by a coverage scan: the edges up to the first one without a common neighbour only join the adjacency
+//      rows, and the next chunk starts at it; once every remaining edge has a common neighbour, nothing can happen
+//      any more and the sweep stops.  Candidate-rich chunks decide b by Boruvka rounds of the whole workgroup.
 //      The multiset of (birth,death) pairs equals that of any persistence algorithm on the
 //      same filtration; tie order inside equal diameters does not change it.
 //  P4  rows are written as float64 (float32-exact) pairs: H0 ascending death then the essential
@@ -1734,7 +1736,18 @@ __device__ __forceinline__ void rips_sweep(int n, int E, int Ev, const u16* rank
         // The end of the story: no class is alive and EVERY remaining edge already has a common neighbour, now and
         // (adjacency only grows) at its own time.  Then no remaining edge is a candidate: no component can merge,
         // no class can be born, and with nothing alive nothing can die -- the rest of the filtration adds no row.
-        if (quiet) {
+        // The scan is entered from every chunk that ends CALM: no status bit and no class alive behind its last
+        // reduction round.  A quiet chunk is calm by definition; a busy chunk in which the last class died leaves the
+        // same state -- the rows hold exactly the edges below r0 + clen and every class vector is zero (dead classes
+        // were substituted out) -- so it scans right here instead of sending one more chunk through phases a and b
+        // to find nothing alive and nothing born.  A chunk that phase b cut short (clen < NT) does NOT scan: it ends
+        // just before a known candidate, the birth that found no class bit, and a scan would spend a round to find
+        // ru == from.  (Computed here, behind phase d, from values that are live anyway: nothing crosses phase d.)
+        bool calm = status == 0 && clen == NT;
+#pragma unroll
+        for (int c = 0; c < W; ++c) calm = calm && alive[c] == 0;
+        if (calm && !quiet) PROF_COUNT(2, 1);
+        if (calm) {
             int from = r0 + clen;                 // the adjacency rows hold exactly the edges of rank below `from`
             // every thread walks its own residue class of the remaining edges and remembers where it stopped: an edge
             // that is covered stays covered, so no edge is looked at twice over all the checks of a window
