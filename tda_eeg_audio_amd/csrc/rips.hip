@@ -52,11 +52,17 @@
 // LDS per workgroup: 26 KB (n = 47, 64 classes), 32 KB (128 classes) .. 52.5 KB (point cloud of up to 124 points, first
 // pass: a third of a CU) .. 79.2 KB (the wide passes of a 124-point cloud).
 // Class capacity ladder: a first pass, then widening passes that redo only flagged windows (tda_set_retry_policy), then a
-// last rung with the class vectors in HBM and no capacity limit (rips_sweep_total).
+// last rung with the class vectors in HBM and no capacity limit (rips_sweep_total).  The rule is in rips_ladder.h; all
+// three flavours run it through run_ladder / launch_pass below.
 // No MFMA: this is irregular integer work; the roofline that binds it is vector issue / LDS latency.
 #include "common.h"
 #include "corr_dist_dev.h"
+#include "rips_ladder.h"
 #include <stdlib.h>
+
+static_assert(TDA_RETRY_AUTO == rips_ladder::AUTO && TDA_RETRY_FIRST_PASS == rips_ladder::FIRST_PASS &&
+              TDA_RETRY_ONLY == rips_ladder::ONLY && TDA_RETRY_ONE_STEP == rips_ladder::ONE_STEP &&
+              TDA_RETRY_LAST_RUNG == rips_ladder::LAST_RUNG, "rips_ladder::plan takes tda_ctx::retry_policy as it is");
 
 #ifndef CLOUD_NB
 #define CLOUD_NB 8192          // ranking buckets of the point-cloud flavour
@@ -2710,31 +2716,10 @@ static tda_status order_h1(tda_ctx* ctx, double* h1, int h1_cap, int* h1_cnt, in
     return launch_diagram_finish(ctx, &one, 1, n_win, st);
 }
 
-template <int NVW, int W>
-static tda_status launch_dm_t(tda_ctx* ctx, const double* dm, int n_win, int n, float thresh, int symmetrise,
-                              RipsOut out, hipStream_t st, int retry_only = 0)
-{
-    const int NT = 256;
-    const RipsLayout L = make_layout(n, W * 8, n * (n - 1) / 2 * 4, NT);
-    auto kern = retry_only ? rips_dm_kernel<256, NVW, W, u64, true> : rips_dm_kernel<256, NVW, W, u64, false>;
-    if (L.total > 48 * 1024)
-        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    // retry passes work off the list of flagged windows on a grid that fits the chip; the widest variant (240 VGPRs, > 80 KB LDS)
-    // needs a nearly empty CU per workgroup, so it asks for few of them
-    const int rgrid = W >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;
-    const int grid = retry_only ? (n_win < rgrid ? n_win : rgrid) : n_win;
-    if (retry_only) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
-    {
-        ProbeScope probe(ctx, retry_only ? -1 : TDA_PROBE_RIPS_DM, st);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), L.total, st, dm, n_win, n, thresh, symmetrise, L, out,
-                           ctx->retry_ctr);
-    }
-    TDA_HIP(ctx, hipGetLastError());
-    return TDA_OK;
-}
-
 static const int LDS_MAX = 160 * 1024;
+#ifndef CLOUD_NT
+#define CLOUD_NT 512           // workgroup size of the point-cloud flavour (one workgroup per CU: LDS)
+#endif
 
 size_t rips_total_scratch_bytes() { return (size_t)TOT_SLOTS * TOT_SLOT_WORDS * sizeof(u64); }
 
@@ -2749,22 +2734,63 @@ static RipsLayout total_layout(int n, int aux_bytes, int NT)
     if (L.total < need) { L.total = need; L.guard[4] = L.total; }
     return L;
 }
-static tda_status launch_dm_total(tda_ctx* ctx, const double* dm, int n_win, int n, float thresh, int symmetrise, RipsOut out,
-                                  hipStream_t st)
+
+// ---- the class capacity ladder: one rule (rips_ladder.h) for matrices, fused EEG windows and clouds ----
+// A first pass (one window per workgroup), widening passes that redo the windows flagged TDA_WIN_CLASS_OVERFLOW at the next
+// capacities while their tables fit LDS (a pass whose windows are all fine exits at once), and the last rung, which redoes
+// whatever is still flagged with the class vectors in HBM: compute_eeg_persistence and compute_audio_persistence never
+// refuse an input (scripts/utils.py:140, :131).  A flavour below supplies its rungs, the kernel and the layout of a rung.
+enum RipsPass { PASS_FIRST, PASS_RETRY, PASS_LAST };
+
+// what a ProbeScope of `which` hands to the probed kernel: the span of that probe if it is armed
+static unsigned long long* armed_span(const tda_ctx* ctx, int which) { return ctx->probe[which].armed ? ctx->probe[which].span : nullptr; }
+
+// One launch of a ladder.  PASS_FIRST: a workgroup per window, inside the probe `probe_id`.  PASS_RETRY: the flagged
+// windows are listed and at most `rgrid` workgroups (what fits the chip at once) work the list off.  PASS_LAST: the same
+// on TOT_SLOTS workgroups, one per HBM slot.
+template <class K, class... A>
+static tda_status launch_pass(tda_ctx* ctx, K kern, RipsPass pass, int rgrid, int nt, int lds, int probe_id, int n_win,
+                              const RipsOut& out, hipStream_t st, A... args)
 {
-    const RipsLayout L = total_layout(n, n * (n - 1) / 2 * 4, 256);
-    auto kern = rips_dm_total_kernel<256>;
-    if (L.total > 48 * 1024)
-        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3(TOT_SLOTS), dim3(256), L.total, st, dm, n_win, n, thresh, symmetrise, L, out,
-                       ctx->total_scratch, ctx->retry_ctr);
+    if (lds > 48 * 1024)
+        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const dim3 grid = pass == PASS_LAST ? dim3(TOT_SLOTS) : dim3(pass == PASS_RETRY && rgrid < n_win ? rgrid : n_win);
+    if (pass != PASS_FIRST) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
+    {
+        ProbeScope probe(ctx, pass == PASS_FIRST ? probe_id : -1, st);
+        hipLaunchKernelGGL(kern, grid, dim3(nt), lds, st, args...);
+    }
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
-#ifndef CLOUD_NT
-#define CLOUD_NT 512           // workgroup size of the point-cloud flavour (one workgroup per CU: LDS)
-#endif
+
+// Runs the plan of a flavour under the context's policy: step(capacity, retry) launches a rung, last() the last rung; a
+// status other than TDA_OK ends the sequence.  The list of the stream goes into `out` first, the H1 rows are ordered last.
+template <class STEP, class LAST>
+static tda_status run_ladder(tda_ctx* ctx, const rips_ladder::Rungs& rungs, int n_win, RipsOut& out, hipStream_t st,
+                             STEP step, LAST last)
+{
+    tda_status rc = retry_list_take(ctx, n_win, out, st);
+    const rips_ladder::Plan plan = rips_ladder::plan(ctx->retry_policy, rungs);
+    for (int i = 0; rc == TDA_OK && i < plan.n; ++i) rc = step(plan.step[i].cap, plan.step[i].retry);
+    if (rc == TDA_OK && plan.last) rc = last();
+    if (rc != TDA_OK) return rc;
+    return order_h1(ctx, out.h1, out.h1_cap, out.h1_cnt, n_win, st);
+}
+
+// the kernel of a rung of W class words (n <= 64: one vertex word)
+static auto dm_kernel(bool one_vertex_word, int W, bool retry)
+{
+    if (!one_vertex_word)
+        return W == 1 ? rips_dm_kernel<256, 2, 1, u64, false>
+                      : retry ? rips_dm_kernel<256, 2, 2, u64, true> : rips_dm_kernel<256, 2, 2, u64, false>;
+    switch (W) {
+    case 1: return rips_dm_kernel<256, 1, 1, u64, false>;
+    case 2: return retry ? rips_dm_kernel<256, 1, 2, u64, true> : rips_dm_kernel<256, 1, 2, u64, false>;
+    case 4: return retry ? rips_dm_kernel<256, 1, 4, u64, true> : rips_dm_kernel<256, 1, 4, u64, false>;
+    default: return rips_dm_kernel<256, 1, 8, u64, true>;     // (n <= 47: 512 bits cover the theoretical maximum of 506 alive classes)
+    }
+}
 
 tda_status launch_rips_dm(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
                           double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt, int* status,
@@ -2775,116 +2801,60 @@ tda_status launch_rips_dm(tda_ctx* ctx, const double* dm, int n_win, int n, doub
     if (h0_cap < n) TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_cap must be >= n");
     RipsOut out{h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status};
     const float th = (float)thresh;
-    tda_status rc = retry_list_take(ctx, n_win, out, st);
-    if (rc != TDA_OK) return rc;
-    int W = ctx->words_dm < 1 ? 1 : ctx->words_dm;      // (32-bit class words exist in the fused EEG kernel only)
-    // largest class capacity that still fits the 160 KiB LDS
-    while (W > 1 && make_layout(n, W * 8, n * (n - 1) / 2 * 4, 256).total > LDS_MAX) W >>= 1;
-    const bool last_only = ctx->retry_policy == TDA_RETRY_LAST_RUNG;
-    const bool do_first = ctx->retry_policy != TDA_RETRY_ONLY && !last_only;
-    const bool do_ladder = ctx->retry_policy != TDA_RETRY_FIRST_PASS && !last_only;
-    const bool one_step = ctx->retry_policy == TDA_RETRY_ONE_STEP;
-    rc = TDA_OK;
-    if (last_only) {
-    } else if (n <= 64) {
-        if (!do_first) {}
-        else if (W == 1) rc = launch_dm_t<1, 1>(ctx, dm, n_win, n, th, symmetrise, out, st);
-        else if (W == 2) rc = launch_dm_t<1, 2>(ctx, dm, n_win, n, th, symmetrise, out, st);
-        else rc = launch_dm_t<1, 4>(ctx, dm, n_win, n, th, symmetrise, out, st);
-        // widening retries: windows that ran out of class bits are redone with 2x, 4x the bits while
-        // the table still fits LDS (n <= 47: 512 bits cover the theoretical maximum of 506 alive
-        // classes).  A retry launch whose windows are all fine exits at once.
-        for (int Wr = 2 * W; do_ladder && rc == TDA_OK && Wr <= 8; Wr *= 2) {
-            if (one_step && Wr > 2 * W) break;
-            if (make_layout(n, Wr * 8, n * (n - 1) / 2 * 4, 256).total > LDS_MAX) break;
-            if (Wr == 2) rc = launch_dm_t<1, 2>(ctx, dm, n_win, n, th, symmetrise, out, st, 1);
-            else if (Wr == 4) rc = launch_dm_t<1, 4>(ctx, dm, n_win, n, th, symmetrise, out, st, 1);
-            else rc = launch_dm_t<1, 8>(ctx, dm, n_win, n, th, symmetrise, out, st, 1);
-        }
-    } else {
-        if (!do_first) {}
-        else if (W == 1) rc = launch_dm_t<2, 1>(ctx, dm, n_win, n, th, symmetrise, out, st);
-        else rc = launch_dm_t<2, 2>(ctx, dm, n_win, n, th, symmetrise, out, st);
-        if (do_ladder && rc == TDA_OK && W == 1 && make_layout(n, 16, n * (n - 1) / 2 * 4, 256).total <= LDS_MAX)
-            rc = launch_dm_t<2, 2>(ctx, dm, n_win, n, th, symmetrise, out, st, 1);
-    }
-    // the last rung: whatever is still flagged (more than 512 / 128 classes alive at once) is redone with the class
-    // vectors in HBM -- compute_eeg_persistence never refuses a matrix (scripts/utils.py:140)
-    if (rc == TDA_OK && ((do_ladder && !one_step) || last_only)) rc = launch_dm_total(ctx, dm, n_win, n, th, symmetrise, out, st);
-    if (rc != TDA_OK) return rc;
-    return order_h1(ctx, h1, h1_cap, h1_cnt, n_win, st);
+    const int aux = n * (n - 1) / 2 * 4;
+    bool fits[4];                                       // the class capacities that still fit the 160 KiB LDS
+    for (int i = 0; i < 4; ++i) fits[i] = make_layout(n, 8 << i, aux, 256).total <= LDS_MAX;
+    return run_ladder(ctx, rips_ladder::dm_rungs(ctx->words_dm, n <= 64, fits), n_win, out, st,
+        [&](int W, bool retry) {
+            const RipsLayout L = make_layout(n, W * 8, aux, 256);
+            // the widest variant (240 VGPRs, > 80 KB LDS) needs a nearly empty CU per workgroup, so it asks for few of them
+            const int rgrid = W >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;
+            return launch_pass(ctx, dm_kernel(n <= 64, W, retry), retry ? PASS_RETRY : PASS_FIRST, rgrid, 256, L.total,
+                               TDA_PROBE_RIPS_DM, n_win, out, st, dm, n_win, n, th, symmetrise, L, out, ctx->retry_ctr);
+        },
+        [&] {
+            const RipsLayout L = total_layout(n, aux, 256);
+            return launch_pass(ctx, rips_dm_total_kernel<256>, PASS_LAST, 0, 256, L.total, -1, n_win, out, st,
+                               dm, n_win, n, th, symmetrise, L, out, ctx->total_scratch, ctx->retry_ctr);
+        });
 }
 
-template <int NB, bool RES, int W, bool RETRY, typename WT = u64, class SRC>
-static tda_status launch_eeg_t(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float thresh, RipsOut out,
-                               double* dist, double* corr, hipStream_t st)
-{
-    RipsLayout L = make_layout(n_ch, W * (int)sizeof(WT), n_ch * (n_ch - 1) / 2 * 4, 256);
-    if ((size_t)L.total < CdLayout<NB>::BYTES) L.total = (int)((CdLayout<NB>::BYTES + 15) & ~(size_t)15);
-    if (L.total > LDS_MAX) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "window too large for LDS");
-    auto kern = eeg_kernel_of<NB, RES, W, RETRY, WT>(&win);
-    if (L.total > 48 * 1024)
-        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    const int rgrid = W >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;
-    const int grid = RETRY ? (n_win < rgrid ? n_win : rgrid) : n_win;
-    if (RETRY) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
-    {
-        ProbeScope probe(ctx, RETRY ? -1 : TDA_PROBE_RIPS_DM, st);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), L.total, st, win, n_win, n_ch, n_t, thresh, L, out, dist, corr,
-                           ctx->retry_ctr);
-    }
-    TDA_HIP(ctx, hipGetLastError());
-    return TDA_OK;
-}
-
-// the last rung of the fused ladder (as launch_dm_total)
+// the fused kernel of a rung: 32 class bits are u32 x 1, 64 / 128 / 512 are u64 x 1 / 2 / 8
 template <bool RES, class SRC>
-static tda_status launch_eeg_total(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float thresh, RipsOut out,
-                                   double* dist, double* corr, hipStream_t st)
+static auto eeg_kernel(const SRC* src, int bits, bool retry)
 {
-    RipsLayout L = total_layout(n_ch, n_ch * (n_ch - 1) / 2 * 4, 256);
-    if ((size_t)L.total < CdLayout<3>::BYTES) { L.total = (int)((CdLayout<3>::BYTES + 15) & ~(size_t)15); L.guard[4] = L.total; }
-    auto kern = eeg_window_total_kernel<3, RES, SRC>;
-    if (L.total > 48 * 1024)
-        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3(TOT_SLOTS), dim3(256), L.total, st, win, n_win, n_ch, n_t, thresh, L, out, dist, corr,
-                       ctx->total_scratch, ctx->retry_ctr);
-    TDA_HIP(ctx, hipGetLastError());
-    return TDA_OK;
+    switch (bits) {
+    case 32: return eeg_kernel_of<3, RES, 1, false, u32>(src);
+    case 64: return retry ? eeg_kernel_of<3, RES, 1, true, u64>(src) : eeg_kernel_of<3, RES, 1, false, u64>(src);
+    case 128: return retry ? eeg_kernel_of<3, RES, 2, true, u64>(src) : eeg_kernel_of<3, RES, 2, false, u64>(src);
+    default: return eeg_kernel_of<3, RES, 8, true, u64>(src);
+    }
 }
 
+// Ladder of the fused kernel: every wider pass recomputes the flagged windows from the samples (the matrix was never
+// stored).  512 bits cover the theoretical maximum of 506 classes alive at once for 47 points, not the 529 of 48: those
+// go on to the last rung.  The MFMA accumulator image of the products (CdLayout<3>) shares the LDS of every rung.
 template <bool RES, class SRC>
-static tda_status launch_eeg_ladder(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float th, RipsOut out,
+static tda_status launch_eeg_ladder(tda_ctx* ctx, const SRC& win, int n_win, int n_ch, int n_t, float th, RipsOut& out,
                                     double* dist, double* corr, hipStream_t st)
 {
-    const bool last_only = ctx->retry_policy == TDA_RETRY_LAST_RUNG;
-    const bool do_first = ctx->retry_policy != TDA_RETRY_ONLY && !last_only;
-    const bool do_ladder = ctx->retry_policy != TDA_RETRY_FIRST_PASS && !last_only;
-    const bool one_step = ctx->retry_policy == TDA_RETRY_ONE_STEP;
-    tda_status rc = TDA_OK;
-    // ladder of the fused kernel: 32 (words_dm = 0) -> 64 -> 128 -> 512 class bits -> the last rung; every wider pass
-    // recomputes the flagged windows from the samples (the matrix was never stored).  512 bits cover the theoretical
-    // maximum of 506 classes alive at once for 47 points, not the 529 of 48: those go on to the last rung
-    const int first = ctx->words_dm >= 2 ? 2 : ctx->words_dm;       // 0, 1 or 2
-    if (do_first) {
-        if (first == 0) rc = launch_eeg_t<3, RES, 1, false, u32>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-        else if (first == 1) rc = launch_eeg_t<3, RES, 1, false>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-        else rc = launch_eeg_t<3, RES, 2, false>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-    }
-    int rung = 0;
-    if (do_ladder && rc == TDA_OK && first == 0 && !(one_step && rung++ >= 1))
-        rc = launch_eeg_t<3, RES, 1, true>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-    if (do_ladder && rc == TDA_OK && first <= 1 && !(one_step && rung++ >= 1))
-        rc = launch_eeg_t<3, RES, 2, true>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-    if (do_ladder && rc == TDA_OK && !(one_step && rung++ >= 1))
-        rc = launch_eeg_t<3, RES, 8, true>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-    // the last rung, under the conditions of launch_rips_dm: whatever is still flagged (more than 512 classes alive at
-    // once: 48 channels only) is redone with the class vectors in HBM
-    if (rc == TDA_OK && ((do_ladder && !one_step) || last_only))
-        rc = launch_eeg_total<RES>(ctx, win, n_win, n_ch, n_t, th, out, dist, corr, st);
-    return rc;
+    const int aux = n_ch * (n_ch - 1) / 2 * 4;
+    const int cd_bytes = (int)((CdLayout<3>::BYTES + 15) & ~(size_t)15);
+    return run_ladder(ctx, rips_ladder::eeg_rungs(ctx->words_dm), n_win, out, st,
+        [&](int bits, bool retry) -> tda_status {
+            RipsLayout L = make_layout(n_ch, bits / 8, aux, 256);
+            if ((size_t)L.total < CdLayout<3>::BYTES) L.total = cd_bytes;
+            if (L.total > LDS_MAX) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "window too large for LDS");
+            const int rgrid = (bits >> 6) >= 8 ? RETRY_GRID_WIDE : RETRY_GRID;   // (eight u64 words: as launch_rips_dm)
+            return launch_pass(ctx, eeg_kernel<RES>(&win, bits, retry), retry ? PASS_RETRY : PASS_FIRST, rgrid, 256, L.total,
+                               TDA_PROBE_RIPS_DM, n_win, out, st, win, n_win, n_ch, n_t, th, L, out, dist, corr, ctx->retry_ctr);
+        },
+        [&] {
+            RipsLayout L = total_layout(n_ch, aux, 256);
+            if ((size_t)L.total < CdLayout<3>::BYTES) { L.total = cd_bytes; L.guard[4] = L.total; }
+            return launch_pass(ctx, eeg_window_total_kernel<3, RES, SRC>, PASS_LAST, 0, 256, L.total, -1, n_win, out, st,
+                               win, n_win, n_ch, n_t, th, L, out, dist, corr, ctx->total_scratch, ctx->retry_ctr);
+        });
 }
 
 template <class SRC>
@@ -2897,7 +2867,6 @@ static tda_status launch_eeg_source(tda_ctx* ctx, const SRC& src, int n_win, int
     if (n_t < 2 || n_t > CD_RES_CHUNKS * CD_TCH) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "the fused EEG kernel takes windows of 2..256 samples (the reference has 250)");
     if (h0_cap < n_ch) TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_cap must be >= n_ch");
     RipsOut out{h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status};
-    { const tda_status rc0 = retry_list_take(ctx, n_win, out, st); if (rc0 != TDA_OK) return rc0; }
     // The window is fetched twice (means, then centred products): 128 VGPRs, four workgroups per CU.  The second
     // fetch misses the 4 MB L2 of the XCD (128 windows in flight there) and shows in FETCH_SIZE (181 KB per window
     // against 95 KB algorithmic), but the windows in flight on the whole chip are 96 MB, inside the 256 MiB Infinity
@@ -2905,10 +2874,8 @@ static tda_status launch_eeg_source(tda_ctx* ctx, const SRC& src, int n_win, int
     // (one fetch, 148 VGPRs, three workgroups per CU) measured 11 % slower on the EEG-only pass and 2 % end to end;
     // it stays available: TDA_EEG_RESIDENT=1
     static const bool stream_twice = getenv("TDA_EEG_RESIDENT") == nullptr;
-    const tda_status rc = stream_twice ? launch_eeg_ladder<false>(ctx, src, n_win, n_ch, n_t, (float)thresh, out, dist, corr, st)
-                                       : launch_eeg_ladder<true>(ctx, src, n_win, n_ch, n_t, (float)thresh, out, dist, corr, st);
-    if (rc != TDA_OK) return rc;
-    return order_h1(ctx, h1, h1_cap, h1_cnt, n_win, st);
+    return stream_twice ? launch_eeg_ladder<false>(ctx, src, n_win, n_ch, n_t, (float)thresh, out, dist, corr, st)
+                        : launch_eeg_ladder<true>(ctx, src, n_win, n_ch, n_t, (float)thresh, out, dist, corr, st);
 }
 
 tda_status launch_eeg_windows(tda_ctx* ctx, const double* win, int n_win, int n_ch, int n_t, double thresh, double* dist,
@@ -2944,31 +2911,15 @@ tda_status launch_eeg_ragged(tda_ctx* ctx, const double* sig, const long long* s
     return launch_eeg_source(ctx, src, n_win, n_ch, win_len, thresh, dist, corr, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status, st);
 }
 
-template <int W, typename WT, bool NARROW = false>
-static tda_status launch_cloud_t(tda_ctx* ctx, const double* src, const int* aux, int n_win, int n_t_or_pcap,
-                                 int dim, int subsample, int mode, int normalise, float thresh, int p_max,
-                                 int* n_points, RipsOut out, hipStream_t st, int retry_only)
+// the cloud kernel of a rung: 32 class bits are u32 x 1 and a first pass only (narrow: the fixed layout of struct NL, three
+// workgroups per CU), 64 / 128 are u64 x 1 / 2; a retry kernel is never narrow
+static auto cloud_kernel(int bits, bool retry, bool narrow)
 {
-    const int NT = NARROW ? NARROW_NT : CLOUD_NT;
-    const RipsLayout L = NARROW ? make_narrow_layout(p_max, dim)
-                                : make_layout(p_max, W * (int)sizeof(WT), p_max * dim * 8, NT);
-    if (L.total > LDS_MAX || L.total == 0) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "point cloud too large for LDS");
-    auto kern = retry_only ? rips_cloud_kernel<CLOUD_NT, W, WT, true, false>
-                           : rips_cloud_kernel<(NARROW ? NARROW_NT : CLOUD_NT), W, WT, false, NARROW>;
-    if (L.total > 48 * 1024)
-        TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    const int rgrid = W >= 2 ? RETRY_GRID / 2 : RETRY_GRID;      // (what fits the chip at once: one / two workgroups per CU)
-    const int grid = retry_only ? (n_win < rgrid ? n_win : rgrid) : n_win;
-    if (retry_only) { const tda_status rc = retry_collect(ctx, out, n_win, st); if (rc != TDA_OK) return rc; }
-    {
-        ProbeScope probe(ctx, retry_only ? -1 : TDA_PROBE_RIPS_CLOUD, st);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), L.total, st, src, aux, n_win, n_t_or_pcap, dim, subsample, mode,
-                           normalise, thresh, L, p_max, n_points, out, probe.on ? probe.span : nullptr,
-                           ctx->retry_ctr);
+    switch (bits) {
+    case 32: return narrow ? rips_cloud_kernel<NARROW_NT, 1, u32, false, true> : rips_cloud_kernel<CLOUD_NT, 1, u32, false, false>;
+    case 64: return retry ? rips_cloud_kernel<CLOUD_NT, 1, u64, true, false> : rips_cloud_kernel<CLOUD_NT, 1, u64, false, false>;
+    default: return rips_cloud_kernel<CLOUD_NT, 2, u64, true, false>;
     }
-    TDA_HIP(ctx, hipGetLastError());
-    return TDA_OK;
 }
 
 tda_status launch_rips_cloud(tda_ctx* ctx, const double* src, const int* aux, int n_win, int n_t_or_pcap, int dim,
@@ -2995,46 +2946,27 @@ tda_status launch_rips_cloud(tda_ctx* ctx, const double* src, const int* aux, in
     if (h0_cap < p_max) TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_cap must be >= max points per cloud");
     RipsOut out{h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, status};
     const float th = (float)thresh;
-    tda_status rc = retry_list_take(ctx, n_win, out, st);
-    if (rc != TDA_OK) return rc;
-    // class capacity ladder: 32 bits (two workgroups per CU for 124-point clouds), then 64, then 128
-    // while the table fits LDS; each wider pass only redoes the windows the previous one flagged
-    const bool fits128 = make_layout(p_max, 16, p_max * dim * 8, CLOUD_NT).total <= LDS_MAX;
-    const bool last_only = ctx->retry_policy == TDA_RETRY_LAST_RUNG;
-    const bool do_first = ctx->retry_policy != TDA_RETRY_ONLY && !last_only;
-    const bool do_ladder = ctx->retry_policy != TDA_RETRY_FIRST_PASS && !last_only;
-    int first = 1;
-    if (ctx->words_cloud == 1) {
-        // first pass: 32 class bits, the narrow layout (three workgroups per CU) whenever the cloud size allows it
-        static const bool no_narrow = getenv("TDA_CLOUD_WIDE_FIRST") != nullptr;
-        const bool narrow = !no_narrow && make_narrow_layout(p_max, dim).total != 0;
-        if (do_first && narrow)
-            rc = launch_cloud_t<1, u32, true>(ctx, src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, p_max,
-                                              n_points, out, st, 0);
-        else if (do_first)
-            rc = launch_cloud_t<1, u32>(ctx, src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, p_max,
-                                        n_points, out, st, 0);
-        first = 0;
-    }
-    if (rc == TDA_OK && (first ? do_first : do_ladder))
-        rc = launch_cloud_t<1, u64>(ctx, src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, p_max,
-                                    n_points, out, st, first ? 0 : 1);
-    if (do_ladder && rc == TDA_OK && fits128 && !(ctx->retry_policy == TDA_RETRY_ONE_STEP && !first))
-        rc = launch_cloud_t<2, u64>(ctx, src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, p_max,
-                                    n_points, out, st, 1);
-    // the last rung: whatever is still flagged (more than 64 / 128 classes alive at once) is redone with the class vectors
-    // in HBM -- compute_audio_persistence never refuses a cloud (scripts/utils.py:131)
-    if (rc == TDA_OK && ((do_ladder && ctx->retry_policy != TDA_RETRY_ONE_STEP) || last_only)) {
-        const RipsLayout L = total_layout(p_max, p_max * dim * 8, CLOUD_NT);
-        auto kern = rips_cloud_total_kernel<CLOUD_NT>;
-        if (L.total > 48 * 1024)
-            TDA_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-        rc = retry_collect(ctx, out, n_win, st);
-        if (rc != TDA_OK) return rc;
-        hipLaunchKernelGGL(kern, dim3(TOT_SLOTS), dim3(CLOUD_NT), L.total, st, src, aux, n_win, n_t_or_pcap, dim, subsample, mode,
-                           normalise, th, L, p_max, n_points, out, ctx->total_scratch, ctx->retry_ctr);
-        TDA_HIP(ctx, hipGetLastError());
-    }
-    if (rc != TDA_OK) return rc;
-    return order_h1(ctx, h1, h1_cap, h1_cnt, n_win, st);
+    const int aux_bytes = p_max * dim * 8;
+    const bool fits128 = make_layout(p_max, 16, aux_bytes, CLOUD_NT).total <= LDS_MAX;
+    // the 32-bit first pass takes the narrow layout whenever the cloud size allows it
+    static const bool no_narrow = getenv("TDA_CLOUD_WIDE_FIRST") != nullptr;
+    const bool narrow_ok = !no_narrow && make_narrow_layout(p_max, dim).total != 0;
+    return run_ladder(ctx, rips_ladder::cloud_rungs(ctx->words_cloud, fits128), n_win, out, st,
+        [&](int bits, bool retry) -> tda_status {
+            const bool narrow = bits == 32 && narrow_ok;
+            const RipsLayout L = narrow ? make_narrow_layout(p_max, dim) : make_layout(p_max, bits / 8, aux_bytes, CLOUD_NT);
+            if (L.total > LDS_MAX || L.total == 0) TDA_FAIL(ctx, TDA_ERR_UNSUPPORTED, "point cloud too large for LDS");
+            const int W = bits == 128 ? 2 : 1;
+            const int rgrid = W >= 2 ? RETRY_GRID / 2 : RETRY_GRID;      // (what fits the chip at once: one / two workgroups per CU)
+            return launch_pass(ctx, cloud_kernel(bits, retry, narrow), retry ? PASS_RETRY : PASS_FIRST, rgrid,
+                               narrow ? NARROW_NT : CLOUD_NT, L.total, TDA_PROBE_RIPS_CLOUD, n_win, out, st,
+                               src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, L, p_max, n_points, out,
+                               retry ? nullptr : armed_span(ctx, TDA_PROBE_RIPS_CLOUD), ctx->retry_ctr);
+        },
+        [&] {
+            const RipsLayout L = total_layout(p_max, aux_bytes, CLOUD_NT);
+            return launch_pass(ctx, rips_cloud_total_kernel<CLOUD_NT>, PASS_LAST, 0, CLOUD_NT, L.total, -1, n_win, out, st,
+                               src, aux, n_win, n_t_or_pcap, dim, subsample, mode, normalise, th, L, p_max, n_points, out,
+                               ctx->total_scratch, ctx->retry_ctr);
+        });
 }

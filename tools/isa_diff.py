@@ -5,7 +5,8 @@ tools/isa_diff.py -- are the gfx950 kernels of csrc/ instruction for instruction
 Compiles each csrc/<file>.hip device-only (the Makefile's flags) from the working tree and from `git show REV:...`,
 disassembles both code objects and compares every kernel whose mangled name matches, line by line.  Addresses are
 dropped, and so is the literal of the s_add_u32 / s_addc_u32 pair after an s_getpc_b64 (PC-relative offsets to constant
-data, which move whenever a kernel is added anywhere in the file).  No GPU needed.
+data, which move whenever a kernel is added anywhere in the file).  A kernel REV has and the working tree has not is
+reported as MISSING, one the working tree has and REV has not as ADDED; either makes the exit status 1.  No GPU needed.
 An instantiation whose template arguments grew since REV is paired with its counterpart through RENAMED (mangled
 prefix at REV -> mangled prefix now):
     python3 tools/isa_diff.py --files wasserstein --match wasserstein_kernel
@@ -114,6 +115,11 @@ def main():
         os.rename(old_dir, old_csrc)
         for name in a.files:
             (old, old_res), (new, new_res) = disasm(old_csrc, name, tmp, "old"), disasm(CSRC, name, tmp, "new")
+            paired = {counterpart(k, new) for k in old}
+            for k in sorted(new):                        # kernels the working tree has and REV has not
+                if pat.search(k) and k not in paired:
+                    bad += 1
+                    print(f"ADDED  {k}")
             for k in sorted(old):
                 if not pat.search(k):
                     continue
