@@ -595,6 +595,64 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap,
                                const double* grid, int n_grid, int n_levels, double* out);
 
+/* ---- Euler characteristic curves and simplex-count curves of Rips complexes ------------
+ * The Euler characteristic of the clique (Vietoris-Rips) complex of a window as the scale sweeps a grid, and the simplex
+ * counts it is made of: the summary of Santos et al. (2019) for functional brain networks, and the Euler characteristic
+ * curve of Dlotko and Gurnari.  It is the one output here that looks above the triangles (K = 3: tetrahedra).  The
+ * contract is this text; tests/euler_ref.py evaluates it.
+ *   Keys.       A window has n vertices and float32 keys k[a][b], a > b: THE KEYS THE RIPS ENTRY POINTS USE for the same
+ *               input, so curve and diagram describe one complex.
+ *                 Distance matrices (n_win, n, n) float64, 1 <= n <= TDA_MAX_POINTS.  symmetrise = 1:
+ *                   v = (D[a][b] + D[b][a]) / 2; if v < 0 then v = 0; k = (float)v.  symmetrise = 0: k = (float)D[b][a],
+ *                   the entry (i, j) with i < j, as tda_rips_dm_batch words it.
+ *                 Point clouds, in the two forms of the cloud Rips entry points: explicit (n_win, p_cap, dim) clouds with
+ *                   n_pts and normalise (tda_cloud_rips_batch), or Takens windows with tau, dim <= TDA_MAX_DIM and
+ *                   subsample (tda_takens_rips_batch: always normalised).  Per-column min-max (scripts/utils.py:127-130,
+ *                   range 0 -> 1), then sklearn's distance: d2 = -2 x.y (x.y = fma(x2, y2, fma(x1, y1, x0 * y0)) and so
+ *                   on), d2 += |x|^2, d2 += |y|^2 with x the point of larger index, d2 = 0 unless d2 > 0, sqrt, (float).
+ *   Grid.       t[g], g < n_grid: float64, 1 <= n_grid <= TDA_MAX_GRID, any values in any order.
+ *   Presence.   Edge {a, b} is present at g iff k <= (float)thresh and (double)k <= t[g]: plain IEEE comparisons, so a NaN
+ *               key or a NaN grid point makes the edge absent; inclusive, so a grid point equal to a key has the edge.
+ *   Counts.     f_j(g), j = 0..K: the number of (j + 1)-subsets of the vertices whose pairs are all present at g;
+ *               f_0 = n.  K = max_dim, 1 <= K <= TDA_EC_MAX_DIM.  chi(g) = sum_j (-1)^j f_j(g): the Euler characteristic
+ *               of the K-skeleton of the Rips complex at scale min(t[g], thresh).
+ *   Outputs.    counts (n_win, K + 2, n_grid) int32: rows f_0 .. f_K, then chi (C(128, 4) = 10,668,000 fits).
+ *               status (n_win) int32: 0 for distance matrices; the cloud forms write TDA_WIN_DEGENERATE (fewer than 3
+ *               points) or TDA_WIN_TOO_LARGE (more than min(p_cap, TDA_MAX_POINTS) points, or tau < 1) exactly where the
+ *               cloud Rips entry points do, and such a window's block of counts is all zeros.  n_points (nullable): as
+ *               tda_takens_rips_batch.
+ *   Means.      tda_euler_mean: mean (n_seg, K + 2, n_grid) float64.  Over the windows seg_off[g] <= w < seg_off[g + 1]
+ *               whose status_in word has no bit of skip_mask (status_in may be NULL), every entry is
+ *               (double)S / (double)m, S the exact int64 sum of the kept windows' int32 values and m their number; m = 0
+ *               gives NaN.  seg_off = NULL: every window is its own group and n_seg must be n_win.  The byte pattern of
+ *               np.mean(stack, axis=0) on the integer rows.
+ *   Limits.     n, p_cap (>= 1), n_t (>= 1), dim, n_grid or max_dim out of range, or n_seg != n_win without a table, is
+ *               TDA_ERR_INVALID with a message in tda_last_error; nothing is launched or written.
+ *   Determinism.  The outputs are the integers of this text.  A window alone and inside a batch give the same bytes.  Every
+ *               loop bound is known before the loop starts (n, n_grid, a popcount); no polls, no atomics.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage every buffer. */
+#define TDA_EC_MAX_DIM 3
+tda_status tda_euler_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                  const double* grid, int n_grid, int max_dim, int* counts, int* status, void* stream);
+tda_status tda_euler_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                              const double* grid, int n_grid, int max_dim, int* counts, int* status);
+tda_status tda_euler_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                     int normalise, double thresh, const double* grid, int n_grid, int max_dim,
+                                     int* counts, int* status, void* stream);
+tda_status tda_euler_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                 int normalise, double thresh, const double* grid, int n_grid, int max_dim,
+                                 int* counts, int* status);
+tda_status tda_euler_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                      int subsample, double thresh, const double* grid, int n_grid, int max_dim,
+                                      int* counts, int* n_points, int* status, void* stream);
+tda_status tda_euler_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                  int subsample, double thresh, const double* grid, int n_grid, int max_dim,
+                                  int* counts, int* n_points, int* status);
+tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
+                              int n_seg, const int* status_in, int skip_mask, double* mean, void* stream);
+tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
+                          int n_seg, const int* status_in, int skip_mask, double* mean);
+
 /* ---- Frechet means of diagrams, per group ---------------------------------------------
  * The mean diagram of a group in the order-2 Wasserstein metric and the group's variance around it: the algorithm of
  * Turner, Mileyko, Mukherjee and Harer (2014), with the update rule of GUDHI's lagrangian_barycenter.  The contract is this

@@ -30,6 +30,7 @@ N_FEATURES = 11
 MAX_LANDSCAPES = 8          # TDA_MAX_LANDSCAPES
 MAX_GRID = 256              # TDA_MAX_GRID
 MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
+EC_MAX_DIM = 3              # TDA_EC_MAX_DIM: highest simplex dimension of the Euler characteristic curves
 MAX_POINTS = 128
 MAX_DIRECTIONS = 128        # TDA_MAX_DIRECTIONS
 SW_MAX_POINTS = 512         # TDA_SW_MAX_POINTS
@@ -154,6 +155,14 @@ SYMBOLS = {
                                    c_vp, c_vp, c_vp, c_vp]),
     "tda_landscape_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp]),
     "tda_landscape_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, _I, c_vp]),
+    "tda_euler_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_euler_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I, _I, c_vp, c_vp]),
+    "tda_euler_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_euler_cloud_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp]),
+    "tda_euler_takens_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_euler_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_euler_mean_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
+    "tda_euler_mean": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
     "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),
     "tda_image_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp]),
     "tda_frechet_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),

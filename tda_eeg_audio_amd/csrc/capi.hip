@@ -503,6 +503,45 @@ tda_status tda_landscape_mean_dev(tda_ctx* ctx, const double* dgm, const int* cn
                                  (hipStream_t)stream);
 }
 
+tda_status tda_euler_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                  const double* grid, int n_grid, int max_dim, int* counts, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, dm); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
+    return launch_euler(ctx, dm, nullptr, n_win, n, 0, 1, 2, symmetrise, thresh, grid, n_grid, max_dim, counts, nullptr,
+                        status, (hipStream_t)stream);
+}
+
+tda_status tda_euler_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                     int normalise, double thresh, const double* grid, int n_grid, int max_dim, int* counts,
+                                     int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
+    return launch_euler(ctx, pc, n_pts, n_win, p_cap, dim, 1, 1, normalise, thresh, grid, n_grid, max_dim, counts, nullptr,
+                        status, (hipStream_t)stream);
+}
+
+tda_status tda_euler_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                      int subsample, double thresh, const double* grid, int n_grid, int max_dim, int* counts,
+                                      int* n_points, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
+    return launch_euler(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, thresh, grid, n_grid, max_dim, counts, n_points,
+                        status, (hipStream_t)stream);
+}
+
+tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
+                              int n_seg, const int* status_in, int skip_mask, double* mean, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    if (n_win) CHECK_PTR(ctx, counts);
+    if (n_seg) CHECK_PTR(ctx, mean);
+    return launch_euler_mean(ctx, counts, n_win, max_dim, n_grid, seg_off, n_seg, status_in, skip_mask, mean,
+                             (hipStream_t)stream);
+}
+
 tda_status tda_frechet_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
                                 int n_seg, const int* status_in, int skip_mask, int max_iter, double* mean, int* mean_cnt,
                                 int cap_out, double* var, int* iters, int* status, void* stream)
@@ -1454,6 +1493,105 @@ tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, 
     RET_IF(s.upload());
     RET_IF(tda_landscape_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
                                   nullptr));
+    return s.download();
+}
+
+// (the limits of launch_euler, checked before anything is staged)
+#define EULER_LIMITS(ctx, n_grid, max_dim)                                                                             \
+    do {                                                                                                               \
+        if ((n_grid) < 1 || (n_grid) > TDA_MAX_GRID) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_grid must be in [1, TDA_MAX_GRID]"); \
+        if ((max_dim) < 1 || (max_dim) > TDA_EC_MAX_DIM)                                                               \
+            TDA_FAIL(ctx, TDA_ERR_INVALID, "max_dim must be in [1, TDA_EC_MAX_DIM]");                                  \
+    } while (0)
+
+tda_status tda_euler_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                              const double* grid, int n_grid, int max_dim, int* counts, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n < 1 || n > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
+    EULER_LIMITS(ctx, n_grid, max_dim);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, dm); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_dm, *d_grid; int *d_cnt, *d_st;
+    s.add((void**)&d_dm, dm, nullptr, (size_t)n_win * n * n * 8);
+    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
+    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_euler_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d_grid, n_grid, max_dim, d_cnt, d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_euler_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                 int normalise, double thresh, const double* grid, int n_grid, int max_dim, int* counts,
+                                 int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
+    if (p_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "p_cap must be >= 1");
+    EULER_LIMITS(ctx, n_grid, max_dim);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_pc, *d_grid; int *d_n, *d_cnt, *d_st;
+    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
+    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
+    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
+    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_euler_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d_grid, n_grid, max_dim, d_cnt,
+                                     d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_euler_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                  int subsample, double thresh, const double* grid, int n_grid, int max_dim, int* counts,
+                                  int* n_points, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
+    if (n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be >= 1");
+    EULER_LIMITS(ctx, n_grid, max_dim);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_win, *d_grid; int *d_tau, *d_cnt, *d_np = nullptr, *d_st;
+    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
+    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
+    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
+    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
+    if (n_points) s.add((void**)&d_np, nullptr, n_points, (size_t)n_win * 4);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_euler_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d_grid, n_grid, max_dim, d_cnt,
+                                      d_np, d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
+                          const int* status_in, int skip_mask, double* mean)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    EULER_LIMITS(ctx, n_grid, max_dim);
+    if (!seg_off && n_seg != n_win) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every window is a group: n_seg != n_win");
+    if (n_seg == 0) return TDA_OK;
+    if (n_win) CHECK_PTR(ctx, counts);
+    CHECK_PTR(ctx, mean);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    const size_t rg = (size_t)(max_dim + 2) * n_grid;
+    int *d_cnt, *d_off = nullptr, *d_si = nullptr; double* d_mean;
+    s.add((void**)&d_cnt, counts, nullptr, (size_t)n_win * rg * 4);
+    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, ((size_t)n_seg + 1) * 4);
+    if (status_in) s.add((void**)&d_si, status_in, nullptr, (size_t)n_win * 4);
+    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * rg * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, d_off, n_seg, d_si, skip_mask, d_mean, nullptr));
     return s.download();
 }
 

@@ -213,6 +213,13 @@ tda_status launch_plv_dist(tda_ctx*, const double* sig, const long long* win_sta
 // (permutation.hip) S00 / S11 / S01 of n_mat matrices under n_perm relabellings.  Checks the limits of the header itself.
 tda_status launch_perm_sums(tda_ctx*, const double* D, int n_mat, int n, int ld, const unsigned long long* lab, int n_perm,
                             double* work, long long work_doubles, double* out, int* n1, hipStream_t);
+// (euler.hip) simplex counts and Euler characteristic on a grid.  mode 0: Takens windows + tau, mode 1: explicit clouds + n_pts
+// (flag = normalise), mode 2: distance matrices (n_in = n, flag = symmetrise).  Checks the limits of the header itself.
+tda_status launch_euler(tda_ctx*, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample, int mode,
+                        int flag, double thresh, const double* grid, int n_grid, int max_dim, int* counts, int* n_points,
+                        int* status, hipStream_t);
+tda_status launch_euler_mean(tda_ctx*, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
+                             const int* status_in, int skip_mask, double* mean, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,
                               hipStream_t, int n_filt = 1);
 tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, const double*, const double*, int, int, double*,

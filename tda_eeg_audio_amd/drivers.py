@@ -197,6 +197,36 @@ def landscape_names(bands=BANDS, levels=5, grid=None):
     return names
 
 
+def euler_curves_from_distances(dist_list, grid, max_dim=3, thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it.  No Rips launch: one launch counts the simplices of every window on
+    `grid`, a second one writes the group means: (len(dist_list), max_dim + 2, n_grid) float64, per group the mean simplex
+    counts f_0 .. f_max_dim and the mean Euler characteristic over its windows (include/tdaeeg.h; engine.euler_dm_dev).
+    A group without a window is NaN.  ValueError for a bad grid or max_dim."""
+    import torch
+    grid, max_dim = engine.euler_args(grid, max_dim)
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    sizes = np.array([len(d) for d in dist_list])
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    grid_t = torch.from_numpy(grid).to(dev)
+    if sizes.sum() == 0:
+        counts_t = torch.empty((0, max_dim + 2, grid.shape[0]), dtype=torch.int32, device=dev)
+        mean_t = engine.euler_mean_dev(counts_t, 0, max_dim, grid.shape[0], seg_off_t=seg_t, ctx=ctx)
+    else:
+        allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+        _, _, mean_t = engine.euler_dm_dev(torch.from_numpy(np.ascontiguousarray(allw)).to(dev), grid_t, max_dim, thresh,
+                                           seg_off_t=seg_t, ctx=ctx)
+    return mean_t.cpu().numpy()
+
+
+def euler_names(bands=BANDS, max_dim=3, grid=None):
+    """Column names of euler_curves_from_distances(...)[r] of every band, flattened band by band: per band the counts
+    f0 .. f<max_dim> and then chi, each at every grid point in order."""
+    n_grid = 64 if grid is None else len(grid)
+    return [f"{band}_{row}_t{j}" for band in bands for row in [f"f{k}" for k in range(int(max_dim) + 1)] + ["chi"]
+            for j in range(n_grid)]
+
+
 def images_from_distances(dist_list, xe, ye, sigma, power=1, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     per diagram set (H0, H1) that writes only the group means: (len(dist_list), 2, n_y, n_x) float64, per group the mean

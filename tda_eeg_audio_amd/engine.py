@@ -12,6 +12,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  sublevel_batch (H0 of the sublevel-set filtration of 1-D signals)
                  plv_dist_batch (phase-locking value matrix of a window's channels and its distance matrix)
                  pack_labels / permutation_sums_batch (within- and between-group sums of matrices under relabellings)
+                 euler_dm_batch, euler_cloud_batch, euler_takens_batch (simplex counts and Euler characteristic of the Rips
+                 complex on a grid of scales, by the keys of the Rips entry points)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -28,6 +30,9 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  rips_dm_dev (Workspace(phase_locking=method)).
                  permutation_sums_dev: the sums of a two-sample permutation test on matrices that never leave the device
                  (utils.two_sample_permutation_test, drivers.two_sample_from_diagrams).
+                 euler_dm_dev / euler_cloud_dev / euler_takens_dev / euler_mean_dev / euler_eeg_windows_dev: Euler
+                 characteristic and simplex-count curves of resident windows and their group means
+                 (utils.compute_eeg_euler_curve, drivers.euler_curves_from_distances).
 """
 import ctypes as C
 
@@ -479,6 +484,65 @@ def landscape_batch(rows, cnt, grid, levels, ctx=None):
     out = np.empty((n, max(levels, 0) + 1, grid.shape[0]))
     ctx.check(ctx.lib.tda_landscape_batch(ctx.h, ptr(rows), ptr(cnt), n, cap, ptr(grid), grid.shape[0], levels, ptr(out)))
     return out
+
+
+def euler_args(grid, max_dim):
+    """The parameters of an Euler characteristic curve as the kernel takes them (include/tdaeeg.h, "Euler characteristic
+    curves"): (grid, max_dim) with grid a contiguous 1-D float64 array of 1..MAX_GRID values (any values, any order: a NaN
+    grid point holds no edge) and max_dim an int in 1..EC_MAX_DIM.  ValueError, before any GPU call, for anything else."""
+    try:
+        grid = np.asarray(grid, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("grid: the scales are a 1-D float64 array") from None
+    if grid.ndim != 1 or not 1 <= grid.shape[0] <= _lib.MAX_GRID:
+        raise ValueError(f"grid: 1..{_lib.MAX_GRID} scales in a 1-D array")
+    grid = np.ascontiguousarray(grid)
+    if isinstance(max_dim, bool) or not isinstance(max_dim, (int, np.integer)) or not 1 <= max_dim <= _lib.EC_MAX_DIM:
+        raise ValueError(f"max_dim must be an integer in 1..{_lib.EC_MAX_DIM}, not {max_dim!r}")
+    return grid, int(max_dim)
+
+
+def euler_dm_batch(dms, grid, max_dim=3, thresh=MAX_EDGE_LENGTH, symmetrise=True, ctx=None):
+    """Simplex counts f_0 .. f_max_dim and the Euler characteristic of the Rips complex of every distance matrix at every
+    scale of grid (include/tdaeeg.h): dms (n_win, n, n) float64 -> (counts (n_win, max_dim + 2, n_grid) int32, status)."""
+    grid, max_dim = euler_args(grid, max_dim)
+    ctx = ctx or get_ctx()
+    d = f64(dms)
+    n_win, n, n2 = d.shape
+    assert n == n2, "distance matrices must be square"
+    out = np.zeros((n_win, max_dim + 2, grid.shape[0]), np.int32); st = np.zeros(n_win, np.int32)
+    ctx.check(ctx.lib.tda_euler_dm_batch(ctx.h, ptr(d), n_win, n, float(thresh), int(bool(symmetrise)), ptr(grid),
+                                         grid.shape[0], max_dim, ptr(out), ptr(st)))
+    return out, st
+
+
+def euler_cloud_batch(clouds, grid, max_dim=3, n_pts=None, normalise=True, thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from explicit clouds (n_win, p_cap, dim) with n_pts rows each, by the keys of cloud_rips_batch.  A window
+    with fewer than 3 or more than min(p_cap, MAX_POINTS) points has TDA_WIN_DEGENERATE / TDA_WIN_TOO_LARGE and zeros."""
+    grid, max_dim = euler_args(grid, max_dim)
+    ctx = ctx or get_ctx()
+    pc = f64(clouds)
+    n_win, p_cap, dim = pc.shape
+    n_pts = i32(np.full(n_win, p_cap) if n_pts is None else n_pts)
+    out = np.zeros((n_win, max_dim + 2, grid.shape[0]), np.int32); st = np.zeros(n_win, np.int32)
+    ctx.check(ctx.lib.tda_euler_cloud_batch(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)), float(thresh),
+                                            ptr(grid), grid.shape[0], max_dim, ptr(out), ptr(st)))
+    return out, st
+
+
+def euler_takens_batch(windows, taus, grid, max_dim=3, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from audio windows (n_win, n_t) and their delays, by the keys of takens_rips_batch: (counts, n_points,
+    status)."""
+    grid, max_dim = euler_args(grid, max_dim)
+    ctx = ctx or get_ctx()
+    w = f64(windows)
+    n_win, n_t = w.shape
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    out = np.zeros((n_win, max_dim + 2, grid.shape[0]), np.int32)
+    npts = np.zeros(n_win, np.int32); st = np.zeros(n_win, np.int32)
+    ctx.check(ctx.lib.tda_euler_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample), float(thresh),
+                                             ptr(grid), grid.shape[0], max_dim, ptr(out), ptr(npts), ptr(st)))
+    return out, npts, st
 
 
 def image_args(xe, ye, sigma, power):
@@ -1344,6 +1408,107 @@ def landscape_mean_dev(rows_t, cnt_t, grid_t, levels, seg_off_t=None, status_t=N
     ctx.check(ctx.lib.tda_landscape_mean_dev(ctx.h, _tp(rows_t), _tp(cnt_t), cap, n, _tp(seg_off_t), n_seg, _tp(status_t),
                                              int(skip_mask), _tp(grid_t), n_grid, levels, _tp(out_t), _stream()))
     return out_t
+
+
+def _euler_dev_args(grid_t, max_dim, n_win, out_t, status_t, device):
+    """Checks of the euler_*_dev forms: grid_t a contiguous 1-D float64 device tensor of 1..MAX_GRID scales, max_dim as
+    euler_args; out_t / status_t are allocated when None (they may be larger than the batch: the tail is not touched)."""
+    import torch
+    if not (grid_t.is_cuda and grid_t.dtype == torch.float64 and grid_t.dim() == 1 and grid_t.is_contiguous()):
+        raise ValueError("grid_t: a contiguous 1-D float64 device tensor")
+    n_grid = int(grid_t.numel())
+    if not 1 <= n_grid <= _lib.MAX_GRID:
+        raise ValueError(f"grid_t: 1..{_lib.MAX_GRID} scales")
+    if isinstance(max_dim, bool) or not isinstance(max_dim, (int, np.integer)) or not 1 <= max_dim <= _lib.EC_MAX_DIM:
+        raise ValueError(f"max_dim must be an integer in 1..{_lib.EC_MAX_DIM}, not {max_dim!r}")
+    max_dim = int(max_dim)
+    if out_t is None:
+        out_t = torch.empty((n_win, max_dim + 2, n_grid), dtype=torch.int32, device=device)
+    if status_t is None:
+        status_t = torch.empty(n_win, dtype=torch.int32, device=device)
+    assert out_t.dtype == torch.int32 and out_t.is_contiguous() and out_t.numel() >= n_win * (max_dim + 2) * n_grid
+    assert status_t.dtype == torch.int32 and status_t.is_contiguous() and status_t.numel() >= n_win
+    return n_grid, max_dim, out_t, status_t
+
+
+def euler_mean_dev(counts_t, n_win, max_dim, n_grid, seg_off_t=None, status_in=None, skip_mask=0, mean_t=None, ctx=None):
+    """Group means of the int32 blocks of euler_*_dev (include/tdaeeg.h): counts_t holds (n_win, max_dim + 2, n_grid);
+    seg_off_t (n_seg + 1,) int32, or None: every window its own group.  Windows whose status_in word has a bit of skip_mask
+    are left out; a group without a kept window is NaN.  mean_t: (n_seg, max_dim + 2, n_grid) float64.  One launch on
+    torch's current stream, nothing allocated when mean_t is given."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_seg = n_win if seg_off_t is None else seg_off_t.numel() - 1
+    if mean_t is None:
+        mean_t = torch.empty((n_seg, max(int(max_dim), 0) + 2, max(int(n_grid), 0)), dtype=torch.float64, device=counts_t.device)
+    assert counts_t.dtype == torch.int32 and counts_t.is_contiguous() and mean_t.is_contiguous()
+    ctx.check(ctx.lib.tda_euler_mean_dev(ctx.h, _tp(counts_t), int(n_win), int(max_dim), int(n_grid), _tp(seg_off_t), n_seg,
+                                         _tp(status_in), int(skip_mask), _tp(mean_t), _stream()))
+    return mean_t
+
+
+def _euler_dev_mean(out_t, status_t, n_win, max_dim, n_grid, mean_t, seg_off_t, status_in, skip_mask, ctx):
+    """The optional second launch of the euler_*_dev forms: asked for by mean_t (a tensor, or True to have one allocated)
+    or by seg_off_t.  status_in defaults to the status words the first launch has just written."""
+    if mean_t is None and seg_off_t is None:
+        return None
+    return euler_mean_dev(out_t, n_win, max_dim, n_grid, seg_off_t, status_t if status_in is None else status_in, skip_mask,
+                          None if mean_t is True else mean_t, ctx)
+
+
+def euler_dm_dev(dm_t, grid_t, max_dim=3, thresh=MAX_EDGE_LENGTH, symmetrise=True, out_t=None, status_t=None, mean_t=None,
+                 seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """euler_dm_batch on device tensors: dm_t (n_win, n, n) float64, grid_t (n_grid,) float64 -> (out_t (n_win, max_dim + 2,
+    n_grid) int32, status_t, mean or None).  One launch on torch's current stream (two with the group means), nothing
+    allocated when the outputs are given."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert dm_t.is_cuda and dm_t.dtype == torch.float64 and dm_t.is_contiguous()
+    n_win, n, n2 = dm_t.shape
+    assert n == n2, "distance matrices must be square"
+    n_grid, max_dim, out_t, status_t = _euler_dev_args(grid_t, max_dim, n_win, out_t, status_t, dm_t.device)
+    ctx.check(ctx.lib.tda_euler_dm_batch_dev(ctx.h, _tp(dm_t), n_win, n, float(thresh), int(bool(symmetrise)), _tp(grid_t),
+                                             n_grid, max_dim, _tp(out_t), _tp(status_t), _stream()))
+    return out_t, status_t, _euler_dev_mean(out_t, status_t, n_win, max_dim, n_grid, mean_t, seg_off_t, status_in, skip_mask, ctx)
+
+
+def euler_cloud_dev(pc_t, n_pts_t, grid_t, max_dim=3, normalise=True, thresh=MAX_EDGE_LENGTH, out_t=None, status_t=None,
+                    mean_t=None, seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """euler_cloud_batch on device tensors: pc_t (n_win, p_cap, dim) float64, n_pts_t (n_win,) int32."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert pc_t.is_cuda and pc_t.dtype == torch.float64 and pc_t.is_contiguous() and n_pts_t.dtype == torch.int32
+    n_win, p_cap, dim = pc_t.shape
+    n_grid, max_dim, out_t, status_t = _euler_dev_args(grid_t, max_dim, n_win, out_t, status_t, pc_t.device)
+    ctx.check(ctx.lib.tda_euler_cloud_batch_dev(ctx.h, _tp(pc_t), _tp(n_pts_t), n_win, p_cap, dim, int(bool(normalise)),
+                                                float(thresh), _tp(grid_t), n_grid, max_dim, _tp(out_t), _tp(status_t),
+                                                _stream()))
+    return out_t, status_t, _euler_dev_mean(out_t, status_t, n_win, max_dim, n_grid, mean_t, seg_off_t, status_in, skip_mask, ctx)
+
+
+def euler_takens_dev(win_t, tau_t, grid_t, max_dim=3, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, out_t=None, status_t=None,
+                     n_points_t=None, mean_t=None, seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """euler_takens_batch on device tensors: win_t (n_win, n_t) float64, tau_t (n_win,) int32; n_points_t (optional, int32)
+    receives the points per window."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    n_grid, max_dim, out_t, status_t = _euler_dev_args(grid_t, max_dim, n_win, out_t, status_t, win_t.device)
+    ctx.check(ctx.lib.tda_euler_takens_batch_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, int(dim), int(subsample),
+                                                 float(thresh), _tp(grid_t), n_grid, max_dim, _tp(out_t), _tp(n_points_t),
+                                                 _tp(status_t), _stream()))
+    return out_t, status_t, _euler_dev_mean(out_t, status_t, n_win, max_dim, n_grid, mean_t, seg_off_t, status_in, skip_mask, ctx)
+
+
+def euler_eeg_windows_dev(win_t, grid_t, max_dim=3, thresh=MAX_EDGE_LENGTH, dist_t=None, out_t=None, status_t=None, mean_t=None,
+                          seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """corr_dist_dev followed by euler_dm_dev on EEG windows win_t (n_win, n_ch, n_t): the curves of exactly the matrix
+    whose diagrams eeg_window_dev gives, so curve and diagram belong to one complex.  dist_t (optional) receives the
+    matrices."""
+    dist_t = corr_dist_dev(win_t, dist_t, ctx=ctx)
+    return euler_dm_dev(dist_t, grid_t, max_dim, thresh, True, out_t, status_t, mean_t, seg_off_t, status_in, skip_mask, ctx)
 
 
 def frechet_mean_dev(rows_t, cnt_t, seg_off_t=None, status_t=None, skip_mask=0, max_iter=32, cap_out=None, out=None, ctx=None):

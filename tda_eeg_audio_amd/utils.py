@@ -141,6 +141,30 @@ def compute_eeg_persistence(dist_matrix, max_dim=MAX_DIM, max_edge_length=MAX_ED
     return [h0[0], h1[0]]
 
 
+def compute_eeg_euler_curve(distance_matrix, grid, max_dim=3, thresh=MAX_EDGE_LENGTH):
+    """The twin of compute_eeg_persistence for the Euler characteristic curve (include/tdaeeg.h, "Euler characteristic
+    curves"): the (max_dim + 2, n_grid) int32 block of the simplex counts f_0 .. f_max_dim and chi of the Rips complex of
+    the symmetrised distance matrix at every scale of grid, by the keys compute_eeg_persistence uses.  Not recorded by
+    utils.batch(): it launches at once.  ValueError for a bad grid or max_dim."""
+    dm = np.asarray(distance_matrix, dtype=np.float64)
+    if dm.ndim != 2 or dm.shape[0] != dm.shape[1]:
+        raise ValueError("Distance matrix is not square")
+    out, _ = engine.euler_dm_batch(dm[None], grid, max_dim=max_dim, thresh=thresh, symmetrise=True)
+    return out[0]
+
+
+def compute_audio_euler_curve(point_cloud, grid, max_dim=3, thresh=MAX_EDGE_LENGTH):
+    """The twin of compute_audio_persistence: the same block for a (P, dim) point cloud, min-max normalised, by the keys
+    compute_audio_persistence uses.  A cloud of fewer than 3 points gives zeros, as its diagrams are [[0, 0]]; more than
+    128 points are a TdaError."""
+    pc = np.asarray(point_cloud, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[0] < 1:
+        raise ValueError("compute_audio_euler_curve: a (P, dim) point cloud")
+    out, st = engine.euler_cloud_batch(pc[None], grid, max_dim=max_dim, thresh=thresh)
+    _check_status(st[0])
+    return out[0]
+
+
 def compute_sublevel_persistence(x, return_index=False):
     """H0 of the sublevel-set (lower-star) filtration of a time series (include/tdaeeg.h, "Sublevel-set persistence of time
     series"; ripser's lower_star example on a 1-D signal): an (m, 2) array like dgms[0], every local minimum paired with
