@@ -653,6 +653,105 @@ tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int ma
 tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
                           int n_seg, const int* status_in, int skip_mask, double* mean);
 
+/* ---- Generators and representative cycles of Rips persistence pairs ---------------------
+ * Which simplices stand behind a row of a diagram, and a cycle that represents every H1 row: the counterpart of
+ * ripser(..., do_cocycles=True) and of GUDHI's flag_persistence_generators, for the question "which channels carry the
+ * loop".  The Rips kernels are not asked: the simplices are recovered afterwards from the keys and the rows they wrote,
+ * by a local rule.  The contract is this text; tests/generators_ref.py evaluates it three times.
+ *   Keys.       k[a][b], a > b: the float32 keys of the Rips entry points for the same input, as "Euler characteristic
+ *               curves" above words them (distance matrices with symmetrise; clouds with n_pts and normalise; Takens
+ *               windows with tau, dim, subsample).  The edges are the pairs with k <= (float)thresh (a NaN key is no
+ *               edge), ordered by (key, a, b): among equal keys by the flat index a (a - 1) / 2 + b.
+ *   Kinds.      G_e is the graph of the edges that precede e = (a, b) in that order.  cn(e): some vertex v has both (a, v)
+ *               and (b, v) in G_e.  conn(e): a and b are connected in G_e.  Forest edges F = {e : !conn(e)} (Kruskal's
+ *               edges under that order), birth edges B = {e : conn(e) and !cn(e)}, death edges K = {e : cn(e)}.
+ *               An edge of K is the youngest edge of a triangle that enters with it and is paired at zero persistence, so
+ *               every H1 row (b, d), d > b, has its birth edge in B with key b and the youngest edge of its killing
+ *               triangle in K with key d; the finite H0 rows pair, in ascending death order, with the edges of F of
+ *               non-zero key (DESIGN.md 3.22 has the proofs).
+ *   Rows in.    The diagrams of the same windows as the Rips entry points wrote them: h0 (n_win, h0_cap, 2) with h0_cnt
+ *               (both nullable when h0_edge is NULL), h1 (n_win, h1_cap, 2) with h1_cnt, h1_cap >= 1.  The rows looked at
+ *               are the first min(count, cap).  rips_status (nullable): a window whose word has a bit of skip_mask gets the
+ *               fill values only.
+ *   h1_gen      (n_win, h1_cap, 4) int16 [birth_a, birth_b, death_a, death_b], a > b.  A maximal run of consecutive rows
+ *               with equal birth x takes the edges of B with (double)k == x in order, one per row.  The death edge of a
+ *               row with d != +inf is the first edge of K with (double)k == d; a row with d = +inf has -1, -1.
+ *   h1_flag     (n_win, h1_cap) int32.  TDA_GEN_BIRTH_TIED: the run has a different number of candidates in B than rows.
+ *               TDA_GEN_DEATH_TIED: more than one candidate in K.  TDA_GEN_NO_EDGE: the row's place in its run is past the
+ *               candidates of B, or d != +inf has no candidate in K -- the diagram is not this input's; the row's edges
+ *               and cycle are -1, its length 0, and it carries no TDA_GEN_CYCLE_TRUNCATED.  TDA_GEN_CYCLE_TRUNCATED: the
+ *               cycle is longer than cyc_cap; cyc holds its first cyc_cap vertices and cyc_len the true length.
+ *   cyc, cyc_len  (n_win, h1_cap, cyc_cap) int16 (nullable: then part must be NULL too; lengths and flags are written as
+ *               if it were there) and (n_win, h1_cap) int32, 4 <= cyc_cap <= TDA_MAX_POINTS.  Breadth-first
+ *               search from birth_b in G_e in level sets; the parent of a vertex is the lowest-numbered adjacent vertex of
+ *               the previous level.  The cycle is birth_a, parent(birth_a), ..., birth_b: with e it is a closed walk whose
+ *               youngest edge is e, so it is born at b and becomes a boundary-equivalent of older cycles exactly at d.
+ *               At least 4 vertices (!cn(e) rules out 3).  -1 fills the rest of the row.
+ *   part        (nullable) (n_win, n_part) float64, n_part = n (matrices), p_cap (clouds), TDA_MAX_POINTS (Takens).
+ *               part[v] = +0.0, then in row order += d - b for every row with a finite d, flag 0 and v on its cycle.
+ *               Entries at and above the window's vertex count are 0.
+ *   h0_edge     (nullable) (n_win, h0_cap, 2) int16 [a, b], a > b.  A maximal run of consecutive H0 rows with equal death x
+ *               takes the edges of F with (double)k == x in order, one per row; a row past the candidates, and every row
+ *               with death +inf, has -1, -1.  On the rows of this input the counts agree: exact under ties as well.
+ *   Fill.       Rows at and above min(count, cap), and every row of a skipped window or of one whose status is not 0:
+ *               h1_gen, cyc, h0_edge -1; h1_flag, cyc_len 0; part 0.
+ *   work        (nullable) (n_win, 4, 2) int32: per wave of the window's workgroup, the searches it ran and their levels
+ *               (for tools/generators_bench.py; no part of the contract beyond "searches <= |F| + |B|").
+ *   status      (n_win) int32: 0 for matrices; TDA_WIN_DEGENERATE / TDA_WIN_TOO_LARGE exactly where the Euler entry points
+ *               set them.  n_points (nullable): as tda_takens_rips_batch.
+ *   Means.      tda_generators_mean: mean (n_seg, n) float64 of part (n_win, n).  Per group and vertex S = +0.0, then
+ *               S += part[w][v] for the windows seg_off[g] <= w < seg_off[g + 1] in order whose status_in word (nullable)
+ *               has no bit of skip_mask; S / (double)m, NaN for m = 0.  seg_off = NULL: n_seg must be n_win.
+ *   Limits.     n in [1, TDA_MAX_POINTS], p_cap, n_t >= 1, dim in [1, TDA_MAX_DIM], cyc_cap in [4, TDA_MAX_POINTS],
+ *               h1_cap >= 1, h0_edge without h0 / h0_cnt / h0_cap >= 1, part without cyc, n < 1 or n_seg != n_win without a table for the
+ *               means: TDA_ERR_INVALID with a message in tda_last_error; nothing is launched or written.
+ *   Determinism.  The outputs are the integers (and the ordered float64 sums) of this text.  A window alone and inside a
+ *               batch give the same bytes.  Every loop bound is known before the loop starts; no polls, no atomics.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage every buffer. */
+#define TDA_GEN_BIRTH_TIED      1
+#define TDA_GEN_DEATH_TIED      2
+#define TDA_GEN_CYCLE_TRUNCATED 4
+#define TDA_GEN_NO_EDGE         8
+tda_status tda_generators_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                       const double* h0, int h0_cap, const int* h0_cnt,
+                                       const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                       int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                       double* part, short* h0_edge, int* work, int* status, void* stream);
+tda_status tda_generators_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                   const double* h0, int h0_cap, const int* h0_cnt,
+                                   const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                   int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                   double* part, short* h0_edge, int* work, int* status);
+tda_status tda_generators_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                          int normalise, double thresh,
+                                          const double* h0, int h0_cap, const int* h0_cnt,
+                                          const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                          int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                          double* part, short* h0_edge, int* work, int* status, void* stream);
+tda_status tda_generators_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                      int normalise, double thresh,
+                                      const double* h0, int h0_cap, const int* h0_cnt,
+                                      const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                      int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                      double* part, short* h0_edge, int* work, int* status);
+tda_status tda_generators_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                           int subsample, double thresh,
+                                           const double* h0, int h0_cap, const int* h0_cnt,
+                                           const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                           int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                           double* part, short* h0_edge, int* work, int* n_points, int* status,
+                                           void* stream);
+tda_status tda_generators_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                       int subsample, double thresh,
+                                       const double* h0, int h0_cap, const int* h0_cnt,
+                                       const double* h1, int h1_cap, const int* h1_cnt, const int* rips_status,
+                                       int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,
+                                       double* part, short* h0_edge, int* work, int* n_points, int* status);
+tda_status tda_generators_mean_dev(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
+                                   const int* status_in, int skip_mask, double* mean, void* stream);
+tda_status tda_generators_mean(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
+                               const int* status_in, int skip_mask, double* mean);
+
 /* ---- Frechet means of diagrams, per group ---------------------------------------------
  * The mean diagram of a group in the order-2 Wasserstein metric and the group's variance around it: the algorithm of
  * Turner, Mileyko, Mukherjee and Harer (2014), with the update rule of GUDHI's lagrangian_barycenter.  The contract is this

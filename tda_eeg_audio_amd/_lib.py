@@ -32,6 +32,10 @@ MAX_GRID = 256              # TDA_MAX_GRID
 MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 EC_MAX_DIM = 3              # TDA_EC_MAX_DIM: highest simplex dimension of the Euler characteristic curves
 MAX_POINTS = 128
+TDA_GEN_BIRTH_TIED = 1       # tda_generators_*: flags of an H1 row (include/tdaeeg.h)
+TDA_GEN_DEATH_TIED = 2
+TDA_GEN_CYCLE_TRUNCATED = 4
+TDA_GEN_NO_EDGE = 8
 MAX_DIRECTIONS = 128        # TDA_MAX_DIRECTIONS
 SW_MAX_POINTS = 512         # TDA_SW_MAX_POINTS
 FM_MAX_ITER = 64            # TDA_FM_MAX_ITER
@@ -70,6 +74,9 @@ def pt_work_doubles(n_mat, n, n_perm):
 
 # every symbol include/tdaeeg.h declares: (name, restype, argtypes)
 _I, _D = C.c_int, C.c_double
+# the row inputs and outputs the tda_generators_* entry points share: h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, rips_status,
+# skip_mask, cyc_cap, h1_gen, h1_flag, cyc, cyc_len, part, h0_edge, work
+_GEN = [c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
 SYMBOLS = {
     "tda_version": (_I, []),
     "tda_ctx_create": (_I, [_I, C.POINTER(c_vp)]),
@@ -163,6 +170,14 @@ SYMBOLS = {
     "tda_euler_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp, c_vp]),
     "tda_euler_mean_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
     "tda_euler_mean": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
+    "tda_generators_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp, c_vp]),
+    "tda_generators_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp]),
+    "tda_generators_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp, c_vp]),
+    "tda_generators_cloud_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp]),
+    "tda_generators_takens_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp, c_vp, c_vp]),
+    "tda_generators_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp, c_vp]),
+    "tda_generators_mean_dev": (_I, [c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
+    "tda_generators_mean": (_I, [c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
     "tda_image_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp, c_vp]),
     "tda_image_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _D, _I, c_vp]),
     "tda_frechet_mean_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),

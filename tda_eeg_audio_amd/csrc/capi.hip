@@ -542,6 +542,62 @@ tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int ma
                              (hipStream_t)stream);
 }
 
+// the row inputs and the outputs that the tda_generators_* entry points share, in the header's order
+#define GEN_PARAMS                                                                                                     \
+    const double* h0, int h0_cap, const int* h0_cnt, const double* h1, int h1_cap, const int* h1_cnt,                  \
+    const int* rips_status, int skip_mask, int cyc_cap, short* h1_gen, int* h1_flag, short* cyc, int* cyc_len,         \
+    double* part, short* h0_edge, int* work
+#define GEN_PASS h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, rips_status, skip_mask, cyc_cap, h1_gen, h1_flag, cyc, cyc_len, \
+                 part, h0_edge, work
+#define GEN_CHECK_PTRS(ctx) do { CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, h1_gen); CHECK_PTR(ctx, h1_flag); \
+                                 CHECK_PTR(ctx, cyc_len); CHECK_PTR(ctx, status); } while (0)
+
+static GenArgs gen_args(GEN_PARAMS)
+{
+    GenArgs g;
+    g.h0 = h0; g.h0_cap = h0_cap; g.h0_cnt = h0_cnt; g.h1 = h1; g.h1_cap = h1_cap; g.h1_cnt = h1_cnt;
+    g.rips_status = rips_status; g.skip_mask = skip_mask; g.cyc_cap = cyc_cap;
+    g.h1_gen = h1_gen; g.h1_flag = h1_flag; g.cyc = cyc; g.cyc_len = cyc_len; g.part = part; g.h0_edge = h0_edge; g.work = work;
+    g.part_ld = 0;
+    return g;
+}
+
+tda_status tda_generators_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                       GEN_PARAMS, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, dm); GEN_CHECK_PTRS(ctx); }
+    return launch_generators(ctx, dm, nullptr, n_win, n, 0, 1, 2, symmetrise, thresh, gen_args(GEN_PASS), nullptr, status,
+                             (hipStream_t)stream);
+}
+
+tda_status tda_generators_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                          int normalise, double thresh, GEN_PARAMS, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); GEN_CHECK_PTRS(ctx); }
+    return launch_generators(ctx, pc, n_pts, n_win, p_cap, dim, 1, 1, normalise, thresh, gen_args(GEN_PASS), nullptr, status,
+                             (hipStream_t)stream);
+}
+
+tda_status tda_generators_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                           int subsample, double thresh, GEN_PARAMS, int* n_points, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); GEN_CHECK_PTRS(ctx); }
+    return launch_generators(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, thresh, gen_args(GEN_PASS), n_points, status,
+                             (hipStream_t)stream);
+}
+
+tda_status tda_generators_mean_dev(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
+                                   const int* status_in, int skip_mask, double* mean, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    if (n_win) CHECK_PTR(ctx, part);
+    if (n_seg) CHECK_PTR(ctx, mean);
+    return launch_generators_mean(ctx, part, n_win, n, seg_off, n_seg, status_in, skip_mask, mean, (hipStream_t)stream);
+}
+
 tda_status tda_frechet_mean_dev(tda_ctx* ctx, const double* dgm, const int* cnt, int cap, int n_dgm, const int* seg_off,
                                 int n_seg, const int* status_in, int skip_mask, int max_iter, double* mean, int* mean_cnt,
                                 int cap_out, double* var, int* iters, int* status, void* stream)
@@ -1592,6 +1648,130 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
     s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * rg * 8);
     RET_IF(s.upload());
     RET_IF(tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, d_off, n_seg, d_si, skip_mask, d_mean, nullptr));
+    return s.download();
+}
+
+// (the limits of launch_generators, checked before anything is staged)
+#define GEN_LIMITS(ctx)                                                                                                \
+    do {                                                                                                               \
+        if (cyc_cap < 4 || cyc_cap > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "cyc_cap must be in [4, TDA_MAX_POINTS]"); \
+        if (h1_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "h1_cap must be >= 1");                                         \
+        if (part && !cyc) TDA_FAIL(ctx, TDA_ERR_INVALID, "part is summed over the cycles: it needs cyc");              \
+        if (h0_edge && (!h0 || !h0_cnt || h0_cap < 1))                                                                 \
+            TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_edge needs the H0 rows: h0, h0_cnt and h0_cap >= 1");                   \
+    } while (0)
+
+// the device twins of the row inputs and outputs of a host call
+struct GenStage {
+    double *h0 = nullptr, *h1 = nullptr, *part = nullptr;
+    int *h0_cnt = nullptr, *h1_cnt = nullptr, *rips_status = nullptr, *h1_flag = nullptr, *cyc_len = nullptr, *work = nullptr;
+    short *h1_gen = nullptr, *cyc = nullptr, *h0_edge = nullptr;
+    void add(Stage& s, size_t nw, int part_ld, GEN_PARAMS)
+    {
+        (void)skip_mask;
+        if (h0 && h0_cnt) {
+            s.add((void**)&this->h0, h0, nullptr, nw * h0_cap * 16);
+            s.add((void**)&this->h0_cnt, h0_cnt, nullptr, nw * 4);
+        }
+        s.add((void**)&this->h1, h1, nullptr, nw * h1_cap * 16);
+        s.add((void**)&this->h1_cnt, h1_cnt, nullptr, nw * 4);
+        if (rips_status) s.add((void**)&this->rips_status, rips_status, nullptr, nw * 4);
+        s.add((void**)&this->h1_gen, nullptr, h1_gen, nw * h1_cap * 8);
+        s.add((void**)&this->h1_flag, nullptr, h1_flag, nw * h1_cap * 4);
+        if (cyc) s.add((void**)&this->cyc, nullptr, cyc, nw * h1_cap * cyc_cap * 2);
+        s.add((void**)&this->cyc_len, nullptr, cyc_len, nw * h1_cap * 4);
+        if (part) s.add((void**)&this->part, nullptr, part, nw * part_ld * 8);
+        if (h0_edge) s.add((void**)&this->h0_edge, nullptr, h0_edge, nw * h0_cap * 4);
+        if (work) s.add((void**)&this->work, nullptr, work, nw * 8 * 4);
+    }
+};
+#define GEN_STAGED(d) d.h0, h0_cap, d.h0_cnt, d.h1, h1_cap, d.h1_cnt, d.rips_status, skip_mask, cyc_cap, d.h1_gen, d.h1_flag, \
+                      d.cyc, d.cyc_len, d.part, d.h0_edge, d.work
+
+tda_status tda_generators_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                   GEN_PARAMS, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n < 1 || n > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
+    GEN_LIMITS(ctx);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, dm); GEN_CHECK_PTRS(ctx);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    GenStage d;
+    double* d_dm; int* d_st;
+    s.add((void**)&d_dm, dm, nullptr, (size_t)n_win * n * n * 8);
+    d.add(s, (size_t)n_win, n, GEN_PASS);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_generators_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, GEN_STAGED(d), d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_generators_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                      int normalise, double thresh, GEN_PARAMS, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
+    if (p_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "p_cap must be >= 1");
+    GEN_LIMITS(ctx);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); GEN_CHECK_PTRS(ctx);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    GenStage d;
+    double* d_pc; int *d_n, *d_st;
+    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
+    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
+    d.add(s, (size_t)n_win, p_cap, GEN_PASS);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_generators_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, GEN_STAGED(d), d_st, nullptr));
+    return s.download();
+}
+
+tda_status tda_generators_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                       int subsample, double thresh, GEN_PARAMS, int* n_points, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
+    if (n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be >= 1");
+    GEN_LIMITS(ctx);
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); GEN_CHECK_PTRS(ctx);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    GenStage d;
+    double* d_win; int *d_tau, *d_np = nullptr, *d_st;
+    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
+    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
+    d.add(s, (size_t)n_win, TDA_MAX_POINTS, GEN_PASS);
+    if (n_points) s.add((void**)&d_np, nullptr, n_points, (size_t)n_win * 4);
+    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
+    RET_IF(s.upload());
+    RET_IF(tda_generators_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, GEN_STAGED(d), d_np, d_st,
+                                           nullptr));
+    return s.download();
+}
+
+tda_status tda_generators_mean(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
+                               const int* status_in, int skip_mask, double* mean)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    if (n < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be >= 1");
+    if (!seg_off && n_seg != n_win) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every window is a group: n_seg != n_win");
+    if (n_seg == 0) return TDA_OK;
+    if (n_win) CHECK_PTR(ctx, part);
+    CHECK_PTR(ctx, mean);
+    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    Stage s(ctx);
+    double *d_part, *d_mean; int *d_off = nullptr, *d_si = nullptr;
+    s.add((void**)&d_part, part, nullptr, (size_t)n_win * n * 8);
+    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, ((size_t)n_seg + 1) * 4);
+    if (status_in) s.add((void**)&d_si, status_in, nullptr, (size_t)n_win * 4);
+    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * n * 8);
+    RET_IF(s.upload());
+    RET_IF(tda_generators_mean_dev(ctx, d_part, n_win, n, d_off, n_seg, d_si, skip_mask, d_mean, nullptr));
     return s.download();
 }
 

@@ -220,6 +220,21 @@ tda_status launch_euler(tda_ctx*, const double* src, const int* aux, int n_win, 
                         int* status, hipStream_t);
 tda_status launch_euler_mean(tda_ctx*, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
                              const int* status_in, int skip_mask, double* mean, hipStream_t);
+// (generators.hip) the edges behind the rows of a Rips diagram and a representative cycle per H1 row.  GenArgs: the rows the
+// Rips entry points wrote and the outputs, as the tda_generators_* entry points take them (part_ld is the launcher's).
+struct GenArgs {
+    const double* h0; int h0_cap; const int* h0_cnt;
+    const double* h1; int h1_cap; const int* h1_cnt;
+    const int* rips_status; int skip_mask; int cyc_cap;
+    short* h1_gen; int* h1_flag; short* cyc; int* cyc_len;
+    double* part; short* h0_edge; int* work;
+    int part_ld;
+};
+// modes and `flag` as launch_euler.  Checks the limits of the header itself.
+tda_status launch_generators(tda_ctx*, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample, int mode,
+                             int flag, double thresh, const GenArgs& g, int* n_points, int* status, hipStream_t);
+tda_status launch_generators_mean(tda_ctx*, const double* part, int n_win, int n, const int* seg_off, int n_seg,
+                                  const int* status_in, int skip_mask, double* mean, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,
                               hipStream_t, int n_filt = 1);
 tda_status launch_filtfilt(tda_ctx*, const double*, int, int, const double*, const double*, const double*, int, int, double*,

@@ -227,6 +227,31 @@ def euler_names(bands=BANDS, max_dim=3, grid=None):
             for j in range(n_grid)]
 
 
+def channel_participation_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
+    that finds the birth edge and a representative cycle of every H1 row and one that writes the group means
+    (include/tdaeeg.h, "Generators and representative cycles"; engine.generators_dm_dev).  Returns (mean, flagged): mean
+    (len(dist_list), n) float64, per group and channel the mean over its windows of the persistence carried by the loops
+    that visit the channel (a group without a window is NaN), and flagged, the number of H1 rows that were left out because
+    a tie or a short cycle buffer flagged them."""
+    import torch
+    if not sum(len(d) for d in dist_list):
+        n = next((np.asarray(d).shape[-1] for d in dist_list if np.asarray(d).ndim == 3), 0)
+        return np.full((len(dist_list), n), np.nan), 0
+    h0, c0, h1, c1, seg = _rips_of_groups(dist_list, thresh, "channel_participation_from_distances")
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    gen = engine.generators_dm_dev(up(allw), (None, None, up(h1), up(c1)), thresh, True, seg_off_t=up(seg), ctx=ctx)
+    return gen.mean.cpu().numpy(), int((gen.h1_flag != 0).sum().item())
+
+
+def participation_names(bands=BANDS, n_ch=47):
+    """Column names of channel_participation_from_distances(...)[0][r] of every band, flattened band by band."""
+    return [f"{band}_part_ch{c}" for band in bands for c in range(int(n_ch))]
+
+
 def images_from_distances(dist_list, xe, ye, sigma, power=1, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     per diagram set (H0, H1) that writes only the group means: (len(dist_list), 2, n_y, n_x) float64, per group the mean

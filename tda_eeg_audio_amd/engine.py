@@ -14,6 +14,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  pack_labels / permutation_sums_batch (within- and between-group sums of matrices under relabellings)
                  euler_dm_batch, euler_cloud_batch, euler_takens_batch (simplex counts and Euler characteristic of the Rips
                  complex on a grid of scales, by the keys of the Rips entry points)
+                 generators_dm_batch, generators_cloud_batch, generators_takens_batch (the edges behind the rows of the
+                 diagrams, a representative cycle per H1 row and the participation of every vertex; generators_args)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -33,6 +35,10 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  euler_dm_dev / euler_cloud_dev / euler_takens_dev / euler_mean_dev / euler_eeg_windows_dev: Euler
                  characteristic and simplex-count curves of resident windows and their group means
                  (utils.compute_eeg_euler_curve, drivers.euler_curves_from_distances).
+                 generators_dm_dev / generators_cloud_dev / generators_takens_dev / generators_mean_dev /
+                 generators_eeg_windows_dev: generators and cycles of resident windows from a DeviceDiagrams or raw row
+                 tensors, into a DeviceGenerators (utils.compute_eeg_generators,
+                 drivers.channel_participation_from_distances).
 """
 import ctypes as C
 
@@ -543,6 +549,91 @@ def euler_takens_batch(windows, taus, grid, max_dim=3, dim=3, subsample=2, thres
     ctx.check(ctx.lib.tda_euler_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample), float(thresh),
                                              ptr(grid), grid.shape[0], max_dim, ptr(out), ptr(npts), ptr(st)))
     return out, npts, st
+
+
+def generators_args(cyc_cap):
+    """The cycle capacity of the generators entry points as the kernel takes it (include/tdaeeg.h, "Generators and
+    representative cycles"): an int in 4..MAX_POINTS.  ValueError, before any GPU call, for anything else."""
+    if isinstance(cyc_cap, bool) or not isinstance(cyc_cap, (int, np.integer)) or not 4 <= cyc_cap <= _lib.MAX_POINTS:
+        raise ValueError(f"cyc_cap must be an integer in 4..{_lib.MAX_POINTS}, not {cyc_cap!r}")
+    return int(cyc_cap)
+
+
+def _gen_host(n_win, n_part, h0, c0, h1, c1, cyc_cap, rips_status, want_part, want_h0, want_work):
+    """Row inputs and output arrays of the host forms -> (dict of outputs, the shared C arguments without skip_mask)."""
+    cyc_cap = generators_args(cyc_cap)
+    h1 = f64(h1); c1 = i32(c1)
+    if h1.ndim != 3 or h1.shape[0] != n_win or h1.shape[2] != 2 or h1.shape[1] < 1 or c1.shape != (n_win,):
+        raise ValueError("h1: (n_win, h1_cap >= 1, 2) rows and (n_win,) counts")
+    h1_cap = h1.shape[1]
+    h0_cap = 0
+    if h0 is not None:
+        h0 = f64(h0); c0 = i32(c0)
+        if h0.ndim != 3 or h0.shape[0] != n_win or h0.shape[2] != 2 or h0.shape[1] < 1 or c0.shape != (n_win,):
+            raise ValueError("h0: (n_win, h0_cap >= 1, 2) rows and (n_win,) counts")
+        h0_cap = h0.shape[1]
+    else:
+        c0, want_h0 = None, False
+    rs = None if rips_status is None else i32(rips_status)
+    out = dict(h1_gen=np.empty((n_win, h1_cap, 4), np.int16), h1_flag=np.empty((n_win, h1_cap), np.int32),
+               cyc=np.empty((n_win, h1_cap, cyc_cap), np.int16), cyc_len=np.empty((n_win, h1_cap), np.int32),
+               status=np.empty(n_win, np.int32))
+    if want_part:
+        out["part"] = np.empty((n_win, n_part), np.float64)
+    if want_h0:
+        out["h0_edge"] = np.empty((n_win, h0_cap, 2), np.int16)
+    if want_work:
+        out["work"] = np.empty((n_win, 4, 2), np.int32)
+    rows = (ptr(h0), h0_cap, ptr(c0), ptr(h1), h1_cap, ptr(c1), ptr(rs))
+    outs = (cyc_cap, ptr(out["h1_gen"]), ptr(out["h1_flag"]), ptr(out["cyc"]), ptr(out["cyc_len"]), ptr(out.get("part")),
+            ptr(out.get("h0_edge")), ptr(out.get("work")))
+    return out, rows, outs
+
+
+def generators_dm_batch(dms, h0, c0, h1, c1, thresh=MAX_EDGE_LENGTH, symmetrise=True, cyc_cap=_lib.MAX_POINTS,
+                        rips_status=None, skip_mask=0, part=True, h0_edge=True, work=False, ctx=None):
+    """The edges behind the rows of rips_dm_batch(dms, ..., raw=True) and a representative cycle of every H1 row
+    (include/tdaeeg.h): dms (n_win, n, n) float64, h0 / c0 (or None) and h1 / c1 the raw rows and counts -> a dict of
+    h1_gen (n_win, h1_cap, 4) int16, h1_flag, cyc (n_win, h1_cap, cyc_cap) int16, cyc_len, status and, when asked for,
+    part (n_win, n) float64, h0_edge (n_win, h0_cap, 2) int16, work."""
+    ctx = ctx or get_ctx()
+    d = f64(dms)
+    n_win, n, n2 = d.shape
+    assert n == n2, "distance matrices must be square"
+    out, rows, outs = _gen_host(n_win, n, h0, c0, h1, c1, cyc_cap, rips_status, part, h0_edge, work)
+    ctx.check(ctx.lib.tda_generators_dm_batch(ctx.h, ptr(d), n_win, n, float(thresh), int(bool(symmetrise)), *rows,
+                                              int(skip_mask), *outs, ptr(out["status"])))
+    return out
+
+
+def generators_cloud_batch(clouds, h0, c0, h1, c1, n_pts=None, normalise=True, thresh=MAX_EDGE_LENGTH,
+                           cyc_cap=_lib.MAX_POINTS, rips_status=None, skip_mask=0, part=True, h0_edge=True, work=False,
+                           ctx=None):
+    """The same for the rows of cloud_rips_batch(clouds, ..., raw=True), by its keys; part has p_cap columns."""
+    ctx = ctx or get_ctx()
+    pc = f64(clouds)
+    n_win, p_cap, dim = pc.shape
+    n_pts = i32(np.full(n_win, p_cap) if n_pts is None else n_pts)
+    out, rows, outs = _gen_host(n_win, p_cap, h0, c0, h1, c1, cyc_cap, rips_status, part, h0_edge, work)
+    ctx.check(ctx.lib.tda_generators_cloud_batch(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)),
+                                                 float(thresh), *rows, int(skip_mask), *outs, ptr(out["status"])))
+    return out
+
+
+def generators_takens_batch(windows, taus, h0, c0, h1, c1, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH,
+                            cyc_cap=_lib.MAX_POINTS, rips_status=None, skip_mask=0, part=True, h0_edge=True, work=False,
+                            ctx=None):
+    """The same for the rows of takens_rips_batch(windows, taus, ..., raw=True); part has MAX_POINTS columns and the dict
+    also holds n_points."""
+    ctx = ctx or get_ctx()
+    w = f64(windows)
+    n_win, n_t = w.shape
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    out, rows, outs = _gen_host(n_win, _lib.MAX_POINTS, h0, c0, h1, c1, cyc_cap, rips_status, part, h0_edge, work)
+    out["n_points"] = np.empty(n_win, np.int32)
+    ctx.check(ctx.lib.tda_generators_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample), float(thresh),
+                                                  *rows, int(skip_mask), *outs, ptr(out["n_points"]), ptr(out["status"])))
+    return out
 
 
 def image_args(xe, ye, sigma, power):
@@ -1509,6 +1600,158 @@ def euler_eeg_windows_dev(win_t, grid_t, max_dim=3, thresh=MAX_EDGE_LENGTH, dist
     matrices."""
     dist_t = corr_dist_dev(win_t, dist_t, ctx=ctx)
     return euler_dm_dev(dist_t, grid_t, max_dim, thresh, True, out_t, status_t, mean_t, seg_off_t, status_in, skip_mask, ctx)
+
+
+class DeviceGenerators:
+    """The outputs of the generators_*_dev forms for a batch of windows, resident in HBM (include/tdaeeg.h, "Generators
+    and representative cycles"): h1_gen (n_win, h1_cap, 4) int16, h1_flag (n_win, h1_cap) int32, cyc (n_win, h1_cap,
+    cyc_cap) int16, cyc_len (n_win, h1_cap) int32, status (n_win,) int32 and, when asked for, part (n_win, n_part) float64,
+    h0_edge (n_win, h0_cap, 2) int16, work (n_win, 4, 2) int32; mean is set by the group-mean launch.  cyc=False (with
+    part=False) leaves the cycle buffer out: edges, lengths and flags only."""
+
+    def __init__(self, n_win, h0_cap, h1_cap, cyc_cap, n_part, device, part=True, h0_edge=True, work=False, cyc=True):
+        import torch
+        kw = dict(device=device)
+        self.h1_gen = torch.empty((n_win, h1_cap, 4), dtype=torch.int16, **kw)
+        self.h1_flag = torch.empty((n_win, h1_cap), dtype=torch.int32, **kw)
+        self.cyc = torch.empty((n_win, h1_cap, cyc_cap), dtype=torch.int16, **kw) if cyc else None
+        assert cyc or not part, "part is summed over the cycles: it needs cyc"
+        self.cyc_len = torch.empty((n_win, h1_cap), dtype=torch.int32, **kw)
+        self.status = torch.empty(n_win, dtype=torch.int32, **kw)
+        self.part = torch.empty((n_win, n_part), dtype=torch.float64, **kw) if part else None
+        self.h0_edge = torch.empty((n_win, h0_cap, 2), dtype=torch.int16, **kw) if h0_edge else None
+        self.work = torch.empty((n_win, 4, 2), dtype=torch.int32, **kw) if work else None
+        self.mean = None
+        self.n_win, self.h0_cap, self.h1_cap, self.cyc_cap, self.n_part = n_win, h0_cap, h1_cap, cyc_cap, n_part
+
+    def to_host(self):
+        """The same arrays as numpy, in a dict keyed like generators_dm_batch's."""
+        return {k: getattr(self, k).cpu().numpy() for k in ("h1_gen", "h1_flag", "cyc", "cyc_len", "part", "h0_edge", "work",
+                                                            "status", "mean") if getattr(self, k) is not None}
+
+
+def _gen_rows_dev(dgm):
+    """The row tensors of a DeviceDiagrams, or of a tuple (h0_t, c0_t, h1_t, c1_t) with h0_t / c0_t None for no H0 rows."""
+    import torch
+    h0, c0, h1, c1 = (dgm.h0, dgm.c0, dgm.h1, dgm.c1) if isinstance(dgm, DeviceDiagrams) else dgm
+    assert h1.is_cuda and h1.dtype == torch.float64 and h1.is_contiguous() and h1.dim() == 3 and h1.shape[2] == 2
+    assert c1.dtype == torch.int32 and c1.is_contiguous()
+    if h0 is not None:
+        assert h0.dtype == torch.float64 and h0.is_contiguous() and h0.dim() == 3 and h0.shape[2] == 2
+        assert c0 is not None and c0.dtype == torch.int32 and c0.is_contiguous()
+    return h0, c0, h1, c1
+
+
+def _gen_dev(n_win, n_part, dgm, cyc_cap, rips_status, part, h0_edge, work, out, device):
+    """Checks and output buffers of the generators_*_dev forms -> (out, the shared tail of the C arguments).  out may be
+    larger than the batch: the tail is not touched."""
+    cyc_cap = generators_args(cyc_cap)
+    h0, c0, h1, c1 = _gen_rows_dev(dgm)
+    assert h1.shape[0] >= n_win and c1.numel() >= n_win and (h0 is None or (h0.shape[0] >= n_win and c0.numel() >= n_win))
+    h1_cap = int(h1.shape[1])
+    h0_cap = int(h0.shape[1]) if h0 is not None else 0
+    if h1_cap < 1:
+        raise ValueError("the H1 rows need h1_cap >= 1")
+    if h0 is None:
+        h0_edge = False
+    if rips_status is None and isinstance(dgm, DeviceDiagrams):
+        rips_status = dgm.status
+    if out is None:
+        out = DeviceGenerators(n_win, h0_cap, h1_cap, cyc_cap, n_part, device, part, h0_edge, work)
+    assert out.n_win >= n_win and (out.h0_cap, out.h1_cap, out.cyc_cap, out.n_part) == (h0_cap, h1_cap, cyc_cap, n_part)
+    tail = (_tp(h0), h0_cap, _tp(c0), _tp(h1), h1_cap, _tp(c1), _tp(rips_status))
+    outs = (cyc_cap, _tp(out.h1_gen), _tp(out.h1_flag), _tp(out.cyc), _tp(out.cyc_len), _tp(out.part), _tp(out.h0_edge),
+            _tp(out.work))
+    return out, tail, outs
+
+
+def generators_mean_dev(part_t, n_win, n, seg_off_t=None, status_in=None, skip_mask=0, mean_t=None, ctx=None):
+    """Group means of the participation rows of generators_*_dev (include/tdaeeg.h): part_t holds (n_win, n) float64;
+    seg_off_t (n_seg + 1,) int32, or None: every window its own group.  Windows whose status_in word has a bit of skip_mask
+    are left out; a group without a kept window is NaN.  mean_t: (n_seg, n) float64.  One launch on torch's current
+    stream, nothing allocated when mean_t is given."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_seg = n_win if seg_off_t is None else seg_off_t.numel() - 1
+    if mean_t is None:
+        mean_t = torch.empty((n_seg, max(int(n), 0)), dtype=torch.float64, device=part_t.device)
+    assert part_t.dtype == torch.float64 and part_t.is_contiguous() and mean_t.is_contiguous()
+    ctx.check(ctx.lib.tda_generators_mean_dev(ctx.h, _tp(part_t), int(n_win), int(n), _tp(seg_off_t), n_seg, _tp(status_in),
+                                              int(skip_mask), _tp(mean_t), _stream()))
+    return mean_t
+
+
+def _gen_dev_mean(out, n_win, seg_off_t, status_in, mean_skip, ctx):
+    """The optional second launch of the generators_*_dev forms, asked for by seg_off_t: the group means of part over the
+    windows whose status_in word (default: none skipped) has no bit of mean_skip."""
+    if seg_off_t is not None:
+        assert out.part is not None, "the group means need part"
+        out.mean = generators_mean_dev(out.part, n_win, out.n_part, seg_off_t, status_in, mean_skip, ctx=ctx)
+    return out
+
+
+def generators_dm_dev(dm_t, dgm, thresh=MAX_EDGE_LENGTH, symmetrise=True, cyc_cap=_lib.MAX_POINTS, rips_status=None,
+                      skip_mask=0, part=True, h0_edge=True, work=False, out=None, seg_off_t=None, status_in=None,
+                      mean_skip=0, ctx=None):
+    """generators_dm_batch on device tensors: dm_t (n_win, n, n) float64 and the diagrams rips_dm_dev / eeg_window_dev
+    wrote for it -- dgm an engine.DeviceDiagrams (its status words are rips_status then) or the raw row tensors (h0_t, c0_t,
+    h1_t, c1_t).  Returns a DeviceGenerators.  One launch on torch's current stream (two with seg_off_t: the group means of
+    part), nothing allocated when out is given."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert dm_t.is_cuda and dm_t.dtype == torch.float64 and dm_t.is_contiguous()
+    n_win, n, n2 = dm_t.shape
+    assert n == n2, "distance matrices must be square"
+    out, rows, outs = _gen_dev(n_win, n, dgm, cyc_cap, rips_status, part, h0_edge, work, out, dm_t.device)
+    ctx.check(ctx.lib.tda_generators_dm_batch_dev(ctx.h, _tp(dm_t), n_win, n, float(thresh), int(bool(symmetrise)), *rows,
+                                                  int(skip_mask), *outs, _tp(out.status), _stream()))
+    return _gen_dev_mean(out, n_win, seg_off_t, status_in, mean_skip, ctx)
+
+
+def generators_cloud_dev(pc_t, n_pts_t, dgm, normalise=True, thresh=MAX_EDGE_LENGTH, cyc_cap=_lib.MAX_POINTS,
+                         rips_status=None, skip_mask=0, part=True, h0_edge=True, work=False, out=None, seg_off_t=None,
+                         status_in=None, mean_skip=0, ctx=None):
+    """generators_cloud_batch on device tensors: pc_t (n_win, p_cap, dim) float64, n_pts_t (n_win,) int32."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert pc_t.is_cuda and pc_t.dtype == torch.float64 and pc_t.is_contiguous() and n_pts_t.dtype == torch.int32
+    n_win, p_cap, dim = pc_t.shape
+    out, rows, outs = _gen_dev(n_win, p_cap, dgm, cyc_cap, rips_status, part, h0_edge, work, out, pc_t.device)
+    ctx.check(ctx.lib.tda_generators_cloud_batch_dev(ctx.h, _tp(pc_t), _tp(n_pts_t), n_win, p_cap, dim, int(bool(normalise)),
+                                                     float(thresh), *rows, int(skip_mask), *outs, _tp(out.status), _stream()))
+    return _gen_dev_mean(out, n_win, seg_off_t, status_in, mean_skip, ctx)
+
+
+def generators_takens_dev(win_t, tau_t, dgm, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, cyc_cap=_lib.MAX_POINTS,
+                          rips_status=None, skip_mask=0, part=True, h0_edge=True, work=False, out=None, n_points_t=None,
+                          seg_off_t=None, status_in=None, mean_skip=0, ctx=None):
+    """generators_takens_batch on device tensors: win_t (n_win, n_t) float64, tau_t (n_win,) int32; n_points_t (optional,
+    int32) receives the points per window.  part has MAX_POINTS columns."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    out, rows, outs = _gen_dev(n_win, _lib.MAX_POINTS, dgm, cyc_cap, rips_status, part, h0_edge, work, out, win_t.device)
+    ctx.check(ctx.lib.tda_generators_takens_batch_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, int(dim), int(subsample),
+                                                      float(thresh), *rows, int(skip_mask), *outs, _tp(n_points_t),
+                                                      _tp(out.status), _stream()))
+    return _gen_dev_mean(out, n_win, seg_off_t, status_in, mean_skip, ctx)
+
+
+def generators_eeg_windows_dev(win_t, thresh=MAX_EDGE_LENGTH, h1_cap=DEFAULT_H1_CAP, cyc_cap=_lib.MAX_POINTS, skip_mask=0,
+                               part=True, h0_edge=True, work=False, dist_t=None, dgm=None, out=None, seg_off_t=None,
+                               status_in=None, mean_skip=0, ctx=None):
+    """eeg_window_dev with its dist output, then generators_dm_dev on the matrices and the diagrams that one launch wrote:
+    edges and cycles of exactly the rows the fused EEG kernel gives.  Returns (diagrams, DeviceGenerators); dist_t
+    (optional) receives the matrices."""
+    import torch
+    n_win, n_ch, _ = win_t.shape
+    if dist_t is None:
+        dist_t = torch.empty((n_win, n_ch, n_ch), dtype=torch.float64, device=win_t.device)
+    dgm = eeg_window_dev(win_t, dgm, thresh, h1_cap, dist_t=dist_t, ctx=ctx)
+    return dgm, generators_dm_dev(dist_t, dgm, thresh, True, cyc_cap, None, skip_mask, part, h0_edge, work, out, seg_off_t,
+                                  status_in, mean_skip, ctx)
 
 
 def frechet_mean_dev(rows_t, cnt_t, seg_off_t=None, status_t=None, skip_mask=0, max_iter=32, cap_out=None, out=None, ctx=None):

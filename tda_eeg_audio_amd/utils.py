@@ -141,6 +141,71 @@ def compute_eeg_persistence(dist_matrix, max_dim=MAX_DIM, max_edge_length=MAX_ED
     return [h0[0], h1[0]]
 
 
+def _generators_result(h0, c0, h1, c1, g, idx=None):
+    """One window's diagrams and generator outputs as compute_*_generators return them; idx (optional) maps the vertex
+    numbers back to the caller's (the landmark indices of n_perm)."""
+    n0, n1 = min(int(c0[0]), h0.shape[1]), min(int(c1[0]), h1.shape[1])
+    back = (lambda a: a) if idx is None else (lambda a: np.where(a >= 0, idx[np.maximum(a, 0)], -1))
+    gen = back(g["h1_gen"][0, :n1].astype(np.int64))
+    part = g["part"][0]
+    if idx is not None:
+        part = part[:len(idx)]
+    return {"dgms": [h0[0, :n0].copy(), h1[0, :n1].copy()],
+            "h0_edges": back(g["h0_edge"][0, :n0].astype(np.int64)),
+            "h1_birth_edges": gen[:, :2], "h1_death_edges": gen[:, 2:],
+            "cycles": [back(g["cyc"][0, r, :min(int(g["cyc_len"][0, r]), g["cyc"].shape[2])].astype(np.int64))
+                       for r in range(n1)],
+            "flags": g["h1_flag"][0, :n1].copy(), "participation": part.copy()}
+
+
+def compute_eeg_generators(distance_matrix, thresh=MAX_EDGE_LENGTH):
+    """The twin of compute_eeg_persistence that also says where the features live (include/tdaeeg.h, "Generators and
+    representative cycles"; ripser's do_cocycles, GUDHI's flag_persistence_generators): a dict of
+      dgms [H0, H1]            the diagrams of compute_eeg_persistence
+      h0_edges (len(H0), 2)    the forest edge [a, b], a > b, of every finite H0 row; -1 for the essential rows
+      h1_birth_edges, h1_death_edges (len(H1), 2)   the edge that closes the loop of every H1 row and the youngest edge of
+                               the triangle that kills it; -1, -1 for the death edge of an essential row
+      cycles                   per H1 row the vertices of a representative cycle, birth_a ... birth_b
+      flags (len(H1),)         TDA_GEN_* bits; 0 on generic input
+      participation (n,)       per channel the persistence summed over the unflagged finite rows whose cycle visits it.
+    Not recorded by utils.batch(): it launches at once."""
+    dm = np.asarray(distance_matrix, dtype=np.float64)
+    if dm.ndim != 2 or dm.shape[0] != dm.shape[1]:
+        raise ValueError("Distance matrix is not square")
+    h0, c0, h1, c1, st = engine.rips_dm_batch(dm[None], thresh=thresh, symmetrise=True, h1_cap=_h1_cap(dm.shape[0]), raw=True)
+    _check_status(st[0])
+    return _generators_result(h0, c0, h1, c1, engine.generators_dm_batch(dm[None], h0, c0, h1, c1, thresh=thresh))
+
+
+def compute_audio_generators(point_cloud, thresh=MAX_EDGE_LENGTH, n_perm=None):
+    """The twin of compute_audio_persistence: the same dict for a (P, dim) point cloud, min-max normalised; the vertex
+    numbers are row numbers of point_cloud.  With n_perm (ripser's keyword) the complex is that of the n_perm greedy
+    landmarks and every index is mapped back through the landmark indices, as ripser's idx_perm allows; participation
+    then has one entry per landmark, in landmark order, and the dict also holds idx_perm.  Fewer than 3 points: TdaError
+    (there is no complex); more than 128 (1024 with n_perm): TdaError."""
+    pc = np.asarray(point_cloud, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[0] < 1:
+        raise ValueError("compute_audio_generators: a (P, dim) point cloud")
+    if pc.shape[0] < 3:
+        raise TdaError("fewer than 3 points: no Rips complex to take generators from")
+    if n_perm is None:
+        h0, c0, h1, c1, st = engine.cloud_rips_batch(pc[None], thresh=thresh, h1_cap=_h1_cap(len(pc)), raw=True)
+        _check_status(st[0])
+        return _generators_result(h0, c0, h1, c1, engine.generators_cloud_batch(pc[None], h0, c0, h1, c1, thresh=thresh))
+    if pc.shape[0] > LM_MAX_POINTS:
+        raise TdaError(f"more than {LM_MAX_POINTS} points: not supported by the landmark kernel")
+    lm, idx, _, _, n_lm, _ = engine.cloud_landmarks_batch(pc[None], n_perm)
+    # the landmark rows are normalised already: the cloud path takes them as they are
+    h0, c0, h1, c1, st = engine.cloud_rips_batch(lm, n_pts=n_lm, normalise=False, thresh=thresh, h1_cap=_h1_cap(int(n_lm[0])),
+                                                 raw=True)
+    _check_status(st[0])
+    g = engine.generators_cloud_batch(lm, h0, c0, h1, c1, n_pts=n_lm, normalise=False, thresh=thresh)
+    idx_perm = idx[0, :int(n_lm[0])].astype(np.int64)
+    out = _generators_result(h0, c0, h1, c1, g, idx_perm)
+    out["idx_perm"] = idx_perm
+    return out
+
+
 def compute_eeg_euler_curve(distance_matrix, grid, max_dim=3, thresh=MAX_EDGE_LENGTH):
     """The twin of compute_eeg_persistence for the Euler characteristic curve (include/tdaeeg.h, "Euler characteristic
     curves"): the (max_dim + 2, n_grid) int32 block of the simplex counts f_0 .. f_max_dim and chi of the Rips complex of
