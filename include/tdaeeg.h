@@ -53,7 +53,8 @@ typedef enum {
 #define TDA_WIN_NO_PAIR       32  /* tda_wasserstein_cross_dev: this diagram has no partner at
                                      its position (mvm:89); the distance is NaN and is no member of the group's mean */
 #define TDA_WIN_NOT_FINITE    64  /* tda_sublevel_batch: the signal has a sample that is not finite; count 0, no rows
-                                     tda_plv_dist_batch: the same for a window; its plv and dist blocks are NaN */
+                                     tda_plv_dist_batch, tda_connectivity_dist_batch: the same for a window; its plv / value
+                                     and dist blocks are NaN */
 
 #define TDA_N_FEATURES 11         /* scripts/utils.py:166-177 key order */
 #define TDA_MAX_POINTS 128        /* vertices per Rips complex (reference needs <= 124)        */
@@ -1101,6 +1102,56 @@ tda_status tda_plv_dist_batch_dev(tda_ctx* ctx, const double* sig, const long lo
 tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
                               int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
                               int* status);
+
+/* ---- Analytic-signal connectivity: wPLI, imaginary coherency, coherence, envelope correlation, and their distances ----
+ * Correlation and the PLV are inflated by volume conduction: one source seen at zero lag by many electrodes gives values
+ * near 1.  The measures that answer it, and the amplitude counterpart: the weighted phase-lag index (Vinck et al. 2011), the
+ * imaginary part of coherency (Nolte et al. 2004), coherence (the full magnitude beside it) and the correlation of the
+ * amplitude envelopes (AEC).  Rips on the result is tda_rips_dm_batch[_dev].  The contract is this text;
+ * tests/connectivity_ref.py evaluates it.
+ *   Window.     x[c][t], float64, c < n_ch, t < n_t.
+ *   Analytic signal.  That of the phase-locking value: h[c][t] = sum_m x[c][m] * g[(t - m) mod n_t], g the host table
+ *               (preprocess._hilbert_g), z = x + i h: scipy.signal.hilbert of the WINDOW ITSELF.
+ *   Sums.       For i < j:  s[t] = h_i[t] x_j[t] - x_i[t] h_j[t] = Im(z_i conj z_j) (in the kernel two rounded products and
+ *               their difference, so identical channels have s = 0 exactly);  r[t] = x_i x_j + h_i h_j;
+ *               S = sum s, A = sum |s|, R = sum r;  P_c = sum (x_c^2 + h_c^2);  a_c[t] = sqrt(x_c^2 + h_c^2).
+ *   Measures.   TAU = TDA_CONN_TAU = 2^-40.  For i != j:
+ *               TDA_CONN_WPLI  (0, "wpli")   abs(S) / A, and exactly 0.0 where A <= TAU * sqrt(P_i P_j): the pair is in phase
+ *                              or antiphase to rounding, no lag information exists
+ *               TDA_CONN_IMCOH (1, "imcoh")  abs(S) / sqrt(P_i P_j), 0.0 where P_i P_j == 0
+ *               TDA_CONN_COH   (2, "coh")    sqrt(S*S + R*R) / sqrt(P_i P_j), 0.0 where P_i P_j == 0
+ *               TDA_CONN_AEC   (3, "aec")    the Pearson correlation of a_i and a_j in centred form (mean first, then products
+ *                              of deviations), and 0.0 where either envelope is flat: sum (a_c - mean_c)^2 <=
+ *                              n_t * (TAU * mean_c)^2 (the reference's NaN -> 0 rule for zero-variance channels)
+ *               The threshold rules are part of the definition, not a tolerance: they make the duplicated, rescaled, zero
+ *               and constant channels deterministic instead of a quotient of rounding noise.  value[i][i] = 1.0 exactly.
+ *               Pair (i, j), i < j, is computed once and stored at both places: symmetric as bytes.
+ *   Distance.   dist = correlation_to_distance(value, method), the four methods of tda_corr_to_dist_batch (clip, formula,
+ *               clamp at 0).  The diagonal is exactly 0, the matrix symmetric as bytes.
+ *   Order.      float64 in an order that is the kernel's, not the contract's (aec: one pass, the deviations taken from the
+ *               mean of the first block of samples, which leaves a covariance what it is): agreement with the definition is
+ *               to rounding (tests/connectivity_ref.py: BAR), not bit for bit.
+ *   Status.     A window with a sample that is not finite gets TDA_WIN_NOT_FINITE and its value and dist blocks are NaN; the
+ *               other windows are unaffected.  Every other window has status 0.
+ *   Addressing. As tda_plv_dist_batch_dev: win_start / win_ld (device int64 tables) or both NULL for stacked windows; one
+ *               NULL is TDA_ERR_INVALID.
+ *   Outputs.    dist (n_win, n_ch, n_ch) float64; value the same, nullable (nothing of it is touched then); status (n_win).
+ *   Limits.     Those of the PLV: 2 <= n_ch <= TDA_PLV_MAX_CHANNELS, 2 <= n_t <= TDA_PLV_MAX_SAMPLES; measure in 0..3, method
+ *               in 0..3; anything else is TDA_ERR_INVALID and nothing is launched.
+ *   Determinism.  No atomics, no scratch; a window alone, inside a batch and through a window table gives the same bytes.
+ * The _dev form only enqueues on `stream` and allocates nothing (g: device, n_t doubles).  The host form stages every
+ * buffer; its tables and g are host arrays. */
+#define TDA_CONN_TAU 0x1p-40
+#define TDA_CONN_WPLI 0
+#define TDA_CONN_IMCOH 1
+#define TDA_CONN_COH 2
+#define TDA_CONN_AEC 3
+tda_status tda_connectivity_dist_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start,
+                                           const long long* win_ld, int n_win, int n_ch, int n_t, const double* g,
+                                           int measure, int method, double* dist, double* value, int* status, void* stream);
+tda_status tda_connectivity_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                       int n_win, int n_ch, int n_t, const double* g, int measure, int method, double* dist,
+                                       double* value, int* status);
 
 /* ---- Two-sample permutation sums: within- and between-group sums of a matrix under many relabellings ----------------
  * The arithmetic of the permutation test of Robinson and Turner (2017, "Hypothesis testing for topological data analysis")

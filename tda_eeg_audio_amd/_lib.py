@@ -51,6 +51,11 @@ LM_MAX_SAMPLES = 4096       # TDA_LM_MAX_SAMPLES
 SL_MAX_SAMPLES = 4096       # TDA_SL_MAX_SAMPLES: longest signal of the sublevel-set persistence
 PLV_MAX_CHANNELS = 64       # TDA_PLV_MAX_CHANNELS: most channels of a phase-locking value window
 PLV_MAX_SAMPLES = 256       # TDA_PLV_MAX_SAMPLES: longest one
+CONN_TAU = 2.0 ** -40       # TDA_CONN_TAU: the threshold of the analytic-signal connectivity's degenerate cases
+TDA_CONN_WPLI = 0           # tda_connectivity_dist_batch: the weighted phase-lag index
+TDA_CONN_IMCOH = 1          # ... the imaginary part of coherency
+TDA_CONN_COH = 2            # ... coherence
+TDA_CONN_AEC = 3            # ... amplitude-envelope correlation
 PT_ROW_BLOCK = 64           # TDA_PT_ROW_BLOCK: rows per block of the permutation sums' written order
 PT_MAX_ITEMS = 4096         # TDA_PT_MAX_ITEMS: largest matrix side of tda_perm_sums_batch
 PT_MAX_PERM = 1048576       # TDA_PT_MAX_PERM: most relabellings of a call
@@ -204,6 +209,8 @@ SYMBOLS = {
     "tda_sublevel_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_plv_dist_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_plv_dist_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_connectivity_dist_batch_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_connectivity_dist_batch": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, _I, c_vp, c_vp, c_vp]),
     "tda_perm_sums_batch_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, C.c_longlong, c_vp, c_vp, c_vp]),
     "tda_perm_sums_batch": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, c_vp]),
     "tda_event_create": (_I, [c_vp, C.POINTER(c_vp)]),

@@ -785,6 +785,16 @@ tda_status tda_plv_dist_batch_dev(tda_ctx* ctx, const double* sig, const long lo
     return launch_plv_dist(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, method, dist, plv, status, (hipStream_t)stream);
 }
 
+tda_status tda_connectivity_dist_batch_dev(tda_ctx* ctx, const double* sig, const long long* win_start,
+                                           const long long* win_ld, int n_win, int n_ch, int n_t, const double* g,
+                                           int measure, int method, double* dist, double* value, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, sig); CHECK_PTR(ctx, g); CHECK_PTR(ctx, dist); CHECK_PTR(ctx, status); }
+    return launch_connectivity_dist(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, measure, method, dist, value, status,
+                                    (hipStream_t)stream);
+}
+
 tda_status tda_perm_sums_batch_dev(tda_ctx* ctx, const double* D, int n_mat, int n, int ld, const unsigned long long* lab,
                                    int n_perm, double* work, long long work_doubles, double* out, int* n1, void* stream)
 {
@@ -1462,9 +1472,13 @@ tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* 
     return s.download();
 }
 
-tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
-                              int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
-                              int* status)
+// The host form shared by tda_plv_dist_batch and tda_connectivity_dist_batch: the limits (before anything is staged), the
+// elements of sig the tables reach, the staging; dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st) enqueues the _dev form.
+extern "C++" {
+template <class Dev>
+static tda_status window_dist_host(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                   int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* mat,
+                                   int* status, Dev dev)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_ch < 2 || n_ch > TDA_PLV_MAX_CHANNELS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_ch must be in [2, TDA_PLV_MAX_CHANNELS]");
@@ -1486,18 +1500,44 @@ tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* 
     TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     const size_t nn = (size_t)n_win * n_ch * n_ch;
-    double *d_sig, *d_g, *d_dist, *d_plv = nullptr;
+    double *d_sig, *d_g, *d_dist, *d_mat = nullptr;
     long long *d_ws = nullptr, *d_wl = nullptr;
     int* d_st;
     s.add((void**)&d_sig, sig, nullptr, (size_t)n_el * 8);
     s.add((void**)&d_g, g, nullptr, (size_t)n_t * 8);
     if (win_start) { s.add((void**)&d_ws, win_start, nullptr, (size_t)n_win * 8); s.add((void**)&d_wl, win_ld, nullptr, (size_t)n_win * 8); }
     s.add((void**)&d_dist, nullptr, dist, nn * 8);
-    if (plv) s.add((void**)&d_plv, nullptr, plv, nn * 8);
+    if (mat) s.add((void**)&d_mat, nullptr, mat, nn * 8);
     s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
     RET_IF(s.upload());
-    RET_IF(tda_plv_dist_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_g, method, d_dist, d_plv, d_st, nullptr));
+    RET_IF(dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st));
     return s.download();
+}
+}   // extern "C++"
+
+tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                              int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
+                              int* status)
+{
+    return window_dist_host(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, method, dist, plv, status,
+        [&](const double* d_sig, const long long* d_ws, const long long* d_wl, const double* d_g, double* d_dist, double* d_plv,
+            int* d_st) {
+            return tda_plv_dist_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_g, method, d_dist, d_plv, d_st, nullptr);
+        });
+}
+
+tda_status tda_connectivity_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
+                                       int n_win, int n_ch, int n_t, const double* g, int measure, int method, double* dist,
+                                       double* value, int* status)
+{
+    CHECK_CTX(ctx);
+    if (measure < 0 || measure > TDA_CONN_AEC) TDA_FAIL(ctx, TDA_ERR_INVALID, "Unknown measure");
+    return window_dist_host(ctx, sig, win_start, win_ld, n_win, n_ch, n_t, g, method, dist, value, status,
+        [&](const double* d_sig, const long long* d_ws, const long long* d_wl, const double* d_g, double* d_dist, double* d_value,
+            int* d_st) {
+            return tda_connectivity_dist_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_g, measure, method, d_dist,
+                                                   d_value, d_st, nullptr);
+        });
 }
 
 // (the limits are checked before anything is staged; of the last row of D only its n entries are copied)

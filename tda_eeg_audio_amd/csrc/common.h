@@ -210,6 +210,11 @@ tda_status launch_sublevel(tda_ctx*, const double* sig, const long long* win_sta
 // (plv.hip) phase-locking value matrix of every window and its distance matrix.  Checks the limits of the header itself.
 tda_status launch_plv_dist(tda_ctx*, const double* sig, const long long* win_start, const long long* win_ld, int n_win,
                            int n_ch, int n_t, const double* g, int method, double* dist, double* plv, int* status, hipStream_t);
+// (connectivity.hip) wPLI / imaginary coherency / coherence / envelope correlation of every window and its distance matrix.
+// Checks the limits of the header itself.
+tda_status launch_connectivity_dist(tda_ctx*, const double* sig, const long long* win_start, const long long* win_ld,
+                                    int n_win, int n_ch, int n_t, const double* g, int measure, int method, double* dist,
+                                    double* value, int* status, hipStream_t);
 // (permutation.hip) S00 / S11 / S01 of n_mat matrices under n_perm relabellings.  Checks the limits of the header itself.
 tda_status launch_perm_sums(tda_ctx*, const double* D, int n_mat, int n, int ld, const unsigned long long* lab, int n_perm,
                             double* work, long long work_doubles, double* out, int* n1, hipStream_t);

@@ -252,6 +252,59 @@ def participation_names(bands=BANDS, n_ch=47):
     return [f"{band}_part_ch{c}" for band in bands for c in range(int(n_ch))]
 
 
+def connectivity_features_from_windows(win_list, measure, method="euclidean"):
+    """win_list: list of (k_i, n_ch, n_t) arrays of EEG windows, one per (recording, band) group.  Per group the np.nanmean
+    over its windows of the 11 extract_features values of H0 and then of H1 of the Rips complex on the distance of the
+    window's channels under the analytic-signal connectivity `measure` ("wpli", "imcoh", "coh" or "aec"; include/tdaeeg.h,
+    engine.connectivity_dist_dev): (len(win_list), 22) float64, the columns named by connectivity_names.  All on the device,
+    the way the phase-locking stage of the step does it: one launch for the distances, rips_dm_dev with the whole retry
+    ladder (exact by itself, whatever the context's retry policy, which is put back), the finishing pass, the segment
+    means.  A window the connectivity kernel flags (a sample that is not finite) is handed to Rips as points on a line and
+    counts as NaN, as does a window with a Rips status; a group without a window is NaN.  ValueError for an unknown measure
+    or method."""
+    import torch
+    from .utils import _h1_cap
+    engine.connectivity_measure(measure)
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    sizes = np.array([len(w) for w in win_list])
+    n_win = int(sizes.sum())
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    out = torch.full((len(win_list), 22), float("nan"), dtype=torch.float64, device=dev)
+    if n_win == 0:
+        engine._dist_method(method)
+        return out.cpu().numpy()
+    allw = np.concatenate([np.asarray(w, dtype=np.float64) for w in win_list if len(w)], axis=0)
+    n_ch = allw.shape[1]
+    dist, _, st = engine.connectivity_dist_dev(torch.from_numpy(np.ascontiguousarray(allw)).to(dev), measure=measure,
+                                               method=method, ctx=ctx)
+    bad = st != 0
+    line = torch.from_numpy(np.abs(np.subtract.outer(np.arange(n_ch), np.arange(n_ch))) / n_ch).to(dev)
+    dist = torch.where(bad[:, None, None], line, dist).contiguous()
+    dgm = engine.DeviceDiagrams(n_win, n_ch, _h1_cap(n_ch), dev)
+    policy = ctx.retry_policy
+    ctx.set_retry_policy(ctx.RETRY_AUTO)
+    try:
+        engine.rips_dm_dev(dist, dgm, ctx=ctx)
+    finally:
+        ctx.set_retry_policy(policy)
+    f0 = torch.empty((n_win, 11), dtype=torch.float64, device=dev)
+    f1 = torch.empty((n_win, 11), dtype=torch.float64, device=dev)
+    engine.diagram_finish_dev([(dgm.h0, dgm.c0, False, f0), (dgm.h1, dgm.c1, True, f1)], ctx=ctx)
+    bad = bad | (dgm.status != 0)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    cols = torch.where(bad[:, None], nan, torch.cat([f0, f1], dim=1)).t().contiguous()
+    for k in range(22):
+        out[:, k].copy_(engine.segment_nanmean_dev(cols[k], seg_t, ctx=ctx))
+    return out.cpu().numpy()
+
+
+def connectivity_names(measure):
+    """Column names of connectivity_features_from_windows(...)[g]: the features of H0, then of H1."""
+    engine.connectivity_measure(measure)
+    return [f"{measure}_{h}_{f}_mean" for h in ("h0", "h1") for f in FEATURE_KEYS]
+
+
 def images_from_distances(dist_list, xe, ye, sigma, power=1, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     per diagram set (H0, H1) that writes only the group means: (len(dist_list), 2, n_y, n_x) float64, per group the mean

@@ -11,6 +11,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  takens_landmarks_batch, cloud_landmarks_batch (greedy permutation, ripser's n_perm)
                  sublevel_batch (H0 of the sublevel-set filtration of 1-D signals)
                  plv_dist_batch (phase-locking value matrix of a window's channels and its distance matrix)
+                 connectivity_dist_batch (wPLI, imaginary coherency, coherence or envelope correlation of a window's
+                 channels and its distance matrix; CONNECTIVITY_MEASURES, connectivity_measure)
                  pack_labels / permutation_sums_batch (within- and between-group sums of matrices under relabellings)
                  euler_dm_batch, euler_cloud_batch, euler_takens_batch (simplex counts and Euler characteristic of the Rips
                  complex on a grid of scales, by the keys of the Rips entry points)
@@ -30,6 +32,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  their 11 features through a bounded scratch (Workspace(sublevel=True)).
                  plv_dist_dev: phase-locking value distance matrices of windows read stacked or in place, ready for
                  rips_dm_dev (Workspace(phase_locking=method)).
+                 connectivity_dist_dev: the same for wPLI, imaginary coherency, coherence and envelope correlation
+                 (drivers.connectivity_features_from_windows).
                  permutation_sums_dev: the sums of a two-sample permutation test on matrices that never leave the device
                  (utils.two_sample_permutation_test, drivers.two_sample_from_diagrams).
                  euler_dm_dev / euler_cloud_dev / euler_takens_dev / euler_mean_dev / euler_eeg_windows_dev: Euler
@@ -238,6 +242,24 @@ def sublevel_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, cap=No
     return dgm, cnt, idx, status
 
 
+def _host_windows(sig, n_t, win_start, win_ld, n_ch):
+    """The window arguments of plv_dist_batch / connectivity_dist_batch: (sig as float64, the int64 tables or None twice,
+    n_win, n_ch, n_t) of stacked windows (n_win, n_ch, n_t), one window (n_ch, n_t), or a flat array with tables."""
+    s = f64(sig)
+    if win_start is None and win_ld is None:
+        if s.ndim == 2:
+            s = s[None]
+        n_win, n_ch, n_t = s.shape
+        ws = wl = None
+    else:
+        ws, wl = (np.ascontiguousarray(t, dtype=np.int64) for t in (win_start, win_ld))
+        assert ws.shape == wl.shape and ws.ndim == 1 and n_ch is not None and n_t is not None
+        n_win, n_ch, n_t = ws.shape[0], int(n_ch), int(n_t)
+        if n_win and n_ch >= 1 and n_t >= 1:
+            assert ws.min() >= 0 and wl.min() >= 0 and int((ws + (n_ch - 1) * wl).max()) + n_t <= s.size, "table past the end of sig"
+    return s, ws, wl, n_win, n_ch, n_t
+
+
 def plv_method(method):
     """The method number of a phase-locking distance: one of DIST_METHODS' names, or True for "euclidean".  ValueError for
     anything else."""
@@ -258,18 +280,7 @@ def plv_dist_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, method
     from .preprocess import _hilbert_g
     m = plv_method(method)
     ctx = ctx or get_ctx()
-    s = f64(sig)
-    if win_start is None and win_ld is None:
-        if s.ndim == 2:
-            s = s[None]
-        n_win, n_ch, n_t = s.shape
-        ws = wl = None
-    else:
-        ws, wl = (np.ascontiguousarray(t, dtype=np.int64) for t in (win_start, win_ld))
-        assert ws.shape == wl.shape and ws.ndim == 1 and n_ch is not None and n_t is not None
-        n_win, n_ch, n_t = ws.shape[0], int(n_ch), int(n_t)
-        if n_win and n_ch >= 1 and n_t >= 1:
-            assert ws.min() >= 0 and wl.min() >= 0 and int((ws + (n_ch - 1) * wl).max()) + n_t <= s.size, "table past the end of sig"
+    s, ws, wl, n_win, n_ch, n_t = _host_windows(sig, n_t, win_start, win_ld, n_ch)
     nc = max(n_ch, 0)
     dist = np.empty((n_win, nc, nc))
     plv = np.empty((n_win, nc, nc)) if want_plv else None
@@ -278,6 +289,47 @@ def plv_dist_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, method
     ctx.check(ctx.lib.tda_plv_dist_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(g), m, ptr(dist), ptr(plv),
                                          ptr(status)))
     return dist, plv, status
+
+
+# the measures of tda_connectivity_dist_batch by name (include/tdaeeg.h, "Analytic-signal connectivity")
+CONNECTIVITY_MEASURES = {"wpli": _lib.TDA_CONN_WPLI, "imcoh": _lib.TDA_CONN_IMCOH, "coh": _lib.TDA_CONN_COH,
+                         "aec": _lib.TDA_CONN_AEC}
+
+
+def connectivity_measure(name):
+    """The measure number of an analytic-signal connectivity: one of CONNECTIVITY_MEASURES' names.  ValueError for anything
+    else."""
+    if not isinstance(name, str) or name not in CONNECTIVITY_MEASURES:
+        raise ValueError(f"connectivity: one of {sorted(CONNECTIVITY_MEASURES)}, not {name!r}")
+    return CONNECTIVITY_MEASURES[name]
+
+
+def _dist_method(method):
+    if not isinstance(method, str) or method not in DIST_METHODS:
+        raise ValueError(f"connectivity: method one of {sorted(DIST_METHODS)}, not {method!r}")
+    return DIST_METHODS[method]
+
+
+def connectivity_dist_batch(sig, n_t=None, win_start=None, win_ld=None, n_ch=None, measure=None, method="euclidean",
+                            want_value=True, ctx=None):
+    """wPLI, imaginary coherency, coherence or envelope correlation of the channels of every window (include/tdaeeg.h,
+    "Analytic-signal connectivity") and its distance matrix: (dist (n_win, n_ch, n_ch), value the same or None, status
+    (n_win)).  measure: one of CONNECTIVITY_MEASURES' names.  sig and the tables as plv_dist_batch takes them; the analytic
+    signal is the window's own.  A window with a sample that is not finite has NaN blocks and status TDA_WIN_NOT_FINITE.
+    ValueError for an unknown measure or method, TdaError for n_ch outside [2, PLV_MAX_CHANNELS] or n_t outside
+    [2, PLV_MAX_SAMPLES]."""
+    from .preprocess import _hilbert_g
+    k, m = connectivity_measure(measure), _dist_method(method)
+    ctx = ctx or get_ctx()
+    s, ws, wl, n_win, n_ch, n_t = _host_windows(sig, n_t, win_start, win_ld, n_ch)
+    nc = max(n_ch, 0)
+    dist = np.empty((n_win, nc, nc))
+    value = np.empty((n_win, nc, nc)) if want_value else None
+    status = np.zeros(n_win, np.int32)
+    g = _hilbert_g(n_t) if n_t >= 1 else np.zeros(1)
+    ctx.check(ctx.lib.tda_connectivity_dist_batch(ctx.h, ptr(s), ptr(ws), ptr(wl), n_win, n_ch, n_t, ptr(g), k, m, ptr(dist),
+                                                  ptr(value), ptr(status)))
+    return dist, value, status
 
 
 def pack_labels(labels):
@@ -1231,6 +1283,21 @@ def plv_g_table(n_t, device):
     return _PLV_G[key]
 
 
+def _dev_windows(sig_t, n_t, win_start_t, win_ld_t, n_ch):
+    """The window arguments of plv_dist_dev / connectivity_dist_dev checked: (n_win, n_ch, n_t) of stacked windows or of a
+    flat tensor with its int64 device tables."""
+    import torch
+    assert sig_t.is_cuda and sig_t.dtype == torch.float64 and sig_t.is_contiguous()
+    if win_start_t is None and win_ld_t is None:
+        assert sig_t.dim() == 3
+        n_win, n_ch, n_t = sig_t.shape
+    else:
+        assert win_start_t.dtype == torch.int64 and win_ld_t.dtype == torch.int64 and win_start_t.numel() == win_ld_t.numel()
+        assert win_start_t.is_contiguous() and win_ld_t.is_contiguous() and n_ch is not None and n_t is not None
+        n_win, n_ch, n_t = int(win_start_t.numel()), int(n_ch), int(n_t)
+    return n_win, n_ch, n_t
+
+
 def plv_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, method="euclidean", out=None, plv_t=None,
                  status_t=None, want_plv=False, ctx=None):
     """plv_dist_batch on device tensors: one launch on torch's current stream.  sig_t (n_win, n_ch, n_t), or flat with the
@@ -1241,14 +1308,7 @@ def plv_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, me
     import torch
     m = plv_method(method)
     ctx = ctx or get_ctx()
-    assert sig_t.is_cuda and sig_t.dtype == torch.float64 and sig_t.is_contiguous()
-    if win_start_t is None and win_ld_t is None:
-        assert sig_t.dim() == 3
-        n_win, n_ch, n_t = sig_t.shape
-    else:
-        assert win_start_t.dtype == torch.int64 and win_ld_t.dtype == torch.int64 and win_start_t.numel() == win_ld_t.numel()
-        assert win_start_t.is_contiguous() and win_ld_t.is_contiguous() and n_ch is not None and n_t is not None
-        n_win, n_ch, n_t = int(win_start_t.numel()), int(n_ch), int(n_t)
+    n_win, n_ch, n_t = _dev_windows(sig_t, n_t, win_start_t, win_ld_t, n_ch)
     dev = sig_t.device
     nc = max(n_ch, 0)
     if out is None:
@@ -1263,6 +1323,32 @@ def plv_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, me
     ctx.check(ctx.lib.tda_plv_dist_batch_dev(ctx.h, _tp(sig_t), _tp(win_start_t), _tp(win_ld_t), n_win, n_ch, n_t, _tp(g_t), m,
                                              _tp(out), _tp(plv_t), _tp(status_t), _stream()))
     return out, plv_t, status_t
+
+
+def connectivity_dist_dev(sig_t, n_t=None, win_start_t=None, win_ld_t=None, n_ch=None, measure=None, method="euclidean",
+                          out=None, value_t=None, status_t=None, want_value=False, ctx=None):
+    """connectivity_dist_batch on device tensors: one launch on torch's current stream.  sig_t and the tables as plv_dist_dev
+    takes them.  out: the (n_win, n_ch, n_ch) distance matrices; value_t: the measure's matrices (made when want_value; not
+    touched when absent).  Nothing is allocated when out and status_t are given and the table of this (n_t, device) is
+    resident (plv_g_table, shared with plv_dist_dev).  Returns (out, value_t or None, status_t)."""
+    import torch
+    k, m = connectivity_measure(measure), _dist_method(method)
+    ctx = ctx or get_ctx()
+    n_win, n_ch, n_t = _dev_windows(sig_t, n_t, win_start_t, win_ld_t, n_ch)
+    dev = sig_t.device
+    nc = max(n_ch, 0)
+    if out is None:
+        out = torch.empty((n_win, nc, nc), dtype=torch.float64, device=dev)
+    if value_t is None and want_value:
+        value_t = torch.empty((n_win, nc, nc), dtype=torch.float64, device=dev)
+    status_t = torch.zeros(n_win, dtype=torch.int32, device=dev) if status_t is None else status_t
+    assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() >= n_win * nc * nc
+    assert value_t is None or (value_t.is_contiguous() and value_t.dtype == torch.float64 and value_t.numel() >= n_win * nc * nc)
+    assert status_t.numel() >= n_win and status_t.dtype == torch.int32 and status_t.is_contiguous()
+    g_t = plv_g_table(max(n_t, 1), dev)
+    ctx.check(ctx.lib.tda_connectivity_dist_batch_dev(ctx.h, _tp(sig_t), _tp(win_start_t), _tp(win_ld_t), n_win, n_ch, n_t,
+                                                      _tp(g_t), k, m, _tp(out), _tp(value_t), _tp(status_t), _stream()))
+    return out, value_t, status_t
 
 
 def permutation_sums_dev(D_t, lab_t, out_t=None, n1_t=None, ctx=None, n_perm=None, work_t=None):

@@ -281,6 +281,33 @@ def compute_plv_persistence(window, method="euclidean", max_dim=MAX_DIM, max_edg
     return [h0[0], h1[0]]
 
 
+def compute_connectivity_matrix(window, measure):
+    """An analytic-signal connectivity of every pair of channels of a window (n_ch, n_t) (include/tdaeeg.h, "Analytic-signal
+    connectivity"): measure "wpli" (weighted phase-lag index, Vinck et al. 2011), "imcoh" (imaginary part of coherency,
+    Nolte et al. 2004), "coh" (coherence) or "aec" (correlation of the amplitude envelopes): an (n_ch, n_ch) symmetric
+    matrix with ones on the diagonal, the analytic signal that of scipy.signal.hilbert of the window itself.  Not recorded
+    by utils.batch(): it launches at once.  ValueError for an unknown measure or samples that are not finite; TdaError for
+    more than PLV_MAX_CHANNELS channels or PLV_MAX_SAMPLES samples."""
+    _, value, st = engine.connectivity_dist_batch(_plv_window(window)[None], measure=measure)
+    if st.any():
+        raise ValueError("compute_connectivity_matrix: the window has samples that are not finite")
+    return value[0]
+
+
+def compute_connectivity_persistence(window, measure, method="euclidean", max_dim=MAX_DIM, max_edge_length=MAX_EDGE_LENGTH):
+    """[H0, H1] of the Rips complex on the distance of a window's channels under an analytic-signal connectivity, the twin
+    of compute_plv_persistence: correlation_to_distance(compute_connectivity_matrix(window, measure), method) through the
+    Rips call of compute_eeg_persistence.  Not recorded by utils.batch(): it launches at once.  ValueError for an unknown
+    measure or method or samples that are not finite."""
+    _check_dim(max_dim)
+    dist, _, st = engine.connectivity_dist_batch(_plv_window(window)[None], measure=measure, method=method, want_value=False)
+    if st.any():
+        raise ValueError("compute_connectivity_persistence: the window has samples that are not finite")
+    h0, h1, rst = engine.rips_dm_batch(dist, thresh=max_edge_length, symmetrise=True, h1_cap=_h1_cap(dist.shape[1]))
+    _check_status(rst[0])
+    return [h0[0], h1[0]]
+
+
 def _h1_cap(n):
     return max(256, n * (n - 1) // 2 - (n - 1)) if n <= 64 else 1024
 
