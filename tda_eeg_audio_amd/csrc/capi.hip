@@ -7,6 +7,181 @@
 
 static thread_local std::string g_create_err;
 
+#define CHECK_CTX(ctx) do { if (!(ctx)) return TDA_ERR_INVALID; } while (0)
+#define CHECK_PTR(ctx, p) do { if (!(p)) TDA_FAIL(ctx, TDA_ERR_INVALID, "null pointer: " #p); } while (0)
+#define CHECK_NONNEG(ctx, v) do { if ((v) < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative size: " #v); } while (0)
+
+// ---------------------------------------------------------------- staging of the host-pointer twins
+// A bump allocator over the context workspace; everything is staged, launched on the
+// default stream, copied back and synchronised.  Sizes are element counts.
+namespace {
+
+struct Stage;
+
+// A staged buffer.  It converts to its device pointer where it is used, inside Stage::run, when the workspace has its
+// final place; a buffer that was not staged (a null host pointer, no element) converts to nullptr.
+template <class T>
+struct Dev {
+    const Stage* s = nullptr;
+    size_t off = 0;
+    operator T*() const;
+};
+
+struct Stage {
+    tda_ctx* ctx;
+    size_t need = 0;
+    struct Item { size_t off; const void* src; void* dst; size_t bytes; };
+    std::vector<Item> items;
+    explicit Stage(tda_ctx* c) : ctx(c) {}
+    Stage(const Stage&) = delete;
+
+    template <class T> Dev<T> in(const T* host, size_t n) { return add<T>(host, nullptr, host ? n : 0); }    // uploaded
+    template <class T> Dev<T> out(T* host, size_t n) { return add<T>(nullptr, host, host ? n : 0); }         // copied back
+    template <class T> Dev<T> inout(T* host, size_t n) { return add<T>(host, host, host ? n : 0); }          // both
+    template <class T> Dev<T> work(size_t n) { return add<T>(nullptr, nullptr, n); }                         // device only
+
+    // Places the buffers, uploads in the order they were added, calls f (a _dev entry point on the staged buffers) and,
+    // only if f succeeded, copies back and synchronises.
+    template <class F>
+    tda_status run(F f)
+    {
+        TDA_HIP(ctx, hipSetDevice(ctx->device));
+        if (need > ctx->ws_bytes) {
+            if (ctx->ws) TDA_HIP(ctx, hipFree(ctx->ws));
+            ctx->ws = nullptr; ctx->ws_bytes = 0;
+            TDA_HIP(ctx, hipMalloc(&ctx->ws, need));
+            ctx->ws_bytes = need;
+        }
+        char* ws = (char*)ctx->ws;
+        for (auto& it : items)
+            if (it.src) TDA_HIP(ctx, hipMemcpyAsync(ws + it.off, it.src, it.bytes, hipMemcpyHostToDevice, 0));
+        const tda_status st = f();
+        if (st != TDA_OK) return st;
+        for (auto& it : items)
+            if (it.dst) TDA_HIP(ctx, hipMemcpyAsync(it.dst, ws + it.off, it.bytes, hipMemcpyDeviceToHost, 0));
+        TDA_HIP(ctx, hipStreamSynchronize(0));
+        return TDA_OK;
+    }
+
+private:
+    template <class T>
+    Dev<T> add(const T* src, T* dst, size_t n)
+    {
+        if (!n) return {};
+        const size_t bytes = n * sizeof(T);
+        items.push_back({need, src, dst, bytes});
+        Dev<T> d{this, need};
+        need += (bytes + 255) & ~(size_t)255;
+        return d;
+    }
+};
+
+template <class T>
+Dev<T>::operator T*() const { return s ? (T*)((char*)s->ctx->ws + off) : nullptr; }
+
+// a set of diagrams: rows (n, cap, 2) and counts (n)
+struct DgmSet { Dev<double> rows; Dev<int> cnt; };
+DgmSet dgm_in(Stage& s, const double* rows, const int* cnt, size_t n, int cap)
+{
+    return {s.in(rows, n * cap * 2), s.in(cnt, n)};
+}
+
+// the group inputs of a mean over n items: seg_off (n_seg + 1), or NULL for every item its own group, and the items'
+// status words (n), or NULL
+struct GroupIn { Dev<int> off, status; };
+GroupIn group_in(Stage& s, const int* seg_off, int n_seg, const int* status_in, size_t n)
+{
+    return {s.in(seg_off, (size_t)n_seg + 1), s.in(status_in, n)};
+}
+
+// the outputs of a Rips call on nw windows; n_points may be NULL
+struct RipsStage { Dev<double> h0, h1; Dev<int> c0, c1, np, st; };
+RipsStage rips_out(Stage& s, size_t nw, double* h0, int h0_cap, int* h0_cnt, double* h1, int h1_cap, int* h1_cnt, int* n_points,
+                   int* status)
+{
+    return {s.out(h0, nw * h0_cap * 2), s.out(h1, nw * h1_cap * 2), s.out(h0_cnt, nw), s.out(h1_cnt, nw), s.out(n_points, nw),
+            s.out(status, nw)};
+}
+
+// The elements of sig the window tables reach; without tables, the stacked windows.
+tda_status sig_extent(tda_ctx* ctx, const long long* win_start, const long long* win_ld, int n_win, int n_ch, int n_t,
+                      long long* n_el)
+{
+    *n_el = (long long)n_win * n_ch * n_t;
+    if (win_start) {
+        *n_el = 0;
+        for (int w = 0; w < n_win; ++w) {
+            if (win_start[w] < 0 || win_ld[w] < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative window table entry");
+            const long long end = win_start[w] + (long long)(n_ch - 1) * win_ld[w] + n_t;
+            *n_el = end > *n_el ? end : *n_el;
+        }
+    }
+    return TDA_OK;
+}
+
+// The two sets, the pair indices and the outputs of a call on pairs of diagrams; dirs (the direction table of the sliced
+// distance) and kvals (of the diagram kernels) are NULL where the entry point has none.
+struct PairDev { DgmSet a, b; Dev<int> ia, ib; Dev<double> dirs, out, kv; Dev<int> st; };
+PairDev pair_stage(Stage& s, const double* dgm_a, const int* cnt_a, int n_a, int cap_a, const double* dgm_b, const int* cnt_b,
+                   int n_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs, const double* dirs, int n_dirs, double* out,
+                   double* kvals, int* status)
+{
+    return {dgm_in(s, dgm_a, cnt_a, (size_t)n_a, cap_a), dgm_in(s, dgm_b, cnt_b, (size_t)n_b, cap_b), s.in(idx_a, (size_t)n_pairs),
+            s.in(idx_b, (size_t)n_pairs), s.in(dirs, (size_t)n_dirs * 2), s.out(out, (size_t)n_pairs),
+            s.out(kvals, (size_t)n_pairs * 3), s.out(status, (size_t)n_pairs)};
+}
+
+// The host-pointer twins of the pair distances from their own argument checks on: pointer and size checks, the pair
+// indices, staging (with the direction table when dirs is given) and `dev`, a call of the _dev entry point on the staged
+// PairDev pointers.
+template <class Call>
+tda_status pair_batch_host(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a, const double* dgm_b,
+                           const int* cnt_b, int n_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
+                           const double* dirs, int n_dirs, double* out, int* status, Call dev)
+{
+    if (n_pairs == 0) return TDA_OK;
+    CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, out);
+    CHECK_PTR(ctx, status);
+    if (n_a < 1 || n_b < 1 || cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
+    for (int i = 0; i < n_pairs; ++i) {
+        const int a = idx_a ? idx_a[i] : i, b = idx_b ? idx_b[i] : i;
+        if (a < 0 || a >= n_a || b < 0 || b >= n_b) TDA_FAIL(ctx, TDA_ERR_INVALID, "pair index out of range");
+    }
+    Stage s(ctx);
+    const PairDev d = pair_stage(s, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, dirs, n_dirs, out,
+                                 nullptr, status);
+    return s.run([&] { return dev(d); });
+}
+
+// The host form shared by tda_plv_dist_batch and tda_connectivity_dist_batch: the limits (before anything is staged), the
+// elements of sig the tables reach, the staging; dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st) enqueues the _dev form.
+template <class Call>
+tda_status window_dist_host(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld, int n_win,
+                            int n_ch, int n_t, const double* g, int method, double* dist, double* mat, int* status, Call dev)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_ch < 2 || n_ch > TDA_PLV_MAX_CHANNELS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_ch must be in [2, TDA_PLV_MAX_CHANNELS]");
+    if (n_t < 2 || n_t > TDA_PLV_MAX_SAMPLES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be in [2, TDA_PLV_MAX_SAMPLES]");
+    if (method < 0 || method > 3) TDA_FAIL(ctx, TDA_ERR_INVALID, "Unknown method");
+    if ((win_start == nullptr) != (win_ld == nullptr)) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_start and win_ld go together");
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, sig); CHECK_PTR(ctx, g); CHECK_PTR(ctx, dist); CHECK_PTR(ctx, status);
+    long long n_el;
+    if (tda_status st = sig_extent(ctx, win_start, win_ld, n_win, n_ch, n_t, &n_el)) return st;
+    Stage s(ctx);
+    const size_t nn = (size_t)n_win * n_ch * n_ch;
+    auto d_sig = s.in(sig, (size_t)n_el);
+    auto d_g = s.in(g, (size_t)n_t);
+    auto d_ws = s.in(win_start, (size_t)n_win);
+    auto d_wl = s.in(win_ld, (size_t)n_win);
+    auto d_dist = s.out(dist, nn);
+    auto d_mat = s.out(mat, nn);
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] { return dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st); });
+}
+
+}   // namespace
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -120,10 +295,6 @@ tda_status tda_set_retry_policy(tda_ctx* ctx, int policy)
     ctx->retry_policy = policy;
     return TDA_OK;
 }
-
-#define CHECK_CTX(ctx) do { if (!(ctx)) return TDA_ERR_INVALID; } while (0)
-#define CHECK_PTR(ctx, p) do { if (!(p)) TDA_FAIL(ctx, TDA_ERR_INVALID, "null pointer: " #p); } while (0)
-#define CHECK_NONNEG(ctx, v) do { if ((v) < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative size: " #v); } while (0)
 
 // ---------------------------------------------------------------- device-pointer API
 tda_status tda_corr_dist_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_ch, int n_t, double* dist,
@@ -804,61 +975,18 @@ tda_status tda_perm_sums_batch_dev(tda_ctx* ctx, const double* D, int n_mat, int
 }
 
 // ---------------------------------------------------------------- host-pointer twins
-// A bump allocator over the context workspace; everything is staged, launched on the
-// default stream, copied back and synchronised.
-struct Stage {
-    tda_ctx* ctx;
-    size_t need = 0, used = 0;
-    struct Item { void** dev; const void* src; void* dst; size_t bytes; };
-    std::vector<Item> items;
-    explicit Stage(tda_ctx* c) : ctx(c) {}
-    void add(void** dev, const void* src, void* dst, size_t bytes)
-    {
-        items.push_back({dev, src, dst, bytes});
-        need += (bytes + 255) & ~(size_t)255;
-    }
-    tda_status upload()
-    {
-        if (need > ctx->ws_bytes) {
-            if (ctx->ws) TDA_HIP(ctx, hipFree(ctx->ws));
-            ctx->ws = nullptr; ctx->ws_bytes = 0;
-            TDA_HIP(ctx, hipMalloc(&ctx->ws, need));
-            ctx->ws_bytes = need;
-        }
-        char* p = (char*)ctx->ws;
-        for (auto& it : items) {
-            *it.dev = it.bytes ? p : nullptr;
-            if (it.src && it.bytes) TDA_HIP(ctx, hipMemcpyAsync(p, it.src, it.bytes, hipMemcpyHostToDevice, 0));
-            p += (it.bytes + 255) & ~(size_t)255;
-        }
-        return TDA_OK;
-    }
-    tda_status download()
-    {
-        for (auto& it : items)
-            if (it.dst && it.bytes) TDA_HIP(ctx, hipMemcpyAsync(it.dst, *it.dev, it.bytes, hipMemcpyDeviceToHost, 0));
-        TDA_HIP(ctx, hipStreamSynchronize(0));
-        return TDA_OK;
-    }
-};
-
-#define RET_IF(x) do { tda_status s__ = (x); if (s__ != TDA_OK) return s__; } while (0)
-
+// Each one checks its arguments, stages its buffers (Stage, above) and runs its _dev entry point on them.
 tda_status tda_corr_dist_batch(tda_ctx* ctx, const double* win, int n_win, int n_ch, int n_t, double* dist, double* corr)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, dist);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_win, *d_dist, *d_corr = nullptr;
     const size_t nw = (size_t)n_win;
-    s.add((void**)&d_win, win, nullptr, nw * n_ch * n_t * 8);
-    s.add((void**)&d_dist, nullptr, dist, nw * n_ch * n_ch * 8);
-    if (corr) s.add((void**)&d_corr, nullptr, corr, nw * n_ch * n_ch * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_corr_dist_batch_dev(ctx, d_win, n_win, n_ch, n_t, d_dist, d_corr, nullptr));
-    return s.download();
+    auto d_win = s.in(win, nw * n_ch * n_t);
+    auto d_dist = s.out(dist, nw * n_ch * n_ch);
+    auto d_corr = s.out(corr, nw * n_ch * n_ch);
+    return s.run([&] { return tda_corr_dist_batch_dev(ctx, d_win, n_win, n_ch, n_t, d_dist, d_corr, nullptr); });
 }
 
 tda_status tda_corr_dist_sliding(tda_ctx* ctx, const double* sig, int n_ch, int n_samples, int win_len, int step,
@@ -869,15 +997,13 @@ tda_status tda_corr_dist_sliding(tda_ctx* ctx, const double* sig, int n_ch, int 
     const int nw = n_samples >= win_len ? (n_samples - win_len) / step + 1 : 0;
     if (n_win) *n_win = nw;
     if (nw == 0) return TDA_OK;
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_sig, *d_dist, *d_corr = nullptr;
-    s.add((void**)&d_sig, sig, nullptr, (size_t)n_ch * n_samples * 8);
-    s.add((void**)&d_dist, nullptr, dist, (size_t)nw * n_ch * n_ch * 8);
-    if (corr) s.add((void**)&d_corr, nullptr, corr, (size_t)nw * n_ch * n_ch * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_corr_dist_sliding_dev(ctx, d_sig, n_ch, n_samples, win_len, step, d_dist, d_corr, nullptr, nullptr));
-    return s.download();
+    auto d_sig = s.in(sig, (size_t)n_ch * n_samples);
+    auto d_dist = s.out(dist, (size_t)nw * n_ch * n_ch);
+    auto d_corr = s.out(corr, (size_t)nw * n_ch * n_ch);
+    return s.run([&] {
+        return tda_corr_dist_sliding_dev(ctx, d_sig, n_ch, n_samples, win_len, step, d_dist, d_corr, nullptr, nullptr);
+    });
 }
 
 tda_status tda_corr_to_dist_batch(tda_ctx* ctx, const double* corr, int n_win, int n, int method, double* dist)
@@ -886,14 +1012,10 @@ tda_status tda_corr_to_dist_batch(tda_ctx* ctx, const double* corr, int n_win, i
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, corr); CHECK_PTR(ctx, dist);
     if (n < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_c, *d_d;
-    s.add((void**)&d_c, corr, nullptr, (size_t)n_win * n * n * 8);
-    s.add((void**)&d_d, nullptr, dist, (size_t)n_win * n * n * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_corr_to_dist_batch_dev(ctx, d_c, n_win, n, method, d_d, nullptr));
-    return s.download();
+    auto d_c = s.in(corr, (size_t)n_win * n * n);
+    auto d_d = s.out(dist, (size_t)n_win * n * n);
+    return s.run([&] { return tda_corr_to_dist_batch_dev(ctx, d_c, n_win, n, method, d_d, nullptr); });
 }
 
 tda_status tda_rips_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
@@ -904,20 +1026,13 @@ tda_status tda_rips_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, d
     CHECK_PTR(ctx, dm); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt); CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt);
     CHECK_PTR(ctx, status);
     if (h0_cap < 1 || h1_cap < 1 || n < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n, h0_cap, h1_cap must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dm, *d_h0, *d_h1; int *d_c0, *d_c1, *d_st;
     const size_t nw = (size_t)n_win;
-    s.add((void**)&d_dm, dm, nullptr, nw * n * n * 8);
-    s.add((void**)&d_h0, nullptr, h0, nw * h0_cap * 16);
-    s.add((void**)&d_h1, nullptr, h1, nw * h1_cap * 16);
-    s.add((void**)&d_c0, nullptr, h0_cnt, nw * 4);
-    s.add((void**)&d_c1, nullptr, h1_cnt, nw * 4);
-    s.add((void**)&d_st, nullptr, status, nw * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_rips_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d_h0, h0_cap, d_c0, d_h1, h1_cap, d_c1, d_st,
-                                 nullptr));
-    return s.download();
+    auto d_dm = s.in(dm, nw * n * n);
+    const RipsStage o = rips_out(s, nw, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, nullptr, status);
+    return s.run([&] {
+        return tda_rips_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, o.h0, h0_cap, o.c0, o.h1, h1_cap, o.c1, o.st, nullptr);
+    });
 }
 
 tda_status tda_takens_rips_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -929,22 +1044,15 @@ tda_status tda_takens_rips_batch(tda_ctx* ctx, const double* win, const int* tau
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt); CHECK_PTR(ctx, h1);
     CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status);
     if (h0_cap < 1 || h1_cap < 1 || n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t, h0_cap, h1_cap must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_win, *d_h0, *d_h1; int *d_tau, *d_c0, *d_c1, *d_np, *d_st;
     const size_t nw = (size_t)n_win;
-    s.add((void**)&d_win, win, nullptr, nw * n_t * 8);
-    s.add((void**)&d_tau, tau, nullptr, nw * 4);
-    s.add((void**)&d_h0, nullptr, h0, nw * h0_cap * 16);
-    s.add((void**)&d_h1, nullptr, h1, nw * h1_cap * 16);
-    s.add((void**)&d_c0, nullptr, h0_cnt, nw * 4);
-    s.add((void**)&d_c1, nullptr, h1_cnt, nw * 4);
-    s.add((void**)&d_np, nullptr, n_points, nw * 4);
-    s.add((void**)&d_st, nullptr, status, nw * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_takens_rips_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d_h0, h0_cap, d_c0, d_h1,
-                                     h1_cap, d_c1, d_np, d_st, nullptr));
-    return s.download();
+    auto d_win = s.in(win, nw * n_t);
+    auto d_tau = s.in(tau, nw);
+    const RipsStage o = rips_out(s, nw, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, n_points, status);
+    return s.run([&] {
+        return tda_takens_rips_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, o.h0, h0_cap, o.c0, o.h1, h1_cap,
+                                         o.c1, o.np, o.st, nullptr);
+    });
 }
 
 tda_status tda_cloud_rips_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -956,39 +1064,34 @@ tda_status tda_cloud_rips_batch(tda_ctx* ctx, const double* pc, const int* n_pts
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt); CHECK_PTR(ctx, h1);
     CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status);
     if (h0_cap < 1 || h1_cap < 1 || p_cap < 1 || dim < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_pc, *d_h0, *d_h1; int *d_n, *d_c0, *d_c1, *d_st;
     const size_t nw = (size_t)n_win;
-    s.add((void**)&d_pc, pc, nullptr, nw * p_cap * dim * 8);
-    s.add((void**)&d_n, n_pts, nullptr, nw * 4);
-    s.add((void**)&d_h0, nullptr, h0, nw * h0_cap * 16);
-    s.add((void**)&d_h1, nullptr, h1, nw * h1_cap * 16);
-    s.add((void**)&d_c0, nullptr, h0_cnt, nw * 4);
-    s.add((void**)&d_c1, nullptr, h1_cnt, nw * 4);
-    s.add((void**)&d_st, nullptr, status, nw * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_cloud_rips_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d_h0, h0_cap, d_c0, d_h1,
-                                    h1_cap, d_c1, d_st, nullptr));
-    return s.download();
+    auto d_pc = s.in(pc, nw * p_cap * dim);
+    auto d_n = s.in(n_pts, nw);
+    const RipsStage o = rips_out(s, nw, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, nullptr, status);
+    return s.run([&] {
+        return tda_cloud_rips_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, o.h0, h0_cap, o.c0, o.h1, h1_cap, o.c1,
+                                        o.st, nullptr);
+    });
 }
 
+namespace {
 // The landmark outputs of a host call: staged in BOTH directions, so what the kernel leaves untouched stays the caller's.
 struct LmStage {
-    double *lm, *lambda, *rc; int *idx, *n_lm, *n_full;
+    Dev<double> lm, lambda, rc; Dev<int> idx, n_lm, n_full;
     void add(Stage& s, int n_win, int n_perm, int dim, double* h_lm, int* h_idx, double* h_lambda, double* h_rc, int* h_nlm,
              int* h_nfull)
     {
         const size_t nw = (size_t)n_win;
-        lambda = nullptr;
-        s.add((void**)&lm, h_lm, h_lm, nw * n_perm * dim * 8);
-        s.add((void**)&idx, h_idx, h_idx, nw * n_perm * 4);
-        if (h_lambda) s.add((void**)&lambda, h_lambda, h_lambda, nw * n_perm * 8);
-        s.add((void**)&rc, h_rc, h_rc, nw * 8);
-        s.add((void**)&n_lm, h_nlm, h_nlm, nw * 4);
-        s.add((void**)&n_full, h_nfull, h_nfull, nw * 4);
+        lm = s.inout(h_lm, nw * n_perm * dim);
+        idx = s.inout(h_idx, nw * n_perm);
+        lambda = s.inout(h_lambda, nw * n_perm);
+        rc = s.inout(h_rc, nw);
+        n_lm = s.inout(h_nlm, nw);
+        n_full = s.inout(h_nfull, nw);
     }
 };
+}   // namespace
 #define CHECK_LM_LIMITS(ctx, cap_ok)                                                                                   \
     do { if (n_perm < 3 || n_perm > TDA_MAX_POINTS || dim < 1 || dim > TDA_MAX_DIM || !(cap_ok))                      \
              TDA_FAIL(ctx, TDA_ERR_INVALID, "landmarks: n_perm, dim or a size outside its limits"); } while (0)
@@ -1001,16 +1104,15 @@ tda_status tda_takens_landmarks(tda_ctx* ctx, const double* win, const int* tau,
     CHECK_LM_LIMITS(ctx, subsample >= 1 && n_t >= 1 && n_t <= TDA_LM_MAX_SAMPLES);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double* d_win; int* d_tau; LmStage o;
-    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
-    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
+    LmStage o;
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.in(tau, (size_t)n_win);
     o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
-    RET_IF(s.upload());
-    RET_IF(tda_takens_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, o.lm, o.idx, o.lambda, o.rc,
-                                    o.n_lm, o.n_full, nullptr));
-    return s.download();
+    return s.run([&] {
+        return tda_takens_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, o.lm, o.idx, o.lambda, o.rc, o.n_lm,
+                                        o.n_full, nullptr);
+    });
 }
 
 tda_status tda_cloud_landmarks(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -1021,16 +1123,15 @@ tda_status tda_cloud_landmarks(tda_ctx* ctx, const double* pc, const int* n_pts,
     CHECK_LM_LIMITS(ctx, p_cap >= 1 && p_cap <= TDA_LM_MAX_POINTS);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_LM_PTRS(ctx);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double* d_pc; int* d_n; LmStage o;
-    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
-    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
+    LmStage o;
+    auto d_pc = s.in(pc, (size_t)n_win * p_cap * dim);
+    auto d_n = s.in(n_pts, (size_t)n_win);
     o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
-    RET_IF(s.upload());
-    RET_IF(tda_cloud_landmarks_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, n_perm, o.lm, o.idx, o.lambda, o.rc,
-                                   o.n_lm, o.n_full, nullptr));
-    return s.download();
+    return s.run([&] {
+        return tda_cloud_landmarks_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, n_perm, o.lm, o.idx, o.lambda, o.rc, o.n_lm,
+                                       o.n_full, nullptr);
+    });
 }
 
 tda_status tda_takens_rips_landmarks(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -1044,24 +1145,17 @@ tda_status tda_takens_rips_landmarks(tda_ctx* ctx, const double* win, const int*
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_LM_PTRS(ctx); CHECK_PTR(ctx, h0); CHECK_PTR(ctx, h0_cnt);
     CHECK_PTR(ctx, h1); CHECK_PTR(ctx, h1_cnt); CHECK_PTR(ctx, status);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_win, *d_h0, *d_h1; int *d_tau, *d_c0, *d_c1, *d_np = nullptr, *d_st; LmStage o;
+    LmStage o;
     const size_t nw = (size_t)n_win;
-    s.add((void**)&d_win, win, nullptr, nw * n_t * 8);
-    s.add((void**)&d_tau, tau, nullptr, nw * 4);
+    auto d_win = s.in(win, nw * n_t);
+    auto d_tau = s.in(tau, nw);
     o.add(s, n_win, n_perm, dim, lm, lm_idx, lm_lambda, r_cover, n_lm, n_full);
-    s.add((void**)&d_h0, nullptr, h0, nw * h0_cap * 16);
-    s.add((void**)&d_h1, nullptr, h1, nw * h1_cap * 16);
-    s.add((void**)&d_c0, nullptr, h0_cnt, nw * 4);
-    s.add((void**)&d_c1, nullptr, h1_cnt, nw * 4);
-    if (n_points) s.add((void**)&d_np, nullptr, n_points, nw * 4);
-    s.add((void**)&d_st, nullptr, status, nw * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_takens_rips_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, thresh, o.lm, o.idx,
-                                         o.lambda, o.rc, o.n_lm, o.n_full, d_h0, h0_cap, d_c0, d_h1, h1_cap, d_c1, d_np,
-                                         d_st, nullptr));
-    return s.download();
+    const RipsStage r = rips_out(s, nw, h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, n_points, status);
+    return s.run([&] {
+        return tda_takens_rips_landmarks_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, n_perm, thresh, o.lm, o.idx, o.lambda,
+                                             o.rc, o.n_lm, o.n_full, r.h0, h0_cap, r.c0, r.h1, h1_cap, r.c1, r.np, r.st, nullptr);
+    });
 }
 
 tda_status tda_sosfiltfilt(tda_ctx* ctx, const double* x, int n_sig, int n_samples, const double* sos, const double* zi,
@@ -1071,15 +1165,11 @@ tda_status tda_sosfiltfilt(tda_ctx* ctx, const double* x, int n_sig, int n_sampl
     if (n_sig == 0) return TDA_OK;
     CHECK_PTR(ctx, x); CHECK_PTR(ctx, y); CHECK_PTR(ctx, sos); CHECK_PTR(ctx, zi);
     if (n_samples < 1 || edge < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "bad sizes");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_y, *d_w;
-    s.add((void**)&d_x, x, nullptr, (size_t)n_sig * n_samples * 8);
-    s.add((void**)&d_y, nullptr, y, (size_t)n_sig * n_samples * 8);
-    s.add((void**)&d_w, nullptr, nullptr, (size_t)n_sig * (n_samples + 2 * edge) * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_sosfiltfilt_dev(ctx, d_x, n_sig, n_samples, sos, zi, n_sections, edge, d_y, d_w, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n_sig * n_samples);
+    auto d_y = s.out(y, (size_t)n_sig * n_samples);
+    auto d_w = s.work<double>((size_t)n_sig * (n_samples + 2 * edge));
+    return s.run([&] { return tda_sosfiltfilt_dev(ctx, d_x, n_sig, n_samples, sos, zi, n_sections, edge, d_y, d_w, nullptr); });
 }
 
 tda_status tda_filtfilt(tda_ctx* ctx, const double* x, int n_sig, int n_samples, const double* b, const double* a,
@@ -1089,15 +1179,11 @@ tda_status tda_filtfilt(tda_ctx* ctx, const double* x, int n_sig, int n_samples,
     if (n_sig == 0) return TDA_OK;
     CHECK_PTR(ctx, x); CHECK_PTR(ctx, y); CHECK_PTR(ctx, b); CHECK_PTR(ctx, a); CHECK_PTR(ctx, zi);
     if (n_samples < 1 || edge < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "bad sizes");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_y, *d_w;
-    s.add((void**)&d_x, x, nullptr, (size_t)n_sig * n_samples * 8);
-    s.add((void**)&d_y, nullptr, y, (size_t)n_sig * n_samples * 8);
-    s.add((void**)&d_w, nullptr, nullptr, (size_t)n_sig * (n_samples + 2 * edge) * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_filtfilt_dev(ctx, d_x, n_sig, n_samples, b, a, zi, ntaps, edge, d_y, d_w, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n_sig * n_samples);
+    auto d_y = s.out(y, (size_t)n_sig * n_samples);
+    auto d_w = s.work<double>((size_t)n_sig * (n_samples + 2 * edge));
+    return s.run([&] { return tda_filtfilt_dev(ctx, d_x, n_sig, n_samples, b, a, zi, ntaps, edge, d_y, d_w, nullptr); });
 }
 
 tda_status tda_upfirdn(tda_ctx* ctx, const double* x, long long n_in, const double* h, int len_h, int up, int down,
@@ -1105,30 +1191,22 @@ tda_status tda_upfirdn(tda_ctx* ctx, const double* x, long long n_in, const doub
 {
     CHECK_CTX(ctx); CHECK_PTR(ctx, x); CHECK_PTR(ctx, h); CHECK_PTR(ctx, y);
     if (n_in < 1 || n_out < 1 || len_h < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "bad sizes");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_h, *d_y;
-    s.add((void**)&d_x, x, nullptr, (size_t)n_in * 8);
-    s.add((void**)&d_h, h, nullptr, (size_t)len_h * 8);
-    s.add((void**)&d_y, nullptr, y, (size_t)n_out * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_upfirdn_dev(ctx, d_x, n_in, d_h, len_h, up, down, n_pre_remove, n_out, d_y, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n_in);
+    auto d_h = s.in(h, (size_t)len_h);
+    auto d_y = s.out(y, (size_t)n_out);
+    return s.run([&] { return tda_upfirdn_dev(ctx, d_x, n_in, d_h, len_h, up, down, n_pre_remove, n_out, d_y, nullptr); });
 }
 
 tda_status tda_hilbert_envelope(tda_ctx* ctx, const double* x, int n, const double* g, double* env)
 {
     CHECK_CTX(ctx); CHECK_PTR(ctx, x); CHECK_PTR(ctx, g); CHECK_PTR(ctx, env);
     if (n < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "bad sizes");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_g, *d_e;
-    s.add((void**)&d_x, x, nullptr, (size_t)n * 8);
-    s.add((void**)&d_g, g, nullptr, (size_t)n * 8);
-    s.add((void**)&d_e, nullptr, env, (size_t)n * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_hilbert_envelope_dev(ctx, d_x, n, d_g, d_e, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n);
+    auto d_g = s.in(g, (size_t)n);
+    auto d_e = s.out(env, (size_t)n);
+    return s.run([&] { return tda_hilbert_envelope_dev(ctx, d_x, n, d_g, d_e, nullptr); });
 }
 
 tda_status tda_tau_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int* tau)
@@ -1137,14 +1215,10 @@ tda_status tda_tau_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, in
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau);
     if (n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double* d_win; int* d_tau;
-    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
-    s.add((void**)&d_tau, nullptr, tau, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_tau_batch_dev(ctx, d_win, n_win, n_t, max_lag, d_tau, nullptr));
-    return s.download();
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.out(tau, (size_t)n_win);
+    return s.run([&] { return tda_tau_batch_dev(ctx, d_win, n_win, n_t, max_lag, d_tau, nullptr); });
 }
 
 tda_status tda_features_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, double* feat)
@@ -1153,15 +1227,10 @@ tda_status tda_features_batch(tda_ctx* ctx, const double* dgm, const int* cnt, i
     if (n_dgm == 0) return TDA_OK;
     CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, feat);
     if (cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "cap must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dgm, *d_feat; int* d_cnt;
-    s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16);
-    s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4);
-    s.add((void**)&d_feat, nullptr, feat, (size_t)n_dgm * TDA_N_FEATURES * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_features_batch_dev(ctx, d_dgm, d_cnt, n_dgm, cap, d_feat, nullptr));
-    return s.download();
+    const DgmSet d = dgm_in(s, dgm, cnt, (size_t)n_dgm, cap);
+    auto d_feat = s.out(feat, (size_t)n_dgm * TDA_N_FEATURES);
+    return s.run([&] { return tda_features_batch_dev(ctx, d.rows, d.cnt, n_dgm, cap, d_feat, nullptr); });
 }
 
 tda_status tda_aggregate_batch(tda_ctx* ctx, const double* feat_h0, const double* feat_h1, const int* seg_off,
@@ -1170,16 +1239,12 @@ tda_status tda_aggregate_batch(tda_ctx* ctx, const double* feat_h0, const double
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg); CHECK_NONNEG(ctx, n_total);
     if (n_seg == 0) return TDA_OK;
     CHECK_PTR(ctx, feat_h0); CHECK_PTR(ctx, feat_h1); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, out);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d0, *d1, *d_out; int* d_off;
-    s.add((void**)&d0, feat_h0, nullptr, (size_t)n_total * TDA_N_FEATURES * 8);
-    s.add((void**)&d1, feat_h1, nullptr, (size_t)n_total * TDA_N_FEATURES * 8);
-    s.add((void**)&d_off, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_seg * 4 * TDA_N_FEATURES * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_aggregate_batch_dev(ctx, d0, d1, d_off, n_seg, d_out, nullptr));
-    return s.download();
+    auto d0 = s.in(feat_h0, (size_t)n_total * TDA_N_FEATURES);
+    auto d1 = s.in(feat_h1, (size_t)n_total * TDA_N_FEATURES);
+    auto d_off = s.in(seg_off, (size_t)(n_seg + 1));
+    auto d_out = s.out(out, (size_t)n_seg * 4 * TDA_N_FEATURES);
+    return s.run([&] { return tda_aggregate_batch_dev(ctx, d0, d1, d_off, n_seg, d_out, nullptr); });
 }
 
 tda_status tda_segment_nanmean(tda_ctx* ctx, const double* x, const int* seg_off, int n_seg, int n_total, double* out)
@@ -1187,15 +1252,11 @@ tda_status tda_segment_nanmean(tda_ctx* ctx, const double* x, const int* seg_off
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg); CHECK_NONNEG(ctx, n_total);
     if (n_seg == 0) return TDA_OK;
     CHECK_PTR(ctx, x); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, out);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_out; int* d_off;
-    s.add((void**)&d_x, x, nullptr, (size_t)n_total * 8);
-    s.add((void**)&d_off, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_seg * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_segment_nanmean_dev(ctx, d_x, d_off, n_seg, d_out, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n_total);
+    auto d_off = s.in(seg_off, (size_t)(n_seg + 1));
+    auto d_out = s.out(out, (size_t)n_seg);
+    return s.run([&] { return tda_segment_nanmean_dev(ctx, d_x, d_off, n_seg, d_out, nullptr); });
 }
 
 tda_status tda_spearman_batch(tda_ctx* ctx, const double* x, const double* y, int n_total, int ld, const int* cols,
@@ -1205,17 +1266,13 @@ tda_status tda_spearman_batch(tda_ctx* ctx, const double* x, const double* y, in
     if (n_seg == 0) return TDA_OK;
     CHECK_PTR(ctx, x); CHECK_PTR(ctx, y); CHECK_PTR(ctx, cols); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, r);
     if (n_total < 1 || ld < 1 || n_cols < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_x, *d_y, *d_r; int *d_c, *d_o;
-    s.add((void**)&d_x, x, nullptr, (size_t)n_total * ld * 8);
-    s.add((void**)&d_y, y, nullptr, (size_t)n_total * ld * 8);
-    s.add((void**)&d_c, cols, nullptr, (size_t)n_cols * 4);
-    s.add((void**)&d_o, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
-    s.add((void**)&d_r, nullptr, r, (size_t)n_seg * n_cols * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_spearman_batch_dev(ctx, d_x, d_y, ld, d_c, n_cols, d_o, n_seg, d_r, nullptr));
-    return s.download();
+    auto d_x = s.in(x, (size_t)n_total * ld);
+    auto d_y = s.in(y, (size_t)n_total * ld);
+    auto d_c = s.in(cols, (size_t)n_cols);
+    auto d_o = s.in(seg_off, (size_t)(n_seg + 1));
+    auto d_r = s.out(r, (size_t)n_seg * n_cols);
+    return s.run([&] { return tda_spearman_batch_dev(ctx, d_x, d_y, ld, d_c, n_cols, d_o, n_seg, d_r, nullptr); });
 }
 
 tda_status tda_temporal_corr_batch(tda_ctx* ctx, const double* fa, const double* fe, int n_total, int ld, const int* cols,
@@ -1230,55 +1287,14 @@ tda_status tda_temporal_corr_batch(tda_ctx* ctx, const double* fa, const double*
     if (seg_off[0] != 0 || seg_off[n_seg] != n_total) TDA_FAIL(ctx, TDA_ERR_INVALID, "seg_off must run from 0 to n_total");
     for (int g = 0; g < n_seg; ++g)
         if (seg_off[g + 1] < seg_off[g]) TDA_FAIL(ctx, TDA_ERR_INVALID, "seg_off must not decrease");
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_a, *d_e, *d_out; int *d_c, *d_o, *d_st = nullptr;
-    s.add((void**)&d_a, fa, nullptr, (size_t)n_total * ld * 8);
-    s.add((void**)&d_e, fe, nullptr, (size_t)n_total * ld * 8);
-    s.add((void**)&d_c, cols, nullptr, (size_t)n_cols * 4);
-    s.add((void**)&d_o, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
-    if (status_b) s.add((void**)&d_st, status_b, nullptr, (size_t)n_total * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_seg * 2 * n_cols * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_temporal_corr_dev(ctx, d_a, d_e, ld, d_c, n_cols, d_o, n_seg, d_st, d_out, nullptr));
-    return s.download();
-}
-
-// The host-pointer twins of the pair distances from their own argument checks on: pointer and size checks, the pair
-// indices, staging (with the direction table when dirs is given) and `dev`, a call of the _dev entry point on the staged
-// PairDev pointers.
-struct PairDev { double *a, *b, *dirs = nullptr, *out; int *ca, *cb, *ia = nullptr, *ib = nullptr, *st; };
-
-extern "C++" {                      // (a template inside the extern "C" block of the ABI)
-template <class Dev>
-static tda_status pair_batch_host(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a, const double* dgm_b,
-                                  const int* cnt_b, int n_b, int cap_b, const int* idx_a, const int* idx_b, int n_pairs,
-                                  const double* dirs, int n_dirs, double* out, int* status, Dev dev)
-{
-    if (n_pairs == 0) return TDA_OK;
-    CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); CHECK_PTR(ctx, out);
-    CHECK_PTR(ctx, status);
-    if (n_a < 1 || n_b < 1 || cap_a < 1 || cap_b < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "sizes must be >= 1");
-    for (int i = 0; i < n_pairs; ++i) {
-        const int a = idx_a ? idx_a[i] : i, b = idx_b ? idx_b[i] : i;
-        if (a < 0 || a >= n_a || b < 0 || b >= n_b) TDA_FAIL(ctx, TDA_ERR_INVALID, "pair index out of range");
-    }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
-    Stage s(ctx);
-    PairDev d;
-    s.add((void**)&d.a, dgm_a, nullptr, (size_t)n_a * cap_a * 16);
-    s.add((void**)&d.ca, cnt_a, nullptr, (size_t)n_a * 4);
-    s.add((void**)&d.b, dgm_b, nullptr, (size_t)n_b * cap_b * 16);
-    s.add((void**)&d.cb, cnt_b, nullptr, (size_t)n_b * 4);
-    if (idx_a) s.add((void**)&d.ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d.ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    if (dirs) s.add((void**)&d.dirs, dirs, nullptr, (size_t)n_dirs * 16);
-    s.add((void**)&d.out, nullptr, out, (size_t)n_pairs * 8);
-    s.add((void**)&d.st, nullptr, status, (size_t)n_pairs * 4);
-    RET_IF(s.upload());
-    RET_IF(dev(d));
-    return s.download();
-}
+    auto d_a = s.in(fa, (size_t)n_total * ld);
+    auto d_e = s.in(fe, (size_t)n_total * ld);
+    auto d_c = s.in(cols, (size_t)n_cols);
+    auto d_o = s.in(seg_off, (size_t)(n_seg + 1));
+    auto d_st = s.in(status_b, (size_t)n_total);
+    auto d_out = s.out(out, (size_t)n_seg * 2 * n_cols);
+    return s.run([&] { return tda_temporal_corr_dev(ctx, d_a, d_e, ld, d_c, n_cols, d_o, n_seg, d_st, d_out, nullptr); });
 }
 
 tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -1287,8 +1303,8 @@ tda_status tda_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* c
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
-        [&](const PairDev& d) { return tda_wasserstein_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
-                                                                 d.out, d.st, nullptr); });
+        [&](const PairDev& d) { return tda_wasserstein_batch_dev(ctx, d.a.rows, d.a.cnt, cap_a, d.b.rows, d.b.cnt, cap_b, d.ia, d.ib,
+                                                                 n_pairs, d.out, d.st, nullptr); });
 }
 
 tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -1297,8 +1313,8 @@ tda_status tda_bottleneck_batch(tda_ctx* ctx, const double* dgm_a, const int* cn
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_pairs);
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
-        [&](const PairDev& d) { return tda_bottleneck_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
-                                                                d.out, d.st, nullptr); });
+        [&](const PairDev& d) { return tda_bottleneck_batch_dev(ctx, d.a.rows, d.a.cnt, cap_a, d.b.rows, d.b.cnt, cap_b, d.ia, d.ib,
+                                                                n_pairs, d.out, d.st, nullptr); });
 }
 
 tda_status tda_wasserstein_q_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -1309,8 +1325,8 @@ tda_status tda_wasserstein_q_batch(tda_ctx* ctx, const double* dgm_a, const int*
     if ((order != 1 && order != 2) || (ground != TDA_GROUND_L2 && ground != TDA_GROUND_LINF))
         TDA_FAIL(ctx, TDA_ERR_INVALID, "order must be 1 or 2 and ground TDA_GROUND_L2 or TDA_GROUND_LINF");
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, status,
-        [&](const PairDev& d) { return tda_wasserstein_q_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
-                                                                   order, ground, d.out, d.st, nullptr); });
+        [&](const PairDev& d) { return tda_wasserstein_q_batch_dev(ctx, d.a.rows, d.a.cnt, cap_a, d.b.rows, d.b.cnt, cap_b, d.ia, d.ib,
+                                                                   n_pairs, order, ground, d.out, d.st, nullptr); });
 }
 
 tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -1325,8 +1341,8 @@ tda_status tda_sliced_wasserstein_batch(tda_ctx* ctx, const double* dgm_a, const
     for (int k = 0; k < 2 * n_dirs; ++k)
         if (!std::isfinite(dirs[k])) TDA_FAIL(ctx, TDA_ERR_INVALID, "directions must be finite");
     return pair_batch_host(ctx, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, dirs, n_dirs, out, status,
-        [&](const PairDev& d) { return tda_sliced_wasserstein_batch_dev(ctx, d.a, d.ca, cap_a, d.b, d.cb, cap_b, d.ia, d.ib, n_pairs,
-                                                                        d.dirs, n_dirs, d.out, d.st, nullptr); });
+        [&](const PairDev& d) { return tda_sliced_wasserstein_batch_dev(ctx, d.a.rows, d.a.cnt, cap_a, d.b.rows, d.b.cnt, cap_b, d.ia,
+                                                                        d.ib, n_pairs, d.dirs, n_dirs, d.out, d.st, nullptr); });
 }
 
 // the parameter checks of the diagram kernels, before anything is staged (the launch repeats them)
@@ -1349,21 +1365,13 @@ tda_status tda_diagram_kernel_pairs(tda_ctx* ctx, const double* dgm_a, const int
     CHECK_PTR(ctx, out); CHECK_PTR(ctx, status);
     if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
     if (n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_a = nullptr, *d_b = nullptr, *d_out, *d_kv = nullptr;
-    int *d_ca = nullptr, *d_cb = nullptr, *d_ia = nullptr, *d_ib = nullptr, *d_st;
-    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
-    if (n_b) { s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16); s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4); }
-    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
-    if (kvals) s.add((void**)&d_kv, nullptr, kvals, (size_t)n_pairs * 24);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_diagram_kernel_pairs_dev(ctx, d_a, d_ca, n_a, cap_a, d_b, d_cb, n_b, cap_b, d_ia, d_ib, n_pairs, ninv, mirror, scale,
-                                        weight, wc, d_out, d_kv, d_st, nullptr));
-    return s.download();
+    const PairDev d = pair_stage(s, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out, kvals,
+                                 status);
+    return s.run([&] {
+        return tda_diagram_kernel_pairs_dev(ctx, d.a.rows, d.a.cnt, n_a, cap_a, d.b.rows, d.b.cnt, n_b, cap_b, d.ia, d.ib, n_pairs,
+                                            ninv, mirror, scale, weight, wc, d.out, d.kv, d.st, nullptr);
+    });
 }
 
 tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
@@ -1385,28 +1393,26 @@ tda_status tda_diagram_kernel_gram(tda_ctx* ctx, const double* dgm_a, const int*
     CHECK_PTR(ctx, out);
     if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
     if (!sym) CHECK_PTR(ctx, cnt_b);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_a = nullptr, *d_b = nullptr, *d_out;
-    int *d_ca = nullptr, *d_cb = nullptr, *d_oa = nullptr, *d_ob = nullptr, *d_sa = nullptr, *d_sb = nullptr;
-    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
-    if (seg_off_a) s.add((void**)&d_oa, seg_off_a, nullptr, (size_t)(n_seg_a + 1) * 4);
-    if (status_a && n_a) s.add((void**)&d_sa, status_a, nullptr, (size_t)n_a * 4);
+    const DgmSet a = dgm_in(s, dgm_a, cnt_a, (size_t)n_a, cap_a);
+    const GroupIn ga = group_in(s, seg_off_a, n_seg_a, status_a, (size_t)n_a);
+    DgmSet b;
+    GroupIn gb;
     if (!sym) {
-        // (an empty second set still needs a non-NULL buffer to be told from the symmetric form: 16 bytes of its own)
-        s.add((void**)&d_b, n_b ? dgm_b : nullptr, nullptr, n_b ? (size_t)n_b * cap_b * 16 : 16);
-        s.add((void**)&d_cb, n_b ? cnt_b : nullptr, nullptr, n_b ? (size_t)n_b * 4 : 4);
-        if (seg_off_b) s.add((void**)&d_ob, seg_off_b, nullptr, (size_t)(n_seg_b + 1) * 4);
-        if (status_b && n_b) s.add((void**)&d_sb, status_b, nullptr, (size_t)n_b * 4);
+        // (an empty second set still needs a non-NULL buffer to be told from the symmetric form: two doubles and an int of
+        // its own)
+        if (n_b) b = dgm_in(s, dgm_b, cnt_b, (size_t)n_b, cap_b);
+        else b = {s.work<double>(2), s.work<int>(1)};
+        gb = group_in(s, seg_off_b, n_seg_b, status_b, (size_t)n_b);
     }
-    s.add((void**)&d_out, nullptr, out, (size_t)n_seg_a * n_seg_b * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_diagram_kernel_gram_dev(ctx, d_a, d_ca, n_a, cap_a, d_oa, n_seg_a, d_sa, d_b, d_cb, n_b, cap_b, d_ob, n_seg_b, d_sb,
-                                       skip_mask, ninv, mirror, scale, weight, wc, d_out, nullptr));
-    return s.download();
+    auto d_out = s.out(out, (size_t)n_seg_a * n_seg_b);
+    return s.run([&] {
+        return tda_diagram_kernel_gram_dev(ctx, a.rows, a.cnt, n_a, cap_a, ga.off, n_seg_a, ga.status, b.rows, b.cnt, n_b, cap_b,
+                                           gb.off, n_seg_b, gb.status, skip_mask, ninv, mirror, scale, weight, wc, d_out, nullptr);
+    });
 }
 
-// (its own staging, not pair_batch_host: an index outside its set is a status of that pair, not a refusal of the call)
+// (not pair_batch_host: an index outside its set is a status of that pair, not a refusal of the call)
 tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const int* cnt_a, int n_a, int cap_a,
                                         const double* dgm_b, const int* cnt_b, int n_b, int cap_b, const int* idx_a,
                                         const int* idx_b, int n_pairs, double ninv, double* out, int* status)
@@ -1418,20 +1424,13 @@ tda_status tda_persistence_fisher_batch(tda_ctx* ctx, const double* dgm_a, const
     CHECK_PTR(ctx, out); CHECK_PTR(ctx, status);
     if (n_a) { CHECK_PTR(ctx, dgm_a); CHECK_PTR(ctx, cnt_a); }
     if (n_b) { CHECK_PTR(ctx, dgm_b); CHECK_PTR(ctx, cnt_b); }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_a = nullptr, *d_b = nullptr, *d_out;
-    int *d_ca = nullptr, *d_cb = nullptr, *d_ia = nullptr, *d_ib = nullptr, *d_st;
-    if (n_a) { s.add((void**)&d_a, dgm_a, nullptr, (size_t)n_a * cap_a * 16); s.add((void**)&d_ca, cnt_a, nullptr, (size_t)n_a * 4); }
-    if (n_b) { s.add((void**)&d_b, dgm_b, nullptr, (size_t)n_b * cap_b * 16); s.add((void**)&d_cb, cnt_b, nullptr, (size_t)n_b * 4); }
-    if (idx_a) s.add((void**)&d_ia, idx_a, nullptr, (size_t)n_pairs * 4);
-    if (idx_b) s.add((void**)&d_ib, idx_b, nullptr, (size_t)n_pairs * 4);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_pairs * 8);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_pairs * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_persistence_fisher_batch_dev(ctx, d_a, d_ca, n_a, cap_a, d_b, d_cb, n_b, cap_b, d_ia, d_ib, n_pairs, ninv, d_out,
-                                            d_st, nullptr));
-    return s.download();
+    const PairDev d = pair_stage(s, dgm_a, cnt_a, n_a, cap_a, dgm_b, cnt_b, n_b, cap_b, idx_a, idx_b, n_pairs, nullptr, 0, out,
+                                 nullptr, status);
+    return s.run([&] {
+        return tda_persistence_fisher_batch_dev(ctx, d.a.rows, d.a.cnt, n_a, cap_a, d.b.rows, d.b.cnt, n_b, cap_b, d.ia, d.ib,
+                                                n_pairs, ninv, d.out, d.st, nullptr);
+    });
 }
 
 // (the outputs are staged in both directions: the kernel writes only rows [0, cnt) of a signal's block)
@@ -1445,75 +1444,21 @@ tda_status tda_sublevel_batch(tda_ctx* ctx, const double* sig, const long long* 
     if ((win_start == nullptr) != (win_ld == nullptr)) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_start and win_ld go together");
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, sig); CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, status);
-    // the elements of sig the tables reach
-    long long n_el = (long long)n_win * n_ch * n_t;
-    if (win_start) {
-        n_el = 0;
-        for (int w = 0; w < n_win; ++w) {
-            if (win_start[w] < 0 || win_ld[w] < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative window table entry");
-            const long long end = win_start[w] + (long long)(n_ch - 1) * win_ld[w] + n_t;
-            n_el = end > n_el ? end : n_el;
-        }
-    }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
+    long long n_el;
+    if (tda_status st = sig_extent(ctx, win_start, win_ld, n_win, n_ch, n_t, &n_el)) return st;
     Stage s(ctx);
     const size_t n_sig = (size_t)n_win * n_ch;
-    double *d_sig, *d_dgm;
-    long long *d_ws = nullptr, *d_wl = nullptr;
-    int *d_cnt, *d_idx = nullptr, *d_st;
-    s.add((void**)&d_sig, sig, nullptr, (size_t)n_el * 8);
-    if (win_start) { s.add((void**)&d_ws, win_start, nullptr, (size_t)n_win * 8); s.add((void**)&d_wl, win_ld, nullptr, (size_t)n_win * 8); }
-    s.add((void**)&d_dgm, dgm, dgm, n_sig * cap * 16);
-    if (idx) s.add((void**)&d_idx, idx, idx, n_sig * cap * 8);
-    s.add((void**)&d_cnt, nullptr, cnt, n_sig * 4);
-    s.add((void**)&d_st, nullptr, status, n_sig * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_sublevel_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_dgm, cap, d_cnt, d_idx, d_st, nullptr));
-    return s.download();
+    auto d_sig = s.in(sig, (size_t)n_el);
+    auto d_ws = s.in(win_start, (size_t)n_win);
+    auto d_wl = s.in(win_ld, (size_t)n_win);
+    auto d_dgm = s.inout(dgm, n_sig * cap * 2);
+    auto d_idx = s.inout(idx, n_sig * cap * 2);
+    auto d_cnt = s.out(cnt, n_sig);
+    auto d_st = s.out(status, n_sig);
+    return s.run([&] {
+        return tda_sublevel_batch_dev(ctx, d_sig, d_ws, d_wl, n_win, n_ch, n_t, d_dgm, cap, d_cnt, d_idx, d_st, nullptr);
+    });
 }
-
-// The host form shared by tda_plv_dist_batch and tda_connectivity_dist_batch: the limits (before anything is staged), the
-// elements of sig the tables reach, the staging; dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st) enqueues the _dev form.
-extern "C++" {
-template <class Dev>
-static tda_status window_dist_host(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
-                                   int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* mat,
-                                   int* status, Dev dev)
-{
-    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (n_ch < 2 || n_ch > TDA_PLV_MAX_CHANNELS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_ch must be in [2, TDA_PLV_MAX_CHANNELS]");
-    if (n_t < 2 || n_t > TDA_PLV_MAX_SAMPLES) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be in [2, TDA_PLV_MAX_SAMPLES]");
-    if (method < 0 || method > 3) TDA_FAIL(ctx, TDA_ERR_INVALID, "Unknown method");
-    if ((win_start == nullptr) != (win_ld == nullptr)) TDA_FAIL(ctx, TDA_ERR_INVALID, "win_start and win_ld go together");
-    if (n_win == 0) return TDA_OK;
-    CHECK_PTR(ctx, sig); CHECK_PTR(ctx, g); CHECK_PTR(ctx, dist); CHECK_PTR(ctx, status);
-    // the elements of sig the tables reach
-    long long n_el = (long long)n_win * n_ch * n_t;
-    if (win_start) {
-        n_el = 0;
-        for (int w = 0; w < n_win; ++w) {
-            if (win_start[w] < 0 || win_ld[w] < 0) TDA_FAIL(ctx, TDA_ERR_INVALID, "negative window table entry");
-            const long long end = win_start[w] + (long long)(n_ch - 1) * win_ld[w] + n_t;
-            n_el = end > n_el ? end : n_el;
-        }
-    }
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
-    Stage s(ctx);
-    const size_t nn = (size_t)n_win * n_ch * n_ch;
-    double *d_sig, *d_g, *d_dist, *d_mat = nullptr;
-    long long *d_ws = nullptr, *d_wl = nullptr;
-    int* d_st;
-    s.add((void**)&d_sig, sig, nullptr, (size_t)n_el * 8);
-    s.add((void**)&d_g, g, nullptr, (size_t)n_t * 8);
-    if (win_start) { s.add((void**)&d_ws, win_start, nullptr, (size_t)n_win * 8); s.add((void**)&d_wl, win_ld, nullptr, (size_t)n_win * 8); }
-    s.add((void**)&d_dist, nullptr, dist, nn * 8);
-    if (mat) s.add((void**)&d_mat, nullptr, mat, nn * 8);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(dev(d_sig, d_ws, d_wl, d_g, d_dist, d_mat, d_st));
-    return s.download();
-}
-}   // extern "C++"
 
 tda_status tda_plv_dist_batch(tda_ctx* ctx, const double* sig, const long long* win_start, const long long* win_ld,
                               int n_win, int n_ch, int n_t, const double* g, int method, double* dist, double* plv,
@@ -1552,22 +1497,17 @@ tda_status tda_perm_sums_batch(tda_ctx* ctx, const double* D, int n_mat, int n, 
     CHECK_PTR(ctx, lab);
     if (n_mat) { CHECK_PTR(ctx, D); CHECK_PTR(ctx, out); }
     if (n_mat == 0 && !n1) return TDA_OK;
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     const long long wd = TDA_PT_WORK_DOUBLES(n_mat, n, n_perm);
-    double *d_D = nullptr, *d_work = nullptr, *d_out = nullptr;
-    unsigned long long* d_lab;
-    int* d_n1 = nullptr;
+    Dev<double> d_D, d_work, d_out;
     if (n_mat) {
-        s.add((void**)&d_D, D, nullptr, (((size_t)n_mat * n - 1) * ld + n) * 8);
-        s.add((void**)&d_work, nullptr, nullptr, (size_t)wd * 8);
-        s.add((void**)&d_out, nullptr, out, (size_t)n_mat * 3 * n_perm * 8);
+        d_D = s.in(D, ((size_t)n_mat * n - 1) * ld + n);
+        d_work = s.work<double>((size_t)wd);
+        d_out = s.out(out, (size_t)n_mat * 3 * n_perm);
     }
-    s.add((void**)&d_lab, lab, nullptr, (size_t)TDA_PT_WORDS(n_perm) * n * 8);
-    if (n1) s.add((void**)&d_n1, nullptr, n1, (size_t)n_perm * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_perm_sums_batch_dev(ctx, d_D, n_mat, n, ld, d_lab, n_perm, d_work, wd, d_out, d_n1, nullptr));
-    return s.download();
+    auto d_lab = s.in(lab, (size_t)TDA_PT_WORDS(n_perm) * n);
+    auto d_n1 = s.out(n1, (size_t)n_perm);
+    return s.run([&] { return tda_perm_sums_batch_dev(ctx, d_D, n_mat, n, ld, d_lab, n_perm, d_work, wd, d_out, d_n1, nullptr); });
 }
 
 tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const double* grid,
@@ -1579,17 +1519,14 @@ tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, 
     if (n_grid < 1 || n_grid > TDA_MAX_GRID) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_grid must be 1..TDA_MAX_GRID");
     if (n_dgm == 0) return TDA_OK;
     CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, out);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dgm, *d_grid, *d_out; int* d_cnt;
-    s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16);
-    s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4);
-    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_dgm * (n_levels + 1) * n_grid * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_landscape_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
-                                  nullptr));
-    return s.download();
+    const DgmSet d = dgm_in(s, dgm, cnt, (size_t)n_dgm, cap);
+    auto d_grid = s.in(grid, (size_t)n_grid);
+    auto d_out = s.out(out, (size_t)n_dgm * (n_levels + 1) * n_grid);
+    return s.run([&] {
+        return tda_landscape_mean_dev(ctx, d.rows, d.cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_grid, n_grid, n_levels, d_out,
+                                      nullptr);
+    });
 }
 
 // (the limits of launch_euler, checked before anything is staged)
@@ -1608,16 +1545,14 @@ tda_status tda_euler_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, 
     EULER_LIMITS(ctx, n_grid, max_dim);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, dm); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dm, *d_grid; int *d_cnt, *d_st;
-    s.add((void**)&d_dm, dm, nullptr, (size_t)n_win * n * n * 8);
-    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
-    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_euler_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d_grid, n_grid, max_dim, d_cnt, d_st, nullptr));
-    return s.download();
+    auto d_dm = s.in(dm, (size_t)n_win * n * n);
+    auto d_grid = s.in(grid, (size_t)n_grid);
+    auto d_cnt = s.out(counts, (size_t)n_win * (max_dim + 2) * n_grid);
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_euler_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d_grid, n_grid, max_dim, d_cnt, d_st, nullptr);
+    });
 }
 
 tda_status tda_euler_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -1630,18 +1565,16 @@ tda_status tda_euler_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pt
     EULER_LIMITS(ctx, n_grid, max_dim);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_pc, *d_grid; int *d_n, *d_cnt, *d_st;
-    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
-    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
-    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
-    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_euler_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d_grid, n_grid, max_dim, d_cnt,
-                                     d_st, nullptr));
-    return s.download();
+    auto d_pc = s.in(pc, (size_t)n_win * p_cap * dim);
+    auto d_n = s.in(n_pts, (size_t)n_win);
+    auto d_grid = s.in(grid, (size_t)n_grid);
+    auto d_cnt = s.out(counts, (size_t)n_win * (max_dim + 2) * n_grid);
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_euler_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d_grid, n_grid, max_dim, d_cnt, d_st,
+                                         nullptr);
+    });
 }
 
 tda_status tda_euler_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -1654,19 +1587,17 @@ tda_status tda_euler_takens_batch(tda_ctx* ctx, const double* win, const int* ta
     EULER_LIMITS(ctx, n_grid, max_dim);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_win, *d_grid; int *d_tau, *d_cnt, *d_np = nullptr, *d_st;
-    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
-    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
-    s.add((void**)&d_grid, grid, nullptr, (size_t)n_grid * 8);
-    s.add((void**)&d_cnt, nullptr, counts, (size_t)n_win * (max_dim + 2) * n_grid * 4);
-    if (n_points) s.add((void**)&d_np, nullptr, n_points, (size_t)n_win * 4);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_euler_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d_grid, n_grid, max_dim, d_cnt,
-                                      d_np, d_st, nullptr));
-    return s.download();
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.in(tau, (size_t)n_win);
+    auto d_grid = s.in(grid, (size_t)n_grid);
+    auto d_cnt = s.out(counts, (size_t)n_win * (max_dim + 2) * n_grid);
+    auto d_np = s.out(n_points, (size_t)n_win);
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_euler_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d_grid, n_grid, max_dim, d_cnt, d_np,
+                                          d_st, nullptr);
+    });
 }
 
 tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
@@ -1678,17 +1609,14 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
     if (n_seg == 0) return TDA_OK;
     if (n_win) CHECK_PTR(ctx, counts);
     CHECK_PTR(ctx, mean);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     const size_t rg = (size_t)(max_dim + 2) * n_grid;
-    int *d_cnt, *d_off = nullptr, *d_si = nullptr; double* d_mean;
-    s.add((void**)&d_cnt, counts, nullptr, (size_t)n_win * rg * 4);
-    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, ((size_t)n_seg + 1) * 4);
-    if (status_in) s.add((void**)&d_si, status_in, nullptr, (size_t)n_win * 4);
-    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * rg * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, d_off, n_seg, d_si, skip_mask, d_mean, nullptr));
-    return s.download();
+    auto d_cnt = s.in(counts, (size_t)n_win * rg);
+    const GroupIn g = group_in(s, seg_off, n_seg, status_in, (size_t)n_win);
+    auto d_mean = s.out(mean, (size_t)n_seg * rg);
+    return s.run([&] {
+        return tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, g.off, n_seg, g.status, skip_mask, d_mean, nullptr);
+    });
 }
 
 // (the limits of launch_generators, checked before anything is staged)
@@ -1701,32 +1629,31 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
             TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_edge needs the H0 rows: h0, h0_cnt and h0_cap >= 1");                   \
     } while (0)
 
+namespace {
 // the device twins of the row inputs and outputs of a host call
 struct GenStage {
-    double *h0 = nullptr, *h1 = nullptr, *part = nullptr;
-    int *h0_cnt = nullptr, *h1_cnt = nullptr, *rips_status = nullptr, *h1_flag = nullptr, *cyc_len = nullptr, *work = nullptr;
-    short *h1_gen = nullptr, *cyc = nullptr, *h0_edge = nullptr;
+    DgmSet h0, h1;
+    Dev<int> rips_status, h1_flag, cyc_len, work;
+    Dev<short> h1_gen, cyc, h0_edge;
+    Dev<double> part;
     void add(Stage& s, size_t nw, int part_ld, GEN_PARAMS)
     {
         (void)skip_mask;
-        if (h0 && h0_cnt) {
-            s.add((void**)&this->h0, h0, nullptr, nw * h0_cap * 16);
-            s.add((void**)&this->h0_cnt, h0_cnt, nullptr, nw * 4);
-        }
-        s.add((void**)&this->h1, h1, nullptr, nw * h1_cap * 16);
-        s.add((void**)&this->h1_cnt, h1_cnt, nullptr, nw * 4);
-        if (rips_status) s.add((void**)&this->rips_status, rips_status, nullptr, nw * 4);
-        s.add((void**)&this->h1_gen, nullptr, h1_gen, nw * h1_cap * 8);
-        s.add((void**)&this->h1_flag, nullptr, h1_flag, nw * h1_cap * 4);
-        if (cyc) s.add((void**)&this->cyc, nullptr, cyc, nw * h1_cap * cyc_cap * 2);
-        s.add((void**)&this->cyc_len, nullptr, cyc_len, nw * h1_cap * 4);
-        if (part) s.add((void**)&this->part, nullptr, part, nw * part_ld * 8);
-        if (h0_edge) s.add((void**)&this->h0_edge, nullptr, h0_edge, nw * h0_cap * 4);
-        if (work) s.add((void**)&this->work, nullptr, work, nw * 8 * 4);
+        if (h0 && h0_cnt) this->h0 = dgm_in(s, h0, h0_cnt, nw, h0_cap);
+        this->h1 = dgm_in(s, h1, h1_cnt, nw, h1_cap);
+        this->rips_status = s.in(rips_status, nw);
+        this->h1_gen = s.out(h1_gen, nw * h1_cap * 4);
+        this->h1_flag = s.out(h1_flag, nw * h1_cap);
+        this->cyc = s.out(cyc, nw * h1_cap * cyc_cap);
+        this->cyc_len = s.out(cyc_len, nw * h1_cap);
+        this->part = s.out(part, nw * part_ld);
+        this->h0_edge = s.out(h0_edge, nw * h0_cap * 2);
+        this->work = s.out(work, nw * 8);
     }
 };
-#define GEN_STAGED(d) d.h0, h0_cap, d.h0_cnt, d.h1, h1_cap, d.h1_cnt, d.rips_status, skip_mask, cyc_cap, d.h1_gen, d.h1_flag, \
-                      d.cyc, d.cyc_len, d.part, d.h0_edge, d.work
+}   // namespace
+#define GEN_STAGED(d) d.h0.rows, h0_cap, d.h0.cnt, d.h1.rows, h1_cap, d.h1.cnt, d.rips_status, skip_mask, cyc_cap, d.h1_gen, \
+                      d.h1_flag, d.cyc, d.cyc_len, d.part, d.h0_edge, d.work
 
 tda_status tda_generators_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
                                    GEN_PARAMS, int* status)
@@ -1736,16 +1663,14 @@ tda_status tda_generators_dm_batch(tda_ctx* ctx, const double* dm, int n_win, in
     GEN_LIMITS(ctx);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, dm); GEN_CHECK_PTRS(ctx);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     GenStage d;
-    double* d_dm; int* d_st;
-    s.add((void**)&d_dm, dm, nullptr, (size_t)n_win * n * n * 8);
+    auto d_dm = s.in(dm, (size_t)n_win * n * n);
     d.add(s, (size_t)n_win, n, GEN_PASS);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_generators_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, GEN_STAGED(d), d_st, nullptr));
-    return s.download();
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_generators_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, GEN_STAGED(d), d_st, nullptr);
+    });
 }
 
 tda_status tda_generators_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -1757,17 +1682,15 @@ tda_status tda_generators_cloud_batch(tda_ctx* ctx, const double* pc, const int*
     GEN_LIMITS(ctx);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); GEN_CHECK_PTRS(ctx);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     GenStage d;
-    double* d_pc; int *d_n, *d_st;
-    s.add((void**)&d_pc, pc, nullptr, (size_t)n_win * p_cap * dim * 8);
-    s.add((void**)&d_n, n_pts, nullptr, (size_t)n_win * 4);
+    auto d_pc = s.in(pc, (size_t)n_win * p_cap * dim);
+    auto d_n = s.in(n_pts, (size_t)n_win);
     d.add(s, (size_t)n_win, p_cap, GEN_PASS);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_generators_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, GEN_STAGED(d), d_st, nullptr));
-    return s.download();
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_generators_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, GEN_STAGED(d), d_st, nullptr);
+    });
 }
 
 tda_status tda_generators_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -1779,19 +1702,17 @@ tda_status tda_generators_takens_batch(tda_ctx* ctx, const double* win, const in
     GEN_LIMITS(ctx);
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); GEN_CHECK_PTRS(ctx);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
     GenStage d;
-    double* d_win; int *d_tau, *d_np = nullptr, *d_st;
-    s.add((void**)&d_win, win, nullptr, (size_t)n_win * n_t * 8);
-    s.add((void**)&d_tau, tau, nullptr, (size_t)n_win * 4);
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.in(tau, (size_t)n_win);
     d.add(s, (size_t)n_win, TDA_MAX_POINTS, GEN_PASS);
-    if (n_points) s.add((void**)&d_np, nullptr, n_points, (size_t)n_win * 4);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_win * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_generators_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, GEN_STAGED(d), d_np, d_st,
-                                           nullptr));
-    return s.download();
+    auto d_np = s.out(n_points, (size_t)n_win);
+    auto d_st = s.out(status, (size_t)n_win);
+    return s.run([&] {
+        return tda_generators_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, GEN_STAGED(d), d_np, d_st,
+                                               nullptr);
+    });
 }
 
 tda_status tda_generators_mean(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
@@ -1803,16 +1724,13 @@ tda_status tda_generators_mean(tda_ctx* ctx, const double* part, int n_win, int 
     if (n_seg == 0) return TDA_OK;
     if (n_win) CHECK_PTR(ctx, part);
     CHECK_PTR(ctx, mean);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_part, *d_mean; int *d_off = nullptr, *d_si = nullptr;
-    s.add((void**)&d_part, part, nullptr, (size_t)n_win * n * 8);
-    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, ((size_t)n_seg + 1) * 4);
-    if (status_in) s.add((void**)&d_si, status_in, nullptr, (size_t)n_win * 4);
-    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * n * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_generators_mean_dev(ctx, d_part, n_win, n, d_off, n_seg, d_si, skip_mask, d_mean, nullptr));
-    return s.download();
+    auto d_part = s.in(part, (size_t)n_win * n);
+    const GroupIn g = group_in(s, seg_off, n_seg, status_in, (size_t)n_win);
+    auto d_mean = s.out(mean, (size_t)n_seg * n);
+    return s.run([&] {
+        return tda_generators_mean_dev(ctx, d_part, n_win, n, g.off, n_seg, g.status, skip_mask, d_mean, nullptr);
+    });
 }
 
 tda_status tda_frechet_mean_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, const int* seg_off,
@@ -1826,21 +1744,18 @@ tda_status tda_frechet_mean_batch(tda_ctx* ctx, const double* dgm, const int* cn
     if (n_seg == 0) return TDA_OK;
     if (n_dgm) { CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); }
     CHECK_PTR(ctx, mean); CHECK_PTR(ctx, mean_cnt); CHECK_PTR(ctx, var); CHECK_PTR(ctx, iters); CHECK_PTR(ctx, status);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dgm = nullptr, *d_mean, *d_var; int *d_cnt = nullptr, *d_off = nullptr, *d_sin = nullptr, *d_mc, *d_it, *d_st;
-    if (n_dgm) { s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16); s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4); }
-    if (seg_off) s.add((void**)&d_off, seg_off, nullptr, (size_t)(n_seg + 1) * 4);
-    if (status_in && n_dgm) s.add((void**)&d_sin, status_in, nullptr, (size_t)n_dgm * 4);
-    s.add((void**)&d_mean, nullptr, mean, (size_t)n_seg * cap_out * 16);
-    s.add((void**)&d_mc, nullptr, mean_cnt, (size_t)n_seg * 4);
-    s.add((void**)&d_var, nullptr, var, (size_t)n_seg * 8);
-    s.add((void**)&d_it, nullptr, iters, (size_t)n_seg * 4);
-    s.add((void**)&d_st, nullptr, status, (size_t)n_seg * 4);
-    RET_IF(s.upload());
-    RET_IF(tda_frechet_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, d_off, n_seg, d_sin, skip_mask, max_iter, d_mean, d_mc, cap_out,
-                                d_var, d_it, d_st, nullptr));
-    return s.download();
+    const DgmSet d = dgm_in(s, dgm, cnt, (size_t)n_dgm, cap);
+    const GroupIn g = group_in(s, seg_off, n_seg, status_in, (size_t)n_dgm);
+    auto d_mean = s.out(mean, (size_t)n_seg * cap_out * 2);
+    auto d_mc = s.out(mean_cnt, (size_t)n_seg);
+    auto d_var = s.out(var, (size_t)n_seg);
+    auto d_it = s.out(iters, (size_t)n_seg);
+    auto d_st = s.out(status, (size_t)n_seg);
+    return s.run([&] {
+        return tda_frechet_mean_dev(ctx, d.rows, d.cnt, cap, n_dgm, g.off, n_seg, g.status, skip_mask, max_iter, d_mean, d_mc, cap_out,
+                                    d_var, d_it, d_st, nullptr);
+    });
 }
 
 static bool image_edges_ok(const double* e, int n)
@@ -1864,18 +1779,15 @@ tda_status tda_image_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int 
         TDA_FAIL(ctx, TDA_ERR_INVALID, "image edges must be finite and strictly ascending");
     if (n_dgm == 0) return TDA_OK;
     CHECK_PTR(ctx, dgm); CHECK_PTR(ctx, cnt); CHECK_PTR(ctx, out);
-    TDA_HIP(ctx, hipSetDevice(ctx->device));
     Stage s(ctx);
-    double *d_dgm, *d_xe, *d_ye, *d_out; int* d_cnt;
-    s.add((void**)&d_dgm, dgm, nullptr, (size_t)n_dgm * cap * 16);
-    s.add((void**)&d_cnt, cnt, nullptr, (size_t)n_dgm * 4);
-    s.add((void**)&d_xe, xe, nullptr, (size_t)(n_x + 1) * 8);
-    s.add((void**)&d_ye, ye, nullptr, (size_t)(n_y + 1) * 8);
-    s.add((void**)&d_out, nullptr, out, (size_t)n_dgm * n_y * n_x * 8);
-    RET_IF(s.upload());
-    RET_IF(tda_image_mean_dev(ctx, d_dgm, d_cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_xe, n_x, d_ye, n_y, sigma, power,
-                              d_out, nullptr));
-    return s.download();
+    const DgmSet d = dgm_in(s, dgm, cnt, (size_t)n_dgm, cap);
+    auto d_xe = s.in(xe, (size_t)(n_x + 1));
+    auto d_ye = s.in(ye, (size_t)(n_y + 1));
+    auto d_out = s.out(out, (size_t)n_dgm * n_y * n_x);
+    return s.run([&] {
+        return tda_image_mean_dev(ctx, d.rows, d.cnt, cap, n_dgm, nullptr, n_dgm, nullptr, 0, d_xe, n_x, d_ye, n_y, sigma, power,
+                                  d_out, nullptr);
+    });
 }
 
 // ---------------------------------------------------------------- timing helpers

@@ -30,6 +30,34 @@ def test_header_symbols_exported_and_bound():
     assert lib.tda_version() >= 100
 
 
+def test_every_ctypes_signature_is_the_headers():
+    """Return type, argument count and the type of every argument of every _lib.SYMBOLS entry against its prototype."""
+    import ctypes as C
+    from tda_eeg_audio_amd import _lib
+    src = open(os.path.join(ROOT, "include", "tdaeeg.h")).read()
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
+    protos = {m.group(2): (m.group(1), m.group(3))
+              for m in re.finditer(r"\b(tda_status|int|size_t|void)\s+(tda_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", src)}
+    assert set(protos) == set(_lib.SYMBOLS)
+    scalars = {"int": C.c_int, "double": C.c_double, "long long": C.c_longlong, "size_t": C.c_size_t}
+    results = {"tda_status": C.c_int, "int": C.c_int, "size_t": C.c_size_t, "void": None}
+
+    def is_pointer(t):
+        return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+
+    for name, (res, args) in _lib.SYMBOLS.items():
+        ret, params = protos[name]
+        assert res is results[ret], name
+        decl = [" ".join(a.split()) for a in params.split(",")]
+        decl = [] if decl == ["void"] else decl
+        assert len(args) == len(decl), name
+        for a, d in zip(args, decl):
+            if "*" in d:
+                assert is_pointer(a), (name, d)
+            else:
+                assert a is scalars[d.replace("const ", "").rsplit(" ", 1)[0]], (name, d)
+
+
 def test_no_gpu_means_loud_failure_not_fallback():
     import torch
     from tda_eeg_audio_amd import _lib

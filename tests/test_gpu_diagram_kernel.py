@@ -97,6 +97,11 @@ def test_pair_values_and_distance(ctx, pair_case, name):
     # the host twin gives the same bytes; without kvals the distances do not change
     out_h, kv_h, st_h = engine.diagram_kernel_batch(ra, ca, rb, cb, KERNELS[name], idx_a=ia, idx_b=ib, ctx=ctx, want_status=True)
     assert out_h.tobytes() == out.tobytes() and kv_h.tobytes() == kv.tobytes() and (st_h == 0).all()
+    p, out_n, st_n = engine.ptr, np.empty(len(ia)), np.empty(len(ia), np.int32)
+    ha, hca, hb, hcb, hia, hib = engine.f64(ra), engine.i32(ca), engine.f64(rb), engine.i32(cb), engine.i32(ia), engine.i32(ib)
+    ctx.check(ctx.lib.tda_diagram_kernel_pairs(ctx.h, p(ha), p(hca), len(ca), ra.shape[1], p(hb), p(hcb), len(cb), rb.shape[1], p(hia),
+                                               p(hib), len(ia), *engine._kernel_params(KERNELS[name]), p(out_n), None, p(st_n)))
+    assert out_n.tobytes() == out.tobytes() and (st_n == 0).all()
     out2, _ = engine.diagram_kernel_dev(t[0], t[1], t[2], t[3], KERNELS[name], idx_a=t[4], idx_b=t[5], ctx=ctx)
     assert out2.cpu().numpy().tobytes() == out.tobytes()
 
@@ -187,6 +192,9 @@ def test_gram_symmetric(ctx, gram_case, name):
     assert np.isnan(X[dead]).all() and np.isnan(X[:, dead]).all()
     _hold(f"gram cross route {name}", X[live], R[live], A[live], N[live], par, dk.wmax(dgms, par))
     assert X[np.triu_indices(7)].tobytes() == G[np.triu_indices(7)].tobytes()         # the tiles h >= g are the same launch shape
+    Xh = engine.diagram_kernel_gram(rows, cnt, KERNELS[name], seg_off_a=off, status_a=status, rows_b=rows, cnt_b=cnt, seg_off_b=off,
+                                    status_b=status, skip_mask=SKIP, ctx=ctx)
+    assert Xh.tobytes() == X.tobytes()                                                # the host twin with status_b
     # a group alone gives the bytes it gives inside the batch; so does a pair of groups through the cross route
     for g in (1, 4, 6):
         sl = slice(off[g], off[g + 1])
@@ -216,6 +224,10 @@ def test_gram_without_groups_and_rectangular(ctx, gram_case):
     # no status array at all: nothing is masked
     G2 = engine.diagram_kernel_gram_dev(t[0], t[1], KERNELS["pwg"], ctx=ctx).cpu().numpy()
     assert np.isfinite(G2).all() and G2[ix].tobytes() == G[ix].tobytes()
+    # the host twin without seg_off, symmetric and cross
+    assert engine.diagram_kernel_gram(rows[:n], cnt[:n], KERNELS["pwg"], status_a=status[:n], skip_mask=SKIP, ctx=ctx).tobytes() == G.tobytes()
+    X2 = engine.diagram_kernel_gram_dev(t[0], t[1], KERNELS["pwg"], rows_b=t[0], cnt_b=t[1], ctx=ctx).cpu().numpy()
+    assert engine.diagram_kernel_gram(rows[:n], cnt[:n], KERNELS["pwg"], rows_b=rows[:n], cnt_b=cnt[:n], ctx=ctx).tobytes() == X2.tobytes()
     # a rectangular 3 x 5 cross matrix between two sets with capacities of their own
     rng = np.random.default_rng(13)
     A3 = [[_diagram(rng, 40), _diagram(rng, 7)], [_diagram(rng, GT + 1)], [_diagram(rng, 3) for _ in range(5)]]

@@ -80,6 +80,7 @@ def test_corr_dist_sliding_other_lengths_steps_and_strides(ctx, n_ch):
         ct = torch.full((n_win, n_ch, n_ch), -7.0, dtype=torch.float64, device=st.device)
         dt = engine.corr_dist_sliding_dev(st, win_len, step, corr_t=ct, ctx=ctx)
         assert dist.shape == corr.shape == tuple(dt.shape) == (n_win, n_ch, n_ch)
+        assert engine.corr_dist_sliding(sig, win_len, step, ctx=ctx).tobytes() == dist.tobytes()       # corr = NULL
         if n_win:
             oc, od = port.corr_dist_batch(sc.stack_of(sig[None], win_len, step))
             ok = np.array_equal(dist, od) and np.array_equal(corr, oc)

@@ -197,6 +197,12 @@ def test_takens_windows(ctx):
     # the host form
     oh, nh, sh = engine.euler_takens_batch(sig, taus, grid, 3, ctx=ctx)
     assert oh.tobytes() == out.tobytes() and sh.tobytes() == st.tobytes() and nh.tolist() == npts.tolist()
+    # ... with n_points = NULL
+    p = engine.ptr
+    w, tau, o2, s2 = engine.f64(sig), engine.i32(taus), np.zeros_like(oh), np.zeros_like(sh)
+    ctx.check(ctx.lib.tda_euler_takens_batch(ctx.h, p(w), p(tau), len(taus), sig.shape[1], 3, 2, 2.0, p(grid), len(grid), 3,
+                                             p(o2), None, p(s2)))
+    assert o2.tobytes() == out.tobytes() and s2.tobytes() == st.tobytes()
 
 
 # ---------------------------------------------------------------- batches, host forms
@@ -256,6 +262,12 @@ def test_group_means(ctx):
     ctx.check(ctx.lib.tda_euler_mean(ctx.h, big.ctypes.data_as(C.c_void_p), 5, 3, 2, seg2.ctypes.data_as(C.c_void_p), 2, None, 0,
                                      mh.ctypes.data_as(C.c_void_p)))
     assert mh.tobytes() == er.mean_exact(big, seg2).tobytes() and mh[0, 0, 0] == (4 * 2_000_000_000 - 7) / 5
+    # the host form with status_in given, and with seg_off = NULL
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)                    # noqa: E731
+    mh4, mh7 = np.full((4, 5, 3), -1.0), np.full((7, 5, 3), -1.0)
+    ctx.check(ctx.lib.tda_euler_mean(ctx.h, hp(out), 7, 3, 3, hp(seg), 4, hp(st), 4 | 16, hp(mh4)))
+    ctx.check(ctx.lib.tda_euler_mean(ctx.h, hp(out), 7, 3, 3, None, 7, None, 0, hp(mh7)))
+    assert mh4.tobytes() == mean.tobytes() and mh7.tobytes() == own.tobytes()
 
 
 def _msg(ctx):

@@ -159,6 +159,8 @@ def test_host_form_against_dev_form(ctx, seeded):
     status = np.zeros(len(cnt), np.int32); status[::3] = 4
     _same(engine.frechet_mean_batch(rows, cnt, seg_off=off, status=status, skip_mask=4, cap_out=192, ctx=ctx),
           _gpu(ctx, rows, cnt, off, status=status, mask=4, cap_out=192))
+    # seg_off = NULL: every diagram its own group
+    _same(engine.frechet_mean_batch(rows[:3], cnt[:3], cap_out=192, ctx=ctx), _gpu(ctx, rows[:3], cnt[:3], cap_out=192))
 
 
 def test_utils_frechet_mean(ctx):

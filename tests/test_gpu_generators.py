@@ -290,6 +290,12 @@ def test_takens_windows(ctx):
     host = engine.generators_takens_batch(sig, taus, h0, c0, h1, c1, ctx=ctx)
     _same(host, out)
     assert host["status"].tolist() == out["status"].tolist() and host["n_points"][:2].tolist() == [23, 123]
+    # ... with n_points = NULL
+    o, rows, outs = engine._gen_host(len(taus), 128, h0, c0, h1, c1, 128, None, True, True, False)
+    w = engine.f64(sig)
+    ctx.check(ctx.lib.tda_generators_takens_batch(ctx.h, engine.ptr(w), engine.ptr(taus), len(taus), sig.shape[1], 3, 2, 2.0,
+                                                  *rows, 0, *outs, None, engine.ptr(o["status"])))
+    _same(o, out, names=NAMES + ("status",))
 
 
 # ---------------------------------------------------------------- batches, host forms, means
@@ -322,6 +328,20 @@ def test_batch_behaviour(ctx):
     rh0, rc0, rh1, rc1, _ = engine.rips_dm_batch(dms, h1_cap=512, ctx=ctx, raw=True)
     host = engine.generators_dm_batch(dms, rh0, rc0, rh1, rc1, cyc_cap=16, ctx=ctx)
     _same(host, {k: v[:24] for k, v in out.items()})
+    # ... its other branches: no H0 rows, the Rips status words, no part, no h0_edge, the work counters
+    lean = dict(cyc_cap=16, part=False, h0_edge=False, work=True, ctx=ctx)
+    lean_d = engine.generators_dm_dev(dm_t, (None, None, dgm.h1, dgm.c1), rips_status=dgm.status, **lean).to_host()
+    lean_h = engine.generators_dm_batch(dms, None, None, rh1, rc1, rips_status=dgm.status.cpu().numpy(), **lean)
+    assert sorted(lean_h) == sorted(lean_d) == ["cyc", "cyc_len", "h1_flag", "h1_gen", "status", "work"]
+    _same(lean_h, lean_d, names=sorted(lean_d))
+    # ... and cyc = NULL: edges, flags and lengths only
+    o, rows, outs = engine._gen_host(24, 47, rh0, rc0, rh1, rc1, 16, None, False, True, False)
+    d = engine.f64(dms)
+    ctx.check(ctx.lib.tda_generators_dm_batch(ctx.h, engine.ptr(d), 24, 47, 2.0, 1, *rows, 0, *outs[:3], None, *outs[4:],
+                                              engine.ptr(o["status"])))
+    bare = engine.DeviceGenerators(24, 47, 512, 16, 47, dm_t.device, part=False, cyc=False)
+    engine.generators_dm_dev(dm_t, dgm, cyc_cap=16, part=False, out=bare, ctx=ctx)
+    _same(o, bare.to_host(), names=("h1_gen", "h1_flag", "cyc_len", "h0_edge", "status"))
     torch.cuda.synchronize()
 
 
@@ -366,6 +386,9 @@ def test_group_means(ctx):
     hp = lambda a: a.ctypes.data_as(C.c_void_p)                   # noqa: E731
     ctx.check(ctx.lib.tda_generators_mean(ctx.h, hp(part), 7, 24, hp(seg), 4, hp(st), 4 | 16, hp(mh)))
     assert mh.tobytes() == ref.tobytes()
+    mo = np.full((7, 24), -1.0)                                   # seg_off = NULL, status_in = NULL
+    ctx.check(ctx.lib.tda_generators_mean(ctx.h, hp(part), 7, 24, None, 7, None, 0, hp(mo)))
+    assert mo.tobytes() == own.tobytes()
 
 
 def _msg(ctx):

@@ -116,6 +116,55 @@ def test_takens_landmarks_and_diagrams(ctx, n_t, dim, sub, n_perm, taus):
             assert got["n_full"][w] == len(X) == ref.n_takens(n_t, dim, tau, sub)
         rows = _check_window(got, w, X, n_perm, tau_ok=tau >= 1)
         _check_diagrams(out, got, w, rows, ctx)
+    if (n_t, dim, sub, n_perm) == (300, 2, 2, 17):
+        _check_host_takens_rips_landmarks(ctx, wins, taus, dim, sub, n_perm, out, got)
+
+
+def _check_host_takens_rips_landmarks(ctx, wins, taus, dim, sub, n_perm, out, got):
+    """The host forms tda_takens_rips_landmarks and tda_takens_landmarks on numpy buffers: the bytes of the _dev form, with
+    and without the optional outputs (lm_lambda, n_points); rows from n_lm on keep the caller's zeros; h0_cap < n_perm is
+    refused."""
+    p = engine.ptr
+    n_win, n_t = wins.shape
+    w_h, tau_h = engine.f64(wins), engine.i32(taus)
+    dev = {k: getattr(out, k).cpu().numpy() for k in ("h0", "c0", "h1", "c1", "status", "n_points")}
+
+    def call(optional, rips=True, h0_cap=_lib.MAX_POINTS):
+        lm, idx, lam, rc, n_lm, n_full = engine._landmark_out(n_win, n_perm, dim)
+        h0, h1 = np.zeros((n_win, _lib.MAX_POINTS, 2)), np.zeros((n_win, H1_CAP, 2))
+        c0, c1, n_points, st = (np.zeros(n_win, np.int32) for _ in range(4))
+        lms = (p(lm), p(idx), p(lam) if optional else None, p(rc), p(n_lm), p(n_full))
+        if rips:
+            rc_ = ctx.lib.tda_takens_rips_landmarks(ctx.h, p(w_h), p(tau_h), n_win, n_t, dim, sub, n_perm, engine.MAX_EDGE_LENGTH,
+                                                    *lms, p(h0), h0_cap, p(c0), p(h1), H1_CAP, p(c1),
+                                                    p(n_points) if optional else None, p(st))
+        else:
+            rc_ = ctx.lib.tda_takens_landmarks(ctx.h, p(w_h), p(tau_h), n_win, n_t, dim, sub, n_perm, *lms)
+        return rc_, dict(lm=lm, idx=idx, lam=lam, r_cover=rc, n_lm=n_lm, n_full=n_full, h0=h0, c0=c0, h1=h1, c1=c1,
+                         n_points=n_points, status=st)
+
+    for optional, rips in ((True, True), (False, True), (True, False), (False, False)):
+        rc_, h = call(optional, rips)
+        assert rc_ == 0
+        for name in ("r_cover", "n_lm", "n_full"):
+            assert h[name].tobytes() == got[name].tobytes(), (optional, rips, name)
+        for w in range(n_win):
+            k = got["n_lm"][w]
+            assert 0 < k <= n_perm
+            for name in ("lm", "idx") + (("lam",) if optional else ()):
+                assert h[name][w, :k].tobytes() == got[name][w, :k].tobytes(), (optional, rips, name, w)
+                assert not h[name][w, k:].any(), (optional, rips, name, w)
+            assert optional or not h["lam"][w].any()
+        if not rips:
+            continue
+        for name in ("c0", "c1", "status"):
+            assert h[name].tobytes() == dev[name].tobytes(), (optional, name)
+        assert h["n_points"].tobytes() == (dev["n_points"] if optional else np.zeros(n_win, np.int32)).tobytes()
+        for w in range(n_win):
+            c0, c1 = dev["c0"][w], dev["c1"][w]
+            assert h["h0"][w, :c0].tobytes() == dev["h0"][w, :c0].tobytes()
+            assert h["h1"][w, :c1].tobytes() == dev["h1"][w, :c1].tobytes()
+    assert call(True, h0_cap=n_perm - 1)[0] == 1
 
 
 @pytest.mark.parametrize("n_t,sub,n_perm,taus,n_lm", [
@@ -166,6 +215,14 @@ def test_cloud_landmarks(ctx, normalise):
     for name, arr in zip(("lm", "idx", "lam", "r_cover", "n_lm", "n_full"), h):
         keep = got[name] != (SENTINEL if arr.dtype == np.float64 else int(SENTINEL))
         assert np.array_equal(arr[keep], got[name][keep], equal_nan=True) and not arr[~keep].any(), name
+    if normalise:                                               # ... and without lm_lambda: the other outputs' bytes
+        p, pc_h, n_h = engine.ptr, engine.f64(pc), engine.i32(n_pts)
+        lm2, idx2, lam2, rc2, n_lm2, n_full2 = engine._landmark_out(len(n_pts), n_perm, dim)
+        assert ctx.lib.tda_cloud_landmarks(ctx.h, p(pc_h), p(n_h), len(n_pts), p_cap, dim, 1, n_perm, p(lm2), p(idx2), None, p(rc2),
+                                           p(n_lm2), p(n_full2)) == 0
+        for a, b in zip((lm2, idx2, rc2, n_lm2, n_full2), (h[0], h[1], h[3], h[4], h[5])):
+            assert a.tobytes() == b.tobytes()
+        assert not lam2.any()
 
 
 def test_batch_of_300_and_single_windows(ctx):

@@ -437,6 +437,16 @@ def test_takens_rips_edge_cases(ctx):
     for w in (3, 4, 5):
         (o0, o1), P = port.audio_persistence(wins[w], int(tau[w]))
         assert st[w] == 0 and _same_multiset(h0[w], o0) and _same_multiset(h1[w], o1)
+    # n_points = NULL: the other outputs' bytes
+    r0, rc0, r1, rc1, _, rst = engine.takens_rips_batch(wins, tau, ctx=ctx, raw=True)
+    p, w_h = engine.ptr, engine.f64(wins)
+    g0, g1 = np.empty_like(r0), np.empty_like(r1)
+    gc0, gc1, gst = (np.empty(6, np.int32) for _ in range(3))
+    ctx.check(ctx.lib.tda_takens_rips_batch(ctx.h, p(w_h), p(tau), 6, wins.shape[1], 3, 2, engine.MAX_EDGE_LENGTH, p(g0), r0.shape[1],
+                                            p(gc0), p(g1), r1.shape[1], p(gc1), None, p(gst)))
+    assert (gc0.tobytes(), gc1.tobytes(), gst.tobytes()) == (rc0.tobytes(), rc1.tobytes(), rst.tobytes())
+    for w in range(6):
+        assert g0[w, :rc0[w]].tobytes() == r0[w, :rc0[w]].tobytes() and g1[w, :rc1[w]].tobytes() == r1[w, :rc1[w]].tobytes()
     # constant window: zero range -> 1 (utils.py:129); all points coincide
     const = np.full((1, 250), 0.75)
     h0, h1, npts, st = engine.takens_rips_batch(const, np.array([2], np.int32), ctx=ctx)

@@ -91,6 +91,12 @@ def test_a_relabelling_alone_and_a_matrix_alone(ctx):
     # fewer relabellings than the packed words hold: the rest is not computed into the outputs
     got, n1 = _run(D, lab, ctx, n_perm=70)
     assert got.tobytes() == want[:, :, :70].tobytes() and np.array_equal(n1, want_n1[:70])
+    # the host form without n1, and with n1 alone (no matrix)
+    p, d, packed = engine.ptr, engine.f64(D), engine.pack_labels(lab)
+    out, n1 = np.empty((3, 3, 257)), np.empty(257, np.int32)
+    ctx.check(ctx.lib.tda_perm_sums_batch(ctx.h, p(d), 3, 129, d.shape[2], p(packed), 257, p(out), None))
+    ctx.check(ctx.lib.tda_perm_sums_batch(ctx.h, None, 0, 129, 129, p(packed), 257, None, p(n1)))
+    assert out.tobytes() == want.tobytes() and np.array_equal(n1, want_n1)
 
 
 def test_complement_swaps_the_within_sums(ctx):

@@ -201,6 +201,11 @@ def test_host_twin_equals_dev_form(ctx, n_t):
     host = engine.sublevel_batch(sigs, cap=cap, dgm=dgm, idx=idx, ctx=ctx)
     _assert_bytes(host, _run_dev(sigs, ctx, cap=cap))
     _assert_bytes(host, ref.sublevel_batch(sigs, cap=cap))
+    if n_t == 65:                                                   # idx = NULL: the rows, counts and status words alone
+        p, s = engine.ptr, engine.f64(sigs)
+        d2, c2, st2 = np.full((13, cap, 2), np.nan), np.zeros(13, np.int32), np.zeros(13, np.int32)
+        ctx.check(ctx.lib.tda_sublevel_batch(ctx.h, p(s), None, None, 13, 1, n_t, p(d2), cap, p(c2), None, p(st2)))
+        assert d2.tobytes() == host[0].tobytes() and c2.tobytes() == host[1].tobytes() and st2.tobytes() == host[3].tobytes()
 
 
 def test_utils_compute_sublevel_persistence(ctx):
