@@ -1,6 +1,7 @@
 // capi.hip -- the C ABI of libtdaeeg.so (include/tdaeeg.h): context, argument checks,
 // host-pointer twins (stage -> launch -> copy back) and timing helpers.
 #include "common.h"
+#include "rips_keys_dev.h"
 #include <string.h>
 #include <cmath>
 #include <vector>
@@ -679,8 +680,8 @@ tda_status tda_euler_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, dm); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
-    return launch_euler(ctx, dm, nullptr, n_win, n, 0, 1, 2, symmetrise, thresh, grid, n_grid, max_dim, counts, nullptr,
-                        status, (hipStream_t)stream);
+    return launch_euler(ctx, WinSrc{dm, nullptr, n, 0, 1, 2, symmetrise, 0}, n_win, thresh, grid, n_grid, max_dim, counts,
+                        nullptr, status, (hipStream_t)stream);
 }
 
 tda_status tda_euler_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -689,8 +690,8 @@ tda_status tda_euler_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* 
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
-    return launch_euler(ctx, pc, n_pts, n_win, p_cap, dim, 1, 1, normalise, thresh, grid, n_grid, max_dim, counts, nullptr,
-                        status, (hipStream_t)stream);
+    return launch_euler(ctx, WinSrc{pc, n_pts, p_cap, dim, 1, 1, normalise, 0}, n_win, thresh, grid, n_grid, max_dim, counts,
+                        nullptr, status, (hipStream_t)stream);
 }
 
 tda_status tda_euler_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -699,8 +700,8 @@ tda_status tda_euler_takens_batch_dev(tda_ctx* ctx, const double* win, const int
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status); }
-    return launch_euler(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, thresh, grid, n_grid, max_dim, counts, n_points,
-                        status, (hipStream_t)stream);
+    return launch_euler(ctx, WinSrc{win, tau, n_t, dim, subsample, 0, 1, 0}, n_win, thresh, grid, n_grid, max_dim, counts,
+                        n_points, status, (hipStream_t)stream);
 }
 
 tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
@@ -738,8 +739,8 @@ tda_status tda_generators_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, dm); GEN_CHECK_PTRS(ctx); }
-    return launch_generators(ctx, dm, nullptr, n_win, n, 0, 1, 2, symmetrise, thresh, gen_args(GEN_PASS), nullptr, status,
-                             (hipStream_t)stream);
+    return launch_generators(ctx, WinSrc{dm, nullptr, n, 0, 1, 2, symmetrise, 0}, n_win, thresh, gen_args(GEN_PASS), nullptr,
+                             status, (hipStream_t)stream);
 }
 
 tda_status tda_generators_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
@@ -747,8 +748,8 @@ tda_status tda_generators_cloud_batch_dev(tda_ctx* ctx, const double* pc, const 
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); GEN_CHECK_PTRS(ctx); }
-    return launch_generators(ctx, pc, n_pts, n_win, p_cap, dim, 1, 1, normalise, thresh, gen_args(GEN_PASS), nullptr, status,
-                             (hipStream_t)stream);
+    return launch_generators(ctx, WinSrc{pc, n_pts, p_cap, dim, 1, 1, normalise, 0}, n_win, thresh, gen_args(GEN_PASS), nullptr,
+                             status, (hipStream_t)stream);
 }
 
 tda_status tda_generators_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
@@ -756,8 +757,8 @@ tda_status tda_generators_takens_batch_dev(tda_ctx* ctx, const double* win, cons
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
     if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); GEN_CHECK_PTRS(ctx); }
-    return launch_generators(ctx, win, tau, n_win, n_t, dim, subsample, 0, 1, thresh, gen_args(GEN_PASS), n_points, status,
-                             (hipStream_t)stream);
+    return launch_generators(ctx, WinSrc{win, tau, n_t, dim, subsample, 0, 1, 0}, n_win, thresh, gen_args(GEN_PASS), n_points,
+                             status, (hipStream_t)stream);
 }
 
 tda_status tda_generators_mean_dev(tda_ctx* ctx, const double* part, int n_win, int n, const int* seg_off, int n_seg,
@@ -1529,20 +1530,14 @@ tda_status tda_landscape_batch(tda_ctx* ctx, const double* dgm, const int* cnt, 
     });
 }
 
-// (the limits of launch_euler, checked before anything is staged)
-#define EULER_LIMITS(ctx, n_grid, max_dim)                                                                             \
-    do {                                                                                                               \
-        if ((n_grid) < 1 || (n_grid) > TDA_MAX_GRID) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_grid must be in [1, TDA_MAX_GRID]"); \
-        if ((max_dim) < 1 || (max_dim) > TDA_EC_MAX_DIM)                                                               \
-            TDA_FAIL(ctx, TDA_ERR_INVALID, "max_dim must be in [1, TDA_EC_MAX_DIM]");                                  \
-    } while (0)
-
+// The host twins refuse by the launchers' own rules (win_src_limits of rips_keys_dev.h, ec_check, gn_check) before anything
+// is staged.
 tda_status tda_euler_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
                               const double* grid, int n_grid, int max_dim, int* counts, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (n < 1 || n > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
-    EULER_LIMITS(ctx, n_grid, max_dim);
+    TDA_TRY(win_src_limits(ctx, 2, n, 0, 1, nullptr, nullptr));
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, dm); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
     Stage s(ctx);
@@ -1560,9 +1555,8 @@ tda_status tda_euler_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pt
                                  int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-    if (p_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "p_cap must be >= 1");
-    EULER_LIMITS(ctx, n_grid, max_dim);
+    TDA_TRY(win_src_limits(ctx, 1, p_cap, dim, 1, nullptr, nullptr));
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
     Stage s(ctx);
@@ -1582,9 +1576,8 @@ tda_status tda_euler_takens_batch(tda_ctx* ctx, const double* win, const int* ta
                                   int* n_points, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-    if (n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be >= 1");
-    EULER_LIMITS(ctx, n_grid, max_dim);
+    TDA_TRY(win_src_limits(ctx, 0, n_t, dim, subsample, nullptr, nullptr));
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, status);
     Stage s(ctx);
@@ -1604,7 +1597,7 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
                           const int* status_in, int skip_mask, double* mean)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
-    EULER_LIMITS(ctx, n_grid, max_dim);
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
     if (!seg_off && n_seg != n_win) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every window is a group: n_seg != n_win");
     if (n_seg == 0) return TDA_OK;
     if (n_win) CHECK_PTR(ctx, counts);
@@ -1618,16 +1611,6 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
         return tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, g.off, n_seg, g.status, skip_mask, d_mean, nullptr);
     });
 }
-
-// (the limits of launch_generators, checked before anything is staged)
-#define GEN_LIMITS(ctx)                                                                                                \
-    do {                                                                                                               \
-        if (cyc_cap < 4 || cyc_cap > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "cyc_cap must be in [4, TDA_MAX_POINTS]"); \
-        if (h1_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "h1_cap must be >= 1");                                         \
-        if (part && !cyc) TDA_FAIL(ctx, TDA_ERR_INVALID, "part is summed over the cycles: it needs cyc");              \
-        if (h0_edge && (!h0 || !h0_cnt || h0_cap < 1))                                                                 \
-            TDA_FAIL(ctx, TDA_ERR_INVALID, "h0_edge needs the H0 rows: h0, h0_cnt and h0_cap >= 1");                   \
-    } while (0)
 
 namespace {
 // the device twins of the row inputs and outputs of a host call
@@ -1659,8 +1642,8 @@ tda_status tda_generators_dm_batch(tda_ctx* ctx, const double* dm, int n_win, in
                                    GEN_PARAMS, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (n < 1 || n > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
-    GEN_LIMITS(ctx);
+    TDA_TRY(win_src_limits(ctx, 2, n, 0, 1, nullptr, nullptr));
+    TDA_TRY(gn_check(ctx, gen_args(GEN_PASS)));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, dm); GEN_CHECK_PTRS(ctx);
     Stage s(ctx);
@@ -1677,9 +1660,8 @@ tda_status tda_generators_cloud_batch(tda_ctx* ctx, const double* pc, const int*
                                       int normalise, double thresh, GEN_PARAMS, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-    if (p_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "p_cap must be >= 1");
-    GEN_LIMITS(ctx);
+    TDA_TRY(win_src_limits(ctx, 1, p_cap, dim, 1, nullptr, nullptr));
+    TDA_TRY(gn_check(ctx, gen_args(GEN_PASS)));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); GEN_CHECK_PTRS(ctx);
     Stage s(ctx);
@@ -1697,9 +1679,8 @@ tda_status tda_generators_takens_batch(tda_ctx* ctx, const double* win, const in
                                        int subsample, double thresh, GEN_PARAMS, int* n_points, int* status)
 {
     CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
-    if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-    if (n_t < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_t must be >= 1");
-    GEN_LIMITS(ctx);
+    TDA_TRY(win_src_limits(ctx, 0, n_t, dim, subsample, nullptr, nullptr));
+    TDA_TRY(gn_check(ctx, gen_args(GEN_PASS)));
     if (n_win == 0) return TDA_OK;
     CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); GEN_CHECK_PTRS(ctx);
     Stage s(ctx);

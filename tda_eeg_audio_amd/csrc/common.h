@@ -79,6 +79,10 @@ struct ProbeScope {
 #define TDA_FAIL(ctx, code, msg)                                                    \
     do { (ctx)->err = (msg); return (code); } while (0)
 
+// passes a refusal on
+#define TDA_TRY(call)                                                               \
+    do { const tda_status rc__ = (call); if (rc__ != TDA_OK) return rc__; } while (0)
+
 // ---- wave64 cross-lane helpers (lane index must be wave-uniform) ----
 __device__ __forceinline__ u32 rl32(u32 v, int lane) { return (u32)__builtin_amdgcn_readlane((int)v, lane); }
 __device__ __forceinline__ u64 rl64(u64 v, int lane)
@@ -181,6 +185,30 @@ __device__ __forceinline__ float sortable_f32(u32 s)
     return __uint_as_float(b);
 }
 
+// mean[g][j] = the mean over the windows w of group g (seg_off[g] <= w < seg_off[g + 1]; seg_off == NULL: every window its
+// own group) of val[w][j], j < row_len, without the windows whose status_in has a bit of skip_mask: one thread per (g, j)
+// adds them in window order in ACC; NaN for a group with none left.  (euler.hip: int32 in int64; generators.hip: double)
+template <typename T, typename ACC>
+__global__ void __launch_bounds__(256)
+group_mean_kernel(const T* __restrict__ val, int n_win, int row_len, const int* __restrict__ seg_off, int n_seg,
+                  const int* __restrict__ status_in, int skip_mask, double* __restrict__ mean)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)n_seg * row_len) return;
+    const int g = (int)(idx / row_len), j = (int)(idx - (long long)g * row_len);
+    int w0 = g, w1 = g + 1;
+    if (seg_off) { w0 = seg_off[g]; w1 = seg_off[g + 1]; }
+    w0 = w0 < 0 ? 0 : w0; w1 = w1 > n_win ? n_win : w1;
+    ACC S = 0;
+    int m = 0;
+    for (int w = w0; w < w1; ++w) {
+        if (status_in && (status_in[w] & skip_mask)) continue;
+        S += val[(size_t)w * row_len + j];
+        ++m;
+    }
+    mean[idx] = m ? (double)S / (double)m : __longlong_as_double(0x7ff8000000000000ll);
+}
+
 // launch-side entry points implemented in the .hip files
 size_t rips_total_scratch_bytes();
 #define TDA_RETRY_SLOTS 32
@@ -218,11 +246,13 @@ tda_status launch_connectivity_dist(tda_ctx*, const double* sig, const long long
 // (permutation.hip) S00 / S11 / S01 of n_mat matrices under n_perm relabellings.  Checks the limits of the header itself.
 tda_status launch_perm_sums(tda_ctx*, const double* D, int n_mat, int n, int ld, const unsigned long long* lab, int n_perm,
                             double* work, long long work_doubles, double* out, int* n1, hipStream_t);
-// (euler.hip) simplex counts and Euler characteristic on a grid.  mode 0: Takens windows + tau, mode 1: explicit clouds + n_pts
-// (flag = normalise), mode 2: distance matrices (n_in = n, flag = symmetrise).  Checks the limits of the header itself.
-tda_status launch_euler(tda_ctx*, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample, int mode,
-                        int flag, double thresh, const double* grid, int n_grid, int max_dim, int* counts, int* n_points,
-                        int* status, hipStream_t);
+// (euler.hip) simplex counts and Euler characteristic on a grid, for the windows of a WinSrc (rips_keys_dev.h) as the entry
+// point has them: src, aux, n_in, dim, subsample, mode, flag.  Checks the limits of the header itself: ec_check (the grid),
+// then win_src_limits.
+struct WinSrc;
+tda_status ec_check(tda_ctx*, int n_grid, int max_dim);
+tda_status launch_euler(tda_ctx*, const WinSrc& src, int n_win, double thresh, const double* grid, int n_grid, int max_dim,
+                        int* counts, int* n_points, int* status, hipStream_t);
 tda_status launch_euler_mean(tda_ctx*, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
                              const int* status_in, int skip_mask, double* mean, hipStream_t);
 // (generators.hip) the edges behind the rows of a Rips diagram and a representative cycle per H1 row.  GenArgs: the rows the
@@ -235,9 +265,11 @@ struct GenArgs {
     double* part; short* h0_edge; int* work;
     int part_ld;
 };
-// modes and `flag` as launch_euler.  Checks the limits of the header itself.
-tda_status launch_generators(tda_ctx*, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample, int mode,
-                             int flag, double thresh, const GenArgs& g, int* n_points, int* status, hipStream_t);
+// The windows as launch_euler takes them.  Checks the limits of the header itself: gn_check (the capacities, and which
+// output needs which), then win_src_limits.
+tda_status gn_check(tda_ctx*, const GenArgs& g);
+tda_status launch_generators(tda_ctx*, const WinSrc& src, int n_win, double thresh, const GenArgs& g, int* n_points,
+                             int* status, hipStream_t);
 tda_status launch_generators_mean(tda_ctx*, const double* part, int n_win, int n, const int* seg_off, int n_seg,
                                   const int* status_in, int skip_mask, double* mean, hipStream_t);
 tda_status launch_sosfiltfilt(tda_ctx*, const double*, int, int, const double*, const double*, int, int, double*, double*,

@@ -4,10 +4,9 @@
 //
 // One workgroup of 256 threads (four waves) per window.
 //   Keys.   The float32 keys k[a][b], a > b, are computed once per window into an LDS triangle (4 * n (n - 1) / 2 bytes:
-//           32.5 KB at 128 points, 4.3 KB at 47), by the rules of the Rips kernels for the same input: the symmetrised
-//           distance matrix of rips_dm_window, or the Takens / min-max / sklearn distance of rips_cloud_window and
-//           KeyFromPtsTab, restated here operation for operation (csrc/rips.hip is not touched; tests/test_gpu_euler.py
-//           pins the restatement to the oracle).  Two workgroup barriers, both before the grid loop.
+//           32.5 KB at 128 points, 4.3 KB at 47) by window_keys of csrc/rips_keys_dev.h, the one statement of the key rules
+//           of the Rips kernels: the symmetrised distance matrix, or the Takens / min-max / sklearn distance of a cloud
+//           (tests/test_gpu_euler.py pins them to the oracle).  Its workgroup barriers all come before the grid loop.
 //   Grid.   A wave per grid point: wave w takes the grid points w, w + 4, ...  Nothing inside the grid loop waits for
 //           another wave.  For its grid point t the wave builds, in its own slice of LDS, the lower adjacency masks
 //               L[v] = { u < v : k[v][u] <= (float)thresh and (double)k[v][u] <= t }          one u64 per 64 vertices
@@ -26,22 +25,12 @@
 // most); it is not balanced here (DESIGN.md 3.21 says what that costs).
 //
 // The group means are a second small launch: one thread per (group, row, grid point) walks the windows of its group and
-// adds their int32 values in int64; (double)S / (double)m, NaN for m = 0.
+// adds their int32 values in int64; (double)S / (double)m, NaN for m = 0 (group_mean_kernel of common.h).
 #include "common.h"
+#include "rips_keys_dev.h"
 
 #define EC_NT 256
 #define EC_WAVES (EC_NT / 64)
-
-__device__ __forceinline__ int ec_tri(int a) { return a * (a - 1) / 2; }
-
-// e -> the row a of the triangle that holds it: tri(a) <= e < tri(a) + a.  e < 8128: the float root is within one row.
-__device__ __forceinline__ int ec_edge_row(int e)
-{
-    int a = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)e)) * 0.5f);
-    if (ec_tri(a) > e) --a;
-    if (ec_tri(a + 1) <= e) ++a;
-    return a;
-}
 
 __device__ __forceinline__ u32 ec_wave_sum(u32 v)
 {
@@ -50,135 +39,36 @@ __device__ __forceinline__ u32 ec_wave_sum(u32 v)
     return v;
 }
 
-struct EcLayout {
-    int off_masks, off_pts, off_nrm, off_mm, total;     // bytes; the keys are at 0
-};
-
-static EcLayout ec_layout(int n_max, int nw, int dim)
-{
-    EcLayout L;
-    int o = (n_max * (n_max - 1) / 2 * 4 + 15) & ~15;
-    L.off_masks = o; o += EC_WAVES * n_max * nw * 8;
-    L.off_pts = o;   o += n_max * dim * 8;
-    L.off_nrm = o;   o += n_max * 8;
-    L.off_mm = o;    o += 2 * TDA_MAX_DIM * 8;
-    L.total = o;
-    return L;
-}
-
-// mode 0: Takens windows (src (n_win, n_t), aux = tau);  mode 1: clouds (src (n_win, p_cap, dim), aux = n_pts);
-// mode 2: distance matrices (src (n_win, n, n), aux unused, n_in = n, `flag` = symmetrise; in modes 0 / 1 `flag` = normalise)
+// `off_masks`: the byte offset of the waves' mask slices, behind the LDS of the key pass
 template <int NW>
 __global__ void __launch_bounds__(EC_NT)
-euler_kernel(const double* __restrict__ src, const int* __restrict__ aux, int n_in, int dim, int subsample, int mode,
-             int flag, float thresh, int p_lim, EcLayout L, const double* __restrict__ grid, int n_grid, int max_dim,
+euler_kernel(WinSrc src, float thresh, KeyLayout L, int off_masks, const double* __restrict__ grid, int n_grid, int max_dim,
              int* __restrict__ counts, int* __restrict__ n_points, int* __restrict__ status)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* key = reinterpret_cast<float*>(smem);
+    const float* key = reinterpret_cast<const float*>(smem);
     const int win = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int* out = counts + (size_t)win * (max_dim + 2) * n_grid;
 
-    int n;
-    if (mode == 2) {
-        n = n_in;
-        const double* D = src + (size_t)win * n * n;
-        // utils.py:137-139 then ripser's float32 cast, as rips_dm_window
-        for (int i = tid; i < n * n; i += EC_NT) {
-            const int a = i / n, b = i - a * n;
-            if (b < a) {
-                double v;
-                if (flag) {
-                    v = (D[(size_t)a * n + b] + D[(size_t)b * n + a]) / 2.0;
-                    if (v < 0.0) v = 0.0;
-                } else {
-                    v = D[(size_t)b * n + a];
-                }
-                key[ec_tri(a) + b] = (float)v;
-            }
-        }
-        if (tid == 0) status[win] = 0;
-    } else {
-        // P exactly as rips_cloud_window counts it (in 64 bits: tau is the caller's)
-        long long P64;
-        const double* base;
-        int tau = 1;
-        if (mode == 0) {
-            tau = aux[win];
-            const long long nn = (long long)n_in - (long long)(dim - 1) * tau;
-            P64 = nn > 0 ? (nn + subsample - 1) / subsample : 0;
-            base = src + (size_t)win * n_in;
-        } else {
-            P64 = aux[win];
-            base = src + (size_t)win * n_in * dim;
-        }
-        if (n_points && tid == 0) n_points[win] = P64 > 0x7fffffffll ? 0x7fffffff : (int)P64;
-        const bool too_large = P64 > p_lim || (mode == 0 && tau < 1);
-        if (too_large || P64 < 3) {
-            for (int i = tid; i < (max_dim + 2) * n_grid; i += EC_NT) out[i] = 0;
-            if (tid == 0) status[win] = too_large ? TDA_WIN_TOO_LARGE : TDA_WIN_DEGENERATE;
-            return;
-        }
-        n = (int)P64;
-        double* pts = reinterpret_cast<double*>(smem + L.off_pts);
-        double* nrm = reinterpret_cast<double*>(smem + L.off_nrm);
-        double* mm = reinterpret_cast<double*>(smem + L.off_mm);
-        for (int idx = tid; idx < n * dim; idx += EC_NT) {
-            const int i = idx / dim, k = idx - i * dim;
-            pts[idx] = (mode == 0) ? base[(size_t)i * subsample + (size_t)k * tau] : base[idx];
-        }
-        __syncthreads();
-        if (flag) {
-            // per-column min-max over the whole cloud (range 0 -> 1), utils.py:127-130: one wave per column
-            if (wave < dim) {
-                double mn = INFINITY, mx = -INFINITY;
-                for (int i = lane; i < n; i += 64) {
-                    const double v = pts[i * dim + wave];
-                    mn = v < mn ? v : mn;
-                    mx = v > mx ? v : mx;
-                }
-                mn = wave_min_f64_dpp(mn);
-                mx = wave_max_f64_dpp(mx);
-                if (lane == 0) { double rg = mx - mn; if (rg == 0.0) rg = 1.0; mm[2 * wave] = mn; mm[2 * wave + 1] = rg; }
-            }
-            __syncthreads();
-            for (int idx = tid; idx < n * dim; idx += EC_NT) {
-                const int k = idx % dim;
-                pts[idx] = (pts[idx] - mm[2 * k]) / mm[2 * k + 1];
-            }
-            __syncthreads();
-        }
-        if (tid < n) {
-            double s = 0.0;
-            for (int k = 0; k < dim; ++k) s += pts[tid * dim + k] * pts[tid * dim + k];
-            nrm[tid] = s;
-        }
-        __syncthreads();
-        // sklearn euclidean_distances: -2 x.y + |x|^2 + |y|^2, clamp, sqrt, float32 -- KeyFromPtsTab of csrc/rips.hip
-        const int E = ec_tri(n);
-        for (int e = tid; e < E; e += EC_NT) {
-            const int a = ec_edge_row(e), b = e - ec_tri(a);
-            double dot = pts[a * dim] * pts[b * dim];
-            for (int k = 1; k < dim; ++k) dot = fma(pts[a * dim + k], pts[b * dim + k], dot);
-            double d2 = -2.0 * dot;
-            d2 += nrm[a];
-            d2 += nrm[b];
-            if (!(d2 > 0.0)) d2 = 0.0;
-            key[e] = (float)sqrt_rn(d2);
-        }
-        if (tid == 0) status[win] = 0;
+    const WinExtent X = win_extent(src, win);
+    const int st = win_status(src, X, win, n_points);
+    if (tid == 0) status[win] = st;
+    if (st) {
+        for (int i = tid; i < (max_dim + 2) * n_grid; i += EC_NT) out[i] = 0;
+        return;
     }
-    __syncthreads();
+    const int n = (int)X.P;
+    window_keys<EC_NT>(src, X, n, smem, L);
 
-    u64* Lm = reinterpret_cast<u64*>(smem + L.off_masks) + (size_t)wave * n * NW;      // this wave's masks: L[v][NW]
-    const int E = ec_tri(n);
+    u64* Lm = reinterpret_cast<u64*>(smem + off_masks) + (size_t)wave * n * NW;      // this wave's masks: L[v][NW]
+    const int E = tri2(n);
     u32 prev_f1 = 0, prev_f2 = 0, prev_f3 = 0;
     for (int g = wave; g < n_grid; g += EC_WAVES) {
         const double t = grid[g];
         // a. lower adjacency masks of this grid point; lane v owns vertices v, v + 64
         u32 f1 = 0, f2 = 0, f3 = 0;
         for (int v = lane; v < n; v += 64) {
-            const float* row = key + ec_tri(v);
+            const float* row = key + tri2(v);
             u64 m[NW];
 #pragma unroll
             for (int w = 0; w < NW; ++w) m[w] = 0ull;
@@ -202,7 +92,7 @@ euler_kernel(const double* __restrict__ src, const int* __restrict__ aux, int n_
         // b. triangles and tetrahedra, counted at their edge a > b
         if (max_dim >= 2 && !again) {
             for (int e = lane; e < E; e += 64) {
-                const int a = ec_edge_row(e), b = e - ec_tri(a);
+                const int a = edge_row(e), b = e - tri2(a);
                 u64 C[NW];
 #pragma unroll
                 for (int w = 0; w < NW; ++w) C[w] = Lm[a * NW + w];
@@ -246,69 +136,29 @@ euler_kernel(const double* __restrict__ src, const int* __restrict__ aux, int n_
     }
 }
 
-__global__ void __launch_bounds__(256)
-euler_mean_kernel(const int* __restrict__ counts, int n_win, int rows_grid, const int* __restrict__ seg_off, int n_seg,
-                  const int* __restrict__ status_in, int skip_mask, double* __restrict__ mean)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n_seg * rows_grid) return;
-    const int g = (int)(idx / rows_grid), j = (int)(idx - (long long)g * rows_grid);
-    int w0 = g, w1 = g + 1;                                          // seg_off == NULL: every window its own group
-    if (seg_off) { w0 = seg_off[g]; w1 = seg_off[g + 1]; }
-    w0 = w0 < 0 ? 0 : w0; w1 = w1 > n_win ? n_win : w1;
-    long long S = 0;
-    int m = 0;
-    for (int w = w0; w < w1; ++w) {
-        if (status_in && (status_in[w] & skip_mask)) continue;
-        S += counts[(size_t)w * rows_grid + j];
-        ++m;
-    }
-    mean[idx] = m ? (double)S / (double)m : __longlong_as_double(0x7ff8000000000000ll);
-}
-
-static tda_status ec_check(tda_ctx* ctx, int n_grid, int max_dim)
+tda_status ec_check(tda_ctx* ctx, int n_grid, int max_dim)
 {
     if (n_grid < 1 || n_grid > TDA_MAX_GRID) TDA_FAIL(ctx, TDA_ERR_INVALID, "n_grid must be in [1, TDA_MAX_GRID]");
     if (max_dim < 1 || max_dim > TDA_EC_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "max_dim must be in [1, TDA_EC_MAX_DIM]");
     return TDA_OK;
 }
 
-// mode 2 (distance matrices): n_in = n, flag = symmetrise, aux = NULL.  mode 0 / 1: as launch_rips_cloud, flag = normalise.
-tda_status launch_euler(tda_ctx* ctx, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample,
-                        int mode, int flag, double thresh, const double* grid, int n_grid, int max_dim, int* counts,
-                        int* n_points, int* status, hipStream_t st)
+tda_status launch_euler(tda_ctx* ctx, const WinSrc& src, int n_win, double thresh, const double* grid, int n_grid,
+                        int max_dim, int* counts, int* n_points, int* status, hipStream_t st)
 {
-    const tda_status rc = ec_check(ctx, n_grid, max_dim);
-    if (rc != TDA_OK) return rc;
-    // n_max sizes the LDS layout; p_lim is the largest cloud a window may have (never more than its buffer holds)
-    int n_max, p_lim = TDA_MAX_POINTS;
-    if (mode == 2) {
-        if (n_in < 1 || n_in > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
-        n_max = n_in; dim = 0; subsample = 1;
-    } else {
-        if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-        if (n_in < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, mode == 0 ? "n_t must be >= 1" : "p_cap must be >= 1");
-        if (subsample < 1) subsample = 1;
-        if (mode == 0) {
-            // tau >= 1 in the reference (utils.py:103-104); P is largest at tau = 1
-            const int nn = n_in - (dim - 1);
-            n_max = nn > 0 ? (nn + subsample - 1) / subsample : 0;
-        } else {
-            n_max = n_in;
-            if (n_in < p_lim) p_lim = n_in;
-        }
-        if (n_max > TDA_MAX_POINTS) n_max = TDA_MAX_POINTS;          // larger clouds are flagged per window
-        if (n_max < 3) n_max = 3;
-    }
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
+    WinSrc s = src;
+    int n_max;
+    TDA_TRY(win_src_limits(ctx, s.mode, s.n_in, s.dim, s.subsample, &s, &n_max));
     if (n_win == 0) return TDA_OK;
-    const int nw = n_max > 64 ? 2 : 1;
-    const EcLayout L = ec_layout(n_max, nw, dim);
+    const KeyLayout L = key_layout(n_max, s.dim);
+    const int nw = n_max > 64 ? 2 : 1, lds = L.total + EC_WAVES * n_max * nw * 8;
     if (nw == 1)
-        hipLaunchKernelGGL(euler_kernel<1>, dim3(n_win), dim3(EC_NT), L.total, st, src, aux, n_in, dim, subsample, mode, flag,
-                           (float)thresh, p_lim, L, grid, n_grid, max_dim, counts, n_points, status);
+        hipLaunchKernelGGL(euler_kernel<1>, dim3(n_win), dim3(EC_NT), lds, st, s, (float)thresh, L, L.total, grid, n_grid, max_dim,
+                           counts, n_points, status);
     else
-        hipLaunchKernelGGL(euler_kernel<2>, dim3(n_win), dim3(EC_NT), L.total, st, src, aux, n_in, dim, subsample, mode, flag,
-                           (float)thresh, p_lim, L, grid, n_grid, max_dim, counts, n_points, status);
+        hipLaunchKernelGGL(euler_kernel<2>, dim3(n_win), dim3(EC_NT), lds, st, s, (float)thresh, L, L.total, grid, n_grid, max_dim,
+                           counts, n_points, status);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
@@ -316,14 +166,13 @@ tda_status launch_euler(tda_ctx* ctx, const double* src, const int* aux, int n_w
 tda_status launch_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
                              int n_seg, const int* status_in, int skip_mask, double* mean, hipStream_t st)
 {
-    const tda_status rc = ec_check(ctx, n_grid, max_dim);
-    if (rc != TDA_OK) return rc;
+    TDA_TRY(ec_check(ctx, n_grid, max_dim));
     if (!seg_off && n_seg != n_win) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every window is a group: n_seg != n_win");
     if (n_seg == 0) return TDA_OK;
     const int rows_grid = (max_dim + 2) * n_grid;
     const long long total = (long long)n_seg * rows_grid;
-    hipLaunchKernelGGL(euler_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, counts, n_win, rows_grid,
-                       seg_off, n_seg, status_in, skip_mask, mean);
+    hipLaunchKernelGGL((group_mean_kernel<int, long long>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, counts,
+                       n_win, rows_grid, seg_off, n_seg, status_in, skip_mask, mean);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }

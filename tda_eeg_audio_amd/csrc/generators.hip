@@ -1,13 +1,13 @@
 // generators.hip -- the simplices behind the rows of a Rips diagram and a representative cycle of every H1 row
 // (include/tdaeeg.h, "Generators and representative cycles").  Integers: the output is the bytes of
-// tests/generators_ref.py or it is wrong.  csrc/rips.hip is not touched: the edges are recovered after the fact from the
-// keys and the rows, by a local rule.
+// tests/generators_ref.py or it is wrong.  The Rips kernels are not touched: the edges are recovered after the fact from
+// the keys and the rows, by a local rule.
 //
 // One workgroup of 256 threads (four waves) per window.
-//   Keys.   The float32 keys k[a][b], a > b, once per window into an LDS triangle (32.5 KB at 128 points), by the rules of
-//           the Rips kernels for the same input, restated here operation for operation as csrc/euler.hip restates them
-//           (tests/test_gpu_generators.py pins the restatement to the oracle).  The edges are ordered by (key, flat index
-//           tri(a) + b); G_e is the graph of the edges with k <= (float)thresh that precede e.
+//   Keys.   The float32 keys k[a][b], a > b, once per window into an LDS triangle (32.5 KB at 128 points) by window_keys of
+//           csrc/rips_keys_dev.h, the one statement of the key rules of the Rips kernels (tests/test_gpu_generators.py
+//           pins them to the oracle).  The edges are ordered by (key, flat index tri2(a) + b); G_e is the graph of the
+//           edges with k <= (float)thresh that precede e.
 //   Items.  A work item is a maximal run of H1 rows with equal birth, or of H0 rows with equal death.  Every wave walks the
 //           rows (a loop of known length over values every lane reads alike) and takes the runs w, w + 4, ...  Nothing in
 //           the row loop waits for another wave.
@@ -25,44 +25,18 @@
 //   it, and every row of a skipped, degenerate or refused window, get the fill values.
 //   Part.   After one workgroup barrier thread v adds d - b over the unflagged rows with finite d whose cycle holds v, in
 //           row order.
-// The group means are a second small launch: one thread per (group, vertex) adds the windows of its group in order.
+// The group means are a second small launch: one thread per (group, vertex) adds the windows of its group in order
+// (group_mean_kernel of common.h).
 #include "common.h"
+#include "rips_keys_dev.h"
 
 #define GN_NT 256
 #define GN_WAVES (GN_NT / 64)
-
-__device__ __forceinline__ int gn_tri(int a) { return a * (a - 1) / 2; }
-
-// e -> the row a of the triangle that holds it: tri(a) <= e < tri(a) + a.  e < 8128: the float root is within one row.
-__device__ __forceinline__ int gn_edge_row(int e)
-{
-    int a = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)e)) * 0.5f);
-    if (gn_tri(a) > e) --a;
-    if (gn_tri(a + 1) <= e) ++a;
-    return a;
-}
-
-__device__ __forceinline__ int gn_flat(int x, int y) { return x > y ? gn_tri(x) + y : gn_tri(y) + x; }
 
 // is the edge of key k and flat index f in G_e, e of key ke and flat index fe?  (a NaN key is no edge)
 __device__ __forceinline__ bool gn_before(float k, int f, float ke, int fe, float thresh)
 {
     return k <= thresh && (k < ke || (k == ke && f < fe));
-}
-
-struct GnLayout {
-    int off_pts, off_nrm, off_mm, total;                // bytes; the keys are at 0
-};
-
-static GnLayout gn_layout(int n_max, int dim)
-{
-    GnLayout L;
-    int o = (n_max * (n_max - 1) / 2 * 4 + 15) & ~15;
-    L.off_pts = o; o += n_max * dim * 8;
-    L.off_nrm = o; o += n_max * 8;
-    L.off_mm = o;  o += 2 * TDA_MAX_DIM * 8;
-    L.total = o;
-    return L;
 }
 
 // what a wave knows about its window
@@ -93,7 +67,7 @@ __device__ __forceinline__ bool gn_cn(const GnWin& W, int a, int b, float ke, in
         const int u = W.lane + 64 * w;
         bool in = false;
         if (u < W.n && u != a && u != b) {
-            const int fa = gn_flat(a, u), fb = gn_flat(b, u);
+            const int fa = pair_index(a, u), fb = pair_index(b, u);
             in = gn_before(W.key[fa], fa, ke, fe, W.thresh) && gn_before(W.key[fb], fb, ke, fe, W.thresh);
         }
         any |= __ballot(in) != 0ull;
@@ -116,7 +90,7 @@ __device__ __forceinline__ int gn_search(const GnWin& W, int a, int b, float ke,
         if (v < n) {
             for (int u = 0; u < n; ++u) {
                 if (u == v) continue;
-                const int f = gn_flat(v, u);
+                const int f = pair_index(v, u);
                 const bool in = gn_before(W.key[f], f, ke, fe, W.thresh);
                 if (NW == 1) adj[w][0] |= (u64)in << u;
                 else if (u < 64) adj[w][0] |= (u64)in << u;
@@ -178,15 +152,12 @@ __device__ __forceinline__ void gn_store_cycle(short* row, int cyc_cap, int lane
     if (lane + 64 < cyc_cap) row[lane + 64] = (short)(lane + 64 < len ? w1 : -1);
 }
 
-// mode 0: Takens windows (src (n_win, n_t), aux = tau);  mode 1: clouds (src (n_win, p_cap, dim), aux = n_pts);
-// mode 2: distance matrices (src (n_win, n, n), aux unused, n_in = n, `flag` = symmetrise; in modes 0 / 1 `flag` = normalise)
 template <int NW>
 __global__ void __launch_bounds__(GN_NT)
-generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, int n_in, int dim, int subsample, int mode,
-                  int flag, float thresh, int p_lim, GnLayout L, GenArgs io, int* __restrict__ n_points, int* __restrict__ status)
+generators_kernel(WinSrc src, float thresh, KeyLayout L, GenArgs io, int* __restrict__ n_points, int* __restrict__ status)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* key = reinterpret_cast<float*>(smem);
+    const float* key = reinterpret_cast<const float*>(smem);
     const int win = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h1_cap = io.h1_cap, h0_cap = io.h0_cap, cyc_cap = io.cyc_cap;
@@ -197,29 +168,8 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
     short* h0e = io.h0_edge ? io.h0_edge + (size_t)win * h0_cap * 2 : nullptr;
     double* part = io.part ? io.part + (size_t)win * io.part_ld : nullptr;
 
-    // the status word and the number of vertices, as euler_kernel has them
-    int n, st = 0;
-    long long P64 = n_in;
-    int tau = 1;
-    const double* base = src;
-    if (mode == 2) {
-        n = n_in;
-    } else {
-        if (mode == 0) {
-            tau = aux[win];
-            const long long nn = (long long)n_in - (long long)(dim - 1) * tau;
-            P64 = nn > 0 ? (nn + subsample - 1) / subsample : 0;
-            base = src + (size_t)win * n_in;
-        } else {
-            P64 = aux[win];
-            base = src + (size_t)win * n_in * dim;
-        }
-        if (n_points && tid == 0) n_points[win] = P64 > 0x7fffffffll ? 0x7fffffff : (int)P64;
-        const bool too_large = P64 > p_lim || (mode == 0 && tau < 1);
-        if (too_large) st = TDA_WIN_TOO_LARGE;
-        else if (P64 < 3) st = TDA_WIN_DEGENERATE;
-        n = st ? 0 : (int)P64;
-    }
+    const WinExtent X = win_extent(src, win);
+    const int st = win_status(src, X, win, n_points), n = st ? 0 : (int)X.P;
     if (tid == 0) status[win] = st;
     const bool skip = st != 0 || (io.rips_status && (io.rips_status[win] & io.skip_mask));
     int R1 = 0, R0 = 0;
@@ -240,74 +190,10 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
         return;
     }
 
-    if (mode == 2) {
-        const double* D = src + (size_t)win * n * n;
-        // utils.py:137-139 then ripser's float32 cast, as rips_dm_window
-        for (int i = tid; i < n * n; i += GN_NT) {
-            const int a = i / n, b = i - a * n;
-            if (b < a) {
-                double v;
-                if (flag) {
-                    v = (D[(size_t)a * n + b] + D[(size_t)b * n + a]) / 2.0;
-                    if (v < 0.0) v = 0.0;
-                } else {
-                    v = D[(size_t)b * n + a];
-                }
-                key[gn_tri(a) + b] = (float)v;
-            }
-        }
-    } else {
-        double* pts = reinterpret_cast<double*>(smem + L.off_pts);
-        double* nrm = reinterpret_cast<double*>(smem + L.off_nrm);
-        double* mm = reinterpret_cast<double*>(smem + L.off_mm);
-        for (int idx = tid; idx < n * dim; idx += GN_NT) {
-            const int i = idx / dim, k = idx - i * dim;
-            pts[idx] = (mode == 0) ? base[(size_t)i * subsample + (size_t)k * tau] : base[idx];
-        }
-        __syncthreads();
-        if (flag) {
-            // per-column min-max over the whole cloud (range 0 -> 1), utils.py:127-130: one wave per column
-            if (wave < dim) {
-                double mn = INFINITY, mx = -INFINITY;
-                for (int i = lane; i < n; i += 64) {
-                    const double v = pts[i * dim + wave];
-                    mn = v < mn ? v : mn;
-                    mx = v > mx ? v : mx;
-                }
-                mn = wave_min_f64_dpp(mn);
-                mx = wave_max_f64_dpp(mx);
-                if (lane == 0) { double rg = mx - mn; if (rg == 0.0) rg = 1.0; mm[2 * wave] = mn; mm[2 * wave + 1] = rg; }
-            }
-            __syncthreads();
-            for (int idx = tid; idx < n * dim; idx += GN_NT) {
-                const int k = idx % dim;
-                pts[idx] = (pts[idx] - mm[2 * k]) / mm[2 * k + 1];
-            }
-            __syncthreads();
-        }
-        if (tid < n) {
-            double s = 0.0;
-            for (int k = 0; k < dim; ++k) s += pts[tid * dim + k] * pts[tid * dim + k];
-            nrm[tid] = s;
-        }
-        __syncthreads();
-        // sklearn euclidean_distances: -2 x.y + |x|^2 + |y|^2, clamp, sqrt, float32 -- KeyFromPtsTab of csrc/rips.hip
-        const int E = gn_tri(n);
-        for (int e = tid; e < E; e += GN_NT) {
-            const int a = gn_edge_row(e), b = e - gn_tri(a);
-            double dot = pts[a * dim] * pts[b * dim];
-            for (int k = 1; k < dim; ++k) dot = fma(pts[a * dim + k], pts[b * dim + k], dot);
-            double d2 = -2.0 * dot;
-            d2 += nrm[a];
-            d2 += nrm[b];
-            if (!(d2 > 0.0)) d2 = 0.0;
-            key[e] = (float)sqrt_rn(d2);
-        }
-    }
-    __syncthreads();
+    window_keys<GN_NT>(src, X, n, smem, L);
 
     GnWin W;
-    W.key = key; W.n = n; W.E = gn_tri(n); W.lane = lane; W.thresh = thresh;
+    W.key = key; W.n = n; W.E = tri2(n); W.lane = lane; W.thresh = thresh;
     const double* h1 = io.h1 + (size_t)win * h1_cap * 2;
     int searches = 0, levels = 0, run = 0;
     // the last death looked up by this wave: rows of equal death share one lookup
@@ -325,7 +211,7 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
                 while (m) {
                     const int e = cb + __builtin_ctzll(m);
                     m &= m - 1;
-                    const int a = gn_edge_row(e), b = e - gn_tri(a);
+                    const int a = edge_row(e), b = e - tri2(a);
                     const float ke = key[e];
                     if (gn_cn<NW>(W, a, b, ke, e)) continue;
                     int walk[NW];
@@ -358,7 +244,7 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
                             while (m && last_cnt < 2) {
                                 const int e = cb + __builtin_ctzll(m);
                                 m &= m - 1;
-                                const int a = gn_edge_row(e), b = e - gn_tri(a);
+                                const int a = edge_row(e), b = e - tri2(a);
                                 if (gn_cn<NW>(W, a, b, key[e], e)) { if (last_cnt == 0) last_e = e; ++last_cnt; }
                             }
                         }
@@ -372,9 +258,9 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
                     if (lane == 0) { gen[r * 4] = gen[r * 4 + 1] = gen[r * 4 + 2] = gen[r * 4 + 3] = -1; rflag[r] = fl; clen[r] = 0; }
                     gn_store_cycle(cyc ? cyc + (size_t)r * cyc_cap : nullptr, cyc_cap, lane, 0, -1, -1);
                 } else if (lane == 0) {
-                    const int da = de >= 0 ? gn_edge_row(de) : -1;
+                    const int da = de >= 0 ? edge_row(de) : -1;
                     gen[r * 4 + 2] = (short)da;
-                    gen[r * 4 + 3] = (short)(de >= 0 ? de - gn_tri(da) : -1);
+                    gen[r * 4 + 3] = (short)(de >= 0 ? de - tri2(da) : -1);
                     rflag[r] |= fl;                                  // (this lane wrote the truncation bit above)
                 }
             }
@@ -396,7 +282,7 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
                     while (m && r0 + found < r1) {
                         const int e = cb + __builtin_ctzll(m);
                         m &= m - 1;
-                        const int a = gn_edge_row(e), b = e - gn_tri(a);
+                        const int a = edge_row(e), b = e - tri2(a);
                         const float ke = key[e];
                         if (gn_cn<NW>(W, a, b, ke, e)) continue;
                         int walk[NW];
@@ -437,27 +323,7 @@ generators_kernel(const double* __restrict__ src, const int* __restrict__ aux, i
     }
 }
 
-__global__ void __launch_bounds__(256)
-generators_mean_kernel(const double* __restrict__ part, int n_win, int n, const int* __restrict__ seg_off, int n_seg,
-                       const int* __restrict__ status_in, int skip_mask, double* __restrict__ mean)
-{
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)n_seg * n) return;
-    const int g = (int)(idx / n), v = (int)(idx - (long long)g * n);
-    int w0 = g, w1 = g + 1;                                          // seg_off == NULL: every window its own group
-    if (seg_off) { w0 = seg_off[g]; w1 = seg_off[g + 1]; }
-    w0 = w0 < 0 ? 0 : w0; w1 = w1 > n_win ? n_win : w1;
-    double S = 0.0;
-    int m = 0;
-    for (int w = w0; w < w1; ++w) {
-        if (status_in && (status_in[w] & skip_mask)) continue;
-        S += part[(size_t)w * n + v];
-        ++m;
-    }
-    mean[idx] = m ? S / (double)m : __longlong_as_double(0x7ff8000000000000ll);
-}
-
-static tda_status gn_check(tda_ctx* ctx, const GenArgs& g)
+tda_status gn_check(tda_ctx* ctx, const GenArgs& g)
 {
     if (g.cyc_cap < 4 || g.cyc_cap > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "cyc_cap must be in [4, TDA_MAX_POINTS]");
     if (g.h1_cap < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, "h1_cap must be >= 1");
@@ -467,44 +333,21 @@ static tda_status gn_check(tda_ctx* ctx, const GenArgs& g)
     return TDA_OK;
 }
 
-// mode 2 (distance matrices): n_in = n, flag = symmetrise, aux = NULL.  mode 0 / 1: as launch_rips_cloud, flag = normalise.
-tda_status launch_generators(tda_ctx* ctx, const double* src, const int* aux, int n_win, int n_in, int dim, int subsample,
-                             int mode, int flag, double thresh, const GenArgs& g, int* n_points, int* status, hipStream_t st)
+tda_status launch_generators(tda_ctx* ctx, const WinSrc& src, int n_win, double thresh, const GenArgs& g, int* n_points,
+                             int* status, hipStream_t st)
 {
-    const tda_status rc = gn_check(ctx, g);
-    if (rc != TDA_OK) return rc;
-    // n_max sizes the LDS layout; p_lim is the largest cloud a window may have (never more than its buffer holds)
-    int n_max, p_lim = TDA_MAX_POINTS, part_ld;
-    if (mode == 2) {
-        if (n_in < 1 || n_in > TDA_MAX_POINTS) TDA_FAIL(ctx, TDA_ERR_INVALID, "n must be in [1, TDA_MAX_POINTS]");
-        n_max = n_in; dim = 0; subsample = 1; part_ld = n_in;
-    } else {
-        if (dim < 1 || dim > TDA_MAX_DIM) TDA_FAIL(ctx, TDA_ERR_INVALID, "dim must be in [1, TDA_MAX_DIM]");
-        if (n_in < 1) TDA_FAIL(ctx, TDA_ERR_INVALID, mode == 0 ? "n_t must be >= 1" : "p_cap must be >= 1");
-        if (subsample < 1) subsample = 1;
-        if (mode == 0) {
-            // tau >= 1 in the reference (utils.py:103-104); P is largest at tau = 1
-            const int nn = n_in - (dim - 1);
-            n_max = nn > 0 ? (nn + subsample - 1) / subsample : 0;
-            part_ld = TDA_MAX_POINTS;
-        } else {
-            n_max = n_in;
-            if (n_in < p_lim) p_lim = n_in;
-            part_ld = n_in;
-        }
-        if (n_max > TDA_MAX_POINTS) n_max = TDA_MAX_POINTS;          // larger clouds are flagged per window
-        if (n_max < 3) n_max = 3;
-    }
+    TDA_TRY(gn_check(ctx, g));
+    WinSrc s = src;
+    int n_max;
+    TDA_TRY(win_src_limits(ctx, s.mode, s.n_in, s.dim, s.subsample, &s, &n_max));
     if (n_win == 0) return TDA_OK;
     GenArgs io = g;
-    io.part_ld = part_ld;
-    const GnLayout L = gn_layout(n_max, dim);
+    io.part_ld = s.mode == 0 ? TDA_MAX_POINTS : s.n_in;              // the columns of part: whatever tau gives, p_cap, n
+    const KeyLayout L = key_layout(n_max, s.dim);
     if (n_max <= 64)
-        hipLaunchKernelGGL(generators_kernel<1>, dim3(n_win), dim3(GN_NT), L.total, st, src, aux, n_in, dim, subsample, mode,
-                           flag, (float)thresh, p_lim, L, io, n_points, status);
+        hipLaunchKernelGGL(generators_kernel<1>, dim3(n_win), dim3(GN_NT), L.total, st, s, (float)thresh, L, io, n_points, status);
     else
-        hipLaunchKernelGGL(generators_kernel<2>, dim3(n_win), dim3(GN_NT), L.total, st, src, aux, n_in, dim, subsample, mode,
-                           flag, (float)thresh, p_lim, L, io, n_points, status);
+        hipLaunchKernelGGL(generators_kernel<2>, dim3(n_win), dim3(GN_NT), L.total, st, s, (float)thresh, L, io, n_points, status);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;
 }
@@ -516,7 +359,7 @@ tda_status launch_generators_mean(tda_ctx* ctx, const double* part, int n_win, i
     if (!seg_off && n_seg != n_win) TDA_FAIL(ctx, TDA_ERR_INVALID, "without seg_off every window is a group: n_seg != n_win");
     if (n_seg == 0) return TDA_OK;
     const long long total = (long long)n_seg * n;
-    hipLaunchKernelGGL(generators_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, n_win, n,
+    hipLaunchKernelGGL((group_mean_kernel<double, double>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, n_win, n,
                        seg_off, n_seg, status_in, skip_mask, mean);
     TDA_HIP(ctx, hipGetLastError());
     return TDA_OK;

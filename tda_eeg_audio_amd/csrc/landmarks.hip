@@ -11,6 +11,7 @@
 // The pairs are double-buffered on the parity of the iteration: a wave writes the pairs of iteration t + 2 only after
 // the barrier of iteration t + 1, which every wave reaches after it has read those of iteration t.  No atomics.
 #include "common.h"
+#include "rips_keys_dev.h"
 #include <climits>
 
 #define LM_NT 256
@@ -34,21 +35,13 @@ landmarks_kernel(const double* __restrict__ src, const int* __restrict__ tau_or_
 
     const int win = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    // P exactly as rips_cloud_window counts it (in 64 bits: tau is the caller's)
-    long long P64;
-    const double* base;
-    int tau = 1;
-    if (mode == 0) {
-        tau = tau_or_npts[win];
-        const long long nn = (long long)n_t_or_pcap - (long long)(DIM - 1) * tau;
-        P64 = nn > 0 ? (nn + subsample - 1) / subsample : 0;
-        base = src + (size_t)win * n_t_or_pcap;
-    } else {
-        P64 = tau_or_npts[win];
-        base = src + (size_t)win * n_t_or_pcap * DIM;
-    }
+    // the points of the window as every Rips consumer counts them (csrc/rips_keys_dev.h); the limit and what a refused
+    // window gets are this kernel's own
+    const WinSrc S{src, tau_or_npts, n_t_or_pcap, DIM, subsample, mode, normalise, 0};
+    const WinExtent X = win_extent(S, win);
+    const long long P64 = X.P;
     const int p_lim = (mode == 1 && n_t_or_pcap < TDA_LM_MAX_POINTS) ? n_t_or_pcap : TDA_LM_MAX_POINTS;
-    if ((mode == 0 && tau < 1) || P64 > p_lim) {
+    if ((mode == 0 && X.tau < 1) || P64 > p_lim) {
         if (tid == 0) {
             n_lm[win] = TDA_MAX_POINTS + 1;            // the cloud Rips flags this count as TDA_WIN_TOO_LARGE itself
             n_full[win] = P64 > INT_MAX ? INT_MAX : (int)P64;
@@ -68,7 +61,7 @@ landmarks_kernel(const double* __restrict__ src, const int* __restrict__ tau_or_
         const int i = tid + j * LM_NT;
 #pragma unroll
         for (int k = 0; k < DIM; ++k)
-            x[j][k] = i < P ? (mode == 0 ? base[(size_t)i * subsample + (size_t)k * tau] : base[(size_t)i * DIM + k]) : 0.0;
+            x[j][k] = i < P ? (mode == 0 ? X.base[(size_t)i * subsample + (size_t)k * X.tau] : X.base[(size_t)i * DIM + k]) : 0.0;
     }
     if (normalise && P > 0) {
         // per-column min-max over the whole cloud (range 0 -> 1), utils.py:127-130

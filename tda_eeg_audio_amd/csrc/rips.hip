@@ -58,6 +58,7 @@
 #include "common.h"
 #include "corr_dist_dev.h"
 #include "rips_ladder.h"
+#include "rips_keys_dev.h"
 #include <stdlib.h>
 
 static_assert(TDA_RETRY_AUTO == rips_ladder::AUTO && TDA_RETRY_FIRST_PASS == rips_ladder::FIRST_PASS &&
@@ -202,21 +203,6 @@ __device__ __forceinline__ double wave_max_f64(double v)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
     return v;
-}
-
-__device__ __forceinline__ int tri2(int v) { return (v * (v - 1)) >> 1; }
-// index of unordered pair {x,y}, x != y
-__device__ __forceinline__ int pair_index(int x, int y) { return x > y ? tri2(x) + y : tri2(y) + x; }
-
-// flat edge index e = tri2(a)+b (a > b)  ->  a
-__device__ __forceinline__ int edge_row(int e)
-{
-    // e < 2^13: 1 + 8e is exact in float and the hardware's v_sqrt_f32 (one ulp, no denormal / class fix-ups: the
-    // correctly rounded sqrtf of -fno-fast-math costs 18 instructions more, tools/probes/valu_rate.hip) puts the estimate
-    // within 1e-4 of (1 + sqrt(1 + 8e)) / 2, i.e. off by at most one row -- one branch-free correction
-    const int a = (int)((1.0f + __builtin_amdgcn_sqrtf(1.0f + 8.0f * (float)e)) * 0.5f);
-    const int t = tri2(a);
-    return a + (t + a <= e ? 1 : 0) - (t > e ? 1 : 0);
 }
 
 // (a << 8 | b) of every flat edge index, as a constant table in device memory: 17 KB that every CU keeps in its vector
@@ -2071,14 +2057,7 @@ __device__ __forceinline__ void rips_dm_window(unsigned char* smem, const int wi
     u32 kmin_thread = 0xffffffffu;
     for (int e = tid; e < E; e += NT) {
         const int a = edge_row(e), b = e - tri2(a);
-        double v;
-        if (symmetrise) {
-            v = (D[(size_t)a * n + b] + D[(size_t)b * n + a]) / 2.0;
-            if (v < 0.0) v = 0.0;
-        } else {
-            v = D[(size_t)b * n + a];
-        }
-        const u32 sk = f32_sortable((float)v);
+        const u32 sk = f32_sortable(dm_key(D, n, a, b, symmetrise));
         key32[e] = sk;
         kmin_thread = sk < kmin_thread ? sk : kmin_thread;
         atomicMax(&vmax[a], sk);
@@ -2127,37 +2106,6 @@ struct KeyFromPts {
         d2 += nb;
         if (!(d2 > 0.0)) d2 = 0.0;
         return (float)sqrt(d2);
-    }
-};
-
-// The same with |x|^2 of every point from a table (the key pass: every point takes part in P - 1 edges; the table holds
-// exactly the value the expression above computes, so the keys are bit-identical)
-struct KeyFromPtsTab {
-    const double* pts; const double* nrm; int dim;
-    __device__ __forceinline__ static double norm2(const double* p, int dim)
-    {
-        if (dim == 3) return (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
-        double n = 0.0;
-        for (int k = 0; k < dim; ++k) n += p[k] * p[k];
-        return n;
-    }
-    __device__ __forceinline__ float operator()(int, int a, int b) const
-    {
-        double dot = 0.0;
-        if (dim == 3) {
-            const double* pa = pts + 3 * a;
-            const double* pb = pts + 3 * b;
-            dot = fma(pa[2], pb[2], fma(pa[1], pb[1], pa[0] * pb[0]));
-        } else
-        for (int k = 0; k < dim; ++k) {
-            const double xa = pts[a * dim + k], xb = pts[b * dim + k];
-            dot = (k == 0) ? xa * xb : fma(xa, xb, dot);
-        }
-        double d2 = -2.0 * dot;
-        d2 += nrm[a];
-        d2 += nrm[b];
-        if (!(d2 > 0.0)) d2 = 0.0;
-        return (float)sqrt_rn(d2);
     }
 };
 

@@ -3,8 +3,8 @@ GPU tests of the generators and representative cycles (csrc/generators.hip; incl
 representative cycles"): every output as bytes against the definition in tests/generators_ref.py ((b), `generators`), fed
 with the keys of the oracle and the rows the Rips kernels themselves wrote.  The shapes are the smallest that can break
 the kernel: the mask word boundary (63, 64, 65, 127, 128), the one- and two-word templates, fewer and more runs than waves,
-tied births and deaths, every capacity below its demand, the three input forms with their status words, batches, means and
-the refusals.
+tied births and deaths, every capacity below its demand, the three input forms with their status words (clouds of dimension
+1 to 4, three Takens embeddings: the key pass is the one the Euler kernels share), batches, means and the refusals.
 """
 import ctypes as C
 
@@ -237,7 +237,7 @@ def _ref_clouds(pc, n_pts, h0, c0, h1, c1, normalise, cyc_cap=128):
     return {name: np.stack([o[name] for o in out]) for name in NAMES}, st
 
 
-@pytest.mark.parametrize("dim,normalise", [(2, True), (3, False)])
+@pytest.mark.parametrize("dim,normalise", [(2, True), (3, False), (1, True), (4, True)])
 def test_clouds(ctx, dim, normalise):
     from tda_eeg_audio_amd import engine
     pc, n_pts = _clouds(dim, 20 + dim)
@@ -248,8 +248,11 @@ def test_clouds(ctx, dim, normalise):
     ref, st = _ref_clouds(pc, n_pts, h0, c0, h1, c1, normalise)
     _same(out, ref)
     assert out["status"].tolist() == st == [4, 0, 0, 0, 0, 16, 0]
-    assert out["part"].shape == (7, 129) and out["part"][4].max() > 0 and not out["part"][4, 128:].any()
-    assert (out["h1_gen"][[0, 5]] == -1).all() and out["cyc"][4].max() >= 64
+    assert out["part"].shape == (7, 129) and not out["part"][4, 128:].any() and (out["h1_gen"][[0, 5]] == -1).all()
+    if dim > 1:
+        assert out["part"][4].max() > 0 and out["cyc"][4].max() >= 64
+    else:                                                         # points of a line: a path of 127 forest edges
+        assert out["h0_edge"][4].max() == 127 and (out["h0_edge"][4, :127] >= 0).all()
     # the host twin
     host = engine.generators_cloud_batch(pc, h0, c0, h1, c1, n_pts, normalise, ctx=ctx)
     _same(host, ref)
@@ -286,6 +289,15 @@ def test_takens_windows(ctx):
     npts = npts_t.cpu().numpy()
     assert npts[:2].tolist() == [23, 123] and npts[3:6].tolist() == [0, 1, 85]
     assert c1[1] > 4 and not out["h1_flag"][1].any() and out["part"][1].max() > 0
+    # other embeddings: dim 4 with subsample 3 (P = 83) and dim 2 with subsample 2 (P = 122)
+    for dim, sub, tau in ((4, 3, 1), (2, 2, 7)):
+        t = _dev(np.full(2, tau, np.int32))
+        d2 = engine.takens_rips_dev(sig_t[:2].contiguous(), t, dim=dim, subsample=sub, h1_cap=512, ctx=ctx)
+        o2 = engine.generators_takens_dev(sig_t[:2].contiguous(), t, d2, dim=dim, subsample=sub, ctx=ctx).to_host()
+        r0, q0, r1, q1 = _rows(d2)
+        ref2 = [gr.generators(er.keys_takens(sig[w], tau, dim, sub), r0[w], q0[w], r1[w], q1[w], 2.0, 128, 128) for w in range(2)]
+        _same(o2, {name: np.stack([o[name] for o in ref2]) for name in NAMES}, where=(dim, sub, tau))
+        assert not o2["status"].any() and q1.min() > 0
     # the host twin
     host = engine.generators_takens_batch(sig, taus, h0, c0, h1, c1, ctx=ctx)
     _same(host, out)

@@ -9,8 +9,9 @@ ONE run:
 Beside each Euler launch the inner steps it ran, read off its own output: sum over windows and grid points of f_2 (one step
 of the tetrahedron loop per triangle, max_dim 3) or of f_1 (one mask intersection per present edge, max_dim 2), and the
 steps per second.  The rate is nominal: a grid point whose edge count repeats that of its wave's previous grid point keeps
-that one's counts and is counted here although it was not run again.  Writes profiles/euler_bench.json.
-    python tools/euler_bench.py [n_rec] [reps]"""
+that one's counts and is counted here although it was not run again.  Writes profiles/euler_bench.json, or `out`
+(an A/B run keeps one file per library: TDA_LIB=libtdaeeg_<variant>.so selects a variant build).
+    python tools/euler_bench.py [n_rec] [reps] [out]"""
 import json
 import os
 import sys
@@ -61,6 +62,7 @@ def euler_summary(ts, out_t, st_t, K):
 def main():
     n_rec = int(sys.argv[1]) if len(sys.argv) > 1 else 1416
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "euler_bench.json")
     ctx = _lib.get_ctx(0)
     dev = torch.device("cuda", 0)
     nb = len(synth.BANDS)
@@ -100,8 +102,8 @@ def main():
     res["audio_rips"] = summary(timed(lambda: engine.takens_rips_dev(A, tau_w, out=da, ctx=ctx), reps),
                                 windows_flagged=int((da.status & ~4 != 0).sum().item()))
     res["audio_points_mean"] = float(da.n_points.double().mean().item())
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "euler_bench.json"), "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps({k: (v["ms_median"], v.get("gsteps_per_s"), v["spread"]) for k, v in res.items()

@@ -8,8 +8,9 @@ the inputs of bench.py), HIP events around whole launches, medians of `reps` lau
   *_gen_edges_only                 without h0_edge, cyc and part: birth and death edges, lengths and flags
   eeg_mean                         engine.generators_mean_dev over the 7,080 (recording, band) groups
 Beside each launch the work it did, from the kernel's own counters (work, a separate launch that is not timed): searches and
-search levels per window, and the flagged rows.  Writes profiles/generators_bench.json.
-    python tools/generators_bench.py [n_rec] [reps]"""
+search levels per window, and the flagged rows.  Writes profiles/generators_bench.json, or `out`
+(an A/B run keeps one file per library: TDA_LIB=libtdaeeg_<variant>.so selects a variant build).
+    python tools/generators_bench.py [n_rec] [reps] [out]"""
 import json
 import os
 import sys
@@ -74,6 +75,7 @@ def variants(run, dg, n, n_part, dev, reps, res, name):
 def main():
     n_rec = int(sys.argv[1]) if len(sys.argv) > 1 else 1416
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "generators_bench.json")
     ctx = _lib.get_ctx(0)
     dev = torch.device("cuda", 0)
     nb = len(synth.BANDS)
@@ -107,8 +109,8 @@ def main():
     variants(lambda out, part, h0e, work: engine.generators_takens_dev(A, tau_w, da, cyc_cap=CYC_CAP, part=part, h0_edge=h0e,
                                                                        work=work, out=out, ctx=ctx),
              da, n, _lib.MAX_POINTS, dev, reps, res, "audio")
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "generators_bench.json"), "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps({k: (v["ms_median"], v.get("searches_per_window"), v["spread"]) for k, v in res.items()

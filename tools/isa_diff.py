@@ -32,7 +32,13 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-
 # wasserstein_kernel<CW> became wasserstein_kernel<CW, SRC>; the pairs from index arrays are SRC = ws_index_pairs
 RENAMED = [(re.compile(r"^_Z18wasserstein_kernelILi(\d+)EEv"), r"_Z18wasserstein_kernelILi\g<1>E14ws_index_pairsEv"),
            # wq_index_pairs and wq_opts became the ws_index_pairs and ws_opts of assign_dev.h
-           (re.compile(r"^(_Z20wasserstein_q_kernelILi\d+ELi\d+ELi\d+E14)wq(_index_pairsEv)"), r"\g<1>ws\g<2>")]
+           (re.compile(r"^(_Z20wasserstein_q_kernelILi\d+ELi\d+ELi\d+E14)wq(_index_pairsEv)"), r"\g<1>ws\g<2>"),
+           # euler_kernel<NW> and generators_kernel<NW> take a WinSrc (rips_keys_dev.h) for their seven loose arguments
+           (re.compile(r"^(_Z12euler_kernelILi\d+EEv)"), r"\g<1>"),
+           (re.compile(r"^(_Z17generators_kernelILi\d+EEv)"), r"\g<1>"),
+           # their mean kernels became the two instantiations of group_mean_kernel<T, ACC> (common.h)
+           (re.compile(r"^_Z17euler_mean_kernelPKi"), r"_Z17group_mean_kernelIixEv"),
+           (re.compile(r"^_Z22generators_mean_kernelPKd"), r"_Z17group_mean_kernelIddEv")]
 
 
 def counterpart(old_name, new):
