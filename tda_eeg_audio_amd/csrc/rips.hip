@@ -457,7 +457,8 @@ __device__ __forceinline__ int rank_edges(const u32* key32, int E, u32 teff, u32
 // arguments the compiler kept two dozen loop-invariant addresses in registers across the sweep and, at the 80 VGPRs
 // that three 512-thread workgroups per CU leave, spilled them to scratch: the reloads sat in the single-wave
 // stretches of every chunk.
-//   ranking:  [keys 4E][members 2E][cursors 2 NB][scratch]                          ...     [points]
+//   keys:     [keys 4E, flat order]                                                 ...     [points]
+//   ranking:  [skey 4 (E + 4): keys by slot, padded][sidx 2E: flat index by slot][cursors 2 NB][scratch]     [points]
 //   sweep:    [rank 2E][class vectors by rank ->   (one region, NL::REGION bytes)   <- ord][misc][points]
 // ---------------------------------------------------------------------------------
 #if defined(TDA_PROFILE) && !defined(TDA_PROFILE_STOPS_ONLY)
@@ -480,7 +481,7 @@ struct NL {                                              // byte offsets of the 
     static constexpr int E = NARROW_EMAX;
     static constexpr int RANK = 0;
     static constexpr int PSI = NL_A16(2 * E) + NL_GUARD;
-    static constexpr int MEMBERS = NL_A16(4 * E);
+    static constexpr int MEMBERS = NL_A16(4 * (E + 4));  // sidx, behind skey and its four padding keys
     static constexpr int CURSOR = NL_A16(MEMBERS + 2 * E);
     static constexpr int RSCR = CURSOR + 2 * NARROW_NB;  // vmax, min-max scratch, wave sums, reductions: 720 bytes
     static constexpr int TOTAL = NARROW_LDS;
@@ -488,28 +489,37 @@ struct NL {                                              // byte offsets of the 
     static constexpr int MISC = AUX - NL_GUARD - NL_A16(8752 + 8 * 32);      // MISC_BYTES(32), checked on the host side
     static constexpr int REGION = MISC - NL_GUARD - PSI;  // class vectors from its start, ord at its end
     static_assert(RSCR + 720 <= AUX - NL_GUARD, "the ranking arrays must end in front of the points");
-    static_assert(MEMBERS >= 4 * (E + 1) && CURSOR >= MEMBERS + 2 * (E + 3), "room for the walk's padding (rank_edges_narrow)");
+    static_assert(MEMBERS >= 4 * (E + 4) && CURSOR >= MEMBERS + 2 * E, "room for the walk's padding: skey[E .. E + 3] (rank_edges_narrow)");
+    static_assert(E < 0x8000 && RANK_NONE >= E, "rank and flat index of a slot share a register (rank_edges_narrow)");
     static_assert(REGION >= 2 * E + 8 * 512, "the first chunks must fit: class vectors of 2 NT ranks next to the whole of ord");
 };
 
 // ---------------------------------------------------------------------------------
-// The same ranking for the NARROW first pass of the point-cloud kernel (three workgroups per CU: 54.6 KB of LDS per
-// window instead of 79): no bucket index parked in the rank table (recomputed for the scatter), 2,048 buckets instead
-// of 8,192 -- and the rank table
-// takes the place of the keys: every thread keeps the ranks of its (at most 16) edges in eight registers across the
-// barrier that ends the last read of a key, and `ord` is written from them at the end of the region it shares with
-// the class vectors (see rips_sweep).  LDS during the ranking: keys 4E | members 2E | cursors 2 NB.
-// The walk over a bucket (3.6 members on average now) fetches four members per trip: two LDS round trips per four
-// members instead of two per member.
+// The same ranking for the NARROW first pass of the point-cloud kernel (three workgroups per CU: 52.5 KB of LDS per
+// window instead of 79), with 2,048 buckets instead of 8,192 and the KEYS BESIDE THE BUCKET MEMBERS:
+//   count    every thread keeps the keys and the buckets of its (at most 15) edges in registers; after the barrier that
+//            ends the count the flat key table is dead;
+//   scatter  slot = cursor[b]++, skey[slot] = key (over the flat table), sidx[slot] = flat index;
+//   rank     IN SLOT ORDER: thread j owns the slots j, j + NT, ...  It reads its key and flat index back, recomputes the
+//            bucket (the same Bucketer as in the count, bit for bit) and counts the keys below its own over skey[lo .. hi)
+//            of that bucket, four consecutive keys per trip and per LDS instruction pair: no member is unpacked into an
+//            address and no key is gathered.  Neighbouring lanes share buckets, so a wave walks about two thirds of the
+//            trips that 64 edges in flat order need.  Equal keys are told apart by the flat index, as everywhere
+//            (rank = position in (key, flat index) order): a bucket in which another slot holds the thread's key is
+//            walked once more, over skey and sidx (the slow path: regular polygons, coincident points);
+//   write    the rank table and `ord` lie over skey / sidx: every thread keeps (rank, flat index) of its slots in
+//            registers across the barrier that ends the last read, then writes rank[e] and ord[rank]; the edges
+//            beyond the effective threshold get RANK_NONE from the thread that counted them (one bit each).
+// LDS during the ranking: skey 4 (E + 4) | sidx 2E | cursors 2 NB.
 // ---------------------------------------------------------------------------------
 template <int NT, int NB>
-__device__ __forceinline__ int rank_edges_narrow(const u32* key32, int E, u32 teff, u32 kmin, u16* members, u32* cursor, int* wsum,
+__device__ __forceinline__ int rank_edges_narrow(u32* skey, int E, u32 teff, u32 kmin, u16* sidx, u32* cursor, int* wsum,
                                                  u16* rank, u16* ord)
 {
     static_assert(NB % (2 * NT) == 0, "every thread scans whole words");
-    static_assert(NB <= 0x8000, "bucket indices are parked in 16 bits, 0xffff = beyond the threshold");
     constexpr int WPT = NB / NT / 2;                  // packed words per thread in the scan
-    constexpr int EPT = 2 * ((NARROW_EMAX + 2 * NT - 1) / (2 * NT));      // edges per thread, at most (even)
+    constexpr int EPT = (NARROW_EMAX + NT - 1) / NT;  // edges (count, scatter) and slots (rank) per thread, at most
+    static_assert(EPT <= 32, "one bit per edge of the thread");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     Bucketer bk;
     bk.dmin = sortable_f32(kmin);
@@ -517,19 +527,21 @@ __device__ __forceinline__ int rank_edges_narrow(const u32* key32, int E, u32 te
     bk.scale = bk.top / (sortable_f32(teff) - bk.dmin);
     for (int i = tid; i < NB / 2; i += NT) cursor[i] = 0u;
     __syncthreads();
-    // ---- count; the bucket of every edge stays in a register (two per VGPR) until its rank takes the place ----
-    u32 rk[EPT / 2];
+    // ---- count; the keys stay in registers until the scatter, `beyond`: this thread's edges past the threshold ----
+    u32 kreg[EPT], breg[EPT];                         // (breg: the bucket, or none)
+    u32 beyond = 0u;
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
         const int e = tid + i * NT;
-        u32 b = 0xffffu;
+        breg[i] = 0xffffffffu;
         if (e < E) {
-            const u32 k = key32[e];
-            if (k <= teff) { b = (u32)bk(k); atomicAdd(&cursor[b >> 1], 1u << (16 * (b & 1))); }
+            const u32 k = skey[e];
+            kreg[i] = k;
+            if (k <= teff) { const u32 b = (u32)bk(k); breg[i] = b; atomicAdd(&cursor[b >> 1], 1u << (16 * (b & 1))); }
+            else beyond |= 1u << i;
         }
-        if (i & 1) rk[i >> 1] |= b << 16; else rk[i >> 1] = b;
     }
-    __syncthreads();
+    __syncthreads();                                  // the flat key table is dead from here on
     // ---- scan ----
     {
         u32 w[WPT];
@@ -549,64 +561,82 @@ __device__ __forceinline__ int rank_edges_narrow(const u32* key32, int E, u32 te
         const u32 add = (u32)basep * 0x00010001u;     // both halves (sums stay below 65,536)
 #pragma unroll
         for (int i = 0; i < WPT; ++i) cursor[tid * WPT + i] = w[i] + add;
-        // The walk below fetches four members per trip WITHOUT looking at the end of its bucket: members of later
-        // buckets have larger keys and never count, and behind the last bucket lie three entries that name a key of
-        // 0xffffffff (both in the padding that the fixed layout leaves behind the two arrays)
+        // The walk below fetches four keys per trip WITHOUT looking at the end of its bucket: later buckets hold
+        // strictly larger keys, which neither count nor tie, and behind the last bucket lie four keys of 0xffffffff
+        // (in the padding that the fixed layout leaves behind skey: NL::MEMBERS)
         if (tid == NT - 1) {
             const int total = basep + s;
-            members[total] = (u16)NARROW_EMAX; members[total + 1] = (u16)NARROW_EMAX; members[total + 2] = (u16)NARROW_EMAX;
-            const_cast<u32*>(key32)[NARROW_EMAX] = 0xffffffffu;
+            skey[total] = 0xffffffffu; skey[total + 1] = 0xffffffffu; skey[total + 2] = 0xffffffffu; skey[total + 3] = 0xffffffffu;
         }
     }
     __syncthreads();
     // ---- scatter: afterwards cursor[b] = end of bucket b = start of bucket b + 1 ----
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
-        const u32 b = i & 1 ? rk[i >> 1] >> 16 : rk[i >> 1] & 0xffffu;
-        if (b != 0xffffu) {
+        const u32 b = breg[i];
+        if (b != 0xffffffffu) {
             const int sh = 16 * (int)(b & 1u);
-            const u32 old = atomicAdd(&cursor[b >> 1], 1u << sh);
-            members[(old >> sh) & 0xffffu] = (u16)(tid + i * NT);
+            const u32 slot = (atomicAdd(&cursor[b >> 1], 1u << sh) >> sh) & 0xffffu;
+            skey[slot] = kreg[i];
+            sidx[slot] = (u16)(tid + i * NT);
         }
     }
     __syncthreads();
-    // ---- rank: rank(e) = start of its bucket + the members that precede it in (key, flat index) order.  Four members
-    // per trip; (key, index) pairs are compared as 64-bit numbers; what a trip reads beyond the end of the bucket
-    // belongs to later buckets or is the padding (see the scan) and does not precede the edge ----
+    // ---- rank, in slot order: rank = start of the bucket + the keys of the bucket below the slot's own (+ the equal
+    // keys with a smaller flat index).  The lanes of a wave take their trips together (a lane that is through goes on
+    // reading later buckets and, from Ev on, the padding: neither counts), so the marks of equal keys are masks in
+    // scalar registers: `twice` has the lanes that met their key at least twice, i.e. in another slot than their own ----
     const u16* cur16 = reinterpret_cast<const u16*>(cursor);
     const int Ev = uni((int)cur16[NB - 1]);           // end of the last bucket = edges within the effective threshold
+    u32 re[EPT];                                      // (rank << 16) | flat index of the thread's slots
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
-        const u32 e = (u32)(tid + i * NT);
-        const u32 b = i & 1 ? rk[i >> 1] >> 16 : rk[i >> 1] & 0xffffu;
-        u32 r = RANK_NONE;
-        if (b != 0xffffu) {
-            const u32 k = key32[e];
-            const u64 me = ((u64)k << 32) | e;
+        const int s = tid + i * NT;
+        re[i] = 0xffffffffu;
+        if (s < Ev) {
+            const u32 k = skey[s];
+            const u32 e = (u32)sidx[s];
+            const u32 b = (u32)bk(k);
             const int lo = b ? (int)cur16[b - 1] : 0, hi = (int)cur16[b];
             int c = 0;
-            for (int j = lo; j < hi; j += 4) {
-                u32 m[4], km[4];
+            u32 q = 4u * (u32)lo;                     // (byte offsets: no shift per trip)
+            const u32 q_hi = 4u * (u32)hi, q_end = 4u * (u32)Ev;
+            u64 once = 0ull, twice = 0ull;
+#pragma unroll 1
+            do {
+                const u32* p = reinterpret_cast<const u32*>(reinterpret_cast<const unsigned char*>(skey) + min(q, q_end));
+                u32 km[4];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) m[t] = (u32)members[j + t];
+                for (int t = 0; t < 4; ++t) km[t] = p[t];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) km[t] = key32[m[t]];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) c += ((((u64)km[t] << 32) | m[t]) < me) ? 1 : 0;
+                for (int t = 0; t < 4; ++t) {
+                    c += km[t] < k ? 1 : 0;
+                    const u64 m = __ballot(km[t] == k);
+                    twice |= once & m;
+                    once |= m;
+                }
+                q += 16u;
+            } while (__any(q < q_hi));
+            if ((twice >> lane) & 1ull) {             // the slow path: equal keys, the flat index decides
+                c = 0;
+#pragma unroll 1
+                for (int j = lo; j < hi; ++j) {
+                    const u32 km = skey[j];
+                    c += (km < k || (km == k && (u32)sidx[j] < e)) ? 1 : 0;
+                }
             }
-            r = (u32)(lo + c);
+            re[i] = ((u32)(lo + c) << 16) | e;
         }
-        if (i & 1) rk[i >> 1] = (rk[i >> 1] & 0xffffu) | (r << 16); else rk[i >> 1] = (rk[i >> 1] & 0xffff0000u) | r;
     }
-    __syncthreads();                                  // rank and ord lie over the keys / members: every read of those is done
+    __syncthreads();                                  // rank and ord lie over skey / sidx: every read of those is done
 #pragma unroll
     for (int i = 0; i < EPT; ++i) {
-        const int e = tid + i * NT;
-        if (e < E) {
-            const u32 r = i & 1 ? rk[i >> 1] >> 16 : rk[i >> 1] & 0xffffu;
+        if (re[i] != 0xffffffffu) {
+            const u32 r = re[i] >> 16, e = re[i] & 0xffffu;
             rank[e] = (u16)r;
-            if (r != RANK_NONE) ord[r] = (u16)edge_ab(e);
+            ord[r] = (u16)edge_ab((int)e);
         }
+        if (beyond & (1u << i)) rank[tid + i * NT] = (u16)RANK_NONE;
     }
     __syncthreads();
     return Ev;
@@ -2327,9 +2357,9 @@ __device__ __forceinline__ void rips_cloud_window(unsigned char* smem, const int
 #ifndef CLOUD_WAVES
 #define CLOUD_WAVES 4
 #endif
-// NARROW: three workgroups of 384 threads per CU = 18 waves, five per SIMD at most: 96 VGPRs.  (Three workgroups of 512
-// would need six waves per SIMD: at 80 VGPRs the sweep spills the thread index and half of its scalars, and every
-// phase, the single-wave stretches included, ran 20-40 % longer -- measured: more than the third workgroup brought.)
+// NARROW: three workgroups of NARROW_NT = 512 threads per CU = 24 waves, NARROW_WAVES = 6 per SIMD: 80 VGPRs, which the
+// kernel keeps without scratch since the layout is fixed at compile time (struct NL; tests/test_narrow_kernel_registers.py
+// reads it off the code object).  Three workgroups of 384 (18 waves, 96 VGPRs) still build (NARROW_NT): measured slower.
 template <int NT, int W, typename WT, bool RETRY, bool NARROW = false>
 __global__ void __launch_bounds__(NT, RETRY ? 2 : (NARROW ? NARROW_WAVES : CLOUD_WAVES))
 rips_cloud_kernel(const double* __restrict__ src, const int* __restrict__ tau_or_npts, int n_win,
