@@ -654,6 +654,83 @@ tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int ma
 tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off,
                           int n_seg, const int* status_in, int skip_mask, double* mean);
 
+/* ---- Network curves: graph measures of the thresholded graphs ----------------------------
+ * The conventional graph measures of the functional-connectivity literature -- degree, clustering coefficient and
+ * transitivity, characteristic path length, global efficiency, number and size of the components -- of the graph G_g of a
+ * window at every point g of a grid of scales: the baseline beside the topological summaries of the same filtration.  The
+ * contract is this text; tests/network_ref.py evaluates it twice.
+ *   Inputs.     The input forms, keys k[a][b], grid t[g], presence rule, refusals and status words are those of "Euler
+ *               characteristic curves" above, word for word: G_g has the vertices 0..n-1 and the edge {a, b} exactly when
+ *               k <= (float)thresh and (double)k <= t[g].  Curve, Euler curve and diagram describe one filtration.
+ *   Notation.   deg(v), N(v): degree and neighbours of v in G_g.  h(u, v): the number of edges of a shortest path, undefined
+ *               when u and v are not connected.  tri(v): the number of pairs {u, w} within N(v) whose edge is present.
+ *               p_d: the number of unordered pairs {u, v} with h(u, v) = d.  C(m, 2) = m (m - 1) / 2.
+ *   counts      (n_win, TDA_NET_ROWS, n_grid) int32, the rows
+ *                 0 edges       number of edges
+ *                 1 isolated    number of v with deg(v) = 0
+ *                 2 max_degree  largest degree
+ *                 3 wedges      sum_v C(deg(v), 2)                                   (at most 128 C(127, 2) = 1,024,128)
+ *                 4 triangles   (sum_v tri(v)) / 3
+ *                 5 components  number of connected components
+ *                 6 largest     size of the largest component
+ *                 7 pairs       unordered connected pairs u != v, sum_d p_d
+ *                 8 hops        sum over those pairs of h          (at most (n - 1) n (n + 1) / 6 = 349,504 at n = 128)
+ *                 9 diameter    largest h; 0 without a pair
+ *   measures    (n_win, TDA_NET_MEASURES, n_grid) float64.  Each value is a function of the integers in one order of IEEE
+ *               operations (no contraction):
+ *                 0 transitivity  wedges ? (double)(3 * triangles) / (double)wedges : 0.0
+ *                 1 clustering    Watts-Strogatz mean local clustering: c_v = deg(v) < 2 ? 0.0 :
+ *                                 (double)tri(v) / (double)C(deg(v), 2); S = 0.0; S += c_0; S += c_1; ... in ascending v;
+ *                                 the value is S / (double)n
+ *                 2 efficiency    Latora-Marchiori global efficiency: n < 2 ? 0.0 :
+ *                                 (sum_{d = 1, 2, ...} (double)p_d / (double)d) / (double)C(n, 2), d ascending, the sum
+ *                                 starting from 0.0 (terms past the diameter are +0.0)
+ *                 3 path_length   characteristic path length over the connected pairs: pairs ? (double)hops /
+ *                                 (double)pairs : 0.0
+ *   nodal       (nullable) (n_win, TDA_NET_NODAL, n_grid, n_node) int32, n_node = n (matrices), p_cap (clouds),
+ *               TDA_MAX_POINTS (Takens): the `part` convention of the generators.  The rows: 0 degree deg(v), 1 triangles
+ *               tri(v), 2 reach (the vertices u != v connected to v), 3 farness sum_u h(v, u), 4 eccentricity max_u h(v, u)
+ *               (0 when there is none).  Entries with v >= n are 0.  A NULL nodal changes no byte of the other outputs.
+ *   status, n_points  as the Euler entry points.  A refused window (TDA_WIN_DEGENERATE, TDA_WIN_TOO_LARGE, tau < 1) has
+ *               all-zero blocks, 0.0 in measures.
+ *   Means.      tda_network_mean: mean_counts (n_seg, TDA_NET_ROWS, n_grid), mean_measures (n_seg, TDA_NET_MEASURES,
+ *               n_grid), mean_nodal (n_seg, TDA_NET_NODAL, n_grid, n_node), all float64; each input is nullable together
+ *               with its mean.  Groups, status_in, skip_mask and seg_off = NULL as tda_euler_mean.  The integer blocks:
+ *               (double)S / (double)m with S the exact int64 sum of the kept windows.  measures: S = 0.0, then S += the
+ *               kept windows' values in ascending window order, S / (double)m.  m = 0 gives NaN.
+ *   Limits.     Those of the Euler entry points, without max_dim; for the means n_seg != n_win without a table, an input
+ *               without its mean or the reverse, or n_node < 1 with nodal: TDA_ERR_INVALID with a message in
+ *               tda_last_error; nothing is launched or written.
+ *   Determinism.  A window alone and inside a batch give the same bytes.  No atomics, no polls.  Every loop is bounded
+ *               before it starts by n, n_grid, n_node or a popcount; the level loop of the search by n - 1.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage every buffer. */
+#define TDA_NET_ROWS     10
+#define TDA_NET_MEASURES 4
+#define TDA_NET_NODAL    5
+tda_status tda_network_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                    const double* grid, int n_grid, int* counts, double* measures, int* nodal, int* status,
+                                    void* stream);
+tda_status tda_network_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                const double* grid, int n_grid, int* counts, double* measures, int* nodal, int* status);
+tda_status tda_network_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                       int normalise, double thresh, const double* grid, int n_grid, int* counts,
+                                       double* measures, int* nodal, int* status, void* stream);
+tda_status tda_network_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                   int normalise, double thresh, const double* grid, int n_grid, int* counts,
+                                   double* measures, int* nodal, int* status);
+tda_status tda_network_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                        int subsample, double thresh, const double* grid, int n_grid, int* counts,
+                                        double* measures, int* nodal, int* n_points, int* status, void* stream);
+tda_status tda_network_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                    int subsample, double thresh, const double* grid, int n_grid, int* counts,
+                                    double* measures, int* nodal, int* n_points, int* status);
+tda_status tda_network_mean_dev(tda_ctx* ctx, const int* counts, const double* measures, const int* nodal, int n_win,
+                                int n_grid, int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                                double* mean_counts, double* mean_measures, double* mean_nodal, void* stream);
+tda_status tda_network_mean(tda_ctx* ctx, const int* counts, const double* measures, const int* nodal, int n_win,
+                            int n_grid, int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                            double* mean_counts, double* mean_measures, double* mean_nodal);
+
 /* ---- Generators and representative cycles of Rips persistence pairs ---------------------
  * Which simplices stand behind a row of a diagram, and a cycle that represents every H1 row: the counterpart of
  * ripser(..., do_cocycles=True) and of GUDHI's flag_persistence_generators, for the question "which channels carry the

@@ -32,6 +32,13 @@ MAX_GRID = 256              # TDA_MAX_GRID
 MAX_IMAGE_SIDE = 32         # TDA_MAX_IMAGE_SIDE
 EC_MAX_DIM = 3              # TDA_EC_MAX_DIM: highest simplex dimension of the Euler characteristic curves
 MAX_POINTS = 128
+NET_ROWS = 10               # TDA_NET_ROWS: integer rows of the network curves (include/tdaeeg.h, "Network curves")
+NET_MEASURES = 4            # TDA_NET_MEASURES: their float64 rows
+NET_NODAL = 5               # TDA_NET_NODAL: their per-vertex rows
+NET_COUNT_NAMES = ("edges", "isolated", "max_degree", "wedges", "triangles", "components", "largest", "pairs", "hops",
+                   "diameter")
+NET_MEASURE_NAMES = ("transitivity", "clustering", "efficiency", "path_length")
+NET_NODAL_NAMES = ("degree", "triangles", "reach", "farness", "eccentricity")
 TDA_GEN_BIRTH_TIED = 1       # tda_generators_*: flags of an H1 row (include/tdaeeg.h)
 TDA_GEN_DEATH_TIED = 2
 TDA_GEN_CYCLE_TRUNCATED = 4
@@ -175,6 +182,14 @@ SYMBOLS = {
     "tda_euler_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, _I, c_vp, c_vp, c_vp]),
     "tda_euler_mean_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp]),
     "tda_euler_mean": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp]),
+    "tda_network_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_cloud_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_takens_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_mean_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_network_mean": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_generators_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp, c_vp]),
     "tda_generators_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp]),
     "tda_generators_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp, c_vp]),

@@ -714,6 +714,48 @@ tda_status tda_euler_mean_dev(tda_ctx* ctx, const int* counts, int n_win, int ma
                              (hipStream_t)stream);
 }
 
+#define NET_CHECK_PTRS(ctx) do { CHECK_PTR(ctx, grid); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, measures); CHECK_PTR(ctx, status); \
+                            } while (0)
+
+tda_status tda_network_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                    const double* grid, int n_grid, int* counts, double* measures, int* nodal, int* status,
+                                    void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, dm); NET_CHECK_PTRS(ctx); }
+    return launch_network(ctx, WinSrc{dm, nullptr, n, 0, 1, 2, symmetrise, 0}, n_win, thresh, grid, n_grid, counts, measures,
+                          nodal, nullptr, status, (hipStream_t)stream);
+}
+
+tda_status tda_network_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                       int normalise, double thresh, const double* grid, int n_grid, int* counts,
+                                       double* measures, int* nodal, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); NET_CHECK_PTRS(ctx); }
+    return launch_network(ctx, WinSrc{pc, n_pts, p_cap, dim, 1, 1, normalise, 0}, n_win, thresh, grid, n_grid, counts, measures,
+                          nodal, nullptr, status, (hipStream_t)stream);
+}
+
+tda_status tda_network_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                        int subsample, double thresh, const double* grid, int n_grid, int* counts,
+                                        double* measures, int* nodal, int* n_points, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); NET_CHECK_PTRS(ctx); }
+    return launch_network(ctx, WinSrc{win, tau, n_t, dim, subsample, 0, 1, 0}, n_win, thresh, grid, n_grid, counts, measures,
+                          nodal, n_points, status, (hipStream_t)stream);
+}
+
+tda_status tda_network_mean_dev(tda_ctx* ctx, const int* counts, const double* measures, const int* nodal, int n_win,
+                                int n_grid, int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                                double* mean_counts, double* mean_measures, double* mean_nodal, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    return launch_network_mean(ctx, counts, measures, nodal, n_win, n_grid, n_node, seg_off, n_seg, status_in, skip_mask,
+                               mean_counts, mean_measures, mean_nodal, (hipStream_t)stream);
+}
+
 // the row inputs and the outputs that the tda_generators_* entry points share, in the header's order
 #define GEN_PARAMS                                                                                                     \
     const double* h0, int h0_cap, const int* h0_cnt, const double* h1, int h1_cap, const int* h1_cnt,                  \
@@ -1609,6 +1651,97 @@ tda_status tda_euler_mean(tda_ctx* ctx, const int* counts, int n_win, int max_di
     auto d_mean = s.out(mean, (size_t)n_seg * rg);
     return s.run([&] {
         return tda_euler_mean_dev(ctx, d_cnt, n_win, max_dim, n_grid, g.off, n_seg, g.status, skip_mask, d_mean, nullptr);
+    });
+}
+
+namespace {
+// the device twins of the outputs of a tda_network_* host call; n_node: the columns of nodal
+struct NetStage {
+    Dev<double> grid, measures;
+    Dev<int> counts, nodal, status;
+    NetStage(Stage& s, size_t nw, const double* grid, int n_grid, int n_node, int* counts, double* measures, int* nodal, int* status)
+        : grid(s.in(grid, (size_t)n_grid)), measures(s.out(measures, nw * TDA_NET_MEASURES * n_grid)),
+          counts(s.out(counts, nw * TDA_NET_ROWS * n_grid)), nodal(s.out(nodal, nw * TDA_NET_NODAL * n_grid * n_node)),
+          status(s.out(status, nw)) {}
+};
+}   // namespace
+
+tda_status tda_network_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                const double* grid, int n_grid, int* counts, double* measures, int* nodal, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 2, n, 0, 1, nullptr, nullptr));
+    TDA_TRY(nt_check(ctx, n_grid));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, dm); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_dm = s.in(dm, (size_t)n_win * n * n);
+    const NetStage d(s, (size_t)n_win, grid, n_grid, n, counts, measures, nodal, status);
+    return s.run([&] {
+        return tda_network_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d.grid, n_grid, d.counts, d.measures, d.nodal,
+                                        d.status, nullptr);
+    });
+}
+
+tda_status tda_network_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                   int normalise, double thresh, const double* grid, int n_grid, int* counts,
+                                   double* measures, int* nodal, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 1, p_cap, dim, 1, nullptr, nullptr));
+    TDA_TRY(nt_check(ctx, n_grid));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_pc = s.in(pc, (size_t)n_win * p_cap * dim);
+    auto d_n = s.in(n_pts, (size_t)n_win);
+    const NetStage d(s, (size_t)n_win, grid, n_grid, p_cap, counts, measures, nodal, status);
+    return s.run([&] {
+        return tda_network_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d.grid, n_grid, d.counts,
+                                           d.measures, d.nodal, d.status, nullptr);
+    });
+}
+
+tda_status tda_network_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                    int subsample, double thresh, const double* grid, int n_grid, int* counts,
+                                    double* measures, int* nodal, int* n_points, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 0, n_t, dim, subsample, nullptr, nullptr));
+    TDA_TRY(nt_check(ctx, n_grid));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.in(tau, (size_t)n_win);
+    const NetStage d(s, (size_t)n_win, grid, n_grid, TDA_MAX_POINTS, counts, measures, nodal, status);
+    auto d_np = s.out(n_points, (size_t)n_win);
+    return s.run([&] {
+        return tda_network_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d.grid, n_grid, d.counts,
+                                            d.measures, d.nodal, d_np, d.status, nullptr);
+    });
+}
+
+tda_status tda_network_mean(tda_ctx* ctx, const int* counts, const double* measures, const int* nodal, int n_win,
+                            int n_grid, int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                            double* mean_counts, double* mean_measures, double* mean_nodal)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    TDA_TRY(nt_mean_check(ctx, counts, measures, nodal, n_win, n_grid, n_node, seg_off, n_seg, mean_counts, mean_measures,
+                          mean_nodal));
+    if (n_seg == 0) return TDA_OK;
+    Stage s(ctx);
+    const size_t ng = (size_t)n_grid, nn = nodal || mean_nodal ? (size_t)n_node : 0;
+    auto d_cnt = s.in(counts, (size_t)n_win * TDA_NET_ROWS * ng);
+    auto d_mea = s.in(measures, (size_t)n_win * TDA_NET_MEASURES * ng);
+    auto d_nod = s.in(nodal, (size_t)n_win * TDA_NET_NODAL * ng * nn);
+    const GroupIn g = group_in(s, seg_off, n_seg, status_in, (size_t)n_win);
+    auto d_mc = s.out(mean_counts, (size_t)n_seg * TDA_NET_ROWS * ng);
+    auto d_mm = s.out(mean_measures, (size_t)n_seg * TDA_NET_MEASURES * ng);
+    auto d_mn = s.out(mean_nodal, (size_t)n_seg * TDA_NET_NODAL * ng * nn);
+    return s.run([&] {
+        return tda_network_mean_dev(ctx, d_cnt, d_mea, d_nod, n_win, n_grid, n_node, g.off, n_seg, g.status, skip_mask, d_mc,
+                                    d_mm, d_mn, nullptr);
     });
 }
 

@@ -255,6 +255,18 @@ tda_status launch_euler(tda_ctx*, const WinSrc& src, int n_win, double thresh, c
                         int* counts, int* n_points, int* status, hipStream_t);
 tda_status launch_euler_mean(tda_ctx*, const int* counts, int n_win, int max_dim, int n_grid, const int* seg_off, int n_seg,
                              const int* status_in, int skip_mask, double* mean, hipStream_t);
+// (network.hip) graph measures of the thresholded graphs on a grid, for the windows as launch_euler takes them.  Checks the
+// limits of the header itself: nt_check (the grid), then win_src_limits; nt_mean_check for the means (which pairs are
+// given, n_seg without a table, the row length of nodal).
+tda_status nt_check(tda_ctx*, int n_grid);
+tda_status launch_network(tda_ctx*, const WinSrc& src, int n_win, double thresh, const double* grid, int n_grid, int* counts,
+                          double* measures, int* nodal, int* n_points, int* status, hipStream_t);
+tda_status nt_mean_check(tda_ctx*, const void* counts, const void* measures, const void* nodal, int n_win, int n_grid,
+                         int n_node, const int* seg_off, int n_seg, const void* mean_counts, const void* mean_measures,
+                         const void* mean_nodal);
+tda_status launch_network_mean(tda_ctx*, const int* counts, const double* measures, const int* nodal, int n_win, int n_grid,
+                               int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                               double* mean_counts, double* mean_measures, double* mean_nodal, hipStream_t);
 // (generators.hip) the edges behind the rows of a Rips diagram and a representative cycle per H1 row.  GenArgs: the rows the
 // Rips entry points wrote and the outputs, as the tda_generators_* entry points take them (part_ld is the launcher's).
 struct GenArgs {

@@ -227,6 +227,90 @@ def euler_names(bands=BANDS, max_dim=3, grid=None):
             for j in range(n_grid)]
 
 
+def _network_group_means(net):
+    """(n_seg, NET_ROWS + NET_MEASURES, n_grid) float64 of a DeviceNetworkCurves with its means: counts, then measures."""
+    import torch
+    return torch.cat([net.mean_counts, net.mean_measures], dim=1).cpu().numpy()
+
+
+def network_curves_from_distances(dist_list, grid, nodal=False, thresh=MAX_EDGE_LENGTH):
+    """dist_list as features_from_distances takes it.  No Rips launch: one launch computes the graph measures of every
+    window's thresholded graph on `grid` (include/tdaeeg.h, "Network curves"; engine.network_dm_dev), the next ones write
+    the group means: (len(dist_list), NET_ROWS + NET_MEASURES, n_grid) float64, per group the mean over its windows of the
+    integer rows (_lib.NET_COUNT_NAMES) and then of the float64 measures (_lib.NET_MEASURE_NAMES), the columns named by
+    network_names.  nodal=True: (means, nodal_means), the second (len(dist_list), NET_NODAL, n_grid, n) float64 with the
+    rows of _lib.NET_NODAL_NAMES.  A group without a window is NaN.  ValueError for a bad grid."""
+    import torch
+    from . import _lib
+    grid = engine.network_args(grid)
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    sizes = np.array([len(d) for d in dist_list])
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    grid_t = torch.from_numpy(grid).to(dev)
+    if sizes.sum() == 0:
+        n = next((np.asarray(d).shape[-1] for d in dist_list if np.asarray(d).ndim == 3), 1)
+        means = np.full((len(dist_list), _lib.NET_ROWS + _lib.NET_MEASURES, grid.shape[0]), np.nan)
+        return (means, np.full((len(dist_list), _lib.NET_NODAL, grid.shape[0], n), np.nan)) if nodal else means
+    allw = np.concatenate([np.asarray(d, dtype=np.float64) for d in dist_list if len(d)], axis=0)
+    net = engine.network_dm_dev(torch.from_numpy(np.ascontiguousarray(allw)).to(dev), grid_t, nodal, thresh, seg_off_t=seg_t,
+                                ctx=ctx)
+    means = _network_group_means(net)
+    return (means, net.mean_nodal.cpu().numpy()) if nodal else means
+
+
+def network_names(bands=BANDS, grid=None):
+    """Column names of network_curves_from_distances(...)[r] of every band, flattened band by band: per band the integer
+    rows and then the measures, each at every grid point in order."""
+    from . import _lib
+    n_grid = 64 if grid is None else len(grid)
+    return [f"{band}_{row}_t{j}" for band in bands for row in _lib.NET_COUNT_NAMES + _lib.NET_MEASURE_NAMES
+            for j in range(n_grid)]
+
+
+NETWORK_MEASURES = ("pearson", "plv") + tuple(engine.CONNECTIVITY_MEASURES)
+
+
+def connectivity_network_curves_from_windows(win_list, measure, grid, method="euclidean"):
+    """win_list: list of (k_i, n_ch, n_t) arrays of EEG windows, one per (recording, band) group.  Per group the mean over
+    its windows of the network curves on `grid` of the graph on the distance of the window's channels under `measure`:
+    "pearson" (engine.corr_dist_dev; method must be "euclidean"), "plv" (engine.plv_dist_dev) or one of
+    engine.CONNECTIVITY_MEASURES (engine.connectivity_dist_dev).  (len(win_list), NET_ROWS + NET_MEASURES, n_grid) float64,
+    counts then measures, as network_curves_from_distances.  All on the device: distances, curves, means.  A window the
+    connectivity kernel flags (a sample that is not finite) is left out of its group's mean; a group without a kept window
+    is NaN.  ValueError for an unknown measure or method or a bad grid."""
+    import torch
+    from . import _lib
+    grid = engine.network_args(grid)
+    if not isinstance(measure, str) or measure not in NETWORK_MEASURES:
+        raise ValueError(f"connectivity: one of {sorted(NETWORK_MEASURES)}, not {measure!r}")
+    if measure == "pearson":
+        if method != "euclidean":
+            raise ValueError("connectivity: the Pearson distance is euclidean")
+    elif measure == "plv":
+        engine.plv_method(method)
+    else:
+        engine._dist_method(method)
+    sizes = np.array([len(w) for w in win_list])
+    if sizes.sum() == 0:
+        return np.full((len(win_list), _lib.NET_ROWS + _lib.NET_MEASURES, grid.shape[0]), np.nan)
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    allw = np.concatenate([np.asarray(w, dtype=np.float64) for w in win_list if len(w)], axis=0)
+    win_t = torch.from_numpy(np.ascontiguousarray(allw)).to(dev)
+    st = None
+    if measure == "pearson":
+        dist = engine.corr_dist_dev(win_t, ctx=ctx)
+    elif measure == "plv":
+        dist, _, st = engine.plv_dist_dev(win_t, method=method, ctx=ctx)
+    else:
+        dist, _, st = engine.connectivity_dist_dev(win_t, measure=measure, method=method, ctx=ctx)
+    net = engine.network_dm_dev(dist, torch.from_numpy(grid).to(dev), seg_off_t=seg_t, status_in=st,
+                                skip_mask=0x7fffffff if st is not None else 0, ctx=ctx)
+    return _network_group_means(net)
+
+
 def channel_participation_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     that finds the birth edge and a representative cycle of every H1 row and one that writes the group means

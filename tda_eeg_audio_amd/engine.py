@@ -16,6 +16,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  pack_labels / permutation_sums_batch (within- and between-group sums of matrices under relabellings)
                  euler_dm_batch, euler_cloud_batch, euler_takens_batch (simplex counts and Euler characteristic of the Rips
                  complex on a grid of scales, by the keys of the Rips entry points)
+                 network_dm_batch, network_cloud_batch, network_takens_batch (the graph measures of the thresholded graphs on
+                 a grid of scales, by the same keys and presence rule; network_args)
                  generators_dm_batch, generators_cloud_batch, generators_takens_batch (the edges behind the rows of the
                  diagrams, a representative cycle per H1 row and the participation of every vertex; generators_args)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
@@ -39,6 +41,9 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  euler_dm_dev / euler_cloud_dev / euler_takens_dev / euler_mean_dev / euler_eeg_windows_dev: Euler
                  characteristic and simplex-count curves of resident windows and their group means
                  (utils.compute_eeg_euler_curve, drivers.euler_curves_from_distances).
+                 network_dm_dev / network_cloud_dev / network_takens_dev / network_mean_dev / network_eeg_windows_dev:
+                 the network curves of resident windows and their group means, into a DeviceNetworkCurves
+                 (utils.compute_eeg_network_curves, drivers.network_curves_from_distances).
                  generators_dm_dev / generators_cloud_dev / generators_takens_dev / generators_mean_dev /
                  generators_eeg_windows_dev: generators and cycles of resident windows from a DeviceDiagrams or raw row
                  tensors, into a DeviceGenerators (utils.compute_eeg_generators,
@@ -601,6 +606,67 @@ def euler_takens_batch(windows, taus, grid, max_dim=3, dim=3, subsample=2, thres
     ctx.check(ctx.lib.tda_euler_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample), float(thresh),
                                              ptr(grid), grid.shape[0], max_dim, ptr(out), ptr(npts), ptr(st)))
     return out, npts, st
+
+
+def network_args(grid):
+    """The grid of the network curves as the kernel takes it (include/tdaeeg.h, "Network curves"): a contiguous 1-D float64
+    array of 1..MAX_GRID values, any values in any order, with the refusals of euler_args.  ValueError, before any GPU
+    call, for anything else."""
+    return euler_args(grid, 1)[0]
+
+
+def _network_host(n_win, n_grid, n_node, nodal):
+    """The zeroed host outputs of the network_*_batch forms: counts, measures, nodal (or None), status."""
+    return (np.zeros((n_win, _lib.NET_ROWS, n_grid), np.int32), np.zeros((n_win, _lib.NET_MEASURES, n_grid), np.float64),
+            np.zeros((n_win, _lib.NET_NODAL, n_grid, n_node), np.int32) if nodal else None, np.zeros(n_win, np.int32))
+
+
+def network_dm_batch(dms, grid, nodal=False, thresh=MAX_EDGE_LENGTH, symmetrise=True, ctx=None):
+    """The graph measures of the thresholded graph of every distance matrix at every scale of grid (include/tdaeeg.h,
+    "Network curves"): dms (n_win, n, n) float64 -> (counts (n_win, NET_ROWS, n_grid) int32, measures (n_win, NET_MEASURES,
+    n_grid) float64, nodal (n_win, NET_NODAL, n_grid, n) int32 or None, status).  The rows are named by
+    _lib.NET_COUNT_NAMES, NET_MEASURE_NAMES and NET_NODAL_NAMES."""
+    grid = network_args(grid)
+    ctx = ctx or get_ctx()
+    d = f64(dms)
+    n_win, n, n2 = d.shape
+    assert n == n2, "distance matrices must be square"
+    cnt, mea, nod, st = _network_host(n_win, grid.shape[0], n, nodal)
+    ctx.check(ctx.lib.tda_network_dm_batch(ctx.h, ptr(d), n_win, n, float(thresh), int(bool(symmetrise)), ptr(grid),
+                                           grid.shape[0], ptr(cnt), ptr(mea), ptr(nod), ptr(st)))
+    return cnt, mea, nod, st
+
+
+def network_cloud_batch(clouds, grid, nodal=False, n_pts=None, normalise=True, thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from explicit clouds (n_win, p_cap, dim) with n_pts rows each, by the keys of cloud_rips_batch; nodal has
+    p_cap columns.  A window with fewer than 3 or more than min(p_cap, MAX_POINTS) points has TDA_WIN_DEGENERATE /
+    TDA_WIN_TOO_LARGE and zeros."""
+    grid = network_args(grid)
+    ctx = ctx or get_ctx()
+    pc = f64(clouds)
+    n_win, p_cap, dim = pc.shape
+    n_pts = i32(np.full(n_win, p_cap) if n_pts is None else n_pts)
+    cnt, mea, nod, st = _network_host(n_win, grid.shape[0], p_cap, nodal)
+    ctx.check(ctx.lib.tda_network_cloud_batch(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)),
+                                              float(thresh), ptr(grid), grid.shape[0], ptr(cnt), ptr(mea),
+                                              ptr(nod), ptr(st)))
+    return cnt, mea, nod, st
+
+
+def network_takens_batch(windows, taus, grid, nodal=False, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from audio windows (n_win, n_t) and their delays, by the keys of takens_rips_batch: (counts, measures,
+    nodal with MAX_POINTS columns or None, n_points, status)."""
+    grid = network_args(grid)
+    ctx = ctx or get_ctx()
+    w = f64(windows)
+    n_win, n_t = w.shape
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    cnt, mea, nod, st = _network_host(n_win, grid.shape[0], _lib.MAX_POINTS, nodal)
+    npts = np.zeros(n_win, np.int32)
+    ctx.check(ctx.lib.tda_network_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample), float(thresh),
+                                               ptr(grid), grid.shape[0], ptr(cnt), ptr(mea), ptr(nod),
+                                               ptr(npts), ptr(st)))
+    return cnt, mea, nod, npts, st
 
 
 def generators_args(cyc_cap):
@@ -1686,6 +1752,137 @@ def euler_eeg_windows_dev(win_t, grid_t, max_dim=3, thresh=MAX_EDGE_LENGTH, dist
     matrices."""
     dist_t = corr_dist_dev(win_t, dist_t, ctx=ctx)
     return euler_dm_dev(dist_t, grid_t, max_dim, thresh, True, out_t, status_t, mean_t, seg_off_t, status_in, skip_mask, ctx)
+
+
+class DeviceNetworkCurves:
+    """The outputs of the network_*_dev forms for a batch of windows, resident in HBM (include/tdaeeg.h, "Network curves"):
+    counts (n_win, NET_ROWS, n_grid) int32, measures (n_win, NET_MEASURES, n_grid) float64, status (n_win,) int32 and, when
+    asked for, nodal (n_win, NET_NODAL, n_grid, n_node) int32; mean_counts, mean_measures and mean_nodal (float64, a row
+    per group) are set by the group-mean launches."""
+
+    def __init__(self, n_win, n_grid, n_node, device, nodal=False):
+        import torch
+        kw = dict(device=device)
+        self.counts = torch.empty((n_win, _lib.NET_ROWS, n_grid), dtype=torch.int32, **kw)
+        self.measures = torch.empty((n_win, _lib.NET_MEASURES, n_grid), dtype=torch.float64, **kw)
+        self.nodal = torch.empty((n_win, _lib.NET_NODAL, n_grid, n_node), dtype=torch.int32, **kw) if nodal else None
+        self.status = torch.empty(n_win, dtype=torch.int32, **kw)
+        self.mean_counts = self.mean_measures = self.mean_nodal = None
+        self.n_win, self.n_grid, self.n_node = n_win, n_grid, n_node
+
+    def to_host(self):
+        """The same arrays as numpy, in a dict."""
+        return {k: getattr(self, k).cpu().numpy() for k in ("counts", "measures", "nodal", "status", "mean_counts",
+                                                            "mean_measures", "mean_nodal") if getattr(self, k) is not None}
+
+
+def network_mean_dev(counts_t, measures_t, nodal_t, n_win, n_grid, n_node, seg_off_t=None, status_in=None, skip_mask=0,
+                     mean_counts_t=None, mean_measures_t=None, mean_nodal_t=None, ctx=None):
+    """Group means of the blocks of network_*_dev (include/tdaeeg.h): each of counts_t, measures_t, nodal_t may be None and
+    then has no mean.  seg_off_t (n_seg + 1,) int32, or None: every window its own group.  Windows whose status_in word has
+    a bit of skip_mask are left out; a group without a kept window is NaN.  Returns (mean_counts, mean_measures,
+    mean_nodal), float64 with a row per group; up to three launches on torch's current stream, nothing allocated when the
+    means are given."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_win, n_grid, n_node = int(n_win), int(n_grid), int(n_node)
+    n_seg = n_win if seg_off_t is None else seg_off_t.numel() - 1
+    shapes = ((_lib.NET_ROWS, max(n_grid, 0)), (_lib.NET_MEASURES, max(n_grid, 0)), (_lib.NET_NODAL, max(n_grid, 0), max(n_node, 0)))
+    ins, means = [counts_t, measures_t, nodal_t], [mean_counts_t, mean_measures_t, mean_nodal_t]
+    for k, (t, dt) in enumerate(zip(ins, (torch.int32, torch.float64, torch.int32))):
+        if t is None:
+            continue
+        assert t.dtype == dt and t.is_contiguous()
+        if means[k] is None:
+            means[k] = torch.empty((n_seg,) + shapes[k], dtype=torch.float64, device=t.device)
+        assert means[k].dtype == torch.float64 and means[k].is_contiguous()
+    ctx.check(ctx.lib.tda_network_mean_dev(ctx.h, _tp(counts_t), _tp(measures_t), _tp(nodal_t), n_win, n_grid, n_node,
+                                           _tp(seg_off_t), n_seg, _tp(status_in), int(skip_mask), _tp(means[0]), _tp(means[1]),
+                                           _tp(means[2]), _stream()))
+    return tuple(means)
+
+
+def _network_dev(grid_t, n_win, n_node, nodal, out, device):
+    """Checks of the network_*_dev forms: grid_t a contiguous 1-D float64 device tensor of 1..MAX_GRID scales; out is
+    allocated when None (it may be larger than the batch: the tail is not touched)."""
+    import torch
+    if not (grid_t.is_cuda and grid_t.dtype == torch.float64 and grid_t.dim() == 1 and grid_t.is_contiguous()):
+        raise ValueError("grid_t: a contiguous 1-D float64 device tensor")
+    n_grid = int(grid_t.numel())
+    if not 1 <= n_grid <= _lib.MAX_GRID:
+        raise ValueError(f"grid_t: 1..{_lib.MAX_GRID} scales")
+    if out is None:
+        out = DeviceNetworkCurves(n_win, n_grid, n_node, device, nodal)
+    assert out.n_win >= n_win and (out.n_grid, out.n_node) == (n_grid, n_node)
+    assert not nodal or out.nodal is not None, "nodal=True needs an out with a nodal tensor"
+    return n_grid, out
+
+
+def _network_dev_mean(out, n_win, nodal, mean, seg_off_t, status_in, skip_mask, ctx):
+    """The optional group-mean launches of the network_*_dev forms: asked for by mean=True or by seg_off_t.  status_in
+    defaults to the status words the first launch has just written."""
+    if mean or seg_off_t is not None:
+        out.mean_counts, out.mean_measures, out.mean_nodal = network_mean_dev(
+            out.counts, out.measures, out.nodal if nodal else None, n_win, out.n_grid, out.n_node, seg_off_t,
+            out.status if status_in is None else status_in, skip_mask, out.mean_counts, out.mean_measures,
+            out.mean_nodal if nodal else None, ctx)
+    return out
+
+
+def network_dm_dev(dm_t, grid_t, nodal=False, thresh=MAX_EDGE_LENGTH, symmetrise=True, out=None, mean=False, seg_off_t=None,
+                   status_in=None, skip_mask=0, ctx=None):
+    """network_dm_batch on device tensors: dm_t (n_win, n, n) float64, grid_t (n_grid,) float64 -> a DeviceNetworkCurves.
+    One launch on torch's current stream (up to three more with the group means), nothing allocated when out is given."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert dm_t.is_cuda and dm_t.dtype == torch.float64 and dm_t.is_contiguous()
+    n_win, n, n2 = dm_t.shape
+    assert n == n2, "distance matrices must be square"
+    n_grid, out = _network_dev(grid_t, n_win, n, nodal, out, dm_t.device)
+    ctx.check(ctx.lib.tda_network_dm_batch_dev(ctx.h, _tp(dm_t), n_win, n, float(thresh), int(bool(symmetrise)), _tp(grid_t),
+                                               n_grid, _tp(out.counts), _tp(out.measures), _tp(out.nodal if nodal else None),
+                                               _tp(out.status), _stream()))
+    return _network_dev_mean(out, n_win, nodal, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+def network_cloud_dev(pc_t, n_pts_t, grid_t, nodal=False, normalise=True, thresh=MAX_EDGE_LENGTH, out=None, mean=False,
+                      seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """network_cloud_batch on device tensors: pc_t (n_win, p_cap, dim) float64, n_pts_t (n_win,) int32."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert pc_t.is_cuda and pc_t.dtype == torch.float64 and pc_t.is_contiguous() and n_pts_t.dtype == torch.int32
+    n_win, p_cap, dim = pc_t.shape
+    n_grid, out = _network_dev(grid_t, n_win, p_cap, nodal, out, pc_t.device)
+    ctx.check(ctx.lib.tda_network_cloud_batch_dev(ctx.h, _tp(pc_t), _tp(n_pts_t), n_win, p_cap, dim, int(bool(normalise)),
+                                                  float(thresh), _tp(grid_t), n_grid, _tp(out.counts), _tp(out.measures),
+                                                  _tp(out.nodal if nodal else None), _tp(out.status), _stream()))
+    return _network_dev_mean(out, n_win, nodal, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+def network_takens_dev(win_t, tau_t, grid_t, nodal=False, dim=3, subsample=2, thresh=MAX_EDGE_LENGTH, out=None,
+                       n_points_t=None, mean=False, seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """network_takens_batch on device tensors: win_t (n_win, n_t) float64, tau_t (n_win,) int32; n_points_t (optional,
+    int32) receives the points per window.  nodal has MAX_POINTS columns."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    n_grid, out = _network_dev(grid_t, n_win, _lib.MAX_POINTS, nodal, out, win_t.device)
+    ctx.check(ctx.lib.tda_network_takens_batch_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, int(dim), int(subsample),
+                                                   float(thresh), _tp(grid_t), n_grid, _tp(out.counts), _tp(out.measures),
+                                                   _tp(out.nodal if nodal else None), _tp(n_points_t), _tp(out.status),
+                                                   _stream()))
+    return _network_dev_mean(out, n_win, nodal, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+def network_eeg_windows_dev(win_t, grid_t, nodal=False, thresh=MAX_EDGE_LENGTH, dist_t=None, out=None, mean=False,
+                            seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """corr_dist_dev followed by network_dm_dev on EEG windows win_t (n_win, n_ch, n_t): the graph measures of exactly the
+    matrix whose diagrams eeg_window_dev gives, so the baseline and the diagram belong to one filtration.  dist_t
+    (optional) receives the matrices."""
+    dist_t = corr_dist_dev(win_t, dist_t, ctx=ctx)
+    return network_dm_dev(dist_t, grid_t, nodal, thresh, True, out, mean, seg_off_t, status_in, skip_mask, ctx)
 
 
 class DeviceGenerators:

@@ -230,6 +230,43 @@ def compute_audio_euler_curve(point_cloud, grid, max_dim=3, thresh=MAX_EDGE_LENG
     return out[0]
 
 
+def _network_rows(counts, measures, nodal):
+    """The blocks of one window as a dict of named rows (_lib.NET_COUNT_NAMES, NET_MEASURE_NAMES; "nodal_" + a name of
+    NET_NODAL_NAMES for the per-vertex rows)."""
+    from . import _lib
+    out = {name: counts[k] for k, name in enumerate(_lib.NET_COUNT_NAMES)}
+    out.update({name: measures[k] for k, name in enumerate(_lib.NET_MEASURE_NAMES)})
+    if nodal is not None:
+        out.update({"nodal_" + name: nodal[k] for k, name in enumerate(_lib.NET_NODAL_NAMES)})
+    return out
+
+
+def compute_eeg_network_curves(distance_matrix, grid, nodal=False, thresh=MAX_EDGE_LENGTH):
+    """The twin of compute_eeg_euler_curve for the graph measures (include/tdaeeg.h, "Network curves"): a dict of named
+    rows, each (n_grid,) -- the int32 counts edges, isolated, max_degree, wedges, triangles, components, largest, pairs,
+    hops, diameter and the float64 measures transitivity, clustering, efficiency, path_length of the graph of the
+    symmetrised distance matrix thresholded at every scale of grid, by the keys compute_eeg_persistence uses.  nodal=True
+    adds the (n_grid, n) int32 rows nodal_degree, nodal_triangles, nodal_reach, nodal_farness, nodal_eccentricity.  Not
+    recorded by utils.batch(): it launches at once.  ValueError for a bad grid."""
+    dm = np.asarray(distance_matrix, dtype=np.float64)
+    if dm.ndim != 2 or dm.shape[0] != dm.shape[1]:
+        raise ValueError("Distance matrix is not square")
+    cnt, mea, nod, _ = engine.network_dm_batch(dm[None], grid, nodal=nodal, thresh=thresh, symmetrise=True)
+    return _network_rows(cnt[0], mea[0], nod[0] if nodal else None)
+
+
+def compute_audio_network_curves(point_cloud, grid, nodal=False, thresh=MAX_EDGE_LENGTH):
+    """The twin of compute_audio_euler_curve: the same dict for a (P, dim) point cloud, min-max normalised, by the keys
+    compute_audio_persistence uses (the nodal rows are (n_grid, P)).  A cloud of fewer than 3 points gives zeros, as its
+    diagrams are [[0, 0]]; more than 128 points are a TdaError."""
+    pc = np.asarray(point_cloud, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[0] < 1:
+        raise ValueError("compute_audio_network_curves: a (P, dim) point cloud")
+    cnt, mea, nod, st = engine.network_cloud_batch(pc[None], grid, nodal=nodal, thresh=thresh)
+    _check_status(st[0])
+    return _network_rows(cnt[0], mea[0], nod[0] if nodal else None)
+
+
 def compute_sublevel_persistence(x, return_index=False):
     """H0 of the sublevel-set (lower-star) filtration of a time series (include/tdaeeg.h, "Sublevel-set persistence of time
     series"; ripser's lower_star example on a 1-D signal): an (m, 2) array like dgms[0], every local minimum paired with
