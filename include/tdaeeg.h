@@ -731,6 +731,90 @@ tda_status tda_network_mean(tda_ctx* ctx, const int* counts, const double* measu
                             int n_grid, int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
                             double* mean_counts, double* mean_measures, double* mean_nodal);
 
+/* ---- Recurrence curves: recurrence quantification of the windows in time order ------------
+ * Recurrence quantification analysis (Zbilut & Webber 1992; Marwan et al. 2007) of a window at every point g of a grid of
+ * scales: the conventional baseline beside the topological summaries of a delay embedding.  The recurrence plot at scale
+ * t[g] is the adjacency matrix of the 1-skeleton of the Rips complex at t[g] on the vertices in time order; the network
+ * curves forget that order, these curves read it.  The contract is this text; tests/recurrence_ref.py evaluates it twice.
+ *   Inputs.     The input forms, keys k[a][b], grid t[g], presence rule, refusals and status words are those of "Euler
+ *               characteristic curves" above, word for word.  Three further parameters: theiler, l_min, v_min.
+ *               For a window with n points R_g[i][j] = 1 iff i != j, |i - j| >= theiler and the edge {i, j} is present at
+ *               g: k <= (float)thresh and (double)k <= t[g].  R_g is symmetric with a zero band of half-width theiler - 1
+ *               around the diagonal; theiler = 1 removes the main diagonal only.  The vertex index is the time index: the
+ *               row of a cloud, point i of a Takens window (with subsample = s one step is s samples).
+ *   Lines.      A diagonal line of length l is a maximal run R[i+m][j+m] = 1, m = 0..l-1, on one diagonal j - i = const,
+ *               counted over the whole matrix: both triangles contribute, every line above the diagonal has its mirror
+ *               below.  A vertical line is a maximal run of consecutive i with R[i][j] = 1 in one column j; the zero band
+ *               interrupts it.  HD(l), HV(l): the numbers of such lines of length exactly l >= 1.
+ *   counts      (n_win, TDA_RQA_ROWS, n_grid) int32, the rows
+ *                 0 recurrences   sum R                                                        (at most 128 * 127)
+ *                 1 diag_lines    sum_{l >= l_min} HD(l)
+ *                 2 diag_points   sum_{l >= l_min} l HD(l)
+ *                 3 diag_longest  largest l with HD(l) > 0, whatever l_min; 0 without one
+ *                 4 vert_lines    sum_{l >= v_min} HV(l)
+ *                 5 vert_points   sum_{l >= v_min} l HV(l)
+ *                 6 vert_longest  largest l with HV(l) > 0, whatever v_min; 0 without one
+ *   measures    (n_win, TDA_RQA_MEASURES, n_grid) float64.  Each value is a function of the integers in one order of IEEE
+ *               operations (no contraction):
+ *                 0 recurrence_rate  N ? (double)recurrences / (double)N : 0.0, N = theiler <= n ?
+ *                                    (n - theiler)(n - theiler + 1) : 0, the ordered pairs outside the band
+ *                 1 determinism      recurrences ? (double)diag_points / (double)recurrences : 0.0
+ *                 2 diag_mean        diag_lines ? (double)diag_points / (double)diag_lines : 0.0
+ *                 3 diag_entropy     S = 0.0; for l = l_min, l_min + 1, ... ascending with HD(l) > 0:
+ *                                    p = (double)HD(l) / (double)diag_lines; S = S - p * log(p).  The value is S; 0.0
+ *                                    without lines
+ *                 4 laminarity       recurrences ? (double)vert_points / (double)recurrences : 0.0
+ *                 5 trapping_time    vert_lines ? (double)vert_points / (double)vert_lines : 0.0
+ *                 6 vert_entropy     as row 3, with HV, v_min and vert_lines
+ *   hist        (nullable) (n_win, 2, n_grid, n_hist) int32, n_hist = n (matrices), p_cap (clouds), TDA_MAX_POINTS
+ *               (Takens): the `nodal` convention of the network curves.  hist[., 0, ., l - 1] = HD(l),
+ *               hist[., 1, ., l - 1] = HV(l); zeros past the window's own n.  A NULL hist changes no byte of the other
+ *               outputs.
+ *   status, n_points  as the Euler entry points.  A refused window (TDA_WIN_DEGENERATE, TDA_WIN_TOO_LARGE, tau < 1) has
+ *               all-zero blocks, 0.0 in measures.
+ *   Means.      tda_recurrence_mean: mean_counts (n_seg, TDA_RQA_ROWS, n_grid), mean_measures (n_seg, TDA_RQA_MEASURES,
+ *               n_grid), mean_hist (n_seg, 2, n_grid, n_hist), all float64; each input is nullable together with its
+ *               mean.  The rules are those of tda_network_mean: groups, status_in, skip_mask and seg_off = NULL as there;
+ *               the integer blocks (double)S / (double)m with S the exact int64 sum of the m kept windows; measures
+ *               S = 0.0, then S += the kept windows' values in ascending window order, S / (double)m.  m = 0 gives NaN.
+ *   Limits.     Those of the Euler entry points, without max_dim; theiler, l_min and v_min in [1, TDA_MAX_POINTS]; for the
+ *               means those of tda_network_mean with n_hist for n_node.  Anything else: TDA_ERR_INVALID with a message in
+ *               tda_last_error; nothing is launched or written.
+ *   Determinism.  Everything but rows 3 and 6 of measures is bytes; those two agree with the written sum to the rounding
+ *               of log (DESIGN.md 3.25 has the measured bar), and a histogram with a single non-zero bin gives exactly
+ *               0.0.  A window alone and inside a batch give the same bytes.  No atomics, no polls.  Every loop is bounded
+ *               before it starts by n, n_grid, n_hist or a popcount.
+ * The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage every buffer. */
+#define TDA_RQA_ROWS     7
+#define TDA_RQA_MEASURES 7
+tda_status tda_recurrence_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                       const double* grid, int n_grid, int theiler, int l_min, int v_min, int* counts,
+                                       double* measures, int* hist, int* status, void* stream);
+tda_status tda_recurrence_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                   const double* grid, int n_grid, int theiler, int l_min, int v_min, int* counts,
+                                   double* measures, int* hist, int* status);
+tda_status tda_recurrence_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                          int normalise, double thresh, const double* grid, int n_grid, int theiler,
+                                          int l_min, int v_min, int* counts, double* measures, int* hist, int* status,
+                                          void* stream);
+tda_status tda_recurrence_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                      int normalise, double thresh, const double* grid, int n_grid, int theiler, int l_min,
+                                      int v_min, int* counts, double* measures, int* hist, int* status);
+tda_status tda_recurrence_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                           int subsample, double thresh, const double* grid, int n_grid, int theiler,
+                                           int l_min, int v_min, int* counts, double* measures, int* hist, int* n_points,
+                                           int* status, void* stream);
+tda_status tda_recurrence_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                       int subsample, double thresh, const double* grid, int n_grid, int theiler, int l_min,
+                                       int v_min, int* counts, double* measures, int* hist, int* n_points, int* status);
+tda_status tda_recurrence_mean_dev(tda_ctx* ctx, const int* counts, const double* measures, const int* hist, int n_win,
+                                   int n_grid, int n_hist, const int* seg_off, int n_seg, const int* status_in,
+                                   int skip_mask, double* mean_counts, double* mean_measures, double* mean_hist,
+                                   void* stream);
+tda_status tda_recurrence_mean(tda_ctx* ctx, const int* counts, const double* measures, const int* hist, int n_win,
+                               int n_grid, int n_hist, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                               double* mean_counts, double* mean_measures, double* mean_hist);
+
 /* ---- Generators and representative cycles of Rips persistence pairs ---------------------
  * Which simplices stand behind a row of a diagram, and a cycle that represents every H1 row: the counterpart of
  * ripser(..., do_cocycles=True) and of GUDHI's flag_persistence_generators, for the question "which channels carry the

@@ -39,6 +39,11 @@ NET_COUNT_NAMES = ("edges", "isolated", "max_degree", "wedges", "triangles", "co
                    "diameter")
 NET_MEASURE_NAMES = ("transitivity", "clustering", "efficiency", "path_length")
 NET_NODAL_NAMES = ("degree", "triangles", "reach", "farness", "eccentricity")
+RQA_ROWS = 7                # TDA_RQA_ROWS: integer rows of the recurrence curves (include/tdaeeg.h, "Recurrence curves")
+RQA_MEASURES = 7            # TDA_RQA_MEASURES: their float64 rows
+RQA_COUNT_NAMES = ("recurrences", "diag_lines", "diag_points", "diag_longest", "vert_lines", "vert_points", "vert_longest")
+RQA_MEASURE_NAMES = ("recurrence_rate", "determinism", "diag_mean", "diag_entropy", "laminarity", "trapping_time",
+                     "vert_entropy")
 TDA_GEN_BIRTH_TIED = 1       # tda_generators_*: flags of an H1 row (include/tdaeeg.h)
 TDA_GEN_DEATH_TIED = 2
 TDA_GEN_CYCLE_TRUNCATED = 4
@@ -89,6 +94,8 @@ _I, _D = C.c_int, C.c_double
 # the row inputs and outputs the tda_generators_* entry points share: h0, h0_cap, h0_cnt, h1, h1_cap, h1_cnt, rips_status,
 # skip_mask, cyc_cap, h1_gen, h1_flag, cyc, cyc_len, part, h0_edge, work
 _GEN = [c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+# theiler, l_min, v_min and the outputs counts, measures, hist of the tda_recurrence_* entry points
+_RQ = [_I, _I, _I, c_vp, c_vp, c_vp]
 SYMBOLS = {
     "tda_version": (_I, []),
     "tda_ctx_create": (_I, [_I, C.POINTER(c_vp)]),
@@ -190,6 +197,14 @@ SYMBOLS = {
     "tda_network_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_network_mean_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "tda_network_mean": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp]),
+    "tda_recurrence_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I] + _RQ + [c_vp, c_vp]),
+    "tda_recurrence_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I, c_vp, _I] + _RQ + [c_vp]),
+    "tda_recurrence_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I] + _RQ + [c_vp, c_vp]),
+    "tda_recurrence_cloud_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I] + _RQ + [c_vp]),
+    "tda_recurrence_takens_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I] + _RQ + [c_vp, c_vp, c_vp]),
+    "tda_recurrence_takens_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, c_vp, _I] + _RQ + [c_vp, c_vp]),
+    "tda_recurrence_mean_dev": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_recurrence_mean": (_I, [c_vp, c_vp, c_vp, c_vp, _I, _I, _I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp]),
     "tda_generators_dm_batch_dev": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp, c_vp]),
     "tda_generators_dm_batch": (_I, [c_vp, c_vp, _I, _I, _D, _I] + _GEN + [c_vp]),
     "tda_generators_cloud_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D] + _GEN + [c_vp, c_vp]),

@@ -756,6 +756,49 @@ tda_status tda_network_mean_dev(tda_ctx* ctx, const int* counts, const double* m
                                mean_counts, mean_measures, mean_nodal, (hipStream_t)stream);
 }
 
+// the parameters that the tda_recurrence_* entry points share behind the grid, in the header's order
+#define RQ_PARAMS int theiler, int l_min, int v_min, int* counts, double* measures, int* hist
+#define RQ_ARGS theiler, l_min, v_min, counts, measures, hist
+
+tda_status tda_recurrence_dm_batch_dev(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                       const double* grid, int n_grid, RQ_PARAMS, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, dm); NET_CHECK_PTRS(ctx); }
+    return launch_recurrence(ctx, WinSrc{dm, nullptr, n, 0, 1, 2, symmetrise, 0}, n_win, thresh, grid, n_grid, RQ_ARGS, nullptr,
+                             status, (hipStream_t)stream);
+}
+
+tda_status tda_recurrence_cloud_batch_dev(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                          int normalise, double thresh, const double* grid, int n_grid, RQ_PARAMS,
+                                          int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); NET_CHECK_PTRS(ctx); }
+    return launch_recurrence(ctx, WinSrc{pc, n_pts, p_cap, dim, 1, 1, normalise, 0}, n_win, thresh, grid, n_grid, RQ_ARGS,
+                             nullptr, status, (hipStream_t)stream);
+}
+
+tda_status tda_recurrence_takens_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                           int subsample, double thresh, const double* grid, int n_grid, RQ_PARAMS,
+                                           int* n_points, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); NET_CHECK_PTRS(ctx); }
+    return launch_recurrence(ctx, WinSrc{win, tau, n_t, dim, subsample, 0, 1, 0}, n_win, thresh, grid, n_grid, RQ_ARGS,
+                             n_points, status, (hipStream_t)stream);
+}
+
+tda_status tda_recurrence_mean_dev(tda_ctx* ctx, const int* counts, const double* measures, const int* hist, int n_win,
+                                   int n_grid, int n_hist, const int* seg_off, int n_seg, const int* status_in,
+                                   int skip_mask, double* mean_counts, double* mean_measures, double* mean_hist,
+                                   void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    return launch_recurrence_mean(ctx, counts, measures, hist, n_win, n_grid, n_hist, seg_off, n_seg, status_in, skip_mask,
+                                  mean_counts, mean_measures, mean_hist, (hipStream_t)stream);
+}
+
 // the row inputs and the outputs that the tda_generators_* entry points share, in the header's order
 #define GEN_PARAMS                                                                                                     \
     const double* h0, int h0_cap, const int* h0_cnt, const double* h1, int h1_cap, const int* h1_cnt,                  \
@@ -1742,6 +1785,96 @@ tda_status tda_network_mean(tda_ctx* ctx, const int* counts, const double* measu
     return s.run([&] {
         return tda_network_mean_dev(ctx, d_cnt, d_mea, d_nod, n_win, n_grid, n_node, g.off, n_seg, g.status, skip_mask, d_mc,
                                     d_mm, d_mn, nullptr);
+    });
+}
+
+namespace {
+// the device twins of the outputs of a tda_recurrence_* host call; n_hist: the columns of hist
+struct RqStage {
+    Dev<double> grid, measures;
+    Dev<int> counts, hist, status;
+    RqStage(Stage& s, size_t nw, const double* grid, int n_grid, int n_hist, int* counts, double* measures, int* hist, int* status)
+        : grid(s.in(grid, (size_t)n_grid)), measures(s.out(measures, nw * TDA_RQA_MEASURES * n_grid)),
+          counts(s.out(counts, nw * TDA_RQA_ROWS * n_grid)), hist(s.out(hist, nw * 2 * n_grid * n_hist)),
+          status(s.out(status, nw)) {}
+};
+}   // namespace
+
+tda_status tda_recurrence_dm_batch(tda_ctx* ctx, const double* dm, int n_win, int n, double thresh, int symmetrise,
+                                   const double* grid, int n_grid, RQ_PARAMS, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 2, n, 0, 1, nullptr, nullptr));
+    TDA_TRY(rq_check(ctx, n_grid, theiler, l_min, v_min));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, dm); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_dm = s.in(dm, (size_t)n_win * n * n);
+    const RqStage d(s, (size_t)n_win, grid, n_grid, n, counts, measures, hist, status);
+    return s.run([&] {
+        return tda_recurrence_dm_batch_dev(ctx, d_dm, n_win, n, thresh, symmetrise, d.grid, n_grid, theiler, l_min, v_min,
+                                           d.counts, d.measures, d.hist, d.status, nullptr);
+    });
+}
+
+tda_status tda_recurrence_cloud_batch(tda_ctx* ctx, const double* pc, const int* n_pts, int n_win, int p_cap, int dim,
+                                      int normalise, double thresh, const double* grid, int n_grid, RQ_PARAMS, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 1, p_cap, dim, 1, nullptr, nullptr));
+    TDA_TRY(rq_check(ctx, n_grid, theiler, l_min, v_min));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, pc); CHECK_PTR(ctx, n_pts); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_pc = s.in(pc, (size_t)n_win * p_cap * dim);
+    auto d_n = s.in(n_pts, (size_t)n_win);
+    const RqStage d(s, (size_t)n_win, grid, n_grid, p_cap, counts, measures, hist, status);
+    return s.run([&] {
+        return tda_recurrence_cloud_batch_dev(ctx, d_pc, d_n, n_win, p_cap, dim, normalise, thresh, d.grid, n_grid, theiler,
+                                              l_min, v_min, d.counts, d.measures, d.hist, d.status, nullptr);
+    });
+}
+
+tda_status tda_recurrence_takens_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int dim,
+                                       int subsample, double thresh, const double* grid, int n_grid, RQ_PARAMS,
+                                       int* n_points, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(win_src_limits(ctx, 0, n_t, dim, subsample, nullptr, nullptr));
+    TDA_TRY(rq_check(ctx, n_grid, theiler, l_min, v_min));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); NET_CHECK_PTRS(ctx);
+    Stage s(ctx);
+    auto d_win = s.in(win, (size_t)n_win * n_t);
+    auto d_tau = s.in(tau, (size_t)n_win);
+    const RqStage d(s, (size_t)n_win, grid, n_grid, TDA_MAX_POINTS, counts, measures, hist, status);
+    auto d_np = s.out(n_points, (size_t)n_win);
+    return s.run([&] {
+        return tda_recurrence_takens_batch_dev(ctx, d_win, d_tau, n_win, n_t, dim, subsample, thresh, d.grid, n_grid, theiler,
+                                               l_min, v_min, d.counts, d.measures, d.hist, d_np, d.status, nullptr);
+    });
+}
+
+tda_status tda_recurrence_mean(tda_ctx* ctx, const int* counts, const double* measures, const int* hist, int n_win,
+                               int n_grid, int n_hist, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                               double* mean_counts, double* mean_measures, double* mean_hist)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win); CHECK_NONNEG(ctx, n_seg);
+    TDA_TRY(rq_mean_check(ctx, counts, measures, hist, n_win, n_grid, n_hist, seg_off, n_seg, mean_counts, mean_measures,
+                          mean_hist));
+    if (n_seg == 0) return TDA_OK;
+    Stage s(ctx);
+    const size_t ng = (size_t)n_grid, nh = hist || mean_hist ? (size_t)n_hist : 0;
+    auto d_cnt = s.in(counts, (size_t)n_win * TDA_RQA_ROWS * ng);
+    auto d_mea = s.in(measures, (size_t)n_win * TDA_RQA_MEASURES * ng);
+    auto d_his = s.in(hist, (size_t)n_win * 2 * ng * nh);
+    const GroupIn g = group_in(s, seg_off, n_seg, status_in, (size_t)n_win);
+    auto d_mc = s.out(mean_counts, (size_t)n_seg * TDA_RQA_ROWS * ng);
+    auto d_mm = s.out(mean_measures, (size_t)n_seg * TDA_RQA_MEASURES * ng);
+    auto d_mh = s.out(mean_hist, (size_t)n_seg * 2 * ng * nh);
+    return s.run([&] {
+        return tda_recurrence_mean_dev(ctx, d_cnt, d_mea, d_his, n_win, n_grid, n_hist, g.off, n_seg, g.status, skip_mask, d_mc,
+                                       d_mm, d_mh, nullptr);
     });
 }
 

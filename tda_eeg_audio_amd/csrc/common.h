@@ -267,6 +267,19 @@ tda_status nt_mean_check(tda_ctx*, const void* counts, const void* measures, con
 tda_status launch_network_mean(tda_ctx*, const int* counts, const double* measures, const int* nodal, int n_win, int n_grid,
                                int n_node, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
                                double* mean_counts, double* mean_measures, double* mean_nodal, hipStream_t);
+// (recurrence.hip) recurrence quantification of the same windows on a grid: the plot is the adjacency matrix in time order
+// without a Theiler band.  Checks the limits of the header itself: rq_check (grid, theiler, l_min, v_min), then
+// win_src_limits; rq_mean_check for the means, as nt_mean_check.
+tda_status rq_check(tda_ctx*, int n_grid, int theiler, int l_min, int v_min);
+tda_status launch_recurrence(tda_ctx*, const WinSrc& src, int n_win, double thresh, const double* grid, int n_grid, int theiler,
+                             int l_min, int v_min, int* counts, double* measures, int* hist, int* n_points, int* status,
+                             hipStream_t);
+tda_status rq_mean_check(tda_ctx*, const void* counts, const void* measures, const void* hist, int n_win, int n_grid,
+                         int n_hist, const int* seg_off, int n_seg, const void* mean_counts, const void* mean_measures,
+                         const void* mean_hist);
+tda_status launch_recurrence_mean(tda_ctx*, const int* counts, const double* measures, const int* hist, int n_win, int n_grid,
+                                  int n_hist, const int* seg_off, int n_seg, const int* status_in, int skip_mask,
+                                  double* mean_counts, double* mean_measures, double* mean_hist, hipStream_t);
 // (generators.hip) the edges behind the rows of a Rips diagram and a representative cycle per H1 row.  GenArgs: the rows the
 // Rips entry points wrote and the outputs, as the tda_generators_* entry points take them (part_ld is the launcher's).
 struct GenArgs {

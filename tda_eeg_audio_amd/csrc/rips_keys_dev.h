@@ -1,7 +1,7 @@
 // rips_keys_dev.h -- the float32 edge keys of a window, stated once: which points a window has, how a pair of them gets its
 // key, and where the keys lie.  Every consumer of a Rips complex reads the rules here: the Rips kernels themselves
 // (csrc/rips.hip), the Euler curves (csrc/euler.hip), the generators (csrc/generators.hip), the network curves
-// (csrc/network.hip) and the landmark selection (csrc/landmarks.hip, the point count only).  The keys are the bytes of the reference or they are wrong, so a rule is
+// (csrc/network.hip), the recurrence curves (csrc/recurrence.hip) and the landmark selection (csrc/landmarks.hip, the point count only).  The keys are the bytes of the reference or they are wrong, so a rule is
 // changed here or nowhere.
 //
 // What csrc/rips.hip still keeps to itself: the staging inside rips_cloud_window (its LDS layout is shared with the ranking

@@ -311,6 +311,56 @@ def connectivity_network_curves_from_windows(win_list, measure, grid, method="eu
     return _network_group_means(net)
 
 
+def recurrence_curves_from_windows(win_list, tau_list, grid, theiler=1, l_min=2, v_min=2, histograms=False, dim=TAKENS_DIM,
+                                   subsample=TAKENS_SUBSAMPLE, thresh=MAX_EDGE_LENGTH):
+    """win_list: list of (k_i, n_t) arrays of signal windows, one per (recording, band) group; tau_list: per group one
+    delay (the reference's one tau per recording and band) or k_i delays, one per window.  Per group the mean over its
+    windows of the recurrence curves on `grid` of the window's delay embedding (include/tdaeeg.h, "Recurrence curves";
+    engine.recurrence_takens_dev): (len(win_list), RQA_ROWS + RQA_MEASURES, n_grid) float64, the integer rows
+    (_lib.RQA_COUNT_NAMES) and then the measures (_lib.RQA_MEASURE_NAMES), the columns named by recurrence_names.
+    histograms=True: (means, hist_means), the second (len(win_list), 2, n_grid, 128) float64, diagonal then vertical line
+    lengths.  All on the device: embedding, keys, curves, means.  A window the kernel refuses (fewer than 3 or more than 128
+    points, tau < 1) is left out of its group's mean, as the reference skips a cloud of fewer than 3 points; a group
+    without a kept window is NaN.  ValueError for a bad grid, theiler, l_min, v_min or tau_list."""
+    import torch
+    from . import _lib
+    grid, theiler, l_min, v_min = engine.recurrence_args(grid, theiler, l_min, v_min)
+    if len(tau_list) != len(win_list):
+        raise ValueError("tau_list: one entry per group")
+    sizes = np.array([len(w) for w in win_list])
+    taus = []
+    for k, tau in zip(sizes, tau_list):
+        tau = np.asarray(tau)
+        if tau.ndim > 1 or (tau.ndim == 1 and tau.shape[0] != k) or not np.issubdtype(tau.dtype, np.integer):
+            raise ValueError("tau_list: per group one integer delay or one per window")
+        taus.append(np.broadcast_to(tau, (k,)).astype(np.int32))
+    n_rows = _lib.RQA_ROWS + _lib.RQA_MEASURES
+    if sizes.sum() == 0:
+        means = np.full((len(win_list), n_rows, grid.shape[0]), np.nan)
+        return (means, np.full((len(win_list), 2, grid.shape[0], _lib.MAX_POINTS), np.nan)) if histograms else means
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    seg_t = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    allw = np.concatenate([np.asarray(w, dtype=np.float64) for w in win_list if len(w)], axis=0)
+    if allw.ndim != 2:
+        raise ValueError("win_list: (k_i, n_t) arrays")
+    rq = engine.recurrence_takens_dev(torch.from_numpy(np.ascontiguousarray(allw)).to(dev),
+                                      torch.from_numpy(np.concatenate(taus)).to(dev), torch.from_numpy(grid).to(dev), theiler,
+                                      l_min, v_min, histograms, dim, subsample, thresh, seg_off_t=seg_t, skip_mask=4 | 16,
+                                      ctx=ctx)
+    means = torch.cat([rq.mean_counts, rq.mean_measures], dim=1).cpu().numpy()
+    return (means, rq.mean_hist.cpu().numpy()) if histograms else means
+
+
+def recurrence_names(bands=BANDS, grid=None):
+    """Column names of recurrence_curves_from_windows(...)[r] of every band, flattened band by band: per band the integer
+    rows and then the measures, each at every grid point in order."""
+    from . import _lib
+    n_grid = 64 if grid is None else len(grid)
+    return [f"{band}_{row}_t{j}" for band in bands for row in _lib.RQA_COUNT_NAMES + _lib.RQA_MEASURE_NAMES
+            for j in range(n_grid)]
+
+
 def channel_participation_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     that finds the birth edge and a representative cycle of every H1 row and one that writes the group means

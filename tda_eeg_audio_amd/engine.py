@@ -18,6 +18,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  complex on a grid of scales, by the keys of the Rips entry points)
                  network_dm_batch, network_cloud_batch, network_takens_batch (the graph measures of the thresholded graphs on
                  a grid of scales, by the same keys and presence rule; network_args)
+                 recurrence_dm_batch, recurrence_cloud_batch, recurrence_takens_batch (recurrence quantification of the
+                 windows in time order on a grid of scales, by the same keys and presence rule; recurrence_args)
                  generators_dm_batch, generators_cloud_batch, generators_takens_batch (the edges behind the rows of the
                  diagrams, a representative cycle per H1 row and the participation of every vertex; generators_args)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
@@ -44,6 +46,9 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  network_dm_dev / network_cloud_dev / network_takens_dev / network_mean_dev / network_eeg_windows_dev:
                  the network curves of resident windows and their group means, into a DeviceNetworkCurves
                  (utils.compute_eeg_network_curves, drivers.network_curves_from_distances).
+                 recurrence_dm_dev / recurrence_cloud_dev / recurrence_takens_dev / recurrence_mean_dev: the recurrence
+                 curves of resident windows and their group means, into a DeviceRecurrenceCurves
+                 (utils.compute_signal_recurrence_curves, drivers.recurrence_curves_from_windows).
                  generators_dm_dev / generators_cloud_dev / generators_takens_dev / generators_mean_dev /
                  generators_eeg_windows_dev: generators and cycles of resident windows from a DeviceDiagrams or raw row
                  tensors, into a DeviceGenerators (utils.compute_eeg_generators,
@@ -667,6 +672,77 @@ def network_takens_batch(windows, taus, grid, nodal=False, dim=3, subsample=2, t
                                                ptr(grid), grid.shape[0], ptr(cnt), ptr(mea), ptr(nod),
                                                ptr(npts), ptr(st)))
     return cnt, mea, nod, npts, st
+
+
+def recurrence_args(grid, theiler=1, l_min=2, v_min=2):
+    """The parameters of the recurrence curves as the kernel takes them (include/tdaeeg.h, "Recurrence curves"): (grid,
+    theiler, l_min, v_min) with grid as network_args takes it and the three others ints in 1..MAX_POINTS.  ValueError,
+    before any GPU call, for anything else."""
+    grid = network_args(grid)
+    out = []
+    for name, v in (("theiler", theiler), ("l_min", l_min), ("v_min", v_min)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= _lib.MAX_POINTS:
+            raise ValueError(f"{name} must be an integer in 1..{_lib.MAX_POINTS}, not {v!r}")
+        out.append(int(v))
+    return (grid,) + tuple(out)
+
+
+def _recurrence_host(n_win, n_grid, n_hist, hist):
+    """The zeroed host outputs of the recurrence_*_batch forms: counts, measures, hist (or None), status."""
+    return (np.zeros((n_win, _lib.RQA_ROWS, n_grid), np.int32), np.zeros((n_win, _lib.RQA_MEASURES, n_grid), np.float64),
+            np.zeros((n_win, 2, n_grid, n_hist), np.int32) if hist else None, np.zeros(n_win, np.int32))
+
+
+def recurrence_dm_batch(dms, grid, theiler=1, l_min=2, v_min=2, hist=False, thresh=MAX_EDGE_LENGTH, symmetrise=True,
+                        ctx=None):
+    """Recurrence quantification of every distance matrix at every scale of grid (include/tdaeeg.h, "Recurrence curves"):
+    dms (n_win, n, n) float64, the vertices in time order -> (counts (n_win, RQA_ROWS, n_grid) int32, measures (n_win,
+    RQA_MEASURES, n_grid) float64, hist (n_win, 2, n_grid, n) int32 or None, status).  The rows are named by
+    _lib.RQA_COUNT_NAMES and RQA_MEASURE_NAMES; hist[:, 0, :, l - 1] and hist[:, 1, :, l - 1] count the diagonal and the
+    vertical lines of length l."""
+    grid, theiler, l_min, v_min = recurrence_args(grid, theiler, l_min, v_min)
+    ctx = ctx or get_ctx()
+    d = f64(dms)
+    n_win, n, n2 = d.shape
+    assert n == n2, "distance matrices must be square"
+    cnt, mea, his, st = _recurrence_host(n_win, grid.shape[0], n, hist)
+    ctx.check(ctx.lib.tda_recurrence_dm_batch(ctx.h, ptr(d), n_win, n, float(thresh), int(bool(symmetrise)), ptr(grid),
+                                              grid.shape[0], theiler, l_min, v_min, ptr(cnt), ptr(mea), ptr(his), ptr(st)))
+    return cnt, mea, his, st
+
+
+def recurrence_cloud_batch(clouds, grid, theiler=1, l_min=2, v_min=2, hist=False, n_pts=None, normalise=True,
+                           thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from explicit clouds (n_win, p_cap, dim) with n_pts rows each in time order, by the keys of
+    cloud_rips_batch; hist has p_cap columns.  A window with fewer than 3 or more than min(p_cap, MAX_POINTS) points has
+    TDA_WIN_DEGENERATE / TDA_WIN_TOO_LARGE and zeros."""
+    grid, theiler, l_min, v_min = recurrence_args(grid, theiler, l_min, v_min)
+    ctx = ctx or get_ctx()
+    pc = f64(clouds)
+    n_win, p_cap, dim = pc.shape
+    n_pts = i32(np.full(n_win, p_cap) if n_pts is None else n_pts)
+    cnt, mea, his, st = _recurrence_host(n_win, grid.shape[0], p_cap, hist)
+    ctx.check(ctx.lib.tda_recurrence_cloud_batch(ctx.h, ptr(pc), ptr(n_pts), n_win, p_cap, dim, int(bool(normalise)),
+                                                 float(thresh), ptr(grid), grid.shape[0], theiler, l_min, v_min, ptr(cnt),
+                                                 ptr(mea), ptr(his), ptr(st)))
+    return cnt, mea, his, st
+
+
+def recurrence_takens_batch(windows, taus, grid, theiler=1, l_min=2, v_min=2, hist=False, dim=3, subsample=2,
+                            thresh=MAX_EDGE_LENGTH, ctx=None):
+    """The same from signal windows (n_win, n_t) and their delays, by the keys of takens_rips_batch: (counts, measures,
+    hist with MAX_POINTS columns or None, n_points, status).  One step of a line is `subsample` samples."""
+    grid, theiler, l_min, v_min = recurrence_args(grid, theiler, l_min, v_min)
+    ctx = ctx or get_ctx()
+    w = f64(windows)
+    n_win, n_t = w.shape
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    cnt, mea, his, st = _recurrence_host(n_win, grid.shape[0], _lib.MAX_POINTS, hist)
+    npts = np.zeros(n_win, np.int32)
+    ctx.check(ctx.lib.tda_recurrence_takens_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, int(dim), int(subsample),
+                                                  float(thresh), ptr(grid), grid.shape[0], theiler, l_min, v_min, ptr(cnt),
+                                                  ptr(mea), ptr(his), ptr(npts), ptr(st)))
+    return cnt, mea, his, npts, st
 
 
 def generators_args(cyc_cap):
@@ -1883,6 +1959,132 @@ def network_eeg_windows_dev(win_t, grid_t, nodal=False, thresh=MAX_EDGE_LENGTH, 
     (optional) receives the matrices."""
     dist_t = corr_dist_dev(win_t, dist_t, ctx=ctx)
     return network_dm_dev(dist_t, grid_t, nodal, thresh, True, out, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+class DeviceRecurrenceCurves:
+    """The outputs of the recurrence_*_dev forms for a batch of windows, resident in HBM (include/tdaeeg.h, "Recurrence
+    curves"): counts (n_win, RQA_ROWS, n_grid) int32, measures (n_win, RQA_MEASURES, n_grid) float64, status (n_win,) int32
+    and, when asked for, hist (n_win, 2, n_grid, n_hist) int32; mean_counts, mean_measures and mean_hist (float64, a row
+    per group) are set by the group-mean launches."""
+
+    def __init__(self, n_win, n_grid, n_hist, device, hist=False):
+        import torch
+        kw = dict(device=device)
+        self.counts = torch.empty((n_win, _lib.RQA_ROWS, n_grid), dtype=torch.int32, **kw)
+        self.measures = torch.empty((n_win, _lib.RQA_MEASURES, n_grid), dtype=torch.float64, **kw)
+        self.hist = torch.empty((n_win, 2, n_grid, n_hist), dtype=torch.int32, **kw) if hist else None
+        self.status = torch.empty(n_win, dtype=torch.int32, **kw)
+        self.mean_counts = self.mean_measures = self.mean_hist = None
+        self.n_win, self.n_grid, self.n_hist = n_win, n_grid, n_hist
+
+    def to_host(self):
+        """The same arrays as numpy, in a dict."""
+        return {k: getattr(self, k).cpu().numpy() for k in ("counts", "measures", "hist", "status", "mean_counts",
+                                                            "mean_measures", "mean_hist") if getattr(self, k) is not None}
+
+
+def recurrence_mean_dev(counts_t, measures_t, hist_t, n_win, n_grid, n_hist, seg_off_t=None, status_in=None, skip_mask=0,
+                        mean_counts_t=None, mean_measures_t=None, mean_hist_t=None, ctx=None):
+    """Group means of the blocks of recurrence_*_dev (include/tdaeeg.h), by the rules of network_mean_dev: each of
+    counts_t, measures_t, hist_t may be None and then has no mean.  Returns (mean_counts, mean_measures, mean_hist),
+    float64 with a row per group; up to three launches on torch's current stream, nothing allocated when the means are
+    given."""
+    import torch
+    ctx = ctx or get_ctx()
+    n_win, n_grid, n_hist = int(n_win), int(n_grid), int(n_hist)
+    n_seg = n_win if seg_off_t is None else seg_off_t.numel() - 1
+    shapes = ((_lib.RQA_ROWS, max(n_grid, 0)), (_lib.RQA_MEASURES, max(n_grid, 0)), (2, max(n_grid, 0), max(n_hist, 0)))
+    ins, means = [counts_t, measures_t, hist_t], [mean_counts_t, mean_measures_t, mean_hist_t]
+    for k, (t, dt) in enumerate(zip(ins, (torch.int32, torch.float64, torch.int32))):
+        if t is None:
+            continue
+        assert t.dtype == dt and t.is_contiguous()
+        if means[k] is None:
+            means[k] = torch.empty((n_seg,) + shapes[k], dtype=torch.float64, device=t.device)
+        assert means[k].dtype == torch.float64 and means[k].is_contiguous()
+    ctx.check(ctx.lib.tda_recurrence_mean_dev(ctx.h, _tp(counts_t), _tp(measures_t), _tp(hist_t), n_win, n_grid, n_hist,
+                                              _tp(seg_off_t), n_seg, _tp(status_in), int(skip_mask), _tp(means[0]),
+                                              _tp(means[1]), _tp(means[2]), _stream()))
+    return tuple(means)
+
+
+def _recurrence_dev(grid_t, theiler, l_min, v_min, n_win, n_hist, hist, out, device):
+    """Checks of the recurrence_*_dev forms: grid_t a contiguous 1-D float64 device tensor of 1..MAX_GRID scales, the three
+    ints as recurrence_args takes them; out is allocated when None (it may be larger than the batch: the tail is not
+    touched)."""
+    import torch
+    if not (grid_t.is_cuda and grid_t.dtype == torch.float64 and grid_t.dim() == 1 and grid_t.is_contiguous()):
+        raise ValueError("grid_t: a contiguous 1-D float64 device tensor")
+    n_grid = int(grid_t.numel())
+    if not 1 <= n_grid <= _lib.MAX_GRID:
+        raise ValueError(f"grid_t: 1..{_lib.MAX_GRID} scales")
+    _, theiler, l_min, v_min = recurrence_args(np.zeros(1), theiler, l_min, v_min)
+    if out is None:
+        out = DeviceRecurrenceCurves(n_win, n_grid, n_hist, device, hist)
+    assert out.n_win >= n_win and (out.n_grid, out.n_hist) == (n_grid, n_hist)
+    assert not hist or out.hist is not None, "hist=True needs an out with a hist tensor"
+    return n_grid, (theiler, l_min, v_min), out
+
+
+def _recurrence_dev_mean(out, n_win, hist, mean, seg_off_t, status_in, skip_mask, ctx):
+    """The optional group-mean launches of the recurrence_*_dev forms: asked for by mean=True or by seg_off_t.  status_in
+    defaults to the status words the first launch has just written."""
+    if mean or seg_off_t is not None:
+        out.mean_counts, out.mean_measures, out.mean_hist = recurrence_mean_dev(
+            out.counts, out.measures, out.hist if hist else None, n_win, out.n_grid, out.n_hist, seg_off_t,
+            out.status if status_in is None else status_in, skip_mask, out.mean_counts, out.mean_measures,
+            out.mean_hist if hist else None, ctx)
+    return out
+
+
+def recurrence_dm_dev(dm_t, grid_t, theiler=1, l_min=2, v_min=2, hist=False, thresh=MAX_EDGE_LENGTH, symmetrise=True,
+                      out=None, mean=False, seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """recurrence_dm_batch on device tensors: dm_t (n_win, n, n) float64, grid_t (n_grid,) float64 -> a
+    DeviceRecurrenceCurves.  One launch on torch's current stream (up to three more with the group means), nothing
+    allocated when out is given."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert dm_t.is_cuda and dm_t.dtype == torch.float64 and dm_t.is_contiguous()
+    n_win, n, n2 = dm_t.shape
+    assert n == n2, "distance matrices must be square"
+    n_grid, par, out = _recurrence_dev(grid_t, theiler, l_min, v_min, n_win, n, hist, out, dm_t.device)
+    ctx.check(ctx.lib.tda_recurrence_dm_batch_dev(ctx.h, _tp(dm_t), n_win, n, float(thresh), int(bool(symmetrise)),
+                                                  _tp(grid_t), n_grid, *par, _tp(out.counts), _tp(out.measures),
+                                                  _tp(out.hist if hist else None), _tp(out.status), _stream()))
+    return _recurrence_dev_mean(out, n_win, hist, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+def recurrence_cloud_dev(pc_t, n_pts_t, grid_t, theiler=1, l_min=2, v_min=2, hist=False, normalise=True,
+                         thresh=MAX_EDGE_LENGTH, out=None, mean=False, seg_off_t=None, status_in=None, skip_mask=0, ctx=None):
+    """recurrence_cloud_batch on device tensors: pc_t (n_win, p_cap, dim) float64, n_pts_t (n_win,) int32."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert pc_t.is_cuda and pc_t.dtype == torch.float64 and pc_t.is_contiguous() and n_pts_t.dtype == torch.int32
+    n_win, p_cap, dim = pc_t.shape
+    n_grid, par, out = _recurrence_dev(grid_t, theiler, l_min, v_min, n_win, p_cap, hist, out, pc_t.device)
+    ctx.check(ctx.lib.tda_recurrence_cloud_batch_dev(ctx.h, _tp(pc_t), _tp(n_pts_t), n_win, p_cap, dim, int(bool(normalise)),
+                                                     float(thresh), _tp(grid_t), n_grid, *par, _tp(out.counts),
+                                                     _tp(out.measures), _tp(out.hist if hist else None), _tp(out.status),
+                                                     _stream()))
+    return _recurrence_dev_mean(out, n_win, hist, mean, seg_off_t, status_in, skip_mask, ctx)
+
+
+def recurrence_takens_dev(win_t, tau_t, grid_t, theiler=1, l_min=2, v_min=2, hist=False, dim=3, subsample=2,
+                          thresh=MAX_EDGE_LENGTH, out=None, n_points_t=None, mean=False, seg_off_t=None, status_in=None,
+                          skip_mask=0, ctx=None):
+    """recurrence_takens_batch on device tensors: win_t (n_win, n_t) float64, tau_t (n_win,) int32; n_points_t (optional,
+    int32) receives the points per window.  hist has MAX_POINTS columns."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous()
+    assert tau_t.dtype == torch.int32 and tau_t.is_cuda
+    n_win, n_t = win_t.shape
+    n_grid, par, out = _recurrence_dev(grid_t, theiler, l_min, v_min, n_win, _lib.MAX_POINTS, hist, out, win_t.device)
+    ctx.check(ctx.lib.tda_recurrence_takens_batch_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, int(dim), int(subsample),
+                                                      float(thresh), _tp(grid_t), n_grid, *par, _tp(out.counts),
+                                                      _tp(out.measures), _tp(out.hist if hist else None), _tp(n_points_t),
+                                                      _tp(out.status), _stream()))
+    return _recurrence_dev_mean(out, n_win, hist, mean, seg_off_t, status_in, skip_mask, ctx)
 
 
 class DeviceGenerators:

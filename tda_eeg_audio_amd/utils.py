@@ -267,6 +267,61 @@ def compute_audio_network_curves(point_cloud, grid, nodal=False, thresh=MAX_EDGE
     return _network_rows(cnt[0], mea[0], nod[0] if nodal else None)
 
 
+def _recurrence_rows(counts, measures, hist):
+    """The blocks of one window as a dict of named rows (_lib.RQA_COUNT_NAMES, RQA_MEASURE_NAMES; diag_hist and vert_hist
+    for the line-length histograms, column l - 1 for the length l)."""
+    from . import _lib
+    out = {name: counts[k] for k, name in enumerate(_lib.RQA_COUNT_NAMES)}
+    out.update({name: measures[k] for k, name in enumerate(_lib.RQA_MEASURE_NAMES)})
+    if hist is not None:
+        out.update({"diag_hist": hist[0], "vert_hist": hist[1]})
+    return out
+
+
+def compute_recurrence_curves_from_distances(distance_matrix, grid, theiler=1, l_min=2, v_min=2, histograms=False,
+                                             thresh=MAX_EDGE_LENGTH):
+    """Recurrence quantification of a distance matrix whose rows are in time order, at every scale of grid
+    (include/tdaeeg.h, "Recurrence curves"): a dict of named rows, each (n_grid,) -- the int32 counts recurrences,
+    diag_lines, diag_points, diag_longest, vert_lines, vert_points, vert_longest and the float64 measures recurrence_rate,
+    determinism, diag_mean, diag_entropy, laminarity, trapping_time, vert_entropy of the recurrence plot of the symmetrised
+    matrix, by the keys compute_eeg_persistence uses.  theiler: pairs closer than theiler steps are no recurrences;
+    l_min, v_min: the shortest diagonal / vertical line that counts.  histograms=True adds the (n_grid, n) int32 rows
+    diag_hist and vert_hist.  Not recorded by utils.batch(): it launches at once.  ValueError for a bad argument."""
+    dm = np.asarray(distance_matrix, dtype=np.float64)
+    if dm.ndim != 2 or dm.shape[0] != dm.shape[1]:
+        raise ValueError("Distance matrix is not square")
+    cnt, mea, his, _ = engine.recurrence_dm_batch(dm[None], grid, theiler, l_min, v_min, histograms, thresh, True)
+    return _recurrence_rows(cnt[0], mea[0], his[0] if histograms else None)
+
+
+def compute_audio_recurrence_curves(point_cloud, grid, theiler=1, l_min=2, v_min=2, histograms=False,
+                                    thresh=MAX_EDGE_LENGTH):
+    """The same dict for a (P, dim) point cloud whose rows are in time order (a Takens embedding), min-max normalised, by
+    the keys compute_audio_persistence uses (the histogram rows are (n_grid, P)).  A cloud of fewer than 3 points gives
+    zeros, as its diagrams are [[0, 0]]; more than 128 points are a TdaError."""
+    pc = np.asarray(point_cloud, dtype=np.float64)
+    if pc.ndim != 2 or pc.shape[0] < 1:
+        raise ValueError("compute_audio_recurrence_curves: a (P, dim) point cloud")
+    cnt, mea, his, st = engine.recurrence_cloud_batch(pc[None], grid, theiler, l_min, v_min, histograms, thresh=thresh)
+    _check_status(st[0])
+    return _recurrence_rows(cnt[0], mea[0], his[0] if histograms else None)
+
+
+def compute_signal_recurrence_curves(x, tau, grid, dim=TAKENS_DIM, subsample=TAKENS_SUBSAMPLE, theiler=1, l_min=2, v_min=2,
+                                     histograms=False, thresh=MAX_EDGE_LENGTH):
+    """The same dict for the delay embedding of a 1-D signal x with delay tau (takens_embedding(x, dim, tau, subsample),
+    gathered inside the kernel): the curves of compute_audio_recurrence_curves of that cloud.  One step of a line is
+    `subsample` samples; the histogram rows are (n_grid, 128).  Fewer than 3 points give zeros; more than 128 points or
+    tau < 1 are a TdaError."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 1 or x.shape[0] < 1:
+        raise ValueError("compute_signal_recurrence_curves: a 1-D signal")
+    cnt, mea, his, _, st = engine.recurrence_takens_batch(x[None], int(tau), grid, theiler, l_min, v_min, histograms, dim,
+                                                          subsample, thresh)
+    _check_status(st[0])
+    return _recurrence_rows(cnt[0], mea[0], his[0] if histograms else None)
+
+
 def compute_sublevel_persistence(x, return_index=False):
     """H0 of the sublevel-set (lower-star) filtration of a time series (include/tdaeeg.h, "Sublevel-set persistence of time
     series"; ripser's lower_star example on a 1-D signal): an (m, 2) array like dgms[0], every local minimum paired with
