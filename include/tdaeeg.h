@@ -329,6 +329,88 @@ tda_status tda_tau_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, in
 tda_status tda_tau_segments_dev(tda_ctx* ctx, const double* win, const int* seg_off, int n_seg, int n_t,
                                 int max_lag, int* tau_seg, int* tau_win, void* stream);
 
+/* ---- Delay and dimension selection: mutual information and false nearest neighbours ------
+ * The two parameters of a delay embedding as the nonlinear time-series literature picks them: the delay tau at the first
+ * minimum of the average mutual information of the signal with its own past (Fraser & Swinney 1986), the dimension as the
+ * smallest one at which the false nearest neighbours vanish (Kennel, Brown & Abarbanel 1992).  compute_tau above is the
+ * linear counterpart of the first; the Takens entry points take what these produce (a per-window tau, dim <= TDA_MAX_DIM).
+ * The contract is this text; tests/embedding_ref.py evaluates it twice.  Every float64 operation below is one IEEE
+ * operation, no contraction.
+ *
+ * Average mutual information: tda_ami_batch[_dev], tda_ami_segments_dev.
+ *   Inputs.     win (n_win, n_t) float64, 4 <= n_t <= TDA_AMI_MAX_SAMPLES.  max_lag < 0 means n_t / 4; max_lag is then cut
+ *               to n_t - 2.  n_bins in [2, TDA_AMI_MAX_BINS].
+ *   Bins.       lo, hi: the exact minimum and maximum of the window, w = hi - lo.
+ *               b_i = min(n_bins - 1, (int)(((x_i - lo) / w) * (double)n_bins)); a sample equal to hi lands in the last bin.
+ *   Joint counts.  For L = 0..max_lag, N = n_t - L: J_L[p][q] = #{ i in [0, N) : b_i = p, b_(i+L) = q },
+ *               r_p = sum_q J_L[p][q], s_q = sum_p J_L[p][q].
+ *   AMI, nats.  I(L) = sum over the cells with J > 0 of ((double)J / (double)N) * log((double)(J * N) / (double)(r_p * s_q)),
+ *               J = J_L[p][q]; the integer products are exact (below 2^27).
+ *   ami         (n_win, max_lag + 1) float64, the I(L), with max_lag as resolved above.
+ *   tau         (n_win) int32: the smallest L in [1, max_lag - 1] with I(L) < I(L-1) and I(L) <= I(L+1), compared on the
+ *               doubles that ami holds, so tau is a byte-exact function of the returned row; 0 without such an L.
+ *   joint       (nullable) (n_win, max_lag + 1, n_bins, n_bins) int32, the J_L.  A NULL joint changes no other byte.
+ *   status      (n_win) int32.  TDA_WIN_NOT_FINITE: a sample is not finite; ami NaN, tau 0, joint 0.
+ *               TDA_WIN_DEGENERATE: hi == lo; ami 0.0, tau 0, joint 0.  Otherwise 0.
+ *   Segments.   tda_ami_segments_dev is to tda_ami_batch_dev what tda_tau_segments_dev is to tda_tau_batch_dev: group g
+ *               takes its delay from its FIRST window (window seg_off[g] of win); tau_seg (n_seg) and, when it is given,
+ *               tau_win (n_total: every window of the group) receive it.  Where the rule gives 0 (no minimum, a refused
+ *               window) both receive compute_tau's fallback max(max_lag / 10, 1) with the resolved max_lag, so tau_win goes
+ *               straight into the Takens entry points.  An empty group has tau_seg 0.  Device pointers only.
+ *   Determinism.  joint and the bins are bytes of this text.  ami holds the rounding of log and of the sum, which the kernel
+ *               adds in one fixed order of its own (DESIGN.md 3.26 has the measured bar against the numpy statement).  A
+ *               window alone and inside a batch, and one run and the next, give the same bytes.  The only atomics are
+ *               integer additions to a wave's own histogram in LDS, which commute; no float atomics, no global atomics, no
+ *               polls; every loop is bounded before it starts by n_t, max_lag or n_bins.
+ *
+ * False nearest neighbours: tda_fnn_batch[_dev].
+ *   Inputs.     win (n_win, n_t) float64, 4 <= n_t <= TDA_FNN_MAX_SAMPLES.  tau (n_win) int32, the delay of every window.
+ *               d_max in [1, TDA_FNN_MAX_DIM], theiler in [1, n_t], r_tol > 0, a_tol > 0, frac_tol in [0, 1].
+ *   Definition, for d = 1..d_max.  M_d = n_t - d tau, the points i = 0..M_d - 1 of the d-dimensional embedding that have a
+ *               (d+1)-th coordinate.  M_d < 2: the rows of this dimension are zero (nn: -1).
+ *               D2_d(i, j): s = 0.0; for k = 0..d-1 ascending: e = x[i + k tau] - x[j + k tau]; s = s + e * e.
+ *               Neighbour j*(i): the j in [0, M_d) with |i - j| >= theiler and the smallest D2_d(i, j), ties to the smallest
+ *               j; -1 without a candidate.  With D2 = D2_d(i, j*), e = x[i + d tau] - x[j* + d tau], e2 = e * e:
+ *                 criterion 1 (distance)  D2 > 0 ? e2 > (r_tol * r_tol) * D2 : e2 > 0.0
+ *                 criterion 2 (size)      (D2 + e2) > R2, R2 = (a_tol * a_tol) * var; m: the sequential sum of the window
+ *                                         divided by (double)n_t (as tda_tau_batch takes its mean), var: the sequential
+ *                                         sum of (x - m) * (x - m) divided by (double)n_t
+ *   counts      (n_win, d_max, TDA_FNN_COLS) int32, the columns
+ *                 0 valid           points with a neighbour
+ *                 1 false_distance  of those, false by criterion 1
+ *                 2 false_size      false by criterion 2
+ *                 3 false_either    false by either
+ *   frac        (n_win, d_max) float64: valid ? (double)false_either / (double)valid : 0.0
+ *   dim         (n_win) int32: the smallest d with valid > 0 and (double)false_either <= frac_tol * (double)valid; 0
+ *               without one.
+ *   nn          (nullable) (n_win, d_max, n_t) int32: nn[., d - 1, i] = j*(i), -1 wherever there is none (i >= M_d, no
+ *               candidate, a refused window).  A NULL nn changes no other byte.
+ *   status      (n_win) int32.  TDA_WIN_NOT_FINITE: a sample is not finite.  TDA_WIN_TOO_LARGE: tau < 1, as the Takens
+ *               entry points refuse it.  TDA_WIN_DEGENERATE: M_1 < 2.  In all three counts, frac and dim are zero and nn
+ *               is -1.  Otherwise 0.
+ *   Determinism.  Every output is bytes of this text.  No atomics, no polls; every loop is bounded before it starts by n_t
+ *               or d_max.
+ *
+ * Limits.  Anything outside the ranges above is TDA_ERR_INVALID with a message in tda_last_error; nothing is launched or
+ * written.  The _dev forms only enqueue on `stream` and allocate nothing.  The host forms stage every buffer. */
+#define TDA_AMI_MAX_SAMPLES 8192
+#define TDA_AMI_MAX_BINS    32
+#define TDA_FNN_MAX_SAMPLES 2048
+#define TDA_FNN_MAX_DIM     8
+#define TDA_FNN_COLS        4
+tda_status tda_ami_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int n_bins, double* ami,
+                             int* tau, int* joint, int* status, void* stream);
+tda_status tda_ami_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int n_bins, double* ami,
+                         int* tau, int* joint, int* status);
+tda_status tda_ami_segments_dev(tda_ctx* ctx, const double* win, const int* seg_off, int n_seg, int n_t, int max_lag,
+                                int n_bins, int* tau_seg, int* tau_win, void* stream);
+tda_status tda_fnn_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int d_max, int theiler,
+                             double r_tol, double a_tol, double frac_tol, int* counts, double* frac, int* dim, int* nn,
+                             int* status, void* stream);
+tda_status tda_fnn_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int d_max, int theiler,
+                         double r_tol, double a_tol, double frac_tol, int* counts, double* frac, int* dim, int* nn,
+                         int* status);
+
 /* ---- 11 scalar features per diagram ------------------------------------------
  * replaces extract_features (scripts/utils.py:144-177) ==
  * extract_persistence_features (tda_eeg_classification_v2.py:179-250).

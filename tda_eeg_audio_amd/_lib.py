@@ -44,6 +44,12 @@ RQA_MEASURES = 7            # TDA_RQA_MEASURES: their float64 rows
 RQA_COUNT_NAMES = ("recurrences", "diag_lines", "diag_points", "diag_longest", "vert_lines", "vert_points", "vert_longest")
 RQA_MEASURE_NAMES = ("recurrence_rate", "determinism", "diag_mean", "diag_entropy", "laminarity", "trapping_time",
                      "vert_entropy")
+AMI_MAX_SAMPLES = 8192      # TDA_AMI_MAX_SAMPLES: longest window of the average mutual information (include/tdaeeg.h,
+AMI_MAX_BINS = 32           # TDA_AMI_MAX_BINS           "Delay and dimension selection")
+FNN_MAX_SAMPLES = 2048      # TDA_FNN_MAX_SAMPLES: longest window of the false nearest neighbours
+FNN_MAX_DIM = 8             # TDA_FNN_MAX_DIM: highest dimension they test
+FNN_COLS = 4                # TDA_FNN_COLS: the columns of their counts
+FNN_COUNT_NAMES = ("valid", "false_distance", "false_size", "false_either")
 TDA_GEN_BIRTH_TIED = 1       # tda_generators_*: flags of an H1 row (include/tdaeeg.h)
 TDA_GEN_DEATH_TIED = 2
 TDA_GEN_CYCLE_TRUNCATED = 4
@@ -139,6 +145,11 @@ SYMBOLS = {
     "tda_hilbert_envelope_ragged_dev": (_I, [c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_tau_batch_dev": (_I, [c_vp, c_vp, _I, _I, _I, c_vp, c_vp]),
     "tda_tau_segments_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_ami_batch_dev": (_I, [c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_ami_batch": (_I, [c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
+    "tda_ami_segments_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp, c_vp]),
+    "tda_fnn_batch_dev": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, _D, _D, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tda_fnn_batch": (_I, [c_vp, c_vp, c_vp, _I, _I, _I, _I, _D, _D, _D, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_recording_rows_dev": (_I, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "tda_set_retry_policy": (_I, [c_vp, _I]),
     "tda_set_retry_counter": (_I, [c_vp, c_vp]),

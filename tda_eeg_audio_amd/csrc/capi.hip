@@ -564,6 +564,34 @@ tda_status tda_tau_segments_dev(tda_ctx* ctx, const double* win, const int* seg_
     return launch_tau_segments(ctx, win, seg_off, n_seg, n_t, max_lag, tau_seg, tau_win, (hipStream_t)stream);
 }
 
+tda_status tda_ami_batch_dev(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int n_bins, double* ami,
+                             int* tau, int* joint, int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, ami); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, status); }
+    return launch_ami(ctx, win, nullptr, n_win, n_t, max_lag, n_bins, ami, tau, joint, status, nullptr, (hipStream_t)stream);
+}
+
+tda_status tda_ami_segments_dev(tda_ctx* ctx, const double* win, const int* seg_off, int n_seg, int n_t, int max_lag,
+                                int n_bins, int* tau_seg, int* tau_win, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_seg);
+    if (n_seg) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, seg_off); CHECK_PTR(ctx, tau_seg); }
+    return launch_ami(ctx, win, seg_off, n_seg, n_t, max_lag, n_bins, nullptr, tau_seg, nullptr, nullptr, tau_win,
+                      (hipStream_t)stream);
+}
+
+tda_status tda_fnn_batch_dev(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int d_max, int theiler,
+                             double r_tol, double a_tol, double frac_tol, int* counts, double* frac, int* dim, int* nn,
+                             int* status, void* stream)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    if (n_win) { CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, frac); CHECK_PTR(ctx, dim);
+                 CHECK_PTR(ctx, status); }
+    return launch_fnn(ctx, win, tau, n_win, n_t, d_max, theiler, r_tol, a_tol, frac_tol, counts, frac, dim, nn, status,
+                      (hipStream_t)stream);
+}
+
 tda_status tda_recording_rows_dev(tda_ctx* ctx, const double* w_h0, const double* w_h1, const int* tau_seg,
                                   const double* feat_h0, const double* feat_h1, const int* seg_off, int n_seg,
                                   double* out, const int* status_a, const int* status_b, int* seg_flags, void* stream)
@@ -1305,6 +1333,47 @@ tda_status tda_tau_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, in
     auto d_win = s.in(win, (size_t)n_win * n_t);
     auto d_tau = s.out(tau, (size_t)n_win);
     return s.run([&] { return tda_tau_batch_dev(ctx, d_win, n_win, n_t, max_lag, d_tau, nullptr); });
+}
+
+tda_status tda_ami_batch(tda_ctx* ctx, const double* win, int n_win, int n_t, int max_lag, int n_bins, double* ami, int* tau,
+                         int* joint, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    int lag = max_lag;                                             // resolved: the rows of ami and joint have lag + 1 entries
+    TDA_TRY(ami_check(ctx, n_t, n_bins, &lag));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, ami); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, status);
+    Stage s(ctx);
+    const size_t nw = (size_t)n_win, nl = (size_t)lag + 1;
+    auto d_win = s.in(win, nw * n_t);
+    auto d_ami = s.out(ami, nw * nl);
+    auto d_tau = s.out(tau, nw);
+    auto d_joint = s.out(joint, nw * nl * n_bins * n_bins);
+    auto d_st = s.out(status, nw);
+    return s.run([&] { return tda_ami_batch_dev(ctx, d_win, n_win, n_t, max_lag, n_bins, d_ami, d_tau, d_joint, d_st, nullptr); });
+}
+
+tda_status tda_fnn_batch(tda_ctx* ctx, const double* win, const int* tau, int n_win, int n_t, int d_max, int theiler,
+                         double r_tol, double a_tol, double frac_tol, int* counts, double* frac, int* dim, int* nn, int* status)
+{
+    CHECK_CTX(ctx); CHECK_NONNEG(ctx, n_win);
+    TDA_TRY(fnn_check(ctx, n_t, d_max, theiler, r_tol, a_tol, frac_tol));
+    if (n_win == 0) return TDA_OK;
+    CHECK_PTR(ctx, win); CHECK_PTR(ctx, tau); CHECK_PTR(ctx, counts); CHECK_PTR(ctx, frac); CHECK_PTR(ctx, dim);
+    CHECK_PTR(ctx, status);
+    Stage s(ctx);
+    const size_t nw = (size_t)n_win;
+    auto d_win = s.in(win, nw * n_t);
+    auto d_tau = s.in(tau, nw);
+    auto d_cnt = s.out(counts, nw * d_max * TDA_FNN_COLS);
+    auto d_frac = s.out(frac, nw * d_max);
+    auto d_dim = s.out(dim, nw);
+    auto d_nn = s.out(nn, nw * d_max * n_t);
+    auto d_st = s.out(status, nw);
+    return s.run([&] {
+        return tda_fnn_batch_dev(ctx, d_win, d_tau, n_win, n_t, d_max, theiler, r_tol, a_tol, frac_tol, d_cnt, d_frac, d_dim, d_nn,
+                                 d_st, nullptr);
+    });
 }
 
 tda_status tda_features_batch(tda_ctx* ctx, const double* dgm, const int* cnt, int n_dgm, int cap, double* feat)

@@ -317,6 +317,15 @@ tda_status launch_hilbert_env_ragged(tda_ctx*, const double*, int, const long lo
                                      const double*, const long long*, double*, hipStream_t);
 tda_status launch_tau(tda_ctx*, const double*, int, int, int, int*, hipStream_t);
 tda_status launch_tau_segments(tda_ctx*, const double*, const int*, int, int, int, int*, int*, hipStream_t);
+// (embedding.hip) delay and dimension selection.  launch_ami: seg_off == NULL: the batch form, n_groups windows; otherwise
+// the segments form (ami, joint, status NULL; tau is tau_seg).  Both check the limits of the header themselves: ami_check
+// (which also resolves max_lag: a negative one is n_t / 4, then the cut to n_t - 2) and fnn_check.
+tda_status ami_check(tda_ctx*, int n_t, int n_bins, int* max_lag);
+tda_status launch_ami(tda_ctx*, const double* win, const int* seg_off, int n_groups, int n_t, int max_lag, int n_bins,
+                      double* ami, int* tau, int* joint, int* status, int* tau_win, hipStream_t);
+tda_status fnn_check(tda_ctx*, int n_t, int d_max, int theiler, double r_tol, double a_tol, double frac_tol);
+tda_status launch_fnn(tda_ctx*, const double* win, const int* tau, int n_win, int n_t, int d_max, int theiler, double r_tol,
+                      double a_tol, double frac_tol, int* counts, double* frac, int* dim, int* nn, int* status, hipStream_t);
 tda_status launch_recording_rows(tda_ctx*, const double*, const double*, const int*, const double*, const double*, const int*,
                                  int, double*, const int*, const int*, int*, hipStream_t);
 tda_status launch_features(tda_ctx*, const double*, const int*, int, int, double*, hipStream_t);

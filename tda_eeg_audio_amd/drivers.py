@@ -361,6 +361,91 @@ def recurrence_names(bands=BANDS, grid=None):
             for j in range(n_grid)]
 
 
+def embedding_parameters_from_windows(win_list, max_lag=None, n_bins=16, max_dim=5, theiler=None, r_tol=10.0, a_tol=2.0,
+                                      frac_tol=0.05):
+    """win_list: list of (k_i, n_t) arrays of signal windows, one per (recording, band) group.  Per group the two
+    parameters of its delay embedding, chosen from the signal (include/tdaeeg.h, "Delay and dimension selection"), and the
+    curves behind them: (len(win_list), 2 + n_lag + max_dim) float64 with n_lag = the resolved max_lag + 1, the columns
+    named by embedding_names --
+      tau_ami          the first minimum of the average mutual information of the group's FIRST window, as the reference
+                       takes its one tau per recording and band, compute_tau's fallback without a minimum
+                       (engine.ami_segments_dev); this delay feeds the false nearest neighbours of every window of the group
+      dim_fnn          the smallest dimension d with V > 0 and (double)E <= frac_tol * (double)V, V and E the group's sums
+                       of valid and false_either at d; 0 without one
+      ami_L0 ...       the mean over the group's windows of their mutual information curves (engine.ami_dev)
+      fnn_frac_d1 ...  the mean over the group's windows of their fractions of false neighbours (engine.fnn_dev)
+    The means add the kept windows in window order and divide by their number; a window with a status word (a sample that
+    is not finite, a constant window, too short for the delay) is left out, a group without a kept window is NaN.  theiler:
+    None means every group's own delay.  All on the device: delays, curves, neighbours, sums.  ValueError for a bad
+    argument."""
+    import torch
+    sizes = np.array([len(w) for w in win_list], dtype=np.int64)
+    shapes = {np.shape(w)[1:] for w in win_list if len(w)}
+    if len(shapes) > 1 or any(len(s) != 1 for s in shapes):
+        raise ValueError("win_list: (k_i, n_t) arrays of one n_t")
+    if theiler is not None and (isinstance(theiler, bool) or not isinstance(theiler, (int, np.integer))):
+        raise ValueError(f"theiler must be an integer or None, not {theiler!r}")
+    if not shapes:
+        lag, _ = engine.ami_args(4, max_lag, n_bins)
+        engine.fnn_args(4, max_dim, 1, r_tol, a_tol, frac_tol)
+        if max_lag is None or max_lag < 0:
+            raise ValueError("max_lag: without a window there is no length to take a quarter of")
+        out = np.full((len(win_list), 2 + int(max_lag) + 1 + max_dim), np.nan)
+        out[:, :2] = 0.0
+        return out
+    n_t = shapes.pop()[0]
+    lag, n_bins = engine.ami_args(n_t, max_lag, n_bins)
+    d_max = engine.fnn_args(n_t, max_dim, 1 if theiler is None else theiler, r_tol, a_tol, frac_tol)[0]
+    ctx = engine.get_ctx()
+    dev = torch.device("cuda", ctx.device)
+    n, n_seg, k_max = int(sizes.sum()), len(win_list), int(sizes.max())
+    seg = np.concatenate([[0], np.cumsum(sizes)])
+    seg_t = torch.from_numpy(seg.astype(np.int32)).to(dev)
+    W = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(w, dtype=np.float64) for w in win_list if len(w)]))).to(dev)
+    tau_seg = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    tau_win = torch.empty(n, dtype=torch.int32, device=dev)
+    engine.ami_segments_dev(W, seg_t, lag, n_bins, tau_seg, tau_win, ctx=ctx)
+    emb = engine.ami_dev(W, lag, n_bins, ctx=ctx)
+    if theiler is not None:
+        fnn = engine.fnn_dev(W, tau_win, d_max, theiler, r_tol, a_tol, frac_tol, ctx=ctx)
+    else:
+        # one launch per delay that occurs: the Theiler window is a parameter of the launch
+        fnn = engine.DeviceEmbedding(n, 0, d_max, dev)
+        for v in torch.unique(tau_win).tolist():
+            idx = (tau_win == v).nonzero().flatten()
+            part = engine.fnn_dev(W[idx].contiguous(), tau_win[idx].contiguous(), d_max, min(max(int(v), 1), n_t), r_tol, a_tol,
+                                  frac_tol, ctx=ctx)
+            for name in ("counts", "frac", "dim", "fnn_status"):
+                getattr(fnn, name).index_copy_(0, idx, getattr(part, name))
+
+    # window k of every group side by side, so that the sums run in window order
+    pos = seg_t[:-1, None].long() + torch.arange(k_max, device=dev)[None, :]
+    there = pos < seg_t[1:, None].long()
+    pos = pos.clamp(max=n - 1)
+
+    def group_mean(val, status):
+        keep = there & (status[pos] == 0)
+        S = torch.zeros((n_seg, val.shape[1]), dtype=torch.float64, device=dev)
+        for k in range(k_max):
+            S = S + torch.where(keep[:, k, None], val[pos[:, k]], torch.zeros((), dtype=torch.float64, device=dev))
+        return S / keep.sum(1, dtype=torch.float64)[:, None]
+
+    keep = (there & (fnn.fnn_status[pos] == 0))[:, :, None, None]
+    tot = (fnn.counts[pos].long() * keep).sum(1)                                        # (n_seg, d_max, 4), exact
+    V, E = tot[:, :, 0], tot[:, :, 3]
+    ok = (V > 0) & (E.double() <= float(frac_tol) * V.double())
+    dim = torch.where(ok.any(1), ok.int().argmax(1) + 1, torch.zeros((), dtype=torch.int64, device=dev))
+    out = torch.cat([tau_seg.double()[:, None], dim.double()[:, None], group_mean(emb.ami, emb.ami_status),
+                     group_mean(fnn.frac, fnn.fnn_status)], dim=1)
+    return out.cpu().numpy()
+
+
+def embedding_names(n_lag, max_dim=5, bands=BANDS):
+    """Column names of embedding_parameters_from_windows(...)[r] of every band, flattened band by band."""
+    return [f"{band}_{name}" for band in bands for name in
+            ["tau_ami", "dim_fnn"] + [f"ami_L{k}" for k in range(n_lag)] + [f"fnn_frac_d{d}" for d in range(1, max_dim + 1)]]
+
+
 def channel_participation_from_distances(dist_list, thresh=MAX_EDGE_LENGTH):
     """dist_list as features_from_distances takes it.  The same Rips launch with the same status checks, then one launch
     that finds the birth edge and a representative cycle of every H1 row and one that writes the group means

@@ -22,6 +22,8 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  windows in time order on a grid of scales, by the same keys and presence rule; recurrence_args)
                  generators_dm_batch, generators_cloud_batch, generators_takens_batch (the edges behind the rows of the
                  diagrams, a representative cycle per H1 row and the participation of every vertex; generators_args)
+                 ami_batch, fnn_batch (the delay at the first minimum of the average mutual information and the dimension
+                 at which the false nearest neighbours vanish; ami_args, fnn_args)
   device tensors (torch, already resident in HBM, launched on torch's current stream):
                  the ``*_dev`` twins -- used by bench.py and the multi-GPU driver.
                  wasserstein_cross_dev / cross_rows_dev: the control experiment's pairs, resolved on the device
@@ -49,6 +51,9 @@ include/tdaeeg.h; all arithmetic happens in the HIP kernels.  There is no CPU pa
                  recurrence_dm_dev / recurrence_cloud_dev / recurrence_takens_dev / recurrence_mean_dev: the recurrence
                  curves of resident windows and their group means, into a DeviceRecurrenceCurves
                  (utils.compute_signal_recurrence_curves, drivers.recurrence_curves_from_windows).
+                 ami_dev / ami_segments_dev / fnn_dev: delay and dimension selection of resident windows, into a
+                 DeviceEmbedding; ami_segments_dev writes the per-window delays the Takens forms take
+                 (utils.compute_tau_ami, drivers.embedding_parameters_from_windows).
                  generators_dm_dev / generators_cloud_dev / generators_takens_dev / generators_mean_dev /
                  generators_eeg_windows_dev: generators and cycles of resident windows from a DeviceDiagrams or raw row
                  tensors, into a DeviceGenerators (utils.compute_eeg_generators,
@@ -388,6 +393,86 @@ def tau_batch(windows, max_lag=None, ctx=None):
     tau = np.empty(n_win, np.int32)
     ctx.check(ctx.lib.tda_tau_batch(ctx.h, ptr(w), n_win, n_t, -1 if max_lag is None else int(max_lag), ptr(tau)))
     return tau
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {v!r}")
+    return int(v)
+
+
+def ami_args(n_t, max_lag=None, n_bins=16):
+    """The parameters of the average mutual information as the kernel takes them (include/tdaeeg.h, "Delay and dimension
+    selection"): (max_lag, n_bins) with max_lag resolved -- None or a negative value is n_t // 4, then the cut to n_t - 2 --
+    so that a row of ami has max_lag + 1 entries.  ValueError, before any GPU call, for n_t outside 4..AMI_MAX_SAMPLES,
+    n_bins outside 2..AMI_MAX_BINS or a max_lag that is no integer."""
+    n_t = _int_in("n_t", n_t, 4, _lib.AMI_MAX_SAMPLES)
+    n_bins = _int_in("n_bins", n_bins, 2, _lib.AMI_MAX_BINS)
+    if max_lag is None:
+        max_lag = -1
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)):
+        raise ValueError(f"max_lag must be an integer or None, not {max_lag!r}")
+    max_lag = n_t // 4 if max_lag < 0 else int(max_lag)
+    return min(max_lag, n_t - 2), n_bins
+
+
+def fnn_args(n_t, d_max=5, theiler=1, r_tol=10.0, a_tol=2.0, frac_tol=0.05):
+    """The parameters of the false nearest neighbours as the kernel takes them: (d_max, theiler, r_tol, a_tol, frac_tol).
+    ValueError, before any GPU call, for n_t outside 4..FNN_MAX_SAMPLES, d_max outside 1..FNN_MAX_DIM, theiler outside
+    1..n_t, r_tol or a_tol not > 0, frac_tol outside [0, 1]."""
+    n_t = _int_in("n_t", n_t, 4, _lib.FNN_MAX_SAMPLES)
+    d_max = _int_in("d_max", d_max, 1, _lib.FNN_MAX_DIM)
+    theiler = _int_in("theiler", theiler, 1, n_t)
+    tol = []
+    for name, v in (("r_tol", r_tol), ("a_tol", a_tol), ("frac_tol", frac_tol)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number, not {v!r}")
+        tol.append(float(v))
+    if not tol[0] > 0.0 or not tol[1] > 0.0:
+        raise ValueError("r_tol and a_tol must be > 0")
+    if not 0.0 <= tol[2] <= 1.0:
+        raise ValueError("frac_tol must be in [0, 1]")
+    return (d_max, theiler) + tuple(tol)
+
+
+def ami_batch(windows, max_lag=None, n_bins=16, joint=False, ctx=None):
+    """Average mutual information of every window with its own past and its first minimum (include/tdaeeg.h, "Delay and
+    dimension selection"): windows (n_win, n_t) float64 -> (ami (n_win, max_lag + 1) float64 in nats, tau (n_win,) int32,
+    joint (n_win, max_lag + 1, n_bins, n_bins) int32 or None, status) with max_lag as ami_args resolves it.  tau is 0
+    without a minimum.  A window with a sample that is not finite has TDA_WIN_NOT_FINITE and NaN, a constant one
+    TDA_WIN_DEGENERATE and 0.0."""
+    w = f64(windows)
+    if w.ndim != 2:
+        raise ValueError("windows: (n_win, n_t)")
+    n_win, n_t = w.shape
+    lag, n_bins = ami_args(n_t, max_lag, n_bins)
+    ctx = ctx or get_ctx()
+    ami = np.zeros((n_win, lag + 1))
+    tau, st = np.zeros(n_win, np.int32), np.zeros(n_win, np.int32)
+    jnt = np.zeros((n_win, lag + 1, n_bins, n_bins), np.int32) if joint else None
+    ctx.check(ctx.lib.tda_ami_batch(ctx.h, ptr(w), n_win, n_t, lag, n_bins, ptr(ami), ptr(tau), ptr(jnt), ptr(st)))
+    return ami, tau, jnt, st
+
+
+def fnn_batch(windows, taus, d_max=5, theiler=1, r_tol=10.0, a_tol=2.0, frac_tol=0.05, nn=False, ctx=None):
+    """False nearest neighbours of the delay embeddings of dimension 1..d_max of every window (include/tdaeeg.h, "Delay and
+    dimension selection"): windows (n_win, n_t) float64, taus one delay or one per window -> (counts (n_win, d_max, 4) int32
+    with the columns _lib.FNN_COUNT_NAMES, frac (n_win, d_max) float64, dim (n_win,) int32, nn (n_win, d_max, n_t) int32 or
+    None, status).  dim is 0 where no dimension has a fraction of at most frac_tol.  A window with tau < 1 has
+    TDA_WIN_TOO_LARGE, one with n_t - tau < 2 TDA_WIN_DEGENERATE, and zeros."""
+    w = f64(windows)
+    if w.ndim != 2:
+        raise ValueError("windows: (n_win, n_t)")
+    n_win, n_t = w.shape
+    par = fnn_args(n_t, d_max, theiler, r_tol, a_tol, frac_tol)
+    ctx = ctx or get_ctx()
+    tau = i32(np.broadcast_to(np.asarray(taus), (n_win,)))
+    cnt = np.zeros((n_win, par[0], _lib.FNN_COLS), np.int32)
+    frac = np.zeros((n_win, par[0]))
+    dim, st = np.zeros(n_win, np.int32), np.zeros(n_win, np.int32)
+    nbr = np.zeros((n_win, par[0], n_t), np.int32) if nn else None
+    ctx.check(ctx.lib.tda_fnn_batch(ctx.h, ptr(w), ptr(tau), n_win, n_t, *par, ptr(cnt), ptr(frac), ptr(dim), ptr(nbr), ptr(st)))
+    return cnt, frac, dim, nbr, st
 
 
 def pack_diagrams(dgms, cap=None):
@@ -1550,6 +1635,88 @@ def tau_segments_dev(win_t, seg_off_t, max_lag=None, tau_seg_t=None, tau_win_t=N
                                            -1 if max_lag is None else int(max_lag), _tp(tau_seg_t), _tp(tau_win_t),
                                            _stream()))
     return tau_seg_t
+
+
+class DeviceEmbedding:
+    """The outputs of ami_dev and fnn_dev for a batch of windows, resident in HBM (include/tdaeeg.h, "Delay and dimension
+    selection"): ami (n_win, n_lag) float64, tau (n_win,) int32, ami_status, and, when asked for, joint (n_win, n_lag,
+    n_bins, n_bins) int32; counts (n_win, d_max, 4) int32, frac (n_win, d_max) float64, dim (n_win,) int32, fnn_status and,
+    when asked for, nn (n_win, d_max, n_t) int32.  n_lag = 0 or d_max = 0 leaves that half out."""
+
+    def __init__(self, n_win, n_lag, d_max, device, n_bins=0, n_t=0):
+        import torch
+        kw = dict(device=device)
+        i32t, f64t = torch.int32, torch.float64
+        self.ami = torch.empty((n_win, n_lag), dtype=f64t, **kw) if n_lag else None
+        self.tau = torch.empty(n_win, dtype=i32t, **kw) if n_lag else None
+        self.ami_status = torch.empty(n_win, dtype=i32t, **kw) if n_lag else None
+        self.joint = torch.empty((n_win, n_lag, n_bins, n_bins), dtype=i32t, **kw) if n_lag and n_bins else None
+        self.counts = torch.empty((n_win, d_max, _lib.FNN_COLS), dtype=i32t, **kw) if d_max else None
+        self.frac = torch.empty((n_win, d_max), dtype=f64t, **kw) if d_max else None
+        self.dim = torch.empty(n_win, dtype=i32t, **kw) if d_max else None
+        self.fnn_status = torch.empty(n_win, dtype=i32t, **kw) if d_max else None
+        self.nn = torch.empty((n_win, d_max, n_t), dtype=i32t, **kw) if d_max and n_t else None
+        self.n_win, self.n_lag, self.d_max = n_win, n_lag, d_max
+
+    def to_host(self):
+        return {k: getattr(self, k).cpu().numpy() for k in ("ami", "tau", "ami_status", "joint", "counts", "frac", "dim",
+                                                            "fnn_status", "nn") if getattr(self, k) is not None}
+
+
+def ami_dev(win_t, max_lag=None, n_bins=16, joint=False, out=None, ctx=None):
+    """ami_batch on device tensors: win_t (n_win, n_t) float64 -> a DeviceEmbedding (out, when given, needs n_lag = the
+    resolved max_lag + 1 and, for joint=True, its joint block); nothing else is allocated."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous() and win_t.dim() == 2
+    n_win, n_t = (int(v) for v in win_t.shape)
+    lag, n_bins = ami_args(n_t, max_lag, n_bins)
+    if out is None:
+        out = DeviceEmbedding(n_win, lag + 1, 0, win_t.device, n_bins if joint else 0)
+    assert out.n_win >= n_win and out.n_lag == lag + 1 and out.ami.is_contiguous()
+    assert not joint or (out.joint is not None and tuple(out.joint.shape[1:]) == (lag + 1, n_bins, n_bins))
+    ctx.check(ctx.lib.tda_ami_batch_dev(ctx.h, _tp(win_t), n_win, n_t, lag, n_bins, _tp(out.ami), _tp(out.tau),
+                                        _tp(out.joint if joint else None), _tp(out.ami_status), _stream()))
+    return out
+
+
+def ami_segments_dev(win_t, seg_off_t, max_lag=None, n_bins=16, tau_seg_t=None, tau_win_t=None, ctx=None):
+    """tau_segments_dev with the first minimum of the average mutual information in place of the zero crossing of the
+    autocorrelation: the delay of every (recording, band) group from its first window, compute_tau's fallback
+    max(max_lag // 10, 1) where there is no minimum; tau_win_t (optional, (n_win,) int32) receives the group's value for
+    every window, ready for the Takens entry points."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous() and win_t.dim() == 2
+    assert seg_off_t.dtype == torch.int32 and seg_off_t.is_contiguous()
+    n_win, n_t = (int(v) for v in win_t.shape)
+    lag, n_bins = ami_args(n_t, max_lag, n_bins)
+    n_seg = seg_off_t.numel() - 1
+    if tau_seg_t is None:
+        tau_seg_t = torch.empty(n_seg, dtype=torch.int32, device=win_t.device)
+    assert tau_seg_t.dtype == torch.int32 and tau_seg_t.numel() >= n_seg
+    assert tau_win_t is None or (tau_win_t.dtype == torch.int32 and tau_win_t.numel() >= n_win)
+    ctx.check(ctx.lib.tda_ami_segments_dev(ctx.h, _tp(win_t), _tp(seg_off_t), n_seg, n_t, lag, n_bins, _tp(tau_seg_t),
+                                           _tp(tau_win_t), _stream()))
+    return tau_seg_t
+
+
+def fnn_dev(win_t, tau_t, d_max=5, theiler=1, r_tol=10.0, a_tol=2.0, frac_tol=0.05, nn=False, out=None, ctx=None):
+    """fnn_batch on device tensors: win_t (n_win, n_t) float64, tau_t (n_win,) int32 -> a DeviceEmbedding (out, when given,
+    needs d_max and, for nn=True, its nn block); nothing else is allocated."""
+    import torch
+    ctx = ctx or get_ctx()
+    assert win_t.is_cuda and win_t.dtype == torch.float64 and win_t.is_contiguous() and win_t.dim() == 2
+    n_win, n_t = (int(v) for v in win_t.shape)
+    assert tau_t.is_cuda and tau_t.dtype == torch.int32 and tau_t.is_contiguous() and tau_t.numel() >= n_win
+    par = fnn_args(n_t, d_max, theiler, r_tol, a_tol, frac_tol)
+    if out is None:
+        out = DeviceEmbedding(n_win, 0, par[0], win_t.device, 0, n_t if nn else 0)
+    assert out.n_win >= n_win and out.d_max == par[0] and out.counts.is_contiguous()
+    assert not nn or (out.nn is not None and tuple(out.nn.shape[1:]) == (par[0], n_t))
+    ctx.check(ctx.lib.tda_fnn_batch_dev(ctx.h, _tp(win_t), _tp(tau_t), n_win, n_t, *par, _tp(out.counts), _tp(out.frac),
+                                        _tp(out.dim), _tp(out.nn if nn else None), _tp(out.fnn_status), _stream()))
+    return out
 
 
 def recording_rows_dev(w0_t, w1_t, tau_seg_t, fe0_t, fe1_t, seg_off_t, out_t=None, status_a=None, status_b=None,

@@ -59,6 +59,64 @@ def compute_tau(s, max_lag=None):
     return int(engine.tau_batch(s, max_lag)[0])
 
 
+def _signal(s, name):
+    s = np.asarray(s, dtype=np.float64)
+    if s.ndim != 1 or s.shape[0] < 1:
+        raise ValueError(f"{name}: a 1-D signal")
+    return s.reshape(1, -1)
+
+
+def compute_ami(s, max_lag=None, n_bins=16):
+    """Average mutual information, in nats, of a 1-D signal with itself L samples later, L = 0..max_lag, on a histogram of
+    n_bins equal bins between the signal's minimum and maximum (include/tdaeeg.h, "Delay and dimension selection"; Fraser
+    & Swinney 1986): a (max_lag + 1,) float64 array.  max_lag None is len(s) // 4, as compute_tau; it is cut to len(s) - 2.
+    A constant signal gives zeros; ValueError for a bad argument or a sample that is not finite."""
+    ami, _, _, st = engine.ami_batch(_signal(s, "compute_ami"), max_lag, n_bins)
+    if st[0] & 64:
+        raise ValueError("compute_ami: the signal has a sample that is not finite")
+    return ami[0]
+
+
+def compute_tau_ami(s, max_lag=None, n_bins=16):
+    """The twin of compute_tau with the nonlinear statistic: the first local minimum of compute_ami(s, max_lag, n_bins),
+    the smallest L >= 1 with I(L) < I(L - 1) and I(L) <= I(L + 1).  Without one (a monotone curve, a constant signal)
+    compute_tau's fallback max(max_lag // 10, 1)."""
+    w = _signal(s, "compute_tau_ami")
+    _, tau, _, st = engine.ami_batch(w, max_lag, n_bins)
+    if st[0] & 64:
+        raise ValueError("compute_tau_ami: the signal has a sample that is not finite")
+    return int(tau[0]) if tau[0] else max(engine.ami_args(w.shape[1], max_lag, n_bins)[0] // 10, 1)
+
+
+def false_nearest_neighbours(s, tau, max_dim=5, theiler=None, r_tol=10.0, a_tol=2.0, frac_tol=0.05):
+    """False nearest neighbours of the delay embeddings of s with delay tau in the dimensions 1..max_dim (include/tdaeeg.h,
+    "Delay and dimension selection"; Kennel, Brown & Abarbanel 1992): a dict of rows, each (max_dim,) -- the int32 counts
+    valid (points with a neighbour), false_distance (the next coordinate moves the neighbour away by more than r_tol times
+    their distance), false_size (the pair ends further apart than a_tol standard deviations of s), false_either, and the
+    float64 fraction = false_either / valid -- with "dim", the smallest dimension whose fraction is at most frac_tol (0
+    without one).  theiler: neighbours closer than theiler samples in time do not count; None means tau.  tau < 1 is a
+    TdaError, as in the Takens calls; ValueError for a bad argument or a sample that is not finite."""
+    from . import _lib
+    w = _signal(s, "false_nearest_neighbours")
+    if isinstance(tau, bool) or not isinstance(tau, (int, np.integer)):
+        raise ValueError(f"tau must be an integer, not {tau!r}")
+    theiler = max(int(tau), 1) if theiler is None else theiler
+    cnt, frac, dim, _, st = engine.fnn_batch(w, int(tau), max_dim, theiler, r_tol, a_tol, frac_tol)
+    if st[0] & 64:
+        raise ValueError("false_nearest_neighbours: the signal has a sample that is not finite")
+    if st[0] & 16:
+        raise TdaError("tau must be >= 1")
+    out = {name: cnt[0, :, k] for k, name in enumerate(_lib.FNN_COUNT_NAMES)}
+    out.update(fraction=frac[0], dim=int(dim[0]))
+    return out
+
+
+def estimate_embedding_dimension(s, tau, max_dim=5, theiler=None, r_tol=10.0, a_tol=2.0, frac_tol=0.05):
+    """The "dim" of false_nearest_neighbours: the smallest dimension in 1..max_dim at which at most frac_tol of the points
+    have a false nearest neighbour; 0 when none has (raise max_dim, or the signal is noise)."""
+    return false_nearest_neighbours(s, tau, max_dim, theiler, r_tol, a_tol, frac_tol)["dim"]
+
+
 def takens_embedding(s, dim, tau, subsample=1):
     """scripts/utils.py:107-116 -- the (P, dim) delay cloud.  A pure gather; the batched path
     (engine.takens_rips_batch) performs it inside the Rips kernel and never materialises it."""
